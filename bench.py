@@ -12,12 +12,20 @@ every rank runs the full single-GPU pipeline on its own 2^20-term shard ("weak" 
 the per-rank partial results (one 96-byte affine point each) are exchanged with ONE tiny
 all-gather per step and folded locally - RCCL has no user-defined reduction for EC addition.
 
+A plain run sets up, warms up, times the K steps and prints the JSON line; nothing else runs.
+--dump-outputs DIR writes what the last timed step returned (the multiexp's affine result) as
+DIR/msm_result.npy in float64, so that two builds can be compared output for output on the same
+seeded inputs.  --full adds everything else after the timed steps: the same steps with two jobs
+in flight, with host scalars, on the classic plan; the CPU baseline (and the check of the last
+result against it); the other BASELINE configs (boolean-heavy scalars, other multiexp shapes,
+FFT, create_proof at several sizes, the N-rank model); at N > 1 the sharded checks and legs.
+
 Extra objects on the JSON line:
   roofline     dominant kernel = msm_accumulate_kernel (bucket accumulation).  achieved =
                algorithmic bytes per launch (128 B per term: 96 B affine base + 32 B scalar,
                SURVEY.md 8d) / mean launch duration measured with HIP events on the job's
                stream inside the library (bh_msm_wait_profile).  peak = 8000 GB/s HBM3E.
-  cpu_baseline the C restatement of bellman's rayon path (oracle/c, one task per window,
+  cpu_baseline (--full) the C restatement of bellman's rayon path (oracle/c, one task per window,
                src/multiexp.rs:288-293) timed on this box's host cores on the same inputs.
 """
 
@@ -64,6 +72,15 @@ def splitmix_scalars(n, seed):
     a = z.reshape(n, 4)
     a[:, 3] %= np.uint64(0x73EDA753299D7D48)
     return np.ascontiguousarray(a)
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: the affine G1 record the last timed step returned (uint64[12]: x | y, Montgomery limbs, all-zero =
+    identity) as DIR/msm_result.npy, float64 [2, 12]: the 32-bit words of x and of y, least significant first (exact: every
+    word is below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(result, dtype="<u8").view("<u4").reshape(2, 12)
+    np.save(os.path.join(out_dir, "msm_result.npy"), words.astype(np.float64))
 
 
 G1_GEN_MONT = np.array(  # BLS12-381 G1 generator, Montgomery limbs (x | y)
@@ -792,8 +809,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-proof", action="store_true", help="skip the create_proof (config C4) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (extras, CPU baseline, other "
+                         "configs; the sharded legs at N > 1); a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result of the last timed step to DIR/msm_result.npy (float64); bench_outputs/ in the "
+                         "repository is ignored by git")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-proof", action="store_true", help="--full: skip the create_proof (config C4) measurement")
     ap.add_argument("--proof-log-n", type=int, default=20)
     ap.add_argument("--c5-proof-log-n", type=int, default=24, help="N = 1: size of the C5 proof leg (0 = skip)")
     ap.add_argument("--c5-log-n", type=int, default=26,
@@ -801,9 +824,12 @@ def main():
     ap.add_argument("--check-log-n", type=int, default=12,
                     help="N > 1 only: per-rank size of the fold == concatenated-multiexp check")
     ap.add_argument("--timed-steps-only", action="store_true",
-                    help="run only warm-up + the K timed steps (no overlapped / PCIe extras): the command profiled for "
+                    help="matters only with --full: leave out the extras that repeat the timed workload (two jobs in flight, "
+                         "host scalars, classic plan); a plain run never runs them and is the command profiled for "
                          "profiles/*kernel_stats.csv, so that rocprof's per-kernel average matches the live HIP-event figure")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -915,6 +941,8 @@ def main():
     stage /= max(args.steps, 1)
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     value = world * n * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:   # (after a collective fold every rank holds the same result)
+        dump_outputs(args.dump_outputs, result)
 
     # extra information (not `value`): the same K steps issued with two jobs in flight, the way
     # create_proof drives multiexp (prover.rs:244-318 issues all eight before the first wait): the
@@ -924,7 +952,7 @@ def main():
                                     scalars_dev=ctypes.c_void_p(s_dev.data_ptr()), n=n, timed=True, flags=ab_flags)
 
     pipelined_value = pcie_value = None
-    extras = not args.timed_steps_only
+    extras = args.full and not args.timed_steps_only
     barrier()
     tp0 = time.perf_counter()
     if extras:
@@ -961,15 +989,15 @@ def main():
         classic_value = n / classic_ms / 1e3
 
     sharded_check = None
-    if distributed:
+    if distributed and args.full:
         sharded_check = check_sharded_fold(worker, lib, world, rank, coll_dev, args.check_log_n)
     sharded_proof = None
-    if distributed and not args.no_proof:
+    if distributed and args.full and not args.no_proof:
         sharded_proof = bench_create_proof_sharded(worker, args.proof_log_n, world, rank, coll_dev)
     # BASELINE.json configs[4]: ONE 2^26-term G1 MSM sharded by bases over all ranks (strong scaling of a
     # fixed problem; extra information, not `value`)
     c5 = None
-    if distributed and args.c5_log_n:
+    if distributed and args.full and args.c5_log_n:
         n5 = (1 << args.c5_log_n) // world
         t5 = torch.from_numpy(splitmix_scalars(n5, 0xC5 + rank * 8 * n5).view(np.int64)).cuda()
         b5 = torch.empty((n5, 12), dtype=torch.int64, device="cuda")
@@ -1017,7 +1045,7 @@ def main():
     # one PROCESS driving every GPU of the node (bh_msm_sharded_async: one context per device, the reference's single
     # process with all cores of one box, src/multicore.rs:21-92): rank 0 runs it while the other ranks wait at the barrier
     one_process = None
-    if distributed and args.c5_log_n:
+    if distributed and args.full and args.c5_log_n:
         barrier()
         if rank == 0:
             one_process = bench_one_process_sharded(lib, min(world, torch.cuda.device_count()) if backend == "nccl" else world,
@@ -1102,7 +1130,7 @@ def main():
                                            "against a peak measured at a higher clock (conservative)"},
             },
         }
-        if not args.no_cpu_baseline and not distributed:   # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and not distributed:   # rank 0 at N=1 only
             # CPU baseline: the oracle restatement of bellman's multicore path, timed here as the
             # reported baseline (never the thing shipped).  Sample = the same 2^log_n-term MSM, once.
             from oracle import cref
@@ -1133,7 +1161,7 @@ def main():
             out["msm_c5_sharded"] = c5
         if one_process is not None:
             out["msm_one_process_sharded"] = one_process
-        if not args.no_proof and not distributed:
+        if args.full and not args.no_proof and not distributed:
             out["msm_boolean_heavy"] = bench_msm_boolean(worker, lib, bases, t_host, n, ms_per_step, check=not args.no_cpu_baseline)
             out["msm_other_shapes"] = [bench_msm_shape(worker, lib, 2, 19), bench_msm_shape(worker, lib, 2, 20),
                                        bench_msm_shape(worker, lib, 1, 16), bench_msm_shape(worker, lib, 1, 18)]

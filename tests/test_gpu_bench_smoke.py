@@ -24,8 +24,42 @@ def _last_json_line(text):
     return json.loads(lines[-1])
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_result(tmp_path):
+    """A plain run: the contract's keys, nothing of --full, and --dump-outputs holds the last step's result exactly:
+    sum_i s_i [t_i]G = [sum_i s_i t_i]G for the seeded inputs bench.py makes (t_i, s_i: its SplitMix vectors)."""
+    import ctypes
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from bellman_amd import _lib
+    from oracle import cref
+
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "12",
+                        "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = _last_json_line(r.stdout)
+    for k in CONTRACT_KEYS:
+        assert k in out, k
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    for k in ("cpu_baseline", "msm_boolean_heavy", "fft", "create_proof", "scaling_model"):
+        assert k not in out, k
+    assert out["config"]["value_with_2_jobs_in_flight"] is None and out["config"]["value_classic_plan_no_table_per_gpu"] is None
+    got = np.load(dump / "msm_result.npy")
+    assert got.dtype == np.float64 and got.shape == (2, 12)
+    n = 1 << 12
+    k = np.array(cref.int_to_limbs(cref.fr_dot(bench.splitmix_scalars(n, 0x5CA1A25), bench.splitmix_scalars(n, 0x62656C6C6D616E)), 4),
+                 dtype=np.uint64)
+    want = np.zeros(12, dtype=np.uint64)
+    _lib.load().bh_point_mul(1, want.ctypes.data_as(ctypes.c_void_p), bench.G1_GEN_MONT.ctypes.data_as(ctypes.c_void_p),
+                             k.ctypes.data_as(ctypes.c_void_p))
+    assert np.array_equal(got, want.view(np.uint32).reshape(2, 12).astype(np.float64))
+
+
 def test_bench_single_gpu_contract_small():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--log-n", "12", "--no-proof"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--log-n", "12", "--no-proof", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = _last_json_line(r.stdout)
@@ -65,7 +99,7 @@ def test_bench_ranks_on_one_gpu_gloo(ranks):
     env = dict(os.environ, BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(29517 + ranks), "bench.py", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--log-n", "12",
-           "--proof-log-n", "10", "--c5-log-n", "13", "--check-log-n", "10"]
+           "--proof-log-n", "10", "--c5-log-n", "13", "--check-log-n", "10", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = _last_json_line(r.stdout)

@@ -343,7 +343,13 @@ def test_ctx_info_and_table_budget(worker):
 
     info = worker.info()
     assert info["num_cus"] == 256 and info["hbm_bytes"] > 200 << 30
-    assert info["hw_queues_requested"] == 16 and info["hw_queues_set_before_hip_init"] == 1   # the loader asked in time
+    # the loader asks for 16 hardware queues unless the caller's environment already holds a count, which it keeps
+    assert info["hw_queues_requested"] == int(os.environ["GPU_MAX_HW_QUEUES"]) and info["hw_queues_set_before_hip_init"] == 1
+    code = "import bellman_amd; w = bellman_amd.Worker(0); i = w.info(); print(i['hw_queues_requested'], i['hw_queues_set_before_hip_init']); w.close()"
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(env, PYTHONPATH=ROOT), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and r.stdout.split() == ["16", "1"], r.stdout[-2000:] + r.stderr[-2000:]   # the loader asked in time
     assert info["max_jobs_in_flight"] >= 8 and info["table_budget"] > 0
     w = bellman_amd.Worker(0)
     try:

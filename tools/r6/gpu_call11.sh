@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6c11
 mkdir -p $OUT
 t0=$(date +%s)
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -c 300 $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json, os
 d = json.loads([l for l in open(os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out/r6c11/bench.json")) if l.startswith("{")][-1])

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-6 final GPU run: smoke, the whole -m gpu suite, bench.py (default flags), and the rocprofv3 evidence DESIGN.md /
+# Round-6 final GPU run: smoke, the whole -m gpu suite, bench.py --full, and the rocprofv3 evidence DESIGN.md /
 # bench.py cite: kernel stats of the timed-steps-only bench command, PMC passes of the dominant kernel (FETCH_SIZE,
 # WRITE_SIZE, VALU counters - separate passes, no trace domains beside --kernel-trace; every pass under `timeout`), the FFT
 # passes; per-size tables (uniform and boolean-heavy); one 2^20 proof's kernel timeline (chain and boolean circuit).
@@ -15,9 +15,9 @@ if [ "$1" != "nosuite" ]; then
 timeout 1100 python -m pytest tests -m gpu -x -q --durations=15 > $OUT/gputests.txt 2>&1; tail -22 $OUT/gputests.txt
 fi
 stamp suite
-timeout 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json
+timeout 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json
 stamp bench
-BENCH="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-proof --timed-steps-only"
+BENCH="python bench.py --steps 10 --warmup 2"   # a plain run: warm-up + the timed steps only
 P="timeout 90 rocprofv3"
 $P --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o p -- $BENCH > $OUT/prof_bench.log 2>&1
 $P --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o p -- $BENCH > $OUT/pmc_fetch.log 2>&1

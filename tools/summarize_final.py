@@ -54,8 +54,8 @@ def main():
         "FETCH_SIZE": {"per_launch_kb_mean": f["FETCH_SIZE"][0], "launches": f["FETCH_SIZE"][1]},
         "WRITE_SIZE": {"per_launch_kb_mean": w["WRITE_SIZE"][0], "launches": w["WRITE_SIZE"][1]},
         "algorithmic_bytes_per_launch": 128 << 20,
-        "note": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace, separate passes, of `python bench.py --steps 10 --warmup 2 "
-                "--no-cpu-baseline --no-proof --timed-steps-only`; units KB as reported.  MI355X_MICROARCH.md: on gfx950 FETCH_SIZE reports half "
+        "note": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace, separate passes, of `python bench.py --steps 10 --warmup 2` "
+                "(a plain run: warm-up + the timed steps only); units KB as reported.  MI355X_MICROARCH.md: on gfx950 FETCH_SIZE reports half "
                 "the bytes of a WIDE COALESCED read and is uncalibrated for other access widths; this kernel's reads are per-lane gathers "
                 "of 96-byte records in 16-byte pieces (6 requests per 128-byte line pair), so the raw value is kept as a LOWER bound "
                 "and the doubled value as an upper bound of the read traffic",
@@ -92,7 +92,7 @@ def write_summary(tag):
     A = L.append
     A("# Final run of %s on one MI355X (tools/gpu_%s.sh, summarised by tools/summarize_final.py)\n" % (tag, tag.replace("_final", "_final") if tag.startswith("r") else "final"))
     A("`pytest tests -m gpu`: %s (`%s_gputests.txt`); `__graft_entry__.smoke()`: ok.\n" % (tests[-1].strip() if tests else "?", tag))
-    A("## bench.py (default flags; `%s_bench.json`)\n" % tag)
+    A("## bench.py --full (`%s_bench.json`)\n" % tag)
     A("| item | value |\n|---|---|")
     A("| `value` (G1 MSM 2^20, inputs resident in HBM, mean of %d steps) | %.1f M scalar-mul/s, %.3f ms per step (median %.3f ms) |" % (d["steps"], d["value"], d["ms_per_step"], d["config"]["ms_per_step_median"]))
     A("| device stages (HIP events inside the library) | pipeline %.2f = digits+sort %.2f + accumulate %.2f + merge/reduce %.2f ms |" % (dm["pipeline"], dm["digits_sort"], dm["bucket_accumulate"], dm["merge_reduce"]))
