@@ -39,6 +39,8 @@ EXPORTS = [
     "bh_r1cs_create", "bh_r1cs_release", "bh_r1cs_shape", "bh_r1cs_density", "bh_r1cs_eval_dev", "bh_r1cs_eval_transposed_dev", "bh_fr_powers_dev", "bh_fr_qap_ext_dev",
     "bh_groth16_prove_witness", "bh_groth16_prove_assignment_async", "bh_groth16_prove_witness_async", "bh_groth16_proof_wait",
     "bh_groth16_prove_witness_part", "bh_groth16_sums_add", "bh_groth16_assemble",
+    "bh_groth16_prepare_verifying_key", "bh_groth16_pvk_from_params", "bh_groth16_pvk_num_inputs", "bh_groth16_verify",
+    "bh_groth16_batch_verify", "bh_groth16_pvk_release",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -46,6 +48,7 @@ TEST_EXPORTS = [
     "bh_test_fr_mul_dev", "bh_test_fp_mul_dev", "bh_test_point_add_dev", "bh_test_g2_k3_dev", "bh_test_g2_pairs_dev", "bh_test_g2_k6_dev",
     "bh_test_fr_mul_host", "bh_test_fr_mul_bform_host", "bh_test_fp_mul_host", "bh_test_point_add_host", "bh_test_point_mul_host", "bh_test_fr_inv_host", "bh_test_fp_lazy_host", "bh_test_proof_slice", "bh_test_synthesis_ms", "bh_test_fr_from_u512_host", "bh_test_fr_ops_host",
     "bh_test_groth16_prove_via_call_sites", "bh_test_demo_assignment", "bh_test_shard_cuts", "bh_test_pool_size_class", "bh_test_capture_check",
+    "bh_test_pairing", "bh_test_pairing_host",
 ]
 
 
@@ -236,6 +239,17 @@ def load():
     lib.bh_groth16_sums_add.argtypes = [vp, vp]
     lib.bh_groth16_sums_add.restype = None
     lib.bh_groth16_assemble.argtypes = [vp, vp, vp, vp, vp]
+    lib.bh_groth16_prepare_verifying_key.argtypes = [vp, vp, vp, vp, vp, vp, sz, c.POINTER(vp)]
+    lib.bh_groth16_pvk_from_params.argtypes = [vp, c.POINTER(vp)]
+    lib.bh_groth16_pvk_num_inputs.argtypes = [vp]
+    lib.bh_groth16_pvk_num_inputs.restype = sz
+    lib.bh_groth16_verify.argtypes = [vp, vp, vp, sz, i32]
+    lib.bh_groth16_batch_verify.argtypes = [vp, vp, sz, vp, sz, i32, vp]
+    lib.bh_groth16_pvk_release.argtypes = [vp]
+    lib.bh_groth16_pvk_release.restype = None
+    lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]
+    lib.bh_test_pairing_host.argtypes = [sz, vp, vp, vp]
+    lib.bh_test_pairing_host.restype = None
     lib.bh_groth16_prove_demo_r1cs_part.argtypes = [vp, vp, i32, sz, c.c_uint64, vp, vp, sz, sz, vp, vp]
     lib.bh_test_fr_mul_dev.argtypes = [vp, vp, vp, vp, sz]
     lib.bh_test_fp_mul_dev.argtypes = [vp, vp, vp, vp, sz]

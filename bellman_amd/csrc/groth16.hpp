@@ -645,4 +645,89 @@ class ProofPipeline {
   void retire_oldest();
 };
 
+// ---- groth16/src/verifier.rs, groth16/src/verifier/batch.rs: verification on the device ---------------------------
+// bellman::VerificationError (src/lib.rs:353-358); code = BH_ERR_INVALID_VERIFYING_KEY / BH_ERR_INVALID_PROOF, or
+// BH_ERR_INVALID_POINT for a proof point that is not on its curve
+struct VerificationError : std::runtime_error {
+  int code;
+  VerificationError(int c, const char *what) : std::runtime_error(what), code(c) {}
+};
+inline void verification_check(int rc) {
+  if (rc == BH_OK) return;
+  if (rc == BH_ERR_INVALID_VERIFYING_KEY) throw VerificationError(rc, "InvalidVerifyingKey");
+  if (rc == BH_ERR_INVALID_PROOF) throw VerificationError(rc, "InvalidProof");
+  if (rc == BH_ERR_INVALID_POINT) throw VerificationError(rc, "proof point not on its curve");
+  throw bellman::SynthesisError(rc, "device verification failed");
+}
+
+// PreparedVerifyingKey (groth16/src/lib.rs:400-409): owns the device handle; release it before the context goes
+class PreparedVerifyingKey {
+ public:
+  PreparedVerifyingKey(bh_ctx *ctx, const VerifyingKey &vk) {   // prepare_verifying_key (verifier.rs:11-21)
+    if (vk.ic.empty()) throw bellman::SynthesisError(BH_ERR_INVALID_ARG, "verifying key without ic");
+    const int rc = bh_groth16_prepare_verifying_key(ctx, &vk.alpha_g1, &vk.beta_g2, &vk.gamma_g2, &vk.delta_g2, vk.ic.data(),
+                                                    vk.ic.size(), &h_);
+    if (rc != BH_OK) throw bellman::SynthesisError(rc, "prepare_verifying_key");
+  }
+  ~PreparedVerifyingKey() { bh_groth16_pvk_release(h_); }
+  PreparedVerifyingKey(const PreparedVerifyingKey &) = delete;
+  PreparedVerifyingKey &operator=(const PreparedVerifyingKey &) = delete;
+  size_t num_inputs() const { return bh_groth16_pvk_num_inputs(h_); }
+  const bh_pvk *handle() const { return h_; }
+
+ private:
+  bh_pvk *h_ = nullptr;
+};
+
+inline std::unique_ptr<PreparedVerifyingKey> prepare_verifying_key(const Parameters &params) {
+  return std::unique_ptr<PreparedVerifyingKey>(new PreparedVerifyingKey(params.ctx, params.vk));
+}
+
+// verify_proof (verifier.rs:23-58): returns normally or throws VerificationError
+inline void verify_proof(const PreparedVerifyingKey &pvk, const Proof &proof, const std::vector<Fr> &public_inputs) {
+  verification_check(bh_groth16_verify(pvk.handle(), &proof, public_inputs.empty() ? nullptr : public_inputs.data(),
+                                       public_inputs.size(), BH_SCALARS_MONT));
+}
+
+// batch::Verifier (batch.rs:68-275) for proofs of one verifying key
+class BatchVerifier {
+ public:
+  void queue(const Proof &proof, std::vector<Fr> inputs) { items_.push_back(Item{proof, std::move(inputs)}); }
+  size_t size() const { return items_.size(); }
+  // Verifier::verify(rng, vk) (batch.rs:93-192): z_j = Fr::from_u512 of 8 words of `rng` (any callable returning
+  // uint64_t, like create_random_proof's), redrawn while zero.  Throws VerificationError.
+  template <class Rng>
+  void verify(Rng &&rng, const PreparedVerifyingKey &pvk) const {
+    const size_t n_in = pvk.num_inputs();
+    for (const Item &it : items_)   // batch.rs:101-107: before any work
+      if (it.inputs.size() != n_in) throw VerificationError(BH_ERR_INVALID_VERIFYING_KEY, "InvalidVerifyingKey");
+    std::vector<Proof> proofs;
+    std::vector<Fr> inputs, z;
+    proofs.reserve(items_.size());
+    inputs.reserve(items_.size() * n_in);
+    z.reserve(items_.size());
+    for (const Item &it : items_) {
+      proofs.push_back(it.proof);
+      inputs.insert(inputs.end(), it.inputs.begin(), it.inputs.end());
+      Fr zj;
+      do {
+        uint64_t w[8];
+        for (uint64_t &x : w) x = rng();
+        zj = Fr::from_u512(w);
+      } while (zj.is_zero());
+      z.push_back(zj);
+    }
+    verification_check(bh_groth16_batch_verify(pvk.handle(), proofs.empty() ? nullptr : proofs.data(), proofs.size(),
+                                               inputs.empty() ? nullptr : inputs.data(), n_in, BH_SCALARS_MONT,
+                                               z.empty() ? nullptr : z.data()));
+  }
+
+ private:
+  struct Item {
+    Proof proof;
+    std::vector<Fr> inputs;
+  };
+  std::vector<Item> items_;
+};
+
 }  // namespace groth16

@@ -68,6 +68,14 @@ int bh_groth16_params_write(const bh_params *p, void *buf, size_t cap, size_t *l
   } catch (const bellman::SynthesisError &e) { return e.code;
   } catch (...) { return BH_ERR_HIP; }
 }
+// prepare_verifying_key (groth16/src/verifier.rs:11-21) on the verifying key of params that carry gamma_g2 and ic
+int bh_groth16_pvk_from_params(const bh_params *p, bh_pvk **out) {
+  if (!p || !out) return BH_ERR_INVALID_ARG;
+  const groth16::Parameters &P = *p->p;
+  if (P.vk.ic.empty()) return BH_ERR_INVALID_ARG;
+  return bh_groth16_prepare_verifying_key(P.ctx, &P.vk.alpha_g1, &P.vk.beta_g2, &P.vk.gamma_g2, &P.vk.delta_g2, P.vk.ic.data(),
+                                          P.vk.ic.size(), out);
+}
 int bh_groth16_params_vk_ext(const bh_params *p, void *gamma_g2, void *ic_out, size_t ic_cap, size_t *n_ic) {
   if (!p) return BH_ERR_INVALID_ARG;
   const groth16::VerifyingKey &vk = p->p->vk;

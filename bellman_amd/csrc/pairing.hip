@@ -1,0 +1,630 @@
+// Groth16 verification on the device: prepare_verifying_key, verify_proof (groth16/src/verifier.rs:11-58) and the batch
+// verifier (groth16/src/verifier/batch.rs:93-275), declared in include/bellman_hip.h.
+//
+// Device work per call (fp12.cuh holds the arithmetic and its conventions):
+//   1. g2_lines_kernel      one lane per G2 point Q: the 68 projective line coefficients of the Miller loop over |x|
+//                           ("G2Prepared"), written to HBM (288 B per line); the on-curve test of Q.
+//   2. proof_prep_kernel    one lane per proof: the on-curve tests of A and C, A' = [z_j] A (double-and-add, one
+//                           inversion to affine), C and z_j copied out as the bases / scalars of the sum of z_j C_j.
+//   3. fr_colsum_kernels    acc_Gamma_i = sum_j z_j a_{j,i} (acc_Gamma_0 = acc_Y = sum_j z_j), Montgomery Fr.
+//   4. miller_kernel        one lane per (P, lines of Q) pair: f = f_{|x|,Q}(P) in Fp12 (576 B).
+//   5. f12_fold_kernel      the product of all f (a halving tree, one launch per level).
+//   6. final_exp.cuh        one lane: f^(3 (p^12 - 1) / q) == 1, as a chain of small kernels.
+// The two multiexps (sum z_j C_j over the proofs' C, Psi = sum acc_Gamma_i ic_i over the key's registered ic) run on
+// the existing multiexp path (bh_msm_async_dev_after), ordered after the kernels that produce their inputs.
+//
+// Batches are processed in chunks of at most BATCH_CHUNK proofs (device workspace < 400 MB whatever the batch size); the
+// Fp12 product of each chunk is folded into a running product that the next chunk multiplies in.
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "common.hpp"
+#include "final_exp.cuh"
+#include "fp12.cuh"
+
+namespace bh {
+
+static constexpr u32 PF_IDENTITY = 1u, PF_OFF_CURVE = 2u;
+static constexpr size_t BATCH_CHUNK = 16384;
+static constexpr size_t INPUTS_CHUNK_BYTES = size_t(256) << 20;
+
+template <class F>
+BH_HD bool on_curve(const Affine<F> &p) {
+  typedef typename F::T T;
+  T lhs, rhs, b;
+  F::sqr(lhs, p.y);
+  F::sqr(rhs, p.x);
+  F::mul(rhs, rhs, p.x);
+  F::curve_b(b);
+  F::add(rhs, rhs, b);
+  return F::eq(lhs, rhs);
+}
+// a 32-byte scalar in the format of bh_msm_async, as a canonical 256-bit integer (a value >= q is used as is: the points
+// it multiplies have order q)
+BH_HD void scalar_bits(fr_t &k, const fr_t &s, int fmt) {
+  if (fmt == BH_SCALARS_MONT) fe_from_mont(k, s);
+  else k = s;
+}
+
+// 1. lines of Q (or -Q with negate); flags: PF_IDENTITY, PF_OFF_CURVE
+__global__ __launch_bounds__(64) void g2_lines_kernel(const Affine<Fp2Ops> *q, size_t stride_words, int negate, line_t *lines,
+                                                      u32 *flags, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Affine<Fp2Ops> p = *(const Affine<Fp2Ops> *)((const u32 *)q + (size_t)i * stride_words);
+  line_t *out = lines + (size_t)i * MILLER_LINES;
+  if (aff_is_identity(p)) {
+    flags[i] = PF_IDENTITY;
+    return;
+  }
+  flags[i] = on_curve(p) ? 0u : PF_OFF_CURVE;
+  if (negate) Fp2Ops::neg(p.y, p.y);
+  g2_lines(p.x, p.y, [&](int k, const line_t &l) { out[k] = l; });
+}
+
+// 2. per proof (384-byte records a | b | c): flags of A and C, P_j = [z_j] A (z == NULL: A itself), the C base (the
+// generator with a zero scalar where C is the identity: multiexp bases must not be the identity) and its scalar
+struct ProofRec {
+  Affine<FpOps> a;
+  Affine<Fp2Ops> b;
+  Affine<FpOps> c;
+};
+__global__ __launch_bounds__(64) void proof_prep_kernel(const ProofRec *proofs, const fr_t *z, int fmt, Affine<FpOps> *p_out,
+                                                        Affine<FpOps> *c_out, fr_t *zc_out, const Affine<FpOps> *g1, u32 *flags,
+                                                        u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<FpOps> a = proofs[i].a, c = proofs[i].c;
+  u32 fl = 0;
+  if (!aff_is_identity(a) && !on_curve(a)) fl |= PF_OFF_CURVE;
+  if (!aff_is_identity(c) && !on_curve(c)) fl |= PF_OFF_CURVE;
+  flags[i] = fl;
+  if (c_out) {
+    const bool ci = aff_is_identity(c);
+    c_out[i] = ci ? *g1 : c;
+    fr_t zz;
+    if (ci) fe_zero(zz);
+    else if (z) zz = z[i];
+    else { fe_zero(zz); zz.l[0] = 1; }   // (not used by the single verification)
+    zc_out[i] = zz;
+  }
+  if (!z) {
+    p_out[i] = a;
+    return;
+  }
+  fr_t k;
+  scalar_bits(k, z[i], fmt);
+  XYZZ<FpOps> acc;
+  xyzz_set_identity(acc);
+  if (!aff_is_identity(a))
+    for (int bit = 255; bit >= 0; bit--) {
+      XYZZ<FpOps> t;
+      xyzz_dbl(t, acc);
+      acc = t;
+      if ((k.l[bit >> 5] >> (bit & 31)) & 1) xyzz_madd(acc, a);
+    }
+  Affine<FpOps> r;
+  xyzz_to_affine(r, acc);
+  p_out[i] = r;
+}
+
+// [s] P for one point and a device scalar (Montgomery): alpha * acc_Y of the batch check
+__global__ __launch_bounds__(64) void g1_mul_one_kernel(Affine<FpOps> *out, const Affine<FpOps> *p, const fr_t *s) {
+  if (threadIdx.x != 0) return;
+  fr_t k;
+  fe_from_mont(k, *s);
+  const Affine<FpOps> a = *p;
+  XYZZ<FpOps> acc;
+  xyzz_set_identity(acc);
+  if (!aff_is_identity(a))
+    for (int bit = 255; bit >= 0; bit--) {
+      XYZZ<FpOps> t;
+      xyzz_dbl(t, acc);
+      acc = t;
+      if ((k.l[bit >> 5] >> (bit & 31)) & 1) xyzz_madd(acc, a);
+    }
+  Affine<FpOps> r;
+  xyzz_to_affine(r, acc);
+  *out = r;
+}
+
+// 3. column sums: part[col * nb + block] = sum over the block's proofs of z_j * a_{j,col} (a_{j,0} = 1), Montgomery
+static constexpr u32 COLSUM_THREADS = 256, COLSUM_BLOCKS = 64;
+BH_HD void scalar_mont(fr_t &r, const fr_t &s, int fmt) {
+  if (fmt == BH_SCALARS_MONT) {
+    r = s;
+    return;
+  }
+  fe_to_mont(r, s);   // a value < 2^256 times R^2 < q R: the product is reduced
+}
+__global__ __launch_bounds__(COLSUM_THREADS) void fr_colsum_kernel(const fr_t *z, const fr_t *inputs, u32 n_inputs, int fmt,
+                                                                   u32 n, fr_t *part) {
+  __shared__ fr_t sh[COLSUM_THREADS];
+  const u32 col = blockIdx.x, t = threadIdx.x;
+  fr_t acc;
+  fe_zero(acc);
+  for (u32 j = blockIdx.y * COLSUM_THREADS + t; j < n; j += gridDim.y * COLSUM_THREADS) {
+    fr_t zm, term;
+    scalar_mont(zm, z[j], fmt);
+    if (col == 0) term = zm;
+    else {
+      fr_t a;
+      scalar_mont(a, inputs[(size_t)j * n_inputs + col - 1], fmt);
+      fe_mul(term, zm, a);
+    }
+    fe_add(acc, acc, term);
+  }
+  sh[t] = acc;
+  __syncthreads();
+  for (u32 h = COLSUM_THREADS / 2; h; h >>= 1) {
+    if (t < h) {
+      fr_t s;
+      fe_add(s, sh[t], sh[t + h]);
+      sh[t] = s;
+    }
+    __syncthreads();
+  }
+  if (t == 0) part[(size_t)col * gridDim.y + blockIdx.y] = sh[0];
+}
+// acc[col] += sum of the column's nb partial sums
+__global__ __launch_bounds__(64) void fr_colsum_finish_kernel(const fr_t *part, u32 nb, u32 ncol, fr_t *acc) {
+  const u32 col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= ncol) return;
+  fr_t s = acc[col];
+  for (u32 b = 0; b < nb; b++) fe_add(s, s, part[(size_t)col * nb + b]);
+  acc[col] = s;
+}
+
+// 4. Miller loops: f[j] = f_{|x|,Q_j}(P_j); the lines of Q_j at lines0 + j * 68 for j < n0, else at lines1 + (j - n0) * 68
+// (a proof's own pairs and the prepared key's in one launch); an identity P or Q gives 1
+__global__ __launch_bounds__(64) void miller_kernel(const Affine<FpOps> *p, const line_t *lines0, const u32 *qflags0, u32 n0,
+                                                    const line_t *lines1, const u32 *qflags1, fp12_t *f, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<FpOps> pp = p[i];
+  const line_t *l = i < n0 ? lines0 + (size_t)i * MILLER_LINES : lines1 + (size_t)(i - n0) * MILLER_LINES;
+  const u32 qf = i < n0 ? qflags0[i] : qflags1[i - n0];
+  fp12_t r;
+  if (aff_is_identity(pp) || (qf & PF_IDENTITY)) {
+    f12_one(r);
+  } else {
+    miller_loop_lines(r, pp.x, pp.y, [&](int k) { return l[k]; });
+  }
+  f[i] = r;
+}
+
+// 5. f[i] *= f[i + h] for i < m - h
+__global__ __launch_bounds__(64) void f12_fold_kernel(fp12_t *f, u32 m, u32 h) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i + h >= m) return;
+  fp12_t a = f[i], b = f[i + h];
+  f12_mul(a, a, b);
+  f[i] = a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+static u32 blocks_of(size_t n, u32 t) { return (u32)((n + t - 1) / t); }
+
+// device buffers from the context's pool, returned on scope exit
+struct PoolBufs {
+  Context &c;
+  std::vector<void *> held;
+  explicit PoolBufs(Context &c_) : c(c_) {}
+  ~PoolBufs() {
+    for (void *p : held) c.pool.release(p);
+  }
+  template <class T>
+  T *get(size_t n) {
+    void *p = c.pool.acquire(n * sizeof(T));
+    if (!p) return nullptr;
+    held.push_back(p);
+    return (T *)p;
+  }
+};
+struct StreamHold {
+  bh_ctx *ctx;
+  hipStream_t st = nullptr;
+  explicit StreamHold(bh_ctx *c) : ctx(c) {}
+  ~StreamHold() {
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      bh_stream_destroy(ctx, (void *)st);
+    }
+  }
+};
+
+int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int negate, line_t *lines, u32 *flags, size_t n) {
+  if (!n) return BH_OK;
+  (void)hipGetLastError();   // a handled error of an earlier call on this thread is not ours
+  hipLaunchKernelGGL(g2_lines_kernel, dim3(blocks_of(n, 64)), dim3(64), 0, st, (const Affine<Fp2Ops> *)q_dev, stride_bytes / 4,
+                     negate, lines, flags, (u32)n);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
+                  const line_t *lines1 = nullptr, const u32 *qflags1 = nullptr, size_t n1 = 0) {
+  if (!(n + n1)) return BH_OK;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(miller_kernel, dim3(blocks_of(n + n1, 64)), dim3(64), 0, st, p, lines, qflags, (u32)n, lines1, qflags1, f,
+                     (u32)(n + n1));
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// product of f[0..m) into f[0]
+int launch_fold(hipStream_t st, fp12_t *f, size_t m) {
+  while (m > 1) {
+    const size_t h = (m + 1) / 2;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(f12_fold_kernel, dim3(blocks_of(m - h, 64)), dim3(64), 0, st, f, (u32)m, (u32)h);
+    BH_HIP_CHECK(hipGetLastError());
+    m = h;
+  }
+  return BH_OK;
+}
+// f^(3 (p^12 - 1) / q) (canonical) and its test against 1, for n values; ws: 4 n Fp12
+int launch_final_exp(hipStream_t st, const fp12_t *f, size_t n, fp12_t *out, u32 *is_one, fp12_t *ws) {
+  if (!final_exp_chain(st, f, out, is_one, ws, (u32)n)) {
+    fprintf(stderr, "[bellman_hip] final exponentiation: launch failed\n");
+    return BH_ERR_HIP;
+  }
+  return BH_OK;
+}
+
+}  // namespace bh
+
+using namespace bh;
+
+// PreparedVerifyingKey (groth16/src/lib.rs:400-409): the lines of -gamma, -delta and beta in HBM, -alpha, and ic
+// registered as multiexp bases (an identity ic_i is replaced by the generator and its scalar forced to zero)
+struct bh_pvk {
+  bh_ctx *ctx = nullptr;
+  Affine<FpOps> neg_alpha;   // host, canonical Montgomery
+  Affine<FpOps> alpha;
+  line_t *lines = nullptr;   // [3][68]: -gamma, -delta, beta
+  u32 *qflags = nullptr;     // [3]
+  Affine<FpOps> *alpha_dev = nullptr;
+  bh_bases *ic = nullptr;
+  size_t n_ic = 0;
+  std::vector<uint8_t> ic_identity;
+};
+
+namespace {
+// the generator of G1 (Montgomery form), from its canonical coordinates
+void g1_generator(Affine<FpOps> &g) {
+  static const u32 gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu,
+                             0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
+  static const u32 gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu,
+                             0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
+  fp_t x, y;
+  memcpy(x.l, gx, 48);
+  memcpy(y.l, gy, 48);
+  fe_to_mont(g.x, x);
+  fe_to_mont(g.y, y);
+}
+void neg_g1_host(Affine<FpOps> &r, const Affine<FpOps> &a) {
+  r = a;
+  if (FpOps::is_zero_canonical(a.x, a.y)) return;
+  bool zero = true;
+  for (int i = 0; i < 12; i++) zero = zero && a.y.l[i] == 0;
+  if (zero) return;
+  u32 br = 0;
+  for (int i = 0; i < 12; i++) r.y.l[i] = subb(FpParams::mod(i), a.y.l[i], br, br);
+}
+// a 32-byte little-endian value that is 0 mod q: 0, q or 2q (3q > 2^256); the same test holds for a Montgomery
+// representative, as aR = 0 mod q exactly when a = 0 mod q
+bool scalar_is_zero_mod_q(const uint8_t *s) {
+  u32 w[8];
+  memcpy(w, s, 32);
+  bool zero = true, is_q = true, is_2q = true;
+  u32 carry = 0;
+  for (int i = 0; i < 8; i++) {
+    const u32 m = FrParams::mod(i);
+    const u32 m2 = (m << 1) | carry;
+    carry = m >> 31;
+    zero = zero && w[i] == 0;
+    is_q = is_q && w[i] == m;
+    is_2q = is_2q && w[i] == m2;
+  }
+  return zero || is_q || is_2q;
+}
+
+// the pairing check itself: n_chunks of proofs were folded into facc; now the three key pairs, the product, the
+// final exponentiation.  key_p: the three G1 points (device) paired with -gamma, -delta, beta.
+// The pairing check: the three key pairs (key_p: the G1 points paired with -gamma, -delta, beta) - after n_own pairs of
+// the caller's (P at key_p - n_own, lines own_lines) in the same launch - times facc (the proofs' product so far, may be
+// NULL), then the final exponentiation.
+int finish_check(hipStream_t st, const bh_pvk *pvk, PoolBufs &bufs, const Affine<FpOps> *key_p_dev, size_t n_own,
+                 const line_t *own_lines, const u32 *own_flags, const fp12_t *facc, u32 *is_one_dev, bool *is_one) {
+  fp12_t *fk = bufs.get<fp12_t>(n_own + 4 + 5);   // the pairs' values, the running product, final exponentiation workspace
+  if (!fk) return BH_ERR_HIP;
+  fp12_t *fe = fk + n_own + 4;
+  int rc = n_own ? launch_miller(st, key_p_dev - n_own, own_lines, own_flags, fk, n_own, pvk->lines, pvk->qflags, 3)
+                 : launch_miller(st, key_p_dev, pvk->lines, pvk->qflags, fk, 3);
+  if (rc) return rc;
+  size_t m = n_own + 3;
+  if (facc) {
+    if (hipMemcpyAsync(fk + m, facc, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return BH_ERR_HIP;
+    m++;
+  }
+  if ((rc = launch_fold(st, fk, m))) return rc;
+  if ((rc = launch_final_exp(st, fk, 1, fe, is_one_dev, fe + 1))) return rc;
+  u32 h = 0;
+  if (hipMemcpyAsync(&h, is_one_dev, 4, hipMemcpyDeviceToHost, st) != hipSuccess) return BH_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return BH_ERR_HIP;
+  *is_one = h == 1;
+  return BH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bh_groth16_prepare_verifying_key(bh_ctx *ctx, const void *alpha_g1, const void *beta_g2, const void *gamma_g2,
+                                     const void *delta_g2, const void *ic, size_t n_ic, bh_pvk **out) {
+  if (!ctx || !alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !out || (n_ic && !ic) || !n_ic) return BH_ERR_INVALID_ARG;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  std::unique_ptr<bh_pvk> k(new bh_pvk);
+  k->ctx = ctx;
+  memcpy(&k->alpha, alpha_g1, 96);
+  neg_g1_host(k->neg_alpha, k->alpha);
+  k->n_ic = n_ic;
+  // ic with identities replaced by the generator (their scalars are zeroed at use)
+  std::vector<Affine<FpOps>> icv(n_ic);
+  memcpy(icv.data(), ic, n_ic * 96);
+  Affine<FpOps> gen;
+  g1_generator(gen);
+  k->ic_identity.assign(n_ic, 0);
+  for (size_t i = 0; i < n_ic; i++)
+    if (FpOps::is_zero_canonical(icv[i].x, icv[i].y)) {
+      k->ic_identity[i] = 1;
+      icv[i] = gen;
+    }
+  int rc = bh_bases_register(ctx, BH_G1, icv.data(), n_ic, 96, -1, &k->ic);
+  if (rc) return rc;
+  k->lines = (line_t *)c.pool.acquire(3 * MILLER_LINES * sizeof(line_t));
+  k->qflags = (u32 *)c.pool.acquire(3 * sizeof(u32) + 2 * sizeof(Affine<FpOps>));
+  if (!k->lines || !k->qflags) {
+    bh_groth16_pvk_release(k.release());
+    return BH_ERR_HIP;
+  }
+  k->alpha_dev = (Affine<FpOps> *)((char *)k->qflags + 64);
+  // -gamma, -delta, beta (groth16/src/verifier.rs:11-21) and their lines
+  std::vector<Affine<Fp2Ops>> q(3);
+  memcpy(&q[0], gamma_g2, 192);
+  memcpy(&q[1], delta_g2, 192);
+  memcpy(&q[2], beta_g2, 192);
+  void *qd = c.pool.acquire(3 * 192);
+  if (!qd) {
+    bh_groth16_pvk_release(k.release());
+    return BH_ERR_HIP;
+  }
+  hipStream_t st = c.stream;
+  std::vector<u32> fl(3, 0);
+  rc = BH_OK;
+  if (hipMemcpyAsync(qd, q.data(), 3 * 192, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(k->alpha_dev, &k->alpha, 96, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = BH_ERR_HIP;
+  if (!rc) rc = launch_g2_lines(st, qd, 192, 1, k->lines, k->qflags, 2);                 // -gamma, -delta
+  if (!rc) rc = launch_g2_lines(st, (char *)qd + 2 * 192, 192, 0, k->lines + 2 * MILLER_LINES, k->qflags + 2, 1);   // beta
+  if (!rc && hipMemcpyAsync(fl.data(), k->qflags, 12, hipMemcpyDeviceToHost, st) != hipSuccess) rc = BH_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
+  c.pool.release(qd);
+  if (!rc)
+    for (u32 f : fl)
+      if (f & PF_OFF_CURVE) rc = BH_ERR_INVALID_POINT;
+  if (rc) {
+    bh_groth16_pvk_release(k.release());
+    return rc;
+  }
+  *out = k.release();
+  return BH_OK;
+}
+
+void bh_groth16_pvk_release(bh_pvk *pvk) {
+  if (!pvk) return;
+  Context &c = pvk->ctx->c;
+  (void)hipSetDevice(c.device);
+  if (pvk->ic) bh_bases_release(pvk->ctx, pvk->ic);
+  c.pool.release(pvk->lines);
+  c.pool.release(pvk->qflags);
+  delete pvk;
+}
+
+size_t bh_groth16_pvk_num_inputs(const bh_pvk *pvk) { return pvk ? pvk->n_ic - 1 : 0; }
+
+// verify_proof (groth16/src/verifier.rs:23-58): acc = ic_0 + sum inputs_i ic_{i+1} (a multiexp over the registered ic),
+// then e(A, B) e(acc, -gamma) e(C, -delta) e(-alpha, beta) == 1 with one final exponentiation - the reference compares
+// the first three against e(alpha, beta), the same equation.
+int bh_groth16_verify(const bh_pvk *pvk, const void *proof, const void *inputs, size_t n_inputs, int scalar_fmt) {
+  if (!pvk || !proof || (n_inputs && !inputs) || (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT))
+    return BH_ERR_INVALID_ARG;
+  if (n_inputs + 1 != pvk->n_ic) return BH_ERR_INVALID_VERIFYING_KEY;   // verifier.rs:27-29
+  bh_ctx *ctx = pvk->ctx;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  // scalars [1, inputs...] over ic
+  std::vector<uint8_t> sc(32 * pvk->n_ic, 0);
+  if (scalar_fmt == BH_SCALARS_MONT) {
+    for (int i = 0; i < 8; i++) {
+      const u32 w = FrParams::one(i);
+      memcpy(&sc[4 * i], &w, 4);
+    }
+  } else {
+    sc[0] = 1;
+  }
+  if (n_inputs) memcpy(&sc[32], inputs, 32 * n_inputs);
+  for (size_t i = 0; i < pvk->n_ic; i++)
+    if (pvk->ic_identity[i]) memset(&sc[32 * i], 0, 32);
+  bh_msm_job *job = nullptr;
+  int rc = bh_msm_async(ctx, pvk->ic, 0, sc.data(), pvk->n_ic, scalar_fmt, nullptr, 0, &job);
+  if (rc) return rc;
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  ProofRec *pr = bufs.get<ProofRec>(1);
+  Affine<FpOps> *pts = bufs.get<Affine<FpOps>>(4);   // [A, acc, C, -alpha]
+  line_t *lines = bufs.get<line_t>(MILLER_LINES);
+  u32 *flags = bufs.get<u32>(4);
+  Affine<FpOps> acc;
+  Affine<FpOps> key[3];   // source of an asynchronous copy: lives until finish_check has synchronised
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) sh.st = nullptr;
+  if (!pr || !pts || !lines || !flags || !sh.st) {
+    bh_msm_wait(job, &acc);
+    return BH_ERR_HIP;
+  }
+  hipStream_t st = sh.st;
+  const ProofRec *hp = (const ProofRec *)proof;
+  if (hipMemcpyAsync(pr, proof, sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+  if (!rc) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(proof_prep_kernel, dim3(1), dim3(64), 0, st, pr, (const fr_t *)nullptr, 0, pts, (Affine<FpOps> *)nullptr,
+                       (fr_t *)nullptr, (const Affine<FpOps> *)nullptr, flags, 1u);
+    if (hipGetLastError() != hipSuccess) rc = BH_ERR_HIP;
+  }
+  if (!rc) rc = launch_g2_lines(st, &pr->b, sizeof(ProofRec), 0, lines, flags + 1, 1);
+  const int mrc = bh_msm_wait(job, &acc);
+  if (!rc) rc = mrc;
+  if (!rc) {
+    key[0] = acc;
+    key[1] = hp->c;
+    key[2] = pvk->neg_alpha;
+    if (hipMemcpyAsync(pts + 1, key, sizeof key, hipMemcpyHostToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+  }
+  bool one = false;
+  if (!rc) rc = finish_check(st, pvk, bufs, pts + 1, 1, lines, flags + 1, nullptr, flags + 3, &one);
+  u32 hf[2] = {0, 0};
+  if (!rc && (hipMemcpyAsync(hf, flags, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+    rc = BH_ERR_HIP;
+  if (rc) return rc;
+  if ((hf[0] | hf[1]) & PF_OFF_CURVE) return BH_ERR_INVALID_POINT;
+  return one ? BH_OK : BH_ERR_INVALID_PROOF;
+}
+
+// batch::Verifier::verify (groth16/src/verifier/batch.rs:93-192) with the caller's z_j:
+//   prod_j e([z_j] A_j, -B_j) * e(-sum z_j C_j, -delta) * e(-Psi, -gamma) * e([acc_Y] alpha, beta) == 1
+// (e(X, Y) = e(-X, -Y): the prepared key's -gamma / -delta lines serve both verifiers).
+int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
+                            int scalar_fmt, const void *z) {
+  if (!pvk || (n_proofs && (!proofs || !z)) || (n_proofs && n_inputs && !inputs) ||
+      (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT))
+    return BH_ERR_INVALID_ARG;
+  if (n_inputs + 1 != pvk->n_ic) return BH_ERR_INVALID_VERIFYING_KEY;   // batch.rs:101-107
+  if (!n_proofs) return BH_OK;                                           // no Miller terms: the reference's empty batch
+  for (size_t j = 0; j < n_proofs; j++)
+    if (scalar_is_zero_mod_q((const uint8_t *)z + 32 * j)) return BH_ERR_INVALID_ARG;   // batch.rs:117-128: z != 0
+  bh_ctx *ctx = pvk->ctx;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) return BH_ERR_HIP;
+  hipStream_t st = sh.st;
+  // chunk: at most BATCH_CHUNK proofs, and at most INPUTS_CHUNK_BYTES of public inputs
+  const size_t by_inputs = std::max<size_t>(1, INPUTS_CHUNK_BYTES / (32 * std::max<size_t>(n_inputs, 1)));
+  const size_t ch = std::min(std::min(n_proofs, BATCH_CHUNK), by_inputs);
+  const size_t ncol = pvk->n_ic;
+  ProofRec *pr = bufs.get<ProofRec>(ch);
+  fr_t *zd = bufs.get<fr_t>(ch);
+  fr_t *ind = bufs.get<fr_t>(ch * (n_inputs ? n_inputs : 1));
+  Affine<FpOps> *pts = bufs.get<Affine<FpOps>>(ch);
+  Affine<FpOps> *cb = bufs.get<Affine<FpOps>>(ch);
+  fr_t *zc = bufs.get<fr_t>(ch);
+  line_t *lines = bufs.get<line_t>(ch * MILLER_LINES);
+  u32 *pflags = bufs.get<u32>(ch), *qflags = bufs.get<u32>(ch + 1);
+  fp12_t *f = bufs.get<fp12_t>(ch + 1);
+  fp12_t *facc = bufs.get<fp12_t>(1);
+  fr_t *part = bufs.get<fr_t>(ncol * COLSUM_BLOCKS);
+  fr_t *acc = bufs.get<fr_t>(ncol);
+  Affine<FpOps> *key = bufs.get<Affine<FpOps>>(3);
+  Affine<FpOps> *gen = bufs.get<Affine<FpOps>>(1);
+  if (!pr || !zd || !ind || !pts || !cb || !zc || !lines || !pflags || !qflags || !f || !facc || !part || !acc || !key || !gen) {
+    fprintf(stderr, "[bellman_hip] batch verification: no device memory for a %zu-proof chunk\n", ch);
+    return BH_ERR_HIP;
+  }
+  fp12_t one;
+  f12_one(one);
+  Affine<FpOps> g;
+  g1_generator(g);
+  int rc = BH_OK;
+  if (hipMemcpyAsync(facc, &one, sizeof one, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(gen, &g, sizeof g, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(acc, 0, ncol * sizeof(fr_t), st) != hipSuccess)
+    return BH_ERR_HIP;
+  Affine<FpOps> sum_c;   // sum z_j C_j over the chunks so far (host, affine)
+  memset(&sum_c, 0, sizeof sum_c);
+  u32 bad = 0;
+  std::vector<u32> hflags(ch), hqflags(ch);
+  for (size_t first = 0; first < n_proofs && !rc; first += ch) {
+    const size_t m = n_proofs - first < ch ? n_proofs - first : ch;
+    if (hipMemcpyAsync(pr, (const ProofRec *)proofs + first, m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(zd, (const fr_t *)z + first, m * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (n_inputs && hipMemcpyAsync(ind, (const fr_t *)inputs + first * n_inputs, m * n_inputs * 32, hipMemcpyHostToDevice, st) !=
+                         hipSuccess)) {
+      rc = BH_ERR_HIP;
+      break;
+    }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(proof_prep_kernel, dim3(blocks_of(m, 64)), dim3(64), 0, st, pr, zd, scalar_fmt, pts, cb, zc, gen, pflags,
+                       (u32)m);
+    if (hipGetLastError() != hipSuccess) { rc = BH_ERR_HIP; break; }
+    if ((rc = launch_g2_lines(st, &pr->b, sizeof(ProofRec), 1, lines, qflags, m))) break;   // -B_j
+    {
+      const u32 nb = (u32)std::min<size_t>(COLSUM_BLOCKS, blocks_of(m, COLSUM_THREADS));
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(fr_colsum_kernel, dim3((u32)ncol, nb), dim3(COLSUM_THREADS), 0, st, zd, ind, (u32)n_inputs, scalar_fmt,
+                         (u32)m, part);
+      hipLaunchKernelGGL(fr_colsum_finish_kernel, dim3(blocks_of(ncol, 64)), dim3(64), 0, st, part, nb, (u32)ncol, acc);
+      if (hipGetLastError() != hipSuccess) { rc = BH_ERR_HIP; break; }
+    }
+    // sum z_j C_j of this chunk on the multiexp path, ordered after the prep kernel
+    bh_bases *cbases = nullptr;
+    bh_msm_job *job = nullptr;
+    if ((rc = bh_bases_wrap_dev(ctx, BH_G1, cb, m, &cbases))) break;
+    rc = bh_msm_async_dev_after(ctx, cbases, 0, zc, m, scalar_fmt, nullptr, 0, nullptr, (void *)st, &job);
+    if (!rc) rc = launch_miller(st, pts, lines, qflags, f, m);
+    if (!rc && hipMemcpyAsync(f + m, facc, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (!rc) rc = launch_fold(st, f, m + 1);
+    if (!rc && hipMemcpyAsync(facc, f, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (!rc && (hipMemcpyAsync(hflags.data(), pflags, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(hqflags.data(), qflags, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+      rc = BH_ERR_HIP;
+    Affine<FpOps> part_c;
+    if (job) {
+      const int mrc = bh_msm_wait(job, &part_c);
+      if (!rc) rc = mrc;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
+    bh_bases_release(ctx, cbases);
+    if (rc) break;
+    bh_point_add(BH_G1, &sum_c, &sum_c, &part_c, 1);
+    for (size_t j = 0; j < m; j++) bad |= hflags[j] | (hqflags[j] & PF_OFF_CURVE);
+  }
+  if (rc) return rc;
+  if (bad & PF_OFF_CURVE) return BH_ERR_INVALID_POINT;
+  // [acc_Y] alpha (acc_Y = acc_Gamma_0), then Psi = sum acc_Gamma_i ic_i with the scalars of identity ic_i zeroed (they take
+  // no part; the zeroing is ordered after the read of acc_Y)
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(g1_mul_one_kernel, dim3(1), dim3(64), 0, st, key + 2, pvk->alpha_dev, (const fr_t *)acc);
+  if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+  for (size_t i = 0; i < ncol; i++)
+    if (pvk->ic_identity[i] && hipMemsetAsync(acc + i, 0, sizeof(fr_t), st) != hipSuccess) return BH_ERR_HIP;
+  bh_msm_job *job = nullptr;
+  if ((rc = bh_msm_async_dev_after(ctx, pvk->ic, 0, acc, ncol, BH_SCALARS_MONT, nullptr, 0, nullptr, (void *)st, &job))) return rc;
+  Affine<FpOps> psi;
+  const int mrc = bh_msm_wait(job, &psi);
+  if (!rc) rc = mrc;
+  if (rc) return rc;
+  Affine<FpOps> k2[2];
+  neg_g1_host(k2[0], psi);
+  neg_g1_host(k2[1], sum_c);
+  if (hipMemcpyAsync(key, k2, sizeof k2, hipMemcpyHostToDevice, st) != hipSuccess) return BH_ERR_HIP;
+  bool ok = false;
+  if ((rc = finish_check(st, pvk, bufs, key, 0, nullptr, nullptr, facc, qflags, &ok))) return rc;
+  return ok ? BH_OK : BH_ERR_INVALID_PROOF;
+}
+
+}  // extern "C"

@@ -4,6 +4,8 @@
 #include <string.h>
 
 #include "../../include/bellman_hip_test.h"
+#include "final_exp.cuh"
+#include "fp12.cuh"
 #include "msm_ec.cuh"
 #include "shard_cuts.hpp"
 
@@ -216,5 +218,97 @@ void bh_test_point_add_host(int group, void *r, const void *a, const void *b, si
 }
 void bh_test_point_mul_host(int group, void *r, const void *a, const void *k) {
   if (group == BH_G1) devhdr_point_mul_t<FpOps>(r, a, (const u32 *)k); else devhdr_point_mul_t<Fp2Ops>(r, a, (const u32 *)k);
+}
+}  // extern "C"
+
+// ---- test hook: full pairings (tests/test_gpu_verifier.py, tests/test_verifier_cpu.py) ------------------------------
+namespace bh {
+__global__ __launch_bounds__(64) void test_lines_kernel(const Affine<Fp2Ops> *q, line_t *lines, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<Fp2Ops> p = q[i];
+  if (aff_is_identity(p)) return;
+  line_t *out = lines + (size_t)i * MILLER_LINES;
+  g2_lines(p.x, p.y, [&](int k, const line_t &l) { out[k] = l; });
+}
+// one pairing per lane; out = 12 canonical Fp (not Montgomery) in w-basis order w^0, w^1 (each c0 then c1 of Fp2), ...
+BH_HD void pairing_one(fp12_t &r, const Affine<FpOps> &p, const Affine<Fp2Ops> &q, const line_t *lines) {
+  fp12_t f;
+  if (aff_is_identity(p) || aff_is_identity(q)) f12_one(f);
+  else miller_loop_lines(f, p.x, p.y, [&](int k) { return lines[k]; });
+  f12_final_exp(r, f);
+  f12_canon(r);
+}
+BH_HD void gt_store_canonical(fp_t *out, const fp12_t &r) {
+  for (int k = 0; k < 6; k++) {
+    fe_from_mont(out[2 * k], f12_w(r, k).c0);
+    fe_from_mont(out[2 * k + 1], f12_w(r, k).c1);
+  }
+}
+__global__ __launch_bounds__(64) void test_miller_kernel(const Affine<FpOps> *p, const Affine<Fp2Ops> *q, const line_t *lines,
+                                                         fp12_t *f, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<FpOps> pp = p[i];
+  fp12_t r;
+  if (aff_is_identity(pp) || aff_is_identity(q[i])) f12_one(r);
+  else {
+    const line_t *l = lines + (size_t)i * MILLER_LINES;
+    miller_loop_lines(r, pp.x, pp.y, [&](int k) { return l[k]; });
+  }
+  f[i] = r;
+}
+__global__ __launch_bounds__(64) void test_gt_store_kernel(const fp12_t *r, fp_t *out, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  gt_store_canonical(out + 12 * (size_t)i, r[i]);
+}
+}  // namespace bh
+
+extern "C" {
+int bh_test_pairing(bh_ctx *ctx, size_t n, const void *g1_affine, const void *g2_affine, void *gt_out) {
+  if (!ctx || (n && (!g1_affine || !g2_affine || !gt_out))) return BH_ERR_INVALID_ARG;
+  if (!n) return BH_OK;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  const size_t bl = n * MILLER_LINES * sizeof(line_t);
+  char *d = (char *)c.pool.acquire(n * 96 + n * 192 + n * 576 + bl + 5 * n * sizeof(fp12_t));
+  if (!d) return BH_ERR_HIP;
+  Affine<FpOps> *p = (Affine<FpOps> *)d;
+  Affine<Fp2Ops> *q = (Affine<Fp2Ops> *)(d + n * 96);
+  fp_t *out = (fp_t *)(d + n * 288);
+  line_t *lines = (line_t *)(d + n * 864);
+  int rc = BH_OK;
+  if (hipMemcpyAsync(p, g1_affine, n * 96, hipMemcpyHostToDevice, c.stream) != hipSuccess ||
+      hipMemcpyAsync(q, g2_affine, n * 192, hipMemcpyHostToDevice, c.stream) != hipSuccess)
+    rc = BH_ERR_HIP;
+  if (!rc) {
+    const u32 nb = (u32)((n + 63) / 64);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(test_lines_kernel, dim3(nb), dim3(64), 0, c.stream, q, lines, (u32)n);
+    fp12_t *f = (fp12_t *)(d + n * 864 + bl);
+    hipLaunchKernelGGL(test_miller_kernel, dim3(nb), dim3(64), 0, c.stream, p, q, lines, f, (u32)n);
+    if (hipGetLastError() != hipSuccess || !final_exp_chain(c.stream, f, f, nullptr, f + n, (u32)n)) rc = BH_ERR_HIP;
+    hipLaunchKernelGGL(test_gt_store_kernel, dim3(nb), dim3(64), 0, c.stream, f, out, (u32)n);
+    if (hipGetLastError() != hipSuccess) rc = BH_ERR_HIP;
+  }
+  if (!rc && hipMemcpyAsync(gt_out, out, n * 576, hipMemcpyDeviceToHost, c.stream) != hipSuccess) rc = BH_ERR_HIP;
+  if (hipStreamSynchronize(c.stream) != hipSuccess && !rc) rc = BH_ERR_HIP;
+  c.pool.release(d);
+  return rc;
+}
+// the same arithmetic compiled for the host (toolchain-only tests of fp12.cuh)
+void bh_test_pairing_host(size_t n, const void *g1_affine, const void *g2_affine, void *gt_out) {
+  std::vector<line_t> lines(MILLER_LINES);
+  for (size_t i = 0; i < n; i++) {
+    Affine<FpOps> p;
+    Affine<Fp2Ops> q;
+    memcpy(&p, (const char *)g1_affine + 96 * i, 96);
+    memcpy(&q, (const char *)g2_affine + 192 * i, 192);
+    if (!aff_is_identity(q)) g2_lines(q.x, q.y, [&](int k, const line_t &l) { lines[k] = l; });
+    fp12_t r;
+    pairing_one(r, p, q, lines.data());
+    gt_store_canonical((fp_t *)gt_out + 12 * i, r);
+  }
 }
 }  // extern "C"

@@ -60,3 +60,24 @@ def check(rc, what="bellman_hip call"):
     if rc == -3:
         raise BellmanHipError("%s: no gfx950 device available (no CPU fallback)" % what)
     raise BellmanHipError("%s failed with code %d" % (what, rc))
+
+
+class VerificationError(Exception):
+    """bellman::VerificationError (src/lib.rs:353-358)"""
+
+
+class InvalidVerifyingKey(VerificationError):
+    """the number of public inputs does not match the verifying key's ic (groth16/src/verifier.rs:27-29)"""
+
+
+class InvalidProof(VerificationError):
+    """the pairing equation does not hold (groth16/src/verifier.rs:55-57, verifier/batch.rs:186-190)"""
+
+
+def check_verification(rc, what="verification"):
+    """the return code of bh_groth16_verify / bh_groth16_batch_verify"""
+    if rc == 8:
+        raise InvalidVerifyingKey()
+    if rc == 9:
+        raise InvalidProof()
+    check(rc, what)

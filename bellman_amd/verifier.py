@@ -1,0 +1,129 @@
+"""groth16 verification on the device: prepare_verifying_key / verify_proof (groth16/src/verifier.rs:11-58) and
+batch::Verifier (groth16/src/verifier/batch.rs), over include/bellman_hip.h's bh_groth16_* verifier entry points.
+
+Public inputs and the batch's random z are Fr values given as Python ints (canonical; taken mod q).  Proofs are
+`groth16.Proof` objects (affine Montgomery records).  The pairing arithmetic runs in HIP kernels (csrc/pairing.hip);
+there is no CPU path.
+"""
+
+import ctypes
+import secrets
+
+import numpy as np
+
+from . import _lib
+from .errors import InvalidVerifyingKey, check, check_verification
+
+Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+_CANONICAL = 0
+
+
+def _fr_bytes(vals):
+    return b"".join((int(v) % Q).to_bytes(32, "little") for v in vals)
+
+
+def _proof_bytes(proof):
+    return np.concatenate([proof.a, proof.b, proof.c]).astype(np.uint64).tobytes()
+
+
+class PreparedVerifyingKey:
+    """groth16/src/lib.rs:400-409: the line coefficients of -gamma, -delta and beta in HBM, ic registered for the
+    multiexp of the public inputs."""
+
+    def __init__(self, worker, handle, n_inputs):
+        self.worker, self._h, self.n_inputs = worker, handle, n_inputs
+
+    @classmethod
+    def from_elements(cls, worker, alpha_g1, beta_g2, gamma_g2, delta_g2, ic):
+        lib = _lib.load()
+        arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (alpha_g1, beta_g2, gamma_g2, delta_g2)]
+        icv = np.ascontiguousarray(ic, dtype=np.uint64).reshape(-1, 12)
+        h = ctypes.c_void_p()
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib.bh_groth16_prepare_verifying_key(worker.ctx, *[p(x) for x in arrs], p(icv), icv.shape[0], ctypes.byref(h)),
+              "prepare_verifying_key")
+        return cls(worker, h, icv.shape[0] - 1)
+
+    def release(self):
+        """must run before the worker's context is destroyed (its device memory lives in the context's pool); after
+        that the handle is only dropped"""
+        if self._h:
+            if self.worker.ctx:
+                _lib.load().bh_groth16_pvk_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def prepare_verifying_key(params):
+    """prepare_verifying_key (groth16/src/verifier.rs:11-21) of generated or read `groth16.Parameters`"""
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    check(lib.bh_groth16_pvk_from_params(params._h, ctypes.byref(h)), "prepare_verifying_key")
+    return PreparedVerifyingKey(params.worker, h, lib.bh_groth16_pvk_num_inputs(h))
+
+
+def verify_proof(pvk, proof, public_inputs):
+    """verify_proof (groth16/src/verifier.rs:23-58): returns None, raises InvalidProof / InvalidVerifyingKey
+    (or InvalidPoint for a proof point that is not on its curve)"""
+    raw = _proof_bytes(proof)
+    ins = _fr_bytes(public_inputs)
+    check_verification(_lib.load().bh_groth16_verify(pvk._h, raw, ins or None, len(public_inputs), _CANONICAL), "verify_proof")
+
+
+class Item:
+    """batch::Item (groth16/src/verifier/batch.rs:37-66)"""
+
+    def __init__(self, proof, inputs):
+        self.proof, self.inputs = proof, list(inputs)
+
+    def verify_single(self, pvk):
+        return verify_proof(pvk, self.proof, self.inputs)
+
+
+class Verifier:
+    """batch::Verifier (groth16/src/verifier/batch.rs:68-275) for proofs of one verifying key"""
+
+    def __init__(self):
+        self.items = []
+
+    def queue(self, item):
+        """queue((proof, inputs)) or an Item"""
+        self.items.append(item if isinstance(item, Item) else Item(*item))
+
+    def _run(self, pvk, zs):
+        n_in = pvk.n_inputs
+        # the reference checks every item's input count before any work (batch.rs:101-107)
+        if any(len(it.inputs) != n_in for it in self.items):
+            raise InvalidVerifyingKey()
+        n = len(self.items)
+        proofs = b"".join(_proof_bytes(it.proof) for it in self.items)
+        ins = b"".join(_fr_bytes(it.inputs) for it in self.items)
+        z = _fr_bytes(zs)
+        check_verification(_lib.load().bh_groth16_batch_verify(pvk._h, proofs or None, n, ins or None, n_in, _CANONICAL,
+                                                               z or None), "batch verify")
+
+    def verify(self, rng, pvk):
+        """Verifier::verify(rng, vk) (batch.rs:93-192): z_j drawn from rng (randrange / getrandbits), redrawn while 0"""
+        zs = []
+        for _ in self.items:
+            z = 0
+            while z == 0:
+                z = rng.randrange(Q) if hasattr(rng, "randrange") else rng.getrandbits(256) % Q
+            zs.append(z)
+        return self._run(pvk, zs)
+
+    def verify_multicore(self, pvk):
+        """Verifier::verify_multicore(vk) (batch.rs:194-275): z_j from the operating system's CSPRNG"""
+        zs = []
+        for _ in self.items:
+            z = 0
+            while z == 0:
+                z = secrets.randbelow(Q)
+            zs.append(z)
+        return self._run(pvk, zs)
+

@@ -36,6 +36,8 @@ extern "C" {
 #define BH_ERR_UNCONSTRAINED_VARIABLE 5 /* SynthesisError::UnconstrainedVariable  groth16/src/generator.rs:464-470 */
 #define BH_ERR_INVALID_POINT 6       /* io::ErrorKind::InvalidData "invalid G1" / "invalid G2" groth16/src/lib.rs:300-304,326-330 */
 #define BH_ERR_POINT_AT_INFINITY 7   /* io::ErrorKind::InvalidData "point at infinity"         groth16/src/lib.rs:306-315,332-341 */
+#define BH_ERR_INVALID_VERIFYING_KEY 8 /* VerificationError::InvalidVerifyingKey  src/lib.rs:353-358 */
+#define BH_ERR_INVALID_PROOF 9       /* VerificationError::InvalidProof           src/lib.rs:353-358 */
 #define BH_ERR_HIP (-1)              /* HIP runtime failure (message on stderr) */
 #define BH_ERR_INVALID_ARG (-2)      /* the reference would panic (e.g. density length mismatch,
                                         src/multiexp.rs:324-329; length mismatch src/domain.rs:155,174) */
@@ -400,6 +402,36 @@ int bh_groth16_prove_assignment(bh_params *params, const void *a_evals, const vo
                                 const uint64_t *a_aux_density, const uint64_t *b_input_density,
                                 const uint64_t *b_aux_density, const void *r, const void *s,
                                 void *proof_out, float *timings4);
+/* ---- groth16 verification (groth16/src/verifier.rs, groth16/src/verifier/batch.rs) ---------------------------------
+ * bh_pvk = PreparedVerifyingKey (groth16/src/lib.rs:400-409): the Miller-loop line coefficients of -gamma, -delta and beta
+ * kept in HBM, and ic registered as multiexp bases.  Points are affine Montgomery records as everywhere in this header
+ * (identity = all zero); a proof is affine a | b | c (384 B), the layout bh_groth16_prove_* write.
+ *   bh_groth16_prepare_verifying_key  prepare_verifying_key (verifier.rs:11-21); n_ic >= 1.  BH_ERR_INVALID_POINT when
+ *                                     beta / gamma / delta is not on the curve.
+ *   bh_groth16_pvk_from_params        the same from the key elements of params made by bh_groth16_params_read or
+ *                                     bh_groth16_generate (BH_ERR_INVALID_ARG for params without gamma_g2 / ic).
+ *   bh_groth16_verify                 verify_proof (verifier.rs:23-58): BH_OK, BH_ERR_INVALID_PROOF, or first
+ *                                     BH_ERR_INVALID_VERIFYING_KEY when n_inputs + 1 != the length of ic.
+ *   bh_groth16_batch_verify           batch::Verifier::verify (batch.rs:93-192) over n_proofs proofs with n_inputs public
+ *                                     inputs each (inputs row-major, n_proofs x n_inputs) and the caller's random
+ *                                     z_j (n_proofs Fr from a CSPRNG, all nonzero: a z_j that is 0 mod q gives BH_ERR_INVALID_ARG).
+ *                                     An empty batch is BH_OK.  Runs in chunks of at most 16384 proofs and 256 MB of inputs (bounded
+ *                                     device workspace),
+ *                                     on its own stream: thread-safe and concurrent with other work on the context.
+ * scalar_fmt applies to inputs and z as for bh_msm_async.  The only point check made is the on-curve test of A, B and C
+ * (BH_ERR_INVALID_POINT, reported before BH_ERR_INVALID_PROOF); subgroup membership, which the reference's Proof::read
+ * guarantees through from_compressed, stays with the caller. */
+typedef struct bh_pvk bh_pvk;
+int bh_groth16_prepare_verifying_key(bh_ctx *ctx, const void *alpha_g1, const void *beta_g2, const void *gamma_g2,
+                                     const void *delta_g2, const void *ic, size_t n_ic, bh_pvk **out);
+int bh_groth16_pvk_from_params(const bh_params *p, bh_pvk **out);
+/* number of public inputs the key expects (ic length - 1) */
+size_t bh_groth16_pvk_num_inputs(const bh_pvk *pvk);
+int bh_groth16_verify(const bh_pvk *pvk, const void *proof, const void *inputs, size_t n_inputs, int scalar_fmt);
+int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
+                            int scalar_fmt, const void *z);
+/* before bh_ctx_destroy of the key's context (the key's device memory lives in the context's pool) */
+void bh_groth16_pvk_release(bh_pvk *pvk);
 /* ---- R1CS resident in HBM: constraint evaluation as sparse matrix x witness --------
  * The reference evaluates the A/B/C linear combinations of every constraint on one host thread
  * during synthesis (groth16/src/prover.rs:19-55 `eval`, :105-145 `enforce`).  The matrices are a

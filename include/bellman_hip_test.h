@@ -55,6 +55,11 @@ int bh_test_g2_k6_dev(bh_ctx *ctx, void *out_add_host, const void *a_dev, const 
 /* the same in the lane-pair form (csrc/fp2pair.cuh: schoolbook Fp2 products, one reduction per lane) */
 int bh_test_g2_pairs_dev(bh_ctx *ctx, void *out_add_host, void *out_madd_host, void *out_dbl_host, const void *a_dev,
                          const void *b_dev, size_t n);
+/* n independent pairings e(g1[i], g2[i]) (affine Montgomery records, identity = all zero), each written as 12 canonical
+ * (not Montgomery) 48-byte Fp values: the w^0 .. w^5 coefficients of Fp12 = Fp2[w]/(w^6 - (u + 1)), c0 then c1 of each.
+ * The value is f_{|x|,Q}(P)^(3 (p^12 - 1) / q) (csrc/fp12.cuh): oracle/pyref's pairing cubed. */
+int bh_test_pairing(bh_ctx *ctx, size_t n, const void *g1_affine, const void *g2_affine, void *gt_out);
+void bh_test_pairing_host(size_t n, const void *g1_affine, const void *g2_affine, void *gt_out);
 /* host-side (CPU) versions of the same arithmetic headers, for toolchain-only unit tests */
 void bh_test_fr_mul_host(void *r, const void *a, const void *b, size_t n);
 void bh_test_fp_mul_host(void *r, const void *a, const void *b, size_t n);

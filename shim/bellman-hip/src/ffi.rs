@@ -43,6 +43,11 @@ pub struct BhMsmShardedJob {
 pub struct BhProofJob {
     _private: [u8; 0],
 }
+/// opaque `bh_pvk`
+#[repr(C)]
+pub struct BhPvk {
+    _private: [u8; 0],
+}
 /// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -178,6 +183,12 @@ extern "C" {
     pub fn bh_proof_write(proof_affine: *const c_void, out192: *mut c_void);
     pub fn bh_groth16_params_release(p: *mut BhParams);
     pub fn bh_groth16_prove_assignment(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
+    pub fn bh_groth16_prepare_verifying_key(ctx: *mut BhCtx, alpha_g1: *const c_void, beta_g2: *const c_void, gamma_g2: *const c_void, delta_g2: *const c_void, ic: *const c_void, n_ic: usize, out: *mut *mut BhPvk) -> c_int;
+    pub fn bh_groth16_pvk_from_params(p: *const BhParams, out: *mut *mut BhPvk) -> c_int;
+    pub fn bh_groth16_pvk_num_inputs(pvk: *const BhPvk) -> usize;
+    pub fn bh_groth16_verify(pvk: *const BhPvk, proof: *const c_void, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int) -> c_int;
+    pub fn bh_groth16_batch_verify(pvk: *const BhPvk, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, z: *const c_void) -> c_int;
+    pub fn bh_groth16_pvk_release(pvk: *mut BhPvk);
     pub fn bh_r1cs_create(ctx: *mut BhCtx, n_inputs: usize, n_aux: usize, n_constraints: usize, abc: *const BhCsr, coeffs: *const c_void, n_coeffs: usize, out: *mut *mut BhR1cs) -> c_int;
     pub fn bh_r1cs_release(r: *mut BhR1cs);
     pub fn bh_r1cs_shape(r: *const BhR1cs, n_inputs: *mut usize, n_aux: *mut usize, n_constraints: *mut usize) -> c_int;

@@ -12,7 +12,8 @@ HEADER = os.path.join(ROOT, "include", "bellman_hip.h")
 OUT = os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")
 
 OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "bh_params": "BhParams", "bh_r1cs": "BhR1cs",
-          "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob"}
+          "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
+          "bh_pvk": "BhPvk"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo"}
 SCALAR = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "uint32_t": "u32", "uint64_t": "u64",
