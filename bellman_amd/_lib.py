@@ -29,7 +29,8 @@ EXPORTS = [
     "bh_dev_alloc", "bh_dev_free", "bh_dev_upload", "bh_dev_download", "bh_dev_zero", "bh_stream_create", "bh_stream_create_priority", "bh_stream_destroy", "bh_stream_synchronize", "bh_dev_upload_on",
     "bh_dev_zero_on", "bh_ctx_synchronize", "bh_ctx_accumulations_after", "bh_ctx_trim",
     "bh_fft_fr", "bh_fft_fr_dev", "bh_fr_mul_assign_dev", "bh_fr_sub_assign_dev",
-    "bh_fr_divide_by_z_on_coset_dev", "bh_fr_distribute_powers_dev", "bh_h_poly_fr", "bh_h_poly_fr_dev", "bh_h_poly_fr_dev_on",
+    "bh_fr_divide_by_z_on_coset_dev", "bh_fr_distribute_powers_dev", "bh_fft_point_dev", "bh_point_distribute_powers_dev", "bh_point_divide_by_z_on_coset_dev",
+    "bh_point_mul_assign_dev", "bh_point_sub_assign_dev", "bh_h_poly_fr", "bh_h_poly_fr_dev", "bh_h_poly_fr_dev_on",
     "bh_bases_register", "bh_bases_register_uncompressed", "bh_bases_read_uncompressed", "bh_bases_download", "bh_bases_write_uncompressed", "bh_bases_copy_dev", "bh_bases_precompute", "bh_bases_table_info", "bh_bases_wrap_dev", "bh_bases_release", "bh_bases_len",
     "bh_msm_async", "bh_msm_async_dev", "bh_msm_wait", "bh_msm_wait_timed", "bh_msm_wait_profile", "bh_msm_wait_stats", "bh_msm_plan_info", "bh_msm_debug_stages", "bh_point_add", "bh_point_mul", "bh_point_lincomb", "bh_msm_async_opts", "bh_msm_async_dev_opts",
     "bh_scalars_register", "bh_scalars_adopt_dev", "bh_scalars_release", "bh_scalars_len", "bh_scalars_dev_ptr", "bh_msm_async_scalars", "bh_h_poly_fr_scalars", "bh_msm_async_dev_after", "bh_msm_start",
@@ -159,6 +160,11 @@ def load():
     lib.bh_fr_sub_assign_dev.argtypes = [vp, vp, vp, sz, vp]
     lib.bh_fr_divide_by_z_on_coset_dev.argtypes = [vp, vp, u32, vp]
     lib.bh_fr_distribute_powers_dev.argtypes = [vp, vp, sz, vp, vp]
+    lib.bh_fft_point_dev.argtypes = [vp, i32, vp, u32, i32, vp]
+    lib.bh_point_distribute_powers_dev.argtypes = [vp, i32, vp, sz, vp, vp]
+    lib.bh_point_divide_by_z_on_coset_dev.argtypes = [vp, i32, vp, u32, vp]
+    lib.bh_point_mul_assign_dev.argtypes = [vp, i32, vp, vp, sz, vp]
+    lib.bh_point_sub_assign_dev.argtypes = [vp, i32, vp, vp, sz, vp]
     lib.bh_h_poly_fr.argtypes = [vp, vp, vp, vp, sz, vp, c.POINTER(sz)]
     lib.bh_h_poly_fr_dev.argtypes = [vp, vp, vp, vp, u32, vp]
     lib.bh_h_poly_fr_dev_on.argtypes = [vp, vp, vp, vp, vp, u32, vp]

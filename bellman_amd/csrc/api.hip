@@ -20,6 +20,12 @@ int fr_divide_by_z(Context &c, fr_t *a, uint32_t log_n, hipStream_t st);
 int fr_distribute_powers(Context &c, fr_t *a, u64 n, const fr_t &g, hipStream_t st);
 int h_poly_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, fr_t *scratch, uint32_t log_n, hipStream_t st);
 int fr_gen_powers(Context &c, fr_t *out, u64 n, const fr_t &g, const fr_t &scale, hipStream_t st);
+// point_fft.hip
+int point_fft(Context &c, int group, void *pts, uint32_t log_n, int mode, hipStream_t st);
+int point_distribute_powers(Context &c, int group, void *pts, u64 n, const fr_t &g, hipStream_t st);
+int point_divide_by_z(int group, void *pts, uint32_t log_n, hipStream_t st);
+int point_mul_assign(int group, void *pts, const void *scalars_mont, u64 n, hipStream_t st);
+int point_sub_assign(int group, void *a, const void *b, u64 n, hipStream_t st);
 // msm.hip
 struct MsmJobImpl;
 MsmJobImpl *msm_job_new(Context *ctx, int group);
@@ -639,6 +645,40 @@ int bh_fr_distribute_powers_dev(bh_ctx *ctx, void *a, size_t n, const void *g_ho
   fr_t g;
   memcpy(&g, g_host, sizeof g);
   return fr_distribute_powers(ctx->c, (fr_t *)a, n, g, pick_stream(ctx, stream));
+}
+// ---- EvaluationDomain<Fr, Point<G>> (point_fft.hip) ----------------------------------------------
+static bool group_ok(int group) { return group == BH_G1 || group == BH_G2; }
+int bh_fft_point_dev(bh_ctx *ctx, int group, void *points_dev, uint32_t log_n, int mode, void *stream) {
+  if (log_n >= 32) return BH_ERR_DEGREE_TOO_LARGE;
+  if (!ctx || !group_ok(group) || mode < 0 || mode > 3 || !points_dev) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  return point_fft(ctx->c, group, points_dev, log_n, mode, pick_stream(ctx, stream));
+}
+int bh_point_distribute_powers_dev(bh_ctx *ctx, int group, void *points_dev, size_t n, const void *g_host, void *stream) {
+  if (!ctx || !group_ok(group) || !g_host) return BH_ERR_INVALID_ARG;
+  if (!n) return BH_OK;
+  fr_t g;
+  memcpy(&g, g_host, sizeof g);
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  return point_distribute_powers(ctx->c, group, points_dev, n, g, pick_stream(ctx, stream));
+}
+int bh_point_divide_by_z_on_coset_dev(bh_ctx *ctx, int group, void *points_dev, uint32_t log_n, void *stream) {
+  if (log_n >= 32) return BH_ERR_DEGREE_TOO_LARGE;
+  if (!ctx || !group_ok(group) || !points_dev) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  return point_divide_by_z(group, points_dev, log_n, pick_stream(ctx, stream));
+}
+int bh_point_mul_assign_dev(bh_ctx *ctx, int group, void *points_dev, const void *scalars_dev, size_t n, void *stream) {
+  if (!ctx || !group_ok(group)) return BH_ERR_INVALID_ARG;
+  if (!n) return BH_OK;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  return point_mul_assign(group, points_dev, scalars_dev, n, pick_stream(ctx, stream));
+}
+int bh_point_sub_assign_dev(bh_ctx *ctx, int group, void *a_dev, const void *b_dev, size_t n, void *stream) {
+  if (!ctx || !group_ok(group)) return BH_ERR_INVALID_ARG;
+  if (!n) return BH_OK;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  return point_sub_assign(group, a_dev, b_dev, n, pick_stream(ctx, stream));
 }
 int bh_fr_powers_dev(bh_ctx *ctx, void *out, size_t n, const void *g_host, const void *scale_host, void *stream) {
   fr_t g, sc;

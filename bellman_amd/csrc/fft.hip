@@ -609,7 +609,7 @@ __global__ void fr_quotient_kernel(fr_t *a, const fr_t *b, const fr_t *c, fr_t z
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static fr_t fr_from_u64_host(u64 v) {
+fr_t fr_from_u64_host(u64 v) {   // (also point_fft.hip)
   fr_t c;
   fe_zero(c);
   c.l[0] = (u32)v;
@@ -638,7 +638,7 @@ static fr_t fr_pow_u64_host(const fr_t &a, u64 e) {
   return r;
 }
 
-static fr_t zinv_host(uint32_t log_n) {  // domain.rs:129-140: (7^m - 1)^-1
+fr_t zinv_host(uint32_t log_n) {  // domain.rs:129-140: (7^m - 1)^-1 (also point_fft.hip)
   fr_t g = fr_from_u64_host(7), z = fr_pow_u64_host(g, (u64)1 << log_n), one, zi;
   fe_one(one);
   fe_sub(z, z, one);
@@ -653,7 +653,8 @@ static PowTable make_pow_table(const fr_t &g, const fr_t &scale) {
   tab.scale = scale;
   return tab;
 }
-static int launch_gen_powers(fr_t *out, u64 n, const fr_t &g, const fr_t &scale, int mul_into, hipStream_t st) {
+// (also the twiddles and coset powers of point_fft.hip)
+int launch_gen_powers(fr_t *out, u64 n, const fr_t &g, const fr_t &scale, int mul_into, hipStream_t st) {
   const PowTable tab = make_pow_table(g, scale);
   u64 threads = (n + 15) / 16;
   u32 blocks = (u32)((threads + 255) / 256);

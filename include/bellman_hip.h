@@ -147,6 +147,18 @@ int bh_fr_mul_assign_dev(bh_ctx *ctx, void *a_dev, const void *b_dev, size_t n, 
 int bh_fr_sub_assign_dev(bh_ctx *ctx, void *a_dev, const void *b_dev, size_t n, void *stream);
 int bh_fr_divide_by_z_on_coset_dev(bh_ctx *ctx, void *a_dev, uint32_t log_n, void *stream);
 int bh_fr_distribute_powers_dev(bh_ctx *ctx, void *a_dev, size_t n, const void *g_host, void *stream);
+/* EvaluationDomain<Fr, Point<G>> (src/domain.rs:192-229 with the methods of :21-190): the same operations on device
+ * vectors of affine G1 / G2 records (group = BH_G1 / BH_G2; Montgomery, identity = all-zero record), in place on `stream`
+ * (NULL = context stream).  The ifft of [tau^i]G from a powers-of-tau transcript gives the Lagrange-basis points
+ * [L_j(tau)]G.  Scalars and g_host are Montgomery Fr as above.  The points are NOT validated (a Point<G> holds a group
+ * element by type): records that are not on the curve give meaningless records.  bh_fft_point_dev and
+ * bh_point_distribute_powers_dev take pool workspace and wait for the stream before they return; the other three only
+ * enqueue.  log_n >= 32 -> BH_ERR_DEGREE_TOO_LARGE, a bad group or mode -> BH_ERR_INVALID_ARG, n = 0 does nothing. */
+int bh_fft_point_dev(bh_ctx *ctx, int group, void *points_dev, uint32_t log_n, int mode, void *stream);   /* BH_FFT..BH_ICOSET_FFT */
+int bh_point_distribute_powers_dev(bh_ctx *ctx, int group, void *points_dev, size_t n, const void *g_host, void *stream);
+int bh_point_divide_by_z_on_coset_dev(bh_ctx *ctx, int group, void *points_dev, uint32_t log_n, void *stream);
+int bh_point_mul_assign_dev(bh_ctx *ctx, int group, void *points_dev, const void *scalars_dev, size_t n, void *stream);
+int bh_point_sub_assign_dev(bh_ctx *ctx, int group, void *a_dev, const void *b_dev, size_t n, void *stream);
 /* The whole h-polynomial block of create_proof (groth16/src/prover.rs:221-240), fused:
  * a,b,c = n_evals constraint evaluations each (Montgomery Fr, HOST); writes the m-1 quotient
  * coefficients (m = next pow2 >= n_evals, :238-239) to h_out_host (Montgomery) and returns

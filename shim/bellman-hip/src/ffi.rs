@@ -134,6 +134,11 @@ extern "C" {
     pub fn bh_fr_sub_assign_dev(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn bh_fr_divide_by_z_on_coset_dev(ctx: *mut BhCtx, a_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
     pub fn bh_fr_distribute_powers_dev(ctx: *mut BhCtx, a_dev: *mut c_void, n: usize, g_host: *const c_void, stream: *mut c_void) -> c_int;
+    pub fn bh_fft_point_dev(ctx: *mut BhCtx, group: c_int, points_dev: *mut c_void, log_n: u32, mode: c_int, stream: *mut c_void) -> c_int;
+    pub fn bh_point_distribute_powers_dev(ctx: *mut BhCtx, group: c_int, points_dev: *mut c_void, n: usize, g_host: *const c_void, stream: *mut c_void) -> c_int;
+    pub fn bh_point_divide_by_z_on_coset_dev(ctx: *mut BhCtx, group: c_int, points_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
+    pub fn bh_point_mul_assign_dev(ctx: *mut BhCtx, group: c_int, points_dev: *mut c_void, scalars_dev: *const c_void, n: usize, stream: *mut c_void) -> c_int;
+    pub fn bh_point_sub_assign_dev(ctx: *mut BhCtx, group: c_int, a_dev: *mut c_void, b_dev: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn bh_h_poly_fr(ctx: *mut BhCtx, a_host: *const c_void, b_host: *const c_void, c_host: *const c_void, n_evals: usize, h_out_host: *mut c_void, h_len: *mut usize) -> c_int;
     pub fn bh_h_poly_fr_dev(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
     pub fn bh_h_poly_fr_dev_on(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, scratch_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
