@@ -166,7 +166,7 @@ struct bh_bases {
   // 96-byte record at a 96-byte stride straddles two lines half of the time).  profiles/archive/r4_call11_padded_bases.txt:
   // FETCH_SIZE of the accumulate launch 2.20 -> 1.58 GB at 2^20; accumulate -1 % at 2^20 (the table sits in the
   // Infinity Cache either way), -3 % at 2^22 (it does not).  Dense `dev` stays what every other path and the API see.
-  // BELLMAN_HIP_BASE_PAD=0 switches it off; vectors whose copy would exceed 1/16 of the device memory are not padded.
+  // Vectors whose copy would exceed 1/16 of the device memory are not padded.
   void *padded = nullptr;
   // [r4] ... and the window table of a G1 vector too large for the Infinity Cache (>= 2^19 points: 16 rows of 2^19
   // records are 0.8 GB) is KEPT at that stride only: `table` then holds W * n records of 128 bytes, read by the bucket
@@ -224,18 +224,7 @@ static int finish_bases(bh_ctx *ctx, bh_bases *b) {
 // 20.7), twelve proof threads 37-40 vs 43-45 proofs/s.  A caller whose multiexps run one at a time can opt in with
 // BELLMAN_HIP_TABLE_MAX_LOG2_G1=22 (or bh_bases_precompute).
 static unsigned auto_table_max_log2(int group) {
-  static const int v = [] {
-    const char *e = getenv("BELLMAN_HIP_TABLE_MAX_LOG2");
-    if (!e || !*e) return -1;
-    const long x = strtol(e, nullptr, 10);
-    return (int)(x < 0 ? 0 : x > 24 ? 24 : x);
-  }();
-  static const int v1 = [] {
-    const char *e = getenv("BELLMAN_HIP_TABLE_MAX_LOG2_G1");
-    if (!e || !*e) return -1;
-    const long x = strtol(e, nullptr, 10);
-    return (int)(x < 0 ? 0 : x > 24 ? 24 : x);
-  }();
+  const int v = env().table_max_log2, v1 = env().table_max_log2_g1;
   if (group == BH_G1 && v1 >= 0) return (unsigned)v1;
   // [r6] G1: up to 2^24 points (it was 2^18): a 13-row table at a 128-byte stride is 1.7 GB per 2^20 points, built in 0.13 s;
   // 2^23 24.6 -> 21.4 ms, 2^24 44.6 -> 40.5 (profiles/r6_call44_g1_tables_2p23_2p24.txt).  Always within the context's table
@@ -245,8 +234,7 @@ static unsigned auto_table_max_log2(int group) {
 // G1 tables of 2^19 points and more are stored at a 128-byte record stride (bh_bases::table_padded);
 // BELLMAN_HIP_TABLE_PAD=0 keeps them dense
 static bool table_will_pad(const bh_bases *b) {
-  static const bool on = [] { const char *e = getenv("BELLMAN_HIP_TABLE_PAD"); return !(e && *e == '0'); }();
-  return on && b->group == BH_G1 && b->n >= ((size_t)1 << 19);
+  return env().table_pad && b->group == BH_G1 && b->n >= ((size_t)1 << 19);
 }
 static size_t table_bytes_for(const bh_bases *b, unsigned c) {
   const u32 W = (256 + c - 1) / c;
@@ -269,7 +257,6 @@ static int new_bases(bh_ctx *ctx, int group, void *dev, size_t n, bool owned, bh
   // automatic window table: only while all automatic tables of the context stay within its budget (default a
   // quarter of the device's memory, BELLMAN_HIP_TABLE_BUDGET_MB / bh_ctx_set_limits): a table is 13-32 x its base
   // vector (2^22 G2 points: 12.9 GB) and must not starve the per-proof workspaces
-  static const bool pad_on = [] { const char *e = getenv("BELLMAN_HIP_BASE_PAD"); return !(e && *e == '0'); }();
   const unsigned lg_table = auto_table_max_log2(group);
   const bool table_size = lg_table && n > TINY_MSM_MAX && n <= (size_t(1) << lg_table);   // (takes a window table instead)
   if (table_size) {
@@ -295,7 +282,7 @@ static int new_bases(bh_ctx *ctx, int group, void *dev, size_t n, bool owned, bh
   }
   // (a vector that got its window table gathers from the table; one that did not - too large, or over the table budget - gets the
   // 128-byte-stride copy of its points for the classic plan's gathers)
-  if (pad_on && group == BH_G1 && !b->table && n >= ((size_t)1 << 17) && n < ((size_t)1 << 31) &&
+  if (group == BH_G1 && !b->table && n >= ((size_t)1 << 17) && n < ((size_t)1 << 31) &&
       (ctx->c.hbm_total == 0 || n * 128 <= ctx->c.hbm_total / 16)) {
     if (hipMalloc(&b->padded, n * 128) == hipSuccess) {
       if (hipMemcpy2DAsync(b->padded, 128, dev, 96, 96, n, hipMemcpyDeviceToDevice, ctx->c.stream) != hipSuccess ||
@@ -328,16 +315,14 @@ static std::atomic<bool> g_hip_touched{false};      // this library has made a H
 static std::atomic<bool> g_configured_early{false};
 int bh_runtime_configure(void) {
   const bool early = !g_hip_touched.load();
-  const char *cur = getenv("GPU_MAX_HW_QUEUES");
-  if (!cur || !*cur) setenv("GPU_MAX_HW_QUEUES", "16", 0);
+  setenv("GPU_MAX_HW_QUEUES", "16", 0);   // (no overwrite: a value the caller chose stays)
   if (early) g_configured_early.store(true);
   return early ? 1 : 0;
 }
 
 int bh_ctx_create(int device, bh_ctx **out) {
   int count = 0;
-  const char *q = getenv("GPU_MAX_HW_QUEUES");
-  const int queues_env = (q && *q) ? atoi(q) : 0;
+  const int queues_env = env_hw_queues();
   const bool early = g_configured_early.load() || (!g_hip_touched.load() && queues_env > 0);
   g_hip_touched.store(true);
   if (hipGetDeviceCount(&count) != hipSuccess || count <= device || device < 0) return BH_ERR_NO_DEVICE;
@@ -354,21 +339,14 @@ int bh_ctx_create(int device, bh_ctx **out) {
   // jobs in flight per context: a 2^20-term multiexp holds ~0.6 GB of workspace - by default as many as fit a
   // quarter of the device's memory at that size, at least 8 (create_proof issues 8, prover.rs:244-318)
   {
-    const char *e = getenv("BELLMAN_HIP_MAX_JOBS");
-    long v = e && *e ? strtol(e, nullptr, 10) : 0;
+    long v = env().max_jobs;
     if (v <= 0) v = (long)(ctx->c.hbm_total / 4 / (size_t(640) << 20));
     ctx->c.max_jobs = (uint32_t)(v < 8 ? 8 : v > 4096 ? 4096 : v);
   }
-  {
-    const char *e = getenv("BELLMAN_HIP_TABLE_BUDGET_MB");
-    ctx->c.table_budget = (e && *e) ? (size_t)strtoull(e, nullptr, 10) << 20 : ctx->c.hbm_total / 4;
-    const char *ef = getenv("BELLMAN_HIP_FFT_TABLE_BUDGET_MB");
-    ctx->c.fft_table_budget = (ef && *ef) ? (size_t)strtoull(ef, nullptr, 10) << 20 : ctx->c.hbm_total / 8;
-  }
-  {
-    const char *e = getenv("BELLMAN_HIP_POOL_CAP_MB");
-    if (e && *e) ctx->c.pool.set_cap((size_t)strtoull(e, nullptr, 10) << 20);
-  }
+  const EnvSettings &e = env();
+  ctx->c.table_budget = e.table_budget != EnvSettings::UNSET ? e.table_budget : ctx->c.hbm_total / 4;
+  ctx->c.fft_table_budget = e.fft_table_budget != EnvSettings::UNSET ? e.fft_table_budget : ctx->c.hbm_total / 8;
+  if (e.pool_cap != EnvSettings::UNSET) ctx->c.pool.set_cap(e.pool_cap);
   Context *cp = &ctx->c;
   ctx->c.pool.set_pressure_handler([cp] { return msm_complete_oldest(*cp); });
   BH_HIP_CHECK(hipStreamCreateWithFlags(&ctx->c.stream, hipStreamNonBlocking));
@@ -465,8 +443,6 @@ void bh_ctx_destroy(bh_ctx *ctx) {
     if (r.acc_event) (void)hipEventDestroy(r.acc_event);
     if (r.sort_event) (void)hipEventDestroy(r.sort_event);
     if (r.pinned) (void)hipHostFree(r.pinned);
-    if (r.hp_event) (void)hipEventDestroy(r.hp_event);
-    if (r.hp_stream) (void)hipStreamDestroy(r.hp_stream);
     if (r.stream) (void)hipStreamDestroy(r.stream);
   }
   ctx->c.job_pool.clear();

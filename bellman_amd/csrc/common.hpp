@@ -15,6 +15,7 @@
 #include "../../include/bellman_hip.h"
 struct bh_bases;
 #include "ec.cuh"
+#include "env_settings.hpp"
 #include "ff.cuh"
 
 namespace bh {
@@ -121,10 +122,8 @@ class DevicePool {
 struct JobResources {
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  // optional (BELLMAN_HIP_REDUCE_PRIORITY=1): the latency-bound merge / reduction kernels of the job on a
-  // high-priority stream, ordered after the accumulation by an event
-  hipStream_t hp_stream = nullptr;
-  hipEvent_t hp_event = nullptr;
+  // (a second, high-priority stream for the job's latency-bound merge / reduction kernels was measured and did not help:
+  // 78.9 against 81.9 ms per 2^20 proof, profiles/archive/r2_call11_reduce_priority_ab.txt)
   hipEvent_t sort_event = nullptr; // lazily created: end of the digit / sort stage of a held job (BH_MSM_HOLD)
   hipEvent_t acc_event = nullptr;  // lazily created: recorded after the job's bucket accumulation launch (the accumulation chain)
   hipEvent_t dep_event = nullptr;  // lazily created: orders the job after another stream (bh_msm_async_dev_after)
@@ -191,7 +190,7 @@ struct Context {
   // (each waits for the previous one's event) instead of sharing the SIMDs - two of them side by side take twice as
   // long each, so every job of a proof would finish late and all the latency-bound merge / reduction tails would pile up
   // at the end with the chip idle (profiles/archive/r3_call3_proof_timeline.txt).  Chained, job k's tail runs beside job k+1's
-  // accumulation.  BELLMAN_HIP_ACC_CHAIN=0 switches it off.
+  // accumulation.
   std::mutex acc_mu;
   hipEvent_t last_acc_event = nullptr;
   std::vector<hipEvent_t> barrier_events;   // events of bh_ctx_accumulations_after (a ring, recycled round robin)

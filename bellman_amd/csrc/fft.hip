@@ -116,12 +116,6 @@ __device__ __forceinline__ constexpr u32 fr_mod2(int i) {   // limb i of 2q
   return (FrParams::mod(i) << 1) | (i ? FrParams::mod(i - 1) >> 31 : 0u);
 }
 __device__ __forceinline__ void frl_add(fr_t &r, const fr_t &a, const fr_t &b) {   // a + b < 4q: bit 256 is the carry
-#ifdef BH_DIAG_CHEAP_ADDSUB   // TIMING-ONLY diagnostic build: carry-free limb-wise additions (wrong results)
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.l[i] = a.l[i] + b.l[i];
-  r.l[0] += a.l[7] >> 3;   // (a ninth limb's worth)
-  return;
-#endif
   u32 t[8], d[8];
   u32 c = 0, br = 0;
 #pragma unroll
@@ -133,12 +127,6 @@ __device__ __forceinline__ void frl_add(fr_t &r, const fr_t &a, const fr_t &b) {
   for (int i = 0; i < 8; i++) r.l[i] = ge ? d[i] : t[i];
 }
 __device__ __forceinline__ void frl_sub(fr_t &r, const fr_t &a, const fr_t &b) {
-#ifdef BH_DIAG_CHEAP_ADDSUB   // ... and subtractions with a per-limb bias
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.l[i] = a.l[i] + fr_mod2(i) - b.l[i];
-  r.l[0] += (a.l[7] + fr_mod2(0) - b.l[7]) >> 3;
-  return;
-#endif
   u32 t[8];
   u32 br = 0, c = 0;
 #pragma unroll
@@ -738,9 +726,8 @@ static int get_tables(Context &c, uint32_t log_n, bool inverse, bool need_tw, bo
   // budget - so that dropping the other sizes always makes room for whichever of its tables is asked for next, and the
   // kind of tables a size uses never changes while it is cached (the inverse twiddle table carries the 1/n: the two kinds
   // are never mixed within a size).  A size that holds two-level tables (over budget, a failed allocation) keeps them.
-  static const bool one_level_on = [] { const char *e = getenv("BELLMAN_HIP_FFT_ONE_LEVEL"); return !(e && *e == '0'); }();
   const bool has_two_level = t.tw_lo[0] || t.tw_lo[1] || t.coset_lo || t.icoset_lo;
-  bool one_level = one_level_on && log_n >= 12 && log_n <= 24 && !t.one_level_failed && !has_two_level &&
+  bool one_level = env().fft_one_level && log_n >= 12 && log_n <= 24 && !t.one_level_failed && !has_two_level &&
                    (t.one_level || one_level_set_bytes(log_n, pL) <= c.fft_table_budget);
   const size_t entry_bytes = (size_t)NTT_ONE_STRIDE << log_n;
   const size_t others = c.fft_table_bytes - (it != c.fft_tables.end() ? it->second.bytes : 0);

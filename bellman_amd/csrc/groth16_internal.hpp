@@ -8,9 +8,10 @@
 #include <memory>
 #include <stdexcept>
 
+#include "env_settings.hpp"
 #include "groth16.hpp"
 
-#define BH_TRACE(...) do { if (getenv("BH_DEBUG")) { fprintf(stderr, "[groth16 %.2f ms] ", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count()); fprintf(stderr, __VA_ARGS__); fputc(10, stderr); fflush(stderr); } } while (0)
+#define BH_TRACE(...) do { if (bh::env().debug) { fprintf(stderr, "[groth16 %.2f ms] ", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count()); fprintf(stderr, __VA_ARGS__); fputc(10, stderr); fflush(stderr); } } while (0)
 
 namespace groth16 {
 namespace detail {

@@ -140,13 +140,10 @@ namespace {
 struct ProofStream {   // uploads + h block of one proof; independent of other proofs in flight
   bh_ctx *ctx;
   void *st = nullptr;
-  // the h block is a short dependent chain on the proof's critical path (the H multiexp waits for it).
-  // BELLMAN_HIP_H_PRIORITY=1 puts it on a high-priority stream; measured: no gain for one proof and 8 % less throughput
-  // with twelve proofs in flight (profiles/archive/r3_call3_oversub.txt), so it is off by default
-  explicit ProofStream(bh_ctx *c) : ctx(c) {
-    static const bool high = [] { const char *e = getenv("BELLMAN_HIP_H_PRIORITY"); return e && *e == '1'; }();
-    check(bh_stream_create_priority(ctx, high ? 1 : 0, &st));
-  }
+  // the h block is a short dependent chain on the proof's critical path (the H multiexp waits for it).  A high-priority
+  // stream for it was measured: no gain for one proof and 8 % less throughput with twelve proofs in flight
+  // (profiles/archive/r3_call3_oversub.txt)
+  explicit ProofStream(bh_ctx *c) : ctx(c) { check(bh_stream_create_priority(ctx, 0, &st)); }
   ~ProofStream() { if (st) { (void)bh_stream_synchronize(ctx, st); (void)bh_stream_destroy(ctx, st); } }
   ProofStream(const ProofStream &) = delete;
 };
@@ -290,13 +287,9 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
   // skipped scalars would have consumed (all of them without a density map, the set bits with one)
   DevBuf dscratch(ctx, log_m > 11 ? m * 32 : 32);   // FFT ping-pong vector of the h block
   StreamDrain drain2{ps};                            // (drains before dscratch is released)
-  // Optional two-phase issue (BH_MSM_HOLD / bh_msm_start, BELLMAN_HIP_PROOF_HOLD=1): first every job's digit + sort
-  // stage, then the bucket accumulations in chain order.  Measured (profiles/archive/r3_call6_hold_ab.txt): no gain for one proof
-  // - the accumulations are as slow with nothing beside them, 6.35 ms for G2 against 5.46 in a warm back-to-back loop:
-  // the chip has just left idle clocks after the host's 51 ms of witness generation - and 12 % less throughput with
-  // twelve proofs in flight (the sorts of one proof no longer fill the gaps of another).  Off by default.
-  static const bool hold_env = [] { const char *e = getenv("BELLMAN_HIP_PROOF_HOLD"); return e && *e == '1'; }();
-  const bool hold_jobs = hold_env && log_m > 16;
+  // (A two-phase issue - BH_MSM_HOLD / bh_msm_start: first every job's digit + sort stage, then the bucket accumulations in
+  // chain order - was measured for proofs above 2^16 and is not used: no gain for one proof and 12 % less throughput with
+  // twelve in flight, the sorts of one proof no longer fill the gaps of another; profiles/archive/r3_call6_hold_ab.txt.)
   auto issue = [&](bh_bases *bases, size_t skip, const void *scalars, size_t n, const uint64_t *dens_dev,
                    const uint64_t *dens_host, bh_msm_job **job, const void *scalars_host = nullptr) {
     const Slice sl = slice_of(n, part, parts);
@@ -309,9 +302,8 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
       BH_TRACE("  multiexp of %zu terms answered on the host", sl.hi - sl.lo);
       return;
     }
-    const bh_msm_opts held = {0, 0, hold_jobs ? BH_MSM_HOLD : 0u};
-    check(bh_msm_async_dev_opts(ctx, bases, base_skip, (const char *)scalars + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT,
-                                dens_dev ? dens_dev + sl.lo / 64 : nullptr, dens_dev ? sl.hi - sl.lo : 0, &held, job));
+    check(bh_msm_async_dev(ctx, bases, base_skip, (const char *)scalars + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT,
+                           dens_dev ? dens_dev + sl.lo / 64 : nullptr, dens_dev ? sl.hi - sl.lo : 0, job));
     BH_TRACE("  multiexp of %zu terms issued", sl.hi - sl.lo);
   };
   auto issue_seven = [&](bool longest_first) {
@@ -379,9 +371,8 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
     // host stages a, b, c (96 MiB of pageable memory at 2^20).
     auto issue_h = [&] {
       const Slice sl = slice_of(m - 1, part, parts);   // a.len() - 1, :238-244
-      const bh_msm_opts held = {0, 0, hold_jobs ? BH_MSM_HOLD : 0u};
       check(bh_msm_async_dev_after(ctx, params.h, sl.lo, (const char *)da.p + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT, nullptr,
-                                   0, &held, ps.st, &h_job));
+                                   0, nullptr, ps.st, &h_job));
     };
     // Issue order = order of the bucket accumulations on the device (the accumulation chain, common.hpp): the G2
     // multiexp first - the longest job, its reduction tail then runs beside the G1 accumulations - and H last, by which
@@ -395,8 +386,6 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
     issue_seven(true);
     if (src.host) enqueue_h_block();
     issue_h();
-    if (hold_jobs)   // second phase, in chain order
-      for (bh_msm_job *j : {b2_aux_job, l_job, a_aux_job, b1_aux_job, h_job, a_in_job, b1_in_job, b2_in_job}) check(bh_msm_start(j));
     BH_TRACE("7 multiexps + h block + H issued; n_cons=%zu m=%zu", n_cons, m);
     t1 = now_ms();
   }

@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <type_traits>
 #include <vector>
-#include <array>
 #include <cmath>
 
 #include "fp2pair.cuh"
@@ -1080,18 +1079,6 @@ __global__ __launch_bounds__(LONG_THREADS) void msm_merge_tail_kernel(XYZZ<typen
   }
 }
 
-// Resident wavefronts per SIMD the lane cost model assumes for the reduction kernels: [0] G1, [1] G2 one lane per
-// point, [2] G2 lane triples.  One each: a second resident wavefront does NOT interleave for free in these mad-bound
-// chains (profiles/archive/r2_call8_slots.txt: G1 2^17-2^20 reduce 0.73-0.99 ms with 1, 0.92-1.19 ms with 2; G2 within noise).
-// BELLMAN_HIP_SUM_SLOTS="a,b,c" overrides for sweeps.
-inline double sum_slot_factor(int kind) {
-  static const std::array<double, 3> f = [] {
-    std::array<double, 3> v = {1.0, 1.0, 1.0};
-    if (const char *e = getenv("BELLMAN_HIP_SUM_SLOTS")) sscanf(e, "%lf,%lf,%lf", &v[0], &v[1], &v[2]);
-    return v;
-  }();
-  return f[kind];
-}
 // ============================================================================================
 // fixed-base scalar multiplication (fixture generation) and test hooks
 // ============================================================================================
@@ -1268,9 +1255,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // much longer than that (window tables over tiny vectors: 32 n entries in 128 buckets, chunks of 8) more workers
   // shorten the chain as long as the launch still fits the chip
   // [r6] G1: the same on lane PAIRS (K2: half the latency of an addition for twice the lanes) when that is cheaper by
-  // the same model - levels x latency of a level x how far the launch overfills the chip.  BELLMAN_HIP_LONG_K2=0: one lane
-  // per point everywhere (A/B)
-  static const bool long_k2 = [] { const char *e = getenv("BELLMAN_HIP_LONG_K2"); return !(e && *e == '0'); }();
+  // the same model - levels x latency of a level x how far the launch overfills the chip
   // [r6] G2 in lane triples: the same on lane SEXTETS (K6Worker)
   constexpr bool G1_PAIRS = std::is_same<FR, FpOps>::value, G2_SEXTETS = std::is_same<FR, Fp2K3Ops>::value;
   constexpr bool PAIRS_POSSIBLE = G1_PAIRS || G2_SEXTETS;   // "pairs" below: the half-point worker of the group
@@ -1290,22 +1275,19 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
       }
     };
     sweep(tree_per_wave<FR>(), LEVEL_US, false);
-    if (PAIRS_POSSIBLE && long_k2) sweep(HalfWorker::PER_WAVE, HALF_LEVEL_US, true);
+    if (PAIRS_POSSIBLE) sweep(HalfWorker::PER_WAVE, HALF_LEVEL_US, true);
     // (the model takes every bucket for a queued run - true of window-table plans; where a typical bucket fits a chunk only
     // the few outliers are queued and the chip has the lanes)
-    if (PAIRS_POSSIBLE && long_k2 && avg_chunks <= 1.0) { run_lanes = 8; runs_on_pairs = true; }
+    if (PAIRS_POSSIBLE && avg_chunks <= 1.0) { run_lanes = 8; runs_on_pairs = true; }
   }
   const u32 max_long = (u32)(nslots / (walk + 1) + 1);
   // runs of more than big_chunks chunks - more than four serial additions per worker of msm_merge_runs_kernel - are cut
-  // into workgroup-sized pieces (msm_merge_long_kernel); G1 pieces run on lane pairs.  BELLMAN_HIP_LONG_K2=0: one lane
-  // per point there too (A/B)
-  constexpr bool LONG_ON_PAIRS = PAIRS_POSSIBLE;
-  const bool long_pairs = LONG_ON_PAIRS && long_k2;
+  // into workgroup-sized pieces (msm_merge_long_kernel) that run on the group's half-point worker (G1: lane pairs)
   // ... but never a run that is merely TYPICAL: where the average bucket already spans dozens of chunks (32 rows of 8 bits over
   // 2^11 G2 points: 64 chunks per bucket) "big" starts at twice the average (round 6, first cut: half of that table's runs
   // went down the long path, 0.81 -> 1.06 ms)
   const u32 big_chunks = std::max(std::max(32u, 4u * run_lanes), (u32)(2.0 * (double)p.n / (double)p.nb / (double)p.chunk));
-  const u32 piece = long_pairs ? long_piece<HalfWorker>() : long_piece<XyzzWorker<FR>>();
+  const u32 piece = long_piece<HalfWorker>();
   const u32 max_big = (u32)(nslots / (big_chunks + 1) + 1);
   // sum of ceil(L_r / piece) over the big runs: consecutive runs share one chunk, so sum L_r <= nslots + max_big
   const u32 max_pieces = (u32)((nslots + max_big) / piece + max_big + 1);
@@ -1332,11 +1314,9 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   constexpr bool TWO_STAGE_FR = std::is_same<FR, FpOps>::value || std::is_same<FR, Fp2K3Ops>::value;
   u32 two_len = 16;
   if (TWO_STAGE_FR) {
-    static const int len_env = [] { const char *e = getenv("BELLMAN_HIP_SUM_TWO_LEN"); return e && *e ? atoi(e) : 0; }();
     const u64 target = (u64)c.num_cus * 4 * 2 * (G2 ? 16 : 32);
     two_len = 4;
     while (two_len < 64 && 2ull * p.NB / two_len > target) two_len <<= 1;
-    if (len_env >= 2) two_len = (u32)len_env;
   }
   const bool want_part = TWO_STAGE_FR && p.NB >= (1u << 17) && p.NB <= (1u << 21) && Lw >= 32 && H >= 32;
   const size_t o_part = want_part ? carve((u64)p.W * ((u64)H * (Lw / std::min(two_len, Lw)) + (u64)Lw * (H / std::min(two_len, H))) * sizeof(Pt)) : 0;
@@ -1371,14 +1351,13 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   BH_HIP_CHECK(hipMemsetAsync(ws, 0, zero_bytes, st));
   const u64 *sorted = nullptr;
   // small multiexps over a window table: one launch for everything up to the filled buckets (msm_small_fill_kernel)
-  static const bool small_on = [] { const char *e = getenv("BELLMAN_HIP_SMALL_FUSED"); return !(e && *e == '0'); }();
   // ... and only when no bucket is EXPECTED to outgrow its list: rows whose top one is a sliver of t = 255 - (Wd - 1) c bits (10-bit
   // rows: t = 5, 11 bits: 2, 12 bits: 3) send the top digit of every scalar to 2^t buckets, nd / 2^t entries each - such buckets fall
   // back to a scan of the whole digit table per worker (an explicit 11-bit table over 2^9 points took 8.9 ms in this kernel against
   // 0.7 through the sort: profiles/r6_call54_tiny_g2_bits.txt); the default 13-bit tables have t = 8
   const u32 top_bits = 255u - (p.Wd - 1) * p.c;
   const u64 sliver_load = top_bits >= 31 ? 0 : ((u64)p.nd >> top_bits);
-  const bool small_fused = small_on && use_table && !opts.padded_table && p.W == 1 && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
+  const bool small_fused = use_table && !opts.padded_table && p.W == 1 && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
                            (u64)p.n <= (u64)SMALL_MAX_PER_BUCKET * p.nb && p.c <= 15 && small_fill_lds_bytes(p.nd, p.n) <= 64 * 1024 &&
                            sliver_load + (u64)p.n / p.nb <= SMALL_LIST_CAP / 2 && !(opts.flags & BH_MSM_NO_SMALL_PATH);
   if (small_fused) {
@@ -1406,7 +1385,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // everything after the sort: run now, or when the job is started (bh_msm_start / its wait)
   Context *cp = &c;
   MsmJobImpl *jp = &job;
-  job.resume = [=]() mutable -> int {
+  job.resume = [=]() -> int {
   Context &c = *cp;
   MsmJobImpl &job = *jp;
   // 4. accumulate equal chunks, then fold the buckets that straddle chunk boundaries
@@ -1421,8 +1400,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     // ... and of the table plan, when the table is one that was laid out that way (bh_bases::table_padded)
     const bool padded_tab = opts.padded_table && use_table;
     // launches that fill the chip join the context's accumulation chain (common.hpp)
-    static const bool chain_on = [] { const char *e = getenv("BELLMAN_HIP_ACC_CHAIN"); return !(e && *e == '0'); }();
-    const bool chained = chain_on && (u64)grid.x * grid.y * 128 >= (u64)c.num_cus * 4 * 64;
+    const bool chained = (u64)grid.x * grid.y * 128 >= (u64)c.num_cus * 4 * 64;
     std::unique_lock<std::mutex> chain_lock(c.acc_mu, std::defer_lock);
     if (chained) {
       if (!job.res.acc_event) BH_HIP_CHECK(hipEventCreateWithFlags(&job.res.acc_event, hipEventDisableTiming));
@@ -1452,11 +1430,6 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
       chain_lock.unlock();
     }
     if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));   // brackets exactly the accumulate launch
-    if (job.hp_stream) {   // the rest of the job (latency-bound chains) runs on the high-priority stream
-      BH_HIP_CHECK(hipEventRecord(job.hp_event, st));
-      BH_HIP_CHECK(hipStreamWaitEvent(job.hp_stream, job.hp_event, 0));
-      st = job.hp_stream;
-    }
     const u32 rwpb = workers_per_block<FR>(128, default_per_wave<FR>());
     const dim3 rgrid((p.chunks_per_window + rwpb - 1) / rwpb, p.W);
     hipLaunchKernelGGL(msm_merge_chunks_kernel<FR>, rgrid, dim3(128), 0, st, sorted, b.zstart, pts, head, tail, p.n,
@@ -1472,31 +1445,18 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
                        max_pieces, err)
     // One launch (medium runs and big pieces side by side) - except the 128-bucket window tables of tiny G2 vectors, whose
     // 128 medium runs are the whole job: two launches there (G2 2^10: 0.74 against 0.85 ms; 2^12 ... 2^16 and every G1 size are
-    // equal or faster fused - G1 2^16 0.79 against 0.88 ms; profiles/r6_call15_tail_split_ab.txt).  BELLMAN_HIP_TAIL_FUSED=0 / 1
-    // forces either for an A/B
-    static const int fused_env = [] { const char *e = getenv("BELLMAN_HIP_TAIL_FUSED"); return e && *e ? (*e == '0' ? 0 : 1) : -1; }();
-    const bool fused = fused_env >= 0 ? fused_env == 1 : (PAIRS_POSSIBLE || p.NB > 128);
-    if (!fused) {
-      const dim3 rg((u32)c.num_cus * 4), lg(long_blocks);
-#define BH_SPLIT(WKR, WKL)                                                                                                  \
-      hipLaunchKernelGGL(msm_merge_runs_kernel<WKR>, rg, dim3(64), 0, st, pts, head, tail, p.c, p.chunks_per_window, long_runs,  \
-                         max_long, run_lanes, err);                                                                         \
-      hipLaunchKernelGGL(msm_merge_long_kernel<WKL>, lg, dim3(LONG_THREADS), 0, st, pts, head, tail, p.c, p.chunks_per_window,   \
-                         big_runs, max_big, piece_out, max_pieces, err)
-      if constexpr (PAIRS_POSSIBLE) {
-        if (runs_on_pairs && long_pairs) { BH_SPLIT(HalfWorker, HalfWorker); }
-        else if (long_pairs) { BH_SPLIT(XyzzWorker<FR>, HalfWorker); }
-        else { BH_SPLIT(XyzzWorker<FR>, XyzzWorker<FR>); }
-      } else {
-        BH_SPLIT(XyzzWorker<FR>, XyzzWorker<FR>);
-      }
-#undef BH_SPLIT
-    } else if constexpr (PAIRS_POSSIBLE) {
-      if (runs_on_pairs && long_pairs) BH_TAIL(HalfWorker, HalfWorker);
-      else if (long_pairs) BH_TAIL(XyzzWorker<FR>, HalfWorker);
-      else BH_TAIL(XyzzWorker<FR>, XyzzWorker<FR>);
-    } else {
+    // equal or faster fused - G1 2^16 0.79 against 0.88 ms; profiles/r6_call15_tail_split_ab.txt).  The big pieces always run
+    // on the half-point worker (HalfWorker is XyzzWorker<FR> where the group has none)
+    if constexpr (PAIRS_POSSIBLE) {
+      if (runs_on_pairs) BH_TAIL(HalfWorker, HalfWorker);
+      else BH_TAIL(XyzzWorker<FR>, HalfWorker);
+    } else if (p.NB > 128) {
       BH_TAIL(XyzzWorker<FR>, XyzzWorker<FR>);
+    } else {
+      hipLaunchKernelGGL(msm_merge_runs_kernel<XyzzWorker<FR>>, dim3((u32)c.num_cus * 4), dim3(64), 0, st, pts, head, tail, p.c,
+                         p.chunks_per_window, long_runs, max_long, run_lanes, err);
+      hipLaunchKernelGGL(msm_merge_long_kernel<XyzzWorker<FR>>, dim3(long_blocks), dim3(LONG_THREADS), 0, st, pts, head, tail,
+                         p.c, p.chunks_per_window, big_runs, max_big, piece_out, max_pieces, err);
     }
 #undef BH_TAIL
     BH_HIP_CHECK(hipGetLastError());
@@ -1508,9 +1468,10 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // workers per output: minimise (serial adds per worker + tree depth) x (waves per SIMD, at least 1);
   // these kernels are latency-bound chains of point additions, not throughput-bound.
   auto pick_lanes = [&](u32 groups, u32 count) {
-    // wavefront slots per SIMD the launch may fill before a step stretches (sum_slot_factor); a block of lane
-    // triples is four wavefronts
-    const double slots = (double)c.num_cus * 4 * sum_slot_factor(G2 ? (FR::LANES == 1 ? 1 : 2) : 0);
+    // wavefront slots the launch may fill before a step stretches: ONE resident wavefront per SIMD - a second does not
+    // interleave for free in these mad-bound chains (G1 2^17-2^20 reduce 0.73-0.99 ms modelled with 1, 0.92-1.19 ms with 2; G2
+    // within noise: profiles/archive/r2_call8_slots.txt); a block of lane triples is four wavefronts
+    const double slots = (double)c.num_cus * 4;
     const double waves_per_block = FR::LANES == 3 ? 4.0 : 1.0;
     u32 best = 1;
     double best_cost = 1e30;
@@ -1533,24 +1494,22 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     return j;
   };
   // G1 launches that leave at least half of the SIMDs empty run on lane pairs (K2, above): half the latency per
-  // addition for twice the lanes.  BELLMAN_HIP_SUM_K2=0 switches it off.
-  static const bool k2_on = [] { const char *e = getenv("BELLMAN_HIP_SUM_K2"); return !(e && *e == '0'); }();
+  // addition for twice the lanes.
   // force: 0 = by the rules below, 1 = lane pairs, 2 = one lane per point (the first stage of a two-stage sum chooses)
   auto launch_sums = [&](SumJobs<FR> js, int force = 0) -> bool {
     const u32 total = js.j[0].nblocks + js.j[1].nblocks + js.j[2].nblocks;
     if (!total) return true;
     if constexpr (std::is_same<FR, FpOps>::value) {
-      static const double k2_fill = [] { const char *e = getenv("BELLMAN_HIP_K2_SUM_FILL"); return e && *e ? atof(e) : 4.0; }();   // wavefronts per SIMD the lane-pair launch may reach
+      constexpr double K2_SUM_FILL = 4.0;   // wavefronts per SIMD the lane-pair launch may reach
       // [r6] a handful of long sums (the bit sums and the total of ONE big bucket set): one workgroup of up to eight
-      // wavefronts per output (msm_sum_k2_wide_kernel).  BELLMAN_HIP_SUM_WIDE=0 switches it off
-      static const bool wide_on = [] { const char *e = getenv("BELLMAN_HIP_SUM_WIDE"); return !(e && *e == '0'); }();
+      // wavefronts per output (msm_sum_k2_wide_kernel)
       u32 groups_all = 0, max_sel = 0;
       for (int q = 0; q < 3; q++)
         if (js.j[q].nblocks) {
           groups_all += js.j[q].d.groups;
           max_sel = std::max(max_sel, js.j[q].d.mode == SUM_BITS ? js.j[q].d.count / 2 : js.j[q].d.count / js.j[q].d.splits);
         }
-      if (k2_on && wide_on && force == 0 && max_sel >= 128 && groups_all <= 2u * (u32)c.num_cus) {
+      if (force == 0 && max_sel >= 128 && groups_all <= 2u * (u32)c.num_cus) {
         // (never more than four wavefronts: a CU has four SIMDs, and the wavefronts of a workgroup that share one take turns -
         // eight were 198 us for 2 + 5 + 3 levels, profiles/r6_call32_timeline.txt)
         u32 nw = 2;
@@ -1560,7 +1519,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
         hipLaunchKernelGGL(msm_sum_k2_wide_kernel<FR>, dim3(js.j[0].nblocks + js.j[1].nblocks + js.j[2].nblocks), dim3(64 * nw), 0, st, js);
         return hipGetLastError() == hipSuccess;
       }
-      if (force != 2 && k2_on && (force == 1 || (double)total * 2 <= k2_fill * (double)c.num_cus * 4)) {   // blocks are single wavefronts
+      if (force != 2 && (force == 1 || (double)total * 2 <= K2_SUM_FILL * (double)c.num_cus * 4)) {   // blocks are single wavefronts
         for (int q = 0; q < 3; q++) {
           SumJob<FR> &j = js.j[q];
           if (!j.nblocks) continue;
@@ -1573,7 +1532,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     }
     if constexpr (std::is_same<FR, Fp2K3Ops>::value) {
       // G2: the same idea on lane sextets (32 workers per 256-thread block) while the launch stays within one wavefront per SIMD
-      if (k2_on && force != 2) {
+      if (force != 2) {
         SumJobs<FR> k6 = js;
         u32 blocks6 = 0;
         for (int q = 0; q < 3; q++) {
@@ -1583,8 +1542,8 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
           j.nblocks = (u32)(((u64)j.d.groups * j.d.lanes + 31) / 32);
           blocks6 += j.nblocks;
         }
-        static const double k6_fill = [] { const char *e = getenv("BELLMAN_HIP_K6_SUM_FILL"); return e && *e ? atof(e) : 8.0; }();   // blocks per CU the launch may reach
-        if ((double)blocks6 <= k6_fill * (double)c.num_cus) {
+        constexpr double K6_SUM_FILL = 8.0;   // blocks per CU the launch may reach
+        if ((double)blocks6 <= K6_SUM_FILL * (double)c.num_cus) {
           hipLaunchKernelGGL(msm_sum_k6_kernel<FR>, dim3(blocks6), dim3(256), 0, st, k6);
           return hipGetLastError() == hipSuccess;
         }
@@ -1606,16 +1565,10 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     // of a 2^20-term multiexp, 0.27 at the multiplier's throughput).  Two stages instead: (1) every output is cut into pieces
     // of `len` consecutive elements and ONE worker adds up a piece - no tree, every lane busy - sized so that the launch is
     // two wavefronts per SIMD; (2) the handful of piece sums per output are folded by a small tree launch.
-    // BELLMAN_HIP_SUM_TWO_STAGE=0: off; 1: stage one on lane pairs; 2: stage one with one lane per point
-    static const int two_env = [] { const char *e = getenv("BELLMAN_HIP_SUM_TWO_STAGE"); return e && *e ? atoi(e) : -1; }();
-    bool two_stage = false;
-    if constexpr (TWO_STAGE_FR) {
-      two_stage = two_env != 0 && part && p.NB >= (1u << 17) && p.NB <= (1u << 21) && Lw >= 32 && H >= 32;
-    }
-    if (two_stage) {
-      // G2 (lane triples): stage one on the lane-triple kernel (16 workers per wavefront; sextets would halve that again)
-      static const bool g2_k6_stage1 = [] { const char *e = getenv("BELLMAN_HIP_SUM_G2_STAGE1_K6"); return e && *e == '1'; }();
-      const bool one_lane = two_env == 2 || (G2 && !g2_k6_stage1);
+    if (part) {   // (want_part, above: the sizes and groups that reduce in two stages)
+      // G1: stage one on lane pairs.  G2 (lane triples): on the lane-triple kernel (16 workers per wavefront; sextets halve
+      // that again and were within noise - reduce 1.89 / 1.96 ms against 1.86 / 1.97 at 2^19 / 2^20, profiles/r6_call42_g2_stage1.txt)
+      const bool one_lane = G2;
       const u32 len_r = std::min(two_len, Lw), len_c = std::min(two_len, H);
       const u32 Sr = Lw / len_r, Sc = H / len_c;
       Pt *part_r = part, *part_c = part + (u64)dr.groups * Sr;
@@ -1742,7 +1695,6 @@ static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
     job.resume = nullptr;
   }
   if (hipStreamSynchronize(job.stream) != hipSuccess) rc = BH_ERR_HIP;
-  if (job.hp_stream && hipStreamSynchronize(job.hp_stream) != hipSuccess) rc = BH_ERR_HIP;
   if (rc == BH_OK) {
     const MsmPlan &p = job.plan;
     constexpr size_t ERR_SLOT = 256;   // the carve granularity of msm_enqueue

@@ -183,24 +183,24 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const u64 *pair
 // after the first pass's scan (one bucket set): the entries it keeps, as the count of those it drops
 __global__ void sort_live_kernel(const u32 *scanned_total, u32 *zstart, u32 n) { zstart[0] = n - *scanned_total; }
 
-// STAGED [r6]: the tile is first sorted into LDS (same stable ballot ranking, positions relative to the tile) and then copied
+// [r6] The tile is first sorted into LDS (same stable ballot ranking, positions relative to the tile) and then copied
 // out, so that neighbouring lanes write neighbouring entries of a bin's run instead of one 8-byte store per bin and round: a
 // timing-only build with coalesced writes put the scattered stores at 25-40 % of the whole sort (0.44 -> 0.33 ms at 2^20,
-// 1.80 -> 1.09 at 2^22: profiles/r6_call52_scatter_writes_upper_bound.txt).
-template <bool STAGED>
+// 1.80 -> 1.09 at 2^22: profiles/r6_call52_scatter_writes_upper_bound.txt).  (Until then every entry went straight to its
+// global position, one store per entry and round.)
 __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *pairs_in, u64 *pairs_out,
                                                                    const u32 *offsets, u32 n, u32 shift,
                                                                    u32 num_tiles, u32 drop_zeros, const u32 *live_from,
                                                                    const u32 *out_shift) {
-  __shared__ u32 base[256];                              // next position of every bin: global, or (STAGED) inside the tile
+  __shared__ u32 base[256];                              // next position of every bin inside the tile
   __shared__ u32 wcnt[SORT_THREADS / 64][256];
-  __shared__ u32 gbase[STAGED ? 256 : 1];                // STAGED: global position of a bin's run minus its position in the tile
-  __shared__ u32 wsum[STAGED ? SORT_THREADS / 64 : 1];
-  __shared__ u64 stage[STAGED ? SORT_TILE : 1];          // STAGED: the tile, sorted (32 KB)
+  __shared__ u32 gbase[256];                             // global position of a bin's run minus its position in the tile
+  __shared__ u32 wsum[SORT_THREADS / 64];
+  __shared__ u64 stage[SORT_TILE];                       // the tile, sorted (32 KB)
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x, w = blockIdx.y;
   if (live_from && tile * SORT_TILE >= n - *live_from) return;   // (uniform over the workgroup: before any barrier)
   const u32 goff = offsets[((u64)w * 256 + tid) * num_tiles + tile];   // global position (all windows)
-  base[tid] = STAGED ? 0u : goff;
+  base[tid] = 0u;
 #pragma unroll
   for (int v = 0; v < SORT_THREADS / 64; v++) wcnt[v][tid] = 0;
   __syncthreads();
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
     keys[r] = idx < nn ? src[idx] : 0;
   }
   u32 tile_total = 0;
-  if constexpr (STAGED) {
+  {
     // the tile's histogram, then its exclusive prefix: where every bin's run starts inside the sorted tile
 #pragma unroll
     for (int r = 0; r < SORT_ROUNDS; r++) {
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
     if (valid) {
       u32 off = base[bin] + rank;
       for (u32 v = 0; v < wave; v++) off += wcnt[v][bin];
-      if constexpr (STAGED) stage[off] = key; else pairs_out[off] = key;
+      stage[off] = key;
     }
     __syncthreads();
     u32 tot = 0;
@@ -274,11 +274,9 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
     base[tid] += tot;
     __syncthreads();
   }
-  if constexpr (STAGED) {
-    for (u32 j = tid; j < tile_total; j += SORT_THREADS) {
-      const u64 key = stage[j];
-      pairs_out[gbase[(u32)(key >> shift) & 0xff] + j] = key;
-    }
+  for (u32 j = tid; j < tile_total; j += SORT_THREADS) {
+    const u64 key = stage[j];
+    pairs_out[gbase[(u32)(key >> shift) & 0xff] + j] = key;
   }
 }
 
@@ -374,19 +372,17 @@ unsigned table_window_bits(u64 n_bases, bool g2) {
   // column sums, bit sums over the selected half, msm_ec.cuh): 2^19 2.01 ms against 2.40 classic and 2.21 with 16-bit rows,
   // 2^20 3.33 against 3.72-3.81 and 3.88, 2^21 6.12 against 6.90, 2^22 11.3 against 12.9 (profiles/r6_call33_tables_after_sums.txt,
   // r6_call34_table_bits_mid.txt: 13 bits still win up to 2^18 - 1.37 against 1.38 there)
-  // G2 keeps its 16-bit rows.  20-bit rows (bh_bases_precompute(.., 20), or BELLMAN_HIP_G2_TABLE20_FROM=<log2 of the first size that
-  // takes them>) win on UNIFORM scalars from 2^20 points - 2^20 9.2-9.4 ms against 9.9-10.1, 2^21 16.6 against 19.1 (2^19: 5.7-5.9
+  // G2 keeps its 16-bit rows.  20-bit rows (still available on request: bh_bases_precompute(.., 20)) won on UNIFORM scalars from 2^20 points - 2^20 9.2-9.4 ms against 9.9-10.1, 2^21 16.6 against 19.1 (2^19: 5.7-5.9
   // against 5.4) - but the reduction of their 2^19-bucket set is ~2 ms on lane triples against 0.6 for 2^15 buckets whatever the
   // scalars are, and the b_g2 query of a real proof meets a boolean-heavy witness: 90 % booleans at 2^20 points 3.9 ms against 2.5
   // (profiles/r6_call40_*, r6_call42_*, r6_call45_drop_zeros.txt against r6_final_boolean_mix.txt).  Not the default.
-  static const u32 g2_from = [] { const char *e = getenv("BELLMAN_HIP_G2_TABLE20_FROM"); long v = e && *e ? strtol(e, nullptr, 10) : 99; return (u32)(v < 0 ? 0 : v); }();
   // [r6] tiny G2 vectors (up to 2^10 points): 13-bit rows like G1 - 20 n entries over 4096 buckets qualify for the one-launch path
   // (msm_small_fill_kernel: at most 16 entries per bucket on average), which the 8-bit rows' 128 buckets never did: 2^8 0.45 against
   // 0.60 ms, 2^9 0.45 against 0.51, 2^10 0.48 against 0.54 - the b_g2 multiexp was the critical path of a MiMC-322 proof; 2^12: 10 bits
   // (0.70 against 0.78).  (Explicit 10- to 12-bit tables over 2^8 ... 2^9 points used to take that path too and were pathologically slow
   // in it - 2-9 ms, bucket lists overflowing under a sliver top row: profiles/r6_call54_tiny_g2_bits.txt; msm_enqueue now declines
   // the path for such plans, r6_call56_small_path_guard.txt.)
-  if (g2) return lg <= 10 ? 13 : lg == 11 ? 8 : lg <= 13 ? 10 : lg >= g2_from ? 20 : 16;
+  if (g2) return lg <= 10 ? 13 : lg == 11 ? 8 : lg <= 13 ? 10 : 16;
   // (2^25 points and more - never automatic, 94 GB for 2^26 points - take 24-bit rows: 11 of them into 2^23 buckets; 2^25 75.1 ms
   // against 83.5 classic and 82.5 / 77.5 with 20- / 22-bit rows, 2^26 145.1 against 162.0: profiles/r6_call46_g1_tables_2p25_2p26.txt)
   if (lg <= 10) return 13;
@@ -413,21 +409,19 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
   const u64 avg = (u64)p.n >> (p.c - 1);
   // ... but never so long that the chip runs out of lanes (one wavefront per SIMD for the register-heavy
   // one-lane-per-point G2 accumulation, two otherwise); runs of 2-4 chunks are still folded by their owner lane
-  // (x BELLMAN_HIP_TABLE_OVERSUB, default 1.  A launch that fills the chip EXACTLY - one wavefront per SIMD for the
+  // (A launch that fills the chip EXACTLY - one wavefront per SIMD for the
   // one-lane-per-point G2 kernel - is the fastest alone, but when other jobs' accumulations hold SIMDs at its start the
   // workgroups that find no slot wait for the first round to END: 10.2 ms instead of 5.5 inside a proof,
-  // profiles/archive/r3_call2_proof_timeline.txt.  Shorter chunks for several rounds bound that tail but multiply the partials
+  // profiles/archive/r3_call2_proof_timeline.txt.  Shorter chunks for several rounds bounded that tail but multiplied the partials
   // the merge has to fold - reduce 1.0 -> 2.0 -> 3.1 ms for 2 / 4 rounds, profiles/archive/r3_call3_oversub.txt; the
   // accumulation chain of common.hpp removes the cause instead.)
-  static const u64 oversub = [] { const char *e = getenv("BELLMAN_HIP_TABLE_OVERSUB"); long v = e && *e ? strtol(e, nullptr, 10) : 1; return (u64)(v < 1 ? 1 : v > 64 ? 64 : v); }();
-  const u64 lanes_min = (u64)num_cus * 4 * 64 * (g2 ? 1 : 2) * oversub;
+  const u64 lanes_min = (u64)num_cus * 4 * 64 * (g2 ? 1 : 2);
   u64 k = std::max<u64>(base_k, avg);
   k = std::min<u64>(k, std::max<u64>(base_k, (u64)p.n / lanes_min));
   // [r6] G1 tables with MANY buckets (20-bit rows over 2^19 ... 2^22 points: the average bucket holds 13-104 entries, the chip's
   // lanes 52-416 each): chunks of a whole number of chip-filling rounds instead of several rounds of average-bucket chunks - the
   // accumulation takes the same time (2.29 against 2.30-2.33 ms at 2^20) and the chunk merge folds a quarter of the partials
-  // (0.21 -> 0.05 ms; profiles/r6_call29_table20_chunks.txt, r6_call30_*).  BELLMAN_HIP_TABLE_ONE_ROUND=0: the rule above
-  static const bool one_round = [] { const char *e = getenv("BELLMAN_HIP_TABLE_ONE_ROUND"); return !(e && *e == '0'); }();
+  // (0.21 -> 0.05 ms; profiles/r6_call29_table20_chunks.txt, r6_call30_*)
   // ... up to 128 entries per lane; beyond, R launches' worth of equal chunks (one round of 208 / 416 entries ran 8 % slower than
   // four of 52 / 104 at 2^21 / 2^22 - 4.58 against 4.24 ms, 9.33 against 8.59 - for 0.2 ms less merging:
   // profiles/r6_call33_tables_after_sums.txt).  And never ONE round: a launch that fills the chip exactly is as fast as any
@@ -435,16 +429,16 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
   // the job before hold some SIMDs when it starts, and the workgroups that find no slot run as a second round of full-length
   // chunks - the first G1 accumulation of a 2^20-constraint proof took 3.75 ms against 2.3 stand-alone; with two rounds the
   // proof's device part is 18.2-18.4 ms against 19.3-19.6 with one and 20.1 without these tables
-  // (profiles/r6_call36_proof_timeline_*.txt, r6_call37_table_rounds.txt).  BELLMAN_HIP_TABLE_ROUNDS=n: at least n rounds
-  static const u64 min_rounds = [] { const char *e = getenv("BELLMAN_HIP_TABLE_ROUNDS"); long v = e && *e ? strtol(e, nullptr, 10) : 2; return (u64)(v < 1 ? 1 : v > 16 ? 16 : v); }();
-  if (one_round && !g2 && (u64)p.n / lanes_min > k) {
-    const u64 per = ((u64)p.n + lanes_min - 1) / lanes_min, rounds = std::max<u64>(min_rounds, (per + 127) / 128);
+  // (profiles/r6_call36_proof_timeline_*.txt, r6_call37_table_rounds.txt)
+  constexpr u64 MIN_ROUNDS = 2;
+  if (!g2 && (u64)p.n / lanes_min > k) {
+    const u64 per = ((u64)p.n + lanes_min - 1) / lanes_min, rounds = std::max<u64>(MIN_ROUNDS, (per + 127) / 128);
     k = std::max<u64>(k, ((u64)p.n + lanes_min * rounds - 1) / (lanes_min * rounds));
   }
   // [r6] G2 tables with many buckets (20-bit rows): the accumulation runs on lane PAIRS, 2 x 32 workers per SIMD; whole rounds
   // of at most 64 entries (2^20 points: four rounds of 52 - 6.86 ms against 7.51 with the 64 the rule above gives, which is
   // 3.25 rounds; profiles/r6_call39_g2_table_bits_triples.txt)
-  if (one_round && g2 && p.c >= 18 && !forced_chunk) {
+  if (g2 && p.c >= 18 && !forced_chunk) {
     const u64 workers = (u64)num_cus * 4 * 2 * 32;
     const u64 per = ((u64)p.n + workers - 1) / workers, rounds = std::max<u64>(2, (per + 63) / 64);
     k = std::max<u64>(8, ((u64)p.n + workers * rounds - 1) / (workers * rounds));
@@ -472,12 +466,9 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
   hipLaunchKernelGGL(msm_digits_kernel, dim3((p.nd + 255) / 256), dim3(256), 0, st, scalars_dev, fmt, p.nd,
                      density_dev, b.word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, b.pairs_a, b.err);
   BH_HIP_CHECK(hipGetLastError());
-  // 2. sort by digit, 8 bits per pass; one bucket set: zero digits dropped by the first pass (BELLMAN_HIP_SORT_DROP_ZEROS=0:
-  // sorted to the front like the classic plan's)
-  static const bool drop_on = [] { const char *e = getenv("BELLMAN_HIP_SORT_DROP_ZEROS"); return !(e && *e == '0'); }();
-  const bool drop = drop_on && p.W == 1;
-  // tiles sorted in LDS and copied out (sort_scatter_kernel<true>).  BELLMAN_HIP_SORT_STAGED=0: one store per entry and round
-  static const bool staged_on = [] { const char *e = getenv("BELLMAN_HIP_SORT_STAGED"); return !(e && *e == '0'); }();
+  // 2. sort by digit, 8 bits per pass; one bucket set: zero digits dropped by the first pass (the classic plan's windows
+  // sort them to the front)
+  const bool drop = p.W == 1;
   u64 *src = b.pairs_a, *dst = b.pairs_b;
   for (u32 pass = 0; pass < p.sort_passes; pass++) {
     const u32 shift = 32 + 8 * pass;
@@ -492,12 +483,8 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
       hipLaunchKernelGGL(sort_live_kernel, dim3(1), dim3(1), 0, st, b.counts + ncounts, b.zstart, p.n);
       BH_HIP_CHECK(hipGetLastError());
     }
-    if (staged_on)
-      hipLaunchKernelGGL(sort_scatter_kernel<true>, dim3(p.num_tiles, p.W), dim3(SORT_THREADS), 0, st, src, dst, b.counts,
-                         p.n, shift, p.num_tiles, (drop && first) ? 1u : 0u, live_from, (drop && last) ? b.zstart : nullptr);
-    else
-      hipLaunchKernelGGL(sort_scatter_kernel<false>, dim3(p.num_tiles, p.W), dim3(SORT_THREADS), 0, st, src, dst, b.counts,
-                         p.n, shift, p.num_tiles, (drop && first) ? 1u : 0u, live_from, (drop && last) ? b.zstart : nullptr);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(p.num_tiles, p.W), dim3(SORT_THREADS), 0, st, src, dst, b.counts,
+                       p.n, shift, p.num_tiles, (drop && first) ? 1u : 0u, live_from, (drop && last) ? b.zstart : nullptr);
     BH_HIP_CHECK(hipGetLastError());
     std::swap(src, dst);
   }
