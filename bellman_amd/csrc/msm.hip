@@ -180,7 +180,7 @@ int msm_job_finish(MsmJobImpl &job, void *out_affine, float *ms, u64 *stats8) {
 int msm_debug_stages(Context &c, const void *scalars_host, u64 n, int fmt, unsigned cbits, u64 *pairs_out, u32 *zstart_out) {
   const MsmPlan p = make_plan(n, cbits, 0, false);
   hipStream_t st = c.stream;
-  const u64 npairs = (u64)p.W * n, ncounts = (u64)p.W * 256 * p.num_tiles;
+  const u64 npairs = (u64)p.W * n, ncounts = sort_counts_elems(p);
   MsmBuffers b;
   std::vector<void *> owned;
   auto alloc = [&](size_t bytes) { void *q = c.pool.acquire(bytes); owned.push_back(q); return q; };

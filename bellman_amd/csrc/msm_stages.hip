@@ -12,8 +12,9 @@
 //                  (|digit| << 32 | sign << 31 | base) pairs, window-major.       msm_stages.hip
 //   2. sort        stable LSD radix sort of every window's pairs by |digit|, 8 bits per pass;
 //                  ranking inside a tile uses wavefront ballots (match-any) + popcounts; the tile is sorted
-//                  into LDS and copied out in runs.  One bucket set (window tables): the first pass drops
-//                  the zero digits.
+//                  into LDS and copied out in runs.  One bucket set (window tables): stages 1 and 2 are one -
+//                  the first pass recodes the scalars itself and keeps the non-zero digits only; key
+//                  |digit| - 1, up to 10 bits per pass.
 //   3. chunks      the sorted stream of every window (zero digits skipped) is cut into equal
 //                  chunks of K entries: every lane performs exactly K mixed additions whatever
 //                  the bucket-size distribution.
@@ -150,38 +151,21 @@ constexpr int SORT_THREADS = 256;
 constexpr int SORT_ROUNDS = 16;
 constexpr int SORT_TILE = SORT_THREADS * SORT_ROUNDS;
 
-// [r6] Plans with ONE bucket set (window tables) drop the zero digits in the first pass instead of sorting them to the front:
-// `drop_zeros` - the pass neither counts nor moves entries whose digit is 0; `live_from` (later passes) - only the
-// n - *live_from entries the first pass kept exist; the last pass writes them to the END of the array (`out_shift`), so that
-// what follows sees exactly what it saw before: *zstart entries to skip, then the sorted non-zero digits.  Boolean-heavy
-// scalars are mostly zero digits (12 of the 13 of a 0 / 1 scalar): a 90 %-boolean 2^20-term multiexp sorted 13.6 M entries to
-// accumulate 1.8 M of them.
 __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const u64 *pairs, u32 *counts, u32 n,
-                                                                u32 shift, u32 num_tiles, u32 drop_zeros, const u32 *live_from) {
+                                                                u32 shift, u32 num_tiles) {
   __shared__ u32 hist[256];
   const u32 tid = threadIdx.x, tile = blockIdx.x, w = blockIdx.y;
   hist[tid] = 0;
   __syncthreads();
   const u64 *src = pairs + (u64)w * n;
-  const u32 nn = live_from ? n - *live_from : n;
-  if (tile * SORT_TILE >= nn) {   // nothing left for this tile (later passes of a vector that was mostly zero digits)
-    counts[((u64)w * 256 + tid) * num_tiles + tile] = 0;
-    return;
-  }
 #pragma unroll 4
   for (int r = 0; r < SORT_ROUNDS; r++) {
     u32 idx = tile * SORT_TILE + r * SORT_THREADS + tid;
-    if (idx < nn) {
-      const u64 key = src[idx];
-      if (!(drop_zeros && (u32)(key >> 32) == 0)) atomicAdd(&hist[(u32)(key >> shift) & 0xff], 1u);
-    }
+    if (idx < n) atomicAdd(&hist[(u32)(src[idx] >> shift) & 0xff], 1u);
   }
   __syncthreads();
   counts[((u64)w * 256 + tid) * num_tiles + tile] = hist[tid];
-  if (drop_zeros && tile == 0 && w == 0 && tid == 0) counts[(u64)gridDim.y * 256 * num_tiles] = 0;   // the scan's total slot
 }
-// after the first pass's scan (one bucket set): the entries it keeps, as the count of those it drops
-__global__ void sort_live_kernel(const u32 *scanned_total, u32 *zstart, u32 n) { zstart[0] = n - *scanned_total; }
 
 // [r6] The tile is first sorted into LDS (same stable ballot ranking, positions relative to the tile) and then copied
 // out, so that neighbouring lanes write neighbouring entries of a bin's run instead of one 8-byte store per bin and round: a
@@ -190,23 +174,19 @@ __global__ void sort_live_kernel(const u32 *scanned_total, u32 *zstart, u32 n) {
 // global position, one store per entry and round.)
 __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *pairs_in, u64 *pairs_out,
                                                                    const u32 *offsets, u32 n, u32 shift,
-                                                                   u32 num_tiles, u32 drop_zeros, const u32 *live_from,
-                                                                   const u32 *out_shift) {
+                                                                   u32 num_tiles) {
   __shared__ u32 base[256];                              // next position of every bin inside the tile
   __shared__ u32 wcnt[SORT_THREADS / 64][256];
   __shared__ u32 gbase[256];                             // global position of a bin's run minus its position in the tile
   __shared__ u32 wsum[SORT_THREADS / 64];
   __shared__ u64 stage[SORT_TILE];                       // the tile, sorted (32 KB)
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x, w = blockIdx.y;
-  if (live_from && tile * SORT_TILE >= n - *live_from) return;   // (uniform over the workgroup: before any barrier)
   const u32 goff = offsets[((u64)w * 256 + tid) * num_tiles + tile];   // global position (all windows)
   base[tid] = 0u;
 #pragma unroll
   for (int v = 0; v < SORT_THREADS / 64; v++) wcnt[v][tid] = 0;
   __syncthreads();
   const u64 *src = pairs_in + (u64)w * n;
-  const u32 nn = live_from ? n - *live_from : n;
-  if (out_shift) pairs_out += *out_shift;
   const u64 lt_mask = ((u64)1 << lane) - 1;
   // all of the thread's keys are loaded before the ranking rounds: one exposed memory latency per tile instead of one
   // per round (the rounds themselves are ballots, LDS and barriers)
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
 #pragma unroll
   for (int r = 0; r < SORT_ROUNDS; r++) {
     const u32 idx = tile * SORT_TILE + r * SORT_THREADS + tid;
-    keys[r] = idx < nn ? src[idx] : 0;
+    keys[r] = idx < n ? src[idx] : 0;
   }
   u32 tile_total = 0;
   {
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
     for (int r = 0; r < SORT_ROUNDS; r++) {
       const u32 idx = tile * SORT_TILE + r * SORT_THREADS + tid;
       const u64 key = keys[r];
-      if (idx < nn && !(drop_zeros && (u32)(key >> 32) == 0)) atomicAdd(&base[(u32)(key >> shift) & 0xff], 1u);
+      if (idx < n) atomicAdd(&base[(u32)(key >> shift) & 0xff], 1u);
     }
     __syncthreads();
     const u32 cnt = base[tid];
@@ -250,7 +230,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
   for (int r = 0; r < SORT_ROUNDS; r++) {
     const u32 idx = tile * SORT_TILE + r * SORT_THREADS + tid;
     const u64 key = keys[r];
-    const bool valid = idx < nn && !(drop_zeros && (u32)(key >> 32) == 0);
+    const bool valid = idx < n;
     const u32 bin = (u32)(key >> shift) & 0xff;
     // wavefront match-any over the 8-bit bin: lanes with equal bins
     u64 mask = __ballot(valid);
@@ -277,6 +257,277 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u64 *p
   for (u32 j = tid; j < tile_total; j += SORT_THREADS) {
     const u64 key = stage[j];
     pairs_out[gbase[(u32)(key >> shift) & 0xff] + j] = key;
+  }
+}
+
+// ============================================================================================
+// 2b. plans with ONE bucket set (window tables): recoding fused into the first pass, up to 10 key bits per pass
+// ============================================================================================
+// The zero digits never reach the sorted stream, so the key of an entry is |d| - 1 in [0, 2^(c-1)): c - 1 bits, sorted in
+// ceil((c - 1) / 10) passes of evenly split widths (c = 20: 10 + 9, where 8-bit passes over |d| needed three; c = 10: one).
+// The first pass reads the SCALARS: its histogram and scatter kernels recode a block of consecutive scalars - all Wd
+// digits of each, one thread per scalar from one 32-byte load - so the unsorted entry array is never written or read.
+// Order inside a bucket after the first pass: by scalar block, wavefront, row, scalar - a pure function of the inputs; the
+// later passes are stable.
+//
+// A workgroup sorts its tile into LDS and copies it out in runs (as sort_scatter_kernel).  Every wavefront owns a
+// CONTIGUOUS eighth of the tile and the start of each bin's run per wavefront (wbase), so that the ranking rounds need
+// no workgroup barrier: match-any ballot, popcount rank, the bin's first lane advances the wavefront's cursor.
+// Tile: 512 threads x 14 entries (56 KiB of staging, 76 KiB of LDS: two workgroups = 16 wavefronts per CU); the first pass
+// one scalar per thread (13 rows: 6656 entries), so that every wavefront ranks the same number of rounds.  Measured best
+// at 2^20 terms of 13 rows: scatter kernels 91 + 74 us, against 164 + 108 with 256 threads x 32 entries (8192-entry tile,
+// 8 wavefronts per CU, three scalars per thread) - occupancy outweighs the longer runs of the copy-out
+// (profiles/sort_table_plan_kernel_stats.txt).
+constexpr int WIDE_THREADS = 512;
+constexpr int WIDE_WAVES = WIDE_THREADS / 64;
+constexpr int WIDE_ROUNDS = 14;
+constexpr int WIDE_TILE = WIDE_THREADS * WIDE_ROUNDS;
+constexpr int WIDE_MAX_BITS = 10, WIDE_MAX_BINS = 1 << WIDE_MAX_BITS;
+constexpr int WIDE_BPT = WIDE_MAX_BINS / WIDE_THREADS;     // consecutive bins per thread in the tile prefix
+constexpr int WIDE_SCALARS = 1;                            // scalars per thread of the first pass (13 rows: 512 per tile)
+static_assert(WIDE_MAX_BINS == WIDE_BPT * WIDE_THREADS, "the tile prefix gives every thread WIDE_BPT consecutive bins");
+static_assert(WIDE_TILE <= 65535, "tile positions are kept in 16 bits");
+static_assert(WIDE_WAVES * WIDE_MAX_BINS * 4 <= WIDE_TILE * 8, "the per-wavefront counts live in the staging area");
+
+static u32 wide_passes(u32 c) { return (c - 1 + WIDE_MAX_BITS - 1) / WIDE_MAX_BITS; }
+static u32 wide_pass_bits(u32 c, u32 pass) {
+  const u32 kb = c - 1, np = wide_passes(c);
+  return kb / np + (pass < kb % np ? 1u : 0u);
+}
+// scalars per tile of the first pass: all their digits fit the staging area
+static u32 wide_scalars_per_tile(u32 Wd) { return std::max(1u, std::min<u32>(WIDE_THREADS * WIDE_SCALARS, WIDE_TILE / Wd)); }
+static u32 wide_first_tiles(const MsmPlan &p) { const u32 spt = wide_scalars_per_tile(p.Wd); return (p.nd + spt - 1) / spt; }
+
+size_t sort_counts_elems(const MsmPlan &p) {
+  if (p.W != 1) return (size_t)p.W * 256 * p.num_tiles;
+  size_t m = ((size_t)1 << wide_pass_bits(p.c, 0)) * wide_first_tiles(p);
+  for (u32 pass = 1; pass < p.sort_passes; pass++) m = std::max(m, ((size_t)1 << wide_pass_bits(p.c, pass)) * p.num_tiles);
+  return m;
+}
+
+struct WideDigits {      // what msm_digits_kernel takes
+  const void *scalars;
+  const u64 *density;
+  const u32 *word_prefix;
+  u64 skip, n_bases;
+  u32 fmt, nd, c, Wd, stride, spt;
+};
+// scalar i: whether it contributes (dense and inside the bases; every dense entry at or after n_bases flags EOF when
+// `err` is given), its reduced value and the record index of its row 0
+__device__ __forceinline__ bool wide_load_scalar(const WideDigits &a, u32 i, fr_t &s, u32 &rec, ErrFlags *err) {
+  bool dense = true;
+  u64 k = a.skip + i;
+  if (a.density) {
+    const u64 word = a.density[i >> 6];
+    dense = (word >> (i & 63)) & 1;
+    k = a.skip + a.word_prefix[i >> 6] + __popcll(word & (((u64)1 << (i & 63)) - 1));
+  }
+  if (!dense) return false;
+  if (k >= a.n_bases) {
+    if (err) atomicOr(&err->eof, 1u);
+    return false;
+  }
+  load_scalar(a.scalars, i, (int)a.fmt, s);
+  rec = (u32)k;
+  return true;
+}
+// the next signed digit (low to high, with carry; msm_digits_kernel) as the upper half and sign bit of an entry; the
+// scalar is shifted down by one row
+__device__ __forceinline__ u64 wide_next_digit(fr_t &s, u32 &carry, u32 c) {
+  u32 v = (s.l[0] & ((1u << c) - 1)) + carry;
+#pragma unroll
+  for (int i = 0; i < 7; i++) s.l[i] = (u32)((((u64)s.l[i + 1] << 32) | s.l[i]) >> c);
+  s.l[7] >>= c;
+  u32 neg = 0;
+  carry = 0;
+  if (v > (1u << (c - 1))) { v = (1u << c) - v; neg = (v != 0); carry = 1; }
+  return ((u64)v << 32) | ((u64)neg << 31);
+}
+__device__ __forceinline__ u32 wide_bin(u64 entry, u32 shift, u32 bin_mask) { return (((u32)(entry >> 32) - 1u) >> shift) & bin_mask; }
+
+__global__ __launch_bounds__(WIDE_THREADS) void wide_hist_digits_kernel(WideDigits a, u32 *counts, u32 num_tiles, u32 bits,
+                                                                        ErrFlags *err) {
+  __shared__ u32 hist[WIDE_MAX_BINS];
+  const u32 tid = threadIdx.x, tile = blockIdx.x, bins = 1u << bits, bin_mask = bins - 1;
+  for (u32 b = tid; b < WIDE_MAX_BINS; b += WIDE_THREADS) hist[b] = 0;
+  __syncthreads();
+  for (u32 j = 0; j < (u32)WIDE_SCALARS; j++) {
+    const u32 local = j * WIDE_THREADS + tid, i = tile * a.spt + local;
+    fr_t s;
+    u32 rec, carry = 0;
+    if (local >= a.spt || i >= a.nd || !wide_load_scalar(a, i, s, rec, err)) continue;
+    for (u32 w = 0; w < a.Wd; w++) {
+      const u64 e = wide_next_digit(s, carry, a.c);
+      if ((u32)(e >> 32)) atomicAdd(&hist[wide_bin(e, 0, bin_mask)], 1u);
+    }
+  }
+  __syncthreads();
+  for (u32 b = tid; b < bins; b += WIDE_THREADS) counts[(u64)b * num_tiles + tile] = hist[b];
+  if (tile == 0 && tid == 0) counts[(u64)bins * num_tiles] = 0;   // the scan's total slot
+}
+__global__ __launch_bounds__(WIDE_THREADS) void wide_hist_kernel(const u64 *pairs, u32 *counts, u32 n, u32 shift, u32 bits,
+                                                                 u32 num_tiles, const u32 *live_from) {
+  __shared__ u32 hist[WIDE_MAX_BINS];
+  const u32 tid = threadIdx.x, tile = blockIdx.x, bins = 1u << bits, bin_mask = bins - 1;
+  const u32 nn = n - *live_from;
+  if (tile * WIDE_TILE >= nn) {   // nothing left for this tile (a vector that was mostly zero digits)
+    for (u32 b = tid; b < bins; b += WIDE_THREADS) counts[(u64)b * num_tiles + tile] = 0;
+    return;
+  }
+  for (u32 b = tid; b < WIDE_MAX_BINS; b += WIDE_THREADS) hist[b] = 0;
+  __syncthreads();
+#pragma unroll 4
+  for (int r = 0; r < WIDE_ROUNDS; r++) {
+    const u32 idx = tile * WIDE_TILE + r * WIDE_THREADS + tid;
+    if (idx < nn) atomicAdd(&hist[wide_bin(pairs[idx], shift, bin_mask)], 1u);
+  }
+  __syncthreads();
+  for (u32 b = tid; b < bins; b += WIDE_THREADS) counts[(u64)b * num_tiles + tile] = hist[b];
+}
+
+// after the first pass's scan: the entries it keeps, as the count of those it drops
+__global__ void sort_live_kernel(const u32 *scanned_total, u32 *zstart, u32 n) { zstart[0] = n - *scanned_total; }
+
+// lanes of the wavefront whose (valid) entry falls into the same bin as this lane's
+__device__ __forceinline__ u64 wide_match(u32 bin, bool valid, u32 bits) {
+  u64 mask = __ballot(valid);
+  for (u32 b = 0; b < bits; b++) {
+    const bool bit = (bin >> b) & 1;
+    const u64 bal = __ballot(bit);
+    mask &= bit ? bal : ~bal;
+  }
+  return mask;
+}
+
+// FUSED: the first pass (entries recoded from the scalars of the tile); otherwise a later pass over the n - *live_from
+// entries the first one kept.  `out_shift` (last pass): the sorted entries go to the END of the array.
+template <bool FUSED>
+__global__ __launch_bounds__(WIDE_THREADS) void wide_scatter_kernel(WideDigits a, const u64 *pairs_in, u64 *pairs_out,
+                                                                    const u32 *offsets, u32 n, u32 shift, u32 bits,
+                                                                    u32 num_tiles, const u32 *live_from, const u32 *out_shift) {
+  __shared__ u64 stage[WIDE_TILE];                         // the tile, sorted (64 KiB); first the per-wavefront bin counts
+  __shared__ unsigned short wbase[WIDE_WAVES][WIDE_MAX_BINS];   // next position of every bin's run, per wavefront
+  __shared__ u32 gbase[WIDE_MAX_BINS];                     // global position of a bin's run minus its position in the tile
+  __shared__ u32 wsum[WIDE_WAVES];
+  u32(*wcnt)[WIDE_MAX_BINS] = reinterpret_cast<u32(*)[WIDE_MAX_BINS]>(stage);
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
+  const u32 bins = 1u << bits, bin_mask = bins - 1;
+  u32 nn = 0;
+  if (!FUSED) {
+    nn = n - *live_from;
+    if (tile * WIDE_TILE >= nn) return;   // (uniform over the workgroup: before any barrier)
+  }
+  u32 goff[WIDE_BPT];
+#pragma unroll
+  for (int k = 0; k < WIDE_BPT; k++) goff[k] = tid * WIDE_BPT + k < bins ? offsets[(u64)(tid * WIDE_BPT + k) * num_tiles + tile] : 0;
+#pragma unroll
+  for (int v = 0; v < WIDE_WAVES; v++)
+#pragma unroll
+    for (int k = 0; k < WIDE_MAX_BINS / WIDE_THREADS; k++) wcnt[v][k * WIDE_THREADS + tid] = 0;
+  __syncthreads();
+  if (out_shift) pairs_out += *out_shift;
+  const u64 lt_mask = ((u64)1 << lane) - 1;
+
+  // the thread's share of the tile, in registers: scalars (first pass) or entries; wavefront `wave` owns a contiguous
+  // eighth of the entries
+  fr_t sc[FUSED ? WIDE_SCALARS : 1];
+  u32 rec[FUSED ? WIDE_SCALARS : 1];
+  bool live[FUSED ? WIDE_SCALARS : 1];
+  u64 keys[FUSED ? 1 : WIDE_ROUNDS];
+  const u32 first = tile * WIDE_TILE + wave * (WIDE_TILE / WIDE_WAVES) + lane;
+  if (FUSED) {
+#pragma unroll
+    for (int j = 0; j < WIDE_SCALARS; j++) {
+      const u32 local = j * WIDE_THREADS + tid, i = tile * a.spt + local;
+      live[j] = local < a.spt && i < a.nd && wide_load_scalar(a, i, sc[j], rec[j], nullptr);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < WIDE_ROUNDS; r++) keys[r] = first + r * 64 < nn ? pairs_in[first + r * 64] : 0;
+  }
+  // 1. bin counts per wavefront
+  if (FUSED) {
+#pragma unroll
+    for (int j = 0; j < WIDE_SCALARS; j++) {
+      if (!live[j]) continue;
+      fr_t s = sc[j];
+      u32 carry = 0;
+      for (u32 w = 0; w < a.Wd; w++) {
+        const u64 e = wide_next_digit(s, carry, a.c);
+        if ((u32)(e >> 32)) atomicAdd(&wcnt[wave][wide_bin(e, 0, bin_mask)], 1u);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < WIDE_ROUNDS; r++)
+      if (first + r * 64 < nn) atomicAdd(&wcnt[wave][wide_bin(keys[r], shift, bin_mask)], 1u);
+  }
+  __syncthreads();
+  // 2. exclusive prefix over (bin, wavefront): where every wavefront's part of a bin's run starts inside the sorted tile
+  u32 cnt[WIDE_BPT][WIDE_WAVES], mine = 0, tile_total = 0;
+#pragma unroll
+  for (int k = 0; k < WIDE_BPT; k++)
+#pragma unroll
+    for (int v = 0; v < WIDE_WAVES; v++) { cnt[k][v] = wcnt[v][tid * WIDE_BPT + k]; mine += cnt[k][v]; }
+  {
+    u32 x = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const u32 y = __shfl_up(x, off);
+      if (lane >= (u32)off) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();   // ... and every count has been read: the staging area is free
+    u32 run = x - mine;
+#pragma unroll
+    for (int v = 0; v < WIDE_WAVES; v++) {
+      if ((u32)v < wave) run += wsum[v];
+      tile_total += wsum[v];
+    }
+#pragma unroll
+    for (int k = 0; k < WIDE_BPT; k++) {
+      gbase[tid * WIDE_BPT + k] = goff[k] - run;
+#pragma unroll
+      for (int v = 0; v < WIDE_WAVES; v++) { wbase[v][tid * WIDE_BPT + k] = (unsigned short)run; run += cnt[k][v]; }
+    }
+    __syncthreads();
+  }
+  // 3. ranking: wavefront-local (its own row of wbase, LDS operations of a wavefront execute in order)
+  auto place = [&](u64 e, bool valid, u32 sh) {
+    const u32 bin = wide_bin(e, sh, bin_mask);
+    const u64 mask = wide_match(bin, valid, bits);
+    const u32 rank = (u32)__popcll(mask & lt_mask);
+    u32 pos = 0;
+    if (valid) pos = wbase[wave][bin];
+    __builtin_amdgcn_wave_barrier();
+    if (valid) {
+      stage[pos + rank] = e;
+      if (rank == 0) wbase[wave][bin] = (unsigned short)(pos + (u32)__popcll(mask));
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
+  if (FUSED) {
+#pragma unroll
+    for (int j = 0; j < WIDE_SCALARS; j++) {
+      if (j * WIDE_THREADS + wave * 64 >= a.spt) continue;   // (uniform over the wavefront)
+      fr_t s = sc[j];
+      u32 carry = 0, r = rec[j];
+      for (u32 w = 0; w < a.Wd; w++) {
+        // with a window table digit w of base k adds row w of the table: 2^(c*w) P_k
+        const u64 e = wide_next_digit(s, carry, a.c) | (r & 0x7fffffffu);
+        r += a.stride;
+        place(e, live[j] && (u32)(e >> 32) != 0, 0);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < WIDE_ROUNDS; r++) place(keys[r], first + r * 64 < nn, shift);
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (u32 j = tid; j < tile_total; j += WIDE_THREADS) {
+    const u64 e = stage[j];
+    pairs_out[gbase[wide_bin(e, shift, bin_mask)] + j] = e;
   }
 }
 
@@ -401,7 +652,7 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
   p.NB = p.nb;
   p.lo_bits = (p.c - 1) / 2;
   p.hi_bits = (p.c - 1) - p.lo_bits;
-  p.num_tiles = (p.n + SORT_TILE - 1) / SORT_TILE;
+  p.num_tiles = (p.n + WIDE_TILE - 1) / WIDE_TILE;   // of the passes after the first (sort_counts_elems)
   // K: at least the average bucket, so that a typical run touches two chunks (one partial to fold) - shorter chunks
   // turn EVERY bucket into a multi-chunk run and the merge into the dominant cost (profiles/archive/r2_call3_*)
   const u32 lg = ilog2(p.n ? p.n : 1);
@@ -445,7 +696,7 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
   }
   p.chunk = forced_chunk ? forced_chunk : (u32)k;
   p.chunks_per_window = (p.n + p.chunk - 1) / p.chunk;
-  p.sort_passes = (p.c + 7) / 8;
+  p.sort_passes = wide_passes(p.c);
   return p;
 }
 
@@ -453,7 +704,6 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
 int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_dev, int fmt, const u64 *density_dev,
                    u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out) {
   const u64 n = p.nd;   // scalars (the density bitmap is indexed by scalar)
-  const u64 ncounts = (u64)p.W * 256 * p.num_tiles;
   const u64 nwords = (n + 63) / 64;
   if (density_dev) {
     hipLaunchKernelGGL(density_popc_kernel, dim3((u32)((nwords + 255) / 256)), dim3(256), 0, st, density_dev,
@@ -462,38 +712,69 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
     int rc = exclusive_scan_u32(b.word_prefix, nwords, b.scan_tmp, st);
     if (rc) return rc;
   }
+  if (p.W == 1) {
+    // one bucket set: digits and sort in one stage (2b above) - the first pass recodes the scalars and keeps the non-zero
+    // digits (*zstart = how many it dropped), the last pass writes them to the END of the array, so that what follows
+    // sees *zstart entries to skip and then the sorted stream
+    WideDigits a;
+    a.scalars = scalars_dev; a.density = density_dev; a.word_prefix = b.word_prefix; a.skip = skip; a.n_bases = n_bases;
+    a.fmt = (u32)fmt; a.nd = p.nd; a.c = p.c; a.Wd = p.Wd; a.stride = (u32)p.base_stride; a.spt = wide_scalars_per_tile(p.Wd);
+    const u32 tiles0 = wide_first_tiles(p);
+    u64 *src = b.pairs_b, *dst = b.pairs_a;   // (the first pass has no source array)
+    u32 shift = 0;
+    for (u32 pass = 0; pass < p.sort_passes; pass++) {
+      const u32 bits = wide_pass_bits(p.c, pass);
+      const bool first = pass == 0, last = pass + 1 == p.sort_passes;
+      const u32 tiles = first ? tiles0 : p.num_tiles;
+      const u64 ncounts = ((u64)1 << bits) * tiles;
+      const u32 *out_shift = last ? b.zstart : nullptr;
+      if (first)
+        hipLaunchKernelGGL(wide_hist_digits_kernel, dim3(tiles), dim3(WIDE_THREADS), 0, st, a, b.counts, tiles, bits, b.err);
+      else
+        hipLaunchKernelGGL(wide_hist_kernel, dim3(tiles), dim3(WIDE_THREADS), 0, st, src, b.counts, p.n, shift, bits, tiles,
+                           b.zstart);
+      BH_HIP_CHECK(hipGetLastError());
+      int rc = exclusive_scan_u32(b.counts, ncounts + (first ? 1 : 0), b.scan_tmp, st);
+      if (rc) return rc;
+      if (first) {
+        hipLaunchKernelGGL(sort_live_kernel, dim3(1), dim3(1), 0, st, b.counts + ncounts, b.zstart, p.n);
+        BH_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(wide_scatter_kernel<true>, dim3(tiles), dim3(WIDE_THREADS), 0, st, a, (const u64 *)nullptr, dst,
+                           b.counts, p.n, 0u, bits, tiles, (const u32 *)nullptr, out_shift);
+      } else {
+        hipLaunchKernelGGL(wide_scatter_kernel<false>, dim3(tiles), dim3(WIDE_THREADS), 0, st, a, src, dst, b.counts, p.n,
+                           shift, bits, tiles, b.zstart, out_shift);
+      }
+      BH_HIP_CHECK(hipGetLastError());
+      std::swap(src, dst);
+      shift += bits;
+    }
+    *sorted_out = src;
+    return BH_OK;
+  }
   // 1. digits
   hipLaunchKernelGGL(msm_digits_kernel, dim3((p.nd + 255) / 256), dim3(256), 0, st, scalars_dev, fmt, p.nd,
                      density_dev, b.word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, b.pairs_a, b.err);
   BH_HIP_CHECK(hipGetLastError());
-  // 2. sort by digit, 8 bits per pass; one bucket set: zero digits dropped by the first pass (the classic plan's windows
-  // sort them to the front)
-  const bool drop = p.W == 1;
+  // 2. sort every window by digit, 8 bits per pass; the zero digits sort to the front
+  const u64 ncounts = (u64)p.W * 256 * p.num_tiles;
   u64 *src = b.pairs_a, *dst = b.pairs_b;
   for (u32 pass = 0; pass < p.sort_passes; pass++) {
     const u32 shift = 32 + 8 * pass;
-    const bool first = pass == 0, last = pass + 1 == p.sort_passes;
-    const u32 *live_from = (drop && !first) ? b.zstart : nullptr;
     hipLaunchKernelGGL(sort_hist_kernel, dim3(p.num_tiles, p.W), dim3(SORT_THREADS), 0, st, src, b.counts, p.n,
-                       shift, p.num_tiles, (drop && first) ? 1u : 0u, live_from);
+                       shift, p.num_tiles);
     BH_HIP_CHECK(hipGetLastError());
-    int rc = exclusive_scan_u32(b.counts, ncounts + ((drop && first) ? 1 : 0), b.scan_tmp, st);
+    int rc = exclusive_scan_u32(b.counts, ncounts, b.scan_tmp, st);
     if (rc) return rc;
-    if (drop && first) {
-      hipLaunchKernelGGL(sort_live_kernel, dim3(1), dim3(1), 0, st, b.counts + ncounts, b.zstart, p.n);
-      BH_HIP_CHECK(hipGetLastError());
-    }
     hipLaunchKernelGGL(sort_scatter_kernel, dim3(p.num_tiles, p.W), dim3(SORT_THREADS), 0, st, src, dst, b.counts,
-                       p.n, shift, p.num_tiles, (drop && first) ? 1u : 0u, live_from, (drop && last) ? b.zstart : nullptr);
+                       p.n, shift, p.num_tiles);
     BH_HIP_CHECK(hipGetLastError());
     std::swap(src, dst);
   }
   *sorted_out = src;
   // 3. where the non-zero digits start in every window
-  if (!drop) {
-    hipLaunchKernelGGL(window_zero_count_kernel, dim3((p.W + 63) / 64), dim3(64), 0, st, src, b.zstart, p.n, p.W);
-    BH_HIP_CHECK(hipGetLastError());
-  }
+  hipLaunchKernelGGL(window_zero_count_kernel, dim3((p.W + 63) / 64), dim3(64), 0, st, src, b.zstart, p.n, p.W);
+  BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
 

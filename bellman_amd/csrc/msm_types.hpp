@@ -126,6 +126,7 @@ MsmPlan make_plan(u64 n, unsigned forced_c, unsigned forced_chunk, bool g2);
 MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool g2, int num_cus);
 unsigned table_window_bits(u64 n_bases, bool g2);   // the c a window table is built for by default
 size_t scan_tmp_elems(u64 n);
+size_t sort_counts_elems(const MsmPlan &p);   // MsmBuffers::counts holds this many + 1, scan_tmp scan_tmp_elems of that
 // runs stages 1-2 (+ per-window first non-zero position) on `st`; *sorted_out = sorted pairs
 int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_dev, int fmt, const u64 *density_dev,
                    u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out);
