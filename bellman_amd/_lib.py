@@ -31,7 +31,7 @@ EXPORTS = [
     "bh_fft_fr", "bh_fft_fr_dev", "bh_fr_mul_assign_dev", "bh_fr_sub_assign_dev",
     "bh_fr_divide_by_z_on_coset_dev", "bh_fr_distribute_powers_dev", "bh_fft_point_dev", "bh_point_distribute_powers_dev", "bh_point_divide_by_z_on_coset_dev",
     "bh_point_mul_assign_dev", "bh_point_sub_assign_dev", "bh_h_poly_fr", "bh_h_poly_fr_dev", "bh_h_poly_fr_dev_on",
-    "bh_bases_register", "bh_bases_register_uncompressed", "bh_bases_read_uncompressed", "bh_bases_download", "bh_bases_write_uncompressed", "bh_bases_copy_dev", "bh_bases_precompute", "bh_bases_table_info", "bh_bases_wrap_dev", "bh_bases_release", "bh_bases_len",
+    "bh_bases_register", "bh_bases_register_uncompressed", "bh_bases_read_uncompressed", "bh_bases_read_compressed", "bh_bases_download", "bh_bases_write_uncompressed", "bh_bases_copy_dev", "bh_bases_precompute", "bh_bases_table_info", "bh_bases_wrap_dev", "bh_bases_release", "bh_bases_len",
     "bh_msm_async", "bh_msm_async_dev", "bh_msm_wait", "bh_msm_wait_timed", "bh_msm_wait_profile", "bh_msm_wait_stats", "bh_msm_plan_info", "bh_msm_debug_stages", "bh_point_add", "bh_point_mul", "bh_point_lincomb", "bh_msm_async_opts", "bh_msm_async_dev_opts",
     "bh_scalars_register", "bh_scalars_adopt_dev", "bh_scalars_release", "bh_scalars_len", "bh_scalars_dev_ptr", "bh_msm_async_scalars", "bh_h_poly_fr_scalars", "bh_msm_async_dev_after", "bh_msm_start",
     "bh_msm_sharded_async", "bh_msm_sharded_wait",
@@ -41,7 +41,7 @@ EXPORTS = [
     "bh_groth16_prove_witness", "bh_groth16_prove_assignment_async", "bh_groth16_prove_witness_async", "bh_groth16_proof_wait",
     "bh_groth16_prove_witness_part", "bh_groth16_sums_add", "bh_groth16_assemble",
     "bh_groth16_prepare_verifying_key", "bh_groth16_pvk_from_params", "bh_groth16_pvk_num_inputs", "bh_groth16_verify",
-    "bh_groth16_batch_verify", "bh_groth16_pvk_release",
+    "bh_groth16_batch_verify", "bh_groth16_pvk_release", "bh_proofs_read", "bh_groth16_batch_verify_compressed",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -49,7 +49,7 @@ TEST_EXPORTS = [
     "bh_test_fr_mul_dev", "bh_test_fp_mul_dev", "bh_test_point_add_dev", "bh_test_g2_k3_dev", "bh_test_g2_pairs_dev", "bh_test_g2_k6_dev",
     "bh_test_fr_mul_host", "bh_test_fr_mul_bform_host", "bh_test_fp_mul_host", "bh_test_point_add_host", "bh_test_point_mul_host", "bh_test_fr_inv_host", "bh_test_fp_lazy_host", "bh_test_proof_slice", "bh_test_synthesis_ms", "bh_test_fr_from_u512_host", "bh_test_fr_ops_host",
     "bh_test_groth16_prove_via_call_sites", "bh_test_demo_assignment", "bh_test_shard_cuts", "bh_test_pool_size_class", "bh_test_capture_check",
-    "bh_test_pairing", "bh_test_pairing_host",
+    "bh_test_pairing", "bh_test_pairing_host", "bh_test_fp_sqrt_host", "bh_test_fp2_sqrt_host",
 ]
 
 
@@ -223,6 +223,7 @@ def load():
     lib.bh_fr_qap_ext_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     lib.bh_proof_write.restype = None
     lib.bh_bases_read_uncompressed.argtypes = [vp, i32, vp, sz, c.c_uint, c.POINTER(vp), c.POINTER(sz)]
+    lib.bh_bases_read_compressed.argtypes = [vp, i32, vp, sz, c.c_uint, c.POINTER(vp), c.POINTER(sz)]
     lib.bh_bases_download.argtypes = [vp, vp, sz, sz, vp]
     lib.bh_bases_write_uncompressed.argtypes = [vp, vp, sz, sz, vp]
     lib.bh_groth16_params_release.restype = None
@@ -251,6 +252,8 @@ def load():
     lib.bh_groth16_pvk_num_inputs.restype = sz
     lib.bh_groth16_verify.argtypes = [vp, vp, vp, sz, i32]
     lib.bh_groth16_batch_verify.argtypes = [vp, vp, sz, vp, sz, i32, vp]
+    lib.bh_proofs_read.argtypes = [vp, vp, sz, vp, vp, c.POINTER(sz)]
+    lib.bh_groth16_batch_verify_compressed.argtypes = [vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
     lib.bh_groth16_pvk_release.argtypes = [vp]
     lib.bh_groth16_pvk_release.restype = None
     lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]
@@ -266,6 +269,9 @@ def load():
     lib.bh_test_g2_pairs_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz]
     lib.bh_test_g2_k6_dev.argtypes = [vp, vp, vp, vp, sz]
     for name in ("bh_test_fr_mul_host", "bh_test_fp_mul_host", "bh_test_fr_mul_bform_host"):
+        getattr(lib, name).argtypes = [vp, vp, vp, sz]
+        getattr(lib, name).restype = None
+    for name in ("bh_test_fp_sqrt_host", "bh_test_fp2_sqrt_host"):
         getattr(lib, name).argtypes = [vp, vp, vp, sz]
         getattr(lib, name).restype = None
     lib.bh_test_fr_inv_host.argtypes = [vp, vp, sz]

@@ -838,6 +838,43 @@ int bh_bases_read_uncompressed(bh_ctx *ctx, int group, const void *host_bytes, s
   }
   return new_bases(ctx, group, dev.release(), n, true, out);
 }
+// from_compressed / from_compressed_unchecked for n points (point_read.hip): the twin of bh_bases_read_uncompressed
+int bh_bases_read_compressed(bh_ctx *ctx, int group, const void *host_bytes, size_t n, unsigned flags, bh_bases **out,
+                             size_t *bad_index) {
+  if (!ctx || !out || (group != BH_G1 && group != BH_G2) || (n && !host_bytes)) return BH_ERR_INVALID_ARG;
+  const size_t rec = group == BH_G1 ? 96 : 192, enc = rec / 2;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  DevGuard dev;
+  BH_HIP_CHECK(hipMalloc(&dev.p, n ? n * rec : 16));
+  if (n) {
+    hipStream_t st = ctx->c.stream;
+    DevGuard raw;
+    const size_t status_off = (n * enc + 15) & ~size_t(15);
+    BH_HIP_CHECK(hipMalloc(&raw.p, status_off + n * 4 + 16));
+    u32 *status = (u32 *)((char *)raw.p + status_off);
+    unsigned long long *min_idx = (unsigned long long *)((char *)status + ((n * 4 + 7) & ~size_t(7)));
+    unsigned long long first = ~0ULL;
+    u32 first_status = 0;
+    BH_HIP_CHECK(hipMemcpyAsync(raw.p, host_bytes, n * enc, hipMemcpyHostToDevice, st));
+    BH_HIP_CHECK(hipMemsetAsync(min_idx, 0xff, 8, st));
+    const ReadLayout lay = {enc, 0, 0, rec, 0, 0, 1, 1, 0, 0};
+    int r = points_read_compressed(group, raw.p, dev.p, n, lay, (flags & BH_POINTS_CHECKED) != 0, status, st);
+    if (r != BH_OK) { (void)hipStreamSynchronize(st); return r; }
+    const u64 blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(first_bad_point_kernel, dim3((u32)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, status,
+                       (u64)n, (flags & BH_POINTS_FORBID_IDENTITY) ? 1u : 0u, min_idx);
+    BH_HIP_CHECK(hipGetLastError());
+    BH_HIP_CHECK(hipMemcpyAsync(&first, min_idx, 8, hipMemcpyDeviceToHost, st));
+    BH_HIP_CHECK(hipStreamSynchronize(st));
+    if (first != ~0ULL) {
+      BH_HIP_CHECK(hipMemcpyAsync(&first_status, status + first, 4, hipMemcpyDeviceToHost, st));
+      BH_HIP_CHECK(hipStreamSynchronize(st));
+      if (bad_index) *bad_index = (size_t)first;
+      return (first_status & PT_INVALID_MASK) ? BH_ERR_INVALID_POINT : BH_ERR_POINT_AT_INFINITY;
+    }
+  }
+  return new_bases(ctx, group, dev.release(), n, true, out);
+}
 int bh_bases_download(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, void *out_host) {
   if (!ctx || !b || first + count > b->n) return BH_ERR_INVALID_ARG;
   const size_t rec = b->group == BH_G1 ? 96 : 192;

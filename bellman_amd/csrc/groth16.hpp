@@ -470,6 +470,11 @@ struct G2Affine { uint64_t v[24]; bool is_identity() const; };
 struct Proof {                                                    // groth16/src/lib.rs:25-30
   G1Affine a; G2Affine b; G1Affine c;
   void write(unsigned char out[192]) const;                       // :38-46 compressed A | B | C
+  // Proof::read (:47-99): the three points decompressed and checked on the device (bh_proofs_read).  Throws IoError:
+  // BH_ERR_INVALID_POINT ("invalid G1" / "invalid G2") or BH_ERR_POINT_AT_INFINITY, for the first bad element a, b, c.
+  static Proof read(bh_ctx *ctx, const unsigned char in[192]);
+  // the same over n concatenated proofs; the error is the first bad proof's, its position in *bad_index (optional)
+  static std::vector<Proof> read(bh_ctx *ctx, const unsigned char *in, size_t n, size_t *bad_index = nullptr);
 };
 
 struct VerifyingKey {                                             // groth16/src/lib.rs:91-128

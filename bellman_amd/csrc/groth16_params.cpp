@@ -283,6 +283,26 @@ void Proof::write(unsigned char out[192]) const {
   g1(c, out + 144);
 }
 
+// ---- groth16/src/lib.rs:47-99 (Proof::read) -----------------------------------------------------------
+std::vector<Proof> Proof::read(bh_ctx *ctx, const unsigned char *in, size_t n, size_t *bad_index) {
+  static_assert(sizeof(Proof) == 384, "a | b | c as the C ABI writes them");
+  std::vector<Proof> out(n);
+  std::vector<uint32_t> status(n);
+  size_t bad = 0;
+  const int rc = bh_proofs_read(ctx, in, n, out.data(), status.data(), &bad);
+  if (rc == BH_ERR_INVALID_POINT || rc == BH_ERR_POINT_AT_INFINITY) {
+    if (bad_index) *bad_index = bad;
+    // the first bad element in the order a, b, c names the group of "invalid G1" / "invalid G2"
+    const uint32_t w = status[bad];
+    const bool b_first = !(w & 0xffu) && (w & 0xff00u);
+    if (rc == BH_ERR_POINT_AT_INFINITY) throw bellman::IoError(rc, "point at infinity");
+    throw bellman::IoError(rc, b_first ? "invalid G2" : "invalid G1");
+  }
+  if (rc != BH_OK) throw std::runtime_error("bh_proofs_read failed with code " + std::to_string(rc));
+  return out;
+}
+Proof Proof::read(bh_ctx *ctx, const unsigned char in[192]) { return read(ctx, in, 1)[0]; }
+
 Parameters::~Parameters() {
   bh_bases_release(ctx, h); bh_bases_release(ctx, l); bh_bases_release(ctx, a);
   bh_bases_release(ctx, b_g1); bh_bases_release(ctx, b_g2);

@@ -150,8 +150,23 @@ enum PointStatus : u32 {
   PT_IS_INF = 16,           // (valid) identity
   PT_OFF_CURVE = 32,
   PT_NOT_IN_SUBGROUP = 64,
-  PT_INVALID_MASK = PT_COMPRESSED | PT_SORT | PT_RANGE | PT_INF_NONZERO | PT_OFF_CURVE | PT_NOT_IN_SUBGROUP,
+  PT_NOT_COMPRESSED = 128,  // compression flag clear on a compressed point (set by the compressed reader only)
+  PT_INVALID_MASK = PT_COMPRESSED | PT_SORT | PT_RANGE | PT_INF_NONZERO | PT_OFF_CURVE | PT_NOT_IN_SUBGROUP | PT_NOT_COMPRESSED,
 };
+// The compressed reader (point_read.hip) uses the same word: PT_SORT = sort flag on an infinity encoding, PT_OFF_CURVE =
+// x^3 + b is not a square (no point has this x).  Where lane i of its kernel finds its point, its record and its status
+// word: group g = i / per, element e = i % per; byte offsets g * stride + first + e * step (status: in words).
+struct ReadLayout {
+  size_t in_stride, in_first, in_step;
+  size_t out_stride, out_first, out_step;
+  u32 per;
+  u32 st_stride, st_first, st_step;
+};
+int points_read_compressed(int group, const void *raw_dev, void *out_dev, u64 n, const ReadLayout &lay, bool checked,
+                           u32 *status_dev, hipStream_t st);
+int proofs_read_dev(const void *bytes_dev, void *proofs_out_dev, u64 n, u32 *pst, u32 *words, unsigned long long *min_idx,
+                    hipStream_t st);
+int proof_status_error(u32 word);
 // on-curve + prime-order-subgroup test of decoded points (skips entries already invalid / identity)
 // fills rows 1 .. W-1 of a window table whose row 0 holds the n bases
 int window_table_g1(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st);

@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "final_exp.cuh"
 #include "fp12.cuh"
+#include "msm_types.hpp"
 
 namespace bh {
 
@@ -504,12 +505,19 @@ int bh_groth16_verify(const bh_pvk *pvk, const void *proof, const void *inputs, 
   return one ? BH_OK : BH_ERR_INVALID_PROOF;
 }
 
+}  // extern "C"
+
 // batch::Verifier::verify (groth16/src/verifier/batch.rs:93-192) with the caller's z_j:
 //   prod_j e([z_j] A_j, -B_j) * e(-sum z_j C_j, -delta) * e(-Psi, -gamma) * e([acc_Y] alpha, beta) == 1
 // (e(X, Y) = e(-X, -Y): the prepared key's -gamma / -delta lines serve both verifiers).
-int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
-                            int scalar_fmt, const void *z) {
-  if (!pvk || (n_proofs && (!proofs || !z)) || (n_proofs && n_inputs && !inputs) ||
+// `proofs`: affine records (384 B each), or NULL with `bytes`: Proof::write's 192 B per proof, decoded chunk by chunk on
+// the verifier's stream (Proof::read: every point checked, the identity refused).  The batch is walked ONCE: a chunk is
+// decoded right in front of its Miller loops; the first chunk with a bad proof ends the call with that proof's read
+// error - chunks are taken in stream order, so it is the first bad proof of the batch - and as the verdict only exists
+// after the last chunk, a read error anywhere comes before BH_ERR_INVALID_PROOF.
+static int batch_verify_impl(const bh_pvk *pvk, const void *proofs, const void *bytes, size_t n_proofs, const void *inputs,
+                             size_t n_inputs, int scalar_fmt, const void *z, size_t *bad_index) {
+  if (!pvk || (n_proofs && ((!proofs && !bytes) || !z)) || (n_proofs && n_inputs && !inputs) ||
       (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT))
     return BH_ERR_INVALID_ARG;
   if (n_inputs + 1 != pvk->n_ic) return BH_ERR_INVALID_VERIFYING_KEY;   // batch.rs:101-107
@@ -541,6 +549,10 @@ int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proo
   fr_t *acc = bufs.get<fr_t>(ncol);
   Affine<FpOps> *key = bufs.get<Affine<FpOps>>(3);
   Affine<FpOps> *gen = bufs.get<Affine<FpOps>>(1);
+  unsigned char *cbytes = bytes ? bufs.get<unsigned char>(ch * 192) : nullptr;   // the chunk as written, its per-point and
+  u32 *pst = bytes ? bufs.get<u32>(4 * ch) : nullptr;                            // per-proof status words, the first bad proof
+  unsigned long long *first_bad = bytes ? bufs.get<unsigned long long>(1) : nullptr;
+  if (bytes && (!cbytes || !pst || !first_bad)) return BH_ERR_HIP;
   if (!pr || !zd || !ind || !pts || !cb || !zc || !lines || !pflags || !qflags || !f || !facc || !part || !acc || !key || !gen) {
     fprintf(stderr, "[bellman_hip] batch verification: no device memory for a %zu-proof chunk\n", ch);
     return BH_ERR_HIP;
@@ -558,10 +570,23 @@ int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proo
   memset(&sum_c, 0, sizeof sum_c);
   u32 bad = 0;
   std::vector<u32> hflags(ch), hqflags(ch);
+  unsigned long long hbad = ~0ULL;   // first proof of the chunk that Proof::read refuses
   for (size_t first = 0; first < n_proofs && !rc; first += ch) {
     const size_t m = n_proofs - first < ch ? n_proofs - first : ch;
-    if (hipMemcpyAsync(pr, (const ProofRec *)proofs + first, m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(zd, (const fr_t *)z + first, m * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
+    hbad = ~0ULL;
+    if (bytes) {
+      if (hipMemcpyAsync(cbytes, (const unsigned char *)bytes + first * 192, m * 192, hipMemcpyHostToDevice, st) != hipSuccess ||
+          hipMemsetAsync(first_bad, 0xff, 8, st) != hipSuccess) {
+        rc = BH_ERR_HIP;
+        break;
+      }
+      if ((rc = proofs_read_dev(cbytes, pr, m, pst, pst + 3 * ch, first_bad, st))) break;
+      if (hipMemcpyAsync(&hbad, first_bad, 8, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = BH_ERR_HIP; break; }
+    } else if (hipMemcpyAsync(pr, (const ProofRec *)proofs + first, m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      rc = BH_ERR_HIP;
+      break;
+    }
+    if (hipMemcpyAsync(zd, (const fr_t *)z + first, m * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
         (n_inputs && hipMemcpyAsync(ind, (const fr_t *)inputs + first * n_inputs, m * n_inputs * 32, hipMemcpyHostToDevice, st) !=
                          hipSuccess)) {
       rc = BH_ERR_HIP;
@@ -600,6 +625,14 @@ int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proo
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
     bh_bases_release(ctx, cbases);
     if (rc) break;
+    if (hbad != ~0ULL) {   // Proof::read failed in this chunk (its points went on as identities; the result is dropped)
+      u32 word = 0;
+      if (hipMemcpyAsync(&word, pst + 3 * ch + hbad, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return BH_ERR_HIP;
+      if (bad_index) *bad_index = first + (size_t)hbad;
+      return proof_status_error(word);
+    }
     bh_point_add(BH_G1, &sum_c, &sum_c, &part_c, 1);
     for (size_t j = 0; j < m; j++) bad |= hflags[j] | (hqflags[j] & PF_OFF_CURVE);
   }
@@ -625,6 +658,62 @@ int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proo
   bool ok = false;
   if ((rc = finish_check(st, pvk, bufs, key, 0, nullptr, nullptr, facc, qflags, &ok))) return rc;
   return ok ? BH_OK : BH_ERR_INVALID_PROOF;
+}
+
+extern "C" {
+
+int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
+                            int scalar_fmt, const void *z) {
+  if (n_proofs && !proofs) return BH_ERR_INVALID_ARG;
+  return batch_verify_impl(pvk, proofs, nullptr, n_proofs, inputs, n_inputs, scalar_fmt, z, nullptr);
+}
+
+// Proof::read of every proof (groth16/src/lib.rs:47-99), then batch::Verifier::verify, the decoded proofs never leaving
+// the device
+int bh_groth16_batch_verify_compressed(const bh_pvk *pvk, const void *bytes, size_t n_proofs, const void *inputs,
+                                       size_t n_inputs, int scalar_fmt, const void *z, size_t *bad_index) {
+  if (n_proofs && !bytes) return BH_ERR_INVALID_ARG;
+  return batch_verify_impl(pvk, nullptr, bytes, n_proofs, inputs, n_inputs, scalar_fmt, z, bad_index);
+}
+
+// Proof::read over n concatenated 192-byte proofs: chunks of at most BATCH_CHUNK proofs on a stream of the call's own
+int bh_proofs_read(bh_ctx *ctx, const void *bytes, size_t n_proofs, void *out_proofs_affine, uint32_t *status,
+                   size_t *bad_index) {
+  if (!ctx || (n_proofs && (!bytes || !out_proofs_affine))) return BH_ERR_INVALID_ARG;
+  if (!n_proofs) return BH_OK;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) return BH_ERR_HIP;
+  hipStream_t st = sh.st;
+  const size_t ch = std::min(n_proofs, BATCH_CHUNK);
+  unsigned char *cbytes = bufs.get<unsigned char>(ch * 192);
+  ProofRec *pr = bufs.get<ProofRec>(ch);
+  u32 *pst = bufs.get<u32>(4 * ch);
+  unsigned long long *first_bad = bufs.get<unsigned long long>(1);
+  if (!cbytes || !pr || !pst || !first_bad) return BH_ERR_HIP;
+  std::vector<u32> words(ch);
+  int result = BH_OK;
+  for (size_t first = 0; first < n_proofs; first += ch) {
+    const size_t m = std::min(ch, n_proofs - first);
+    unsigned long long hbad = ~0ULL;
+    if (hipMemcpyAsync(cbytes, (const unsigned char *)bytes + first * 192, m * 192, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(first_bad, 0xff, 8, st) != hipSuccess)
+      return BH_ERR_HIP;
+    const int rc = proofs_read_dev(cbytes, pr, m, pst, pst + 3 * ch, first_bad, st);
+    if (rc) return rc;
+    if (hipMemcpyAsync((ProofRec *)out_proofs_affine + first, pr, m * sizeof(ProofRec), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(words.data(), pst + 3 * ch, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&hbad, first_bad, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return BH_ERR_HIP;
+    if (status) memcpy(status + first, words.data(), m * 4);
+    if (hbad != ~0ULL && result == BH_OK) {
+      result = proof_status_error(words[hbad]);
+      if (bad_index) *bad_index = first + (size_t)hbad;
+    }
+  }
+  return result;
 }
 
 }  // extern "C"

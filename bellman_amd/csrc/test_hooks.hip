@@ -7,6 +7,7 @@
 #include "final_exp.cuh"
 #include "fp12.cuh"
 #include "msm_ec.cuh"
+#include "point_read.cuh"
 #include "shard_cuts.hpp"
 
 namespace bh {
@@ -189,6 +190,24 @@ void bh_test_fr_mul_bform_host(void *r, const void *a, const void *b, size_t n) 
 }
 void bh_test_fp_mul_host(void *r, const void *a, const void *b, size_t n) {
   for (size_t i = 0; i < n; i++) fe_mul(((fp_t *)r)[i], ((const fp_t *)a)[i], ((const fp_t *)b)[i]);
+}
+void bh_test_fp_sqrt_host(void *r, unsigned char *ok, const void *a, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    fp_t x, y;
+    memcpy(&x, (const char *)a + 48 * i, 48);
+    ok[i] = fp_sqrt(y, x) ? 1 : 0;
+    fpl_canon(y, y);
+    memcpy((char *)r + 48 * i, &y, 48);
+  }
+}
+void bh_test_fp2_sqrt_host(void *r, unsigned char *ok, const void *a, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    fp2_t x, y;
+    memcpy(&x, (const char *)a + 96 * i, 96);
+    ok[i] = fp2_sqrt(y, x) ? 1 : 0;
+    Fp2Ops::canon(y);
+    memcpy((char *)r + 96 * i, &y, 96);
+  }
 }
 int bh_test_fp_lazy_host(int op, void *r, const void *a, const void *b) {
   // the lazily reduced Fp helpers of the curve code (ff.cuh), compiled for the host; operands in [0, 2p)

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .errors import check
+from .errors import UnexpectedEof, check
 
 Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _R = (1 << 256) % Q
@@ -146,6 +146,42 @@ class Proof:
         out = np.zeros(192, dtype=np.uint8)
         _lib.load().bh_proof_write(raw.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p))
         return out.tobytes()
+
+
+    @classmethod
+    def read(cls, worker, data):
+        """Proof::read (groth16/src/lib.rs:47-99) of 192 bytes: the three points decompressed and checked on the device.
+        Raises UnexpectedEof for a shorter input (read_exact), InvalidPoint / PointAtInfinity for a bad element."""
+        data = bytes(data)
+        if len(data) < 192:
+            raise UnexpectedEof("failed to fill whole buffer")
+        return read_proofs(worker, data[:192])[0]
+
+
+def read_proofs(worker, data, return_status=False):
+    """Proof::read over concatenated 192-byte proofs (bh_proofs_read).  Returns the list of proofs; the first bad proof in
+    stream order raises InvalidPoint / PointAtInfinity with `.index` = its position.  return_status=True never raises
+    for a bad proof: it returns (proofs, status) with one uint32 per proof (0 = good; the bits are documented at
+    bh_proofs_read in include/bellman_hip.h) and None in place of every bad proof."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    if buf.size % 192:
+        raise UnexpectedEof("failed to fill whole buffer")
+    n = buf.size // 192
+    out = np.zeros((n, 48), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint32)
+    bad = ctypes.c_size_t(0)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    rc = _lib.load().bh_proofs_read(worker.ctx, p(buf) if n else None, n, p(out) if n else None, p(status), ctypes.byref(bad))
+    if return_status:
+        if rc not in (0, 6, 7):
+            check(rc, "proofs_read")
+        return [Proof(out[i]) if status[i] == 0 else None for i in range(n)], status
+    try:
+        check(rc, "proofs_read")
+    except IOError as e:
+        e.index = bad.value
+        raise
+    return [Proof(out[i]) for i in range(n)]
 
 
 class Parameters:

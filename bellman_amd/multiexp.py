@@ -114,6 +114,28 @@ class Bases:
         self._auto_precompute()
         return self
 
+    @classmethod
+    def read_compressed(cls, worker, group, data, checked=True, forbid_identity=True):
+        """`from_compressed` (checked: the square root exists and the point is in the prime-order subgroup) or
+        `from_compressed_unchecked` for concatenated compressed points (48 / 96 bytes each), plus the "point at infinity"
+        rule; all on the device.  Raises InvalidPoint / PointAtInfinity carrying `.index` = first offending point."""
+        enc = _WORDS[group] * 4
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        assert buf.size % enc == 0
+        self = cls.__new__(cls)
+        self.worker, self.group, self.n = worker, group, buf.size // enc
+        h, bad = ctypes.c_void_p(), ctypes.c_size_t(0)
+        flags = (1 if checked else 0) | (2 if forbid_identity else 0)
+        try:
+            check(_lib.load().bh_bases_read_compressed(worker.ctx, group, buf.ctypes.data_as(ctypes.c_void_p), self.n, flags,
+                                                       ctypes.byref(h), ctypes.byref(bad)), "bases_read_compressed")
+        except IOError as e:
+            e.index = bad.value
+            raise
+        self._h = h
+        self._auto_precompute()
+        return self
+
     def _auto_precompute(self):
         # BELLMAN_HIP_PRECOMPUTE=1 (or =<window bits>): build the window table at registration
         v = os.environ.get("BELLMAN_HIP_PRECOMPUTE", "")

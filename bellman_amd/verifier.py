@@ -2,7 +2,8 @@
 batch::Verifier (groth16/src/verifier/batch.rs), over include/bellman_hip.h's bh_groth16_* verifier entry points.
 
 Public inputs and the batch's random z are Fr values given as Python ints (canonical; taken mod q).  Proofs are
-`groth16.Proof` objects (affine Montgomery records).  The pairing arithmetic runs in HIP kernels (csrc/pairing.hip);
+`groth16.Proof` objects (affine Montgomery records: only the on-curve test is made) or the 192 bytes of `Proof::write`,
+which are read on the device as Proof::read reads them (decompression, subgroup checks, no identity).  The pairing arithmetic runs in HIP kernels (csrc/pairing.hip);
 there is no CPU path.
 """
 
@@ -12,7 +13,7 @@ import secrets
 import numpy as np
 
 from . import _lib
-from .errors import InvalidVerifyingKey, check, check_verification
+from .errors import InvalidVerifyingKey, UnexpectedEof, check, check_verification
 
 Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _CANONICAL = 0
@@ -67,9 +68,18 @@ def prepare_verifying_key(params):
     return PreparedVerifyingKey(params.worker, h, lib.bh_groth16_pvk_num_inputs(h))
 
 
+def _is_compressed(proof):
+    return isinstance(proof, (bytes, bytearray, memoryview))
+
+
 def verify_proof(pvk, proof, public_inputs):
     """verify_proof (groth16/src/verifier.rs:23-58): returns None, raises InvalidProof / InvalidVerifyingKey
-    (or InvalidPoint for a proof point that is not on its curve)"""
+    (or InvalidPoint for a proof point that is not on its curve).  `proof` may be the 192 bytes of Proof::write: they
+    go through Proof.read first (InvalidPoint / PointAtInfinity / UnexpectedEof)."""
+    if _is_compressed(proof):
+        from .groth16 import Proof
+
+        proof = Proof.read(pvk.worker, proof)
     raw = _proof_bytes(proof)
     ins = _fr_bytes(public_inputs)
     check_verification(_lib.load().bh_groth16_verify(pvk._h, raw, ins or None, len(public_inputs), _CANONICAL), "verify_proof")
@@ -92,7 +102,7 @@ class Verifier:
         self.items = []
 
     def queue(self, item):
-        """queue((proof, inputs)) or an Item"""
+        """queue((proof, inputs)) or an Item; the proof is a groth16.Proof or the 192 bytes of Proof::write"""
         self.items.append(item if isinstance(item, Item) else Item(*item))
 
     def _run(self, pvk, zs):
@@ -101,10 +111,39 @@ class Verifier:
         if any(len(it.inputs) != n_in for it in self.items):
             raise InvalidVerifyingKey()
         n = len(self.items)
-        proofs = b"".join(_proof_bytes(it.proof) for it in self.items)
+        lib = _lib.load()
         ins = b"".join(_fr_bytes(it.inputs) for it in self.items)
         z = _fr_bytes(zs)
-        check_verification(_lib.load().bh_groth16_batch_verify(pvk._h, proofs or None, n, ins or None, n_in, _CANONICAL,
+        packed = [_is_compressed(it.proof) for it in self.items]
+        if n and all(packed):
+            # every proof as written: read and verified in one call, the decoded proofs never leave the device
+            if any(len(it.proof) != 192 for it in self.items):
+                raise UnexpectedEof("failed to fill whole buffer")
+            bad = ctypes.c_size_t(0)
+            try:
+                check_verification(lib.bh_groth16_batch_verify_compressed(pvk._h, b"".join(bytes(it.proof) for it in self.items), n,
+                                                                          ins or None, n_in, _CANONICAL, z, ctypes.byref(bad)),
+                                   "batch verify")
+            except IOError as e:
+                e.index = bad.value
+                raise
+            return
+        if any(packed):   # a mixed batch: the byte items are read first
+            from .groth16 import read_proofs
+
+            where = [i for i, c in enumerate(packed) if c]
+            if any(len(self.items[i].proof) != 192 for i in where):
+                raise UnexpectedEof("failed to fill whole buffer")
+            try:
+                read = read_proofs(pvk.worker, b"".join(bytes(self.items[i].proof) for i in where))
+            except IOError as e:
+                e.index = where[e.index]
+                raise
+            decoded = dict(zip(where, read))
+        else:
+            decoded = {}
+        proofs = b"".join(_proof_bytes(decoded.get(i, it.proof)) for i, it in enumerate(self.items))
+        check_verification(lib.bh_groth16_batch_verify(pvk._h, proofs or None, n, ins or None, n_in, _CANONICAL,
                                                                z or None), "batch verify")
 
     def verify(self, rng, pvk):

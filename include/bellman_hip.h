@@ -197,6 +197,14 @@ int bh_bases_register_uncompressed(bh_ctx *ctx, int group, const void *host_byte
 #define BH_POINTS_FORBID_IDENTITY 2u
 int bh_bases_read_uncompressed(bh_ctx *ctx, int group, const void *host_bytes, size_t n, unsigned flags,
                                bh_bases **out, size_t *bad_index);
+/* `from_compressed` / `from_compressed_unchecked` for `n` COMPRESSED points (48 B for G1, 96 B for G2 = x.c1|x.c0; byte 0
+ * carries the flags compressed 0x80, infinity 0x40, sort 0x20), all on the device: the twin of bh_bases_read_uncompressed,
+ * with the same flags, return codes and "first offending point in stream order" rule.  A point is valid iff the compressed
+ * flag is set, every coordinate is < p, and either the infinity flag is set with every other bit clear (the identity) or
+ * x^3 + b is a square - y is then the root whose "lexicographically largest" equals the sort flag.  BH_POINTS_CHECKED adds
+ * the prime-order-subgroup test (by endomorphism: csrc/point_read.hip); without it the call is from_compressed_unchecked. */
+int bh_bases_read_compressed(bh_ctx *ctx, int group, const void *host_bytes, size_t n, unsigned flags,
+                             bh_bases **out, size_t *bad_index);
 /* copies `count` device-resident affine records (Montgomery) starting at `first` back to the host */
 int bh_bases_download(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, void *out_host);
 /* the same range in the uncompressed encoding Parameters::write emits (groth16/src/lib.rs:258-287; 96 / 192 bytes per
@@ -430,9 +438,10 @@ int bh_groth16_prove_assignment(bh_params *params, const void *a_evals, const vo
  *                                     An empty batch is BH_OK.  Runs in chunks of at most 16384 proofs and 256 MB of inputs (bounded
  *                                     device workspace),
  *                                     on its own stream: thread-safe and concurrent with other work on the context.
- * scalar_fmt applies to inputs and z as for bh_msm_async.  The only point check made is the on-curve test of A, B and C
- * (BH_ERR_INVALID_POINT, reported before BH_ERR_INVALID_PROOF); subgroup membership, which the reference's Proof::read
- * guarantees through from_compressed, stays with the caller. */
+ * scalar_fmt applies to inputs and z as for bh_msm_async.  The only point check these two AFFINE entry points make is the
+ * on-curve test of A, B and C (BH_ERR_INVALID_POINT, reported before BH_ERR_INVALID_PROOF): for them subgroup membership,
+ * which the reference's Proof::read guarantees through from_compressed, stays with the caller.  bh_proofs_read and
+ * bh_groth16_batch_verify_compressed below take the proofs as Proof::write emits them and make every check of Proof::read. */
 typedef struct bh_pvk bh_pvk;
 int bh_groth16_prepare_verifying_key(bh_ctx *ctx, const void *alpha_g1, const void *beta_g2, const void *gamma_g2,
                                      const void *delta_g2, const void *ic, size_t n_ic, bh_pvk **out);
@@ -442,6 +451,33 @@ size_t bh_groth16_pvk_num_inputs(const bh_pvk *pvk);
 int bh_groth16_verify(const bh_pvk *pvk, const void *proof, const void *inputs, size_t n_inputs, int scalar_fmt);
 int bh_groth16_batch_verify(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
                             int scalar_fmt, const void *z);
+/* Proof::read (groth16/src/lib.rs:47-99) over n_proofs concatenated 192-byte proofs (compressed A 48 | B 96 | C 48, what
+ * bh_proof_write emits), on the device: every point decompressed and checked (encoding, square root, prime-order subgroup),
+ * the identity refused.  Writes n_proofs x 384 bytes of affine a | b | c, the layout bh_groth16_verify / _batch_verify take
+ * (an element that fails is written as the all-zero record).  Returns BH_OK, or the error of the FIRST bad proof in stream
+ * order and inside it of the first bad element in the order a, b, c - what the reference's sequential reader reports:
+ * BH_ERR_INVALID_POINT ("invalid G1" / "invalid G2": bad encoding, no square root, outside the subgroup) or
+ * BH_ERR_POINT_AT_INFINITY (a well-formed identity); *bad_index (optional) is that proof's position.
+ * status (optional, one word per proof, written for EVERY proof whatever the return code; 0 = good proof) holds one byte
+ * per element - bits 0-7 a, 8-15 b, 16-23 c - of these bits (csrc/msm_types.hpp PointStatus):
+ *   0x02 sort flag on an infinity encoding   0x04 a coordinate >= p   0x08 infinity flag with coordinate bits set
+ *   0x10 a well-formed identity ("point at infinity"; every other bit means "invalid")
+ *   0x20 x^3 + b is not a square   0x40 not in the prime-order subgroup   0x80 compression flag clear
+ * Runs in chunks of at most 16384 proofs on a stream of its own: thread-safe.  n_proofs = 0 is BH_OK. */
+#define BH_PROOF_STATUS_IDENTITY 0x10u
+#define BH_PROOF_STATUS_INVALID 0xeeu
+int bh_proofs_read(bh_ctx *ctx, const void *bytes, size_t n_proofs, void *out_proofs_affine, uint32_t *status,
+                   size_t *bad_index);
+/* Proof::read of every proof followed by batch::Verifier::verify, without the decoded proofs visiting the host: 192 bytes
+ * per proof are uploaded and decoded on the verifier's stream into the records the chunk pipeline of
+ * bh_groth16_batch_verify consumes (same chunks, same bounded workspace, thread-safe and concurrent with other work on the
+ * context like it).  Errors in this order: the argument errors of bh_groth16_batch_verify (input count, a z_j = 0 mod q),
+ * then read errors as bh_proofs_read reports them (with *bad_index, optional) - a read error ANYWHERE in the batch wins
+ * over BH_ERR_INVALID_PROOF, as for a caller of the reference who reads all proofs before queueing them - then the
+ * verdict.  The batch is walked once: each chunk is decoded right before its Miller loops, and the first chunk that
+ * holds a bad proof ends the call (the verdict exists only after the last chunk). */
+int bh_groth16_batch_verify_compressed(const bh_pvk *pvk, const void *bytes, size_t n_proofs, const void *inputs,
+                                       size_t n_inputs, int scalar_fmt, const void *z, size_t *bad_index);
 /* before bh_ctx_destroy of the key's context (the key's device memory lives in the context's pool) */
 void bh_groth16_pvk_release(bh_pvk *pvk);
 /* ---- R1CS resident in HBM: constraint evaluation as sparse matrix x witness --------

@@ -86,6 +86,10 @@ double bh_test_capture_check(int circuit_kind, size_t size, uint64_t seed, size_
 int bh_test_demo_assignment(int circuit_kind, size_t size, uint64_t seed, const void *witness, const void *constants,
                             size_t counts3[3], void *a, void *b, void *c, void *inputs, void *aux, uint64_t *a_aux_density,
                             uint64_t *b_input_density, uint64_t *b_aux_density);
+/* host build of the square roots of the compressed-point reader (csrc/point_read.cuh), n Montgomery elements (48 B in Fp,
+ * c0 | c1 = 96 B in Fp2) in and out (canonical); ok[i] = 1 when a[i] is a square and r[i] one of its roots, else 0 */
+void bh_test_fp_sqrt_host(void *r, unsigned char *ok, const void *a, size_t n);
+void bh_test_fp2_sqrt_host(void *r, unsigned char *ok, const void *a, size_t n);
 void bh_test_fr_from_u512_host(void *r, const void *limbs8); /* 64 bytes LE -> Montgomery Fr (create_random_proof's sampling) */
 /* host only: the scalar-field arithmetic of the C++ mirror (bellman::Fr, csrc/groth16.hpp - what circuits and the
  * linear-combination evaluation compute with during synthesis), n operations on arrays of 32-byte Montgomery elements:

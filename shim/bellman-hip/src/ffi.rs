@@ -145,6 +145,7 @@ extern "C" {
     pub fn bh_bases_register(ctx: *mut BhCtx, group: c_int, host_points: *const c_void, n: usize, stride: usize, inf_offset: c_long, out: *mut *mut BhBases) -> c_int;
     pub fn bh_bases_register_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, out: *mut *mut BhBases) -> c_int;
     pub fn bh_bases_read_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, flags: c_uint, out: *mut *mut BhBases, bad_index: *mut usize) -> c_int;
+    pub fn bh_bases_read_compressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, flags: c_uint, out: *mut *mut BhBases, bad_index: *mut usize) -> c_int;
     pub fn bh_bases_download(ctx: *mut BhCtx, b: *const BhBases, first: usize, count: usize, out_host: *mut c_void) -> c_int;
     pub fn bh_bases_write_uncompressed(ctx: *mut BhCtx, bases: *const BhBases, first: usize, count: usize, out_host_bytes: *mut c_void) -> c_int;
     pub fn bh_bases_precompute(ctx: *mut BhCtx, b: *mut BhBases, window_bits: c_uint) -> c_int;
@@ -193,6 +194,8 @@ extern "C" {
     pub fn bh_groth16_pvk_num_inputs(pvk: *const BhPvk) -> usize;
     pub fn bh_groth16_verify(pvk: *const BhPvk, proof: *const c_void, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int) -> c_int;
     pub fn bh_groth16_batch_verify(pvk: *const BhPvk, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, z: *const c_void) -> c_int;
+    pub fn bh_proofs_read(ctx: *mut BhCtx, bytes: *const c_void, n_proofs: usize, out_proofs_affine: *mut c_void, status: *mut u32, bad_index: *mut usize) -> c_int;
+    pub fn bh_groth16_batch_verify_compressed(pvk: *const BhPvk, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, z: *const c_void, bad_index: *mut usize) -> c_int;
     pub fn bh_groth16_pvk_release(pvk: *mut BhPvk);
     pub fn bh_r1cs_create(ctx: *mut BhCtx, n_inputs: usize, n_aux: usize, n_constraints: usize, abc: *const BhCsr, coeffs: *const c_void, n_coeffs: usize, out: *mut *mut BhR1cs) -> c_int;
     pub fn bh_r1cs_release(r: *mut BhR1cs);
