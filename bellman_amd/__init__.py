@@ -24,4 +24,4 @@ from .multicore import Waiter, Worker  # noqa: F401
 from .multiexp import Bases, DensityTracker, FullDensity, Scalars, multiexp, multiexp_scalars, multiexp_sharded, point_add  # noqa: F401
 from .domain import EvaluationDomain, PointEvaluationDomain  # noqa: F401
 from . import verifier  # noqa: F401,E402
-from .verifier import PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_proof  # noqa: F401,E402
+from .verifier import PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each, verify_proof  # noqa: F401,E402

@@ -42,6 +42,7 @@ EXPORTS = [
     "bh_groth16_prove_witness_part", "bh_groth16_sums_add", "bh_groth16_assemble",
     "bh_groth16_prepare_verifying_key", "bh_groth16_pvk_from_params", "bh_groth16_pvk_num_inputs", "bh_groth16_verify",
     "bh_groth16_batch_verify", "bh_groth16_pvk_release", "bh_proofs_read", "bh_groth16_batch_verify_compressed",
+    "bh_groth16_verify_each", "bh_groth16_verify_each_compressed",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -254,6 +255,8 @@ def load():
     lib.bh_groth16_batch_verify.argtypes = [vp, vp, sz, vp, sz, i32, vp]
     lib.bh_proofs_read.argtypes = [vp, vp, sz, vp, vp, c.POINTER(sz)]
     lib.bh_groth16_batch_verify_compressed.argtypes = [vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
+    lib.bh_groth16_verify_each.argtypes = [vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
+    lib.bh_groth16_verify_each_compressed.argtypes = [vp, vp, sz, vp, sz, i32, vp, vp, c.POINTER(sz)]
     lib.bh_groth16_pvk_release.argtypes = [vp]
     lib.bh_groth16_pvk_release.restype = None
     lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]

@@ -17,6 +17,7 @@ struct EnvSettings {
   size_t table_budget = UNSET;    // BELLMAN_HIP_TABLE_BUDGET_MB, in bytes
   size_t fft_table_budget = UNSET;   // BELLMAN_HIP_FFT_TABLE_BUDGET_MB, in bytes
   size_t pool_cap = UNSET;        // BELLMAN_HIP_POOL_CAP_MB, in bytes
+  bool verify_each_shared = false;   // BELLMAN_HIP_VERIFY_EACH_SHARED=1: one three-pair Miller loop per proof, shared squarings (tools/bench_verify_each.py)
   bool debug = false;             // BH_DEBUG (set to anything): the prover's trace on stderr
 };
 
@@ -43,6 +44,7 @@ inline const EnvSettings &env() {
     v.table_budget = megabytes("BELLMAN_HIP_TABLE_BUDGET_MB");
     v.fft_table_budget = megabytes("BELLMAN_HIP_FFT_TABLE_BUDGET_MB");
     v.pool_cap = megabytes("BELLMAN_HIP_POOL_CAP_MB");
+    if (const char *e = text("BELLMAN_HIP_VERIFY_EACH_SHARED")) v.verify_each_shared = *e != '0';
     v.debug = getenv("BH_DEBUG") != nullptr;
     return v;
   }();

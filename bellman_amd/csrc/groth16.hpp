@@ -726,6 +726,43 @@ class BatchVerifier {
                                                inputs.empty() ? nullptr : inputs.data(), n_in, BH_SCALARS_MONT,
                                                z.empty() ? nullptr : z.data()));
   }
+  // Item::verify_single (batch.rs:55-66) of every queued item in one device call (bh_groth16_verify_each): element j is
+  // BH_OK or the code verify_proof's VerificationError would carry for item j alone.  Throws only for call-level errors
+  // (a wrong input count: InvalidVerifyingKey, before any work).
+  std::vector<int> verify_each(const PreparedVerifyingKey &pvk) const {
+    const size_t n_in = pvk.num_inputs();
+    for (const Item &it : items_)
+      if (it.inputs.size() != n_in) throw VerificationError(BH_ERR_INVALID_VERIFYING_KEY, "InvalidVerifyingKey");
+    std::vector<Proof> proofs;
+    std::vector<Fr> inputs;
+    proofs.reserve(items_.size());
+    inputs.reserve(items_.size() * n_in);
+    for (const Item &it : items_) {
+      proofs.push_back(it.proof);
+      inputs.insert(inputs.end(), it.inputs.begin(), it.inputs.end());
+    }
+    std::vector<int32_t> verdicts(items_.size(), 0);
+    verification_check(bh_groth16_verify_each(pvk.handle(), proofs.empty() ? nullptr : proofs.data(), proofs.size(),
+                                              inputs.empty() ? nullptr : inputs.data(), n_in, BH_SCALARS_MONT,
+                                              verdicts.empty() ? nullptr : verdicts.data(), nullptr));
+    return std::vector<int>(verdicts.begin(), verdicts.end());
+  }
+  // the fallback batch.rs:55-66 describes, as one call: empty when the batch check passes, else the indices of the items
+  // whose own verification fails
+  template <class Rng>
+  std::vector<size_t> find_invalid(Rng &&rng, const PreparedVerifyingKey &pvk) const {
+    try {
+      verify(rng, pvk);
+      return {};
+    } catch (const VerificationError &e) {
+      if (e.code == BH_ERR_INVALID_VERIFYING_KEY) throw;
+    }
+    std::vector<size_t> bad;
+    const std::vector<int> v = verify_each(pvk);
+    for (size_t j = 0; j < v.size(); j++)
+      if (v[j] != BH_OK) bad.push_back(j);
+    return bad;
+  }
 
  private:
   struct Item {

@@ -15,10 +15,16 @@
 //
 // Batches are processed in chunks of at most BATCH_CHUNK proofs (device workspace < 400 MB whatever the batch size); the
 // Fp12 product of each chunk is folded into a running product that the next chunk multiplies in.
+//
+// Per-proof verdicts (bh_groth16_verify_each: Item::verify_single, batch.rs:55-66, for every proof of a batch) take one
+// lane per proof through kernels 6-9 below instead of the multiexps and the product tree: ic_table_kernel (once per key),
+// ic_accumulate_kernel, miller3_kernel, f12_mul_const_kernel, the same final exponentiation chain over the whole chunk,
+// verdict_kernel.
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
+#include <mutex>
 #include <vector>
 
 #include "common.hpp"
@@ -206,6 +212,129 @@ __global__ __launch_bounds__(64) void f12_fold_kernel(fp12_t *f, u32 m, u32 h) {
   f[i] = a;
 }
 
+// ---- per-proof verdicts (bh_groth16_verify_each): one lane per proof from the inputs to the verdict --------------------
+// 6. The window table of the key's ic_1 .. ic_n: entry (i, win, d - 1) = [d 2^(w win)] ic_{i+1} for d = 1 .. 2^w - 1,
+// affine; one lane per entry (double-and-add over the w (win + 1) bits of the multiplier, one inversion).  The entries of
+// an identity ic_i are identity records, which the accumulation skips.
+__global__ __launch_bounds__(64) void ic_table_kernel(const Affine<FpOps> *ic, u32 w, Affine<FpOps> *table, u32 total) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const u32 entries = (1u << w) - 1, windows = 256 / w;
+  const u32 d = t % entries + 1, win = (t / entries) % windows, i = t / (entries * windows);
+  const Affine<FpOps> a = ic[i];
+  XYZZ<FpOps> acc;
+  xyzz_set_identity(acc);
+  if (!aff_is_identity(a))
+    for (int bit = (int)(w * win + w) - 1; bit >= 0; bit--) {
+      XYZZ<FpOps> dd;
+      xyzz_dbl(dd, acc);
+      acc = dd;
+      const int b = bit - (int)(w * win);
+      if (b >= 0 && ((d >> b) & 1)) xyzz_madd(acc, a);
+    }
+  Affine<FpOps> r;
+  xyzz_to_affine(r, acc);
+  table[t] = r;
+}
+// 7. acc_j = ic_0 + sum_i a_{j,i} ic_{i+1} (verifier.rs:31-35) from the table: 256 / w mixed additions per input and no
+// doubling, one inversion to affine.  xyzz_madd covers equal and opposite operands, so any inputs are summed exactly.
+__global__ __launch_bounds__(64) void ic_accumulate_kernel(const fr_t *inputs, u32 n_inputs, int fmt, const Affine<FpOps> *table,
+                                                           u32 w, const Affine<FpOps> *ic0, Affine<FpOps> *out, u32 n) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const u32 entries = (1u << w) - 1, windows = 256 / w;
+  XYZZ<FpOps> acc;
+  xyzz_set_identity(acc);
+#pragma unroll 1
+  for (u32 i = 0; i < n_inputs; i++) {
+    fr_t k;
+    scalar_bits(k, inputs[(size_t)j * n_inputs + i], fmt);
+    const Affine<FpOps> *row = table + (size_t)i * windows * entries;
+#pragma unroll 1
+    for (u32 win = 0; win < windows; win++) {
+      const u32 d = (k.l[(win * w) >> 5] >> ((win * w) & 31)) & entries;
+      if (!d) continue;
+      const Affine<FpOps> e = row[(size_t)win * entries + d - 1];
+      if (!aff_is_identity(e)) xyzz_madd(acc, e);
+    }
+  }
+  const Affine<FpOps> first = *ic0;
+  if (!aff_is_identity(first)) xyzz_madd(acc, first);
+  Affine<FpOps> r;
+  xyzz_to_affine(r, acc);
+  out[j] = r;
+}
+// 8. The three Miller loops of one proof: f(A_j, B_j), f(acc_j, -gamma), f(C_j, -delta).  B_j's lines are the lane's own
+// (g2_lines_kernel); the key's lines (klines: -gamma's 68, then -delta's) have the same address in every lane.  The G1
+// points are read again at every product instead of living in registers through the loop.  A pair with an identity on
+// either side takes no part, as in miller_kernel.  Two forms, selected by the grid:
+//   gridDim.y = 3 (shipped)  block row y runs pair y alone and writes f[y n + j]: 3 n lanes, then two products per proof
+//                            (f12_fold_kernel).  15.7 k Fp products per proof.
+//   gridDim.y = 1            one lane per proof multiplies the pairs of `pairs` (7: all) under ONE chain of squarings,
+//                            the reference's multi_miller_loop: one Fp12 squaring and three sparse line products per
+//                            step, 11.0 k Fp products per proof.
+// A 2^14-proof chunk is 256 waves on 1024 SIMDs at one wave per SIMD, so a launch costs one wave's latency and not the
+// chip's throughput: the shared form's lane does twice the work of a one-pair lane and takes twice as long (16.6 against
+// 8.2 + 0.2 ms per chunk, profiles/verify_each_bench.json), while the three-loop form's 768 waves still fit the chip at
+// once.  The shared form is kept behind BELLMAN_HIP_VERIFY_EACH_SHARED=1 for tools/bench_verify_each.py.
+__global__ __launch_bounds__(64) void miller3_kernel(const Affine<FpOps> *a, const Affine<FpOps> *acc, const ProofRec *proofs,
+                                                     const line_t *blines, const u32 *bflags, const line_t *__restrict__ klines,
+                                                     const u32 *__restrict__ kflags, u32 pairs, fp12_t *f, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (gridDim.y > 1) {
+    pairs = 1u << blockIdx.y;
+    f += (size_t)blockIdx.y * n;
+  }
+  const Affine<FpOps> *pa = a + i, *pg = acc + i, *pc = &proofs[i].c;
+  const line_t *bl = blines + (size_t)i * MILLER_LINES;
+  const bool on0 = (pairs & 1u) && !aff_is_identity(*pa) && !(bflags[i] & PF_IDENTITY);
+  const bool on1 = (pairs & 2u) && !aff_is_identity(*pg) && !(kflags[0] & PF_IDENTITY);
+  const bool on2 = (pairs & 4u) && !aff_is_identity(*pc) && !(kflags[1] & PF_IDENTITY);
+  fp12_t r;
+  f12_one(r);
+  int k = 0;
+#pragma unroll 1
+  for (int s = 62; s >= 0; s--) {
+    if (s != 62) f12_sqr(r, r);   // r = 1 before the first step
+    const int steps = ((BLS_X_ABS >> s) & 1) ? 2 : 1;
+#pragma unroll 1
+    for (int t = 0; t < steps; t++, k++) {
+      if (on0) f12_mul_line_at(r, bl[k], pa->x, pa->y);
+      if (on1) f12_mul_line_at(r, klines[k], pg->x, pg->y);
+      if (on2) f12_mul_line_at(r, klines[MILLER_LINES + k], pc->x, pc->y);
+    }
+  }
+  f[i] = r;
+}
+// f[i] *= *c: the key's constant f(-alpha, beta) into every proof's product
+__global__ __launch_bounds__(64) void f12_mul_const_kernel(fp12_t *f, const fp12_t *c, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fp12_t x = f[i], y = *c;
+  f12_mul(x, x, y);
+  f[i] = x;
+}
+// 9. the code bh_groth16_verify returns for proof j alone - after, for proofs given as bytes, the code bh_proofs_read
+// returns for it (words: its status words, or NULL): a read error, else a point off its curve, else the pairing check
+__global__ __launch_bounds__(256) void verdict_kernel(const u32 *words, const u32 *pflags, const u32 *qflags, const u32 *is_one,
+                                                      int *verdicts, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int v = BH_OK;
+  if (words)
+    for (int k = 0; k < 3 && v == BH_OK; k++) {   // proof_status_error: the first bad element in the order a, b, c
+      const u32 s = (words[i] >> (8 * k)) & 0xffu;
+      if (s & PT_INVALID_MASK) v = BH_ERR_INVALID_POINT;
+      else if (s & PT_IS_INF) v = BH_ERR_POINT_AT_INFINITY;
+    }
+  if (v == BH_OK) {
+    if ((pflags[i] | qflags[i]) & PF_OFF_CURVE) v = BH_ERR_INVALID_POINT;
+    else if (is_one[i] != 1u) v = BH_ERR_INVALID_PROOF;
+  }
+  verdicts[i] = v;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -292,6 +421,20 @@ struct bh_pvk {
   bh_bases *ic = nullptr;
   size_t n_ic = 0;
   std::vector<uint8_t> ic_identity;
+  std::vector<Affine<FpOps>> ic_pts;   // ic as given (identities as they came)
+  // What bh_groth16_verify_each adds to the key, built by the first call that needs it (std::call_once: the key is shared
+  // const between threads): the window table of ic_1 .. ic_n, ic_0, and f(-alpha, beta).
+  struct Each {
+    std::once_flag once;
+    int rc = BH_ERR_HIP;
+    Affine<FpOps> *table = nullptr;   // [n_inputs][256 / w][2^w - 1]
+    u32 w = 0;
+    size_t table_bytes = 0;           // counted in the context's table budget (a bh_ctx_trim zeroes the context's count:
+                                      // the release clamps)
+    Affine<FpOps> *ic0 = nullptr;     // ic_0, then (inside the same block) the Fp12 constant
+    fp12_t *f_ab = nullptr;
+  };
+  mutable Each each;
 };
 
 namespace {
@@ -377,6 +520,7 @@ int bh_groth16_prepare_verifying_key(bh_ctx *ctx, const void *alpha_g1, const vo
   // ic with identities replaced by the generator (their scalars are zeroed at use)
   std::vector<Affine<FpOps>> icv(n_ic);
   memcpy(icv.data(), ic, n_ic * 96);
+  k->ic_pts = icv;
   Affine<FpOps> gen;
   g1_generator(gen);
   k->ic_identity.assign(n_ic, 0);
@@ -431,6 +575,12 @@ void bh_groth16_pvk_release(bh_pvk *pvk) {
   Context &c = pvk->ctx->c;
   (void)hipSetDevice(c.device);
   if (pvk->ic) bh_bases_release(pvk->ctx, pvk->ic);
+  c.pool.release(pvk->each.table);
+  c.pool.release(pvk->each.ic0);
+  if (pvk->each.table_bytes) {
+    std::lock_guard<std::mutex> g(c.job_mu);
+    c.table_bytes = c.table_bytes > pvk->each.table_bytes ? c.table_bytes - pvk->each.table_bytes : 0;
+  }
   c.pool.release(pvk->lines);
   c.pool.release(pvk->qflags);
   delete pvk;
@@ -714,6 +864,168 @@ int bh_proofs_read(bh_ctx *ctx, const void *bytes, size_t n_proofs, void *out_pr
     }
   }
   return result;
+}
+
+}  // extern "C"
+
+// ---- per-proof verdicts: Item::verify_single for every proof of a batch (groth16/src/verifier/batch.rs:55-66, which is
+// verify_proof, groth16/src/verifier.rs:23-58) in one call --------------------------------------------------------------
+// Every proof takes one lane through: proof_prep_kernel / g2_lines_kernel (curve flags, B_j's lines), ic_accumulate_kernel
+// (acc_j from the key's window table), miller3_kernel (three pairs, shared squarings), f12_mul_const_kernel (the key's
+// f(-alpha, beta)), the n-wide final exponentiation chain and verdict_kernel.  No multiexp job, no host loop over proofs;
+// one download and one synchronisation per chunk.
+namespace {
+// the key's share, once per key: the largest window of 8, 4, 2, 1 bits whose table fits the context's table budget
+void build_each(const bh_pvk *pvk) {
+  bh_pvk::Each &e = pvk->each;
+  bh_ctx *ctx = pvk->ctx;
+  Context &c = ctx->c;
+  const size_t n_in = pvk->n_ic - 1;
+  e.rc = BH_ERR_HIP;
+  if (hipSetDevice(c.device) != hipSuccess) return;
+  for (u32 w = 8; n_in && w >= 1; w >>= 1) {
+    const size_t bytes = n_in * (256 / w) * ((size_t(1) << w) - 1) * sizeof(Affine<FpOps>);
+    {
+      std::lock_guard<std::mutex> g(c.job_mu);
+      if (w > 1 && c.table_bytes + bytes > c.table_budget) continue;   // (one-bit windows are the floor)
+      c.table_bytes += bytes;
+    }
+    e.table = (Affine<FpOps> *)c.pool.acquire(bytes);
+    if (e.table) {
+      e.w = w;
+      e.table_bytes = bytes;
+      break;
+    }
+    std::lock_guard<std::mutex> g(c.job_mu);
+    c.table_bytes -= bytes;
+  }
+  if (n_in && !e.table) {
+    fprintf(stderr, "[bellman_hip] verify_each: no device memory for the window table of %zu ic points\n", n_in);
+    return;
+  }
+  e.ic0 = (Affine<FpOps> *)c.pool.acquire(sizeof(Affine<FpOps>) + 32 + sizeof(fp12_t) + sizeof(Affine<FpOps>));
+  Affine<FpOps> *icd = (Affine<FpOps> *)c.pool.acquire(pvk->n_ic * sizeof(Affine<FpOps>));
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) sh.st = nullptr;
+  if (e.ic0 && icd && sh.st) {
+    hipStream_t st = sh.st;
+    e.f_ab = (fp12_t *)((char *)e.ic0 + 128);
+    Affine<FpOps> *na = (Affine<FpOps> *)(e.f_ab + 1);
+    bool ok = hipMemcpyAsync(icd, pvk->ic_pts.data(), pvk->n_ic * sizeof(Affine<FpOps>), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(e.ic0, pvk->ic_pts.data(), sizeof(Affine<FpOps>), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(na, &pvk->neg_alpha, sizeof(Affine<FpOps>), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && n_in) {
+      const size_t total = e.table_bytes / sizeof(Affine<FpOps>);
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(ic_table_kernel, dim3(blocks_of(total, 64)), dim3(64), 0, st, icd + 1, e.w, e.table, (u32)total);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    // f(-alpha, beta): one lane of the existing Miller kernel over the key's beta lines
+    if (ok) ok = launch_miller(st, na, pvk->lines + 2 * MILLER_LINES, pvk->qflags + 2, e.f_ab, 1) == BH_OK;
+    if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+    if (ok) e.rc = BH_OK;
+  }
+  c.pool.release(icd);
+}
+
+int verify_each_impl(const bh_pvk *pvk, const void *proofs, const void *bytes, size_t n_proofs, const void *inputs,
+                     size_t n_inputs, int scalar_fmt, int32_t *verdicts, uint32_t *status, size_t *n_bad) {
+  if (!pvk || (n_proofs && ((!proofs && !bytes) || !verdicts)) || (n_proofs && n_inputs && !inputs) ||
+      (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT))
+    return BH_ERR_INVALID_ARG;
+  if (n_bad) *n_bad = 0;
+  if (!n_proofs) return BH_OK;
+  bh_ctx *ctx = pvk->ctx;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  std::call_once(pvk->each.once, build_each, pvk);
+  const bh_pvk::Each &e = pvk->each;
+  if (e.rc) return e.rc;
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) return BH_ERR_HIP;
+  hipStream_t st = sh.st;
+  const bool separate = !env().verify_each_shared;   // three one-pair loops: the faster form at 2^14 proofs, see miller3_kernel
+  const size_t by_inputs = std::max<size_t>(1, INPUTS_CHUNK_BYTES / (32 * std::max<size_t>(n_inputs, 1)));
+  const size_t ch = std::min(std::min(n_proofs, BATCH_CHUNK), by_inputs);
+  ProofRec *pr = bufs.get<ProofRec>(ch);
+  fr_t *ind = bufs.get<fr_t>(ch * (n_inputs ? n_inputs : 1));
+  Affine<FpOps> *pts = bufs.get<Affine<FpOps>>(2 * ch);   // A_j, then acc_j
+  line_t *lines = bufs.get<line_t>(ch * MILLER_LINES);
+  u32 *words = bufs.get<u32>(5 * ch);                     // curve flags of A/C, of B, is_one, verdicts, status words
+  fp12_t *f = bufs.get<fp12_t>((separate ? 3 : 1) * ch);
+  fp12_t *ws = bufs.get<fp12_t>(4 * ch);                  // final exponentiation workspace
+  unsigned char *cbytes = bytes ? bufs.get<unsigned char>(ch * 192) : nullptr;
+  u32 *pst = bytes ? bufs.get<u32>(3 * ch) : nullptr;
+  unsigned long long *first_bad = bytes ? bufs.get<unsigned long long>(1) : nullptr;   // (the reader's; not used here)
+  if (!pr || !ind || !pts || !lines || !words || !f || !ws || (bytes && (!cbytes || !pst || !first_bad))) {
+    fprintf(stderr, "[bellman_hip] verify_each: no device memory for a %zu-proof chunk\n", ch);
+    return BH_ERR_HIP;
+  }
+  u32 *pflags = words, *qflags = words + ch, *is_one = words + 2 * ch, *wst = bytes ? words + 4 * ch : nullptr;
+  int *vd = (int *)(words + 3 * ch);
+  Affine<FpOps> *accp = pts + ch;
+  size_t bad = 0;
+  for (size_t first = 0; first < n_proofs; first += ch) {
+    const size_t m = std::min(ch, n_proofs - first);
+    if (bytes) {
+      if (hipMemcpyAsync(cbytes, (const unsigned char *)bytes + first * 192, m * 192, hipMemcpyHostToDevice, st) != hipSuccess)
+        return BH_ERR_HIP;
+      const int rc = proofs_read_dev(cbytes, pr, m, pst, wst, first_bad, st);
+      if (rc) return rc;
+    } else if (hipMemcpyAsync(pr, (const ProofRec *)proofs + first, m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      return BH_ERR_HIP;
+    }
+    if (n_inputs && hipMemcpyAsync(ind, (const fr_t *)inputs + first * n_inputs, m * n_inputs * 32, hipMemcpyHostToDevice, st) != hipSuccess)
+      return BH_ERR_HIP;
+    const dim3 g(blocks_of(m, 64)), blk(64);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(proof_prep_kernel, g, blk, 0, st, pr, (const fr_t *)nullptr, 0, pts, (Affine<FpOps> *)nullptr, (fr_t *)nullptr,
+                       (const Affine<FpOps> *)nullptr, pflags, (u32)m);
+    hipLaunchKernelGGL(ic_accumulate_kernel, g, blk, 0, st, ind, (u32)n_inputs, scalar_fmt, e.table, e.w ? e.w : 8u, e.ic0, accp,
+                       (u32)m);
+    if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+    int rc = launch_g2_lines(st, &pr->b, sizeof(ProofRec), 0, lines, qflags, m);
+    if (rc) return rc;
+    hipLaunchKernelGGL(miller3_kernel, dim3(g.x, separate ? 3 : 1), blk, 0, st, pts, accp, pr, lines, qflags, pvk->lines, pvk->qflags,
+                       7u, f, (u32)m);
+    if (separate) {   // f[j] *= f[m + j] * f[2 m + j]
+      hipLaunchKernelGGL(f12_fold_kernel, g, blk, 0, st, f + m, (u32)(2 * m), (u32)m);
+      hipLaunchKernelGGL(f12_fold_kernel, g, blk, 0, st, f, (u32)(2 * m), (u32)m);
+    }
+    hipLaunchKernelGGL(f12_mul_const_kernel, g, blk, 0, st, f, e.f_ab, (u32)m);
+    if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+    if ((rc = launch_final_exp(st, f, m, f, is_one, ws))) return rc;
+    hipLaunchKernelGGL(verdict_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, st, wst, pflags, qflags, is_one, vd, (u32)m);
+    if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+    if (hipMemcpyAsync(verdicts + first, vd, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (status && hipMemcpyAsync(status + first, wst, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return BH_ERR_HIP;
+    for (size_t j = 0; j < m; j++) bad += verdicts[first + j] != BH_OK;
+  }
+  if (n_bad) *n_bad = bad;
+  return BH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// batch::Item::verify_single (batch.rs:55-66) = verify_proof (verifier.rs:23-58) of every proof, verdict by verdict
+int bh_groth16_verify_each(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
+                           int scalar_fmt, int32_t *verdicts, size_t *n_bad) {
+  if (pvk && n_inputs + 1 != pvk->n_ic) return BH_ERR_INVALID_VERIFYING_KEY;   // verifier.rs:27-29, before anything else
+  if (n_proofs && !proofs) return BH_ERR_INVALID_ARG;
+  return verify_each_impl(pvk, proofs, nullptr, n_proofs, inputs, n_inputs, scalar_fmt, verdicts, nullptr, n_bad);
+}
+
+// the same from the bytes of Proof::write: Proof::read (groth16/src/lib.rs:47-99) of proof j, then verify_proof
+// (verifier.rs:23-58) / Item::verify_single (batch.rs:55-66); the decoded proofs stay on the device
+int bh_groth16_verify_each_compressed(const bh_pvk *pvk, const void *bytes, size_t n_proofs, const void *inputs,
+                                      size_t n_inputs, int scalar_fmt, int32_t *verdicts, uint32_t *status, size_t *n_bad) {
+  if (pvk && n_inputs + 1 != pvk->n_ic) return BH_ERR_INVALID_VERIFYING_KEY;
+  if (n_proofs && !bytes) return BH_ERR_INVALID_ARG;
+  return verify_each_impl(pvk, nullptr, bytes, n_proofs, inputs, n_inputs, scalar_fmt, verdicts, status, n_bad);
 }
 
 }  // extern "C"

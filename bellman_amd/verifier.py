@@ -13,7 +13,8 @@ import secrets
 import numpy as np
 
 from . import _lib
-from .errors import InvalidVerifyingKey, UnexpectedEof, check, check_verification
+from .errors import (InvalidPoint, InvalidProof, InvalidVerifyingKey, PointAtInfinity, UnexpectedEof, check,
+                     check_verification)
 
 Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _CANONICAL = 0
@@ -83,6 +84,78 @@ def verify_proof(pvk, proof, public_inputs):
     raw = _proof_bytes(proof)
     ins = _fr_bytes(public_inputs)
     check_verification(_lib.load().bh_groth16_verify(pvk._h, raw, ins or None, len(public_inputs), _CANONICAL), "verify_proof")
+
+
+def _verdict_error(code):
+    """the exception Item.verify_single raises for a verdict code of bh_groth16_verify_each (None for BH_OK)"""
+    if code == 0:
+        return None
+    if code == 9:
+        return InvalidProof()
+    if code == 6:
+        return InvalidPoint("invalid G1/G2")
+    if code == 7:
+        return PointAtInfinity("point at infinity")
+    raise AssertionError("unexpected verdict code %d" % code)
+
+
+def verify_each(pvk, items):
+    """Item::verify_single (groth16/src/verifier/batch.rs:55-66) for every item, in one device call: a list with None for a
+    good proof and, for a bad one, the exception instance Item.verify_single would raise (not raised).  Items are `Item`s or
+    (proof, inputs) pairs; a proof is a groth16.Proof or the 192 bytes of Proof::write.  A batch of byte proofs only is read
+    and judged on the device (bh_groth16_verify_each_compressed); in a mixed batch the byte items are read first, as
+    Verifier._run does, and a read error becomes that item's entry.  Raises InvalidVerifyingKey before any work when an
+    item's input count does not match the key."""
+    items = [it if isinstance(it, Item) else Item(*it) for it in items]
+    n_in = pvk.n_inputs
+    if any(len(it.inputs) != n_in for it in items):
+        raise InvalidVerifyingKey()
+    n = len(items)
+    if not n:
+        return []
+    lib = _lib.load()
+    packed = [_is_compressed(it.proof) for it in items]
+    if any(c and len(it.proof) != 192 for c, it in zip(packed, items)):
+        raise UnexpectedEof("failed to fill whole buffer")
+    ins = b"".join(_fr_bytes(it.inputs) for it in items)
+    verdicts = (ctypes.c_int32 * n)()
+    if all(packed):
+        check_verification(lib.bh_groth16_verify_each_compressed(pvk._h, b"".join(bytes(it.proof) for it in items), n, ins or None,
+                                                                 n_in, _CANONICAL, verdicts, None, None), "verify_each")
+        return [_verdict_error(v) for v in verdicts]
+    out = [None] * n
+    decoded = {}
+    where = [i for i, c in enumerate(packed) if c]
+    if where:   # a mixed batch: the byte items are read first; the unreadable ones keep their read error
+        from .groth16 import Proof
+
+        raw = b"".join(bytes(items[i].proof) for i in where)
+        recs = np.zeros((len(where), 48), dtype=np.uint64)
+        status = (ctypes.c_uint32 * len(where))()
+        rc = lib.bh_proofs_read(pvk.worker.ctx, raw, len(where), recs.ctypes.data_as(ctypes.c_void_p), status, None)
+        if rc not in (0, 6, 7):
+            check(rc, "Proof.read")
+        for k, i in enumerate(where):
+            word = status[k]
+            for e in range(3):   # the first bad element in the order a, b, c
+                byte = (word >> (8 * e)) & 0xFF
+                if byte & 0xEE:
+                    out[i] = InvalidPoint("invalid G1/G2")
+                    break
+                if byte & 0x10:
+                    out[i] = PointAtInfinity("point at infinity")
+                    break
+            decoded[i] = Proof(recs[k].copy())
+    live = [i for i in range(n) if out[i] is None]
+    if live:
+        proofs = b"".join(_proof_bytes(decoded.get(i, items[i].proof)) for i in live)
+        ins = b"".join(_fr_bytes(items[i].inputs) for i in live)
+        verdicts = (ctypes.c_int32 * len(live))()
+        check_verification(lib.bh_groth16_verify_each(pvk._h, proofs, len(live), ins or None, n_in, _CANONICAL, verdicts, None),
+                           "verify_each")
+        for i, v in zip(live, verdicts):
+            out[i] = _verdict_error(v)
+    return out
 
 
 class Item:
@@ -166,3 +239,16 @@ class Verifier:
             zs.append(z)
         return self._run(pvk, zs)
 
+    def verify_each(self, pvk):
+        """per-item verdicts of the queued items (module-level verify_each): None or the exception verify_single would raise"""
+        return verify_each(pvk, self.items)
+
+    def find_invalid(self, rng, pvk):
+        """the fallback batch.rs:55-66 describes, as one call: [] when the batch check passes, else the indices of the items
+        whose own verification fails"""
+        try:
+            self.verify(rng, pvk)
+            return []
+        except (InvalidProof, IOError):
+            pass
+        return [i for i, e in enumerate(self.verify_each(pvk)) if e is not None]

@@ -478,6 +478,28 @@ int bh_proofs_read(bh_ctx *ctx, const void *bytes, size_t n_proofs, void *out_pr
  * holds a bad proof ends the call (the verdict exists only after the last chunk). */
 int bh_groth16_batch_verify_compressed(const bh_pvk *pvk, const void *bytes, size_t n_proofs, const void *inputs,
                                        size_t n_inputs, int scalar_fmt, const void *z, size_t *bad_index);
+/* Per-proof verdicts for n_proofs proofs of one key in one call: batch::Item::verify_single (groth16/src/verifier/batch.rs:55-66,
+ * "for fallback logic when batch verification fails"), which is verify_proof (groth16/src/verifier.rs:23-58), for every proof.
+ * proofs: n_proofs x 384 B affine a | b | c; inputs: row-major n_proofs x n_inputs (row j belongs to proof j), scalar_fmt as
+ * for bh_groth16_verify.  verdicts[j] is exactly the code bh_groth16_verify(pvk, proof_j, inputs_j, n_inputs, scalar_fmt)
+ * returns for that proof alone: BH_OK, BH_ERR_INVALID_POINT (A, B or C off its curve; before BH_ERR_INVALID_PROOF) or
+ * BH_ERR_INVALID_PROOF; an all-zero identity record counts as it does there.  A bad proof never ends the walk.
+ * The return value carries call-level outcomes only: BH_ERR_INVALID_VERIFYING_KEY first when n_inputs + 1 != the length of
+ * ic, BH_ERR_INVALID_ARG, BH_ERR_HIP, and BH_OK whenever every verdict was written - even if every proof is bad.
+ * *n_bad (optional) = the number of nonzero verdicts; n_proofs = 0 is BH_OK with *n_bad = 0.
+ * Every proof takes one lane on the device (fixed-base accumulation of its inputs over a window table of ic kept with the
+ * key, three Miller loops under shared squarings, its own final exponentiation): no host loop over proofs.  Runs in chunks
+ * of at most 16384 proofs (bounded workspace) on a stream of its own: thread-safe and concurrent with other work on the
+ * context, like the batch verifier.  The key's table is built by the first call (once, under std::call_once) and counts
+ * against the context's table budget (bh_ctx_set_limits); a table that would not fit is built with a narrower window. */
+int bh_groth16_verify_each(const bh_pvk *pvk, const void *proofs, size_t n_proofs, const void *inputs, size_t n_inputs,
+                           int scalar_fmt, int32_t *verdicts, size_t *n_bad);
+/* The same over n_proofs x 192 B as Proof::write emits them; the decoded proofs never visit the host.  verdicts[j] is what
+ * bh_proofs_read returns for those 192 bytes alone if it fails (BH_ERR_INVALID_POINT / BH_ERR_POINT_AT_INFINITY), otherwise
+ * what bh_groth16_verify returns on the decoded proof (batch.rs:55-66, verifier.rs:23-58 after groth16/src/lib.rs:47-99).
+ * status[j] (optional) is the word bh_proofs_read writes for proof j.  The proofs after a bad one are still judged. */
+int bh_groth16_verify_each_compressed(const bh_pvk *pvk, const void *bytes, size_t n_proofs, const void *inputs,
+                                      size_t n_inputs, int scalar_fmt, int32_t *verdicts, uint32_t *status, size_t *n_bad);
 /* before bh_ctx_destroy of the key's context (the key's device memory lives in the context's pool) */
 void bh_groth16_pvk_release(bh_pvk *pvk);
 /* ---- R1CS resident in HBM: constraint evaluation as sparse matrix x witness --------

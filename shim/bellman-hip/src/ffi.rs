@@ -196,6 +196,8 @@ extern "C" {
     pub fn bh_groth16_batch_verify(pvk: *const BhPvk, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, z: *const c_void) -> c_int;
     pub fn bh_proofs_read(ctx: *mut BhCtx, bytes: *const c_void, n_proofs: usize, out_proofs_affine: *mut c_void, status: *mut u32, bad_index: *mut usize) -> c_int;
     pub fn bh_groth16_batch_verify_compressed(pvk: *const BhPvk, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, z: *const c_void, bad_index: *mut usize) -> c_int;
+    pub fn bh_groth16_verify_each(pvk: *const BhPvk, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, verdicts: *mut i32, n_bad: *mut usize) -> c_int;
+    pub fn bh_groth16_verify_each_compressed(pvk: *const BhPvk, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, verdicts: *mut i32, status: *mut u32, n_bad: *mut usize) -> c_int;
     pub fn bh_groth16_pvk_release(pvk: *mut BhPvk);
     pub fn bh_r1cs_create(ctx: *mut BhCtx, n_inputs: usize, n_aux: usize, n_constraints: usize, abc: *const BhCsr, coeffs: *const c_void, n_coeffs: usize, out: *mut *mut BhR1cs) -> c_int;
     pub fn bh_r1cs_release(r: *mut BhR1cs);
