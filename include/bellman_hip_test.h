@@ -97,6 +97,34 @@ void bh_test_fr_from_u512_host(void *r, const void *limbs8); /* 64 bytes LE -> M
  * 5 r = canonical limbs of a (to_canonical), 6 r = a^-1 (a != 0) */
 void bh_test_fr_ops_host(int op, void *r, const void *a, const void *b, size_t n);
 
+/* ONE field operation per element on operands of the caller's choice, raw results (nothing is canonicalised), through the
+ * function objects the kernels use (csrc/test_field_hooks.hip; tests/test_gpu_field_corners.py).  Operands and results
+ * are arrays of fixed-size slots; flags[k] carries a predicate's answer (0 elsewhere).
+ *   form 0 / 1  canonical Fe<FrParams> / Fe<FpParams> (32 / 48-byte slots): op 0 fe_add, 1 fe_sub, 2 fe_neg, 3 fe_dbl,
+ *               4 fe_mul, 5 fe_mul_b(a, fe_to_bform(b)), 6 fe_sqr, 7 fe_to_mont, 8 fe_from_mont, 9 fe_inv
+ *   form 2 / 3  FpOps / Fp2Ops, lazily reduced (48 / 96-byte slots): op 0 add, 1 sub, 2 neg, 3 dbl, 4 canon, 5 is_zero,
+ *               6 eq, 7 mul, 8 mul_tail, 9 sqr, 10 mul2_sub(a, b, c, d), 11 mul2_sub_tail, 12 inv; form 2 only:
+ *               13 fpl_add2, 14 fpl_sub2 on the pairs (a, b) and (c, d): two results per element
+ *   form 4 / 5  Fp2K3Ops / Fp2PairOps (device only; 96-byte Fp2 operands, the kernels' lane mapping): the ops of form 3
+ *               up to 7, 9, and 13 load / store round trip, 14 one, 15 curve_b.  r = n * LANES 48-byte lane values (what
+ *               lane `role` of element i holds: r[i * LANES + role], the sum lane of a triple included) followed by the n
+ *               Fp2 values F::store wrote; flags[i * LANES + role]
+ *   form 6      the tower of csrc/fp12.cuh, 576-byte slots (an operation reads as much of a slot as its argument type
+ *               needs): op 0 f2_mul_xi, 1 f2_mul_fp(a, b: Fp), 2 f2_conj, 3 / 4 / 5 f2_mul_small by 3 / 4 / 12, 6 f6_mul,
+ *               7 f6_mul_01(a, b, c), 8 f6_mul_1(a, b), 9 f6_mul_v, 10 f6_inv, 11 f12_mul, 12 f12_sqr,
+ *               13 f12_mul_line(a; b, c, d), 14 f12_inv, 15 f12_conj, 16 f12_frob1, 17 f12_frob2, 18 f12_cyc_sqr,
+ *               19 f12_cyc_exp_x, 20 f12_is_one (flag), 21 f12_final_exp (canonical, flag = is one); on the device 19
+ *               and 21 are the kernel chains of csrc/final_exp.cuh
+ *   form 7      csrc/point_read.cuh, 96-byte slots: op 0 fp_sqrt (c0; flag = ok), 1 fp2_sqrt (flag = ok), 2 fpl_half (c0),
+ *               3 fp_lex_largest (c0; flag), 4 fp2_lex_largest (flag)
+ * bh_test_field_ops_shape: out4 = [result bytes per element, flags per element, operand slot bytes, operands used]. */
+int bh_test_field_ops_shape(int form, int op, size_t out4[4]);
+int bh_test_field_ops_dev(bh_ctx *ctx, int form, int op, void *r_dev, uint32_t *flags_dev, const void *a_dev,
+                          const void *b_dev, const void *c_dev, const void *d_dev, size_t n);
+/* the same `apply` compiled for the host (forms 0 - 3, 6, 7) */
+int bh_test_field_ops_host(int form, int op, void *r, uint32_t *flags, const void *a, const void *b, const void *c,
+                           const void *d, size_t n);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,

@@ -138,7 +138,7 @@ def test_host_field_mul_matches_oracle(lib):
 
 @pytest.mark.parametrize("group", [1, 2])
 def test_host_group_law_matches_oracle(lib, group):
-    n = 10
+    n = 14
     w = 12 if group == 1 else 24
     A = cref.gen_bases(group, n, a=5, b=3)
     B = cref.gen_bases(group, n, a=7, b=11)
@@ -146,11 +146,20 @@ def test_host_group_law_matches_oracle(lib, group):
     B[1] = 0  # + identity
     A[2] = 0  # identity +
     B[3] = cref.point_mul(group, A[3], bls.Q - 1)  # P + (-P)
+    if group == 1:
+        # (0, 2) and (0, p - 2), x = 0: the doubling slope vanishes, intermediate zeros in both representatives
+        # (tests/test_gpu_parity.py::test_point_add_on_device runs the same on the device)
+        r = pow(2, 384, bls.P)
+        T = cref.ints_to_arr([0, 2 * r % bls.P], 6).reshape(12)
+        Tn = cref.ints_to_arr([0, (bls.P - 2) * r % bls.P], 6).reshape(12)
+        A[5], B[6], A[7], B[7], A[8], B[9], A[10], B[10], A[11], B[11], A[12], B[12] = T, T, T, T, Tn, Tn, Tn, Tn, T, Tn, Tn, T
     out = np.zeros((n, w), dtype=np.uint64)
     lib.bh_test_point_add_host(group, _p(out), _p(A), _p(B), n)
     want = np.stack([cref.point_add(group, A[i], B[i]) for i in range(n)])
     assert np.array_equal(out, want)
     assert not out[3].any()
+    if group == 1:
+        assert np.array_equal(out[7], Tn) and np.array_equal(out[10], T) and not out[11].any() and not out[12].any()
     for k in (0, 1, 2, bls.Q - 1, random.Random(4).randrange(bls.Q)):
         ka = np.array(cref.int_to_limbs(k, 4), dtype=np.uint64)
         o = np.zeros(w, dtype=np.uint64)

@@ -82,6 +82,17 @@ def test_point_add_on_device(worker, group):
     B[3] = cref.point_mul(group, A[3], Q - 1)
     A[4] = 0
     B[4] = 0
+    if group == 1:
+        # the curve points (0, 2) and (0, p - 2): x = 0, so the doubling slope 3 x^2 vanishes and the lazily reduced
+        # intermediates are zero in both representatives (0 and p); as A, as B and as A = B.  T = (0, 2) has order 3.
+        r = pow(2, 384, bls.P)
+        T = cref.ints_to_arr([0, 2 * r % bls.P], 6).reshape(12)
+        Tn = cref.ints_to_arr([0, (bls.P - 2) * r % bls.P], 6).reshape(12)
+        for k, (x, y) in enumerate([(T, None), (None, T), (T, T), (Tn, None), (None, Tn), (Tn, Tn), (T, Tn), (Tn, T)]):
+            if x is not None:
+                A[5 + k] = x
+            if y is not None:
+                B[5 + k] = y
     dA, dB, dR = _dev(worker, A), _dev(worker, B), worker.alloc(A.nbytes)
     assert lib.bh_test_point_add_dev(worker.ctx, group, dR, dA, dB, n) == 0
     out = np.empty_like(A)
@@ -89,6 +100,9 @@ def test_point_add_on_device(worker, group):
     want = np.stack([cref.point_add(group, A[i], B[i]) for i in range(n)])
     assert np.array_equal(out, want)
     assert out.shape[1] == w and not out[3].any() and not out[4].any()
+    if group == 1:
+        assert np.array_equal(out[7], Tn) and np.array_equal(out[10], T)      # 2 T = -T
+        assert not out[11].any() and not out[12].any()                        # T + (-T)
 
 
 def test_g2_k3_group_law(worker):
