@@ -125,6 +125,44 @@ int bh_test_field_ops_dev(bh_ctx *ctx, int form, int op, void *r_dev, uint32_t *
 int bh_test_field_ops_host(int form, int op, void *r, uint32_t *flags, const void *a, const void *b, const void *c,
                            const void *d, size_t n);
 
+/* ONE group operation per worker on RAW projective operands of the caller's choice, raw results (nothing is canonicalised),
+ * through the functions the kernels call and with the kernels' worker and lane mapping (csrc/test_group_hooks.hip;
+ * tests/test_gpu_group_law.py, tests/test_group_model_cpu.py).  Records are XYZZ<Mem> (X, Y, ZZ, ZZZ: 4 x 48 bytes in G1,
+ * 4 x 96 in G2, every coordinate a Montgomery residue in [0, 2p)) and canonical affine records (x, y; all zero = identity).
+ *   form 0  G1, one lane (XYZZ<FpOps>)            device and host
+ *   form 1  G1, lane pairs (K2 HalfPt)            device
+ *   form 2  G2, one lane (Fp2Ops)                 device and host
+ *   form 3  G2, lane triples (Fp2K3Ops)           device
+ *   form 4  G2, lane pairs (Fp2PairOps)           device
+ *   form 5  G2, lane sextets (K6 HalfPt)          device
+ *   op  0 add            r = a + b: xyzz_add (forms 0, 2, 3, 4), k2_add (1), k6_add (5); b = XYZZ records
+ *       1 add_alias      the same with r aliasing a, as the merge kernels call it
+ *       2 madd           r = a + b, b = AFFINE records: xyzz_madd; an identity b is skipped as the accumulation does
+ *       3 madd_prefetch  the overload with a prefetch functor, which loads the first word of b's record
+ *       4 dbl            xyzz_dbl(a)
+ *       5 dbl_affine     xyzz_dbl_affine(b), b affine and not the identity
+ *       6 from_affine    xyzz_from_affine(b)
+ *       7 to_affine      xyzz_to_affine(a) into X, Y of the result (ZZ = ZZZ = 0); forms 0 and 2 only: the lane bundles
+ *                        have no inversion, and no kernel converts in those forms
+ *       8 is_identity    xyzz_is_identity(a); r = a
+ *       9 load_store     k2_load / k2_store, k6_load / k6_store round trip (forms 1 and 5 only)
+ *      10 tree           r[g] = a[g G] + ... + a[g G + G - 1] by group_reduce_points / k2_group_reduce / k6_group_reduce over
+ *                        G consecutive workers of a wavefront, G a power of two in [2, workers per wavefront]; n groups
+ *      11 block_sum      r[c] = the sum of the 4 x (workers per wavefront) records of case c by long_block_sum at
+ *                        LONG_THREADS, one workgroup per case; on the host G = the workers per wavefront to fold by
+ *                        (0: the form's own), so that a host run adds in the order of any device form of the same group
+ *   ops 2 - 8 exist for forms 0, 2, 3, 4.  flags: `lanes` words per worker, one per lane of the worker (flags[i * lanes +
+ *   role]): bit 0 = the result is the identity as the form's own predicate sees it in that lane (to_affine: the affine
+ *   record is the identity), bit 1 = what xyzz_madd returned, bits 4-7 = how often the prefetch functor ran, bits 16-31 =
+ *   the low half of the word it loaded.
+ * bh_test_group_ops_shape: out4 = [XYZZ record bytes, flag words per worker, affine record bytes, workers per wavefront
+ * in the trees]. */
+int bh_test_group_ops_shape(int form, int op, size_t out4[4]);
+int bh_test_group_ops_dev(bh_ctx *ctx, int form, int op, unsigned G, void *r_dev, uint32_t *flags_dev, const void *a_dev,
+                          const void *b_dev, size_t n);
+/* the same `apply` compiled for the host (forms 0 and 2); trees and block sums add in the order of the shuffle trees */
+int bh_test_group_ops_host(int form, int op, unsigned G, void *r, uint32_t *flags, const void *a, const void *b, size_t n);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,
