@@ -53,7 +53,7 @@ TEST_EXPORTS = [
     "bh_test_groth16_prove_via_call_sites", "bh_test_demo_assignment", "bh_test_shard_cuts", "bh_test_pool_size_class", "bh_test_capture_check",
     "bh_test_pairing", "bh_test_pairing_host", "bh_test_fp_sqrt_host", "bh_test_fp2_sqrt_host",
     "bh_test_field_ops_shape", "bh_test_field_ops_dev", "bh_test_field_ops_host",
-    "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host",
+    "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev",
 ]
 
 

@@ -431,112 +431,14 @@ __device__ __forceinline__ void group_reduce_points(XYZZ<F> &acc, u32 G, u32 sub
 }
 
 // ============================================================================================
-// 5. reductions: G lanes per output point (serial partial sums, then a shuffle tree)
+// 5. reductions: the half-point adder, the worker policies, and ONE sum kernel written over them
 // ============================================================================================
-// the j-th index with bit k set, j = 0, 1, ...  (SUM_BITS walks exactly the selected half of its vector: striding over ALL
-// indices left the workers whose own index has bit k clear - k < log2 G - with nothing to add and the others with twice the
-// chain; [r6] 13 -> 9 levels for the bit sums of a 2^15-bucket window, 37 -> 21 for a 2^19-bucket set)
-__device__ __forceinline__ u32 nth_with_bit(u32 j, u32 k) { return ((j >> k) << (k + 1)) | (1u << k) | (j & ((1u << k) - 1u)); }
-// out[g] = sum of a set of in[] points chosen by the mode:
-//   SUM_STRIDED: g = (outer, inner): elements in[(outer << group_shift) + inner*istride + t*stride], t < count
-//   SUM_BITS   : g = (outer, k):     elements in[(outer << group_shift) + i], i < count, bit k of i set
-template <class F>
-struct SumJob {
-  const XYZZ<typename F::Mem> *in;
-  XYZZ<typename F::Mem> *out;
-  SumDesc d;
-  u32 nblocks;   // one-wavefront blocks assigned to this job
-};
-// up to three independent reductions per launch (rows + columns, then the bit-sum sets and the
-// plain window totals): they are latency-bound, so sharing a launch lets the hardware overlap them.
-template <class F>
-struct SumJobs {
-  SumJob<F> j[3];
-};
-// A block carries 64 workers: one wavefront of single lanes, or FOUR wavefronts of 16 lane triples (K3) - so that a
-// K3 reduction can also put up to 64 workers on one output (the tree then crosses wavefronts through LDS); with 16
-// the 256-element column sums of a window table's 2^15 buckets were 16 + 4 additions deep.
-template <class F>
-constexpr u32 sum_block_threads() { return F::LANES == 3 ? 256u : F::LANES == 2 ? 128u : 64u; }
-template <class F>
-__global__ __launch_bounds__(sum_block_threads<F>(), F::LANES == 3 ? 2 : 1) void msm_sum_kernel(SumJobs<F> jobs) {
-  u32 blk = blockIdx.x;
-  u32 which = 0;
-  if (blk >= jobs.j[0].nblocks) { blk -= jobs.j[0].nblocks; which = 1; if (blk >= jobs.j[1].nblocks) { blk -= jobs.j[1].nblocks; which = 2; } }
-  const SumDesc d = jobs.j[which].d;
-  const XYZZ<typename F::Mem> *in = jobs.j[which].in;
-  XYZZ<typename F::Mem> *out = jobs.j[which].out;
-  // (lane triples: 16 per wavefront where shuffle trees want a power of two - but all 21 when every worker sums alone, the
-  // first stage of a two-stage sum [r6]: WPB == 84 then, and the host counts its blocks accordingly)
-  constexpr u32 NWAVES = sum_block_threads<F>() / 64;
-  const u32 PW = (F::LANES == 3 && d.lanes == 1) ? default_per_wave<F>() : tree_per_wave<F>(), WPB = PW * NWAVES;   // WPB == 64
-  u32 t, gid;
-  const bool live = worker_index<F>(PW, t, gid);   // t = worker inside the block
-  const u32 G = d.lanes;
-  const u32 g = (blk * WPB + t) / G;
-  const u32 sub = t & (G - 1);
-  // single-lane G2: partial sums live in LDS slots (an XYZZ<Fp2> accumulator is 96 VGPRs) and the tree reads
-  // the partner's slot directly; G1 and K3-form G2 keep registers + shuffles
-  constexpr bool LDS_ACC = (F::LANES == 1 && F::WORDS == 24);
-  __shared__ XYZZ<F> lds_acc[LDS_ACC ? 64 : 1];
-  __shared__ XYZZ<F> wave_part[NWAVES > 1 ? NWAVES : 1][F::LANES];
-  XYZZ<F> reg_acc;
-  XYZZ<F> &acc = LDS_ACC ? lds_acc[threadIdx.x] : reg_acc;
-  xyzz_set_identity(acc);
-  if (live && g < d.groups) {
-    const u32 gg = g / d.splits, len = d.count / d.splits, k0 = (g % d.splits) * len;   // (splits == 1: the whole group)
-    const u32 outer = gg / d.inner, in_idx = gg % d.inner;
-    const XYZZ<typename F::Mem> *base = in + ((u64)outer << d.group_shift);
-    if (d.mode == SUM_STRIDED) {
-      for (u32 k = k0 + sub; k < k0 + len; k += G) {
-        XYZZ<F> o, r;
-        load_xyzz<F>(o, base + (u64)in_idx * d.istride + (u64)k * d.stride);
-        xyzz_add(r, acc, o);
-        acc = r;
-      }
-    } else {  // SUM_BITS: in_idx = bit position
-      for (u32 j = sub; j < (d.count >> 1); j += G) {
-        XYZZ<F> o, r;
-        load_xyzz<F>(o, base + nth_with_bit(j, in_idx));
-        xyzz_add(r, acc, o);
-        acc = r;
-      }
-    }
-  }
-  if (LDS_ACC) {
-    for (u32 off = G >> 1; off >= 1; off >>= 1) {
-      __syncthreads();
-      if (sub < off) {
-        XYZZ<F> r;
-        xyzz_add(r, lds_acc[threadIdx.x], lds_acc[threadIdx.x + off]);
-        lds_acc[threadIdx.x] = r;
-      }
-    }
-  } else if (NWAVES == 1 || G <= PW) {
-    group_reduce_points<F>(acc, G, sub);
-  } else {
-    // the group spans G / PW wavefronts: tree inside each wavefront, partials through LDS, tree over the partials
-    const u32 wave = threadIdx.x >> 6, t_in_wave = t - wave * PW, role = worker_role<F>();
-    group_reduce_points<F>(acc, PW, t_in_wave);
-    if (live && t_in_wave == 0) wave_part[wave][role] = acc;
-    __syncthreads();
-    const u32 wpg = G / PW;                       // wavefronts per group (2 or 4); the group's first wavefront folds
-    if ((wave & (wpg - 1)) == 0) {
-      if (live && t_in_wave < wpg) acc = wave_part[wave + t_in_wave][role]; else xyzz_set_identity(acc);
-      group_reduce_points<F>(acc, wpg, t_in_wave);
-    }
-  }
-  if (live && sub == 0 && g < d.groups) store_xyzz<F>(&out[g], acc);
-}
-
-// ============================================================================================
-// 5'. G1 point additions on lane PAIRS ("K2") for the latency-bound reductions
-// ============================================================================================
+// 5a. A point split over an x side and a y side: G1 on lane PAIRS ("K2"), G2 on lane SEXTETS ("K6")
 // A reduction launch of a small or medium job uses a fraction of the chip and is a chain of dependent point additions
 // (~14 deep for 4096 buckets), each 8.2 K instructions = 20 us on a wavefront that has its SIMD to itself.  Lanes are free
 // there, so a point is split over two neighbouring lanes - the even lane holds (X, ZZ), the odd lane (Y, ZZZ) - and the
 // general addition add-2008-s runs as SEVEN lane-local product slots instead of fourteen products:
-//     slot   even lane (x side)        odd lane (y side)
+//     slot   x side                    y side
 //      1     U1 = X1 ZZ2               S1 = Y1 ZZZ2
 //      2     U2 = X2 ZZ1               S2 = Y2 ZZZ1            then  P = U2 - U1 | R = S2 - S1
 //      3     PP = P^2                  RR = R^2                exchange: x gets RR, y gets PP
@@ -544,221 +446,108 @@ __global__ __launch_bounds__(sum_block_threads<F>(), F::LANES == 3 ? 2 : 1) void
 //      5     Q = U1 PP                 S1P = S1 PPP            x: X3 = RR - PPP - 2Q, D = Q - X3; exchange: y gets D
 //      6     T = ZZ1 ZZ2               ZZZ3 = ZT PPP
 //      7     ZZ3 = T PP                Y3 = R D - S1P
-// (three 12-word DPP exchanges, quad_perm [1,0,3,2]); an addition has about half the latency of the one-lane form, and a
-// worker holds 24 words of state instead of 48.  The rare equal-points case falls back to the one-lane doubling,
-// computed redundantly by both lanes.  Only the reduction kernels of G1 use it, and only for launches that leave at
-// least half of the SIMDs empty (msm_enqueue).
-struct HalfPt {
-  fp_t u, v;   // even lane: X, ZZ    odd lane: Y, ZZZ
-};
-__device__ __forceinline__ u32 k2_role() { return k3_lane() & 1u; }
-__device__ __forceinline__ fp_t k2_swap(const fp_t &x) {   // the value held by the other lane of my pair
-  fp_t r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.l[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)x.l[i], 0xB1, 0xf, 0xf, false);
-  return r;
-}
-__device__ __forceinline__ bool k2_flag_from(bool mine, u32 want_role) {   // the predicate as the `want_role` lane of my pair sees it
-  const u32 lane = k3_lane();
-  const u64 m = __ballot(mine);
-  return (m >> ((lane & ~1u) | want_role)) & 1;
-}
-__device__ __forceinline__ fp_t k2_sel(bool odd, const fp_t &even_v, const fp_t &odd_v) {
-  fp_t r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.l[i] = odd ? odd_v.l[i] : even_v.l[i];
-  return r;
-}
-__device__ __forceinline__ void k2_load(HalfPt &h, const XYZZ<FpOps> *p) {
-  const bool odd = k2_role();
-  h.u = odd ? p->y : p->x;
-  h.v = odd ? p->zzz : p->zz;
-}
-__device__ __forceinline__ void k2_store(XYZZ<FpOps> *p, const HalfPt &h) {
-  if (k2_role()) { p->y = h.u; p->zzz = h.v; } else { p->x = h.u; p->zz = h.v; }
-}
-__device__ __forceinline__ void k2_set_identity(HalfPt &h) { fe_zero(h.u); fe_zero(h.v); }
-__device__ __forceinline__ bool k2_is_identity(const HalfPt &h) { return k2_flag_from(fpl_is_zero(h.v), 0u); }   // ZZ == 0
-// r = a + b; r may alias a.  Every lane of a pair takes the same branches.
-__device__ __forceinline__ void k2_add(HalfPt &r, const HalfPt &a, const HalfPt &b) {
-  const bool odd = k2_role();
-  if (k2_is_identity(a)) { r = b; return; }
-  if (k2_is_identity(b)) { r = a; return; }
-  fp_t t1 = fp_mul_call(a.u, b.v);          // U1 | S1
-  fp_t t2 = fp_mul_call(b.u, a.v);          // U2 | S2
-  fp_t d;
-  fpl_sub(d, t2, t1);                       // P | R
-  const bool dz = fpl_is_zero(d);
-  if (k2_flag_from(dz, 0u)) {               // P == 0: the same x coordinate
-    if (k2_flag_from(dz, 1u)) {             // ... and R == 0: the same point - one-lane doubling, both lanes redundantly
-      XYZZ<FpOps> full, dbl;
-      const fp_t ou = k2_swap(a.u), ov = k2_swap(a.v);
-      full.x = odd ? ou : a.u; full.y = odd ? a.u : ou;
-      full.zz = odd ? ov : a.v; full.zzz = odd ? a.v : ov;
-      xyzz_dbl(dbl, full);
-      r.u = odd ? dbl.y : dbl.x;
-      r.v = odd ? dbl.zzz : dbl.zz;
-    } else {
-      k2_set_identity(r);                   // opposite points
-    }
-    return;
-  }
-  const fp_t sq = fp_sqr_call(d);           // PP | RR
-  const fp_t osq = k2_swap(sq);             // x lane: RR    y lane: PP
-  const fp_t pp = odd ? osq : sq;           // PP in both lanes
-  // slot 4: P PP | ZZZ1 ZZZ2
-  const fp_t m4 = fp_mul_call(k2_sel(odd, d, a.v), k2_sel(odd, sq, b.v));
-  const fp_t om4 = k2_swap(m4);
-  const fp_t ppp = odd ? om4 : m4;          // PPP in both lanes
-  // slot 5: U1 PP | S1 PPP
-  const fp_t m5 = fp_mul_call(t1, k2_sel(odd, pp, ppp));        // Q | S1P
-  fp_t x3, dq;
-  fpl_sub(x3, osq, ppp);                    // x lane: RR - PPP (the y lane computes garbage it never uses)
-  fpl_sub(x3, x3, m5);
-  fpl_sub(x3, x3, m5);                      // X3 = RR - PPP - 2Q
-  fpl_sub(dq, m5, x3);                      // Q - X3
-  const fp_t odq = k2_swap(dq);             // y lane: Q - X3
-  // slot 6: ZZ1 ZZ2 | ZT PPP
-  const fp_t m6 = fp_mul_call(k2_sel(odd, a.v, m4), k2_sel(odd, b.v, ppp));   // T | ZZZ3
-  // slot 7: T PP | R (Q - X3)
-  const fp_t m7 = fp_mul_call(k2_sel(odd, m6, d), k2_sel(odd, pp, odq));      // ZZ3 | R (Q - X3)
-  fp_t y3;
-  fpl_sub(y3, m7, m5);                      // y lane: Y3 = R (Q - X3) - S1P
-  r.u = odd ? y3 : x3;
-  r.v = odd ? m6 : m7;
-}
-// shuffle tree over groups of G consecutive lane pairs of one wavefront (G a power of two <= 32)
-__device__ __forceinline__ void k2_group_reduce(HalfPt &acc, u32 G, u32 sub) {
-  for (u32 off = G >> 1; off >= 1; off >>= 1) {
-    HalfPt o;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-      o.u.l[i] = __shfl_down(acc.u.l[i], off * 2);
-      o.v.l[i] = __shfl_down(acc.v.l[i], off * 2);
-    }
-    if (sub < off) k2_add(acc, acc, o);   // pairs take the branch together (sub is a property of the pair)
-  }
-}
-// worker `sub` of the G that share output g adds up its share of the output's elements
-__device__ __forceinline__ void k2_partial_sum(HalfPt &acc, const SumDesc &d, const XYZZ<FpOps> *in, u32 g, u32 sub, u32 G) {
-  const u32 gg = g / d.splits, len = d.count / d.splits, k0 = (g % d.splits) * len;   // (splits == 1: the whole group)
-  const u32 outer = gg / d.inner, in_idx = gg % d.inner;
-  const XYZZ<FpOps> *base = in + ((u64)outer << d.group_shift);
-  if (d.mode == SUM_STRIDED) {
-    for (u32 k = k0 + sub; k < k0 + len; k += G) {
-      HalfPt o;
-      k2_load(o, base + (u64)in_idx * d.istride + (u64)k * d.stride);
-      k2_add(acc, acc, o);
-    }
-  } else {  // SUM_BITS: in_idx = bit position
-    for (u32 j = sub; j < (d.count >> 1); j += G) {
-      HalfPt o;
-      k2_load(o, base + nth_with_bit(j, in_idx));
-      k2_add(acc, acc, o);
-    }
-  }
-}
-// msm_sum_kernel for G1 with lane-pair workers: one wavefront = 32 workers per block
-template <class FK>   // always FpOps: a template only so that both translation units may see the definition
-__global__ __launch_bounds__(64) void msm_sum_k2_kernel(SumJobs<FK> jobs) {
-  u32 blk = blockIdx.x;
-  u32 which = 0;
-  if (blk >= jobs.j[0].nblocks) { blk -= jobs.j[0].nblocks; which = 1; if (blk >= jobs.j[1].nblocks) { blk -= jobs.j[1].nblocks; which = 2; } }
-  const SumDesc d = jobs.j[which].d;
-  const XYZZ<FpOps> *in = jobs.j[which].in;
-  XYZZ<FpOps> *out = jobs.j[which].out;
-  const u32 t = threadIdx.x >> 1;           // worker inside the block
-  const u32 G = d.lanes;                    // workers per output (<= 32)
-  const u32 g = (blk * 32 + t) / G;
-  const u32 sub = t & (G - 1);
-  HalfPt acc;
-  k2_set_identity(acc);
-  if (g < d.groups) {
-    k2_partial_sum(acc, d, in, g, sub, G);
-  }
-  k2_group_reduce(acc, G, sub);
-  if (sub == 0 && g < d.groups) k2_store(&out[g], acc);
-}
-// The same with ONE output per workgroup of NW = blockDim.x / 64 <= 4 wavefronts (G = 32 NW workers): tree inside each wavefront,
-// the NW partial sums through LDS, tree over them in the first wavefront.  For the handful of long sums a big single bucket
-// set ends in (the 20-bit window table of a 2^20-point G1 query: 10 + 9 bit sums and a total over 512 selected points
-// each were 16 serial additions + 5 levels on one wavefront; 2 + 5 + 3 here).
-template <class FK>
-__global__ __launch_bounds__(256) void msm_sum_k2_wide_kernel(SumJobs<FK> jobs) {
-  u32 blk = blockIdx.x;
-  u32 which = 0;
-  if (blk >= jobs.j[0].nblocks) { blk -= jobs.j[0].nblocks; which = 1; if (blk >= jobs.j[1].nblocks) { blk -= jobs.j[1].nblocks; which = 2; } }
-  const SumDesc d = jobs.j[which].d;
-  const XYZZ<FpOps> *in = jobs.j[which].in;
-  XYZZ<FpOps> *out = jobs.j[which].out;
-  __shared__ HalfPt wave_part[4][2];
-  const u32 NW = blockDim.x >> 6, wave = threadIdx.x >> 6, t_in_wave = (threadIdx.x & 63u) >> 1, role = k2_role();
-  const u32 g = blk;                        // one output per workgroup
-  HalfPt acc;
-  k2_set_identity(acc);
-  if (g < d.groups) k2_partial_sum(acc, d, in, g, wave * 32 + t_in_wave, NW * 32);
-  k2_group_reduce(acc, 32, t_in_wave);
-  if (t_in_wave == 0) wave_part[wave][role] = acc;
-  __syncthreads();
-  if (wave == 0) {
-    if (t_in_wave < NW) acc = wave_part[t_in_wave][role]; else k2_set_identity(acc);
-    k2_group_reduce(acc, NW, t_in_wave);
-    if (t_in_wave == 0 && g < d.groups) k2_store(&out[g], acc);
-  }
-}
-
-// ============================================================================================
-// 5''. G2 point additions on lane SEXTETS ("K6") for the latency-bound merges [r6]
-// ============================================================================================
-// The x / y split of K2 on top of the lane triples of K3 (fp2k3.cuh): a G2 point is held by two neighbouring triples -
-// the even triple (X, ZZ), the odd triple (Y, ZZZ), each an Fp2 element in (c0, c1, c0 + c1) form - and the general
-// addition runs as SEVEN product slots of one lane-local Fp product each instead of fourteen (the table of 5' above,
-// with Fp2 products).  A level of a merge tree costs ~20 us instead of the ~37 us of the lane-triple form: what the big
+// (three 12-word exchanges); an addition has about half the latency of the one-lane form, and a worker holds 24 words of
+// state instead of 48.  The rare equal-points case falls back to the doubling of the full-point form, computed
+// redundantly by both sides.  Only the reduction kernels use it, and only for launches that leave at least half of the
+// SIMDs empty (msm_enqueue).
+// The same split on top of the lane triples of K3 (fp2k3.cuh) [r6]: a G2 point is held by two neighbouring triples - the
+// even triple (X, ZZ), the odd triple (Y, ZZZ), each an Fp2 element in (c0, c1, c0 + c1) form - and a slot is one
+// lane-local Fp product.  A level of a merge tree costs ~20 us instead of the ~37 us of the lane-triple form: what the big
 // bucket runs of boolean-heavy G2 queries and the medium runs of small window tables are made of (a 90 %-boolean G2
 // query of 2^19 points: 14 levels, 0.58 ms in lane triples - profiles/r6_call5_*).  Eight workers per wavefront (48
-// lanes: a power of two for the shuffle trees).  The side exchanges are ds_bpermute moves by +-3 lanes.
-constexpr u32 K6_PER_WAVE = 8;
-__device__ __forceinline__ u32 k6_lane_in_worker() { const u32 l = k3_lane(); return l - 6u * ((l * 43u) >> 8); }   // lane % 6
-__device__ __forceinline__ u32 k6_side() { return k6_lane_in_worker() >= 3u ? 1u : 0u; }   // 0: (X, ZZ)   1: (Y, ZZZ)
-__device__ __forceinline__ fp_t k6_swap(const fp_t &x) {   // the same role's value in the other triple of my sextet
-  const int src = (int)k3_lane() + (k6_side() ? -3 : 3);
+// lanes: a power of two for the shuffle trees).
+struct HalfPt {
+  fp_t u, v;   // x side: X, ZZ    y side: Y, ZZZ
+};
+__device__ __forceinline__ fp_t half_sel(bool y, const fp_t &x_v, const fp_t &y_v) {
   fp_t r;
 #pragma unroll
-  for (int i = 0; i < 12; i++) r.l[i] = (u32)__shfl((int)x.l[i], src);
+  for (int i = 0; i < 12; i++) r.l[i] = y ? y_v.l[i] : x_v.l[i];
   return r;
 }
-// the (triple-uniform) predicate as the `want_side` triple of my sextet sees it
-__device__ __forceinline__ bool k6_flag_from(bool mine, u32 want_side) {
-  const u32 lane = k3_lane();
-  const u64 m = __ballot(mine);
-  return (m >> (lane - k6_lane_in_worker() + 3u * want_side)) & 1;
-}
-__device__ __forceinline__ void k6_load(HalfPt &h, const XYZZ<Fp2Ops> *p) {
-  const bool y = k6_side();
-  Fp2K3Ops::load(h.u, y ? &p->y : &p->x);
-  Fp2K3Ops::load(h.v, y ? &p->zzz : &p->zz);
-}
-__device__ __forceinline__ void k6_store(XYZZ<Fp2Ops> *p, const HalfPt &h) {
-  const bool y = k6_side();
-  Fp2K3Ops::store(y ? &p->y : &p->x, h.u);
-  Fp2K3Ops::store(y ? &p->zzz : &p->zz, h.v);
-}
-__device__ __forceinline__ bool k6_is_identity(const HalfPt &h) { return k6_flag_from(Fp2K3Ops::is_zero(h.v), 0u); }   // ZZ == 0
-// r = a + b; r may alias a.  Every lane of a sextet takes the same branches.
-__device__ __forceinline__ void k6_add(HalfPt &r, const HalfPt &a, const HalfPt &b) {
+// What a half-point form is made of: the field bundle F of one side (XYZZ<F> is the full point of the doubling fallback),
+// the records it reads (XYZZ<Mem>), and how a lane finds its worker, its side and the other side's values.
+struct PairHalf {   // G1: the even lane of a pair is the x side, the odd lane the y side
+  typedef FpOps F;
+  typedef FpOps Mem;
+  static constexpr u32 LANES = 2, PER_WAVE = 32;
+  __device__ __forceinline__ static bool index(u32 &in_block) { in_block = threadIdx.x >> 1; return true; }
+  __device__ __forceinline__ static u32 role() { return k3_lane() & 1u; }
+  __device__ __forceinline__ static u32 side() { return role(); }
+  __device__ __forceinline__ static fp_t swap(const fp_t &x) {   // the value held by the other lane of my pair (DPP quad_perm [1,0,3,2])
+    fp_t r;
+#pragma unroll
+    for (int i = 0; i < 12; i++) r.l[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)x.l[i], 0xB1, 0xf, 0xf, false);
+    return r;
+  }
+  __device__ __forceinline__ static bool flag_from(bool mine, u32 want_side) {   // the predicate as the `want_side` lane of my pair sees it
+    const u32 lane = k3_lane();
+    const u64 m = __ballot(mine);
+    return (m >> ((lane & ~1u) | want_side)) & 1;
+  }
+  __device__ __forceinline__ static void load(HalfPt &h, const XYZZ<FpOps> *p) {
+    const bool odd = side();
+    h.u = odd ? p->y : p->x;
+    h.v = odd ? p->zzz : p->zz;
+  }
+  __device__ __forceinline__ static void store(XYZZ<FpOps> *p, const HalfPt &h) {
+    if (side()) { p->y = h.u; p->zzz = h.v; } else { p->x = h.u; p->zz = h.v; }
+  }
+};
+constexpr u32 K6_PER_WAVE = 8;
+struct SextetHalf {   // G2: the even triple of a sextet is the x side, the odd triple the y side
   typedef Fp2K3Ops F;
-  const bool y = k6_side();
-  if (k6_is_identity(a)) { r = b; return; }
-  if (k6_is_identity(b)) { r = a; return; }
+  typedef Fp2Ops Mem;
+  static constexpr u32 LANES = 6, PER_WAVE = K6_PER_WAVE;
+  __device__ __forceinline__ static bool index(u32 &in_block) {
+    const u32 t = (k3_lane() * 43u) >> 8;   // sextet inside the wavefront
+    in_block = (threadIdx.x >> 6) * PER_WAVE + t;
+    return t < PER_WAVE;
+  }
+  __device__ __forceinline__ static u32 role() { const u32 l = k3_lane(); return l - 6u * ((l * 43u) >> 8); }   // lane % 6
+  __device__ __forceinline__ static u32 side() { return role() >= 3u ? 1u : 0u; }
+  __device__ __forceinline__ static fp_t swap(const fp_t &x) {   // the same role's value in the other triple of my sextet (ds_bpermute by +-3 lanes)
+    const int src = (int)k3_lane() + (side() ? -3 : 3);
+    fp_t r;
+#pragma unroll
+    for (int i = 0; i < 12; i++) r.l[i] = (u32)__shfl((int)x.l[i], src);
+    return r;
+  }
+  // the (triple-uniform) predicate as the `want_side` triple of my sextet sees it
+  __device__ __forceinline__ static bool flag_from(bool mine, u32 want_side) {
+    const u32 lane = k3_lane();
+    const u64 m = __ballot(mine);
+    return (m >> (lane - role() + 3u * want_side)) & 1;
+  }
+  __device__ __forceinline__ static void load(HalfPt &h, const XYZZ<Fp2Ops> *p) {
+    const bool y = side();
+    Fp2K3Ops::load(h.u, y ? &p->y : &p->x);
+    Fp2K3Ops::load(h.v, y ? &p->zzz : &p->zz);
+  }
+  __device__ __forceinline__ static void store(XYZZ<Fp2Ops> *p, const HalfPt &h) {
+    const bool y = side();
+    Fp2K3Ops::store(y ? &p->y : &p->x, h.u);
+    Fp2K3Ops::store(y ? &p->zzz : &p->zz, h.v);
+  }
+};
+template <class P>
+__device__ __forceinline__ bool half_is_identity(const HalfPt &h) { return P::flag_from(P::F::is_zero(h.v), 0u); }   // ZZ == 0
+// r = a + b; r may alias a.  Every lane of a worker takes the same branches.
+template <class P>
+__device__ __forceinline__ void half_add(HalfPt &r, const HalfPt &a, const HalfPt &b) {
+  typedef typename P::F F;
+  const bool y = P::side();
+  if (half_is_identity<P>(a)) { r = b; return; }
+  if (half_is_identity<P>(b)) { r = a; return; }
   fp_t t1, t2, d;
   F::mul(t1, a.u, b.v);                     // U1 | S1
   F::mul(t2, b.u, a.v);                     // U2 | S2
   F::sub(d, t2, t1);                        // P | R
   const bool dz = F::is_zero(d);
-  if (k6_flag_from(dz, 0u)) {               // P == 0: the same x coordinate
-    if (k6_flag_from(dz, 1u)) {             // ... and R == 0: the same point - the lane-triple doubling, both triples redundantly
+  if (P::flag_from(dz, 0u)) {               // P == 0: the same x coordinate
+    if (P::flag_from(dz, 1u)) {             // ... and R == 0: the same point - the full-point doubling, both sides redundantly
       XYZZ<F> full, dbl;
-      const fp_t ou = k6_swap(a.u), ov = k6_swap(a.v);
+      const fp_t ou = P::swap(a.u), ov = P::swap(a.v);
       full.x = y ? ou : a.u; full.y = y ? a.u : ou;
       full.zz = y ? ov : a.v; full.zzz = y ? a.v : ov;
       xyzz_dbl(dbl, full);
@@ -771,90 +560,205 @@ __device__ __forceinline__ void k6_add(HalfPt &r, const HalfPt &a, const HalfPt 
   }
   fp_t sq, m4, m5, m6, m7;
   F::sqr(sq, d);                            // PP | RR
-  const fp_t osq = k6_swap(sq);             // x side: RR    y side: PP
+  const fp_t osq = P::swap(sq);             // x side: RR    y side: PP
   const fp_t pp = y ? osq : sq;             // PP on both sides
-  F::mul(m4, k2_sel(y, d, a.v), k2_sel(y, sq, b.v));        // P PP | ZZZ1 ZZZ2
-  const fp_t om4 = k6_swap(m4);
+  F::mul(m4, half_sel(y, d, a.v), half_sel(y, sq, b.v));        // P PP | ZZZ1 ZZZ2
+  const fp_t om4 = P::swap(m4);
   const fp_t ppp = y ? om4 : m4;            // PPP on both sides
-  F::mul(m5, t1, k2_sel(y, pp, ppp));       // Q | S1P
+  F::mul(m5, t1, half_sel(y, pp, ppp));     // Q | S1P
   fp_t x3, dq, y3;
   F::sub(x3, osq, ppp);                     // x side: RR - PPP (the y side computes garbage it never uses)
   F::sub(x3, x3, m5);
   F::sub(x3, x3, m5);                       // X3 = RR - PPP - 2Q
   F::sub(dq, m5, x3);                       // Q - X3
-  const fp_t odq = k6_swap(dq);             // y side: Q - X3
-  F::mul(m6, k2_sel(y, a.v, m4), k2_sel(y, b.v, ppp));      // T | ZZZ3
-  F::mul(m7, k2_sel(y, m6, d), k2_sel(y, pp, odq));         // ZZ3 | R (Q - X3)
+  const fp_t odq = P::swap(dq);             // y side: Q - X3
+  F::mul(m6, half_sel(y, a.v, m4), half_sel(y, b.v, ppp));      // T | ZZZ3
+  F::mul(m7, half_sel(y, m6, d), half_sel(y, pp, odq));         // ZZ3 | R (Q - X3)
   F::sub(y3, m7, m5);                       // y side: Y3 = R (Q - X3) - S1P
   r.u = y ? y3 : x3;
   r.v = y ? m6 : m7;
 }
-// shuffle tree over groups of G consecutive sextets of one wavefront (G a power of two <= 8)
-__device__ __forceinline__ void k6_group_reduce(HalfPt &acc, u32 G, u32 sub) {
+// shuffle tree over groups of G consecutive workers of one wavefront (G a power of two <= PER_WAVE)
+template <class P>
+__device__ __forceinline__ void half_group_reduce(HalfPt &acc, u32 G, u32 sub) {
   for (u32 off = G >> 1; off >= 1; off >>= 1) {
     HalfPt o;
 #pragma unroll
     for (int i = 0; i < 12; i++) {
-      o.u.l[i] = __shfl_down(acc.u.l[i], off * 6);
-      o.v.l[i] = __shfl_down(acc.v.l[i], off * 6);
+      o.u.l[i] = __shfl_down(acc.u.l[i], off * P::LANES);
+      o.v.l[i] = __shfl_down(acc.v.l[i], off * P::LANES);
     }
-    if (sub < off) k6_add(acc, acc, o);   // sextets take the branch together
+    if (sub < off) half_add<P>(acc, acc, o);   // the lanes of a worker take the branch together (sub is a property of the worker)
   }
 }
 
-// msm_sum_kernel for G2 with lane-sextet workers: 256 threads = four wavefronts of 8 sextets = 32 workers per block; a
-// group of G <= 8 workers folds inside its wavefront, 16 or 32 through LDS.  For the launches that leave the chip mostly
-// empty (the bucket sets of small window tables: a MiMC-322 proof's G2 job spent 2 x 136 us here in lane triples).
-template <class FK>   // always Fp2K3Ops: a template only so that both translation units may see the definition
-__global__ __launch_bounds__(256) void msm_sum_k6_kernel(SumJobs<FK> jobs) {
+// 5b. Worker policies: what the sum kernel and the merge kernels are written over.  A worker is a lane / lane pair / lane
+// triple of bundle F holding an XYZZ point, or a lane pair (G1) / sextet (G2) holding half a point (5a).  PER_WAVE workers
+// of a wavefront take part in shuffle trees; SOLO_PER_WAVE fit where every worker sums alone (all 21 lane triples).
+template <class F>
+struct XyzzWorker {
+  typedef XYZZ<F> Pt;
+  typedef F Ops;
+  typedef typename F::Mem Mem;
+  static constexpr u32 PER_WAVE = tree_per_wave<F>(), SOLO_PER_WAVE = default_per_wave<F>(), LANES = F::LANES;
+  __device__ __forceinline__ static bool index(u32 &in_block, u32 per_wave = PER_WAVE) { u32 g; return worker_index<F>(per_wave, in_block, g); }
+  __device__ __forceinline__ static u32 role() { return worker_role<F>(); }
+  __device__ __forceinline__ static void identity(Pt &p) { xyzz_set_identity(p); }
+  __device__ __forceinline__ static bool is_identity(const Pt &p) { return xyzz_is_identity(p); }
+  __device__ __forceinline__ static void load(Pt &p, const XYZZ<Mem> *m) { load_xyzz<F>(p, m); }
+  __device__ __forceinline__ static void store(XYZZ<Mem> *m, const Pt &p) { store_xyzz<F>(m, p); }
+  __device__ __forceinline__ static void add(Pt &acc, const Pt &o) { Pt r; xyzz_add(r, acc, o); acc = r; }
+  __device__ __forceinline__ static void tree(Pt &acc, u32 G, u32 sub) { group_reduce_points<F>(acc, G, sub); }
+};
+template <class P>
+struct HalfWorker {
+  typedef HalfPt Pt;
+  typedef P Half;
+  typedef typename P::Mem Mem;
+  static constexpr u32 PER_WAVE = P::PER_WAVE, SOLO_PER_WAVE = P::PER_WAVE, LANES = P::LANES;
+  __device__ __forceinline__ static bool index(u32 &in_block, u32 = PER_WAVE) { return P::index(in_block); }
+  __device__ __forceinline__ static u32 role() { return P::role(); }
+  __device__ __forceinline__ static void identity(Pt &p) { fe_zero(p.u); fe_zero(p.v); }
+  __device__ __forceinline__ static bool is_identity(const Pt &p) { return half_is_identity<P>(p); }
+  __device__ __forceinline__ static void load(Pt &p, const XYZZ<Mem> *m) { P::load(p, m); }
+  __device__ __forceinline__ static void store(XYZZ<Mem> *m, const Pt &p) { P::store(m, p); }
+  __device__ __forceinline__ static void add(Pt &acc, const Pt &o) { half_add<P>(acc, acc, o); }
+  __device__ __forceinline__ static void tree(Pt &acc, u32 G, u32 sub) { half_group_reduce<P>(acc, G, sub); }
+};
+typedef HalfWorker<PairHalf> K2Worker;
+typedef HalfWorker<SextetHalf> K6Worker;
+// A group of wpg * PW workers spans wpg wavefronts (a power of two): tree inside each wavefront, the partials through LDS,
+// tree over the partials in the group's first wavefront -> the group's first worker.  `t` = worker inside the workgroup;
+// every thread of the workgroup calls it.
+template <class WK>
+__device__ __forceinline__ void fold_over_waves(typename WK::Pt &acc, bool live, u32 PW, u32 wpg, u32 t, typename WK::Pt (*wave_part)[WK::LANES]) {
+  const u32 wave = threadIdx.x >> 6, t_in_wave = t - wave * PW, role = WK::role();
+  WK::tree(acc, PW, t_in_wave);
+  if (live && t_in_wave == 0) wave_part[wave][role] = acc;
+  __syncthreads();
+  if ((wave & (wpg - 1)) == 0) {
+    if (live && t_in_wave < wpg) acc = wave_part[wave + t_in_wave][role]; else WK::identity(acc);
+    WK::tree(acc, wpg, t_in_wave);
+  }
+}
+
+// 5c. The sum kernel: G workers per output point (serial partial sums, then a tree)
+// the j-th index with bit k set, j = 0, 1, ...  (SUM_BITS walks exactly the selected half of its vector: striding over ALL
+// indices left the workers whose own index has bit k clear - k < log2 G - with nothing to add and the others with twice the
+// chain; [r6] 13 -> 9 levels for the bit sums of a 2^15-bucket window, 37 -> 21 for a 2^19-bucket set)
+__device__ __forceinline__ u32 nth_with_bit(u32 j, u32 k) { return ((j >> k) << (k + 1)) | (1u << k) | (j & ((1u << k) - 1u)); }
+// out[g] = sum of a set of in[] points chosen by the mode:
+//   SUM_STRIDED: g = (outer, inner): elements in[(outer << group_shift) + inner*istride + t*stride], t < count
+//   SUM_BITS   : g = (outer, k):     elements in[(outer << group_shift) + i], i < count, bit k of i set
+template <class M>   // the records' field bundle
+struct SumJob {
+  const XYZZ<M> *in;
+  XYZZ<M> *out;
+  SumDesc d;       // (groups == 0: nothing to do)
+  u32 nblocks = 0; // workgroups assigned to this job: sum_count fills it in
+};
+// up to three independent reductions per launch (rows + columns, then the bit-sum sets and the
+// plain window totals): they are latency-bound, so sharing a launch lets the hardware overlap them.
+template <class M>
+struct SumJobs {
+  SumJob<M> j[3];
+};
+// worker `sub` of the G that share output g adds up its share of the output's elements
+template <class WK>
+__device__ __forceinline__ void partial_sum(typename WK::Pt &acc, const SumDesc &d, const XYZZ<typename WK::Mem> *in, u32 g, u32 sub, u32 G) {
+  const u32 gg = g / d.splits, len = d.count / d.splits, k0 = (g % d.splits) * len;   // (splits == 1: the whole group)
+  const u32 outer = gg / d.inner, in_idx = gg % d.inner;
+  const XYZZ<typename WK::Mem> *base = in + ((u64)outer << d.group_shift);
+  if (d.mode == SUM_STRIDED) {
+    for (u32 k = k0 + sub; k < k0 + len; k += G) {
+      typename WK::Pt o;
+      WK::load(o, base + (u64)in_idx * d.istride + (u64)k * d.stride);
+      WK::add(acc, o);
+    }
+  } else {  // SUM_BITS: in_idx = bit position
+    for (u32 j = sub; j < (d.count >> 1); j += G) {
+      typename WK::Pt o;
+      WK::load(o, base + nth_with_bit(j, in_idx));
+      WK::add(acc, o);
+    }
+  }
+}
+// workers of a wavefront in a job of `lanes` workers per output: PER_WAVE (a power of two for the trees) - but all of
+// SOLO_PER_WAVE when every worker sums alone, the first stage of a two-stage sum on lane triples [r6]: 84 per workgroup
+template <class WK>
+BH_HD constexpr u32 sum_per_wave(u32 lanes) { return (WK::SOLO_PER_WAVE != WK::PER_WAVE && lanes == 1) ? WK::SOLO_PER_WAVE : WK::PER_WAVE; }
+// the one-lane and lane-triple forms put 64 workers in a workgroup: one wavefront of single lanes, or FOUR wavefronts of
+// 16 lane triples - so that a K3 reduction can also put up to 64 workers on one output; with 16 the 256-element column
+// sums of a window table's 2^15 buckets were 16 + 4 additions deep
+template <class F>
+constexpr u32 sum_waves() { return F::LANES == 3 ? 4u : 1u; }
+// A workgroup is NWAVES wavefronts; a group of G <= PER_WAVE workers folds inside its wavefront, a wider one (up to the
+// whole workgroup) through LDS.  What runs where (msm_enqueue decides):
+//   one lane per point, 1 wavefront      G1 and single-lane G2 launches that fill the chip
+//   lane triples, 4 wavefronts           the same for K3-form G2
+//   lane pairs, 1 wavefront              G1 launches that leave SIMDs empty: 32 workers per workgroup
+//   lane pairs, 2 or 4 wavefronts        ONE output per workgroup (G = 32 NWAVES) for the handful of long sums a big single
+//                                        bucket set ends in (the 20-bit window table of a 2^20-point G1 query: 10 + 9 bit
+//                                        sums and a total over 512 selected points each were 16 serial additions + 5 levels
+//                                        on one wavefront; 2 + 5 + 3 here)
+//   lane sextets, 4 wavefronts           G2 launches that leave the chip mostly empty (the bucket sets of small window
+//                                        tables: a MiMC-322 proof's G2 job spent 2 x 136 us here in lane triples)
+template <class WK, u32 NWAVES>
+__global__ __launch_bounds__(64 * NWAVES, WK::LANES == 3 ? 2 : 1) void msm_sum_kernel(SumJobs<typename WK::Mem> jobs) {
+  typedef typename WK::Pt Pt;
   u32 blk = blockIdx.x;
   u32 which = 0;
   if (blk >= jobs.j[0].nblocks) { blk -= jobs.j[0].nblocks; which = 1; if (blk >= jobs.j[1].nblocks) { blk -= jobs.j[1].nblocks; which = 2; } }
   const SumDesc d = jobs.j[which].d;
-  const XYZZ<Fp2Ops> *in = jobs.j[which].in;
-  XYZZ<Fp2Ops> *out = jobs.j[which].out;
-  constexpr u32 PW = K6_PER_WAVE, WPB = 4 * PW;   // 32 workers per block
-  __shared__ HalfPt wave_part[4][6];
-  const u32 lane = k3_lane(), t_in_wave = (lane * 43u) >> 8, wave = threadIdx.x >> 6, role = k6_lane_in_worker();
-  const bool live = t_in_wave < PW;
-  const u32 t = wave * PW + t_in_wave;      // worker inside the block
-  const u32 G = d.lanes;                    // workers per output (a power of two <= 32)
+  const XYZZ<typename WK::Mem> *in = jobs.j[which].in;
+  XYZZ<typename WK::Mem> *out = jobs.j[which].out;
+  const u32 PW = sum_per_wave<WK>(d.lanes), WPB = PW * NWAVES;
+  u32 t;
+  const bool live = WK::index(t, PW);   // t = worker inside the workgroup
+  const u32 G = d.lanes;
   const u32 g = (blk * WPB + t) / G;
   const u32 sub = t & (G - 1);
-  HalfPt acc;
-  fe_zero(acc.u); fe_zero(acc.v);
-  if (live && g < d.groups) {
-    const u32 gg = g / d.splits, len = d.count / d.splits, k0 = (g % d.splits) * len;   // (splits == 1: the whole group)
-    const u32 outer = gg / d.inner, in_idx = gg % d.inner;
-    const XYZZ<Fp2Ops> *base = in + ((u64)outer << d.group_shift);
-    if (d.mode == SUM_STRIDED) {
-      for (u32 k = k0 + sub; k < k0 + len; k += G) {
-        HalfPt o;
-        k6_load(o, base + (u64)in_idx * d.istride + (u64)k * d.stride);
-        k6_add(acc, acc, o);
-      }
-    } else {  // SUM_BITS: in_idx = bit position
-      for (u32 j = sub; j < (d.count >> 1); j += G) {
-        HalfPt o;
-        k6_load(o, base + nth_with_bit(j, in_idx));
-        k6_add(acc, acc, o);
-      }
+  // single-lane G2: partial sums live in LDS slots (an XYZZ<Fp2> accumulator is 96 VGPRs) and the tree reads
+  // the partner's slot directly; every other form keeps registers + shuffles
+  constexpr bool LDS_ACC = (WK::LANES == 1 && sizeof(Pt) > 200);
+  __shared__ Pt lds_acc[LDS_ACC ? 64 : 1];
+  __shared__ Pt wave_part[NWAVES][WK::LANES];
+  Pt reg_acc;
+  Pt &acc = LDS_ACC ? lds_acc[threadIdx.x] : reg_acc;
+  WK::identity(acc);
+  if (live && g < d.groups) partial_sum<WK>(acc, d, in, g, sub, G);
+  if constexpr (LDS_ACC) {
+    for (u32 off = G >> 1; off >= 1; off >>= 1) {
+      __syncthreads();
+      if (sub < off) WK::add(lds_acc[threadIdx.x], lds_acc[threadIdx.x + off]);
     }
-  }
-  if (G <= PW) {
-    k6_group_reduce(acc, G, sub);
+  } else if (NWAVES == 1 || G <= PW) {
+    WK::tree(acc, G, sub);
   } else {
-    // the group spans G / 8 wavefronts: tree inside each wavefront, partials through LDS, tree over the partials
-    k6_group_reduce(acc, PW, t_in_wave);
-    if (live && t_in_wave == 0) wave_part[wave][role] = acc;
-    __syncthreads();
-    const u32 wpg = G / PW;                      // wavefronts per group (2 or 4); the group's first wavefront folds
-    if ((wave & (wpg - 1)) == 0) {
-      if (live && t_in_wave < wpg) acc = wave_part[wave + t_in_wave][role]; else { fe_zero(acc.u); fe_zero(acc.v); }
-      k6_group_reduce(acc, wpg, t_in_wave);
-    }
+    fold_over_waves<WK>(acc, live, PW, G / PW, t, wave_part);
   }
-  if (live && sub == 0 && g < d.groups) k6_store(&out[g], acc);
+  if (live && sub == 0 && g < d.groups) WK::store(&out[g], acc);
+}
+// The one place that counts: clamps every job's workers per output to what a workgroup holds and fills in its
+// workgroups; returns their total
+template <class WK, u32 NWAVES>
+static u32 sum_count(SumJobs<typename WK::Mem> &js) {
+  u32 total = 0;
+  for (int q = 0; q < 3; q++) {
+    SumJob<typename WK::Mem> &j = js.j[q];
+    if (j.d.lanes > NWAVES * WK::PER_WAVE) j.d.lanes = NWAVES * WK::PER_WAVE;
+    const u32 wpb = NWAVES * sum_per_wave<WK>(j.d.lanes);
+    j.nblocks = (u32)(((u64)j.d.groups * j.d.lanes + wpb - 1) / wpb);
+    total += j.nblocks;
+  }
+  return total;
+}
+template <class WK, u32 NWAVES>
+static bool sum_launch(SumJobs<typename WK::Mem> js, hipStream_t st) {
+  const u32 total = sum_count<WK, NWAVES>(js);
+  if (!total) return true;
+  hipLaunchKernelGGL((msm_sum_kernel<WK, NWAVES>), dim3(total), dim3(64 * NWAVES), 0, st, js);
+  return hipGetLastError() == hipSuccess;
 }
 
 // ============================================================================================
@@ -868,48 +772,6 @@ __global__ __launch_bounds__(256) void msm_sum_k6_kernel(SumJobs<FK> jobs) {
 // into pieces of 2 x (workers of a 256-thread workgroup) partials - one serial addition, then the tree, four wavefronts on
 // four SIMDs - spread over the chip, and the workgroup that finishes a run's last piece (a counter in the run's record)
 // folds the piece results the same way: depth ~ log2 L + 2.
-// A worker is a lane / lane triple of bundle F holding an XYZZ point, or - G1 - a lane PAIR holding half a point (K2 above).
-template <class F>
-struct XyzzWorker {
-  typedef XYZZ<F> Pt;
-  typedef typename F::Mem Mem;
-  static constexpr u32 PER_WAVE = tree_per_wave<F>(), LANES = F::LANES;
-  __device__ __forceinline__ static bool index(u32 &in_block) { u32 g; return worker_index<F>(PER_WAVE, in_block, g); }
-  __device__ __forceinline__ static u32 role() { return worker_role<F>(); }
-  __device__ __forceinline__ static void identity(Pt &p) { xyzz_set_identity(p); }
-  __device__ __forceinline__ static void load(Pt &p, const XYZZ<Mem> *m) { load_xyzz<F>(p, m); }
-  __device__ __forceinline__ static void store(XYZZ<Mem> *m, const Pt &p) { store_xyzz<F>(m, p); }
-  __device__ __forceinline__ static void add(Pt &acc, const Pt &o) { Pt r; xyzz_add(r, acc, o); acc = r; }
-  __device__ __forceinline__ static void tree(Pt &acc, u32 G, u32 sub) { group_reduce_points<F>(acc, G, sub); }
-};
-struct K2Worker {
-  typedef HalfPt Pt;
-  typedef FpOps Mem;
-  static constexpr u32 PER_WAVE = 32, LANES = 2;
-  __device__ __forceinline__ static bool index(u32 &in_block) { in_block = threadIdx.x >> 1; return true; }
-  __device__ __forceinline__ static u32 role() { return k2_role(); }
-  __device__ __forceinline__ static void identity(Pt &p) { k2_set_identity(p); }
-  __device__ __forceinline__ static void load(Pt &p, const XYZZ<FpOps> *m) { k2_load(p, m); }
-  __device__ __forceinline__ static void store(XYZZ<FpOps> *m, const Pt &p) { k2_store(m, p); }
-  __device__ __forceinline__ static void add(Pt &acc, const Pt &o) { k2_add(acc, acc, o); }
-  __device__ __forceinline__ static void tree(Pt &acc, u32 G, u32 sub) { k2_group_reduce(acc, G, sub); }
-};
-struct K6Worker {   // G2 on lane sextets (5'' above)
-  typedef HalfPt Pt;
-  typedef Fp2Ops Mem;
-  static constexpr u32 PER_WAVE = K6_PER_WAVE, LANES = 6;
-  __device__ __forceinline__ static bool index(u32 &in_block) {
-    const u32 t = (k3_lane() * 43u) >> 8;   // sextet inside the wavefront
-    in_block = (threadIdx.x >> 6) * PER_WAVE + t;
-    return t < PER_WAVE;
-  }
-  __device__ __forceinline__ static u32 role() { return k6_lane_in_worker(); }
-  __device__ __forceinline__ static void identity(Pt &p) { fe_zero(p.u); fe_zero(p.v); }
-  __device__ __forceinline__ static void load(Pt &p, const XYZZ<Fp2Ops> *m) { k6_load(p, m); }
-  __device__ __forceinline__ static void store(XYZZ<Fp2Ops> *m, const Pt &p) { k6_store(m, p); }
-  __device__ __forceinline__ static void add(Pt &acc, const Pt &o) { k6_add(acc, acc, o); }
-  __device__ __forceinline__ static void tree(Pt &acc, u32 G, u32 sub) { k6_group_reduce(acc, G, sub); }
-};
 constexpr u32 LONG_THREADS = 256;
 template <class WK>
 constexpr u32 long_workers() { return (LONG_THREADS / 64) * WK::PER_WAVE; }
@@ -918,17 +780,7 @@ constexpr u32 long_piece() { return 2 * long_workers<WK>(); }   // partials per 
 // sum over the workgroup's workers -> worker 0 (every thread of the workgroup calls it)
 template <class WK>
 __device__ __forceinline__ void long_block_sum(typename WK::Pt &acc, bool live, u32 wid, typename WK::Pt (*wave_part)[WK::LANES]) {
-  constexpr u32 PW = WK::PER_WAVE, NWAVES = LONG_THREADS / 64;
-  const u32 wave = threadIdx.x >> 6, t_in_wave = wid - wave * PW, role = WK::role();
-  if (live) {
-    WK::tree(acc, PW, t_in_wave);
-    if (t_in_wave == 0) wave_part[wave][role] = acc;
-  }
-  __syncthreads();
-  if (wave == 0 && live) {
-    if (t_in_wave < NWAVES) acc = wave_part[t_in_wave][role]; else WK::identity(acc);
-    WK::tree(acc, NWAVES, t_in_wave);
-  }
+  fold_over_waves<WK>(acc, live, WK::PER_WAVE, LONG_THREADS / 64, wid, wave_part);
   __syncthreads();
 }
 // Medium runs: tail[l0] + sum of head[l0+1 .. l1] by G workers per run (G a power of two chosen by the host, PER_WAVE / G
@@ -1259,7 +1111,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // [r6] G2 in lane triples: the same on lane SEXTETS (K6Worker)
   constexpr bool G1_PAIRS = std::is_same<FR, FpOps>::value, G2_SEXTETS = std::is_same<FR, Fp2K3Ops>::value;
   constexpr bool PAIRS_POSSIBLE = G1_PAIRS || G2_SEXTETS;   // "pairs" below: the half-point worker of the group
-  typedef typename std::conditional<G1_PAIRS, K2Worker, typename std::conditional<G2_SEXTETS, K6Worker, XyzzWorker<FR>>::type>::type HalfWorker;
+  typedef typename std::conditional<G1_PAIRS, K2Worker, typename std::conditional<G2_SEXTETS, K6Worker, XyzzWorker<FR>>::type>::type HalfWK;
   constexpr double LEVEL_US = G2_SEXTETS ? 37.0 : 19.0, HALF_LEVEL_US = G2_SEXTETS ? 20.0 : 10.5;   // a tree level, by worker kind
   u32 run_lanes = 8;
   bool runs_on_pairs = false;
@@ -1275,7 +1127,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
       }
     };
     sweep(tree_per_wave<FR>(), LEVEL_US, false);
-    if (PAIRS_POSSIBLE) sweep(HalfWorker::PER_WAVE, HALF_LEVEL_US, true);
+    if (PAIRS_POSSIBLE) sweep(HalfWK::PER_WAVE, HALF_LEVEL_US, true);
     // (the model takes every bucket for a queued run - true of window-table plans; where a typical bucket fits a chunk only
     // the few outliers are queued and the chip has the lanes)
     if (PAIRS_POSSIBLE && avg_chunks <= 1.0) { run_lanes = 8; runs_on_pairs = true; }
@@ -1287,7 +1139,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // 2^11 G2 points: 64 chunks per bucket) "big" starts at twice the average (round 6, first cut: half of that table's runs
   // went down the long path, 0.81 -> 1.06 ms)
   const u32 big_chunks = std::max(std::max(32u, 4u * run_lanes), (u32)(2.0 * (double)p.n / (double)p.nb / (double)p.chunk));
-  const u32 piece = long_piece<HalfWorker>();
+  const u32 piece = long_piece<HalfWK>();
   const u32 max_big = (u32)(nslots / (big_chunks + 1) + 1);
   // sum of ceil(L_r / piece) over the big runs: consecutive runs share one chunk, so sum L_r <= nslots + max_big
   const u32 max_pieces = (u32)((nslots + max_big) / piece + max_big + 1);
@@ -1446,10 +1298,10 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     // One launch (medium runs and big pieces side by side) - except the 128-bucket window tables of tiny G2 vectors, whose
     // 128 medium runs are the whole job: two launches there (G2 2^10: 0.74 against 0.85 ms; 2^12 ... 2^16 and every G1 size are
     // equal or faster fused - G1 2^16 0.79 against 0.88 ms; profiles/r6_call15_tail_split_ab.txt).  The big pieces always run
-    // on the half-point worker (HalfWorker is XyzzWorker<FR> where the group has none)
+    // on the half-point worker (HalfWK is XyzzWorker<FR> where the group has none)
     if constexpr (PAIRS_POSSIBLE) {
-      if (runs_on_pairs) BH_TAIL(HalfWorker, HalfWorker);
-      else BH_TAIL(XyzzWorker<FR>, HalfWorker);
+      if (runs_on_pairs) BH_TAIL(HalfWK, HalfWK);
+      else BH_TAIL(XyzzWorker<FR>, HalfWK);
     } else if (p.NB > 128) {
       BH_TAIL(XyzzWorker<FR>, XyzzWorker<FR>);
     } else {
@@ -1464,7 +1316,8 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // 5. reduce: rows (sum over lo, contiguous), columns (sum over hi, stride Lw), then bits.
   // G workers per output chosen so that each launch is about one wavefront per SIMD.
   Pt *rows = rowcol, *cols = rowcol + (u64)p.W * H;
-  constexpr u32 PW = 64;   // workers per block of the sum kernel (one wavefront, or four wavefronts of 16 lane triples)
+  typedef XyzzWorker<FR> FullWK;   // the launches that fill the chip: one lane (triple) per point
+  constexpr u32 NW = sum_waves<FR>(), PW = NW * FullWK::PER_WAVE;   // workers per workgroup of that kernel: 64
   // workers per output: minimise (serial adds per worker + tree depth) x (waves per SIMD, at least 1);
   // these kernels are latency-bound chains of point additions, not throughput-bound.
   auto pick_lanes = [&](u32 groups, u32 count) {
@@ -1472,93 +1325,64 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     // interleave for free in these mad-bound chains (G1 2^17-2^20 reduce 0.73-0.99 ms modelled with 1, 0.92-1.19 ms with 2; G2
     // within noise: profiles/archive/r2_call8_slots.txt); a block of lane triples is four wavefronts
     const double slots = (double)c.num_cus * 4;
-    const double waves_per_block = FR::LANES == 3 ? 4.0 : 1.0;
     u32 best = 1;
     double best_cost = 1e30;
     for (u32 g = 1, lg = 0; g <= PW; g <<= 1, lg++) {
       if (g > count && g > 1) break;
       // a lane-triple group wider than one wavefront pays two barriers and an LDS round trip (measured: ~2 additions)
       const double steps = (double)((count + g - 1) / g) + lg + ((FR::LANES == 3 && g > 16) ? 2.0 : 0.0);
-      const double waves = (double)groups * g / (double)PW * waves_per_block;
+      const double waves = (double)groups * g / (double)PW * (double)NW;
       const double cost = steps * std::max(1.0, waves / slots);
       if (cost < best_cost) { best_cost = cost; best = g; }
     }
     return best;
   };
-  auto blocks_for = [&](u32 groups, u32 lanes) { return (u32)(((u64)groups * lanes + PW - 1) / PW); };
   auto make_job = [&](const Pt *in, Pt *out, SumDesc d) {
-    SumJob<FR> j;
+    SumJob<M> j;
     d.lanes = d.groups ? pick_lanes(d.groups, d.mode == SUM_BITS ? std::max(1u, d.count / 2) : d.count) : 1;
     j.in = in; j.out = out; j.d = d;
-    j.nblocks = blocks_for(d.groups, d.lanes);
     return j;
   };
-  // G1 launches that leave at least half of the SIMDs empty run on lane pairs (K2, above): half the latency per
-  // addition for twice the lanes.
+  // Which worker kind a launch runs on; sum_launch counts its workgroups.  G1 launches that leave at least half of the
+  // SIMDs empty run on lane pairs (K2, above): half the latency per addition for twice the lanes.
   // force: 0 = by the rules below, 1 = lane pairs, 2 = one lane per point (the first stage of a two-stage sum chooses)
-  auto launch_sums = [&](SumJobs<FR> js, int force = 0) -> bool {
-    const u32 total = js.j[0].nblocks + js.j[1].nblocks + js.j[2].nblocks;
-    if (!total) return true;
+  auto launch_sums = [&](SumJobs<M> js, int force = 0) -> bool {
     if constexpr (std::is_same<FR, FpOps>::value) {
       constexpr double K2_SUM_FILL = 4.0;   // wavefronts per SIMD the lane-pair launch may reach
-      // [r6] a handful of long sums (the bit sums and the total of ONE big bucket set): one workgroup of up to eight
-      // wavefronts per output (msm_sum_k2_wide_kernel)
+      // [r6] a handful of long sums (the bit sums and the total of ONE big bucket set): one workgroup of several
+      // wavefronts per output
       u32 groups_all = 0, max_sel = 0;
       for (int q = 0; q < 3; q++)
-        if (js.j[q].nblocks) {
+        if (js.j[q].d.groups) {
           groups_all += js.j[q].d.groups;
           max_sel = std::max(max_sel, js.j[q].d.mode == SUM_BITS ? js.j[q].d.count / 2 : js.j[q].d.count / js.j[q].d.splits);
         }
       if (force == 0 && max_sel >= 128 && groups_all <= 2u * (u32)c.num_cus) {
         // (never more than four wavefronts: a CU has four SIMDs, and the wavefronts of a workgroup that share one take turns -
         // eight were 198 us for 2 + 5 + 3 levels, profiles/r6_call32_timeline.txt)
-        u32 nw = 2;
-        while (nw < 4 && nw * 64 < max_sel) nw <<= 1;
-        for (int q = 0; q < 3; q++)
-          if (js.j[q].nblocks) js.j[q].nblocks = js.j[q].d.groups;
-        hipLaunchKernelGGL(msm_sum_k2_wide_kernel<FR>, dim3(js.j[0].nblocks + js.j[1].nblocks + js.j[2].nblocks), dim3(64 * nw), 0, st, js);
-        return hipGetLastError() == hipSuccess;
+        const bool four = 2 * 64 < max_sel;
+        for (int q = 0; q < 3; q++) js.j[q].d.lanes = (four ? 4 : 2) * K2Worker::PER_WAVE;
+        return four ? sum_launch<K2Worker, 4>(js, st) : sum_launch<K2Worker, 2>(js, st);
       }
-      if (force != 2 && (force == 1 || (double)total * 2 <= K2_SUM_FILL * (double)c.num_cus * 4)) {   // blocks are single wavefronts
-        for (int q = 0; q < 3; q++) {
-          SumJob<FR> &j = js.j[q];
-          if (!j.nblocks) continue;
-          if (j.d.lanes > 32) j.d.lanes = 32;                  // a wavefront carries 32 lane pairs
-          j.nblocks = (u32)(((u64)j.d.groups * j.d.lanes + 31) / 32);
-        }
-        hipLaunchKernelGGL(msm_sum_k2_kernel<FR>, dim3(js.j[0].nblocks + js.j[1].nblocks + js.j[2].nblocks), dim3(64), 0, st, js);
-        return hipGetLastError() == hipSuccess;
-      }
+      // (the one-lane launch would be single wavefronts)
+      if (force != 2 && (force == 1 || (double)sum_count<FullWK, NW>(js) * 2 <= K2_SUM_FILL * (double)c.num_cus * 4))
+        return sum_launch<K2Worker, 1>(js, st);
     }
     if constexpr (std::is_same<FR, Fp2K3Ops>::value) {
       // G2: the same idea on lane sextets (32 workers per 256-thread block) while the launch stays within one wavefront per SIMD
-      if (force != 2) {
-        SumJobs<FR> k6 = js;
-        u32 blocks6 = 0;
-        for (int q = 0; q < 3; q++) {
-          SumJob<FR> &j = k6.j[q];
-          if (!j.nblocks) continue;
-          if (j.d.lanes > 32) j.d.lanes = 32;
-          j.nblocks = (u32)(((u64)j.d.groups * j.d.lanes + 31) / 32);
-          blocks6 += j.nblocks;
-        }
-        constexpr double K6_SUM_FILL = 8.0;   // blocks per CU the launch may reach
-        if ((double)blocks6 <= K6_SUM_FILL * (double)c.num_cus) {
-          hipLaunchKernelGGL(msm_sum_k6_kernel<FR>, dim3(blocks6), dim3(256), 0, st, k6);
-          return hipGetLastError() == hipSuccess;
-        }
-      }
+      constexpr double K6_SUM_FILL = 8.0;   // blocks per CU the launch may reach
+      SumJobs<M> k6 = js;
+      if (force != 2 && (double)sum_count<K6Worker, 4>(k6) <= K6_SUM_FILL * (double)c.num_cus) return sum_launch<K6Worker, 4>(k6, st);
     }
-    hipLaunchKernelGGL(msm_sum_kernel<FR>, dim3(total), dim3(sum_block_threads<FR>()), 0, st, js);
-    return hipGetLastError() == hipSuccess;
+    return sum_launch<FullWK, NW>(js, st);
   };
   {
     const u32 cb = p.c - 1;   // bits of a bucket index
     SumDesc dr, dc;
     dr.mode = SUM_STRIDED; dr.groups = p.W * H; dr.count = Lw; dr.inner = H; dr.stride = 1; dr.istride = Lw; dr.group_shift = cb;
     dc = dr; dc.groups = p.W * Lw; dc.count = H; dc.inner = Lw; dc.stride = Lw; dc.istride = 1;
-    SumJobs<FR> js;
-    js.j[0] = make_job(pts, rows, dr); js.j[1] = make_job(pts, cols, dc); js.j[2] = js.j[1]; js.j[2].nblocks = 0;
+    SumJobs<M> js;
+    js.j[0] = make_job(pts, rows, dr); js.j[1] = make_job(pts, cols, dc); js.j[2] = js.j[1]; js.j[2].d.groups = 0;
     // [r6] G1, bucket sets of 2^17 ... 2^21 points (16 windows of 2^15, or the 2^19 buckets of a 20-bit window table): the launch
     // above gives every output 16-32 lane pairs - 8-16 serial additions, then a 4-5 level tree in which half, a quarter, ...
     // of the lanes work: 12-13 levels at four wavefronts per SIMD of which 61 % is useful work (0.50 ms for the 2^20 additions
@@ -1575,22 +1399,20 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
       SumDesc r1 = dr, c1 = dc;
       r1.splits = Sr; r1.groups = dr.groups * Sr; r1.lanes = 1;
       c1.splits = Sc; c1.groups = dc.groups * Sc; c1.lanes = 1;
-      SumJobs<FR> s1;
-      // (blocks of the one-lane / lane-triple kernel: 64 workers, 84 for lane triples that each sum alone)
-      const u32 wpb1 = (G2 && one_lane) ? 4 * default_per_wave<FR>() : PW;
-      s1.j[0].in = pts; s1.j[0].out = Sr > 1 ? part_r : rows; s1.j[0].d = r1; s1.j[0].nblocks = (r1.groups + wpb1 - 1) / wpb1;
-      s1.j[1].in = pts; s1.j[1].out = Sc > 1 ? part_c : cols; s1.j[1].d = c1; s1.j[1].nblocks = (c1.groups + wpb1 - 1) / wpb1;
-      s1.j[2] = s1.j[1]; s1.j[2].nblocks = 0;
+      SumJobs<M> s1;
+      s1.j[0].in = pts; s1.j[0].out = Sr > 1 ? part_r : rows; s1.j[0].d = r1;
+      s1.j[1].in = pts; s1.j[1].out = Sc > 1 ? part_c : cols; s1.j[1].d = c1;
+      s1.j[2] = s1.j[1]; s1.j[2].d.groups = 0;
       if (!launch_sums(s1, one_lane ? 2 : 1)) return BH_ERR_HIP;
       SumDesc r2, c2;
       r2.mode = SUM_STRIDED; r2.groups = dr.groups; r2.count = Sr; r2.inner = dr.groups; r2.stride = 1; r2.istride = Sr; r2.group_shift = 0;
       c2 = r2; c2.groups = dc.groups; c2.count = Sc; c2.inner = dc.groups; c2.istride = Sc;
-      SumJobs<FR> s2;
-      s2.j[0] = make_job(part_r, rows, r2); if (Sr <= 1) s2.j[0].nblocks = 0;
-      s2.j[1] = make_job(part_c, cols, c2); if (Sc <= 1) s2.j[1].nblocks = 0;
-      s2.j[2] = s2.j[1]; s2.j[2].nblocks = 0;
+      SumJobs<M> s2;
+      s2.j[0] = make_job(part_r, rows, r2); if (Sr <= 1) s2.j[0].d.groups = 0;
+      s2.j[1] = make_job(part_c, cols, c2); if (Sc <= 1) s2.j[1].d.groups = 0;
+      s2.j[2] = s2.j[1]; s2.j[2].d.groups = 0;
       if (!launch_sums(s2, 1)) return BH_ERR_HIP;
-      js.j[0].nblocks = js.j[1].nblocks = 0;   // (done)
+      js.j[0].d.groups = js.j[1].d.groups = 0;   // (done)
     }
     if (G2 && FR::LANES == 1) {
       // single-lane G2 (one resident wavefront per SIMD, so sharing a SIMD doubles every step): the two jobs share
@@ -1607,8 +1429,8 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
           const double cost = steps * std::max(1.0, waves / simds);
           if (cost < best) { best = cost; best_r = gr; best_c = gc; }
         }
-      js.j[0].d.lanes = best_r; js.j[0].nblocks = blocks_for(dr.groups, best_r);
-      js.j[1].d.lanes = best_c; js.j[1].nblocks = blocks_for(dc.groups, best_c);
+      js.j[0].d.lanes = best_r;
+      js.j[1].d.lanes = best_c;
     }
     if (!launch_sums(js)) return BH_ERR_HIP;
     // sum_idx (idx+1) B[idx] = sum_p 2^p U[p] + T, idx = hi*2^l + lo:

@@ -1,9 +1,10 @@
 // libbellman_hip_test.so: ONE group operation per worker on raw projective operands the caller chooses, raw results back
 // (bh_test_group_ops_dev / _host of include/bellman_hip_test.h; tests/test_gpu_group_law.py, tests/test_group_model_cpu.py).
-// Every operation goes through the functions the kernels call (xyzz_add / xyzz_madd / xyzz_dbl of ec.cuh, k2_add / k6_add,
-// group_reduce_points / k2_group_reduce / k6_group_reduce and long_block_sum of msm_ec.cuh) with the kernels' own worker
-// and lane mapping; nothing is canonicalised on the way out.  The one-lane forms compile for the host too: the same
-// `apply` runs in the kernel and in the host loop, and the host trees add in the order of the shuffle trees.
+// Every operation goes through the functions the kernels call (xyzz_add / xyzz_madd / xyzz_dbl of ec.cuh, half_add,
+// group_reduce_points / half_group_reduce and long_block_sum of msm_ec.cuh) through the kernels' own worker policies
+// (XyzzWorker<F>, HalfWorker<P>); nothing is canonicalised on the way out.  The one-lane forms compile for the host too: the
+// same `apply` runs in the kernel and in the host loop, and the host trees add in the order of the shuffle trees.
+// bh_test_sum_jobs_dev runs msm_sum_kernel itself (tests/test_gpu_sum_jobs.py).
 #include <string.h>
 
 #include <utility>
@@ -68,126 +69,67 @@ BH_HD u32 apply(XYZZ<F> &res, const XYZZ<F> &pa, const XYZZ<F> &pb, const Affine
   return f | (xyzz_is_identity(res) ? 1u : 0u);
 }
 
-template <class F, int OP>
-__global__ __launch_bounds__(128) void group_op_kernel(XYZZ<typename F::Mem> *r, u32 *flags, const XYZZ<typename F::Mem> *a,
+// the same for a half-point worker (forms 1 and 5), which has the three operations its kernels use
+template <class P, int OP>
+__device__ __forceinline__ u32 apply_half(HalfPt &res, const HalfPt &pa, const HalfPt &pb) {
+  res = pa;
+  if constexpr (OP == OP_ADD) half_add<P>(res, pa, pb);
+  else if constexpr (OP == OP_ADD_ALIAS) half_add<P>(res, res, pb);
+  return half_is_identity<P>(res) ? 1u : 0u;
+}
+
+// false for lanes that carry no worker; `gid` = the worker's index over the whole launch
+template <class WK>
+__device__ __forceinline__ bool worker_global(u32 per_wave, u32 &gid) {
+  u32 in_block;
+  const bool live = WK::index(in_block, per_wave);
+  gid = blockIdx.x * (blockDim.x >> 6) * per_wave + in_block;
+  return live;
+}
+template <class WK, int OP>
+__global__ __launch_bounds__(128) void group_op_kernel(XYZZ<typename WK::Mem> *r, u32 *flags, const XYZZ<typename WK::Mem> *a,
                                                        const void *b, u32 n) {
-  typedef typename F::Mem M;
-  u32 in_block, i;
-  if (!worker_index<F>(default_per_wave<F>(), in_block, i) || i >= n) return;
-  XYZZ<F> pa, pb, res;
-  Affine<F> q;
-  xyzz_set_identity(pa);
-  xyzz_set_identity(pb);
-  F::zero(q.x);
-  F::zero(q.y);
-  if (op_reads_a(OP)) load_xyzz<F>(pa, a + i);
-  if (op_b_is_xyzz(OP)) load_xyzz<F>(pb, (const XYZZ<M> *)b + i);
-  if (op_b_is_affine(OP)) load_affine<F>(q, (const Affine<M> *)b + i);
-  const u32 f = apply<F, OP>(res, pa, pb, q, op_b_is_affine(OP) ? (const u32 *)((const Affine<M> *)b + i) : nullptr);
-  store_xyzz<F>(r + i, res);
-  flags[(size_t)i * F::LANES + worker_role<F>()] = f;
+  typedef typename WK::Mem M;
+  u32 i;
+  if (!worker_global<WK>(WK::SOLO_PER_WAVE, i) || i >= n) return;
+  typename WK::Pt pa, pb, res;
+  WK::identity(pa);
+  WK::identity(pb);
+  if (op_reads_a(OP)) WK::load(pa, a + i);
+  if (op_b_is_xyzz(OP)) WK::load(pb, (const XYZZ<M> *)b + i);
+  u32 f;
+  if constexpr (std::is_same<typename WK::Pt, HalfPt>::value) {
+    f = apply_half<typename WK::Half, OP>(res, pa, pb);
+  } else {
+    typedef typename WK::Ops F;
+    Affine<F> q;
+    F::zero(q.x);
+    F::zero(q.y);
+    if (op_b_is_affine(OP)) load_affine<F>(q, (const Affine<M> *)b + i);
+    f = apply<F, OP>(res, pa, pb, q, op_b_is_affine(OP) ? (const u32 *)((const Affine<M> *)b + i) : nullptr);
+  }
+  WK::store(r + i, res);
+  flags[(size_t)i * WK::LANES + WK::role()] = f;
 }
 // groups of G consecutive workers of one wavefront, as msm_sum_kernel folds them: r[g] = sum of a[g G .. g G + G)
-template <class F>
-__global__ __launch_bounds__(64) void group_tree_kernel(XYZZ<typename F::Mem> *r, u32 *flags, const XYZZ<typename F::Mem> *a, u32 G,
+template <class WK>
+__global__ __launch_bounds__(64) void group_tree_kernel(XYZZ<typename WK::Mem> *r, u32 *flags, const XYZZ<typename WK::Mem> *a, u32 G,
                                                         u32 n_groups) {
-  u32 t, gid;
-  const bool live = worker_index<F>(tree_per_wave<F>(), t, gid);
+  u32 gid;
+  const bool live = worker_global<WK>(WK::PER_WAVE, gid);
   const u32 g = gid / G, sub = gid & (G - 1);
-  XYZZ<F> acc;
-  xyzz_set_identity(acc);
-  if (live && g < n_groups) load_xyzz<F>(acc, a + gid);
-  group_reduce_points<F>(acc, G, sub);   // every lane of the wavefront takes part in the shuffles
-  const bool id = xyzz_is_identity(acc);
+  typename WK::Pt acc;
+  WK::identity(acc);
+  if (live && g < n_groups) WK::load(acc, a + gid);
+  WK::tree(acc, G, sub);   // every lane of the wavefront takes part in the shuffles
+  const bool id = WK::is_identity(acc);
   if (live && sub == 0 && g < n_groups) {
-    store_xyzz<F>(r + g, acc);
-    flags[(size_t)g * F::LANES + worker_role<F>()] = id ? 1u : 0u;
-  }
-}
-
-// ---- form 1: G1 on lane pairs ----------------------------------------------------------------------------------------
-template <int OP>
-__global__ __launch_bounds__(128) void k2_op_kernel(XYZZ<FpOps> *r, u32 *flags, const XYZZ<FpOps> *a, const XYZZ<FpOps> *b, u32 n) {
-  const u32 i = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  if (i >= n) return;
-  HalfPt ha, hb, hr;
-  k2_load(ha, a + i);
-  if (OP == OP_LOAD_STORE) {
-    hr = ha;
-  } else {
-    k2_load(hb, b + i);
-    if (OP == OP_ADD) {
-      k2_add(hr, ha, hb);
-    } else {
-      hr = ha;
-      k2_add(hr, hr, hb);
-    }
-  }
-  const bool id = k2_is_identity(hr);
-  k2_store(r + i, hr);
-  flags[(size_t)i * 2 + k2_role()] = id ? 1u : 0u;
-}
-__global__ __launch_bounds__(64) void k2_tree_kernel(XYZZ<FpOps> *r, u32 *flags, const XYZZ<FpOps> *a, u32 G, u32 n_groups) {
-  const u32 gid = blockIdx.x * 32 + (threadIdx.x >> 1);   // as msm_sum_k2_kernel
-  const u32 g = gid / G, sub = gid & (G - 1);
-  HalfPt acc;
-  k2_set_identity(acc);
-  if (g < n_groups) k2_load(acc, a + gid);
-  k2_group_reduce(acc, G, sub);
-  const bool id = k2_is_identity(acc);
-  if (sub == 0 && g < n_groups) {
-    k2_store(r + g, acc);
-    flags[(size_t)g * 2 + k2_role()] = id ? 1u : 0u;
-  }
-}
-
-// ---- form 5: G2 on lane sextets --------------------------------------------------------------------------------------
-template <int OP>
-__global__ __launch_bounds__(256) void k6_op_kernel(XYZZ<Fp2Ops> *r, u32 *flags, const XYZZ<Fp2Ops> *a, const XYZZ<Fp2Ops> *b, u32 n) {
-  const u32 t_in_wave = (k3_lane() * 43u) >> 8, wave = threadIdx.x >> 6;   // as msm_sum_k6_kernel
-  const u32 i = (blockIdx.x * (blockDim.x >> 6) + wave) * K6_PER_WAVE + t_in_wave;
-  if (t_in_wave >= K6_PER_WAVE || i >= n) return;
-  HalfPt ha, hb, hr;
-  k6_load(ha, a + i);
-  if (OP == OP_LOAD_STORE) {
-    hr = ha;
-  } else {
-    k6_load(hb, b + i);
-    if (OP == OP_ADD) {
-      k6_add(hr, ha, hb);
-    } else {
-      hr = ha;
-      k6_add(hr, hr, hb);
-    }
-  }
-  const bool id = k6_is_identity(hr);
-  k6_store(r + i, hr);
-  flags[(size_t)i * 6 + k6_lane_in_worker()] = id ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k6_tree_kernel(XYZZ<Fp2Ops> *r, u32 *flags, const XYZZ<Fp2Ops> *a, u32 G, u32 n_groups) {
-  const u32 t_in_wave = (k3_lane() * 43u) >> 8, wave = threadIdx.x >> 6;
-  const bool live = t_in_wave < K6_PER_WAVE;
-  const u32 gid = (blockIdx.x * (blockDim.x >> 6) + wave) * K6_PER_WAVE + t_in_wave;
-  const u32 g = gid / G, sub = gid & (G - 1);
-  HalfPt acc;
-  fe_zero(acc.u);
-  fe_zero(acc.v);
-  if (live && g < n_groups) k6_load(acc, a + gid);
-  k6_group_reduce(acc, G, sub);
-  const bool id = k6_is_identity(acc);
-  if (live && sub == 0 && g < n_groups) {
-    k6_store(r + g, acc);
-    flags[(size_t)g * 6 + k6_lane_in_worker()] = id ? 1u : 0u;
+    WK::store(r + g, acc);
+    flags[(size_t)g * WK::LANES + WK::role()] = id ? 1u : 0u;
   }
 }
 
 // ---- long_block_sum: one workgroup of LONG_THREADS per case, long_workers<WK>() records each ---------------------------
-template <class WK>
-__device__ __forceinline__ bool wk_identity_flag(const typename WK::Pt &p) {
-  if constexpr (WK::LANES == 6) return k6_is_identity(p);
-  else if constexpr (std::is_same<typename WK::Pt, HalfPt>::value) return k2_is_identity(p);
-  else return xyzz_is_identity(p);
-}
 template <class WK>
 __global__ __launch_bounds__(LONG_THREADS) void block_sum_kernel(XYZZ<typename WK::Mem> *r, u32 *flags, const XYZZ<typename WK::Mem> *a) {
   typedef typename WK::Pt Pt;
@@ -199,7 +141,7 @@ __global__ __launch_bounds__(LONG_THREADS) void block_sum_kernel(XYZZ<typename W
   if (live) WK::load(acc, a + (size_t)blockIdx.x * long_workers<WK>() + wid);
   long_block_sum<WK>(acc, live, wid, wave_part);
   if (live && wid == 0) {
-    const bool id = wk_identity_flag<WK>(acc);
+    const bool id = WK::is_identity(acc);
     WK::store(r + blockIdx.x, acc);
     flags[(size_t)blockIdx.x * WK::LANES + WK::role()] = id ? 1u : 0u;
   }
@@ -211,14 +153,16 @@ struct FormInfo {
   u32 lanes;        // flag words per worker
   u32 per_wave;     // workers of a wavefront in the trees
 };
+template <class WK>
+static FormInfo info_of() { return {sizeof(XYZZ<typename WK::Mem>) == sizeof(XYZZ<FpOps>) ? 1 : 2, WK::LANES, WK::PER_WAVE}; }
 static bool form_info(int form, FormInfo &fi) {
   switch (form) {
-    case 0: fi = {1, 1, tree_per_wave<FpOps>()}; return true;
-    case 1: fi = {1, 2, K2Worker::PER_WAVE}; return true;
-    case 2: fi = {2, 1, tree_per_wave<Fp2Ops>()}; return true;
-    case 3: fi = {2, 3, tree_per_wave<Fp2K3Ops>()}; return true;
-    case 4: fi = {2, 2, tree_per_wave<Fp2PairOps>()}; return true;
-    case 5: fi = {2, 6, K6_PER_WAVE}; return true;
+    case 0: fi = info_of<XyzzWorker<FpOps>>(); return true;
+    case 1: fi = info_of<K2Worker>(); return true;
+    case 2: fi = info_of<XyzzWorker<Fp2Ops>>(); return true;
+    case 3: fi = info_of<XyzzWorker<Fp2K3Ops>>(); return true;
+    case 4: fi = info_of<XyzzWorker<Fp2PairOps>>(); return true;
+    case 5: fi = info_of<K6Worker>(); return true;
     default: return false;
   }
 }
@@ -238,60 +182,63 @@ static bool args_ok(int form, int op, u32 G, const void *r, const void *flags, c
   return true;
 }
 
-template <class F, int... OP>
+template <class WK, int... OP>
 static auto op_entry(int op, std::integer_sequence<int, OP...>) {
-  typedef void (*fn)(XYZZ<typename F::Mem> *, u32 *, const XYZZ<typename F::Mem> *, const void *, u32);
-  static const fn t[] = {group_op_kernel<F, OP>...};
+  typedef void (*fn)(XYZZ<typename WK::Mem> *, u32 *, const XYZZ<typename WK::Mem> *, const void *, u32);
+  static const fn t[] = {group_op_kernel<WK, OP>...};
   return t[op];
 }
-template <class F, class WK>
-static int run_generic(hipStream_t st, int op, u32 G, void *r, u32 *flags, const void *a, const void *b, size_t n) {
-  typedef XYZZ<typename F::Mem> Rec;
+template <class WK>
+static int run_dev(hipStream_t st, int op, u32 G, void *r, u32 *flags, const void *a, const void *b, size_t n) {
+  typedef XYZZ<typename WK::Mem> Rec;
   if (op == OP_TREE) {
-    const u32 pw = tree_per_wave<F>();
-    hipLaunchKernelGGL(group_tree_kernel<F>, dim3((u32)((n * G + pw - 1) / pw)), dim3(64), 0, st, (Rec *)r, flags, (const Rec *)a, G, (u32)n);
+    const u32 pw = WK::PER_WAVE;
+    hipLaunchKernelGGL(group_tree_kernel<WK>, dim3((u32)((n * G + pw - 1) / pw)), dim3(64), 0, st, (Rec *)r, flags, (const Rec *)a, G, (u32)n);
   } else if (op == OP_BLOCK_SUM) {
     hipLaunchKernelGGL(block_sum_kernel<WK>, dim3((u32)n), dim3(LONG_THREADS), 0, st, (Rec *)r, flags, (const Rec *)a);
   } else {
-    const u32 wpb = workers_per_block<F>(128, default_per_wave<F>());
-    hipLaunchKernelGGL(op_entry<F>(op, std::make_integer_sequence<int, OP_LOAD_STORE>()), dim3((u32)((n + wpb - 1) / wpb)), dim3(128), 0,
+    const u32 wpb = (128 / 64) * WK::SOLO_PER_WAVE;
+    hipLaunchKernelGGL(op_entry<WK>(op, std::make_integer_sequence<int, OP_TREE>()), dim3((u32)((n + wpb - 1) / wpb)), dim3(128), 0,
                        st, (Rec *)r, flags, (const Rec *)a, b, (u32)n);
   }
   BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
-static int run_k2(hipStream_t st, int op, u32 G, void *r, u32 *flags, const void *a, const void *b, size_t n) {
-  typedef XYZZ<FpOps> Rec;
-  const dim3 grid((u32)((2 * n + 127) / 128)), block(128);
-  if (op == OP_TREE)
-    hipLaunchKernelGGL(k2_tree_kernel, dim3((u32)((n * G + 31) / 32)), dim3(64), 0, st, (Rec *)r, flags, (const Rec *)a, G, (u32)n);
-  else if (op == OP_BLOCK_SUM)
-    hipLaunchKernelGGL(block_sum_kernel<K2Worker>, dim3((u32)n), dim3(LONG_THREADS), 0, st, (Rec *)r, flags, (const Rec *)a);
-  else if (op == OP_ADD)
-    hipLaunchKernelGGL(k2_op_kernel<OP_ADD>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  else if (op == OP_ADD_ALIAS)
-    hipLaunchKernelGGL(k2_op_kernel<OP_ADD_ALIAS>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  else
-    hipLaunchKernelGGL(k2_op_kernel<OP_LOAD_STORE>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  BH_HIP_CHECK(hipGetLastError());
-  return BH_OK;
+
+// ---- msm_sum_kernel on its own: up to three jobs in one launch, counted and launched by sum_launch ------------------------
+enum { SJ_MODE, SJ_GROUPS, SJ_COUNT, SJ_INNER, SJ_STRIDE, SJ_ISTRIDE, SJ_GROUP_SHIFT, SJ_SPLITS, SJ_LANES, SJ_IN_OFF, SJ_OUT_OFF, SJ_WORDS };
+// every record a job reads lies inside [0, n_in), every output inside [0, n_out)
+static bool sum_job_ok(const u32 *w, u32 max_lanes, size_t n_in, size_t n_out) {
+  const u64 groups = w[SJ_GROUPS], count = w[SJ_COUNT], inner = w[SJ_INNER], splits = w[SJ_SPLITS], lanes = w[SJ_LANES];
+  if (!groups || !count || !inner || !splits || count % splits || groups % splits || w[SJ_GROUP_SHIFT] > 24) return false;
+  if (!is_pow2((u32)lanes) || lanes > max_lanes || w[SJ_OUT_OFF] + groups > n_out) return false;
+  const u64 outer_max = (groups / splits - 1) / inner;
+  u64 last;
+  if (w[SJ_MODE] == SUM_STRIDED) last = (inner - 1) * w[SJ_ISTRIDE] + (count - 1) * w[SJ_STRIDE];
+  else if (w[SJ_MODE] == SUM_BITS && is_pow2((u32)count) && splits == 1 && (1ull << inner) <= count) last = count - 1;
+  else return false;
+  return w[SJ_IN_OFF] + (outer_max << w[SJ_GROUP_SHIFT]) + last < n_in;
 }
-static int run_k6(hipStream_t st, int op, u32 G, void *r, u32 *flags, const void *a, const void *b, size_t n) {
-  typedef XYZZ<Fp2Ops> Rec;
-  const u32 wpb = (256 / 64) * K6_PER_WAVE;
-  const dim3 grid((u32)((n + wpb - 1) / wpb)), block(256);
-  if (op == OP_TREE)
-    hipLaunchKernelGGL(k6_tree_kernel, dim3((u32)((n * G + wpb - 1) / wpb)), block, 0, st, (Rec *)r, flags, (const Rec *)a, G, (u32)n);
-  else if (op == OP_BLOCK_SUM)
-    hipLaunchKernelGGL(block_sum_kernel<K6Worker>, dim3((u32)n), dim3(LONG_THREADS), 0, st, (Rec *)r, flags, (const Rec *)a);
-  else if (op == OP_ADD)
-    hipLaunchKernelGGL(k6_op_kernel<OP_ADD>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  else if (op == OP_ADD_ALIAS)
-    hipLaunchKernelGGL(k6_op_kernel<OP_ADD_ALIAS>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  else
-    hipLaunchKernelGGL(k6_op_kernel<OP_LOAD_STORE>, grid, block, 0, st, (Rec *)r, flags, (const Rec *)a, (const Rec *)b, (u32)n);
-  BH_HIP_CHECK(hipGetLastError());
-  return BH_OK;
+template <class WK, u32 NWAVES>
+static int run_sum_jobs(hipStream_t st, const void *in, size_t n_in, void *out, size_t n_out, const u32 *words, size_t n_jobs) {
+  typedef typename WK::Mem M;
+  SumJobs<M> js{};
+  for (size_t q = 0; q < 3; q++) {
+    SumJob<M> &j = js.j[q];
+    j.in = (const XYZZ<M> *)in;
+    j.out = (XYZZ<M> *)out;
+    j.d.groups = 0;
+    j.d.lanes = 1;
+    if (q >= n_jobs) continue;
+    const u32 *w = words + q * SJ_WORDS;
+    if (!sum_job_ok(w, NWAVES * WK::PER_WAVE, n_in, n_out)) return BH_ERR_INVALID_ARG;
+    j.in += w[SJ_IN_OFF];
+    j.out += w[SJ_OUT_OFF];
+    j.d.mode = w[SJ_MODE]; j.d.groups = w[SJ_GROUPS]; j.d.count = w[SJ_COUNT]; j.d.inner = w[SJ_INNER];
+    j.d.stride = w[SJ_STRIDE]; j.d.istride = w[SJ_ISTRIDE]; j.d.group_shift = w[SJ_GROUP_SHIFT];
+    j.d.splits = w[SJ_SPLITS]; j.d.lanes = w[SJ_LANES];
+  }
+  return sum_launch<WK, NWAVES>(js, st) ? BH_OK : BH_ERR_HIP;
 }
 
 // ---- the host twins (forms 0 and 2) ------------------------------------------------------------------------------------
@@ -389,13 +336,32 @@ int bh_test_group_ops_dev(bh_ctx *ctx, int form, int op, unsigned G, void *r_dev
   hipStream_t st = ctx->c.stream;
   int rc;
   switch (form) {
-    case 0: rc = run_generic<FpOps, XyzzWorker<FpOps>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
-    case 1: rc = run_k2(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
-    case 2: rc = run_generic<Fp2Ops, XyzzWorker<Fp2Ops>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
-    case 3: rc = run_generic<Fp2K3Ops, XyzzWorker<Fp2K3Ops>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
-    case 4: rc = run_generic<Fp2PairOps, XyzzWorker<Fp2PairOps>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
-    default: rc = run_k6(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    case 0: rc = run_dev<XyzzWorker<FpOps>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    case 1: rc = run_dev<K2Worker>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    case 2: rc = run_dev<XyzzWorker<Fp2Ops>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    case 3: rc = run_dev<XyzzWorker<Fp2K3Ops>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    case 4: rc = run_dev<XyzzWorker<Fp2PairOps>>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
+    default: rc = run_dev<K6Worker>(st, op, G, r_dev, flags_dev, a_dev, b_dev, n); break;
   }
+  if (rc == BH_OK) BH_HIP_CHECK(hipStreamSynchronize(st));
+  return rc;
+}
+int bh_test_sum_jobs_dev(bh_ctx *ctx, int form, unsigned waves, const void *in_dev, size_t n_in, void *out_dev, size_t n_out,
+                         const uint32_t *jobs, size_t n_jobs) {
+  if (!ctx || !in_dev || !out_dev || !jobs || !n_jobs || n_jobs > 3 || n_in > (1u << 24) || n_out > (1u << 24)) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = ctx->c.stream;
+  int rc = BH_ERR_INVALID_ARG;
+#define BH_SUM_FORM(FORM, WAVES, WK) \
+  if (form == FORM && waves == WAVES) rc = run_sum_jobs<WK, WAVES>(st, in_dev, n_in, out_dev, n_out, jobs, n_jobs)
+  BH_SUM_FORM(0, 1, XyzzWorker<FpOps>);
+  BH_SUM_FORM(1, 1, K2Worker);
+  BH_SUM_FORM(1, 2, K2Worker);
+  BH_SUM_FORM(1, 4, K2Worker);
+  BH_SUM_FORM(2, 1, XyzzWorker<Fp2Ops>);
+  BH_SUM_FORM(3, 4, XyzzWorker<Fp2K3Ops>);
+  BH_SUM_FORM(5, 4, K6Worker);
+#undef BH_SUM_FORM
   if (rc == BH_OK) BH_HIP_CHECK(hipStreamSynchronize(st));
   return rc;
 }

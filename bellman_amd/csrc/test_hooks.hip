@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64) void k6_add_kernel(XYZZ<Fp2Ops> *r, const Affin
   const u32 t = (k3_lane() * 43u) >> 8;
   const u32 i = blockIdx.x * K6_PER_WAVE + t;
   if (t >= K6_PER_WAVE || i >= n) return;
-  const bool y = k6_side();
+  const bool y = SextetHalf::side();
   auto from_affine = [&](HalfPt &h, const Affine<Fp2Ops> *p) {
     Fp2K3Ops::load(h.u, y ? &p->y : &p->x);
     fp_t ox, oy;
@@ -98,8 +98,8 @@ __global__ __launch_bounds__(64) void k6_add_kernel(XYZZ<Fp2Ops> *r, const Affin
   HalfPt pa, pb;
   from_affine(pa, a + i);
   from_affine(pb, b + i);
-  k6_add(pa, pa, pb);
-  k6_store(&r[i], pa);
+  half_add<SextetHalf>(pa, pa, pb);
+  SextetHalf::store(&r[i], pa);
 }
 static int test_g2_k6(Context &c, void *out_add, const void *a_dev, const void *b_dev, u64 n) {
   typedef XYZZ<Fp2Ops> Pt;

@@ -130,12 +130,12 @@ int bh_test_field_ops_host(int form, int op, void *r, uint32_t *flags, const voi
  * tests/test_gpu_group_law.py, tests/test_group_model_cpu.py).  Records are XYZZ<Mem> (X, Y, ZZ, ZZZ: 4 x 48 bytes in G1,
  * 4 x 96 in G2, every coordinate a Montgomery residue in [0, 2p)) and canonical affine records (x, y; all zero = identity).
  *   form 0  G1, one lane (XYZZ<FpOps>)            device and host
- *   form 1  G1, lane pairs (K2 HalfPt)            device
+ *   form 1  G1, lane pairs (HalfWorker<PairHalf>)    device
  *   form 2  G2, one lane (Fp2Ops)                 device and host
  *   form 3  G2, lane triples (Fp2K3Ops)           device
  *   form 4  G2, lane pairs (Fp2PairOps)           device
- *   form 5  G2, lane sextets (K6 HalfPt)          device
- *   op  0 add            r = a + b: xyzz_add (forms 0, 2, 3, 4), k2_add (1), k6_add (5); b = XYZZ records
+ *   form 5  G2, lane sextets (HalfWorker<SextetHalf>) device
+ *   op  0 add            r = a + b: xyzz_add (forms 0, 2, 3, 4), half_add (1, 5); b = XYZZ records
  *       1 add_alias      the same with r aliasing a, as the merge kernels call it
  *       2 madd           r = a + b, b = AFFINE records: xyzz_madd; an identity b is skipped as the accumulation does
  *       3 madd_prefetch  the overload with a prefetch functor, which loads the first word of b's record
@@ -145,8 +145,8 @@ int bh_test_field_ops_host(int form, int op, void *r, uint32_t *flags, const voi
  *       7 to_affine      xyzz_to_affine(a) into X, Y of the result (ZZ = ZZZ = 0); forms 0 and 2 only: the lane bundles
  *                        have no inversion, and no kernel converts in those forms
  *       8 is_identity    xyzz_is_identity(a); r = a
- *       9 load_store     k2_load / k2_store, k6_load / k6_store round trip (forms 1 and 5 only)
- *      10 tree           r[g] = a[g G] + ... + a[g G + G - 1] by group_reduce_points / k2_group_reduce / k6_group_reduce over
+ *       9 load_store     PairHalf / SextetHalf load and store, round trip (forms 1 and 5 only)
+ *      10 tree           r[g] = a[g G] + ... + a[g G + G - 1] by group_reduce_points / half_group_reduce (WK::tree) over
  *                        G consecutive workers of a wavefront, G a power of two in [2, workers per wavefront]; n groups
  *      11 block_sum      r[c] = the sum of the 4 x (workers per wavefront) records of case c by long_block_sum at
  *                        LONG_THREADS, one workgroup per case; on the host G = the workers per wavefront to fold by
@@ -162,6 +162,16 @@ int bh_test_group_ops_dev(bh_ctx *ctx, int form, int op, unsigned G, void *r_dev
                           const void *b_dev, size_t n);
 /* the same `apply` compiled for the host (forms 0 and 2); trees and block sums add in the order of the shuffle trees */
 int bh_test_group_ops_host(int form, int op, unsigned G, void *r, uint32_t *flags, const void *a, const void *b, size_t n);
+/* msm_sum_kernel on its own: up to three reduction jobs in ONE launch, counted and launched by sum_launch as msm_enqueue
+ * does.  form = the worker kind (the forms above; 4 has no sum kernel), waves = wavefronts per workgroup:
+ *   (0, 1) one-lane G1   (1, 1) lane pairs   (1, 2), (1, 4) lane pairs, "wide"   (2, 1) one-lane G2 (LDS accumulators)
+ *   (3, 4) lane triples   (5, 4) lane sextets
+ * in_dev: n_in XYZZ records, out_dev: n_out.  A job is 11 words - mode (1 strided, 2 bits), groups, count, inner, stride,
+ * istride, group_shift, splits, lanes (a power of two <= waves x workers per wavefront in the trees), and the record
+ * offsets of its input and output - SumDesc of csrc/msm_types.hpp; a job that would read or write outside the buffers
+ * is refused.  out[out_off + g], g < groups, are the raw sums. */
+int bh_test_sum_jobs_dev(bh_ctx *ctx, int form, unsigned waves, const void *in_dev, size_t n_in, void *out_dev, size_t n_out,
+                         const uint32_t *jobs, size_t n_jobs);
 
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */

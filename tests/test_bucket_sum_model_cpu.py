@@ -1,4 +1,4 @@
-"""Index arithmetic of the bucket reduction (bellman_amd/csrc/msm_ec.cuh, section 5), restated over plain integers.
+"""Index arithmetic of the bucket reduction (bellman_amd/csrc/msm_ec.cuh, section 5c), restated over plain integers.
 
 The device computes  sum_d (d + 1) * B[d]  over 2^(c-1) buckets without a serial running sum: d = hi * 2^l + lo, row sums over
 lo, column sums over hi, then per-bit sums of those vectors and a plain total; the host finishes with
@@ -7,34 +7,13 @@ points (a point is an element of an abelian group; Z is one):
   * SumDesc::splits - the two-stage row / column sums: every output is cut into `splits` pieces of count / splits consecutive
     elements, one worker adds up a piece (out[group * splits + piece]), a second SUM_STRIDED job folds the pieces;
   * nth_with_bit    - SUM_BITS walks the j-th index with bit k set, j < count / 2, instead of striding over all indices.
-Everything is mirrored statement by statement from the kernels (k2_partial_sum / msm_sum_kernel), so a change there shows here."""
+The model itself (nth_with_bit / partial_sum / run_job, mirrored statement by statement from partial_sum<WK> and
+msm_sum_kernel<WK, NWAVES>) is tests/models/bucket_sum_model.py, shared with tests/test_gpu_sum_jobs.py, which runs the kernel."""
 import random
 
 import pytest
 
-
-def nth_with_bit(j, k):   # msm_ec.cuh nth_with_bit
-    return ((j >> k) << (k + 1)) | (1 << k) | (j & ((1 << k) - 1))
-
-
-def partial_sum(d, data, g, sub, G):
-    """what worker `sub` of the G workers of output g adds up (k2_partial_sum)"""
-    gg, ln = g // d["splits"], d["count"] // d["splits"]
-    k0 = (g % d["splits"]) * ln
-    outer, in_idx = gg // d["inner"], gg % d["inner"]
-    base = outer << d["group_shift"]
-    acc = 0
-    if d["mode"] == "strided":
-        for k in range(k0 + sub, k0 + ln, G):
-            acc += data[base + in_idx * d["istride"] + k * d["stride"]]
-    else:   # bits: in_idx = bit position
-        for j in range(sub, d["count"] >> 1, G):
-            acc += data[base + nth_with_bit(j, in_idx)]
-    return acc
-
-
-def run_job(d, data, G):
-    return [sum(partial_sum(d, data, g, sub, G) for sub in range(G)) for g in range(d["groups"])]
+from tests.models.bucket_sum_model import nth_with_bit, run_job
 
 
 @pytest.mark.parametrize("k", range(0, 11))

@@ -6,7 +6,7 @@ coordinates, P + P only ever bit-identical.  What the merges add is two partial 
 anywhere in [0, 2p), and whether they are the same point, opposite points or an identity is decided from is_zero of a
 lazily reduced difference - computed, in the lane-pair (K2) and lane-sextet (K6) forms, on one half of the lanes and carried
 to the other half by ballot / DPP / shuffle.  Here every operation runs ON ITS OWN through bh_test_group_ops_dev - xyzz_add,
-both overloads of xyzz_madd, xyzz_dbl, xyzz_dbl_affine, the conversions, k2_add, k6_add, the shuffle trees and
+both overloads of xyzz_madd, xyzz_dbl, xyzz_dbl_affine, the conversions, half_add on lane pairs and on lane sextets, the shuffle trees and
 long_block_sum, with the kernels' worker and lane mapping - over the tables of tests/group_model.py: every branch class
 with its own pair of scalings, interleaved within wavefronts and as whole wavefronts of one branch.  All checks are exact:
   * every returned coordinate < 2p; ZZ^3 = ZZZ^2; (X / ZZ, Y / ZZZ) equals the integer model's affine sum;
