@@ -1068,6 +1068,156 @@ static int points_check_t(const void *pts_dev, u64 n, u32 *status_dev, hipStream
   return BH_OK;
 }
 // ============================================================================================
+// host side of stage 4: the merge parameters of a plan, the queue bounds, and the two launch sequences
+// (msm_enqueue; csrc/test_bucket_hooks.hip runs the same functions on a stream of the caller's choice)
+// ============================================================================================
+// the half-point worker of the merge bundle FR: lane pairs in G1, lane sextets for G2 in lane triples; one-lane G2 has none
+template <class FR>
+struct MergeWorkers {
+  static constexpr bool G1_PAIRS = std::is_same<FR, FpOps>::value, G2_SEXTETS = std::is_same<FR, Fp2K3Ops>::value;
+  static constexpr bool PAIRS_POSSIBLE = G1_PAIRS || G2_SEXTETS;   // "pairs" below: the half-point worker of the group
+  typedef typename std::conditional<G1_PAIRS, K2Worker, typename std::conditional<G2_SEXTETS, K6Worker, XyzzWorker<FR>>::type>::type HalfWK;
+};
+struct MergeBounds {
+  u32 max_long, max_big, max_pieces;   // entries of long_runs, big_runs, piece_out
+};
+struct MergePlan {
+  u32 walk;            // the owner lane of a run folds at most this many following chunks itself
+  u32 run_lanes;       // G workers per queued medium run
+  bool runs_on_pairs;  // ... on the group's half-point worker
+  u32 big_chunks;      // runs of more following chunks than this are cut into pieces
+  u32 piece;           // partials per piece
+  u32 max_long, max_big, max_pieces;
+};
+// Upper bounds of what msm_merge_chunks_kernel can queue over nslots chunks (all windows).  A queued run owns the chunks
+// [lane, last) alone - its last chunk may be the first of the next run - so a run of more than `walk` following chunks
+// takes at least walk + 1 chunks out of nslots, a big one big_chunks + 1.
+// Pieces: sum of ceil(L_r / piece) over the big runs: consecutive runs share one chunk, so sum L_r <= nslots + max_big
+inline MergeBounds merge_bounds(u64 nslots, u32 walk, u32 big_chunks, u32 piece) {
+  MergeBounds b;
+  b.max_long = (u32)(nslots / (walk + 1) + 1);
+  b.max_big = (u32)(nslots / (big_chunks + 1) + 1);
+  b.max_pieces = (u32)((nslots + b.max_big) / piece + b.max_big + 1);
+  return b;
+}
+template <class FR>
+static MergePlan merge_plan(const MsmPlan &p, int num_cus) {
+  typedef typename MergeWorkers<FR>::HalfWK HalfWK;
+  constexpr bool G2_SEXTETS = MergeWorkers<FR>::G2_SEXTETS, PAIRS_POSSIBLE = MergeWorkers<FR>::PAIRS_POSSIBLE;
+  MergePlan mp;
+  // the owner lane of a run folds at most `walk` following chunks itself; longer runs are queued for
+  // msm_merge_runs_kernel (G workers per run), the longest of those for the workgroup kernel
+  mp.walk = 4;
+  // G workers per queued run: 8-16 chunk runs become 1-2 serial additions + 3 tree levels; when the AVERAGE run is
+  // much longer than that (window tables over tiny vectors: 32 n entries in 128 buckets, chunks of 8) more workers
+  // shorten the chain as long as the launch still fits the chip
+  // [r6] G1: the same on lane PAIRS (K2: half the latency of an addition for twice the lanes) when that is cheaper by
+  // the same model - levels x latency of a level x how far the launch overfills the chip
+  // [r6] G2 in lane triples: the same on lane SEXTETS (K6Worker)
+  constexpr double LEVEL_US = G2_SEXTETS ? 37.0 : 19.0, HALF_LEVEL_US = G2_SEXTETS ? 20.0 : 10.5;   // a tree level, by worker kind
+  u32 run_lanes = 8;
+  bool runs_on_pairs = false;
+  {
+    const double avg_chunks = (double)p.n / (double)p.nb / (double)p.chunk;   // per window: n sorted entries, nb buckets
+    double best_cost = 1e30;
+    auto sweep = [&](u32 per_wave, double level_us, bool pairs) {
+      for (u32 g = 8, lg = 3; g <= per_wave; g <<= 1, lg++) {
+        const double steps = std::ceil(std::max(1.0, avg_chunks) / g) + lg;
+        const double waves = (double)p.NB * g / (double)per_wave;
+        const double cost = steps * level_us * std::max(1.0, waves / ((double)num_cus * 4));
+        if (cost < best_cost) { best_cost = cost; run_lanes = g; runs_on_pairs = pairs; }
+      }
+    };
+    sweep(tree_per_wave<FR>(), LEVEL_US, false);
+    if (PAIRS_POSSIBLE) sweep(HalfWK::PER_WAVE, HALF_LEVEL_US, true);
+    // (the model takes every bucket for a queued run - true of window-table plans; where a typical bucket fits a chunk only
+    // the few outliers are queued and the chip has the lanes)
+    if (PAIRS_POSSIBLE && avg_chunks <= 1.0) { run_lanes = 8; runs_on_pairs = true; }
+  }
+  mp.run_lanes = run_lanes;
+  mp.runs_on_pairs = runs_on_pairs;
+  // runs of more than big_chunks chunks - more than four serial additions per worker of msm_merge_runs_kernel - are cut
+  // into workgroup-sized pieces (msm_merge_long_kernel) that run on the group's half-point worker (G1: lane pairs)
+  // ... but never a run that is merely TYPICAL: where the average bucket already spans dozens of chunks (32 rows of 8 bits over
+  // 2^11 G2 points: 64 chunks per bucket) "big" starts at twice the average (round 6, first cut: half of that table's runs
+  // went down the long path, 0.81 -> 1.06 ms)
+  mp.big_chunks = std::max(std::max(32u, 4u * run_lanes), (u32)(2.0 * (double)p.n / (double)p.nb / (double)p.chunk));
+  mp.piece = long_piece<HalfWK>();
+  const MergeBounds mb = merge_bounds((u64)p.W * p.chunks_per_window, mp.walk, mp.big_chunks, mp.piece);
+  mp.max_long = mb.max_long; mp.max_big = mb.max_big; mp.max_pieces = mb.max_pieces;
+  return mp;
+}
+// 4. accumulate equal chunks ...
+template <class F>
+static dim3 accumulate_grid(const MsmPlan &p) {
+  const u32 wpb = workers_per_block<F>(128, default_per_wave<F>());
+  return dim3((p.chunks_per_window + wpb - 1) / wpb, p.W);
+}
+// (every variant of the kernel takes the record stride, so a padded table is read correctly by all of them)
+template <class F>
+static int launch_accumulate(hipStream_t st, const MsmPlan &p, bool lds_acc, const u64 *sorted, const u32 *zstart,
+                             const Affine<typename F::Mem> *acc_bases, u32 acc_stride, XYZZ<typename F::Mem> *pts,
+                             XYZZ<typename F::Mem> *head, XYZZ<typename F::Mem> *tail, ErrFlags *err) {
+  const dim3 grid = accumulate_grid<F>(p);
+  if constexpr (F::LANES == 1) {
+    if (lds_acc)
+      hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), grid, dim3(128), 0, st, sorted, zstart, acc_bases, pts, head,
+                         tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
+    else
+      hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), grid, dim3(128), 0, st, sorted, zstart, acc_bases, pts, head,
+                         tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
+  } else {
+    hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), grid, dim3(128), 0, st, sorted, zstart, acc_bases, pts, head,
+                       tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
+  }
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// ... then fold the buckets that straddle chunk boundaries.  block_cap (tests): 0, or at most block_cap workgroups for the
+// medium runs and 2 block_cap for the pieces, so that a small job goes round the kernels' grid-stride loops
+template <class FR>
+static int launch_merges(hipStream_t st, const MsmPlan &p, const MergePlan &mp, int num_cus, u32 block_cap, const u64 *sorted,
+                         const u32 *zstart, XYZZ<typename FR::Mem> *pts, XYZZ<typename FR::Mem> *head,
+                         XYZZ<typename FR::Mem> *tail, LongRun *long_runs, BigRun *big_runs, XYZZ<typename FR::Mem> *piece_out,
+                         ErrFlags *err) {
+  typedef typename MergeWorkers<FR>::HalfWK HalfWK;
+  constexpr bool PAIRS_POSSIBLE = MergeWorkers<FR>::PAIRS_POSSIBLE;
+  const u32 max_long = mp.max_long, max_big = mp.max_big, max_pieces = mp.max_pieces, run_lanes = mp.run_lanes;
+  const u32 rwpb = workers_per_block<FR>(128, default_per_wave<FR>());
+  const dim3 rgrid((p.chunks_per_window + rwpb - 1) / rwpb, p.W);
+  hipLaunchKernelGGL(msm_merge_chunks_kernel<FR>, rgrid, dim3(128), 0, st, sorted, zstart, pts, head, tail, p.n,
+                     p.c, p.chunk, p.chunks_per_window, mp.walk, long_runs, max_long, big_runs, max_big, mp.big_chunks, mp.piece, err);
+  BH_HIP_CHECK(hipGetLastError());
+  // medium runs and the pieces of the big runs in ONE launch (a launch with nothing to do costs ~5 us): a wavefront per
+  // SIMD for the medium runs, one workgroup per piece at a time for the big ones
+  u32 run_blocks = (u32)num_cus, long_blocks = std::min<u32>(max_pieces, (u32)num_cus * 8);
+  if (block_cap) { run_blocks = std::min(run_blocks, block_cap); long_blocks = std::min(long_blocks, 2 * block_cap); }
+  const dim3 tgrid(run_blocks + long_blocks);
+#define BH_TAIL(WKR, WKL)                                                                                                   \
+  hipLaunchKernelGGL((msm_merge_tail_kernel<WKR, WKL>), tgrid, dim3(LONG_THREADS), 0, st, pts, head, tail, p.c,              \
+                     p.chunks_per_window, long_runs, max_long, run_lanes, run_blocks, big_runs, max_big, piece_out,           \
+                     max_pieces, err)
+  // One launch (medium runs and big pieces side by side) - except the 128-bucket window tables of tiny G2 vectors, whose
+  // 128 medium runs are the whole job: two launches there (G2 2^10: 0.74 against 0.85 ms; 2^12 ... 2^16 and every G1 size are
+  // equal or faster fused - G1 2^16 0.79 against 0.88 ms; profiles/r6_call15_tail_split_ab.txt).  The big pieces always run
+  // on the half-point worker (HalfWK is XyzzWorker<FR> where the group has none)
+  if constexpr (PAIRS_POSSIBLE) {
+    if (mp.runs_on_pairs) BH_TAIL(HalfWK, HalfWK);
+    else BH_TAIL(XyzzWorker<FR>, HalfWK);
+  } else if (p.NB > 128) {
+    BH_TAIL(XyzzWorker<FR>, XyzzWorker<FR>);
+  } else {
+    hipLaunchKernelGGL(msm_merge_runs_kernel<XyzzWorker<FR>>, dim3(run_blocks * 4), dim3(64), 0, st, pts, head, tail, p.c,
+                       p.chunks_per_window, long_runs, max_long, run_lanes, err);
+    hipLaunchKernelGGL(msm_merge_long_kernel<XyzzWorker<FR>>, dim3(long_blocks), dim3(LONG_THREADS), 0, st, pts, head, tail,
+                       p.c, p.chunks_per_window, big_runs, max_big, piece_out, max_pieces, err);
+  }
+#undef BH_TAIL
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+
+// ============================================================================================
 // host orchestration
 // ============================================================================================
 // F = the ops bundle the accumulation computes with (FpOps for G1; Fp2K3Ops, or single-lane Fp2Ops, for G2), FR the
@@ -1100,49 +1250,8 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const u64 npairs = (u64)p.Wd * n;
   const u64 ncounts = sort_counts_elems(p);
   const u64 nslots = (u64)p.W * p.chunks_per_window;
-  // the owner lane of a run folds at most `walk` following chunks itself; longer runs are queued for
-  // msm_merge_runs_kernel (G workers per run), the longest of those for the workgroup kernel
-  const u32 walk = 4;
-  // G workers per queued run: 8-16 chunk runs become 1-2 serial additions + 3 tree levels; when the AVERAGE run is
-  // much longer than that (window tables over tiny vectors: 32 n entries in 128 buckets, chunks of 8) more workers
-  // shorten the chain as long as the launch still fits the chip
-  // [r6] G1: the same on lane PAIRS (K2: half the latency of an addition for twice the lanes) when that is cheaper by
-  // the same model - levels x latency of a level x how far the launch overfills the chip
-  // [r6] G2 in lane triples: the same on lane SEXTETS (K6Worker)
-  constexpr bool G1_PAIRS = std::is_same<FR, FpOps>::value, G2_SEXTETS = std::is_same<FR, Fp2K3Ops>::value;
-  constexpr bool PAIRS_POSSIBLE = G1_PAIRS || G2_SEXTETS;   // "pairs" below: the half-point worker of the group
-  typedef typename std::conditional<G1_PAIRS, K2Worker, typename std::conditional<G2_SEXTETS, K6Worker, XyzzWorker<FR>>::type>::type HalfWK;
-  constexpr double LEVEL_US = G2_SEXTETS ? 37.0 : 19.0, HALF_LEVEL_US = G2_SEXTETS ? 20.0 : 10.5;   // a tree level, by worker kind
-  u32 run_lanes = 8;
-  bool runs_on_pairs = false;
-  {
-    const double avg_chunks = (double)p.n / (double)p.nb / (double)p.chunk;   // per window: n sorted entries, nb buckets
-    double best_cost = 1e30;
-    auto sweep = [&](u32 per_wave, double level_us, bool pairs) {
-      for (u32 g = 8, lg = 3; g <= per_wave; g <<= 1, lg++) {
-        const double steps = std::ceil(std::max(1.0, avg_chunks) / g) + lg;
-        const double waves = (double)p.NB * g / (double)per_wave;
-        const double cost = steps * level_us * std::max(1.0, waves / ((double)c.num_cus * 4));
-        if (cost < best_cost) { best_cost = cost; run_lanes = g; runs_on_pairs = pairs; }
-      }
-    };
-    sweep(tree_per_wave<FR>(), LEVEL_US, false);
-    if (PAIRS_POSSIBLE) sweep(HalfWK::PER_WAVE, HALF_LEVEL_US, true);
-    // (the model takes every bucket for a queued run - true of window-table plans; where a typical bucket fits a chunk only
-    // the few outliers are queued and the chip has the lanes)
-    if (PAIRS_POSSIBLE && avg_chunks <= 1.0) { run_lanes = 8; runs_on_pairs = true; }
-  }
-  const u32 max_long = (u32)(nslots / (walk + 1) + 1);
-  // runs of more than big_chunks chunks - more than four serial additions per worker of msm_merge_runs_kernel - are cut
-  // into workgroup-sized pieces (msm_merge_long_kernel) that run on the group's half-point worker (G1: lane pairs)
-  // ... but never a run that is merely TYPICAL: where the average bucket already spans dozens of chunks (32 rows of 8 bits over
-  // 2^11 G2 points: 64 chunks per bucket) "big" starts at twice the average (round 6, first cut: half of that table's runs
-  // went down the long path, 0.81 -> 1.06 ms)
-  const u32 big_chunks = std::max(std::max(32u, 4u * run_lanes), (u32)(2.0 * (double)p.n / (double)p.nb / (double)p.chunk));
-  const u32 piece = long_piece<HalfWK>();
-  const u32 max_big = (u32)(nslots / (big_chunks + 1) + 1);
-  // sum of ceil(L_r / piece) over the big runs: consecutive runs share one chunk, so sum L_r <= nslots + max_big
-  const u32 max_pieces = (u32)((nslots + max_big) / piece + max_big + 1);
+  const MergePlan mp = merge_plan<FR>(p, c.num_cus);
+  const u32 max_long = mp.max_long, max_big = mp.max_big, max_pieces = mp.max_pieces;
   const u32 H = 1u << p.hi_bits, Lw = 1u << p.lo_bits;
   const u64 nwords = (n + 63) / 64;
   size_t off = 0;
@@ -1244,8 +1353,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   if (small_fused) {
     if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));
   } else {
-    const u32 wpb = workers_per_block<F>(128, default_per_wave<F>());
-    const dim3 grid((p.chunks_per_window + wpb - 1) / wpb, p.W);
+    const dim3 grid = accumulate_grid<F>(p);
     const Affine<M> *bases = (const Affine<M> *)bases_dev;
     // G1 records at a 128-byte stride for the gathers of the classic plan (api.hip bh_bases::padded)
     const bool padded = opts.padded_bases && !use_table && !G2 && F::LANES == 1 && !lds_acc;
@@ -1264,54 +1372,14 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     // (every variant of the kernel takes the record stride, so a padded table is read correctly by all of them)
     const Affine<M> *acc_bases = padded_tab ? (const Affine<M> *)opts.padded_table : padded ? (const Affine<M> *)opts.padded_bases : bases;
     const u32 acc_stride = (padded || padded_tab) ? 128u : (u32)sizeof(Affine<M>);
-    if constexpr (F::LANES == 1) {
-      if (lds_acc)
-        hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), grid, dim3(128), 0, st, sorted, b.zstart, acc_bases, pts, head,
-                           tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
-      else
-        hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), grid, dim3(128), 0, st, sorted, b.zstart, acc_bases, pts, head,
-                           tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
-    } else {
-      hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), grid, dim3(128), 0, st, sorted, b.zstart, acc_bases, pts, head,
-                         tail, p.n, p.c, p.chunk, p.chunks_per_window, err, acc_stride);
-    }
-    BH_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_accumulate<F>(st, p, lds_acc, sorted, b.zstart, acc_bases, acc_stride, pts, head, tail, err)) return rc;
     if (chained) {
       BH_HIP_CHECK(hipEventRecord(job.res.acc_event, st));
       c.last_acc_event = job.res.acc_event;
       chain_lock.unlock();
     }
     if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));   // brackets exactly the accumulate launch
-    const u32 rwpb = workers_per_block<FR>(128, default_per_wave<FR>());
-    const dim3 rgrid((p.chunks_per_window + rwpb - 1) / rwpb, p.W);
-    hipLaunchKernelGGL(msm_merge_chunks_kernel<FR>, rgrid, dim3(128), 0, st, sorted, b.zstart, pts, head, tail, p.n,
-                       p.c, p.chunk, p.chunks_per_window, walk, long_runs, max_long, big_runs, max_big, big_chunks, piece, err);
-    BH_HIP_CHECK(hipGetLastError());
-    // medium runs and the pieces of the big runs in ONE launch (a launch with nothing to do costs ~5 us): a wavefront per
-    // SIMD for the medium runs, one workgroup per piece at a time for the big ones
-    const u32 run_blocks = (u32)c.num_cus, long_blocks = std::min<u32>(max_pieces, (u32)c.num_cus * 8);
-    const dim3 tgrid(run_blocks + long_blocks);
-#define BH_TAIL(WKR, WKL)                                                                                                   \
-    hipLaunchKernelGGL((msm_merge_tail_kernel<WKR, WKL>), tgrid, dim3(LONG_THREADS), 0, st, pts, head, tail, p.c,              \
-                       p.chunks_per_window, long_runs, max_long, run_lanes, run_blocks, big_runs, max_big, piece_out,           \
-                       max_pieces, err)
-    // One launch (medium runs and big pieces side by side) - except the 128-bucket window tables of tiny G2 vectors, whose
-    // 128 medium runs are the whole job: two launches there (G2 2^10: 0.74 against 0.85 ms; 2^12 ... 2^16 and every G1 size are
-    // equal or faster fused - G1 2^16 0.79 against 0.88 ms; profiles/r6_call15_tail_split_ab.txt).  The big pieces always run
-    // on the half-point worker (HalfWK is XyzzWorker<FR> where the group has none)
-    if constexpr (PAIRS_POSSIBLE) {
-      if (runs_on_pairs) BH_TAIL(HalfWK, HalfWK);
-      else BH_TAIL(XyzzWorker<FR>, HalfWK);
-    } else if (p.NB > 128) {
-      BH_TAIL(XyzzWorker<FR>, XyzzWorker<FR>);
-    } else {
-      hipLaunchKernelGGL(msm_merge_runs_kernel<XyzzWorker<FR>>, dim3((u32)c.num_cus * 4), dim3(64), 0, st, pts, head, tail, p.c,
-                         p.chunks_per_window, long_runs, max_long, run_lanes, err);
-      hipLaunchKernelGGL(msm_merge_long_kernel<XyzzWorker<FR>>, dim3(long_blocks), dim3(LONG_THREADS), 0, st, pts, head, tail,
-                         p.c, p.chunks_per_window, big_runs, max_big, piece_out, max_pieces, err);
-    }
-#undef BH_TAIL
-    BH_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_merges<FR>(st, p, mp, c.num_cus, 0, sorted, b.zstart, pts, head, tail, long_runs, big_runs, piece_out, err)) return rc;
   }
   // 5. reduce: rows (sum over lo, contiguous), columns (sum over hi, stride Lw), then bits.
   // G workers per output chosen so that each launch is about one wavefront per SIMD.

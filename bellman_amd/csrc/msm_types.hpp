@@ -8,8 +8,8 @@ struct ErrFlags {       // device-side status word block
   u32 eof;              // a dense entry found the base cursor at/after the end (multiexp.rs:55-61,74-80)
   u32 ident;            // an identity base was consumed (multiexp.rs:63-65)
   u32 ident_top;        // ... in the reference's top window, before the first EOF entry
-  u32 nlong;            // number of bucket runs queued for the wavefront-parallel merge
-  u32 nbig;             // ... of those, runs long enough to be passed on to the workgroup-parallel merge
+  u32 nlong;            // number of (medium) bucket runs queued for the wavefront-parallel merge
+  u32 nbig;             // runs long enough for the workgroup-parallel merge instead: counted here alone, not in nlong
   u32 npieces;          // ... and the workgroup-sized pieces they were cut into (msm_merge_tail_kernel)
   // what the job executed (bh_msm_wait_stats): mixed additions into a non-empty accumulator by the accumulate launch
   // (entries that OPEN a bucket or a chunk partial are copies, ec.cuh xyzz_madd), zero digits the sort moved to the front

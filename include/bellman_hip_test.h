@@ -173,6 +173,43 @@ int bh_test_group_ops_host(int form, int op, unsigned G, void *r, uint32_t *flag
 int bh_test_sum_jobs_dev(bh_ctx *ctx, int form, unsigned waves, const void *in_dev, size_t n_in, void *out_dev, size_t n_out,
                          const uint32_t *jobs, size_t n_jobs);
 
+/* Stage 4 of a multiexp on its own (csrc/test_bucket_hooks.hip; tests/test_gpu_bucket_stage.py, tests/models/
+ * bucket_stage_model.py): msm_accumulate_kernel, msm_merge_chunks_kernel and the tail - msm_merge_tail_kernel, or
+ * msm_merge_runs_kernel + msm_merge_long_kernel - over a SORTED pair stream of the caller's choice, launched by the functions
+ * msm_enqueue launches them with (launch_accumulate, launch_merges of csrc/msm_ec.cuh), with the merge parameters of the
+ * shipped merge_plan and queues sized by the shipped merge_bounds.
+ *   acc_form    0 G1 in registers   1 G1, accumulator in LDS   2 G2 one lane, accumulator in LDS (pipelined)
+ *               3 G2 one lane in registers (pipelined)   4 G2 lane triples   5 G2 lane pairs
+ *   merge_form  0 G1, medium runs on XyzzWorker<FpOps>   1 G1, medium runs on lane pairs (big runs: lane pairs in both)
+ *               2 G2 in lane triples, medium runs on XyzzWorker<Fp2K3Ops>   3 ... on lane sextets (big runs: sextets in both)
+ *               4 G2 one lane, the fused tail kernel (needs W 2^(c-1) > 128 buckets)   5 G2 one lane, the two launches
+ *               (needs at most 128 buckets)
+ * bh_test_bucket_stage_shape: out12 = [XYZZ record bytes, dense affine record bytes, partials per piece, workers per
+ * wavefront of the medium worker, ... of the big worker, smallest and largest admissible G (workers per medium run, a
+ * power of two), guard bytes behind every returned buffer, sizeof LongRun, BigRun, ErrFlags, the sentinel byte].
+ * bh_test_merge_plan (host only): the merge parameters of a plan (W windows of n entries, c window bits, chunks of K,
+ * chunks_per_window lanes per window; NB = W 2^(c-1), nb = 2^(c-1)) on a chip of num_cus compute units: plan_out8 = [walk,
+ * run_lanes (G), runs_on_pairs, big_chunks, piece, max_long, max_big, max_pieces].  The form fixes which worker folds the medium
+ * runs; where merge_plan chose the other one G is 8.  Here alone merge_form may also be 6, 7 or 8: the plan of the bundle FpOps,
+ * Fp2K3Ops or Fp2Ops exactly as msm_enqueue gets it.  overrides4 (optional; 0 = keep) = [walk, run_lanes, big_chunks, block
+ * cap]: the bounds are then the shipped bounds of the overridden values.  block cap b: at most b workgroups for the medium
+ * runs and 2 b for the pieces of the big runs.
+ * bh_test_bucket_stage_dev: pairs = W x n entries (|digit| << 32 | sign << 31 | base index), zstart[W] = each window's first
+ * live entry, bases = n_bases affine records base_stride bytes apart (the dense size; 128 with acc_form 0).  Refused before
+ * any launch: live digits that decrease or leave [1, 2^(c-1)], a base index >= n_bases, z > n, n > chunks_per_window K, a G
+ * that is no power of two in the admissible range, W > 16, n > 2^20, c > 16, more than 2^20 chunks.  With every output pointer
+ * NULL it only fills plan_out8: the caller sizes its buffers by it - pts_out W 2^(c-1) records, head_out and tail_out
+ * W chunks_per_window records, long_out max_long LongRun, big_out max_big BigRun, pieces_out max_pieces records, err_out one
+ * ErrFlags, each followed by the guard bytes - and calls again.  pts and ErrFlags start zeroed as in production; head,
+ * tail, the piece results, both queues and every guard start filled with the sentinel byte. */
+int bh_test_bucket_stage_shape(int acc_form, int merge_form, size_t out12[12]);
+int bh_test_merge_plan(int merge_form, unsigned W, unsigned n, unsigned c, unsigned K, unsigned chunks_per_window, int num_cus,
+                       const uint32_t *overrides4, uint32_t plan_out8[8]);
+int bh_test_bucket_stage_dev(bh_ctx *ctx, int acc_form, int merge_form, const uint64_t *pairs, const uint32_t *zstart, unsigned W,
+                             unsigned n, const void *bases, size_t n_bases, unsigned base_stride, unsigned c, unsigned K,
+                             unsigned chunks_per_window, const uint32_t *overrides4, uint32_t plan_out8[8], void *pts_out,
+                             void *head_out, void *tail_out, void *long_out, void *big_out, void *pieces_out, void *err_out);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,
