@@ -55,6 +55,7 @@ TEST_EXPORTS = [
     "bh_test_field_ops_shape", "bh_test_field_ops_dev", "bh_test_field_ops_host",
     "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev",
     "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev",
+    "bh_test_sort_plan", "bh_test_scan_dev", "bh_test_sort_stage_dev",
 ]
 
 

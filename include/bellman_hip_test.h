@@ -210,6 +210,33 @@ int bh_test_bucket_stage_dev(bh_ctx *ctx, int acc_form, int merge_form, const ui
                              unsigned chunks_per_window, const uint32_t *overrides4, uint32_t plan_out8[8], void *pts_out,
                              void *head_out, void *tail_out, void *long_out, void *big_out, void *pieces_out, void *err_out);
 
+/* Stages 1 - 3 of a multiexp on their own (csrc/test_sort_hooks.hip, which compiles csrc/msm_stages.hip a second time into
+ * the test library; tests/test_gpu_sort_stage.py, tests/models/sort_stage_model.py): density prefix, recursive scan,
+ * signed-digit recoding, the 8-bit sort of the classic plan, the fused recode-and-sort of the table plan, the zero-digit search.
+ * kind: 0 the classic plan (make_plan; n entries per window, stride must be 0), 1 the table plan (make_table_plan over a table
+ * of ceil(256/c) rows `stride` records apart; n scalars).  Refused everywhere: c outside [2, 24], n = 0, Wd n >= 2^32,
+ * Wd stride >= 2^31 - the conditions of msm_enqueue.
+ * bh_test_sort_plan (host only): plan_out23 = [n, c, W, nd, Wd, num_tiles, sort_passes, base_stride, key bits of passes 0 - 3
+ * (0 where there is no such pass), wide_scalars_per_tile and the first pass's tile count (table plan; else 0),
+ * sort_counts_elems, scan_tmp_elems(counts + 1), SORT_TILE, WIDE_TILE, WIDE_THREADS, SCAN_TILE, guard bytes, the sentinel
+ * byte, sizeof ErrFlags].
+ * bh_test_scan_dev: exclusive_scan_u32 in place over data[n] (n <= 2^24) with a scratch of exactly scan_tmp_elems(n) words,
+ * which is returned raw in tmp_out; *tmp_elems_out is that count, and with data, tmp_out and guards_out2 all NULL nothing
+ * else happens (host only: ctx may be NULL, any n < 2^32).  guards_out2 = [data, scratch]: 1 when the guard bytes behind the buffer came back untouched.
+ * bh_test_sort_stage_dev: msm_run_stages once, on the context's stream, over nd scalars (32 bytes each; Montgomery ones must
+ * be below q) and an optional density bitmap of ceil(nd / 64) words; at most 2^21 entries (Wd nd).  Buffers as msm_enqueue
+ * sizes them, without its rounding to 256 bytes: pairs_a_out and pairs_b_out Wd nd entries, zstart_out W words, counts_out
+ * sort_counts_elems + 1, word_prefix_out ceil(nd / 64) + 1 (NULL exactly when density_words is), err_out one ErrFlags.
+ * ErrFlags starts zeroed as in production, everything else and every guard filled with the sentinel byte.
+ * *sorted_is_b_out: which pair array msm_run_stages returned.  guards_out8 = [pairs_a, pairs_b, counts, scan scratch, zstart,
+ * word_prefix, ErrFlags, scalars]: 1 = untouched. */
+int bh_test_sort_plan(int kind, size_t n, unsigned c, size_t stride, int g2, int num_cus, uint64_t plan_out23[23]);
+int bh_test_scan_dev(bh_ctx *ctx, uint32_t *data, size_t n, size_t *tmp_elems_out, uint32_t *tmp_out, uint32_t guards_out2[2]);
+int bh_test_sort_stage_dev(bh_ctx *ctx, int kind, unsigned c, const void *scalars, int fmt, size_t nd, const uint64_t *density_words,
+                           size_t skip, size_t n_bases, size_t stride, uint64_t *pairs_a_out, uint64_t *pairs_b_out,
+                           int *sorted_is_b_out, uint32_t *zstart_out, uint32_t *counts_out, uint32_t *word_prefix_out, void *err_out,
+                           uint32_t guards_out8[8]);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,
