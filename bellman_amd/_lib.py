@@ -56,6 +56,10 @@ TEST_EXPORTS = [
     "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev",
     "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev",
     "bh_test_sort_plan", "bh_test_scan_dev", "bh_test_sort_stage_dev",
+    "bh_test_pairing_stage_shape", "bh_test_proof_status_error", "bh_test_pairing_lines_dev", "bh_test_pairing_miller_dev", "bh_test_pairing_fold_dev",
+    "bh_test_pairing_proof_prep_dev", "bh_test_pairing_g1_mul_one_dev", "bh_test_pairing_colsum_dev", "bh_test_pairing_ic_table_dev",
+    "bh_test_pairing_ic_accumulate_dev", "bh_test_pairing_miller3_dev", "bh_test_pairing_fold3_const_dev",
+    "bh_test_pairing_verdict_dev", "bh_test_pairing_final_exp_dev",
 ]
 
 

@@ -166,7 +166,15 @@ int points_read_compressed(int group, const void *raw_dev, void *out_dev, u64 n,
                            u32 *status_dev, hipStream_t st);
 int proofs_read_dev(const void *bytes_dev, void *proofs_out_dev, u64 n, u32 *pst, u32 *words, unsigned long long *min_idx,
                     hipStream_t st);
-int proof_status_error(u32 word);
+// the error a sequential reader reports for a proof with this status word: the first bad element in the order a, b, c
+inline int proof_status_error(u32 word) {
+  for (int k = 0; k < 3; k++) {
+    const u32 s = (word >> (8 * k)) & 0xffu;
+    if (s & PT_INVALID_MASK) return BH_ERR_INVALID_POINT;
+    if (s & PT_IS_INF) return BH_ERR_POINT_AT_INFINITY;
+  }
+  return BH_OK;
+}
 // on-curve + prime-order-subgroup test of decoded points (skips entries already invalid / identity)
 // fills rows 1 .. W-1 of a window table whose row 0 holds the n bases
 int window_table_g1(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st);

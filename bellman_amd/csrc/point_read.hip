@@ -232,14 +232,4 @@ int proofs_read_dev(const void *bytes_dev, void *proofs_out_dev, u64 n, u32 *pst
   return BH_OK;
 }
 
-// the error a sequential reader reports for a proof with this status word: the first bad element in the order a, b, c
-int proof_status_error(u32 word) {
-  for (int k = 0; k < 3; k++) {
-    const u32 s = (word >> (8 * k)) & 0xffu;
-    if (s & PT_INVALID_MASK) return BH_ERR_INVALID_POINT;
-    if (s & PT_IS_INF) return BH_ERR_POINT_AT_INFINITY;
-  }
-  return BH_OK;
-}
-
 }  // namespace bh

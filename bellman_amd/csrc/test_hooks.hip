@@ -242,14 +242,10 @@ void bh_test_point_mul_host(int group, void *r, const void *a, const void *k) {
 
 // ---- test hook: full pairings (tests/test_gpu_verifier.py, tests/test_verifier_cpu.py) ------------------------------
 namespace bh {
-__global__ __launch_bounds__(64) void test_lines_kernel(const Affine<Fp2Ops> *q, line_t *lines, u32 n) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Affine<Fp2Ops> p = q[i];
-  if (aff_is_identity(p)) return;
-  line_t *out = lines + (size_t)i * MILLER_LINES;
-  g2_lines(p.x, p.y, [&](int k, const line_t &l) { out[k] = l; });
-}
+// the shipped launch functions of csrc/pairing_kernels.cuh, which test_pairing_hooks.hip compiles into this library
+int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int negate, line_t *lines, u32 *flags, size_t n);
+int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
+                  const line_t *lines1, const u32 *qflags1, size_t n1);
 // one pairing per lane; out = 12 canonical Fp (not Montgomery) in w-basis order w^0, w^1 (each c0 then c1 of Fp2), ...
 BH_HD void pairing_one(fp12_t &r, const Affine<FpOps> &p, const Affine<Fp2Ops> &q, const line_t *lines) {
   fp12_t f;
@@ -263,19 +259,6 @@ BH_HD void gt_store_canonical(fp_t *out, const fp12_t &r) {
     fe_from_mont(out[2 * k], f12_w(r, k).c0);
     fe_from_mont(out[2 * k + 1], f12_w(r, k).c1);
   }
-}
-__global__ __launch_bounds__(64) void test_miller_kernel(const Affine<FpOps> *p, const Affine<Fp2Ops> *q, const line_t *lines,
-                                                         fp12_t *f, u32 n) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Affine<FpOps> pp = p[i];
-  fp12_t r;
-  if (aff_is_identity(pp) || aff_is_identity(q[i])) f12_one(r);
-  else {
-    const line_t *l = lines + (size_t)i * MILLER_LINES;
-    miller_loop_lines(r, pp.x, pp.y, [&](int k) { return l[k]; });
-  }
-  f[i] = r;
 }
 __global__ __launch_bounds__(64) void test_gt_store_kernel(const fp12_t *r, fp_t *out, u32 n) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -291,7 +274,7 @@ int bh_test_pairing(bh_ctx *ctx, size_t n, const void *g1_affine, const void *g2
   Context &c = ctx->c;
   BH_HIP_CHECK(hipSetDevice(c.device));
   const size_t bl = n * MILLER_LINES * sizeof(line_t);
-  char *d = (char *)c.pool.acquire(n * 96 + n * 192 + n * 576 + bl + 5 * n * sizeof(fp12_t));
+  char *d = (char *)c.pool.acquire(n * 96 + n * 192 + n * 576 + bl + 5 * n * sizeof(fp12_t) + n * sizeof(u32));
   if (!d) return BH_ERR_HIP;
   Affine<FpOps> *p = (Affine<FpOps> *)d;
   Affine<Fp2Ops> *q = (Affine<Fp2Ops> *)(d + n * 96);
@@ -304,10 +287,13 @@ int bh_test_pairing(bh_ctx *ctx, size_t n, const void *g1_affine, const void *g2
   if (!rc) {
     const u32 nb = (u32)((n + 63) / 64);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(test_lines_kernel, dim3(nb), dim3(64), 0, c.stream, q, lines, (u32)n);
     fp12_t *f = (fp12_t *)(d + n * 864 + bl);
-    hipLaunchKernelGGL(test_miller_kernel, dim3(nb), dim3(64), 0, c.stream, p, q, lines, f, (u32)n);
-    if (hipGetLastError() != hipSuccess || !final_exp_chain(c.stream, f, f, nullptr, f + n, (u32)n)) rc = BH_ERR_HIP;
+    u32 *qflags = (u32 *)(f + 5 * n);
+    if (launch_g2_lines(c.stream, q, sizeof(Affine<Fp2Ops>), 0, lines, qflags, n) != BH_OK ||
+        launch_miller(c.stream, p, lines, qflags, f, n, nullptr, nullptr, 0) != BH_OK ||
+        !final_exp_chain(c.stream, f, f, nullptr, f + n, (u32)n))
+      rc = BH_ERR_HIP;
+    (void)hipGetLastError();
     hipLaunchKernelGGL(test_gt_store_kernel, dim3(nb), dim3(64), 0, c.stream, f, out, (u32)n);
     if (hipGetLastError() != hipSuccess) rc = BH_ERR_HIP;
   }

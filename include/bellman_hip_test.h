@@ -237,6 +237,59 @@ int bh_test_sort_stage_dev(bh_ctx *ctx, int kind, unsigned c, const void *scalar
                            int *sorted_is_b_out, uint32_t *zstart_out, uint32_t *counts_out, uint32_t *word_prefix_out, void *err_out,
                            uint32_t guards_out8[8]);
 
+/* The kernels of the Groth16 verifier on their own (csrc/test_pairing_hooks.hip, which compiles csrc/pairing_kernels.cuh a
+ * second time into the test library; tests/test_gpu_pairing_stages.py, tests/models/pairing_stage_model.py).  Each call runs
+ * one stage once on the context's stream through the shipped launch function (launch_g2_lines, launch_miller, launch_fold,
+ * launch_colsum, launch_fold3_const, launch_final_exp) or, where the verifier launches the kernel inline, with the verifier's
+ * block size.  Every device buffer has exactly the size the verifier gives it for n proofs, followed by a guard; outputs
+ * and guards start filled with the sentinel byte, results come back raw, and guards[k] = 1 when the guard behind buffer k
+ * (in the order given below) came back untouched.  Refused before any launch: n = 0 or n > 2^15, a width outside
+ * {1, 2, 4, 8}, a stride other than 192 or 384, nb_override > COLSUM_BLOCKS, a scalar format that does not exist.
+ * bh_test_pairing_stage_shape: out16 = [sizeof line_t, fp12_t, ProofRec, MILLER_LINES, PF_IDENTITY, PF_OFF_CURVE,
+ *   PT_INVALID_MASK, PT_IS_INF, COLSUM_THREADS, COLSUM_BLOCKS, BATCH_CHUNK, guard bytes, the sentinel byte, the offsets of
+ *   ProofRec::b and ::c, sizeof an affine G1 record].
+ * lines: n records stride_bytes apart (192: G2 points; 384: proofs, the point at ProofRec::b); lines_out n x 68 line_t,
+ *   flags_out n words.  guards: [records, lines, flags].
+ * miller: p = n0 + n1 G1 points; lines0 / flags0 serve the first n0, lines1 / flags1 the rest.  guards: [p, lines0, flags0,
+ *   lines1, flags1, f].
+ * fold: launch_fold over f_inout[m]; the whole array comes back.
+ * proof_prep: z may be NULL; want_c = 0 passes NULL for c_out, zc_out and the generator.  guards: [proofs, z, generator,
+ *   p_out, c_out, zc_out, flags].
+ * g1_mul_one: guards [p, s, out].
+ * colsum: launch_colsum over n proofs of n_inputs inputs each; acc_inout n_inputs + 1 values (read and written), part_out
+ *   (n_inputs + 1) x COLSUM_BLOCKS values; nb_override 0 = the shipped rule.  guards: [z, inputs, part, acc].
+ * ic_table: the (n_in, 256 / w, 2^w - 1) table of ic[n_in].  guards: [ic, table].
+ * ic_accumulate: over a table of the caller's (n_inputs = 0: table may be NULL).  guards: [inputs, table, ic0, out].
+ * miller3: separate != 0: gridDim.y = 3 and f_out 3 n values (pairs is then ignored); else gridDim.y = 1, f_out n values.
+ *   klines 2 x 68 lines, kflags2 2 words.  guards: [a, acc, proofs, blines, bflags, klines, kflags, f].
+ * fold3_const: launch_fold3_const over f_inout (3 n values when separate, else n) and the constant c.  guards: [f, c].
+ * verdict: words may be NULL.  guards: [words, pflags, qflags, is_one, verdicts].
+ * final_exp: launch_final_exp over n <= 4096 values with a workspace of 4 n.  guards: [f, out, is_one, workspace]. */
+int bh_test_pairing_stage_shape(uint64_t out16[16]);
+/* host only: the verifier's proof_status_error of a status word of bh_proofs_read */
+int bh_test_proof_status_error(uint32_t word);
+int bh_test_pairing_lines_dev(bh_ctx *ctx, const void *records, size_t stride_bytes, int negate, size_t n, void *lines_out,
+                              uint32_t *flags_out, uint32_t guards[3]);
+int bh_test_pairing_miller_dev(bh_ctx *ctx, const void *p, const void *lines0, const uint32_t *flags0, size_t n0,
+                               const void *lines1, const uint32_t *flags1, size_t n1, void *f_out, uint32_t guards[6]);
+int bh_test_pairing_fold_dev(bh_ctx *ctx, void *f_inout, size_t m, uint32_t guards[1]);
+int bh_test_pairing_proof_prep_dev(bh_ctx *ctx, const void *proofs, const void *z, int fmt, size_t n, int want_c,
+                                   const void *g1_generator, void *p_out, void *c_out, void *zc_out, uint32_t *flags_out,
+                                   uint32_t guards[7]);
+int bh_test_pairing_g1_mul_one_dev(bh_ctx *ctx, const void *p, const void *s_mont, void *out, uint32_t guards[3]);
+int bh_test_pairing_colsum_dev(bh_ctx *ctx, const void *z, const void *inputs, size_t n_inputs, int fmt, size_t n,
+                               unsigned nb_override, void *acc_inout, void *part_out, uint32_t guards[4]);
+int bh_test_pairing_ic_table_dev(bh_ctx *ctx, const void *ic, size_t n_in, unsigned w, void *table_out, uint32_t guards[2]);
+int bh_test_pairing_ic_accumulate_dev(bh_ctx *ctx, const void *inputs, size_t n_inputs, int fmt, const void *table, unsigned w,
+                                      const void *ic0, size_t n, void *out, uint32_t guards[4]);
+int bh_test_pairing_miller3_dev(bh_ctx *ctx, const void *a, const void *acc, const void *proofs, const void *blines,
+                                const uint32_t *bflags, const void *klines, const uint32_t *kflags2, int separate, unsigned pairs,
+                                size_t n, void *f_out, uint32_t guards[8]);
+int bh_test_pairing_fold3_const_dev(bh_ctx *ctx, void *f_inout, const void *c, size_t n, int separate, uint32_t guards[2]);
+int bh_test_pairing_verdict_dev(bh_ctx *ctx, const uint32_t *words, const uint32_t *pflags, const uint32_t *qflags,
+                                const uint32_t *is_one, size_t n, int32_t *verdicts_out, uint32_t guards[5]);
+int bh_test_pairing_final_exp_dev(bh_ctx *ctx, const void *f, size_t n, void *out, uint32_t *is_one_out, uint32_t guards[4]);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,
