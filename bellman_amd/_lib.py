@@ -53,7 +53,7 @@ TEST_EXPORTS = [
     "bh_test_groth16_prove_via_call_sites", "bh_test_demo_assignment", "bh_test_shard_cuts", "bh_test_pool_size_class", "bh_test_capture_check",
     "bh_test_pairing", "bh_test_pairing_host", "bh_test_fp_sqrt_host", "bh_test_fp2_sqrt_host",
     "bh_test_field_ops_shape", "bh_test_field_ops_dev", "bh_test_field_ops_host",
-    "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev",
+    "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev", "bh_test_g1_madd_sliced_dev", "bh_test_g1_madd_sliced_host",
     "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev",
     "bh_test_sort_plan", "bh_test_scan_dev", "bh_test_sort_stage_dev",
     "bh_test_pairing_stage_shape", "bh_test_proof_status_error", "bh_test_pairing_lines_dev", "bh_test_pairing_miller_dev", "bh_test_pairing_fold_dev",
@@ -284,6 +284,8 @@ def load():
     lib.bh_test_g2_k3_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz]
     lib.bh_test_g2_pairs_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz]
     lib.bh_test_g2_k6_dev.argtypes = [vp, vp, vp, vp, sz]
+    lib.bh_test_g1_madd_sliced_dev.argtypes = [vp, vp, vp, vp, vp, sz]
+    lib.bh_test_g1_madd_sliced_host.argtypes = [vp, vp, vp, vp, sz]
     for name in ("bh_test_fr_mul_host", "bh_test_fp_mul_host", "bh_test_fr_mul_bform_host"):
         getattr(lib, name).argtypes = [vp, vp, vp, sz]
         getattr(lib, name).restype = None

@@ -11,6 +11,8 @@
 // addition for short-Weierstrass a = 0 curves: 8M + 2S vs 11M for the complete formulas.
 // Identity: ZZ == 0 (an all-zero record is the identity, so hipMemset(0) clears buckets).
 #pragma once
+#include <type_traits>
+
 #include "ff.cuh"
 
 namespace bh {
@@ -143,6 +145,8 @@ BH_HD void order_after(T &v) {
   (void)v;
 #endif
 }
+// (xyzz_madd_sliced below is a copy of this formula over sliced operands, for the G1 bucket accumulation: a change to the
+// branches or to the order of the products here is made there too - the word-for-word tests compare the two.)
 // Returns false when acc was the identity (the "addition" is a copy), true when a group addition was executed.
 template <class F, class PF>
 BH_HD bool xyzz_madd(XYZZ<F> &acc, const Affine<F> &q, PF prefetch) {
@@ -243,6 +247,69 @@ BH_HD bool xyzz_madd(XYZZ<F> &acc, const Affine<F> &q) {
   acc.x = t;
   return true;
 }
+
+// The mixed addition of the G1 bucket accumulation (FpOps): xyzz_madd's formula, the same products and subtractions in
+// the same order, but every value is cut into 30-bit limbs ONCE (ff.cuh fe_to_hform) and the products take the limbs.
+// xyzz_madd cuts both operands inside every product - 18 cuts per addition, of which PP is cut three times and PPP,
+// P, R, ZZ1 and ZZZ1 twice each.  Here there are 11: x2, y2, ZZ1, ZZZ1, P, PP, PPP, X1, R and, in the fused tail, Q - X3
+// and 2p - Y1.  The limbs exist in registers between the products of one addition only; the accumulator, the table and
+// everything that leaves this function keep the 32-bit words, and the results are the same words as xyzz_madd's.
+// Only the accumulation uses it: with 26 instead of 24 argument registers per product the register-bound G1 kernels
+// that also call xyzz_madd (fixed_base_table_kernel 226, point_check_kernel 239 VGPRs) fell to one wave per SIMD.
+// Returns what xyzz_madd returns.
+template <class F>
+BH_HD bool xyzz_madd_sliced(XYZZ<F> &acc, const Affine<F> &q) {
+  typedef typename F::T T;
+  typedef typename F::H H;
+  if (xyzz_is_identity(acc)) {
+    acc.x = q.x;
+    acc.y = q.y;
+    F::one(acc.zz);
+    F::one(acc.zzz);
+    return false;
+  }
+  T p, r, pp, ppp, qq, t;
+  H ha, hb, hzz, hzzz;
+  F::slice(ha, q.x);
+  F::slice(hzz, acc.zz);
+  F::mul_hh(p, ha, hzz);
+  F::sub(p, p, acc.x);     // P = U2 - X1
+  F::slice(ha, q.y);
+  F::slice(hzzz, acc.zzz);
+  F::mul_hh(r, ha, hzzz);
+  F::sub(r, r, acc.y);     // R = S2 - Y1
+  if (F::is_zero(p)) {
+    if (F::is_zero(r)) {
+      xyzz_dbl_affine(acc, q);  // same point
+    } else {
+      xyzz_set_identity(acc);   // opposite points
+    }
+    return true;
+  }
+  F::slice(ha, p);
+  F::sqr_h(pp, ha);
+  F::slice(hb, pp);                   // PP, for its three products
+  F::mul_hh(ppp, ha, hb);             // p dead
+  F::slice(ha, acc.x);
+  F::mul_hh(qq, ha, hb);              // Q = X1*PP
+  F::mul_hh(acc.zz, hzz, hb);         // ZZ3 = ZZ1*PP          (pp dead)
+  F::slice(hb, ppp);                  // PPP, for ZZZ3 and the tail
+  F::mul_hh(acc.zzz, hzzz, hb);       // ZZZ3 = ZZZ1*PPP
+  F::slice(ha, r);                    // R, for its square and the tail
+  F::sqr_h(t, ha);
+  F::sub(t, t, ppp);
+  F::sub(t, t, qq);
+  F::sub(t, t, qq);                   // X3 = R^2 - PPP - 2Q
+  F::sub(qq, qq, t);
+  F::mul2_sub_tail_h(acc.y, ha, qq, acc.y, hb);   // Y3 = R*(Q - X3) - Y1*PPP under one reduction, as in xyzz_madd
+  acc.x = t;
+  return true;
+}
+// whether the field bundle has the sliced products (FpOps)
+template <class F, class = void>
+struct has_sliced_products : std::false_type {};
+template <class F>
+struct has_sliced_products<F, std::void_t<typename F::H>> : std::true_type {};
 
 // add-2008-s: r = a + b (general)
 template <class F>

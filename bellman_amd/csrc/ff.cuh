@@ -463,6 +463,87 @@ BH_HD void fe_sqr(Fe<P> &r, const Fe<P> &a) {
   fe_mont_reduce30<P, CANONICAL>(r, c);
 }
 
+// ---------------------------------------------------------------------------------------
+// Products of operands that are ALREADY sliced ("H form": the L 30-bit limbs of x << SHIFT/2).
+//
+// fe_mul cuts a into limbs of a and b into limbs of b << SHIFT; fe_sqr cuts a into limbs of a << SHIFT/2.  All of them
+// feed the reduction the columns of the integer a*b*2^SHIFT, and (a << SHIFT/2) * (b << SHIFT/2) is that same integer:
+// with ONE sliced form per value, the form the squaring already uses, a value that enters several products - or a
+// squaring and a product - is cut once (about 3 VALU instructions per limb, 39 per Fp operand) instead of once per use.
+// The reduction computes (T + M*m) / 2^(30L) with M the unique multiplier below 2^(30L) that clears the low half, so
+// its output depends on the integer T alone and not on how T is spread over the columns: these entry points return the
+// same words as fe_mul / fe_sqr / fe_mul2 for the same operands (tests/cpp/sliced_products_check.hip, run by tests/test_sliced_products_cpu.py: word for word).  Every limb is masked
+// to 30 bits and the column counts are those of the unsliced forms, so the static overflow proofs above (Radix30,
+// Radix30Fused: every limb of every operand at 2^30 - 1) cover them as written.
+// The slices live in registers only: nothing is stored or laid out in this form (ec.cuh xyzz_madd_sliced).
+// ---------------------------------------------------------------------------------------
+template <class P>
+BH_HD void fe_to_hform(u32 *H, const Fe<P> &x) {
+  typedef Radix30<P> R;
+  static_assert(R::SHIFT % 2 == 0, "the sliced form splits the Montgomery pre-shift evenly");
+#pragma unroll
+  for (int i = 0; i < R::L; i++) H[i] = fe_limb30<P, R::SHIFT / 2>(x, i);
+}
+template <class P, bool CANONICAL = true>
+BH_HD void fe_mul_hh(Fe<P> &r, const u32 *A, const u32 *B) {
+  constexpr int L = Radix30<P>::L;
+  u64 c[2 * L];
+#pragma unroll
+  for (int k = 0; k < 2 * L; k++) c[k] = 0;
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+#pragma unroll
+    for (int j = 0; j < L; j++) c[i + j] += (u64)A[i] * B[j];
+  }
+  fe_mont_reduce30<P, CANONICAL>(r, c);
+}
+template <class P, bool CANONICAL = true>
+BH_HD void fe_sqr_h(Fe<P> &r, const u32 *A) {
+  constexpr int L = Radix30<P>::L;
+  u64 c[2 * L];
+#pragma unroll
+  for (int k = 0; k < 2 * L; k++) c[k] = 0;
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+#pragma unroll
+    for (int j = i + 1; j < L; j++) c[i + j] += (u64)A[i] * A[j];
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * L; k++) c[k] <<= 1;
+#pragma unroll
+  for (int i = 0; i < L; i++) c[2 * i] += (u64)A[i] * A[i];
+  fe_mont_reduce30<P, CANONICAL>(r, c);
+}
+// (a*b + c*d) * 2^(-32N) under one reduction, all four operands sliced: fe_mul2's columns, relief and reduction plan
+template <class P, bool CANONICAL = true>
+BH_HD void fe_mul2_hh(Fe<P> &r, const u32 *A, const u32 *B, const u32 *C, const u32 *D) {
+  typedef Radix30<P> R;
+  typedef Radix30Fused<P> RF;
+  constexpr int L = R::L;
+  static_assert(RF::columns_fit(), "a product column overflows before the reduction");
+  u64 c[2 * L];
+#pragma unroll
+  for (int k = 0; k < 2 * L; k++) c[k] = 0;
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+#pragma unroll
+    for (int j = 0; j < L; j++) c[i + j] += (u64)A[i] * B[j];
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * L - 1; k++) {
+    if ((RF::PLAN.relieve >> k) & 1) {
+      c[k + 1] += c[k] >> 30;
+      c[k] &= R::MASK;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+#pragma unroll
+    for (int j = 0; j < L; j++) c[i + j] += (u64)C[i] * D[j];
+  }
+  fe_mont_reduce30<P, CANONICAL, RF::PLAN.whole>(r, c);
+}
+
 // canonical <-> Montgomery
 template <class P>
 BH_HD void fe_to_mont(Fe<P> &r, const Fe<P> &a) {
@@ -629,6 +710,35 @@ BH_HD fp_t fp_mul_call(const fp_t &a, const fp_t &b) {
                     u32x4{a.l[8], a.l[9], a.l[10], a.l[11]}, u32x4{b.l[0], b.l[1], b.l[2], b.l[3]},
                     u32x4{b.l[4], b.l[5], b.l[6], b.l[7]}, u32x4{b.l[8], b.l[9], b.l[10], b.l[11]});
 }
+// The same two products over SLICED operands (fe_to_hform), for the G1 mixed addition, which cuts every value once and
+// hands the limbs on.  The caller slices, the callee receives 13 limbs per operand as three vectors and a scalar: 26 of
+// the 32 argument VGPRs.  (A limb array handed over by reference would go through the stack - the round trip described
+// above, and scratch in kernels that have none.)
+struct fp_h {
+  u32 l[13];   // the thirteen 30-bit limbs of x << 3; lives in registers only
+};
+BH_NOINLINE_HD static fp_t fp_mul_hvec(u32x4 a0, u32x4 a1, u32x4 a2, u32 a3, u32x4 b0, u32x4 b1, u32x4 b2, u32 b3) {
+  const u32 A[13] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3};
+  const u32 B[13] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3};
+  fp_t r;
+  fe_mul_hh<FpParams, false>(r, A, B);   // lazily reduced
+  return r;
+}
+BH_NOINLINE_HD static fp_t fp_sqr_hvec(u32x4 a0, u32x4 a1, u32x4 a2, u32 a3) {
+  const u32 A[13] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3};
+  fp_t r;
+  fe_sqr_h<FpParams, false>(r, A);       // lazily reduced
+  return r;
+}
+BH_HD fp_t fp_mul_hh_call(const fp_h &a, const fp_h &b) {
+  return fp_mul_hvec(u32x4{a.l[0], a.l[1], a.l[2], a.l[3]}, u32x4{a.l[4], a.l[5], a.l[6], a.l[7]},
+                     u32x4{a.l[8], a.l[9], a.l[10], a.l[11]}, a.l[12], u32x4{b.l[0], b.l[1], b.l[2], b.l[3]},
+                     u32x4{b.l[4], b.l[5], b.l[6], b.l[7]}, u32x4{b.l[8], b.l[9], b.l[10], b.l[11]}, b.l[12]);
+}
+BH_HD fp_t fp_sqr_h_call(const fp_h &a) {
+  return fp_sqr_hvec(u32x4{a.l[0], a.l[1], a.l[2], a.l[3]}, u32x4{a.l[4], a.l[5], a.l[6], a.l[7]},
+                     u32x4{a.l[8], a.l[9], a.l[10], a.l[11]}, a.l[12]);
+}
 
 // ---------------------------------------------------------------------------------------
 // Fp2
@@ -676,6 +786,23 @@ struct FpOps {
     fe_mul2<FpParams, false>(r, a, b, nc, d);
   }
   BH_HD static void mul2_sub(T &r, const T &a, const T &b, const T &c, const T &d) { mul2_sub_tail(r, a, b, c, d); }
+  // The products once more over operands the caller has sliced (fe_to_hform): the same words as mul / sqr /
+  // mul2_sub_tail.  Used by the G1 mixed addition (ec.cuh), where most values enter two or three products.
+  typedef fp_h H;
+  BH_HD static void slice(H &h, const T &a) { fe_to_hform<FpParams>(h.l, a); }
+  BH_HD static void mul_hh(T &r, const H &a, const H &b) { r = fp_mul_hh_call(a, b); }
+  BH_HD static void sqr_h(T &r, const H &a) { r = fp_sqr_h_call(a); }
+  // r = a*b - c*d, inline like mul2_sub_tail; a and d arrive sliced, b and c are cut here (c as 2p - c)
+  BH_HD static void mul2_sub_tail_h(T &r, const H &a, const T &b, const T &c, const H &d) {
+    T nc;
+    u32 br = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) nc.l[i] = subb(fp_mod2(i), c.l[i], br, br);   // 2p - c in (0, 2p]
+    H hb, hc;
+    slice(hb, b);
+    slice(hc, nc);
+    fe_mul2_hh<FpParams, false>(r, a.l, hb.l, hc.l, d.l);
+  }
   BH_HD static void curve_b(T &r) {   // G1: y^2 = x^3 + 4
     T one2;
     fe_one(r);

@@ -118,6 +118,12 @@ __device__ __forceinline__ bool chunk_view(const u64 *src, u32 n, u32 z, u32 lan
   return true;
 }
 
+// Trips: every wavefront runs as many trips as its longest lane has entries; an entry that OPENS a bucket or a chunk
+// partial - 0.78 M of the 13.63 M entries of the 2^20-term plan - is a copy inside xyzz_madd while the other lanes add.
+// Letting the lane go on to its next entry within the same trip (one addition per trip in every lane) was built and
+// measured SLOWER, +0.04 ms alone and +0.05 ms on top of the sliced addition: nearly every trip has an opener in one of
+// its 64 lanes, and the whole wavefront then waits for that lane's second pair of dependent loads (entry, then base) -
+// profiles/accumulate_slices_and_openers.txt.  The loop is the plain one.
 // LDS_ACC: the running bucket sum lives in the lane's LDS slot instead of 48/96 VGPRs - for G2 this
 // is the difference between spilling at one wave per SIMD and fitting two.
 // (measured and removed in round 6: a variant that reads one word of the NEXT entry's record right before the iteration's
@@ -155,6 +161,8 @@ __global__ __launch_bounds__(128) void msm_accumulate_kernel(const u64 *pairs, c
   // s_waitcnt vmcnt(0) (ec.cuh).  With one resident wavefront per SIMD the two dependent loads of an iteration were
   // 21 % of the kernel's time (profiles/archive/r2_call8_pmc_g2_accumulate.json).
   constexpr bool PIPELINED = F::LANES == 1 && F::WORDS == 24;
+  // the mixed addition over sliced operands (ec.cuh): the G1 kernel with its accumulator in registers, the one measured
+  constexpr bool SLICED_MADD = has_sliced_products<F>::value && F::LANES == 1 && !LDS_ACC;
   // record `idx` of the vector the accumulation gathers from: every variant reads at the caller's record stride
   auto base_at = [&](u32 idx) {
     return reinterpret_cast<const Affine<typename F::Mem> *>(reinterpret_cast<const char *>(bases) + (size_t)idx * base_stride);
@@ -201,7 +209,8 @@ __global__ __launch_bounds__(128) void msm_accumulate_kernel(const u64 *pairs, c
       load_affine<F>(q, base_at((u32)e & 0x7fffffffu));
       if (aff_is_identity(q)) { saw_identity = true; continue; }
       if ((u32)e >> 31) F::neg(q.y, q.y);   // negative digit: add -P
-      adds += xyzz_madd(acc, q) ? 1u : 0u;
+      if constexpr (SLICED_MADD) adds += xyzz_madd_sliced(acc, q) ? 1u : 0u;   // G1 in registers: every value cut once
+      else adds += xyzz_madd(acc, q) ? 1u : 0u;
     }
   }
   store_xyzz<F>((cur == v.d_first && v.head_partial) ? &head[slot] : v.tail_partial ? &tail[slot] : &bucket[cur], acc);

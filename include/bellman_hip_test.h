@@ -173,6 +173,14 @@ int bh_test_group_ops_host(int form, int op, unsigned G, void *r, uint32_t *flag
 int bh_test_sum_jobs_dev(bh_ctx *ctx, int form, unsigned waves, const void *in_dev, size_t n_in, void *out_dev, size_t n_out,
                          const uint32_t *jobs, size_t n_jobs);
 
+/* The mixed addition of the G1 bucket accumulation over sliced operands (csrc/test_sliced_hooks.hip, ec.cuh
+ * xyzz_madd_sliced; tests/test_gpu_madd_sliced.py) next to xyzz_madd: a = n raw XYZZ records, q = n affine records (G1, one
+ * lane).  r = 2 n raw records: r[i] xyzz_madd(a[i], q[i]), r[n + i] the sliced addition.  An identity q[i] is skipped as the
+ * accumulation skips it.  flags[i]: bit 0 what xyzz_madd returned, bit 1 what the sliced addition returned, bit 4 q[i] was
+ * the identity. */
+int bh_test_g1_madd_sliced_dev(bh_ctx *ctx, void *r_dev, uint32_t *flags_dev, const void *a_dev, const void *q_dev, size_t n);
+int bh_test_g1_madd_sliced_host(void *r, uint32_t *flags, const void *a, const void *q, size_t n);
+
 /* Stage 4 of a multiexp on its own (csrc/test_bucket_hooks.hip; tests/test_gpu_bucket_stage.py, tests/models/
  * bucket_stage_model.py): msm_accumulate_kernel, msm_merge_chunks_kernel and the tail - msm_merge_tail_kernel, or
  * msm_merge_runs_kernel + msm_merge_long_kernel - over a SORTED pair stream of the caller's choice, launched by the functions
