@@ -11,6 +11,7 @@ from .errors import (  # noqa: F401
     InvalidData,
     InvalidPoint,
     InvalidProof,
+    InvalidTranscript,
     InvalidVerifyingKey,
     PointAtInfinity,
     PolynomialDegreeTooLarge,
@@ -25,3 +26,5 @@ from .multiexp import Bases, DensityTracker, FullDensity, Scalars, multiexp, mul
 from .domain import EvaluationDomain, PointEvaluationDomain  # noqa: F401
 from . import verifier  # noqa: F401,E402
 from .verifier import PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each, verify_proof  # noqa: F401,E402
+from . import ceremony  # noqa: F401,E402
+from .ceremony import PtauReport, pairing_product_is_one, verify_powers_of_tau  # noqa: F401,E402

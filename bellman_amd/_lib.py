@@ -44,6 +44,7 @@ EXPORTS = [
     "bh_groth16_prepare_verifying_key", "bh_groth16_pvk_from_params", "bh_groth16_pvk_num_inputs", "bh_groth16_verify",
     "bh_groth16_batch_verify", "bh_groth16_pvk_release", "bh_proofs_read", "bh_groth16_batch_verify_compressed",
     "bh_groth16_verify_each", "bh_groth16_verify_each_compressed",
+    "bh_bases_validate", "bh_pairing_product_is_one", "bh_powers_of_tau_verify",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -60,6 +61,7 @@ TEST_EXPORTS = [
     "bh_test_pairing_proof_prep_dev", "bh_test_pairing_g1_mul_one_dev", "bh_test_pairing_colsum_dev", "bh_test_pairing_ic_table_dev",
     "bh_test_pairing_ic_accumulate_dev", "bh_test_pairing_miller3_dev", "bh_test_pairing_fold3_const_dev",
     "bh_test_pairing_verdict_dev", "bh_test_pairing_final_exp_dev",
+    "bh_test_ptau_rlc_host", "bh_test_ptau_rlc_dev", "bh_test_ptau_sums",
 ]
 
 
@@ -272,6 +274,13 @@ def load():
     lib.bh_groth16_verify_each_compressed.argtypes = [vp, vp, sz, vp, sz, i32, vp, vp, c.POINTER(sz)]
     lib.bh_groth16_pvk_release.argtypes = [vp]
     lib.bh_groth16_pvk_release.restype = None
+    lib.bh_bases_validate.argtypes = [vp, vp, sz, sz, c.c_uint, vp, c.POINTER(sz)]
+    lib.bh_pairing_product_is_one.argtypes = [vp, vp, vp, sz, c.POINTER(i32)]
+    lib.bh_powers_of_tau_verify.argtypes = [vp, vp, vp, c.c_uint, vp]
+    lib.bh_test_ptau_rlc_host.argtypes = [vp, u32, sz, vp]
+    lib.bh_test_ptau_rlc_host.restype = None
+    lib.bh_test_ptau_rlc_dev.argtypes = [vp, vp, u32, sz, vp]
+    lib.bh_test_ptau_sums.argtypes = [vp, vp, vp, vp, vp]
     lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]
     lib.bh_test_pairing_host.argtypes = [sz, vp, vp, vp]
     lib.bh_test_pairing_host.restype = None

@@ -173,6 +173,9 @@ struct bh_bases {
   // accumulation alone (MsmOpts::padded_table); everything else of such a job reads the dense `dev`.
   bool table_padded = false;
 };
+namespace bh {
+int bases_group(const ::bh_bases *b) { return b->group; }   // for the units that see the handle only as an opaque type
+}
 static inline size_t table_rec_bytes(const bh_bases *b) { return b->group == BH_G1 ? (b->table_padded ? 128 : 96) : 192; }
 // a scalar vector resident in HBM (bh_scalars_*): create_proof hands the same assignment to up to four multiexps
 struct bh_scalars {
@@ -874,6 +877,60 @@ int bh_bases_read_compressed(bh_ctx *ctx, int group, const void *host_bytes, siz
     }
   }
   return new_bases(ctx, group, dev.release(), n, true, out);
+}
+// curve and subgroup tests over records [first, first + count) of a resident handle (point_read.hip validate_kernel),
+// VALIDATE_CHUNK records at a time on a stream of its own; the first offending record in order decides the return code
+int bh_bases_validate(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, unsigned flags, uint32_t *status_host,
+                      size_t *bad_index) {
+  if (!ctx || !b || first > b->n || count > b->n - first || (flags & ~(BH_POINTS_CHECKED | BH_POINTS_FORBID_IDENTITY)))
+    return BH_ERR_INVALID_ARG;
+  if (!count) return BH_OK;
+  constexpr size_t VALIDATE_CHUNK = size_t(1) << 20;   // 4 MB of status words
+  const size_t rec = b->group == BH_G1 ? 96 : 192;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  const size_t chunk = count < VALIDATE_CHUNK ? count : VALIDATE_CHUNK;
+  u32 *status = (u32 *)ctx->c.pool.acquire(chunk * 4 + 16);
+  if (!status) return BH_ERR_HIP;
+  unsigned long long *min_idx = (unsigned long long *)((char *)status + ((chunk * 4 + 7) & ~size_t(7)));
+  void *stream = nullptr;
+  if (bh_stream_create(ctx, &stream) != BH_OK) {
+    ctx->c.pool.release(status);
+    return BH_ERR_HIP;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int rc = BH_OK, verdict = BH_OK;
+  for (size_t off = 0; off < count && rc == BH_OK; off += chunk) {
+    const size_t m = count - off < chunk ? count - off : chunk;
+    unsigned long long bad = ~0ULL;
+    u32 bad_status = 0;
+    if (hipMemsetAsync(min_idx, 0xff, 8, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (rc == BH_OK)
+      rc = points_validate(b->group, (const char *)b->dev + (first + off) * rec, m, (flags & BH_POINTS_CHECKED) != 0, status, st);
+    if (rc == BH_OK) {
+      const u64 blocks = (m + 255) / 256;
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(first_bad_point_kernel, dim3((u32)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, status, (u64)m,
+                         (flags & BH_POINTS_FORBID_IDENTITY) ? 1u : 0u, min_idx);
+      if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, min_idx, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+          (status_host && hipMemcpyAsync(status_host + off, status, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+        rc = BH_ERR_HIP;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && rc == BH_OK) rc = BH_ERR_HIP;
+    if (rc == BH_OK && bad != ~0ULL && verdict == BH_OK) {
+      if (hipMemcpyAsync(&bad_status, status + bad, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess) {
+        rc = BH_ERR_HIP;
+      } else {
+        if (bad_index) *bad_index = off + (size_t)bad;
+        verdict = (bad_status & PT_INVALID_MASK) ? BH_ERR_INVALID_POINT : BH_ERR_POINT_AT_INFINITY;
+      }
+    }
+    if (verdict != BH_OK && !status_host) break;   // later chunks cannot hold an earlier record
+  }
+  (void)hipStreamSynchronize(st);
+  bh_stream_destroy(ctx, stream);
+  ctx->c.pool.release(status);
+  return rc != BH_OK ? rc : verdict;
 }
 int bh_bases_download(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, void *out_host) {
   if (!ctx || !b || first + count > b->n) return BH_ERR_INVALID_ARG;

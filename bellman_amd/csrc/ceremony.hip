@@ -1,0 +1,239 @@
+// What a receiver of a powers-of-tau transcript needs before deriving parameters from it (declared in
+// include/bellman_hip.h): bh_pairing_product_is_one over arbitrary host pairs, and bh_powers_of_tau_verify - the random
+// linear combination of each vector against its own shift (ptau_rlc.cuh) and six pairing equations.
+//
+// The pairings run through the verifier's own launch functions (pairing_kernels.cuh, compiled in pairing.hip - the one
+// unit of this library that includes that header - and declared here): the lines of every Q, one Miller lane per pair,
+// the fold, the final exponentiation.  An equation e(X, Y) = e(Z, W) is evaluated as e(X, Y) e(-Z, W) == 1 on two lanes.
+#include <string.h>
+
+#include <vector>
+
+#include "fp12.cuh"
+#include "msm_types.hpp"
+#include "point_read.cuh"
+#include "ptau_rlc.cuh"
+
+namespace bh {
+int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int negate, line_t *lines, u32 *flags, size_t n);
+int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
+                  const line_t *lines1, const u32 *qflags1, size_t n1);
+int launch_fold(hipStream_t st, fp12_t *f, size_t m);
+int launch_fold_rows(hipStream_t st, fp12_t *f, size_t m);
+int launch_final_exp(hipStream_t st, const fp12_t *f, size_t n, fp12_t *out, u32 *is_one, fp12_t *ws);
+int bases_group(const ::bh_bases *b);   // api.hip
+
+namespace {
+
+struct OwnStream {
+  bh_ctx *ctx;
+  void *st = nullptr;
+  explicit OwnStream(bh_ctx *c) : ctx(c) {
+    if (bh_stream_create(ctx, &st) != BH_OK) st = nullptr;
+  }
+  ~OwnStream() {
+    if (st) {
+      (void)hipStreamSynchronize((hipStream_t)st);
+      bh_stream_destroy(ctx, st);
+    }
+  }
+  hipStream_t get() const { return (hipStream_t)st; }
+};
+
+void neg_g1(Affine<FpOps> &r, const Affine<FpOps> &a) {
+  r = a;
+  if (aff_is_identity(a)) return;
+  FpOps::neg(r.y, a.y);
+  FpOps::canon(r.y);
+}
+
+// `lanes` pairs (p[i], q[i]) on the host.  products == 1: is_one[0] = (prod_i e(p_i, q_i) == 1).  Otherwise lanes ==
+// 2 * products and is_one[k] = (e(p_k, q_k) e(p_{k + products}, q_{k + products}) == 1): the pairs fold pairwise and the
+// final exponentiations run in one launch.  A pair with the identity on either side contributes 1.  *off_curve: some
+// non-identity point is not on its curve (G1 tested on the host, G2 by the lines kernel); is_one is then meaningless.
+int pairing_products(bh_ctx *ctx, hipStream_t st, const Affine<FpOps> *p, const Affine<Fp2Ops> *q, size_t lanes,
+                     size_t products, u32 *is_one, bool *off_curve) {
+  *off_curve = false;
+  for (size_t i = 0; i < lanes; i++)
+    if (!aff_is_identity(p[i]) && !on_curve(p[i])) *off_curve = true;
+  if (*off_curve) return BH_OK;
+  Context &c = ctx->c;
+  const size_t bytes_p = lanes * sizeof(Affine<FpOps>), bytes_q = lanes * sizeof(Affine<Fp2Ops>);
+  const size_t bytes_l = lanes * MILLER_LINES * sizeof(line_t), bytes_f = (lanes + 5 * products) * sizeof(fp12_t);
+  char *d = (char *)c.pool.acquire(bytes_p + bytes_q + bytes_l + bytes_f + (lanes + products) * sizeof(u32));
+  if (!d) return BH_ERR_HIP;
+  Affine<FpOps> *pd = (Affine<FpOps> *)d;
+  Affine<Fp2Ops> *qd = (Affine<Fp2Ops> *)(d + bytes_p);
+  line_t *lines = (line_t *)(d + bytes_p + bytes_q);
+  fp12_t *f = (fp12_t *)(d + bytes_p + bytes_q + bytes_l);
+  fp12_t *fe = f + lanes;   // the final exponentiations' results, then 4 values of workspace each
+  u32 *qflags = (u32 *)(f + lanes + 5 * products), *one_dev = qflags + lanes;
+  std::vector<u32> hflags(lanes);
+  int rc = BH_OK;
+  if (hipMemcpyAsync(pd, p, bytes_p, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(qd, q, bytes_q, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = BH_ERR_HIP;
+  if (!rc) rc = launch_g2_lines(st, qd, sizeof(Affine<Fp2Ops>), 0, lines, qflags, lanes);
+  if (!rc) rc = launch_miller(st, pd, lines, qflags, f, lanes, nullptr, nullptr, 0);
+  if (!rc) rc = products == 1 ? launch_fold(st, f, lanes) : launch_fold_rows(st, f, products);
+  if (!rc) rc = launch_final_exp(st, f, products, fe, one_dev, fe + products);
+  if (!rc && (hipMemcpyAsync(hflags.data(), qflags, lanes * sizeof(u32), hipMemcpyDeviceToHost, st) != hipSuccess ||
+              hipMemcpyAsync(is_one, one_dev, products * sizeof(u32), hipMemcpyDeviceToHost, st) != hipSuccess))
+    rc = BH_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
+  c.pool.release(d);
+  if (!rc)
+    for (u32 fl : hflags)
+      if (fl & PF_OFF_CURVE) *off_curve = true;
+  return rc;
+}
+
+template <class F>
+bool head_ok(const Affine<F> &p) {
+  return !aff_is_identity(p) && on_curve(p);
+}
+}  // namespace
+}  // namespace bh
+
+using namespace bh;
+
+extern "C" {
+
+int bh_pairing_product_is_one(bh_ctx *ctx, const void *g1_affine_host, const void *g2_affine_host, size_t n, int *is_one) {
+  if (!ctx || !is_one || (n && (!g1_affine_host || !g2_affine_host)) || n > BATCH_CHUNK) return BH_ERR_INVALID_ARG;
+  *is_one = 0;
+  if (!n) {
+    *is_one = 1;
+    return BH_OK;
+  }
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  OwnStream own(ctx);
+  if (!own.st) return BH_ERR_HIP;
+  u32 one = 0;
+  bool off = false;
+  const int rc = pairing_products(ctx, own.get(), (const Affine<FpOps> *)g1_affine_host, (const Affine<Fp2Ops> *)g2_affine_host,
+                                  n, 1, &one, &off);
+  if (rc) return rc;
+  if (off) return BH_ERR_INVALID_POINT;
+  *is_one = one == 1;
+  return BH_OK;
+}
+
+int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *seed32, unsigned flags, bh_ptau_report *report) {
+  bh_ptau_report local;
+  bh_ptau_report &rep = report ? *report : local;
+  rep.failed = 0;
+  rep.bad_vector = 0;
+  rep.bad_index = 0;
+  if (!ctx || !t || !seed32 || !t->tau_g1 || !t->tau_g2 || !t->alpha_tau_g1 || !t->beta_tau_g1 || !t->beta_g2 ||
+      (flags & ~BH_PTAU_VALIDATE_POINTS))
+    return BH_ERR_INVALID_ARG;
+  const bh_bases *vec[4] = {t->tau_g1, t->tau_g2, t->alpha_tau_g1, t->beta_tau_g1};
+  static const size_t min_len[4] = {2, 2, 1, 1};
+  for (int v = 0; v < 4; v++)
+    if (bases_group(vec[v]) != (v == 1 ? BH_G2 : BH_G1) || bh_bases_len(vec[v]) < min_len[v]) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+
+  if (flags & BH_PTAU_VALIDATE_POINTS)
+    for (int v = 0; v < 4; v++) {
+      size_t bad = 0;
+      const int rc = bh_bases_validate(ctx, vec[v], 0, bh_bases_len(vec[v]), BH_POINTS_CHECKED | BH_POINTS_FORBID_IDENTITY,
+                                       nullptr, &bad);
+      if (rc == BH_ERR_INVALID_POINT || rc == BH_ERR_POINT_AT_INFINITY) {
+        rep.failed = BH_PTAU_FAILED_POINTS;
+        rep.bad_vector = (uint32_t)v;
+        rep.bad_index = bad;
+      }
+      if (rc) return rc;
+    }
+
+  OwnStream own(ctx);
+  if (!own.st) return BH_ERR_HIP;
+  hipStream_t st = own.get();
+  // the head points: g1, s1 = T[0], T[1]; g2, s2 = U[0], U[1]; A[0]; B[0]; beta_g2
+  Affine<FpOps> g1, s1, a0, b0;
+  Affine<Fp2Ops> g2, s2, beta2;
+  {
+    char *stage = (char *)ctx->c.pool.acquire(4 * 96 + 2 * 192);
+    if (!stage) return BH_ERR_HIP;
+    int rc = bh_bases_copy_out_dev(ctx, vec[0], BH_G1, 0, 2, stage, st);
+    if (!rc) rc = bh_bases_copy_out_dev(ctx, vec[2], BH_G1, 0, 1, stage + 192, st);
+    if (!rc) rc = bh_bases_copy_out_dev(ctx, vec[3], BH_G1, 0, 1, stage + 288, st);
+    if (!rc) rc = bh_bases_copy_out_dev(ctx, vec[1], BH_G2, 0, 2, stage + 384, st);
+    unsigned char h[4 * 96 + 2 * 192];
+    if (!rc && hipMemcpyAsync(h, stage, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
+    ctx->c.pool.release(stage);
+    if (rc) return rc;
+    memcpy(&g1, h, 96);
+    memcpy(&s1, h + 96, 96);
+    memcpy(&a0, h + 192, 96);
+    memcpy(&b0, h + 288, 96);
+    memcpy(&g2, h + 384, 192);
+    memcpy(&s2, h + 576, 192);
+    memcpy(&beta2, t->beta_g2, 192);
+  }
+  if (!head_ok(g1) || !head_ok(s1) || !head_ok(a0) || !head_ok(b0) || !head_ok(g2) || !head_ok(s2) || !head_ok(beta2)) {
+    rep.failed = BH_PTAU_FAILED_HEAD;
+    return BH_ERR_INVALID_TRANSCRIPT;
+  }
+
+  alignas(16) unsigned char sums[8][192];
+  int rcs[8];
+  int rc = ptau_sums(ctx, vec, seed32, st, sums, rcs);
+  if (rc) return rc;
+  static const uint32_t vec_bit[4] = {BH_PTAU_FAILED_TAU_G1, BH_PTAU_FAILED_TAU_G2, BH_PTAU_FAILED_ALPHA, BH_PTAU_FAILED_BETA};
+  bool skip_eq[4];
+  for (int v = 0; v < 4; v++) {
+    const bool ident = rcs[2 * v] == BH_ERR_UNEXPECTED_IDENTITY || rcs[2 * v + 1] == BH_ERR_UNEXPECTED_IDENTITY;
+    if (ident) rep.failed |= vec_bit[v];   // no consistent transcript holds an identity
+    skip_eq[v] = ident || bh_bases_len(vec[v]) == 1;   // (one point: no relation to check)
+  }
+
+  // the equations e(X, Y) = e(Z, W) as lanes (X, Y) and (-Z, W)
+  Affine<FpOps> px[6], pz[6];
+  Affine<Fp2Ops> qy[6], qw[6];
+  uint32_t bit[6];
+  size_t m = 0;
+  auto equation = [&](uint32_t b, const Affine<FpOps> &x, const Affine<Fp2Ops> &y, const Affine<FpOps> &z, const Affine<Fp2Ops> &w) {
+    bit[m] = b;
+    px[m] = x;
+    qy[m] = y;
+    neg_g1(pz[m], z);
+    qw[m] = w;
+    m++;
+  };
+  Affine<FpOps> P1[4], Q1[4];   // the G1 sums (index 1 unused)
+  Affine<Fp2Ops> PU, QU;
+  for (int v = 0; v < 4; v++) {
+    if (v == 1) continue;
+    memcpy(&P1[v], sums[2 * v], 96);
+    memcpy(&Q1[v], sums[2 * v + 1], 96);
+  }
+  memcpy(&PU, sums[2], 192);
+  memcpy(&QU, sums[3], 192);
+  equation(BH_PTAU_FAILED_TAU_G1_G2, s1, g2, g1, s2);
+  if (!skip_eq[0]) equation(BH_PTAU_FAILED_TAU_G1, P1[0], s2, Q1[0], g2);
+  if (!skip_eq[1]) equation(BH_PTAU_FAILED_TAU_G2, s1, PU, g1, QU);
+  if (!skip_eq[2]) equation(BH_PTAU_FAILED_ALPHA, P1[2], s2, Q1[2], g2);
+  if (!skip_eq[3]) equation(BH_PTAU_FAILED_BETA, P1[3], s2, Q1[3], g2);
+  equation(BH_PTAU_FAILED_BETA_G2, b0, g2, g1, beta2);
+  Affine<FpOps> p[12];
+  Affine<Fp2Ops> q[12];
+  for (size_t k = 0; k < m; k++) {
+    p[k] = px[k];
+    q[k] = qy[k];
+    p[m + k] = pz[k];
+    q[m + k] = qw[k];
+  }
+  u32 one[6] = {0, 0, 0, 0, 0, 0};
+  bool off = false;
+  rc = pairing_products(ctx, st, p, q, 2 * m, m, one, &off);
+  if (rc) return rc;
+  if (off) return BH_ERR_INVALID_POINT;   // a multiexp over records that are not on the curve (validate the points)
+  for (size_t k = 0; k < m; k++)
+    if (one[k] != 1) rep.failed |= bit[k];
+  return rep.failed ? BH_ERR_INVALID_TRANSCRIPT : BH_OK;
+}
+
+}  // extern "C"

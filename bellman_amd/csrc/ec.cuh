@@ -55,6 +55,19 @@ template <class F>
 BH_HD bool aff_is_identity(const Affine<F> &p) {
   return F::is_zero_canonical(p.x, p.y);
 }
+// y^2 = x^3 + b for an affine Montgomery record that is not the identity (the verifier's point tests, the validation of
+// resident records, the head points of a transcript: host and device)
+template <class F>
+BH_HD bool on_curve(const Affine<F> &p) {
+  typedef typename F::T T;
+  T lhs, rhs, b;
+  F::sqr(lhs, p.y);
+  F::sqr(rhs, p.x);
+  F::mul(rhs, rhs, p.x);
+  F::curve_b(b);
+  F::add(rhs, rhs, b);
+  return F::eq(lhs, rhs);
+}
 template <class F>
 BH_HD void xyzz_set_identity(XYZZ<F> &p) {
   F::zero(p.x);

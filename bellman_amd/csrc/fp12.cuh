@@ -32,6 +32,11 @@ struct alignas(16) line_t {
   fp2_t l0, l2, l3;
 };
 static constexpr u64 BLS_X_ABS = 0xd201000000010000ull;   // |x|; x < 0
+// what the verifier's launch functions (pairing_kernels.cuh) share with the units that only declare them (ceremony.hip):
+// the flag bits launch_g2_lines writes per G2 point, and the most pairs one call takes (bounds the workspace: 19.6 KB of
+// lines per pair)
+static constexpr u32 PF_IDENTITY = 1u, PF_OFF_CURVE = 2u;
+static constexpr size_t BATCH_CHUNK = 16384;
 static constexpr int MILLER_LINES = 68;                    // 63 doubling + 5 addition steps
 
 // Frobenius constants in Montgomery form (R = 2^384): FROB1[i-1] = xi^(i (p - 1) / 6) (Fp2, c0 then c1),

@@ -164,6 +164,8 @@ struct ReadLayout {
 };
 int points_read_compressed(int group, const void *raw_dev, void *out_dev, u64 n, const ReadLayout &lay, bool checked,
                            u32 *status_dev, hipStream_t st);
+// status words (PT_IS_INF; with `checked` PT_RANGE, PT_OFF_CURVE, PT_NOT_IN_SUBGROUP) of n resident affine records
+int points_validate(int group, const void *pts_dev, u64 n, bool checked, u32 *status_dev, hipStream_t st);
 int proofs_read_dev(const void *bytes_dev, void *proofs_out_dev, u64 n, u32 *pst, u32 *words, unsigned long long *min_idx,
                     hipStream_t st);
 // the error a sequential reader reports for a proof with this status word: the first bad element in the order a, b, c

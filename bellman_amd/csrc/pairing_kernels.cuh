@@ -14,21 +14,9 @@
 
 namespace bh {
 
-static constexpr u32 PF_IDENTITY = 1u, PF_OFF_CURVE = 2u;
-static constexpr size_t BATCH_CHUNK = 16384;
+// (PF_IDENTITY, PF_OFF_CURVE and BATCH_CHUNK: fp12.cuh, shared with ceremony.hip; on_curve: ec.cuh)
 static constexpr size_t INPUTS_CHUNK_BYTES = size_t(256) << 20;
 
-template <class F>
-BH_HD bool on_curve(const Affine<F> &p) {
-  typedef typename F::T T;
-  T lhs, rhs, b;
-  F::sqr(lhs, p.y);
-  F::sqr(rhs, p.x);
-  F::mul(rhs, rhs, p.x);
-  F::curve_b(b);
-  F::add(rhs, rhs, b);
-  return F::eq(lhs, rhs);
-}
 // a 32-byte scalar in the format of bh_msm_async, as a canonical 256-bit integer (a value >= q is used as is: the points
 // it multiplies have order q)
 BH_HD void scalar_bits(fr_t &k, const fr_t &s, int fmt) {
@@ -346,6 +334,14 @@ int launch_fold(hipStream_t st, fp12_t *f, size_t m) {
     BH_HIP_CHECK(hipGetLastError());
     m = h;
   }
+  return BH_OK;
+}
+// m products of two factors each, laid out as two rows: f[i] *= f[m + i] for i < m (one launch)
+int launch_fold_rows(hipStream_t st, fp12_t *f, size_t m) {
+  if (!m) return BH_OK;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(f12_fold_kernel, dim3(blocks_of(m, 64)), dim3(64), 0, st, f, (u32)(2 * m), (u32)m);
+  BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
 // f^(3 (p^12 - 1) / q) (canonical) and its test against 1, for n values; ws: 4 n Fp12

@@ -137,6 +137,12 @@ __device__ __forceinline__ bool in_subgroup(const Affine<Fp2Ops> &p, G1Slot &) {
   return equals_neg<Fp2Ops>(ex, ey, q);
 }
 
+// every coordinate of a resident record is a canonical value (< p)
+__device__ __forceinline__ bool coords_in_range(const Affine<FpOps> &p) { return fp_in_range(p.x) && fp_in_range(p.y); }
+__device__ __forceinline__ bool coords_in_range(const Affine<Fp2Ops> &p) {
+  return fp_in_range(p.x.c0) && fp_in_range(p.x.c1) && fp_in_range(p.y.c0) && fp_in_range(p.y.c1);
+}
+
 // ---- the kernel --------------------------------------------------------------------------------------------------------
 // Lane i reads point e = i % per of group g = i / per: the `per` points of one group (a proof's A and C; 1 for a plain
 // vector) sit in_step / out_step / st_step apart, groups in_stride / out_stride / st_stride apart.  Offsets in bytes
@@ -190,6 +196,43 @@ __global__ void __launch_bounds__(64, F::WORDS == 12 ? 2 : 1)
     *rec = zero;
   }
   status[g * lay.st_stride + lay.st_first + e * lay.st_step] = st;
+}
+
+// ---- validation of records already resident (bh_bases_validate) --------------------------------------------------------
+// One lane per affine Montgomery record: the identity (the all-zero record) is PT_IS_INF; with `checked` every other record
+// must hold coordinates < p (PT_RANGE), satisfy y^2 = x^3 + b (PT_OFF_CURVE) and pass the endomorphism subgroup test above
+// (PT_NOT_IN_SUBGROUP).  Same launch bounds and LDS parking as the compressed reader; a lane whose record is the identity
+// or already invalid is masked off during the multiplications.  Nothing is written but the status word.
+template <class F>
+__global__ void __launch_bounds__(64, F::WORDS == 12 ? 2 : 1)
+    validate_kernel(const Affine<F> *pts, u64 n, u32 checked, u32 *status) {
+  __shared__ G1Slot slots[F::WORDS == 12 ? 64 : 1];   // G1 only, see in_subgroup
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<F> p = pts[i];
+  u32 st = 0;
+  if (aff_is_identity(p)) {
+    st = PT_IS_INF;
+  } else if (checked) {
+    if (!coords_in_range(p)) st = PT_RANGE;
+    else if (!on_curve(p)) st = PT_OFF_CURVE;
+    else if (!in_subgroup(p, slots[F::WORDS == 12 ? threadIdx.x : 0])) st = PT_NOT_IN_SUBGROUP;
+  }
+  status[i] = st;
+}
+
+int points_validate(int group, const void *pts_dev, u64 n, bool checked, u32 *status_dev, hipStream_t st) {
+  if (!n) return BH_OK;
+  const u32 blocks = (u32)((n + 63) / 64);
+  (void)hipGetLastError();
+  if (group == BH_G1)
+    hipLaunchKernelGGL(validate_kernel<FpOps>, dim3(blocks), dim3(64), 0, st, (const Affine<FpOps> *)pts_dev, n,
+                       checked ? 1u : 0u, status_dev);
+  else
+    hipLaunchKernelGGL(validate_kernel<Fp2Ops>, dim3(blocks), dim3(64), 0, st, (const Affine<Fp2Ops> *)pts_dev, n,
+                       checked ? 1u : 0u, status_dev);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
 }
 
 // a proof's status word from the PointStatus bits of its three points (a | b << 8 | c << 16), and the first bad proof

@@ -35,6 +35,15 @@ class PointAtInfinity(InvalidData):
     """"point at infinity": a query or ic point is the identity"""
 
 
+class InvalidTranscript(Exception):
+    """bh_powers_of_tau_verify: the transcript's vectors are not consistent powers of one (tau, alpha, beta).  `.report` is
+    the ceremony.PtauReport of the call: `.failed` holds the BH_PTAU_FAILED_* bits of the equations that do not hold."""
+
+    def __init__(self, report=None):
+        super().__init__("inconsistent powers-of-tau transcript (failed = 0x%02x)" % (report.failed if report is not None else 0))
+        self.report = report
+
+
 class BellmanHipError(RuntimeError):
     """HIP runtime failure / missing device: never silently replaced by a CPU path."""
 
@@ -54,6 +63,8 @@ def check(rc, what="bellman_hip call"):
         raise InvalidPoint("invalid G1/G2")
     if rc == 7:
         raise PointAtInfinity("point at infinity")
+    if rc == 10:
+        raise InvalidTranscript()
     if rc == -2:
         # the reference panics here (assert!), e.g. src/multiexp.rs:324-329, src/domain.rs:155,174
         raise AssertionError("%s: invalid argument (the reference panics)" % what)

@@ -162,6 +162,26 @@ class Bases:
               "bases_download")
         return out
 
+    def validate(self, first=0, count=None, checked=True, forbid_identity=False, return_status=False):
+        """Curve and subgroup tests over records [first, first + count) as they sit in HBM (bh_bases_validate): with
+        `checked` every record that is not the identity must hold coordinates < p, lie on the curve and - by the
+        endomorphism test - in the prime-order subgroup; `forbid_identity` refuses the identity.  Raises InvalidPoint /
+        PointAtInfinity carrying `.index` = the first offending record relative to `first` (and `.status` when asked
+        for).  return_status=True returns the status words ([count] uint32: 0x04 coordinate >= p, 0x10 identity, 0x20 off
+        the curve, 0x40 not in the subgroup)."""
+        count = self.n - first if count is None else count
+        st = np.zeros(count, dtype=np.uint32) if return_status else None
+        bad = ctypes.c_size_t(0)
+        flags = (1 if checked else 0) | (2 if forbid_identity else 0)
+        try:
+            check(_lib.load().bh_bases_validate(self.worker.ctx, self._h, first, count, flags,
+                                                st.ctypes.data_as(ctypes.c_void_p) if return_status else None, ctypes.byref(bad)),
+                  "bases_validate")
+        except IOError as e:
+            e.index, e.status = bad.value, st
+            raise
+        return st
+
     @classmethod
     def wrap_device(cls, worker, group, dev_ptr, n):
         """A LIVE view of a device array of packed records (not owned, nothing snapshotted: no window table unless

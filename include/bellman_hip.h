@@ -38,6 +38,7 @@ extern "C" {
 #define BH_ERR_POINT_AT_INFINITY 7   /* io::ErrorKind::InvalidData "point at infinity"         groth16/src/lib.rs:306-315,332-341 */
 #define BH_ERR_INVALID_VERIFYING_KEY 8 /* VerificationError::InvalidVerifyingKey  src/lib.rs:353-358 */
 #define BH_ERR_INVALID_PROOF 9       /* VerificationError::InvalidProof           src/lib.rs:353-358 */
+#define BH_ERR_INVALID_TRANSCRIPT 10  /* bh_powers_of_tau_verify: a consistency equation of the transcript fails (no reference twin) */
 #define BH_ERR_HIP (-1)              /* HIP runtime failure (message on stderr) */
 #define BH_ERR_INVALID_ARG (-2)      /* the reference would panic (e.g. density length mismatch,
                                         src/multiexp.rs:324-329; length mismatch src/domain.rs:155,174) */
@@ -205,6 +206,19 @@ int bh_bases_read_uncompressed(bh_ctx *ctx, int group, const void *host_bytes, s
  * the prime-order-subgroup test (by endomorphism: csrc/point_read.hip); without it the call is from_compressed_unchecked. */
 int bh_bases_read_compressed(bh_ctx *ctx, int group, const void *host_bytes, size_t n, unsigned flags,
                              bh_bases **out, size_t *bad_index);
+/* The same tests for records that are ALREADY RESIDENT: [first, first + count) of any handle - one made by
+ * bh_bases_copy_dev / bh_bases_wrap_dev, by a point transform or a contribution step included.  flags as above: without
+ * BH_POINTS_CHECKED only the identity rule (BH_POINTS_FORBID_IDENTITY) is applied; with it every record that is not the
+ * identity (the all-zero record) must hold coordinates < p, satisfy y^2 = x^3 + b and lie in the prime-order subgroup - by
+ * endomorphism (csrc/point_read.hip: two multiplications by the 64-bit |z| for G1, one for G2) instead of the [q] P test
+ * of bh_bases_read_uncompressed.  Returns BH_OK, BH_ERR_INVALID_POINT or BH_ERR_POINT_AT_INFINITY; *bad_index (optional)
+ * is the first offending record in order, relative to `first` - the rule of the readers.  status_host (optional, `count`
+ * words, written for every record whatever the return code) receives the PointStatus bits of csrc/msm_types.hpp:
+ * 0x04 a coordinate >= p, 0x10 identity, 0x20 off the curve, 0x40 not in the subgroup.  A range beyond the handle is
+ * BH_ERR_INVALID_ARG, count = 0 is BH_OK.  Runs in chunks of 2^20 records (4 MB of status workspace) on a stream of its
+ * own: thread-safe.  A wrapped handle is read as it is when the call runs. */
+int bh_bases_validate(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, unsigned flags, uint32_t *status_host,
+                      size_t *bad_index);
 /* copies `count` device-resident affine records (Montgomery) starting at `first` back to the host */
 int bh_bases_download(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, void *out_host);
 /* the same range in the uncompressed encoding Parameters::write emits (groth16/src/lib.rs:258-287; 96 / 192 bytes per
@@ -576,9 +590,9 @@ typedef struct {
  * sets delta.  Identities are dropped from a, b_g1, b_g2 and an identity in l is BH_ERR_UNCONSTRAINED_VARIABLE, as there.
  * BH_ERR_INVALID_ARG for a null or wrong-group handle, BH_ERR_DEGREE_TOO_LARGE when a vector is too short.
  * THIS CALL VALIDATES NOTHING: neither that the points are on their curves and in the prime-order subgroups - read the
- * transcript with bh_bases_read_uncompressed / _compressed and BH_POINTS_CHECKED for that - nor that the four vectors
- * and beta_g2 are consistent powers of one (tau, alpha, beta), which takes pairings and is the ceremony verifier's
- * job.  Runs on a stream of its own: thread-safe and concurrent with other work on the context. */
+ * transcript with bh_bases_read_uncompressed / _compressed and BH_POINTS_CHECKED, or run bh_bases_validate over the
+ * handles, for that - nor that the four vectors and beta_g2 are consistent powers of one (tau, alpha, beta), which takes
+ * pairings: bh_powers_of_tau_verify below makes both checks.  Runs on a stream of its own: thread-safe and concurrent with other work on the context. */
 int bh_groth16_generate_from_powers_of_tau(bh_ctx *ctx, bh_r1cs *r1cs, const bh_powers_of_tau *t, bh_params **out);
 /* New parameters with delta multiplied by d (32-byte Montgomery Fr on the host): delta_g1 and delta_g2 are multiplied by d,
  * every point of h and l by 1/d (on the device; the new queries are registered like any other, so they get window
@@ -586,6 +600,51 @@ int bh_groth16_generate_from_powers_of_tau(bh_ctx *ctx, bh_r1cs *r1cs, const bh_
  * Applied to the delta = 1 output of the call above it gives generate(alpha, beta, 1, d, tau); applied repeatedly it is
  * one contributor's step of a circuit-specific ceremony (the contribution proofs are the caller's business). */
 int bh_groth16_params_rescale_delta(const bh_params *p, const void *d_mont, bh_params **out);
+/* ---- checking a transcript before deriving parameters from it -----------------------------------------------------------
+ * bh_pairing_product_is_one: *is_one = (prod_i e(P_i, Q_i) == 1) over n pairs of affine records on the host (96 B / 192 B
+ * each): the lines of every Q_i, one Miller lane per pair, the product, one final exponentiation - the verifier's kernels.
+ * A pair with the identity on either side contributes 1; n = 0 gives 1.  A point off its curve is BH_ERR_INVALID_POINT, n
+ * above 16384 BH_ERR_INVALID_ARG.  Subgroup membership stays with the caller, as for bh_groth16_verify.  Thread-safe (a
+ * stream of its own).  The primitive of the transcript check below; a ceremony verifier checks contribution proofs with it. */
+int bh_pairing_product_is_one(bh_ctx *ctx, const void *g1_affine_host, const void *g2_affine_host, size_t n, int *is_one);
+/* bh_powers_of_tau_verify: are the four vectors and beta_g2 powers of ONE (tau, alpha, beta)?  With T = tau_g1 (at least 2
+ * points), U = tau_g2 (at least 2), A = alpha_tau_g1, B = beta_tau_g1 (at least 1 each; a shorter vector is
+ * BH_ERR_INVALID_ARG; the WHOLE length of every handle is checked), g1 = T[0], s1 = T[1], g2 = U[0], s2 = U[1], and for a
+ * vector V of n points P(V) = sum_{i<n-1} rho_i V[i], Q(V) = sum_{i<n-1} rho_i V[i+1] (two multiexps over the same
+ * coefficients, skip 0 and 1), the bits of report->failed are
+ *   HEAD       one of g1, s1, g2, s2, A[0], B[0], beta_g2 is the identity or off its curve; nothing else is evaluated
+ *   TAU_G1_G2  e(s1, g2) != e(g1, s2)                 TAU_G1   e(P(T), s2) != e(Q(T), g2)
+ *   TAU_G2     e(s1, P(U)) != e(g1, Q(U))             ALPHA    e(P(A), s2) != e(Q(A), g2)   (vacuous for one point)
+ *   BETA       the same for B                         BETA_G2  e(B[0], g2) != e(g1, beta_g2)
+ *   POINTS     only with BH_PTAU_VALIDATE_POINTS in flags: the four vectors first go through bh_bases_validate with
+ *              CHECKED | FORBID_IDENTITY; the first failure in the order T, U, A, B ends the call with bad_vector (0..3),
+ *              bad_index and the return code BH_ERR_INVALID_POINT / BH_ERR_POINT_AT_INFINITY.
+ * A multiexp that meets an identity (BH_ERR_UNEXPECTED_IDENTITY) sets its vector's bit: no consistent transcript holds
+ * one.  Returns BH_OK when failed == 0, BH_ERR_INVALID_TRANSCRIPT when an equation bit (or HEAD) is set, otherwise the
+ * usual call-level codes; without BH_PTAU_VALIDATE_POINTS a sum over records that are not on the curve can surface as
+ * BH_ERR_INVALID_POINT.  report may be NULL.
+ * The coefficients rho are expanded on the device from seed32 (csrc/ptau_rlc.cuh: BLAKE2s keyed with the seed, 128 bits
+ * per coefficient).  THE SEED MUST BE CHOSEN AFTER THE TRANSCRIPT IS FIXED, AND FROM A CSPRNG: whoever knows it beforehand
+ * can build an inconsistent transcript that passes - the counterpart of the z_j rule of bh_groth16_batch_verify.
+ * The eight multiexps run together as ordinary jobs with the default plans (a window table is used where a handle has one;
+ * none is built), all equations in one Miller launch.  Thread-safe and concurrent with other work on the context.
+ * NOT COVERED: a proof of knowledge of the contributors' secrets (contribution proofs), tau being a root of unity of the
+ * domain (such a transcript passes and gives unusable parameters), and the parsing of any ceremony's file format. */
+#define BH_PTAU_VALIDATE_POINTS 1u
+#define BH_PTAU_FAILED_HEAD 0x01u
+#define BH_PTAU_FAILED_TAU_G1_G2 0x02u
+#define BH_PTAU_FAILED_TAU_G1 0x04u
+#define BH_PTAU_FAILED_TAU_G2 0x08u
+#define BH_PTAU_FAILED_ALPHA 0x10u
+#define BH_PTAU_FAILED_BETA 0x20u
+#define BH_PTAU_FAILED_BETA_G2 0x40u
+#define BH_PTAU_FAILED_POINTS 0x80u
+typedef struct {
+  uint32_t failed;
+  uint32_t bad_vector;
+  size_t bad_index;
+} bh_ptau_report;
+int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *seed32, unsigned flags, bh_ptau_report *report);
 /* create_proof (prover.rs:217-360) from the witness alone: input_assignment (n_inputs, [0] = 1) and
  * aux_assignment (n_aux) as produced by the circuit's alloc closures; lengths must match the R1CS. */
 int bh_groth16_prove_witness(bh_params *params, const bh_r1cs *r1cs, const void *input_assignment,

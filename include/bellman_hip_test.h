@@ -298,6 +298,16 @@ int bh_test_pairing_verdict_dev(bh_ctx *ctx, const uint32_t *words, const uint32
                                 const uint32_t *is_one, size_t n, int32_t *verdicts_out, uint32_t guards[5]);
 int bh_test_pairing_final_exp_dev(bh_ctx *ctx, const void *f, size_t n, void *out, uint32_t *is_one_out, uint32_t guards[4]);
 
+/* ---- the powers-of-tau check (csrc/ptau_rlc.cuh, compiled into this library by csrc/test_ceremony_hooks.hip) -----------
+ * bh_test_ptau_rlc_host / _dev: the `count` coefficients of vector v (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1)
+ * expanded from seed32, count x 32 bytes to out_host - by the host build of the expander (no GPU) and by its kernel.
+ * bh_test_ptau_sums: the eight sums P(V), Q(V) of a transcript as affine records - sums_out[k] (192 bytes each; a G1 record
+ * fills the first 96) for k = 2 v + (0 for P, 1 for Q), rcs_out[k] the code of that multiexp; exactly the function
+ * bh_powers_of_tau_verify calls. */
+void bh_test_ptau_rlc_host(const void *seed32, uint32_t v, size_t count, void *out_host);
+int bh_test_ptau_rlc_dev(bh_ctx *ctx, const void *seed32, uint32_t v, size_t count, void *out_host);
+int bh_test_ptau_sums(bh_ctx *ctx, const bh_powers_of_tau *t, const void *seed32, void *sums_out, int *rcs_out);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,

@@ -92,6 +92,14 @@ pub struct BhPowersOfTau {
     pub beta_tau_g1: *const BhBases,
     pub beta_g2: *const c_void,
 }
+/// `bh_ptau_report`: what bh_powers_of_tau_verify found (the BH_PTAU_FAILED_* bits; the first bad point)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhPtauReport {
+    pub failed: u32,
+    pub bad_vector: u32,
+    pub bad_index: usize,
+}
 
 pub const BH_OK: c_int = 0;
 pub const BH_ERR_UNEXPECTED_IDENTITY: c_int = 1;
@@ -100,6 +108,7 @@ pub const BH_ERR_DEGREE_TOO_LARGE: c_int = 3;
 pub const BH_ERR_UNCONSTRAINED_VARIABLE: c_int = 5;
 pub const BH_ERR_INVALID_POINT: c_int = 6;
 pub const BH_ERR_POINT_AT_INFINITY: c_int = 7;
+pub const BH_ERR_INVALID_TRANSCRIPT: c_int = 10;
 pub const BH_ERR_HIP: c_int = -1;
 pub const BH_ERR_INVALID_ARG: c_int = -2;
 pub const BH_ERR_NO_DEVICE: c_int = -3;
@@ -113,6 +122,15 @@ pub const BH_COSET_FFT: c_int = 2;
 pub const BH_ICOSET_FFT: c_int = 3;
 pub const BH_POINTS_CHECKED: c_uint = 1;
 pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;
+pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;
+pub const BH_PTAU_FAILED_HEAD: u32 = 0x01;
+pub const BH_PTAU_FAILED_TAU_G1_G2: u32 = 0x02;
+pub const BH_PTAU_FAILED_TAU_G1: u32 = 0x04;
+pub const BH_PTAU_FAILED_TAU_G2: u32 = 0x08;
+pub const BH_PTAU_FAILED_ALPHA: u32 = 0x10;
+pub const BH_PTAU_FAILED_BETA: u32 = 0x20;
+pub const BH_PTAU_FAILED_BETA_G2: u32 = 0x40;
+pub const BH_PTAU_FAILED_POINTS: u32 = 0x80;
 pub const BH_MSM_SUMS_BYTES: usize = 960;
 
 #[link(name = "bellman_hip")]
@@ -156,6 +174,7 @@ extern "C" {
     pub fn bh_bases_register_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, out: *mut *mut BhBases) -> c_int;
     pub fn bh_bases_read_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, flags: c_uint, out: *mut *mut BhBases, bad_index: *mut usize) -> c_int;
     pub fn bh_bases_read_compressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, flags: c_uint, out: *mut *mut BhBases, bad_index: *mut usize) -> c_int;
+    pub fn bh_bases_validate(ctx: *mut BhCtx, b: *const BhBases, first: usize, count: usize, flags: c_uint, status_host: *mut u32, bad_index: *mut usize) -> c_int;
     pub fn bh_bases_download(ctx: *mut BhCtx, b: *const BhBases, first: usize, count: usize, out_host: *mut c_void) -> c_int;
     pub fn bh_bases_write_uncompressed(ctx: *mut BhCtx, bases: *const BhBases, first: usize, count: usize, out_host_bytes: *mut c_void) -> c_int;
     pub fn bh_bases_precompute(ctx: *mut BhCtx, b: *mut BhBases, window_bits: c_uint) -> c_int;
@@ -221,6 +240,8 @@ extern "C" {
     pub fn bh_r1cs_eval_transposed_points_dev(ctx: *mut BhCtx, r: *mut BhR1cs, group: c_int, matrix: c_int, lagrange_points_dev: *const c_void, out_points_dev: *mut c_void, accumulate: c_int, stream: *mut c_void) -> c_int;
     pub fn bh_groth16_generate_from_powers_of_tau(ctx: *mut BhCtx, r1cs: *mut BhR1cs, t: *const BhPowersOfTau, out: *mut *mut BhParams) -> c_int;
     pub fn bh_groth16_params_rescale_delta(p: *const BhParams, d_mont: *const c_void, out: *mut *mut BhParams) -> c_int;
+    pub fn bh_pairing_product_is_one(ctx: *mut BhCtx, g1_affine_host: *const c_void, g2_affine_host: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
+    pub fn bh_powers_of_tau_verify(ctx: *mut BhCtx, t: *const BhPowersOfTau, seed32: *const c_void, flags: c_uint, report: *mut BhPtauReport) -> c_int;
     pub fn bh_groth16_prove_witness(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_assignment_async(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_prove_witness_async(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;

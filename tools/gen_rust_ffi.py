@@ -15,7 +15,7 @@ OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "b
           "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
           "bh_pvk": "BhPvk"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo",
-           "bh_powers_of_tau": "BhPowersOfTau"}
+           "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport"}
 SCALAR = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "uint32_t": "u32", "uint64_t": "u64",
     "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char", "void": "c_void",
@@ -111,17 +111,24 @@ def render(decls):
         "#[repr(C)]", "#[derive(Clone, Copy)]",
         "pub struct BhPowersOfTau {", "    pub tau_g1: *const BhBases,", "    pub tau_g2: *const BhBases,",
         "    pub alpha_tau_g1: *const BhBases,", "    pub beta_tau_g1: *const BhBases,", "    pub beta_g2: *const c_void,", "}",
+        "/// `bh_ptau_report`: what bh_powers_of_tau_verify found (the BH_PTAU_FAILED_* bits; the first bad point)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhPtauReport {", "    pub failed: u32,", "    pub bad_vector: u32,", "    pub bad_index: usize,", "}",
         "",
     ]
     consts = [("BH_OK", 0), ("BH_ERR_UNEXPECTED_IDENTITY", 1), ("BH_ERR_UNEXPECTED_EOF", 2), ("BH_ERR_DEGREE_TOO_LARGE", 3),
               ("BH_ERR_UNCONSTRAINED_VARIABLE", 5), ("BH_ERR_INVALID_POINT", 6), ("BH_ERR_POINT_AT_INFINITY", 7),
-              ("BH_ERR_HIP", -1), ("BH_ERR_INVALID_ARG", -2), ("BH_ERR_NO_DEVICE", -3), ("BH_SCALARS_CANONICAL", 0),
+              ("BH_ERR_INVALID_TRANSCRIPT", 10), ("BH_ERR_HIP", -1), ("BH_ERR_INVALID_ARG", -2), ("BH_ERR_NO_DEVICE", -3), ("BH_SCALARS_CANONICAL", 0),
               ("BH_SCALARS_MONT", 1), ("BH_G1", 1), ("BH_G2", 2), ("BH_FFT", 0), ("BH_IFFT", 1), ("BH_COSET_FFT", 2),
               ("BH_ICOSET_FFT", 3)]
     for k, v in consts:
         lines.append("pub const %s: c_int = %d;" % (k, v))
     lines += ["pub const BH_POINTS_CHECKED: c_uint = 1;", "pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;",
-              "pub const BH_MSM_SUMS_BYTES: usize = 960;", "", "#[link(name = \"bellman_hip\")]", "extern \"C\" {"]
+              "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;"]
+    lines += ["pub const %s: u32 = 0x%02x;" % (k, v) for k, v in
+              (("BH_PTAU_FAILED_HEAD", 1), ("BH_PTAU_FAILED_TAU_G1_G2", 2), ("BH_PTAU_FAILED_TAU_G1", 4), ("BH_PTAU_FAILED_TAU_G2", 8),
+               ("BH_PTAU_FAILED_ALPHA", 16), ("BH_PTAU_FAILED_BETA", 32), ("BH_PTAU_FAILED_BETA_G2", 64), ("BH_PTAU_FAILED_POINTS", 128))]
+    lines += ["pub const BH_MSM_SUMS_BYTES: usize = 960;", "", "#[link(name = \"bellman_hip\")]", "extern \"C\" {"]
     for name, params, ret in decls:
         ps = ", ".join("%s: %s" % (("r#" + p) if p in RUST_KEYWORDS else p, t) for p, t in params)
         lines.append("    pub fn %s(%s)%s;" % (name, ps, (" -> " + ret) if ret else ""))
