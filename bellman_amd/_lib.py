@@ -56,6 +56,7 @@ TEST_EXPORTS = [
     "bh_test_field_ops_shape", "bh_test_field_ops_dev", "bh_test_field_ops_host",
     "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev", "bh_test_g1_madd_sliced_dev", "bh_test_g1_madd_sliced_host",
     "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev",
+    "bh_test_reduce_plan", "bh_test_reduce_stage_dev", "bh_test_msm_host_tail",
     "bh_test_sort_plan", "bh_test_scan_dev", "bh_test_sort_stage_dev",
     "bh_test_pairing_stage_shape", "bh_test_proof_status_error", "bh_test_pairing_lines_dev", "bh_test_pairing_miller_dev", "bh_test_pairing_fold_dev",
     "bh_test_pairing_proof_prep_dev", "bh_test_pairing_g1_mul_one_dev", "bh_test_pairing_colsum_dev", "bh_test_pairing_ic_table_dev",
@@ -295,6 +296,9 @@ def load():
     lib.bh_test_g2_k6_dev.argtypes = [vp, vp, vp, vp, sz]
     lib.bh_test_g1_madd_sliced_dev.argtypes = [vp, vp, vp, vp, vp, sz]
     lib.bh_test_g1_madd_sliced_host.argtypes = [vp, vp, vp, vp, sz]
+    lib.bh_test_reduce_plan.argtypes = [vp, i32, i32, c.c_uint, i32, vp, vp, sz, c.POINTER(sz)]
+    lib.bh_test_reduce_stage_dev.argtypes = [vp, i32, i32, c.c_uint, i32, vp, vp, vp, vp, vp, vp]
+    lib.bh_test_msm_host_tail.argtypes = [i32, i32, c.c_uint, vp, vp]
     for name in ("bh_test_fr_mul_host", "bh_test_fp_mul_host", "bh_test_fr_mul_bform_host"):
         getattr(lib, name).argtypes = [vp, vp, vp, sz]
         getattr(lib, name).restype = None

@@ -1226,6 +1226,186 @@ static int launch_merges(hipStream_t st, const MsmPlan &p, const MergePlan &mp, 
   return BH_OK;
 }
 
+// 5. reduce: what msm_enqueue carves for it and what it launches (also run on their own by csrc/test_reduce_hooks.hip)
+struct ReducePlan {
+  u32 two_len;      // elements per piece of the two-stage row / column sums
+  bool want_part;   // ... which this plan takes
+  u64 rowcol_elems, part_elems, bits_elems;   // records of `rowcol` ([W][H] row sums, [W][Lw] column sums), `part`, `bits`
+};
+template <class FR>
+static ReducePlan reduce_plan(const MsmPlan &p, int num_cus) {
+  constexpr bool G2 = (FR::Mem::WORDS == 24);
+  const u32 H = 1u << p.hi_bits, Lw = 1u << p.lo_bits;
+  ReducePlan rp;
+  // [r6] piece sums of the two-stage row / column sums (G1, 2^17 ... 2^21 buckets; below): pieces of `two_len` elements - the
+  // launch of 2 NB / two_len lane pairs is then two wavefronts per SIMD (four with one lane per point and half the length)
+  // [r6] the same for G2 sets reduced on lane triples (the 2^19 buckets of a 20-bit table): 16 workers per wavefront
+  constexpr bool TWO_STAGE_FR = std::is_same<FR, FpOps>::value || std::is_same<FR, Fp2K3Ops>::value;
+  u32 two_len = 16;
+  if (TWO_STAGE_FR) {
+    const u64 target = (u64)num_cus * 4 * 2 * (G2 ? 16 : 32);
+    two_len = 4;
+    while (two_len < 64 && 2ull * p.NB / two_len > target) two_len <<= 1;
+  }
+  rp.two_len = two_len;
+  rp.want_part = TWO_STAGE_FR && p.NB >= (1u << 17) && p.NB <= (1u << 21) && Lw >= 32 && H >= 32;
+  rp.rowcol_elems = (u64)p.W * (H + Lw);
+  rp.part_elems = rp.want_part ? (u64)p.W * ((u64)H * (Lw / std::min(two_len, Lw)) + (u64)Lw * (H / std::min(two_len, H))) : 0;
+  rp.bits_elems = (u64)p.W * p.c;   // per window: (c-1) bit sums U[w][p], then W plain totals T[w]
+  return rp;
+}
+// where launch_reduce sends its launches: production launches them; the plan query of the tests records them instead
+struct SumLaunchSink {
+  template <class WK, u32 NWAVES>
+  bool launch(SumJobs<typename WK::Mem> js, hipStream_t st) { return sum_launch<WK, NWAVES>(js, st); }
+};
+// rows (sum over lo, contiguous), columns (sum over hi, stride Lw), then bits.
+// G workers per output chosen so that each launch is about one wavefront per SIMD.
+// pts: NB filled buckets; rowcol, part (null unless rp.want_part), bits (zeroed): rp's element counts
+template <class FR, class Sink>
+static int launch_reduce(hipStream_t st, const MsmPlan &p, const ReducePlan &rp, int num_cus, const XYZZ<typename FR::Mem> *pts,
+                         XYZZ<typename FR::Mem> *rowcol, XYZZ<typename FR::Mem> *part, XYZZ<typename FR::Mem> *bits, Sink &sink) {
+  typedef typename FR::Mem M;
+  typedef XYZZ<M> Pt;
+  constexpr bool G2 = (M::WORDS == 24);
+  const u32 H = 1u << p.hi_bits, Lw = 1u << p.lo_bits;
+  const u32 two_len = rp.two_len;
+  Pt *rows = rowcol, *cols = rowcol + (u64)p.W * H;
+  typedef XyzzWorker<FR> FullWK;   // the launches that fill the chip: one lane (triple) per point
+  constexpr u32 NW = sum_waves<FR>(), PW = NW * FullWK::PER_WAVE;   // workers per workgroup of that kernel: 64
+  // workers per output: minimise (serial adds per worker + tree depth) x (waves per SIMD, at least 1);
+  // these kernels are latency-bound chains of point additions, not throughput-bound.
+  auto pick_lanes = [&](u32 groups, u32 count) {
+    // wavefront slots the launch may fill before a step stretches: ONE resident wavefront per SIMD - a second does not
+    // interleave for free in these mad-bound chains (G1 2^17-2^20 reduce 0.73-0.99 ms modelled with 1, 0.92-1.19 ms with 2; G2
+    // within noise: profiles/archive/r2_call8_slots.txt); a block of lane triples is four wavefronts
+    const double slots = (double)num_cus * 4;
+    u32 best = 1;
+    double best_cost = 1e30;
+    for (u32 g = 1, lg = 0; g <= PW; g <<= 1, lg++) {
+      if (g > count && g > 1) break;
+      // a lane-triple group wider than one wavefront pays two barriers and an LDS round trip (measured: ~2 additions)
+      const double steps = (double)((count + g - 1) / g) + lg + ((FR::LANES == 3 && g > 16) ? 2.0 : 0.0);
+      const double waves = (double)groups * g / (double)PW * (double)NW;
+      const double cost = steps * std::max(1.0, waves / slots);
+      if (cost < best_cost) { best_cost = cost; best = g; }
+    }
+    return best;
+  };
+  auto make_job = [&](const Pt *in, Pt *out, SumDesc d) {
+    SumJob<M> j;
+    d.lanes = d.groups ? pick_lanes(d.groups, d.mode == SUM_BITS ? std::max(1u, d.count / 2) : d.count) : 1;
+    j.in = in; j.out = out; j.d = d;
+    return j;
+  };
+  // Which worker kind a launch runs on; sum_launch counts its workgroups.  G1 launches that leave at least half of the
+  // SIMDs empty run on lane pairs (K2, above): half the latency per addition for twice the lanes.
+  // force: 0 = by the rules below, 1 = lane pairs, 2 = one lane per point (the first stage of a two-stage sum chooses)
+  auto launch_sums = [&](SumJobs<M> js, int force = 0) -> bool {
+    if constexpr (std::is_same<FR, FpOps>::value) {
+      constexpr double K2_SUM_FILL = 4.0;   // wavefronts per SIMD the lane-pair launch may reach
+      // [r6] a handful of long sums (the bit sums and the total of ONE big bucket set): one workgroup of several
+      // wavefronts per output
+      u32 groups_all = 0, max_sel = 0;
+      for (int q = 0; q < 3; q++)
+        if (js.j[q].d.groups) {
+          groups_all += js.j[q].d.groups;
+          max_sel = std::max(max_sel, js.j[q].d.mode == SUM_BITS ? js.j[q].d.count / 2 : js.j[q].d.count / js.j[q].d.splits);
+        }
+      if (force == 0 && max_sel >= 128 && groups_all <= 2u * (u32)num_cus) {
+        // (never more than four wavefronts: a CU has four SIMDs, and the wavefronts of a workgroup that share one take turns -
+        // eight were 198 us for 2 + 5 + 3 levels, profiles/r6_call32_timeline.txt)
+        const bool four = 2 * 64 < max_sel;
+        for (int q = 0; q < 3; q++) js.j[q].d.lanes = (four ? 4 : 2) * K2Worker::PER_WAVE;
+        return four ? sink.template launch<K2Worker, 4>(js, st) : sink.template launch<K2Worker, 2>(js, st);
+      }
+      // (the one-lane launch would be single wavefronts)
+      if (force != 2 && (force == 1 || (double)sum_count<FullWK, NW>(js) * 2 <= K2_SUM_FILL * (double)num_cus * 4))
+        return sink.template launch<K2Worker, 1>(js, st);
+    }
+    if constexpr (std::is_same<FR, Fp2K3Ops>::value) {
+      // G2: the same idea on lane sextets (32 workers per 256-thread block) while the launch stays within one wavefront per SIMD
+      constexpr double K6_SUM_FILL = 8.0;   // blocks per CU the launch may reach
+      SumJobs<M> k6 = js;
+      if (force != 2 && (double)sum_count<K6Worker, 4>(k6) <= K6_SUM_FILL * (double)num_cus) return sink.template launch<K6Worker, 4>(k6, st);
+    }
+    return sink.template launch<FullWK, NW>(js, st);
+  };
+  const u32 cb = p.c - 1;   // bits of a bucket index
+  SumDesc dr, dc;
+  dr.mode = SUM_STRIDED; dr.groups = p.W * H; dr.count = Lw; dr.inner = H; dr.stride = 1; dr.istride = Lw; dr.group_shift = cb;
+  dc = dr; dc.groups = p.W * Lw; dc.count = H; dc.inner = Lw; dc.stride = Lw; dc.istride = 1;
+  SumJobs<M> js;
+  js.j[0] = make_job(pts, rows, dr); js.j[1] = make_job(pts, cols, dc); js.j[2] = js.j[1]; js.j[2].d.groups = 0;
+  // [r6] G1, bucket sets of 2^17 ... 2^21 points (16 windows of 2^15, or the 2^19 buckets of a 20-bit window table): the launch
+  // above gives every output 16-32 lane pairs - 8-16 serial additions, then a 4-5 level tree in which half, a quarter, ...
+  // of the lanes work: 12-13 levels at four wavefronts per SIMD of which 61 % is useful work (0.50 ms for the 2^20 additions
+  // of a 2^20-term multiexp, 0.27 at the multiplier's throughput).  Two stages instead: (1) every output is cut into pieces
+  // of `len` consecutive elements and ONE worker adds up a piece - no tree, every lane busy - sized so that the launch is
+  // two wavefronts per SIMD; (2) the handful of piece sums per output are folded by a small tree launch.
+  if (part) {   // (rp.want_part: the sizes and groups that reduce in two stages)
+    // G1: stage one on lane pairs.  G2 (lane triples): on the lane-triple kernel (16 workers per wavefront; sextets halve
+    // that again and were within noise - reduce 1.89 / 1.96 ms against 1.86 / 1.97 at 2^19 / 2^20, profiles/r6_call42_g2_stage1.txt)
+    const bool one_lane = G2;
+    const u32 len_r = std::min(two_len, Lw), len_c = std::min(two_len, H);
+    const u32 Sr = Lw / len_r, Sc = H / len_c;
+    Pt *part_r = part, *part_c = part + (u64)dr.groups * Sr;
+    SumDesc r1 = dr, c1 = dc;
+    r1.splits = Sr; r1.groups = dr.groups * Sr; r1.lanes = 1;
+    c1.splits = Sc; c1.groups = dc.groups * Sc; c1.lanes = 1;
+    SumJobs<M> s1;
+    s1.j[0].in = pts; s1.j[0].out = Sr > 1 ? part_r : rows; s1.j[0].d = r1;
+    s1.j[1].in = pts; s1.j[1].out = Sc > 1 ? part_c : cols; s1.j[1].d = c1;
+    s1.j[2] = s1.j[1]; s1.j[2].d.groups = 0;
+    if (!launch_sums(s1, one_lane ? 2 : 1)) return BH_ERR_HIP;
+    SumDesc r2, c2;
+    r2.mode = SUM_STRIDED; r2.groups = dr.groups; r2.count = Sr; r2.inner = dr.groups; r2.stride = 1; r2.istride = Sr; r2.group_shift = 0;
+    c2 = r2; c2.groups = dc.groups; c2.count = Sc; c2.inner = dc.groups; c2.istride = Sc;
+    SumJobs<M> s2;
+    s2.j[0] = make_job(part_r, rows, r2); if (Sr <= 1) s2.j[0].d.groups = 0;
+    s2.j[1] = make_job(part_c, cols, c2); if (Sc <= 1) s2.j[1].d.groups = 0;
+    s2.j[2] = s2.j[1]; s2.j[2].d.groups = 0;
+    if (!launch_sums(s2, 1)) return BH_ERR_HIP;
+    js.j[0].d.groups = js.j[1].d.groups = 0;   // (done)
+  }
+  if (G2 && FR::LANES == 1) {
+    // single-lane G2 (one resident wavefront per SIMD, so sharing a SIMD doubles every step): the two jobs share
+    // one launch, choose their lane counts jointly - the launch lasts as long as its longest chain, stretched by
+    // how many wavefronts each SIMD has to interleave.  (With two wavefronts per SIMD - G1, K3-form G2 - they
+    // interleave almost for free and the per-job choice above is better.)
+    const double simds = (double)num_cus * 4;
+    double best = 1e30;
+    u32 best_r = js.j[0].d.lanes, best_c = js.j[1].d.lanes;
+    for (u32 gr = 1, lr = 0; gr <= 64 && gr <= std::max(1u, dr.count); gr <<= 1, lr++)
+      for (u32 gc = 1, lc = 0; gc <= 64 && gc <= std::max(1u, dc.count); gc <<= 1, lc++) {
+        const double steps = std::max((double)((dr.count + gr - 1) / gr) + lr, (double)((dc.count + gc - 1) / gc) + lc);
+        const double waves = ((double)dr.groups * gr + (double)dc.groups * gc) / 64.0;
+        const double cost = steps * std::max(1.0, waves / simds);
+        if (cost < best) { best = cost; best_r = gr; best_c = gc; }
+      }
+    js.j[0].d.lanes = best_r;
+    js.j[1].d.lanes = best_c;
+  }
+  if (!launch_sums(js)) return BH_ERR_HIP;
+  // sum_idx (idx+1) B[idx] = sum_p 2^p U[p] + T, idx = hi*2^l + lo:
+  //   U[w][p], p < lo_bits from the column sums (weights lo), p >= lo_bits from the row sums (weights hi),
+  //   T[w] = plain sum of all buckets = sum of the row sums.
+  SumDesc bl, bh_, bt;
+  bl.mode = SUM_BITS; bl.stride = 1; bl.istride = 0;
+  bl.groups = p.W * p.lo_bits; bl.count = Lw; bl.inner = std::max(1u, p.lo_bits); bl.group_shift = p.lo_bits;
+  bh_ = bl; bh_.groups = p.W * p.hi_bits; bh_.count = H; bh_.inner = std::max(1u, p.hi_bits); bh_.group_shift = p.hi_bits;
+  // the plain total is the sum of the column sums as well as of the row sums: take the shorter vector
+  // (this job is the longest chain of the launch)
+  const bool t_from_cols = Lw < H;
+  bt.mode = SUM_STRIDED; bt.groups = p.W; bt.count = t_from_cols ? Lw : H; bt.inner = 1; bt.stride = 1; bt.istride = 0;
+  bt.group_shift = t_from_cols ? p.lo_bits : p.hi_bits;
+  js.j[0] = make_job(cols, bits, bl);
+  js.j[1] = make_job(rows, bits + (u64)p.W * p.lo_bits, bh_);
+  js.j[2] = make_job(t_from_cols ? cols : rows, bits + (u64)p.W * cb, bt);
+  if (!launch_sums(js)) return BH_ERR_HIP;
+  return BH_OK;
+}
+
 // ============================================================================================
 // host orchestration
 // ============================================================================================
@@ -1261,13 +1441,13 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const u64 nslots = (u64)p.W * p.chunks_per_window;
   const MergePlan mp = merge_plan<FR>(p, c.num_cus);
   const u32 max_long = mp.max_long, max_big = mp.max_big, max_pieces = mp.max_pieces;
-  const u32 H = 1u << p.hi_bits, Lw = 1u << p.lo_bits;
+  const ReducePlan rp = reduce_plan<FR>(p, c.num_cus);
   const u64 nwords = (n + 63) / 64;
   size_t off = 0;
   auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~size_t(255); return at; };
   // zero-initialised region first: status words, the result slots (so that both leave in ONE copy), then the buckets
   // (all-zero XYZZ == identity)
-  const size_t bits_bytes = (size_t)p.W * p.c * sizeof(Pt);   // per window: (c-1) bit sums U[w][p], then W plain totals T[w]
+  const size_t bits_bytes = (size_t)rp.bits_elems * sizeof(Pt);   // per window: (c-1) bit sums U[w][p], then W plain totals T[w]
   const size_t o_err = carve(sizeof(ErrFlags));                // 256-byte slot
   const size_t o_bits = carve(bits_bytes);
   const size_t o_pts = carve((u64)p.NB * sizeof(Pt));
@@ -1277,19 +1457,9 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const size_t o_head = carve(nslots * sizeof(Pt)), o_tail = carve(nslots * sizeof(Pt));
   const size_t o_long = carve((u64)max_long * sizeof(LongRun)), o_big = carve((u64)max_big * sizeof(BigRun));
   const size_t o_pieces = carve((u64)max_pieces * sizeof(Pt));
-  const size_t o_rowcol = carve((u64)p.W * (H + Lw) * sizeof(Pt));
-  // [r6] piece sums of the two-stage row / column sums (G1, 2^17 ... 2^21 buckets; below): pieces of `two_len` elements - the
-  // launch of 2 NB / two_len lane pairs is then two wavefronts per SIMD (four with one lane per point and half the length)
-  // [r6] the same for G2 sets reduced on lane triples (the 2^19 buckets of a 20-bit table): 16 workers per wavefront
-  constexpr bool TWO_STAGE_FR = std::is_same<FR, FpOps>::value || std::is_same<FR, Fp2K3Ops>::value;
-  u32 two_len = 16;
-  if (TWO_STAGE_FR) {
-    const u64 target = (u64)c.num_cus * 4 * 2 * (G2 ? 16 : 32);
-    two_len = 4;
-    while (two_len < 64 && 2ull * p.NB / two_len > target) two_len <<= 1;
-  }
-  const bool want_part = TWO_STAGE_FR && p.NB >= (1u << 17) && p.NB <= (1u << 21) && Lw >= 32 && H >= 32;
-  const size_t o_part = want_part ? carve((u64)p.W * ((u64)H * (Lw / std::min(two_len, Lw)) + (u64)Lw * (H / std::min(two_len, H))) * sizeof(Pt)) : 0;
+  const size_t o_rowcol = carve(rp.rowcol_elems * sizeof(Pt));
+  const bool want_part = rp.want_part;   // (the piece sums of the two-stage row / column sums: reduce_plan)
+  const size_t o_part = want_part ? carve(rp.part_elems * sizeof(Pt)) : 0;
   const size_t o_prefix = density_dev ? carve((nwords + 1) * 4) : 0;
   char *ws = (char *)c.pool.acquire(off);
   if (!ws) return BH_ERR_HIP;
@@ -1390,143 +1560,9 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));   // brackets exactly the accumulate launch
     if (int rc = launch_merges<FR>(st, p, mp, c.num_cus, 0, sorted, b.zstart, pts, head, tail, long_runs, big_runs, piece_out, err)) return rc;
   }
-  // 5. reduce: rows (sum over lo, contiguous), columns (sum over hi, stride Lw), then bits.
-  // G workers per output chosen so that each launch is about one wavefront per SIMD.
-  Pt *rows = rowcol, *cols = rowcol + (u64)p.W * H;
-  typedef XyzzWorker<FR> FullWK;   // the launches that fill the chip: one lane (triple) per point
-  constexpr u32 NW = sum_waves<FR>(), PW = NW * FullWK::PER_WAVE;   // workers per workgroup of that kernel: 64
-  // workers per output: minimise (serial adds per worker + tree depth) x (waves per SIMD, at least 1);
-  // these kernels are latency-bound chains of point additions, not throughput-bound.
-  auto pick_lanes = [&](u32 groups, u32 count) {
-    // wavefront slots the launch may fill before a step stretches: ONE resident wavefront per SIMD - a second does not
-    // interleave for free in these mad-bound chains (G1 2^17-2^20 reduce 0.73-0.99 ms modelled with 1, 0.92-1.19 ms with 2; G2
-    // within noise: profiles/archive/r2_call8_slots.txt); a block of lane triples is four wavefronts
-    const double slots = (double)c.num_cus * 4;
-    u32 best = 1;
-    double best_cost = 1e30;
-    for (u32 g = 1, lg = 0; g <= PW; g <<= 1, lg++) {
-      if (g > count && g > 1) break;
-      // a lane-triple group wider than one wavefront pays two barriers and an LDS round trip (measured: ~2 additions)
-      const double steps = (double)((count + g - 1) / g) + lg + ((FR::LANES == 3 && g > 16) ? 2.0 : 0.0);
-      const double waves = (double)groups * g / (double)PW * (double)NW;
-      const double cost = steps * std::max(1.0, waves / slots);
-      if (cost < best_cost) { best_cost = cost; best = g; }
-    }
-    return best;
-  };
-  auto make_job = [&](const Pt *in, Pt *out, SumDesc d) {
-    SumJob<M> j;
-    d.lanes = d.groups ? pick_lanes(d.groups, d.mode == SUM_BITS ? std::max(1u, d.count / 2) : d.count) : 1;
-    j.in = in; j.out = out; j.d = d;
-    return j;
-  };
-  // Which worker kind a launch runs on; sum_launch counts its workgroups.  G1 launches that leave at least half of the
-  // SIMDs empty run on lane pairs (K2, above): half the latency per addition for twice the lanes.
-  // force: 0 = by the rules below, 1 = lane pairs, 2 = one lane per point (the first stage of a two-stage sum chooses)
-  auto launch_sums = [&](SumJobs<M> js, int force = 0) -> bool {
-    if constexpr (std::is_same<FR, FpOps>::value) {
-      constexpr double K2_SUM_FILL = 4.0;   // wavefronts per SIMD the lane-pair launch may reach
-      // [r6] a handful of long sums (the bit sums and the total of ONE big bucket set): one workgroup of several
-      // wavefronts per output
-      u32 groups_all = 0, max_sel = 0;
-      for (int q = 0; q < 3; q++)
-        if (js.j[q].d.groups) {
-          groups_all += js.j[q].d.groups;
-          max_sel = std::max(max_sel, js.j[q].d.mode == SUM_BITS ? js.j[q].d.count / 2 : js.j[q].d.count / js.j[q].d.splits);
-        }
-      if (force == 0 && max_sel >= 128 && groups_all <= 2u * (u32)c.num_cus) {
-        // (never more than four wavefronts: a CU has four SIMDs, and the wavefronts of a workgroup that share one take turns -
-        // eight were 198 us for 2 + 5 + 3 levels, profiles/r6_call32_timeline.txt)
-        const bool four = 2 * 64 < max_sel;
-        for (int q = 0; q < 3; q++) js.j[q].d.lanes = (four ? 4 : 2) * K2Worker::PER_WAVE;
-        return four ? sum_launch<K2Worker, 4>(js, st) : sum_launch<K2Worker, 2>(js, st);
-      }
-      // (the one-lane launch would be single wavefronts)
-      if (force != 2 && (force == 1 || (double)sum_count<FullWK, NW>(js) * 2 <= K2_SUM_FILL * (double)c.num_cus * 4))
-        return sum_launch<K2Worker, 1>(js, st);
-    }
-    if constexpr (std::is_same<FR, Fp2K3Ops>::value) {
-      // G2: the same idea on lane sextets (32 workers per 256-thread block) while the launch stays within one wavefront per SIMD
-      constexpr double K6_SUM_FILL = 8.0;   // blocks per CU the launch may reach
-      SumJobs<M> k6 = js;
-      if (force != 2 && (double)sum_count<K6Worker, 4>(k6) <= K6_SUM_FILL * (double)c.num_cus) return sum_launch<K6Worker, 4>(k6, st);
-    }
-    return sum_launch<FullWK, NW>(js, st);
-  };
-  {
-    const u32 cb = p.c - 1;   // bits of a bucket index
-    SumDesc dr, dc;
-    dr.mode = SUM_STRIDED; dr.groups = p.W * H; dr.count = Lw; dr.inner = H; dr.stride = 1; dr.istride = Lw; dr.group_shift = cb;
-    dc = dr; dc.groups = p.W * Lw; dc.count = H; dc.inner = Lw; dc.stride = Lw; dc.istride = 1;
-    SumJobs<M> js;
-    js.j[0] = make_job(pts, rows, dr); js.j[1] = make_job(pts, cols, dc); js.j[2] = js.j[1]; js.j[2].d.groups = 0;
-    // [r6] G1, bucket sets of 2^17 ... 2^21 points (16 windows of 2^15, or the 2^19 buckets of a 20-bit window table): the launch
-    // above gives every output 16-32 lane pairs - 8-16 serial additions, then a 4-5 level tree in which half, a quarter, ...
-    // of the lanes work: 12-13 levels at four wavefronts per SIMD of which 61 % is useful work (0.50 ms for the 2^20 additions
-    // of a 2^20-term multiexp, 0.27 at the multiplier's throughput).  Two stages instead: (1) every output is cut into pieces
-    // of `len` consecutive elements and ONE worker adds up a piece - no tree, every lane busy - sized so that the launch is
-    // two wavefronts per SIMD; (2) the handful of piece sums per output are folded by a small tree launch.
-    if (part) {   // (want_part, above: the sizes and groups that reduce in two stages)
-      // G1: stage one on lane pairs.  G2 (lane triples): on the lane-triple kernel (16 workers per wavefront; sextets halve
-      // that again and were within noise - reduce 1.89 / 1.96 ms against 1.86 / 1.97 at 2^19 / 2^20, profiles/r6_call42_g2_stage1.txt)
-      const bool one_lane = G2;
-      const u32 len_r = std::min(two_len, Lw), len_c = std::min(two_len, H);
-      const u32 Sr = Lw / len_r, Sc = H / len_c;
-      Pt *part_r = part, *part_c = part + (u64)dr.groups * Sr;
-      SumDesc r1 = dr, c1 = dc;
-      r1.splits = Sr; r1.groups = dr.groups * Sr; r1.lanes = 1;
-      c1.splits = Sc; c1.groups = dc.groups * Sc; c1.lanes = 1;
-      SumJobs<M> s1;
-      s1.j[0].in = pts; s1.j[0].out = Sr > 1 ? part_r : rows; s1.j[0].d = r1;
-      s1.j[1].in = pts; s1.j[1].out = Sc > 1 ? part_c : cols; s1.j[1].d = c1;
-      s1.j[2] = s1.j[1]; s1.j[2].d.groups = 0;
-      if (!launch_sums(s1, one_lane ? 2 : 1)) return BH_ERR_HIP;
-      SumDesc r2, c2;
-      r2.mode = SUM_STRIDED; r2.groups = dr.groups; r2.count = Sr; r2.inner = dr.groups; r2.stride = 1; r2.istride = Sr; r2.group_shift = 0;
-      c2 = r2; c2.groups = dc.groups; c2.count = Sc; c2.inner = dc.groups; c2.istride = Sc;
-      SumJobs<M> s2;
-      s2.j[0] = make_job(part_r, rows, r2); if (Sr <= 1) s2.j[0].d.groups = 0;
-      s2.j[1] = make_job(part_c, cols, c2); if (Sc <= 1) s2.j[1].d.groups = 0;
-      s2.j[2] = s2.j[1]; s2.j[2].d.groups = 0;
-      if (!launch_sums(s2, 1)) return BH_ERR_HIP;
-      js.j[0].d.groups = js.j[1].d.groups = 0;   // (done)
-    }
-    if (G2 && FR::LANES == 1) {
-      // single-lane G2 (one resident wavefront per SIMD, so sharing a SIMD doubles every step): the two jobs share
-      // one launch, choose their lane counts jointly - the launch lasts as long as its longest chain, stretched by
-      // how many wavefronts each SIMD has to interleave.  (With two wavefronts per SIMD - G1, K3-form G2 - they
-      // interleave almost for free and the per-job choice above is better.)
-      const double simds = (double)c.num_cus * 4;
-      double best = 1e30;
-      u32 best_r = js.j[0].d.lanes, best_c = js.j[1].d.lanes;
-      for (u32 gr = 1, lr = 0; gr <= 64 && gr <= std::max(1u, dr.count); gr <<= 1, lr++)
-        for (u32 gc = 1, lc = 0; gc <= 64 && gc <= std::max(1u, dc.count); gc <<= 1, lc++) {
-          const double steps = std::max((double)((dr.count + gr - 1) / gr) + lr, (double)((dc.count + gc - 1) / gc) + lc);
-          const double waves = ((double)dr.groups * gr + (double)dc.groups * gc) / 64.0;
-          const double cost = steps * std::max(1.0, waves / simds);
-          if (cost < best) { best = cost; best_r = gr; best_c = gc; }
-        }
-      js.j[0].d.lanes = best_r;
-      js.j[1].d.lanes = best_c;
-    }
-    if (!launch_sums(js)) return BH_ERR_HIP;
-    // sum_idx (idx+1) B[idx] = sum_p 2^p U[p] + T, idx = hi*2^l + lo:
-    //   U[w][p], p < lo_bits from the column sums (weights lo), p >= lo_bits from the row sums (weights hi),
-    //   T[w] = plain sum of all buckets = sum of the row sums.
-    SumDesc bl, bh_, bt;
-    bl.mode = SUM_BITS; bl.stride = 1; bl.istride = 0;
-    bl.groups = p.W * p.lo_bits; bl.count = Lw; bl.inner = std::max(1u, p.lo_bits); bl.group_shift = p.lo_bits;
-    bh_ = bl; bh_.groups = p.W * p.hi_bits; bh_.count = H; bh_.inner = std::max(1u, p.hi_bits); bh_.group_shift = p.hi_bits;
-    // the plain total is the sum of the column sums as well as of the row sums: take the shorter vector
-    // (this job is the longest chain of the launch)
-    const bool t_from_cols = Lw < H;
-    bt.mode = SUM_STRIDED; bt.groups = p.W; bt.count = t_from_cols ? Lw : H; bt.inner = 1; bt.stride = 1; bt.istride = 0;
-    bt.group_shift = t_from_cols ? p.lo_bits : p.hi_bits;
-    js.j[0] = make_job(cols, bits, bl);
-    js.j[1] = make_job(rows, bits + (u64)p.W * p.lo_bits, bh_);
-    js.j[2] = make_job(t_from_cols ? cols : rows, bits + (u64)p.W * cb, bt);
-    if (!launch_sums(js)) return BH_ERR_HIP;
-  }
+  // 5. reduce: row and column sums, then the bit sums and totals the host tail combines (launch_reduce, above)
+  SumLaunchSink sink;
+  if (int rc = launch_reduce<FR>(st, p, rp, c.num_cus, pts, rowcol, part, bits, sink)) return rc;
   if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_end, st));
   // status words + results to pinned host memory, one copy: [ErrFlags slot (256 B)][bit sums]
   job.host_result_bytes = (o_bits - o_err) + bits_bytes;

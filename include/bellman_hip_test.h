@@ -218,6 +218,37 @@ int bh_test_bucket_stage_dev(bh_ctx *ctx, int acc_form, int merge_form, const ui
                              unsigned chunks_per_window, const uint32_t *overrides4, uint32_t plan_out8[8], void *pts_out,
                              void *head_out, void *tail_out, void *long_out, void *big_out, void *pieces_out, void *err_out);
 
+/* Stage 5 of a multiexp on its own, and its host tail (csrc/test_reduce_hooks.hip; tests/test_gpu_reduce_stage.py,
+ * tests/models/reduce_stage_model.py): the row / column sums, their two-stage split over piece sums, the bit sums and the
+ * window totals over FILLED BUCKETS of the caller's choice, issued by the function msm_enqueue issues them with
+ * (launch_reduce of csrc/msm_ec.cuh) into buffers of exactly the sizes msm_enqueue carves (reduce_plan).
+ *   form   0 G1 (FpOps)   1 G2 on lane triples (Fp2K3Ops)   2 G2 one lane (Fp2Ops): the bundles msm_enqueue reduces with
+ *   kind   0 the classic plan (make_plan: W = ceil(256 / c) windows)   1 the table plan (make_table_plan: W = 1)
+ *   c      window bits, 2 ... 24.  num_cus: 0 = the context's own, else passed to the plan in its place (it steers choices
+ *          only; grids come from the descriptors)
+ * bh_test_reduce_plan (host only; ctx may be NULL unless num_cus is 0): plan_out16 = [c, W, nb, NB, lo_bits, hi_bits, two_len,
+ * want_part, records of rowcol, of part, of bits, guard bytes, the sentinel byte, XYZZ record bytes, affine record bytes,
+ * num_cus used].  *n_launches_out = the launches launch_reduce issues, in order - recorded by running launch_reduce itself
+ * with a sink that records where production's launches; launches_out (optional, room for max_launches) = 46 words each:
+ * [worker kind (the forms of bh_test_sum_jobs_dev), wavefronts per workgroup, workgroups, lanes a workgroup holds], then three
+ * jobs of 14 words: the 11 of bh_test_sum_jobs_dev after sum_count's clamping, with offsets in records inside the job's
+ * buffers, then [buffer read, buffer written, workgroups]; buffers 0 pts, 1 rowcol (rows, then cols at W 2^hi_bits), 2 part,
+ * 3 bits.  A job with groups = 0 does nothing; launches of no workgroup are not issued and not recorded.
+ * bh_test_reduce_stage_dev: pts_in = NB raw XYZZ records.  rowcol, part and bits are allocated at exactly the planned sizes,
+ * each followed by a guard; bits starts zeroed as in production, rowcol, part and every guard filled with the sentinel byte.
+ * launch_reduce runs once on the context's stream; rowcol_out, part_out, bits_out receive the buffers raw (part_out may not be
+ * NULL even where the plan has no part); guards_out4 = [pts, rowcol, part, bits]: 1 = the guard came back untouched (pts: and
+ * the buckets themselves unchanged).  affine_out = the shipped msm_host_tail over bits_out.  Refused before any launch: c
+ * outside [2, 24], a form or kind that does not exist, NB above 2^22 records, a recorded launch that would leave its buffers.
+ * bh_test_msm_host_tail (host only): msm_host_tail<FpOps> (group 1) / <Fp2Ops> (group 2) over W c raw records of the
+ * caller's choice in the layout of bits - [W][lo_bits] column-bit sums, [W][hi_bits] row-bit sums, [W] totals - for the
+ * plan (kind, c). */
+int bh_test_reduce_plan(bh_ctx *ctx, int form, int kind, unsigned c, int num_cus, uint32_t plan_out16[16], uint32_t *launches_out,
+                        size_t max_launches, size_t *n_launches_out);
+int bh_test_reduce_stage_dev(bh_ctx *ctx, int form, int kind, unsigned c, int num_cus, const void *pts_in, void *rowcol_out,
+                             void *part_out, void *bits_out, uint32_t guards_out4[4], void *affine_out);
+int bh_test_msm_host_tail(int group, int kind, unsigned c, const void *bits_in, void *affine_out);
+
 /* Stages 1 - 3 of a multiexp on their own (csrc/test_sort_hooks.hip, which compiles csrc/msm_stages.hip a second time into
  * the test library; tests/test_gpu_sort_stage.py, tests/models/sort_stage_model.py): density prefix, recursive scan,
  * signed-digit recoding, the 8-bit sort of the classic plan, the fused recode-and-sort of the table plan, the zero-digit search.
