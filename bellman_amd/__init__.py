@@ -28,3 +28,4 @@ from . import verifier  # noqa: F401,E402
 from .verifier import PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each, verify_proof  # noqa: F401,E402
 from . import ceremony  # noqa: F401,E402
 from .ceremony import PtauReport, pairing_product_is_one, verify_powers_of_tau  # noqa: F401,E402
+from .ceremony import bases_first_difference, contribute, same_ratio_each, tau_is_root_of_unity, verify_contributions  # noqa: F401,E402

@@ -45,6 +45,7 @@ EXPORTS = [
     "bh_groth16_batch_verify", "bh_groth16_pvk_release", "bh_proofs_read", "bh_groth16_batch_verify_compressed",
     "bh_groth16_verify_each", "bh_groth16_verify_each_compressed",
     "bh_bases_validate", "bh_pairing_product_is_one", "bh_powers_of_tau_verify",
+    "bh_bases_first_difference", "bh_pairing_same_ratio_each", "bh_groth16_params_verify_step",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -63,6 +64,7 @@ TEST_EXPORTS = [
     "bh_test_pairing_ic_accumulate_dev", "bh_test_pairing_miller3_dev", "bh_test_pairing_fold3_const_dev",
     "bh_test_pairing_verdict_dev", "bh_test_pairing_final_exp_dev",
     "bh_test_ptau_rlc_host", "bh_test_ptau_rlc_dev", "bh_test_ptau_sums",
+    "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
 ]
 
 
@@ -282,6 +284,13 @@ def load():
     lib.bh_test_ptau_rlc_host.restype = None
     lib.bh_test_ptau_rlc_dev.argtypes = [vp, vp, u32, sz, vp]
     lib.bh_test_ptau_sums.argtypes = [vp, vp, vp, vp, vp]
+    lib.bh_bases_first_difference.argtypes = [vp, vp, sz, vp, sz, sz, c.POINTER(sz)]
+    lib.bh_pairing_same_ratio_each.argtypes = [vp, vp, vp, vp, vp, sz, vp, c.POINTER(sz)]
+    lib.bh_groth16_params_verify_step.argtypes = [vp, vp, vp, vp, c.c_uint, vp]
+    lib.bh_test_phase2_sums.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.bh_test_records_differ_host.argtypes = [i32, vp, vp, sz, vp]
+    lib.bh_test_compare_shape.argtypes = [vp]
+    lib.bh_test_compare_shape.restype = None
     lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]
     lib.bh_test_pairing_host.argtypes = [sz, vp, vp, vp]
     lib.bh_test_pairing_host.restype = None

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "../../include/bellman_hip.h"
+#include "bases_compare.cuh"
 #include "common.hpp"
 #include "msm_types.hpp"
 #include "shard_cuts.hpp"
@@ -931,6 +932,37 @@ int bh_bases_validate(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count
   bh_stream_destroy(ctx, stream);
   ctx->c.pool.release(status);
   return rc != BH_OK ? rc : verdict;
+}
+// the first record at which two resident ranges differ (bases_compare.cuh): one launch on a stream of its own
+int bh_bases_first_difference(bh_ctx *ctx, const bh_bases *a, size_t first_a, const bh_bases *b, size_t first_b, size_t count,
+                              size_t *index) {
+  if (!ctx || !a || !b || !index || a->group != b->group || first_a > a->n || count > a->n - first_a || first_b > b->n ||
+      count > b->n - first_b)
+    return BH_ERR_INVALID_ARG;
+  *index = 0;
+  if (!count) return BH_OK;
+  const size_t rec = a->group == BH_G1 ? 96 : 192;
+  const char *pa = (const char *)a->dev + first_a * rec, *pb = (const char *)b->dev + first_b * rec;
+  if (((uintptr_t)pa | (uintptr_t)pb) & 15) return BH_ERR_INVALID_ARG;   // (a wrapped buffer: the kernel loads 16-byte vectors)
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  unsigned long long *min_idx = (unsigned long long *)ctx->c.pool.acquire(8);
+  if (!min_idx) return BH_ERR_HIP;
+  void *stream = nullptr;
+  if (bh_stream_create(ctx, &stream) != BH_OK) {
+    ctx->c.pool.release(min_idx);
+    return BH_ERR_HIP;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long found = ~0ULL;
+  int rc = BH_OK;
+  if (hipMemsetAsync(min_idx, 0xff, 8, st) != hipSuccess) rc = BH_ERR_HIP;
+  if (rc == BH_OK) rc = launch_first_difference(st, a->group, pa, pb, (u64)count, min_idx);
+  if (rc == BH_OK && hipMemcpyAsync(&found, min_idx, 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = BH_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == BH_OK) rc = BH_ERR_HIP;
+  bh_stream_destroy(ctx, stream);
+  ctx->c.pool.release(min_idx);
+  if (rc == BH_OK) *index = found < (unsigned long long)count ? (size_t)found : count;
+  return rc;
 }
 int bh_bases_download(bh_ctx *ctx, const bh_bases *b, size_t first, size_t count, void *out_host) {
   if (!ctx || !b || first + count > b->n) return BH_ERR_INVALID_ARG;

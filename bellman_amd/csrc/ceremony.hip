@@ -1,6 +1,9 @@
 // What a receiver of a powers-of-tau transcript needs before deriving parameters from it (declared in
 // include/bellman_hip.h): bh_pairing_product_is_one over arbitrary host pairs, and bh_powers_of_tau_verify - the random
-// linear combination of each vector against its own shift (ptau_rlc.cuh) and six pairing equations.
+// linear combination of each vector against its own shift (ptau_rlc.cuh) and six pairing equations.  And what a receiver
+// of a circuit-specific contribution needs: bh_pairing_same_ratio_each (one verdict per equation e(a, B) = e(b, A): the
+// contribution proofs) and bh_groth16_params_verify_step - byte comparison of everything a step must leave alone
+// (bh_bases_first_difference, api.hip), one linear combination per side of h and l (phase2_sums.cuh), three equations.
 //
 // The pairings run through the verifier's own launch functions (pairing_kernels.cuh, compiled in pairing.hip - the one
 // unit of this library that includes that header - and declared here): the lines of every Q, one Miller lane per pair,
@@ -11,6 +14,7 @@
 
 #include "fp12.cuh"
 #include "msm_types.hpp"
+#include "phase2_sums.cuh"
 #include "point_read.cuh"
 #include "ptau_rlc.cuh"
 
@@ -227,6 +231,216 @@ int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *
     q[m + k] = qw[k];
   }
   u32 one[6] = {0, 0, 0, 0, 0, 0};
+  bool off = false;
+  rc = pairing_products(ctx, st, p, q, 2 * m, m, one, &off);
+  if (rc) return rc;
+  if (off) return BH_ERR_INVALID_POINT;   // a multiexp over records that are not on the curve (validate the points)
+  for (size_t k = 0; k < m; k++)
+    if (one[k] != 1) rep.failed |= bit[k];
+  return rep.failed ? BH_ERR_INVALID_TRANSCRIPT : BH_OK;
+}
+
+int bh_pairing_same_ratio_each(bh_ctx *ctx, const void *a_g1, const void *b_g1, const void *A_g2, const void *B_g2, size_t n,
+                               int32_t *verdicts, size_t *n_bad) {
+  if (!ctx || (n && (!a_g1 || !b_g1 || !A_g2 || !B_g2 || !verdicts))) return BH_ERR_INVALID_ARG;
+  if (n_bad) *n_bad = 0;
+  if (!n) return BH_OK;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  OwnStream own(ctx);
+  if (!own.st) return BH_ERR_HIP;
+  constexpr size_t ROWS = BATCH_CHUNK / 2;
+  const size_t ch = n < ROWS ? n : ROWS;
+  std::vector<Affine<FpOps>> p(2 * ch);
+  std::vector<Affine<Fp2Ops>> q(2 * ch);
+  std::vector<u32> one(ch);
+  size_t bad = 0;
+  for (size_t off = 0; off < n; off += ch) {
+    const size_t m = n - off < ch ? n - off : ch;
+    // row k of the chunk: lanes k = (a, B) and m + k = (-b, A); a row decided here keeps both lanes, as identity pairs
+    for (size_t k = 0; k < m; k++) {
+      Affine<FpOps> a, b;
+      Affine<Fp2Ops> A, B;
+      memcpy(&a, (const char *)a_g1 + (off + k) * 96, 96);
+      memcpy(&b, (const char *)b_g1 + (off + k) * 96, 96);
+      memcpy(&A, (const char *)A_g2 + (off + k) * 192, 192);
+      memcpy(&B, (const char *)B_g2 + (off + k) * 192, 192);
+      int32_t v = BH_OK;
+      if (aff_is_identity(a) || aff_is_identity(b) || aff_is_identity(A) || aff_is_identity(B))
+        v = BH_ERR_POINT_AT_INFINITY;
+      else if (!on_curve(a) || !on_curve(b) || !on_curve(A) || !on_curve(B))
+        v = BH_ERR_INVALID_POINT;
+      verdicts[off + k] = v;
+      if (v != BH_OK) {
+        memset(&p[k], 0, 96);
+        memset(&p[m + k], 0, 96);
+        memset(&q[k], 0, 192);
+        memset(&q[m + k], 0, 192);
+      } else {
+        p[k] = a;
+        q[k] = B;
+        neg_g1(p[m + k], b);
+        q[m + k] = A;
+      }
+    }
+    bool off_curve = false;
+    const int rc = pairing_products(ctx, own.get(), p.data(), q.data(), 2 * m, m, one.data(), &off_curve);
+    if (rc) return rc;
+    if (off_curve) return BH_ERR_HIP;   // (every point was tested above: the device disagrees with the host)
+    for (size_t k = 0; k < m; k++) {
+      if (verdicts[off + k] == BH_OK && one[k] != 1) verdicts[off + k] = BH_ERR_INVALID_TRANSCRIPT;
+      if (verdicts[off + k] != BH_OK) bad++;
+    }
+  }
+  if (n_bad) *n_bad = bad;
+  return BH_OK;
+}
+
+int bh_groth16_params_verify_step(bh_ctx *ctx, const bh_params *before, const bh_params *after, const void *seed32,
+                                  unsigned flags, bh_params_step_report *report) {
+  bh_params_step_report local;
+  bh_params_step_report &rep = report ? *report : local;
+  rep.failed = 0;
+  rep.bad_vector = 0;
+  rep.bad_index = 0;
+  if (!ctx || !before || !after || !seed32 || (flags & ~BH_STEP_VALIDATE_POINTS)) return BH_ERR_INVALID_ARG;
+  // which = 0 h, 1 l, 2 a, 3 b_g1, 4 b_g2; side 0 = before, 1 = after
+  const bh_params *side[2] = {before, after};
+  const bh_bases *qv[2][5];
+  size_t n_ic[2] = {0, 0};
+  for (int s = 0; s < 2; s++) {
+    for (int w = 0; w < 5; w++) {
+      const int rc = bh_groth16_params_query(side[s], w, &qv[s][w], nullptr);
+      if (rc) return rc;
+      if (!qv[s][w] || bases_group(qv[s][w]) != (w == 4 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
+    }
+    const int rc = bh_groth16_params_vk_ext(side[s], nullptr, nullptr, 0, &n_ic[s]);
+    if (rc) return rc;
+  }
+  bool shape = n_ic[0] != n_ic[1];
+  for (int w = 0; w < 5; w++) shape = shape || bh_bases_len(qv[0][w]) != bh_bases_len(qv[1][w]);
+  if (shape) {
+    rep.failed = BH_STEP_FAILED_SHAPE;
+    return BH_ERR_INVALID_TRANSCRIPT;
+  }
+  // the key elements: alpha_g1, beta_g1, beta_g2, gamma_g2, ic compared; delta_g1, delta_g2 related by the equations
+  Affine<FpOps> alpha[2], beta1[2], delta1[2];
+  Affine<Fp2Ops> beta2[2], gamma2[2], delta2[2];
+  std::vector<Affine<FpOps>> ic[2];
+  for (int s = 0; s < 2; s++) {
+    ic[s].resize(n_ic[s]);
+    int rc = bh_groth16_params_vk(side[s], &alpha[s], &beta1[s], &beta2[s], &delta1[s], &delta2[s]);
+    if (!rc) rc = bh_groth16_params_vk_ext(side[s], &gamma2[s], n_ic[s] ? ic[s].data() : nullptr, n_ic[s], nullptr);
+    if (rc) return rc;
+  }
+  if (!head_ok(delta1[0]) || !head_ok(delta1[1]) || !head_ok(delta2[0]) || !head_ok(delta2[1])) {
+    rep.failed = BH_STEP_FAILED_HEAD;
+    return BH_ERR_INVALID_TRANSCRIPT;
+  }
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+
+  if (flags & BH_STEP_VALIDATE_POINTS) {
+    const unsigned vflags = BH_POINTS_CHECKED | BH_POINTS_FORBID_IDENTITY;
+    auto points_failed = [&](int rc, uint32_t vector, size_t index) {
+      if (rc == BH_ERR_INVALID_POINT || rc == BH_ERR_POINT_AT_INFINITY) {
+        rep.failed = BH_STEP_FAILED_POINTS;
+        rep.bad_vector = vector;
+        rep.bad_index = index;
+      }
+      return rc;
+    };
+    for (int w = 0; w < 2; w++) {
+      size_t bad = 0;
+      const int rc = bh_bases_validate(ctx, qv[1][w], 0, bh_bases_len(qv[1][w]), vflags, nullptr, &bad);
+      if (rc) return points_failed(rc, 4 + (uint32_t)w, bad);
+    }
+    for (int g = 0; g < 2; g++) {   // delta_g1', delta_g2': one-record views of a staging buffer
+      const int group = g == 0 ? BH_G1 : BH_G2;
+      const size_t rec = g == 0 ? 96 : 192;
+      void *stage = nullptr;
+      bh_bases *one = nullptr;
+      int rc = bh_dev_alloc(ctx, rec, &stage);
+      if (rc) return rc;
+      rc = bh_dev_upload(ctx, stage, g == 0 ? (const void *)&delta1[1] : (const void *)&delta2[1], rec);
+      if (!rc) rc = bh_bases_wrap_dev(ctx, group, stage, 1, &one);
+      if (!rc) rc = bh_bases_validate(ctx, one, 0, 1, vflags, nullptr, nullptr);
+      if (one) bh_bases_release(ctx, one);
+      bh_dev_free(ctx, stage);
+      if (rc) return points_failed(rc, 6 + (uint32_t)g, 0);
+    }
+  }
+
+  bool placed = false;   // bad_vector / bad_index name the first finding that has a position
+  auto finding = [&](uint32_t bit, uint32_t vector, size_t index) {
+    rep.failed |= bit;
+    if (!placed) {
+      rep.bad_vector = vector;
+      rep.bad_index = index;
+      placed = true;
+    }
+  };
+  if (memcmp(&alpha[0], &alpha[1], 96)) finding(BH_STEP_FAILED_KEY, 0, 0);
+  if (memcmp(&beta1[0], &beta1[1], 96)) finding(BH_STEP_FAILED_KEY, 0, 1);
+  if (memcmp(&beta2[0], &beta2[1], 192)) finding(BH_STEP_FAILED_KEY, 0, 2);
+  if (memcmp(&gamma2[0], &gamma2[1], 192)) finding(BH_STEP_FAILED_KEY, 0, 3);
+  for (size_t i = 0; i < n_ic[0]; i++)
+    if (memcmp(&ic[0][i], &ic[1][i], 96)) {
+      finding(BH_STEP_FAILED_KEY, 0, 4 + i);
+      break;
+    }
+  static const uint32_t same_bit[3] = {BH_STEP_FAILED_A, BH_STEP_FAILED_B_G1, BH_STEP_FAILED_B_G2};
+  for (int w = 2; w < 5; w++) {
+    const size_t len = bh_bases_len(qv[0][w]);
+    size_t at = len;
+    const int rc = bh_bases_first_difference(ctx, qv[0][w], 0, qv[1][w], 0, len, &at);
+    if (rc) return rc;
+    if (at != len) finding(same_bit[w - 2], (uint32_t)(w - 1), at);
+  }
+
+  OwnStream own(ctx);
+  if (!own.st) return BH_ERR_HIP;
+  hipStream_t st = own.get();
+  const bh_bases *sq[4] = {qv[0][0], qv[1][0], qv[0][1], qv[1][1]};
+  alignas(16) unsigned char sums[4][96];
+  int rcs[4];
+  int rc = phase2_sums(ctx, sq, seed32, st, sums, rcs);
+  if (rc) return rc;
+  static const uint32_t sum_bit[2] = {BH_STEP_FAILED_H, BH_STEP_FAILED_L};
+  bool skip_eq[2];
+  for (int v = 0; v < 2; v++) {
+    const bool ident = rcs[2 * v] == BH_ERR_UNEXPECTED_IDENTITY || rcs[2 * v + 1] == BH_ERR_UNEXPECTED_IDENTITY;
+    if (ident) rep.failed |= sum_bit[v];   // no honest query holds an identity
+    skip_eq[v] = ident || bh_bases_len(sq[2 * v]) == 0;
+  }
+  // the equations e(X, Y) = e(Z, W) as lanes (X, Y) and (-Z, W)
+  Affine<FpOps> p[6];
+  Affine<Fp2Ops> q[6];
+  Affine<FpOps> px[3], pz[3];
+  Affine<Fp2Ops> qy[3], qw[3];
+  uint32_t bit[3];
+  size_t m = 0;
+  auto equation = [&](uint32_t b, const Affine<FpOps> &x, const Affine<Fp2Ops> &y, const Affine<FpOps> &z, const Affine<Fp2Ops> &w) {
+    bit[m] = b;
+    px[m] = x;
+    qy[m] = y;
+    neg_g1(pz[m], z);
+    qw[m] = w;
+    m++;
+  };
+  equation(BH_STEP_FAILED_DELTA, delta1[1], delta2[0], delta1[0], delta2[1]);
+  for (int v = 0; v < 2; v++) {
+    if (skip_eq[v]) continue;
+    Affine<FpOps> s0, s1;
+    memcpy(&s0, sums[2 * v], 96);
+    memcpy(&s1, sums[2 * v + 1], 96);
+    equation(sum_bit[v], s0, delta2[0], s1, delta2[1]);
+  }
+  for (size_t k = 0; k < m; k++) {
+    p[k] = px[k];
+    q[k] = qy[k];
+    p[m + k] = pz[k];
+    q[m + k] = qw[k];
+  }
+  u32 one[3] = {0, 0, 0};
   bool off = false;
   rc = pairing_products(ctx, st, p, q, 2 * m, m, one, &off);
   if (rc) return rc;

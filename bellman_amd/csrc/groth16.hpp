@@ -523,6 +523,16 @@ class Parameters {
   // New parameters with delta multiplied by d: delta_g1, delta_g2 *= d, h and l *= 1/d, the rest copied; *this is
   // unchanged.  Throws SynthesisError(UnexpectedIdentity) for d = 0.
   std::unique_ptr<Parameters> rescale_delta(const Fr &d) const;
+  // The receiver's check of one such step (bh_groth16_params_verify_step): is `after` *this with delta multiplied by some
+  // unknown d != 0 and nothing else changed?  seed32: 32 bytes drawn from a CSPRNG AFTER `after` is fixed.  Returns the
+  // call's code - BH_OK, BH_ERR_INVALID_TRANSCRIPT, or with BH_STEP_VALIDATE_POINTS BH_ERR_INVALID_POINT /
+  // BH_ERR_POINT_AT_INFINITY - beside the report (the BH_STEP_FAILED_* bits); throws for every other code.  d = 1 passes.
+  struct StepCheck {
+    int code;
+    bh_params_step_report report;
+    bool ok() const { return code == BH_OK; }
+  };
+  StepCheck verify_step(const Parameters &after, const void *seed32, unsigned flags = BH_STEP_VALIDATE_POINTS) const;
   // Parameters::write (groth16/src/lib.rs:258-287)
   std::vector<unsigned char> write() const;
   size_t serialized_size() const;                            // bytes `write` produces

@@ -283,6 +283,16 @@ std::unique_ptr<Parameters> Parameters::rescale_delta(const Fr &d) const {
   return out;
 }
 
+Parameters::StepCheck Parameters::verify_step(const Parameters &after, const void *seed32, unsigned flags) const {
+  const bh_params before_h{const_cast<Parameters *>(this)}, after_h{const_cast<Parameters *>(&after)};
+  StepCheck out;
+  out.code = bh_groth16_params_verify_step(ctx, &before_h, &after_h, seed32, flags, &out.report);
+  if (out.code == BH_ERR_INVALID_ARG) throw std::invalid_argument("Parameters::verify_step: invalid argument");
+  if (out.code != BH_ERR_INVALID_TRANSCRIPT && out.code != BH_ERR_INVALID_POINT && out.code != BH_ERR_POINT_AT_INFINITY)
+    check(out.code);
+  return out;
+}
+
 // ---- groth16/src/lib.rs:143-156 + :258-287 (VerifyingKey::write, Parameters::write) -------------------
 namespace {
 void fp_to_be48(unsigned char *out, const uint64_t mont[6], bool *lex_largest, bool *is_zero);

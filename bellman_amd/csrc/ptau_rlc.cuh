@@ -113,8 +113,8 @@ BH_HD void ptau_rlc_store(u32 *out, const u32 digest[8], u64 j, u64 count) {
 struct PtauKeyed {
   u32 h[8];
 };
-// one lane per block
-__global__ __launch_bounds__(256) void ptau_rlc_kernel(PtauKeyed keyed, u32 v, u64 count, u32 *out) {
+// one lane per block (internal linkage: the test library includes this header from two units)
+static __global__ __launch_bounds__(256) void ptau_rlc_kernel(PtauKeyed keyed, u32 v, u64 count, u32 *out) {
   const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (2 * j >= count) return;
   u32 d[8];

@@ -37,10 +37,12 @@ class PointAtInfinity(InvalidData):
 
 class InvalidTranscript(Exception):
     """bh_powers_of_tau_verify: the transcript's vectors are not consistent powers of one (tau, alpha, beta).  `.report` is
-    the ceremony.PtauReport of the call: `.failed` holds the BH_PTAU_FAILED_* bits of the equations that do not hold."""
+    the ceremony.PtauReport of the call: `.failed` holds the BH_PTAU_FAILED_* bits of the equations that do not hold.
+    bh_groth16_params_verify_step (Parameters.verify_step): `after` is not `before` with only delta rescaled; `.report` is
+    the groth16.ParamsStepReport with the BH_STEP_FAILED_* bits."""
 
-    def __init__(self, report=None):
-        super().__init__("inconsistent powers-of-tau transcript (failed = 0x%02x)" % (report.failed if report is not None else 0))
+    def __init__(self, report=None, what="inconsistent powers-of-tau transcript"):
+        super().__init__("%s (failed = 0x%02x)" % (what, report.failed if report is not None else 0))
         self.report = report
 
 

@@ -17,6 +17,15 @@ Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _R = (1 << 256) % Q
 _MASK = (1 << 64) - 1
 INPUT, AUX = 0, 1
+STEP_VALIDATE_POINTS = 1
+STEP_FAILED_SHAPE, STEP_FAILED_HEAD, STEP_FAILED_KEY, STEP_FAILED_A, STEP_FAILED_B_G1 = 0x001, 0x002, 0x004, 0x008, 0x010
+STEP_FAILED_B_G2, STEP_FAILED_DELTA, STEP_FAILED_H, STEP_FAILED_L, STEP_FAILED_POINTS = 0x020, 0x040, 0x080, 0x100, 0x200
+
+
+class ParamsStepReport(ctypes.Structure):
+    """bh_params_step_report: `failed` = the STEP_FAILED_* bits; `bad_vector` (0 key, 1 a, 2 b_g1, 3 b_g2; with
+    STEP_FAILED_POINTS 4 h, 5 l, 6 delta_g1, 7 delta_g2) and `bad_index` name the first finding that has a position"""
+    _fields_ = [("failed", ctypes.c_uint32), ("bad_vector", ctypes.c_uint32), ("bad_index", ctypes.c_size_t)]
 
 
 def fr_to_mont_array(vals):
@@ -265,6 +274,33 @@ class Parameters:
               "Parameters.rescale_delta")
         out._h = h_
         return out
+
+    def verify_step(self, after, seed=None, validate_points=True):
+        """Is `after` this set with delta multiplied by some unknown d != 0 and nothing else changed - the receiver's check
+        of one `rescale_delta` step (bh_groth16_params_verify_step): a, b_g1, b_g2 and the key are compared byte for byte on
+        the device, h and l by one random linear combination per side, delta by pairings.  d = 1 passes.
+        validate_points=True first puts `after`'s h, l, delta_g1 and delta_g2 through the curve and subgroup tests:
+        InvalidPoint / PointAtInfinity with `.report` naming the vector (4 h, 5 l, 6 delta_g1, 7 delta_g2) and the index.
+        `seed`: 32 bytes from which the coefficients are expanded; it MUST be drawn after `after` is fixed, from a CSPRNG -
+        left None it comes from secrets.token_bytes.  Raises InvalidTranscript with `.report` (ParamsStepReport: the
+        STEP_FAILED_* bits, bad_vector, bad_index); returns the report (failed == 0)."""
+        import secrets
+
+        from .errors import InvalidData, InvalidTranscript
+
+        seed = secrets.token_bytes(32) if seed is None else bytes(seed)
+        assert len(seed) == 32
+        rep = ParamsStepReport()
+        rc = _lib.load().bh_groth16_params_verify_step(self.worker.ctx, self._h, after._h, seed,
+                                                       STEP_VALIDATE_POINTS if validate_points else 0, ctypes.byref(rep))
+        if rc == 10:
+            raise InvalidTranscript(rep, "not a rescaling of delta alone")
+        try:
+            check(rc, "Parameters.verify_step")
+        except InvalidData as e:
+            e.report = rep
+            raise
+        return rep
 
     def write(self):
         """Parameters::write (groth16/src/lib.rs:258-287) -> bytes"""

@@ -598,7 +598,8 @@ int bh_groth16_generate_from_powers_of_tau(bh_ctx *ctx, bh_r1cs *r1cs, const bh_
  * every point of h and l by 1/d (on the device; the new queries are registered like any other, so they get window
  * tables), a, b_g1, b_g2 and the rest of the key are copied.  `p` is left unchanged.  d = 0 -> BH_ERR_UNEXPECTED_IDENTITY.
  * Applied to the delta = 1 output of the call above it gives generate(alpha, beta, 1, d, tau); applied repeatedly it is
- * one contributor's step of a circuit-specific ceremony (the contribution proofs are the caller's business). */
+ * one contributor's step of a circuit-specific ceremony; the receiver checks the step with bh_groth16_params_verify_step
+ * and the contribution proofs with bh_pairing_same_ratio_each (below). */
 int bh_groth16_params_rescale_delta(const bh_params *p, const void *d_mont, bh_params **out);
 /* ---- checking a transcript before deriving parameters from it -----------------------------------------------------------
  * bh_pairing_product_is_one: *is_one = (prod_i e(P_i, Q_i) == 1) over n pairs of affine records on the host (96 B / 192 B
@@ -628,8 +629,9 @@ int bh_pairing_product_is_one(bh_ctx *ctx, const void *g1_affine_host, const voi
  * can build an inconsistent transcript that passes - the counterpart of the z_j rule of bh_groth16_batch_verify.
  * The eight multiexps run together as ordinary jobs with the default plans (a window table is used where a handle has one;
  * none is built), all equations in one Miller launch.  Thread-safe and concurrent with other work on the context.
- * NOT COVERED: a proof of knowledge of the contributors' secrets (contribution proofs), tau being a root of unity of the
- * domain (such a transcript passes and gives unusable parameters), and the parsing of any ceremony's file format. */
+ * NOT COVERED by this call: a proof of knowledge of the contributors' secrets (contribution proofs:
+ * bh_pairing_same_ratio_each), tau being a root of unity of the domain (such a transcript passes and gives unusable
+ * parameters: compare tau_g1[m] with tau_g1[0] by bh_bases_first_difference), and the parsing of any ceremony's file format. */
 #define BH_PTAU_VALIDATE_POINTS 1u
 #define BH_PTAU_FAILED_HEAD 0x01u
 #define BH_PTAU_FAILED_TAU_G1_G2 0x02u
@@ -645,6 +647,73 @@ typedef struct {
   size_t bad_index;
 } bh_ptau_report;
 int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *seed32, unsigned flags, bh_ptau_report *report);
+/* ---- checking a circuit-specific ceremony step (what the RECEIVER of bh_groth16_params_rescale_delta's output runs) ------
+ * bh_bases_first_difference: *index = the first i < count at which record first_a + i of `a` differs from record
+ * first_b + i of `b`, or `count` when the two ranges hold the same records.  Records are compared AS STORED (96 / 192
+ * bytes, Montgomery, identity = the all-zero record): the resident form of every handle this library makes is the reduced
+ * one (coordinates < p), so equal points are equal bytes; a record with a coordinate >= p differs from its reduced twin -
+ * bh_bases_validate (status 0x04) is the call that finds such a record.  BH_OK whether or not a difference exists;
+ * BH_ERR_INVALID_ARG for handles of different groups, a range beyond a handle, or a wrapped buffer that is not 16-byte
+ * aligned; count = 0 gives *index = 0.  `a` and `b` may be the same handle.  One kernel launch of any length (one lane per
+ * record, bandwidth-bound: csrc/bases_compare.cuh) on a stream of its own: thread-safe. */
+int bh_bases_first_difference(bh_ctx *ctx, const bh_bases *a, size_t first_a, const bh_bases *b, size_t first_b, size_t count,
+                              size_t *index);
+/* bh_pairing_same_ratio_each: n independent equations over affine host records (96 B / 192 B each, row i of each array):
+ * verdicts[i] = BH_OK iff e(a_i, B_i) == e(b_i, A_i), that is b_i / a_i = B_i / A_i - the "same ratio" test of a
+ * contribution proof.  Otherwise BH_ERR_POINT_AT_INFINITY when any of the row's four points is the identity (a ratio
+ * through the identity proves nothing - NOT the "contributes 1" rule of bh_pairing_product_is_one; tested first),
+ * BH_ERR_INVALID_POINT when one of them is off its curve, BH_ERR_INVALID_TRANSCRIPT when the equation fails.  A bad row
+ * never ends the walk and never changes another row's verdict.  The return value carries call-level outcomes only, as for
+ * bh_groth16_verify_each: BH_OK whenever every verdict was written; *n_bad (optional) = the number of nonzero verdicts;
+ * n = 0 is BH_OK.  Two Miller lanes per row, one fold launch, one final exponentiation per row in one launch; rows decided
+ * on the host keep their lanes (with identity pairs).  Runs in chunks of at most 8192 rows on a stream of its own, for any
+ * n: thread-safe.  Subgroup membership stays with the caller, as for bh_groth16_verify. */
+int bh_pairing_same_ratio_each(bh_ctx *ctx, const void *a_g1, const void *b_g1, const void *A_g2, const void *B_g2, size_t n,
+                               int32_t *verdicts, size_t *n_bad);
+/* bh_groth16_params_verify_step: is `after` = `before` with delta multiplied by some unknown d != 0 and NOTHING else
+ * changed - the check of one bh_groth16_params_rescale_delta step by someone who holds both sets on the device.  d = 1
+ * (`after` equal to `before`) passes: that a contributor knows a d of their own is what the contribution proofs
+ * (bh_pairing_same_ratio_each) establish.  With rho the coefficients expanded from seed32 (csrc/ptau_rlc.cuh) under the
+ * vector tags 4 (h) and 5 (l), and x' the element of `after`, the bits of report->failed are, in the order they are
+ * evaluated:
+ *   SHAPE   the five queries or ic differ in length; nothing else is evaluated
+ *   HEAD    delta_g1 or delta_g2 of either side is the identity or off its curve; nothing else is evaluated
+ *   POINTS  only with BH_STEP_VALIDATE_POINTS in flags: h' and l' go through bh_bases_validate(CHECKED | FORBID_IDENTITY),
+ *           delta_g1' and delta_g2' through the same validator; the first failure in that order ENDS the call with
+ *           bad_vector (4 h, 5 l, 6 delta_g1, 7 delta_g2), bad_index and the validator's return code
+ *           (BH_ERR_INVALID_POINT / BH_ERR_POINT_AT_INFINITY) - before any sum over those points is taken
+ *   KEY     alpha_g1, beta_g1, beta_g2, gamma_g2 or some ic[i] differs (compared on the host): bad_vector = 0,
+ *           bad_index = the position in that order (ic[i] at 4 + i)
+ *   A, B_G1, B_G2   bh_bases_first_difference over the query found a difference: bad_vector = 1 / 2 / 3, bad_index = the record
+ *   DELTA   e(delta_g1', delta_g2) != e(delta_g1, delta_g2')
+ *   H       e(sum rho_i h_i, delta_g2) != e(sum rho_i h'_i, delta_g2'); also set when one of the two multiexps meets an
+ *           identity (BH_ERR_UNEXPECTED_IDENTITY); vacuous for an empty query
+ *   L       the same over l, with the coefficients of tag 5
+ * The other vectors need no validation: they are compared equal to `before`'s.  bad_vector / bad_index name the FIRST
+ * finding that has a position (KEY, A, B_G1, B_G2 in that order).  Returns BH_OK when failed == 0,
+ * BH_ERR_INVALID_TRANSCRIPT when a bit is set, the validator's code for POINTS, call-level codes otherwise; report may be
+ * NULL; an unknown flag bit is BH_ERR_INVALID_ARG.  The seed rule of bh_powers_of_tau_verify applies: seed32 MUST BE DRAWN
+ * AFTER `after` IS FIXED, FROM A CSPRNG.  The four multiexps run together as ordinary jobs with the default plans (a window
+ * table is used where a handle has one; none is built; each query's coefficients are expanded once and shared by both
+ * sides), the up to three equations in one Miller launch.  Thread-safe (a stream of its own). */
+#define BH_STEP_VALIDATE_POINTS 1u
+#define BH_STEP_FAILED_SHAPE 0x001u
+#define BH_STEP_FAILED_HEAD 0x002u
+#define BH_STEP_FAILED_KEY 0x004u
+#define BH_STEP_FAILED_A 0x008u
+#define BH_STEP_FAILED_B_G1 0x010u
+#define BH_STEP_FAILED_B_G2 0x020u
+#define BH_STEP_FAILED_DELTA 0x040u
+#define BH_STEP_FAILED_H 0x080u
+#define BH_STEP_FAILED_L 0x100u
+#define BH_STEP_FAILED_POINTS 0x200u
+typedef struct {
+  uint32_t failed;
+  uint32_t bad_vector;
+  size_t bad_index;
+} bh_params_step_report;
+int bh_groth16_params_verify_step(bh_ctx *ctx, const bh_params *before, const bh_params *after, const void *seed32,
+                                  unsigned flags, bh_params_step_report *report);
 /* create_proof (prover.rs:217-360) from the witness alone: input_assignment (n_inputs, [0] = 1) and
  * aux_assignment (n_aux) as produced by the circuit's alloc closures; lengths must match the R1CS. */
 int bh_groth16_prove_witness(bh_params *params, const bh_r1cs *r1cs, const void *input_assignment,

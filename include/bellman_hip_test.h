@@ -339,6 +339,20 @@ void bh_test_ptau_rlc_host(const void *seed32, uint32_t v, size_t count, void *o
 int bh_test_ptau_rlc_dev(bh_ctx *ctx, const void *seed32, uint32_t v, size_t count, void *out_host);
 int bh_test_ptau_sums(bh_ctx *ctx, const bh_powers_of_tau *t, const void *seed32, void *sums_out, int *rcs_out);
 
+/* ---- the ceremony-step check (csrc/phase2_sums.cuh, csrc/bases_compare.cuh, compiled into this library by
+ * csrc/test_phase2_hooks.hip) ---------------------------------------------------------------------------------------
+ * bh_test_phase2_sums: the four sums of bh_groth16_params_verify_step as affine G1 records (96 bytes each) - sum rho_i h_i,
+ * sum rho_i h'_i (tag 4), sum rho_i l_i, sum rho_i l'_i (tag 5; x' = the element of `after`) - and rcs_out[k] the code of
+ * that multiexp; exactly the function the product calls.  An empty query has empty sums: identity records, BH_OK.
+ * bh_test_records_differ_host: out[i] = 1 when record i of a differs from record i of b (n dense records of `group`, host
+ * arrays, 16-byte aligned), by the host build of the comparison kernel's per-record predicate (no GPU).
+ * bh_test_compare_shape: out2 = threads per block, most blocks of one launch of the comparison kernel (a longer range is
+ * walked by the same grid in strides). */
+int bh_test_phase2_sums(bh_ctx *ctx, const bh_params *before, const bh_params *after, const void *seed32, void *sums_out,
+                        int *rcs_out);
+int bh_test_records_differ_host(int group, const void *a, const void *b, size_t n, unsigned char *out);
+void bh_test_compare_shape(uint32_t out2[2]);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,

@@ -100,6 +100,14 @@ pub struct BhPtauReport {
     pub bad_vector: u32,
     pub bad_index: usize,
 }
+/// `bh_params_step_report`: what bh_groth16_params_verify_step found (the BH_STEP_FAILED_* bits; the first position)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhParamsStepReport {
+    pub failed: u32,
+    pub bad_vector: u32,
+    pub bad_index: usize,
+}
 
 pub const BH_OK: c_int = 0;
 pub const BH_ERR_UNEXPECTED_IDENTITY: c_int = 1;
@@ -123,6 +131,7 @@ pub const BH_ICOSET_FFT: c_int = 3;
 pub const BH_POINTS_CHECKED: c_uint = 1;
 pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;
 pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;
+pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;
 pub const BH_PTAU_FAILED_HEAD: u32 = 0x01;
 pub const BH_PTAU_FAILED_TAU_G1_G2: u32 = 0x02;
 pub const BH_PTAU_FAILED_TAU_G1: u32 = 0x04;
@@ -131,6 +140,16 @@ pub const BH_PTAU_FAILED_ALPHA: u32 = 0x10;
 pub const BH_PTAU_FAILED_BETA: u32 = 0x20;
 pub const BH_PTAU_FAILED_BETA_G2: u32 = 0x40;
 pub const BH_PTAU_FAILED_POINTS: u32 = 0x80;
+pub const BH_STEP_FAILED_SHAPE: u32 = 0x001;
+pub const BH_STEP_FAILED_HEAD: u32 = 0x002;
+pub const BH_STEP_FAILED_KEY: u32 = 0x004;
+pub const BH_STEP_FAILED_A: u32 = 0x008;
+pub const BH_STEP_FAILED_B_G1: u32 = 0x010;
+pub const BH_STEP_FAILED_B_G2: u32 = 0x020;
+pub const BH_STEP_FAILED_DELTA: u32 = 0x040;
+pub const BH_STEP_FAILED_H: u32 = 0x080;
+pub const BH_STEP_FAILED_L: u32 = 0x100;
+pub const BH_STEP_FAILED_POINTS: u32 = 0x200;
 pub const BH_MSM_SUMS_BYTES: usize = 960;
 
 #[link(name = "bellman_hip")]
@@ -242,6 +261,9 @@ extern "C" {
     pub fn bh_groth16_params_rescale_delta(p: *const BhParams, d_mont: *const c_void, out: *mut *mut BhParams) -> c_int;
     pub fn bh_pairing_product_is_one(ctx: *mut BhCtx, g1_affine_host: *const c_void, g2_affine_host: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
     pub fn bh_powers_of_tau_verify(ctx: *mut BhCtx, t: *const BhPowersOfTau, seed32: *const c_void, flags: c_uint, report: *mut BhPtauReport) -> c_int;
+    pub fn bh_bases_first_difference(ctx: *mut BhCtx, a: *const BhBases, first_a: usize, b: *const BhBases, first_b: usize, count: usize, index: *mut usize) -> c_int;
+    pub fn bh_pairing_same_ratio_each(ctx: *mut BhCtx, a_g1: *const c_void, b_g1: *const c_void, A_g2: *const c_void, B_g2: *const c_void, n: usize, verdicts: *mut i32, n_bad: *mut usize) -> c_int;
+    pub fn bh_groth16_params_verify_step(ctx: *mut BhCtx, before: *const BhParams, after: *const BhParams, seed32: *const c_void, flags: c_uint, report: *mut BhParamsStepReport) -> c_int;
     pub fn bh_groth16_prove_witness(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_assignment_async(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_prove_witness_async(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;

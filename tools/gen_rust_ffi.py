@@ -15,7 +15,8 @@ OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "b
           "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
           "bh_pvk": "BhPvk"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo",
-           "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport"}
+           "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport",
+           "bh_params_step_report": "BhParamsStepReport"}
 SCALAR = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "uint32_t": "u32", "uint64_t": "u64",
     "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char", "void": "c_void",
@@ -114,6 +115,9 @@ def render(decls):
         "/// `bh_ptau_report`: what bh_powers_of_tau_verify found (the BH_PTAU_FAILED_* bits; the first bad point)",
         "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
         "pub struct BhPtauReport {", "    pub failed: u32,", "    pub bad_vector: u32,", "    pub bad_index: usize,", "}",
+        "/// `bh_params_step_report`: what bh_groth16_params_verify_step found (the BH_STEP_FAILED_* bits; the first position)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhParamsStepReport {", "    pub failed: u32,", "    pub bad_vector: u32,", "    pub bad_index: usize,", "}",
         "",
     ]
     consts = [("BH_OK", 0), ("BH_ERR_UNEXPECTED_IDENTITY", 1), ("BH_ERR_UNEXPECTED_EOF", 2), ("BH_ERR_DEGREE_TOO_LARGE", 3),
@@ -124,10 +128,13 @@ def render(decls):
     for k, v in consts:
         lines.append("pub const %s: c_int = %d;" % (k, v))
     lines += ["pub const BH_POINTS_CHECKED: c_uint = 1;", "pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;",
-              "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;"]
+              "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;", "pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;"]
     lines += ["pub const %s: u32 = 0x%02x;" % (k, v) for k, v in
               (("BH_PTAU_FAILED_HEAD", 1), ("BH_PTAU_FAILED_TAU_G1_G2", 2), ("BH_PTAU_FAILED_TAU_G1", 4), ("BH_PTAU_FAILED_TAU_G2", 8),
                ("BH_PTAU_FAILED_ALPHA", 16), ("BH_PTAU_FAILED_BETA", 32), ("BH_PTAU_FAILED_BETA_G2", 64), ("BH_PTAU_FAILED_POINTS", 128))]
+    lines += ["pub const %s: u32 = 0x%03x;" % (k, 1 << i) for i, k in enumerate(
+        ("BH_STEP_FAILED_SHAPE", "BH_STEP_FAILED_HEAD", "BH_STEP_FAILED_KEY", "BH_STEP_FAILED_A", "BH_STEP_FAILED_B_G1",
+         "BH_STEP_FAILED_B_G2", "BH_STEP_FAILED_DELTA", "BH_STEP_FAILED_H", "BH_STEP_FAILED_L", "BH_STEP_FAILED_POINTS"))]
     lines += ["pub const BH_MSM_SUMS_BYTES: usize = 960;", "", "#[link(name = \"bellman_hip\")]", "extern \"C\" {"]
     for name, params, ret in decls:
         ps = ", ".join("%s: %s" % (("r#" + p) if p in RUST_KEYWORDS else p, t) for p, t in params)
