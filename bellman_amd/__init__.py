@@ -25,7 +25,8 @@ from .multicore import Waiter, Worker  # noqa: F401
 from .multiexp import Bases, DensityTracker, FullDensity, Scalars, multiexp, multiexp_scalars, multiexp_sharded, point_add  # noqa: F401
 from .domain import EvaluationDomain, PointEvaluationDomain  # noqa: F401
 from . import verifier  # noqa: F401,E402
-from .verifier import PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each, verify_proof  # noqa: F401,E402
+from .verifier import (KeySet, MultiVerifier, PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each,  # noqa: F401,E402
+                       verify_each_keys, verify_proof)
 from . import ceremony  # noqa: F401,E402
 from .ceremony import PtauReport, pairing_product_is_one, verify_powers_of_tau  # noqa: F401,E402
 from .ceremony import bases_first_difference, contribute, same_ratio_each, tau_is_root_of_unity, verify_contributions  # noqa: F401,E402

@@ -44,6 +44,8 @@ EXPORTS = [
     "bh_groth16_prepare_verifying_key", "bh_groth16_pvk_from_params", "bh_groth16_pvk_num_inputs", "bh_groth16_verify",
     "bh_groth16_batch_verify", "bh_groth16_pvk_release", "bh_proofs_read", "bh_groth16_batch_verify_compressed",
     "bh_groth16_verify_each", "bh_groth16_verify_each_compressed",
+    "bh_groth16_pvk_set_create", "bh_groth16_pvk_set_len", "bh_groth16_pvk_set_release", "bh_groth16_verify_each_keys",
+    "bh_groth16_verify_each_keys_compressed", "bh_groth16_batch_verify_keys", "bh_groth16_batch_verify_keys_compressed",
     "bh_bases_validate", "bh_pairing_product_is_one", "bh_powers_of_tau_verify",
     "bh_bases_first_difference", "bh_pairing_same_ratio_each", "bh_groth16_params_verify_step",
 ]
@@ -63,6 +65,8 @@ TEST_EXPORTS = [
     "bh_test_pairing_proof_prep_dev", "bh_test_pairing_g1_mul_one_dev", "bh_test_pairing_colsum_dev", "bh_test_pairing_ic_table_dev",
     "bh_test_pairing_ic_accumulate_dev", "bh_test_pairing_miller3_dev", "bh_test_pairing_fold3_const_dev",
     "bh_test_pairing_verdict_dev", "bh_test_pairing_final_exp_dev",
+    "bh_test_pairing_ic_accumulate_keys_dev", "bh_test_pairing_miller3_keys_dev", "bh_test_pairing_fold3_const_keys_dev",
+    "bh_test_pairing_colsum_keys_dev", "bh_test_pairing_g1_mul_keys_dev", "bh_test_pairing_miller_keys_dev",
     "bh_test_ptau_rlc_host", "bh_test_ptau_rlc_dev", "bh_test_ptau_sums",
     "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
 ]
@@ -276,6 +280,15 @@ def load():
     lib.bh_groth16_verify_each.argtypes = [vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
     lib.bh_groth16_verify_each_compressed.argtypes = [vp, vp, sz, vp, sz, i32, vp, vp, c.POINTER(sz)]
     lib.bh_groth16_pvk_release.argtypes = [vp]
+    lib.bh_groth16_pvk_set_create.argtypes = [c.POINTER(vp), sz, c.POINTER(vp)]
+    lib.bh_groth16_pvk_set_len.argtypes = [vp]
+    lib.bh_groth16_pvk_set_len.restype = sz
+    lib.bh_groth16_pvk_set_release.argtypes = [vp]
+    lib.bh_groth16_pvk_set_release.restype = None
+    lib.bh_groth16_verify_each_keys.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
+    lib.bh_groth16_verify_each_keys_compressed.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp, vp, c.POINTER(sz)]
+    lib.bh_groth16_batch_verify_keys.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp]
+    lib.bh_groth16_batch_verify_keys_compressed.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp, c.POINTER(sz)]
     lib.bh_groth16_pvk_release.restype = None
     lib.bh_bases_validate.argtypes = [vp, vp, sz, sz, c.c_uint, vp, c.POINTER(sz)]
     lib.bh_pairing_product_is_one.argtypes = [vp, vp, vp, sz, c.POINTER(i32)]

@@ -672,3 +672,463 @@ int bh_groth16_verify_each_compressed(const bh_pvk *pvk, const void *bytes, size
 }
 
 }  // extern "C"
+
+// ---- proofs of several keys in one call --------------------------------------------------------------------------------
+// A bh_pvk_set names 1 .. BH_PVK_SET_MAX_KEYS prepared keys of one context and owns one device table of KeyDesc
+// (pairing_kernels.cuh).  The half of a descriptor that the batch check reads (lines, flags, alpha, input count, column
+// offset) is written when the set is made; the half that verify_each adds to a key (bh_pvk::Each: window table, width,
+// ic_0, f(-alpha, beta)) is built key by key through the key's own std::call_once and written into a second copy of the
+// table by the first bh_groth16_verify_each_keys* call.  Neither copy changes after it is written.
+// Every chunk is grouped by key on the host (a stable counting sort) and cut into blocks of at most 64 rows of one key;
+// proofs, inputs and z go up in that order, verdicts and status words come back through the permutation.
+struct bh_pvk_set {
+  bh_ctx *ctx = nullptr;
+  std::vector<const bh_pvk *> keys;
+  std::vector<KeyDesc> host;      // the descriptors as uploaded at creation
+  KeyDesc *dev = nullptr;         // [2][n_keys]: the batch's copy, then verify_each's
+  size_t total_cols = 0, max_in = 0;
+  mutable std::once_flag each_once;
+  mutable int each_rc = BH_ERR_HIP;
+};
+
+namespace {
+void set_build_each(const bh_pvk_set *set) {
+  Context &c = set->ctx->c;
+  std::vector<KeyDesc> d = set->host;
+  for (size_t k = 0; k < d.size(); k++) {
+    const bh_pvk *pvk = set->keys[k];
+    std::call_once(pvk->each.once, build_each, pvk);
+    if (pvk->each.rc) {
+      set->each_rc = pvk->each.rc;
+      return;
+    }
+    d[k].table = pvk->each.table;
+    d[k].w = pvk->each.w ? pvk->each.w : 8u;
+    d[k].ic0 = pvk->each.ic0;
+    d[k].f_ab = pvk->each.f_ab;
+  }
+  if (hipSetDevice(c.device) != hipSuccess) return;
+  StreamHold sh(set->ctx);
+  if (bh_stream_create(set->ctx, (void **)&sh.st) != BH_OK) {
+    sh.st = nullptr;
+    return;
+  }
+  if (hipMemcpyAsync(set->dev + d.size(), d.data(), d.size() * sizeof(KeyDesc), hipMemcpyHostToDevice, sh.st) != hipSuccess ||
+      hipStreamSynchronize(sh.st) != hipSuccess)
+    return;
+  set->each_rc = BH_OK;
+}
+
+// the rows [first, first + m) of a call grouped by key
+struct Grouping {
+  std::vector<u32> perm;          // grouped row r is the chunk's row perm[r]
+  std::vector<KeySeg> segs;       // per key
+  std::vector<KeyBlock> blocks;
+  size_t n_in = 0, max_seg = 0;   // scalars of the chunk; its longest run
+  void make(const bh_pvk_set *set, const uint32_t *key_of, size_t m) {
+    const size_t nk = set->keys.size();
+    segs.assign(nk, KeySeg{0, 0, 0, 0});
+    for (size_t j = 0; j < m; j++) segs[key_of[j]].count++;
+    u32 row = 0, in = 0;
+    blocks.clear();
+    max_seg = 0;
+    for (size_t k = 0; k < nk; k++) {
+      const u32 n_inputs = set->host[k].n_inputs;
+      segs[k].first = row;
+      segs[k].in_off = in;
+      for (u32 t = 0; t < segs[k].count; t += 64)
+        blocks.push_back(KeyBlock{(u32)k, row + t, std::min<u32>(64, segs[k].count - t), in + t * n_inputs});
+      row += segs[k].count;
+      in += segs[k].count * n_inputs;
+      max_seg = std::max<size_t>(max_seg, segs[k].count);
+    }
+    n_in = in;
+    perm.resize(m);
+    std::vector<u32> next(nk);
+    for (size_t k = 0; k < nk; k++) next[k] = segs[k].first;
+    for (size_t j = 0; j < m; j++) perm[next[key_of[j]]++] = (u32)j;
+  }
+};
+
+// the call-level checks both forms share; offs[j]: the first scalar of proof j in `inputs` (n_proofs + 1 values)
+int keys_check_args(const bh_pvk_set *set, const uint32_t *key_of, size_t n_proofs, const void *inputs, size_t n_inputs_total,
+                    int scalar_fmt, std::vector<size_t> &offs) {
+  if (!set || (n_proofs && !key_of) || (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT)) return BH_ERR_INVALID_ARG;
+  const size_t nk = set->keys.size();
+  offs.resize(n_proofs + 1);
+  size_t total = 0;
+  for (size_t j = 0; j < n_proofs; j++) {
+    if (key_of[j] >= nk) return BH_ERR_INVALID_ARG;
+    offs[j] = total;
+    total += set->host[key_of[j]].n_inputs;
+  }
+  offs[n_proofs] = total;
+  if (total != n_inputs_total) return BH_ERR_INVALID_VERIFYING_KEY;   // batch.rs:101-107, for every proof's own key
+  if (total && !inputs) return BH_ERR_INVALID_ARG;
+  return BH_OK;
+}
+// chunk: at most BATCH_CHUNK proofs, and at most INPUTS_CHUNK_BYTES of public inputs if every proof had the widest key
+size_t keys_chunk(const bh_pvk_set *set, size_t n_proofs) {
+  const size_t by_inputs = std::max<size_t>(1, INPUTS_CHUNK_BYTES / (32 * std::max<size_t>(set->max_in, 1)));
+  return std::min(std::min(n_proofs, BATCH_CHUNK), by_inputs);
+}
+// the chunk's records (rec bytes each) and inputs in grouped order
+void keys_gather(const Grouping &g, const bh_pvk_set *set, const uint32_t *key_of, const unsigned char *recs, size_t rec,
+                 const unsigned char *inputs, const size_t *offs, std::vector<unsigned char> &hrec, std::vector<unsigned char> &hin) {
+  const size_t m = g.perm.size();
+  hrec.resize(m * rec);
+  hin.resize(std::max<size_t>(g.n_in, 1) * 32);
+  size_t in = 0;
+  for (size_t r = 0; r < m; r++) {
+    const size_t j = g.perm[r];
+    memcpy(&hrec[r * rec], recs + j * rec, rec);
+    const size_t cnt = set->host[key_of[j]].n_inputs;
+    if (cnt) memcpy(&hin[in * 32], inputs + offs[j] * 32, cnt * 32);
+    in += cnt;
+  }
+}
+
+int verify_each_keys_impl(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, const void *bytes, size_t n_proofs,
+                          const void *inputs, size_t n_inputs_total, int scalar_fmt, int32_t *verdicts, uint32_t *status,
+                          size_t *n_bad) {
+  std::vector<size_t> offs;
+  int rc = keys_check_args(set, key_of, n_proofs, inputs, n_inputs_total, scalar_fmt, offs);
+  if (rc) return rc;
+  if (n_proofs && ((!proofs && !bytes) || !verdicts)) return BH_ERR_INVALID_ARG;
+  if (n_bad) *n_bad = 0;
+  if (!n_proofs) return BH_OK;
+  bh_ctx *ctx = set->ctx;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  std::call_once(set->each_once, set_build_each, set);
+  if (set->each_rc) return set->each_rc;
+  const size_t nk = set->keys.size();
+  const KeyDesc *kd = set->dev + nk;
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) return BH_ERR_HIP;
+  hipStream_t st = sh.st;
+  const bool separate = !env().verify_each_shared;
+  const size_t ch = keys_chunk(set, n_proofs);
+  size_t in_max = 1;   // the most scalars any chunk holds
+  for (size_t first = 0; first < n_proofs; first += ch)
+    in_max = std::max(in_max, offs[std::min(first + ch, n_proofs)] - offs[first]);
+  const size_t max_blocks = ch / 64 + nk + 1;
+  ProofRec *pr = bufs.get<ProofRec>(ch);
+  fr_t *ind = bufs.get<fr_t>(in_max);
+  Affine<FpOps> *pts = bufs.get<Affine<FpOps>>(2 * ch);   // A_j, then acc_j
+  line_t *lines = bufs.get<line_t>(ch * MILLER_LINES);
+  u32 *words = bufs.get<u32>(5 * ch);                     // curve flags of A/C, of B, is_one, verdicts, status words
+  fp12_t *f = bufs.get<fp12_t>((separate ? 3 : 1) * ch);
+  fp12_t *ws = bufs.get<fp12_t>(4 * ch);                  // final exponentiation workspace
+  KeyBlock *blk = bufs.get<KeyBlock>(max_blocks);
+  unsigned char *cbytes = bytes ? bufs.get<unsigned char>(ch * 192) : nullptr;
+  u32 *pst = bytes ? bufs.get<u32>(3 * ch) : nullptr;
+  unsigned long long *first_bad = bytes ? bufs.get<unsigned long long>(1) : nullptr;   // (the reader's; not used here)
+  if (!pr || !ind || !pts || !lines || !words || !f || !ws || !blk || (bytes && (!cbytes || !pst || !first_bad))) {
+    fprintf(stderr, "[bellman_hip] verify_each_keys: no device memory for a %zu-proof chunk\n", ch);
+    return BH_ERR_HIP;
+  }
+  u32 *pflags = words, *qflags = words + ch, *is_one = words + 2 * ch, *wst = bytes ? words + 4 * ch : nullptr;
+  int *vd = (int *)(words + 3 * ch);
+  Affine<FpOps> *accp = pts + ch;
+  const size_t rec = bytes ? 192 : sizeof(ProofRec);
+  const unsigned char *src = (const unsigned char *)(bytes ? bytes : proofs);
+  Grouping g;
+  std::vector<unsigned char> hrec, hin;
+  std::vector<int32_t> hv(ch);
+  std::vector<uint32_t> hs(ch);
+  size_t bad = 0;
+  for (size_t first = 0; first < n_proofs; first += ch) {
+    const size_t m = std::min(ch, n_proofs - first);
+    g.make(set, key_of + first, m);
+    keys_gather(g, set, key_of + first, src + first * rec, rec, (const unsigned char *)inputs, offs.data() + first, hrec, hin);
+    const size_t nb = g.blocks.size();
+    if (hipMemcpyAsync(blk, g.blocks.data(), nb * sizeof(KeyBlock), hipMemcpyHostToDevice, st) != hipSuccess) return BH_ERR_HIP;
+    if (bytes) {
+      if (hipMemcpyAsync(cbytes, hrec.data(), m * 192, hipMemcpyHostToDevice, st) != hipSuccess) return BH_ERR_HIP;
+      if ((rc = proofs_read_dev(cbytes, pr, m, pst, wst, first_bad, st))) return rc;
+    } else if (hipMemcpyAsync(pr, hrec.data(), m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      return BH_ERR_HIP;
+    }
+    if (g.n_in && hipMemcpyAsync(ind, hin.data(), g.n_in * 32, hipMemcpyHostToDevice, st) != hipSuccess) return BH_ERR_HIP;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(proof_prep_kernel, dim3(blocks_of(m, 64)), dim3(64), 0, st, pr, (const fr_t *)nullptr, 0, pts,
+                       (Affine<FpOps> *)nullptr, (fr_t *)nullptr, (const Affine<FpOps> *)nullptr, pflags, (u32)m);
+    if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+    if ((rc = launch_ic_accumulate_keys(st, ind, scalar_fmt, kd, blk, nb, accp))) return rc;
+    if ((rc = launch_g2_lines(st, &pr->b, sizeof(ProofRec), 0, lines, qflags, m))) return rc;
+    if ((rc = launch_miller3_keys(st, pts, accp, pr, lines, qflags, kd, blk, nb, separate, f, m))) return rc;
+    if ((rc = launch_fold3_const_keys(st, f, kd, blk, nb, m, separate))) return rc;
+    if ((rc = launch_final_exp(st, f, m, f, is_one, ws))) return rc;
+    hipLaunchKernelGGL(verdict_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, st, wst, pflags, qflags, is_one, vd, (u32)m);
+    if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+    if (hipMemcpyAsync(hv.data(), vd, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (status && hipMemcpyAsync(hs.data(), wst, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return BH_ERR_HIP;
+    for (size_t r = 0; r < m; r++) {
+      verdicts[first + g.perm[r]] = hv[r];
+      if (status) status[first + g.perm[r]] = hs[r];
+      bad += hv[r] != BH_OK;
+    }
+  }
+  if (n_bad) *n_bad = bad;
+  return BH_OK;
+}
+
+// bh_groth16_batch_verify over a set: with E_j the value whose being 1 is proof j's equation under its own key,
+// prod_j E_j^{z_j} == 1 - the product over the keys of what batch_verify_impl tests per key, under ONE final
+// exponentiation.  Per chunk: one column-sum launch for all keys, one multiexp job per key that has rows (issued
+// together); the tail runs [acc_Y,k] alpha_k on K lanes, Psi_k per key, and ONE Miller launch over the 3 K key pairs.
+int batch_verify_keys_impl(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, const void *bytes, size_t n_proofs,
+                           const void *inputs, size_t n_inputs_total, int scalar_fmt, const void *z, size_t *bad_index) {
+  std::vector<size_t> offs;
+  int rc = keys_check_args(set, key_of, n_proofs, inputs, n_inputs_total, scalar_fmt, offs);
+  if (rc) return rc;
+  if (n_proofs && ((!proofs && !bytes) || !z)) return BH_ERR_INVALID_ARG;
+  if (!n_proofs) return BH_OK;
+  for (size_t j = 0; j < n_proofs; j++)
+    if (scalar_is_zero_mod_q((const uint8_t *)z + 32 * j)) return BH_ERR_INVALID_ARG;
+  bh_ctx *ctx = set->ctx;
+  Context &c = ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  const size_t nk = set->keys.size(), ncol = set->total_cols;
+  const KeyDesc *kd = set->dev;
+  PoolBufs bufs(c);     // declared before the stream: released only after the stream has drained
+  StreamHold sh(ctx);
+  if (bh_stream_create(ctx, (void **)&sh.st) != BH_OK) return BH_ERR_HIP;
+  hipStream_t st = sh.st;
+  const size_t ch = keys_chunk(set, n_proofs);
+  size_t in_max = 1;
+  for (size_t first = 0; first < n_proofs; first += ch)
+    in_max = std::max(in_max, offs[std::min(first + ch, n_proofs)] - offs[first]);
+  ProofRec *pr = bufs.get<ProofRec>(ch);
+  fr_t *zd = bufs.get<fr_t>(ch);
+  fr_t *ind = bufs.get<fr_t>(in_max);
+  Affine<FpOps> *pts = bufs.get<Affine<FpOps>>(ch);
+  Affine<FpOps> *cb = bufs.get<Affine<FpOps>>(ch);
+  fr_t *zc = bufs.get<fr_t>(ch);
+  line_t *lines = bufs.get<line_t>(ch * MILLER_LINES);
+  u32 *pflags = bufs.get<u32>(ch), *qflags = bufs.get<u32>(ch + 1);
+  fp12_t *f = bufs.get<fp12_t>(ch + 1);
+  fp12_t *facc = bufs.get<fp12_t>(1);
+  fr_t *part = bufs.get<fr_t>(ncol * COLSUM_BLOCKS);
+  fr_t *acc = bufs.get<fr_t>(ncol);
+  Affine<FpOps> *key = bufs.get<Affine<FpOps>>(3 * nk);   // [-Psi_k], [-sum z C of k], [[acc_Y,k] alpha_k]
+  Affine<FpOps> *gen = bufs.get<Affine<FpOps>>(1);
+  KeySeg *segd = bufs.get<KeySeg>(nk);
+  fp12_t *fk = bufs.get<fp12_t>(3 * nk + 1 + 5);          // the key pairs' values, the running product, final exponentiation
+  unsigned char *cbytes = bytes ? bufs.get<unsigned char>(ch * 192) : nullptr;
+  u32 *pst = bytes ? bufs.get<u32>(4 * ch) : nullptr;
+  unsigned long long *first_bad = bytes ? bufs.get<unsigned long long>(1) : nullptr;
+  if (bytes && (!cbytes || !pst || !first_bad)) return BH_ERR_HIP;
+  if (!pr || !zd || !ind || !pts || !cb || !zc || !lines || !pflags || !qflags || !f || !facc || !part || !acc || !key || !gen ||
+      !segd || !fk) {
+    fprintf(stderr, "[bellman_hip] batch verification over a key set: no device memory for a %zu-proof chunk\n", ch);
+    return BH_ERR_HIP;
+  }
+  fp12_t one;
+  f12_one(one);
+  Affine<FpOps> gpt;
+  g1_generator(gpt);
+  if (hipMemcpyAsync(facc, &one, sizeof one, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(gen, &gpt, sizeof gpt, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(acc, 0, ncol * sizeof(fr_t), st) != hipSuccess)
+    return BH_ERR_HIP;
+  std::vector<Affine<FpOps>> sum_c(nk);   // per key: sum z_j C_j over the chunks so far (host, affine)
+  memset(sum_c.data(), 0, nk * sizeof(Affine<FpOps>));
+  std::vector<unsigned char> active(nk, 0);
+  u32 bad = 0;
+  std::vector<u32> hflags(ch), hqflags(ch), hwords(bytes ? ch : 0);
+  const size_t rec = bytes ? 192 : sizeof(ProofRec);
+  const unsigned char *src = (const unsigned char *)(bytes ? bytes : proofs);
+  Grouping g;
+  std::vector<unsigned char> hrec, hin, hz;
+  std::vector<bh_bases *> cbases(nk, nullptr);
+  std::vector<bh_msm_job *> jobs(nk, nullptr);
+  for (size_t first = 0; first < n_proofs && !rc; first += ch) {
+    const size_t m = std::min(ch, n_proofs - first);
+    g.make(set, key_of + first, m);
+    keys_gather(g, set, key_of + first, src + first * rec, rec, (const unsigned char *)inputs, offs.data() + first, hrec, hin);
+    hz.resize(m * 32);
+    for (size_t r = 0; r < m; r++) memcpy(&hz[r * 32], (const unsigned char *)z + (first + g.perm[r]) * 32, 32);
+    unsigned long long hbad = ~0ULL;   // a proof of the chunk that Proof::read refuses
+    if (hipMemcpyAsync(segd, g.segs.data(), nk * sizeof(KeySeg), hipMemcpyHostToDevice, st) != hipSuccess) { rc = BH_ERR_HIP; break; }
+    if (bytes) {
+      if (hipMemcpyAsync(cbytes, hrec.data(), m * 192, hipMemcpyHostToDevice, st) != hipSuccess ||
+          hipMemsetAsync(first_bad, 0xff, 8, st) != hipSuccess) {
+        rc = BH_ERR_HIP;
+        break;
+      }
+      if ((rc = proofs_read_dev(cbytes, pr, m, pst, pst + 3 * ch, first_bad, st))) break;
+      if (hipMemcpyAsync(&hbad, first_bad, 8, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = BH_ERR_HIP; break; }
+    } else if (hipMemcpyAsync(pr, hrec.data(), m * sizeof(ProofRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      rc = BH_ERR_HIP;
+      break;
+    }
+    if (hipMemcpyAsync(zd, hz.data(), m * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (g.n_in && hipMemcpyAsync(ind, hin.data(), g.n_in * 32, hipMemcpyHostToDevice, st) != hipSuccess)) {
+      rc = BH_ERR_HIP;
+      break;
+    }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(proof_prep_kernel, dim3(blocks_of(m, 64)), dim3(64), 0, st, pr, zd, scalar_fmt, pts, cb, zc, gen, pflags,
+                       (u32)m);
+    if (hipGetLastError() != hipSuccess) { rc = BH_ERR_HIP; break; }
+    if ((rc = launch_g2_lines(st, &pr->b, sizeof(ProofRec), 1, lines, qflags, m))) break;   // -B_j
+    if ((rc = launch_colsum_keys(st, zd, ind, scalar_fmt, kd, segd, nk, set->max_in + 1, ncol, g.max_seg, part, acc))) break;
+    // sum z_j C_j of every key's run on the multiexp path, ordered after the prep kernel: all issued before the first wait
+    for (size_t k = 0; k < nk && !rc; k++) {
+      const KeySeg &s = g.segs[k];
+      if (!s.count) continue;
+      active[k] = 1;
+      if ((rc = bh_bases_wrap_dev(ctx, BH_G1, cb + s.first, s.count, &cbases[k]))) break;
+      rc = bh_msm_async_dev_after(ctx, cbases[k], 0, zc + s.first, s.count, scalar_fmt, nullptr, 0, nullptr, (void *)st, &jobs[k]);
+    }
+    if (!rc) rc = launch_miller(st, pts, lines, qflags, f, m);
+    if (!rc && hipMemcpyAsync(f + m, facc, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (!rc) rc = launch_fold(st, f, m + 1);
+    if (!rc && hipMemcpyAsync(facc, f, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
+    if (!rc && (hipMemcpyAsync(hflags.data(), pflags, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(hqflags.data(), qflags, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                (bytes && hipMemcpyAsync(hwords.data(), pst + 3 * ch, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess)))
+      rc = BH_ERR_HIP;
+    std::vector<Affine<FpOps>> part_c(nk);
+    for (size_t k = 0; k < nk; k++)
+      if (jobs[k]) {
+        const int mrc = bh_msm_wait(jobs[k], &part_c[k]);
+        if (!rc) rc = mrc;
+      }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = BH_ERR_HIP;
+    for (size_t k = 0; k < nk; k++) {
+      if (cbases[k]) bh_bases_release(ctx, cbases[k]);
+      cbases[k] = nullptr;
+      if (jobs[k] && !rc) bh_point_add(BH_G1, &sum_c[k], &sum_c[k], &part_c[k], 1);
+      jobs[k] = nullptr;
+    }
+    if (rc) break;
+    if (hbad != ~0ULL) {   // Proof::read failed in this chunk: the first such proof in the CALLER's order
+      size_t where = ~size_t(0);
+      for (size_t r = 0; r < m; r++)
+        if (proof_status_error(hwords[r]) != BH_OK && g.perm[r] < where) where = g.perm[r];
+      if (where == ~size_t(0)) return BH_ERR_HIP;
+      if (bad_index) *bad_index = first + where;
+      for (size_t r = 0; r < m; r++)
+        if (g.perm[r] == where) return proof_status_error(hwords[r]);
+    }
+    for (size_t j = 0; j < m; j++) bad |= hflags[j] | (hqflags[j] & PF_OFF_CURVE);
+  }
+  if (rc) return rc;
+  if (bad & PF_OFF_CURVE) return BH_ERR_INVALID_POINT;
+  // [acc_Y,k] alpha_k on K lanes, then Psi_k = sum acc_Gamma_{k,i} ic_{k,i} with the scalars of identity ic_i zeroed (the
+  // zeroing is ordered after the read of acc_Y,k); a key without a proof in the batch takes no part (three identities)
+  if ((rc = launch_g1_mul_keys(st, key + 2 * nk, kd, acc, nk))) return rc;
+  for (size_t k = 0; k < nk; k++) {
+    const bh_pvk *pvk = set->keys[k];
+    for (size_t i = 0; i < pvk->n_ic; i++)
+      if (pvk->ic_identity[i] && hipMemsetAsync(acc + set->host[k].col_off + i, 0, sizeof(fr_t), st) != hipSuccess) return BH_ERR_HIP;
+  }
+  for (size_t k = 0; k < nk && !rc; k++)
+    if (active[k])
+      rc = bh_msm_async_dev_after(ctx, set->keys[k]->ic, 0, acc + set->host[k].col_off, set->keys[k]->n_ic, BH_SCALARS_MONT, nullptr,
+                                  0, nullptr, (void *)st, &jobs[k]);
+  std::vector<Affine<FpOps>> k2(2 * nk);
+  memset(k2.data(), 0, 2 * nk * sizeof(Affine<FpOps>));
+  for (size_t k = 0; k < nk; k++) {
+    if (!jobs[k]) continue;
+    Affine<FpOps> psi;
+    const int mrc = bh_msm_wait(jobs[k], &psi);
+    if (!rc) rc = mrc;
+    neg_g1_host(k2[k], psi);
+    neg_g1_host(k2[nk + k], sum_c[k]);
+  }
+  if (rc) return rc;
+  if (hipMemcpyAsync(key, k2.data(), 2 * nk * sizeof(Affine<FpOps>), hipMemcpyHostToDevice, st) != hipSuccess) return BH_ERR_HIP;
+  if ((rc = launch_miller_keys(st, key, kd, nk, fk))) return rc;
+  if (hipMemcpyAsync(fk + 3 * nk, facc, sizeof(fp12_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return BH_ERR_HIP;
+  if ((rc = launch_fold(st, fk, 3 * nk + 1))) return rc;
+  fp12_t *fe = fk + 3 * nk + 1;
+  if ((rc = launch_final_exp(st, fk, 1, fe, qflags, fe + 1))) return rc;
+  u32 h = 0;
+  if (hipMemcpyAsync(&h, qflags, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return BH_ERR_HIP;
+  return h == 1 ? BH_OK : BH_ERR_INVALID_PROOF;
+}
+}  // namespace
+
+extern "C" {
+
+int bh_groth16_pvk_set_create(const bh_pvk *const *pvks, size_t n_keys, bh_pvk_set **out) {
+  if (!pvks || !out || !n_keys || n_keys > BH_PVK_SET_MAX_KEYS) return BH_ERR_INVALID_ARG;
+  for (size_t k = 0; k < n_keys; k++)
+    if (!pvks[k] || pvks[k]->ctx != pvks[0]->ctx) return BH_ERR_INVALID_ARG;
+  std::unique_ptr<bh_pvk_set> s(new bh_pvk_set);
+  s->ctx = pvks[0]->ctx;
+  Context &c = s->ctx->c;
+  BH_HIP_CHECK(hipSetDevice(c.device));
+  s->keys.assign(pvks, pvks + n_keys);
+  s->host.resize(n_keys);
+  for (size_t k = 0; k < n_keys; k++) {
+    const bh_pvk *p = pvks[k];
+    KeyDesc &d = s->host[k];
+    memset(&d, 0, sizeof d);
+    d.lines = p->lines;
+    d.qflags = p->qflags;
+    d.alpha = p->alpha_dev;
+    d.w = 8;
+    d.n_inputs = (u32)(p->n_ic - 1);
+    d.col_off = (u32)s->total_cols;
+    s->total_cols += p->n_ic;
+    s->max_in = std::max(s->max_in, p->n_ic - 1);
+  }
+  s->dev = (KeyDesc *)c.pool.acquire(2 * n_keys * sizeof(KeyDesc));
+  if (!s->dev) return BH_ERR_HIP;
+  StreamHold sh(s->ctx);
+  int rc = bh_stream_create(s->ctx, (void **)&sh.st);
+  if (rc) sh.st = nullptr;
+  if (!rc && (hipMemcpyAsync(s->dev, s->host.data(), n_keys * sizeof(KeyDesc), hipMemcpyHostToDevice, sh.st) != hipSuccess ||
+              hipStreamSynchronize(sh.st) != hipSuccess))
+    rc = BH_ERR_HIP;
+  if (rc) {
+    c.pool.release(s->dev);
+    return rc;
+  }
+  *out = s.release();
+  return BH_OK;
+}
+
+size_t bh_groth16_pvk_set_len(const bh_pvk_set *set) { return set ? set->keys.size() : 0; }
+
+void bh_groth16_pvk_set_release(bh_pvk_set *set) {
+  if (!set) return;
+  Context &c = set->ctx->c;
+  (void)hipSetDevice(c.device);
+  c.pool.release(set->dev);
+  delete set;
+}
+
+int bh_groth16_verify_each_keys(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, size_t n_proofs,
+                                const void *inputs, size_t n_inputs_total, int scalar_fmt, int32_t *verdicts, size_t *n_bad) {
+  return verify_each_keys_impl(set, key_of, proofs, nullptr, n_proofs, inputs, n_inputs_total, scalar_fmt, verdicts, nullptr,
+                               n_bad);
+}
+
+int bh_groth16_verify_each_keys_compressed(const bh_pvk_set *set, const uint32_t *key_of, const void *bytes, size_t n_proofs,
+                                           const void *inputs, size_t n_inputs_total, int scalar_fmt, int32_t *verdicts,
+                                           uint32_t *status, size_t *n_bad) {
+  return verify_each_keys_impl(set, key_of, nullptr, bytes, n_proofs, inputs, n_inputs_total, scalar_fmt, verdicts, status, n_bad);
+}
+
+int bh_groth16_batch_verify_keys(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, size_t n_proofs,
+                                 const void *inputs, size_t n_inputs_total, int scalar_fmt, const void *z) {
+  return batch_verify_keys_impl(set, key_of, proofs, nullptr, n_proofs, inputs, n_inputs_total, scalar_fmt, z, nullptr);
+}
+
+int bh_groth16_batch_verify_keys_compressed(const bh_pvk_set *set, const uint32_t *key_of, const void *bytes, size_t n_proofs,
+                                            const void *inputs, size_t n_inputs_total, int scalar_fmt, const void *z,
+                                            size_t *bad_index) {
+  return batch_verify_keys_impl(set, key_of, nullptr, bytes, n_proofs, inputs, n_inputs_total, scalar_fmt, z, bad_index);
+}
+
+}  // extern "C"

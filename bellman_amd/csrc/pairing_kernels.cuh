@@ -1,6 +1,7 @@
 // The device half of the Groth16 verifier (pairing.hip holds the host half and the description of the whole): the curve
-// tests, the thirteen kernels and the functions that launch them.  Included by pairing.hip (the product) and by
-// test_pairing_hooks.hip (the test library), which runs every kernel on its own: tests/test_gpu_pairing_stages.py.
+// tests, the thirteen kernels of the one-key calls, the six key-aware ones of the calls over a key set, and the functions
+// that launch them.  Included by pairing.hip (the product) and by test_pairing_hooks.hip (the test library), which runs
+// every kernel on its own: tests/test_gpu_pairing_stages.py, tests/test_gpu_verify_keys_stages.py.
 // ONE translation unit per library may include this header: the kernels and the launch_* functions have external linkage
 // (the text is pairing.hip's, unchanged), so a second including unit in the same library would define them twice.  Another
 // unit of the same library that needs a launch function declares it (test_hooks.hip does, for bh_test_pairing).
@@ -303,6 +304,178 @@ __global__ __launch_bounds__(256) void verdict_kernel(const u32 *words, const u3
   verdicts[i] = v;
 }
 
+// ---- proofs of several keys in one call (bh_groth16_verify_each_keys, bh_groth16_batch_verify_keys) ----------------------
+// The host groups the rows of a chunk by key (a stable counting sort) and cuts every key's run into blocks of at most 64
+// rows, so that a 64-lane block belongs to ONE key: the block fetches its KeyBlock and the key's KeyDesc by blockIdx, and
+// the key's pointers stay wave-uniform (scalar loads), as the kernel arguments of the one-key kernels are.  Rows are
+// addressed in the grouped order; the host carries verdicts and status words back through the permutation.
+struct KeyDesc {                // one per key of a bh_pvk_set (device table, immutable once written)
+  const line_t *lines;          // [3][68]: -gamma, -delta, beta
+  const u32 *qflags;            // [3]
+  const Affine<FpOps> *alpha;
+  const Affine<FpOps> *table;   // window table of ic_1 .. ic_n (NULL for a key without inputs), its width below
+  const Affine<FpOps> *ic0;
+  const fp12_t *f_ab;           // f(-alpha, beta)
+  u32 w, n_inputs;
+  u32 col_off, pad;             // the key's first column in the set's column sums (n_inputs + 1 columns per key)
+};
+struct KeyBlock {               // rows [first, first + count) of the grouped chunk belong to `key`; count <= 64;
+  u32 key, first, count, in_off;   // the inputs of row first + t are the n_inputs scalars from in_off + t * n_inputs on
+};
+struct KeySeg {                 // a key's whole run of rows in the grouped chunk (count may be 0) and its first input
+  u32 first, count, in_off, pad;
+};
+
+// 7k. ic_accumulate_kernel from the row's own key: its table, width and ic_0, the ragged input offset
+__global__ __launch_bounds__(64) void ic_accumulate_keys_kernel(const fr_t *inputs, int fmt, const KeyDesc *__restrict__ keys,
+                                                                const KeyBlock *__restrict__ blocks, Affine<FpOps> *out) {
+  const KeyBlock b = blocks[blockIdx.x];
+  if (threadIdx.x >= b.count) return;
+  const KeyDesc kd = keys[b.key];
+  const u32 w = kd.w, n_inputs = kd.n_inputs;
+  const fr_t *in = inputs + (size_t)b.in_off + (size_t)threadIdx.x * n_inputs;
+  const u32 entries = (1u << w) - 1, windows = 256 / w;
+  XYZZ<FpOps> acc;
+  xyzz_set_identity(acc);
+#pragma unroll 1
+  for (u32 i = 0; i < n_inputs; i++) {
+    fr_t k;
+    scalar_bits(k, in[i], fmt);
+    const Affine<FpOps> *row = kd.table + (size_t)i * windows * entries;
+#pragma unroll 1
+    for (u32 win = 0; win < windows; win++) {
+      const u32 d = (k.l[(win * w) >> 5] >> ((win * w) & 31)) & entries;
+      if (!d) continue;
+      const Affine<FpOps> e = row[(size_t)win * entries + d - 1];
+      if (!aff_is_identity(e)) xyzz_madd(acc, e);
+    }
+  }
+  const Affine<FpOps> first = *kd.ic0;
+  if (!aff_is_identity(first)) xyzz_madd(acc, first);
+  Affine<FpOps> r;
+  xyzz_to_affine(r, acc);
+  out[b.first + threadIdx.x] = r;
+}
+// 8k. miller3_kernel with the -gamma and -delta lines of the row's key, in both grid forms (n: the rows of the chunk)
+__global__ __launch_bounds__(64) void miller3_keys_kernel(const Affine<FpOps> *a, const Affine<FpOps> *acc, const ProofRec *proofs,
+                                                          const line_t *blines, const u32 *bflags, const KeyDesc *__restrict__ keys,
+                                                          const KeyBlock *__restrict__ blocks, u32 pairs, fp12_t *f, u32 n) {
+  const KeyBlock b = blocks[blockIdx.x];
+  if (threadIdx.x >= b.count) return;
+  const u32 i = b.first + threadIdx.x;
+  const line_t *__restrict__ klines = keys[b.key].lines;
+  const u32 *__restrict__ kflags = keys[b.key].qflags;
+  if (gridDim.y > 1) {
+    pairs = 1u << blockIdx.y;
+    f += (size_t)blockIdx.y * n;
+  }
+  const Affine<FpOps> *pa = a + i, *pg = acc + i, *pc = &proofs[i].c;
+  const line_t *bl = blines + (size_t)i * MILLER_LINES;
+  const bool on0 = (pairs & 1u) && !aff_is_identity(*pa) && !(bflags[i] & PF_IDENTITY);
+  const bool on1 = (pairs & 2u) && !aff_is_identity(*pg) && !(kflags[0] & PF_IDENTITY);
+  const bool on2 = (pairs & 4u) && !aff_is_identity(*pc) && !(kflags[1] & PF_IDENTITY);
+  fp12_t r;
+  f12_one(r);
+  int k = 0;
+#pragma unroll 1
+  for (int s = 62; s >= 0; s--) {
+    if (s != 62) f12_sqr(r, r);
+    const int steps = ((BLS_X_ABS >> s) & 1) ? 2 : 1;
+#pragma unroll 1
+    for (int t = 0; t < steps; t++, k++) {
+      if (on0) f12_mul_line_at(r, bl[k], pa->x, pa->y);
+      if (on1) f12_mul_line_at(r, klines[k], pg->x, pg->y);
+      if (on2) f12_mul_line_at(r, klines[MILLER_LINES + k], pc->x, pc->y);
+    }
+  }
+  f[i] = r;
+}
+// f[row] *= f(-alpha, beta) of the row's key
+__global__ __launch_bounds__(64) void f12_mul_const_keys_kernel(fp12_t *f, const KeyDesc *__restrict__ keys,
+                                                                const KeyBlock *__restrict__ blocks) {
+  const KeyBlock b = blocks[blockIdx.x];
+  if (threadIdx.x >= b.count) return;
+  const u32 i = b.first + threadIdx.x;
+  fp12_t x = f[i], y = *keys[b.key].f_ab;
+  f12_mul(x, x, y);
+  f[i] = x;
+}
+// 3k. segmented column sums: for key k = blockIdx.y / nb and its run of rows, part[(col_off_k + col) * nb + block] as
+// fr_colsum_kernel writes it for one key; block columns beyond the key's n_inputs + 1 leave at once.  The columns of all
+// keys lie side by side, so fr_colsum_finish_kernel over the set's total column count finishes them.
+__global__ __launch_bounds__(COLSUM_THREADS) void fr_colsum_keys_kernel(const fr_t *z, const fr_t *inputs, int fmt,
+                                                                        const KeyDesc *__restrict__ keys,
+                                                                        const KeySeg *__restrict__ segs, u32 nb, fr_t *part) {
+  __shared__ fr_t sh[COLSUM_THREADS];
+  const u32 key = blockIdx.y / nb, by = blockIdx.y % nb, col = blockIdx.x, t = threadIdx.x;
+  const u32 n_inputs = keys[key].n_inputs;
+  if (col > n_inputs) return;
+  const KeySeg s = segs[key];
+  fr_t acc;
+  fe_zero(acc);
+  for (u32 j = by * COLSUM_THREADS + t; j < s.count; j += nb * COLSUM_THREADS) {
+    fr_t zm, term;
+    scalar_mont(zm, z[s.first + j], fmt);
+    if (col == 0) term = zm;
+    else {
+      fr_t a;
+      scalar_mont(a, inputs[(size_t)s.in_off + (size_t)j * n_inputs + col - 1], fmt);
+      fe_mul(term, zm, a);
+    }
+    fe_add(acc, acc, term);
+  }
+  sh[t] = acc;
+  __syncthreads();
+  for (u32 h = COLSUM_THREADS / 2; h; h >>= 1) {
+    if (t < h) {
+      fr_t v;
+      fe_add(v, sh[t], sh[t + h]);
+      sh[t] = v;
+    }
+    __syncthreads();
+  }
+  if (t == 0) part[(size_t)(keys[key].col_off + col) * nb + by] = sh[0];
+}
+// [acc_Y,k] alpha_k for every key of the set, one lane per key: out[k] = [acc[col_off_k]] alpha_k (Montgomery scalar)
+__global__ __launch_bounds__(64) void g1_mul_keys_kernel(Affine<FpOps> *out, const KeyDesc *__restrict__ keys, const fr_t *acc,
+                                                         u32 n_keys) {
+  const u32 key = blockIdx.x * blockDim.x + threadIdx.x;
+  if (key >= n_keys) return;
+  fr_t k;
+  fe_from_mont(k, acc[keys[key].col_off]);
+  const Affine<FpOps> a = *keys[key].alpha;
+  XYZZ<FpOps> r;
+  xyzz_set_identity(r);
+  if (!aff_is_identity(a))
+    for (int bit = 255; bit >= 0; bit--) {
+      XYZZ<FpOps> t;
+      xyzz_dbl(t, r);
+      r = t;
+      if ((k.l[bit >> 5] >> (bit & 31)) & 1) xyzz_madd(r, a);
+    }
+  Affine<FpOps> o;
+  xyzz_to_affine(o, r);
+  out[key] = o;
+}
+// the 3 K key pairs of a batch over a set, one lane per pair: f[which * K + k] = f(p[which * K + k], lines `which` of
+// key k) for which = 0 (-gamma), 1 (-delta), 2 (beta); an identity on either side gives 1, as in miller_kernel
+__global__ __launch_bounds__(64) void miller_keys_kernel(const Affine<FpOps> *p, const KeyDesc *__restrict__ keys, u32 n_keys,
+                                                         fp12_t *f) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * n_keys) return;
+  const u32 which = i / n_keys, key = i % n_keys;
+  const Affine<FpOps> pp = p[i];
+  const line_t *l = keys[key].lines + (size_t)which * MILLER_LINES;
+  const u32 qf = keys[key].qflags[which];
+  fp12_t r;
+  if (aff_is_identity(pp) || (qf & PF_IDENTITY)) {
+    f12_one(r);
+  } else {
+    miller_loop_lines(r, pp.x, pp.y, [&](int k) { return l[k]; });
+  }
+  f[i] = r;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -376,6 +549,67 @@ int launch_fold3_const(hipStream_t st, fp12_t *f, const fp12_t *c, size_t m, boo
     hipLaunchKernelGGL(f12_fold_kernel, g, blk, 0, st, f, (u32)(2 * m), (u32)m);
   }
   hipLaunchKernelGGL(f12_mul_const_kernel, g, blk, 0, st, f, c, (u32)m);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+
+// ---- several keys: `blocks` holds nblocks KeyBlock of the grouped chunk, `keys` the set's descriptors (both on the device)
+int launch_ic_accumulate_keys(hipStream_t st, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeyBlock *blocks,
+                              size_t nblocks, Affine<FpOps> *out) {
+  if (!nblocks) return BH_OK;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(ic_accumulate_keys_kernel, dim3((u32)nblocks), dim3(64), 0, st, inputs, fmt, keys, blocks, out);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// f: 3 m values where the three pairs run apart (separate), else m
+int launch_miller3_keys(hipStream_t st, const Affine<FpOps> *a, const Affine<FpOps> *acc, const ProofRec *proofs,
+                        const line_t *blines, const u32 *bflags, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks,
+                        bool separate, fp12_t *f, size_t m) {
+  if (!nblocks) return BH_OK;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(miller3_keys_kernel, dim3((u32)nblocks, separate ? 3 : 1), dim3(64), 0, st, a, acc, proofs, blines, bflags,
+                     keys, blocks, 7u, f, (u32)m);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// launch_fold3_const with the constant of every row's key
+int launch_fold3_const_keys(hipStream_t st, fp12_t *f, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks, size_t m,
+                            bool separate) {
+  if (!m || !nblocks) return BH_OK;
+  const dim3 g(blocks_of(m, 64)), blk(64);
+  (void)hipGetLastError();
+  if (separate) {
+    hipLaunchKernelGGL(f12_fold_kernel, g, blk, 0, st, f + m, (u32)(2 * m), (u32)m);
+    hipLaunchKernelGGL(f12_fold_kernel, g, blk, 0, st, f, (u32)(2 * m), (u32)m);
+  }
+  hipLaunchKernelGGL(f12_mul_const_keys_kernel, dim3((u32)nblocks), blk, 0, st, f, keys, blocks);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// the column sums of one grouped chunk for every key of the set: one launch whatever n_keys is, then the finish step over
+// the set's total_cols columns (part: total_cols * COLSUM_BLOCKS values; acc: total_cols).  max_seg: the longest run of
+// the chunk; max_cols: the largest n_inputs + 1 of the set; nb as for launch_colsum
+int launch_colsum_keys(hipStream_t st, const fr_t *z, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeySeg *segs,
+                       size_t n_keys, size_t max_cols, size_t total_cols, size_t max_seg, fr_t *part, fr_t *acc, u32 nb = 0) {
+  if (!nb) nb = (u32)std::max<size_t>(1, std::min<size_t>(COLSUM_BLOCKS, blocks_of(max_seg, COLSUM_THREADS)));
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(fr_colsum_keys_kernel, dim3((u32)max_cols, (u32)(n_keys * nb)), dim3(COLSUM_THREADS), 0, st, z, inputs, fmt,
+                     keys, segs, nb, part);
+  hipLaunchKernelGGL(fr_colsum_finish_kernel, dim3(blocks_of(total_cols, 64)), dim3(64), 0, st, part, nb, (u32)total_cols, acc);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+int launch_g1_mul_keys(hipStream_t st, Affine<FpOps> *out, const KeyDesc *keys, const fr_t *acc, size_t n_keys) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(g1_mul_keys_kernel, dim3(blocks_of(n_keys, 64)), dim3(64), 0, st, out, keys, acc, (u32)n_keys);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// p, f: 3 n_keys values, [which][key]
+int launch_miller_keys(hipStream_t st, const Affine<FpOps> *p, const KeyDesc *keys, size_t n_keys, fp12_t *f) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(miller_keys_kernel, dim3(blocks_of(3 * n_keys, 64)), dim3(64), 0, st, p, keys, (u32)n_keys, f);
   BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }

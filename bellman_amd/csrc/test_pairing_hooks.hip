@@ -270,6 +270,195 @@ int bh_test_pairing_verdict_dev(bh_ctx *ctx, const uint32_t *words, const uint32
   });
 }
 
+// ---- the key-aware kernels (bh_groth16_*_keys): the keys of a set as bh_test_key_layout names them, uploaded as seven
+// buffers (tables, ic_0, lines, flags, f(-alpha, beta), alpha, the descriptors), whose guards follow the hook's own
+struct KeyBufs {
+  DevBuf tables, ic0, lines, qflags, fab, alpha, descs;
+  std::vector<size_t> table_off;   // records before key k's table
+  size_t total_cols = 0, max_in = 0, table_total = 0;
+  bool check(const bh_test_key_layout *k, bool tables_needed) {
+    if (!k || !k->n_keys || k->n_keys > BH_PVK_SET_MAX_KEYS || !k->n_inputs || !k->widths) return false;
+    table_off.assign(k->n_keys, 0);
+    for (size_t i = 0; i < k->n_keys; i++) {
+      if (k->n_inputs[i] > 64 || !width_ok(k->widths[i])) return false;
+      table_off[i] = table_total;
+      table_total += table_entries(k->n_inputs[i], k->widths[i]);
+      total_cols += k->n_inputs[i] + 1;
+      max_in = std::max<size_t>(max_in, k->n_inputs[i]);
+    }
+    return !(tables_needed && table_total && !k->tables);
+  }
+  // appends the seven buffers to the hook's lists from position `at` on
+  void list(const bh_test_key_layout *k, DevBuf **bufs, size_t *sizes, const void **ins, void **outs, int at) {
+    static const char none = 0;
+    const size_t nk = k->n_keys;
+    DevBuf *b[7] = {&tables, &ic0, &lines, &qflags, &fab, &alpha, &descs};
+    const size_t sz[7] = {k->tables ? table_total * sizeof(G1A) : 0, k->ic0 ? nk * sizeof(G1A) : 0,
+                          k->lines ? nk * 3 * MILLER_LINES * sizeof(line_t) : 0, k->qflags ? nk * 12 : 0,
+                          k->f_ab ? nk * sizeof(fp12_t) : 0, k->alpha ? nk * sizeof(G1A) : 0, nk * sizeof(KeyDesc)};
+    const void *in[7] = {k->tables, k->ic0, k->lines, k->qflags, k->f_ab, k->alpha, nullptr};
+    for (int i = 0; i < 7; i++) {
+      bufs[at + i] = b[i];
+      sizes[at + i] = sz[i];
+      ins[at + i] = sz[i] && in[i] ? in[i] : (i == 6 ? nullptr : &none);
+      outs[at + i] = nullptr;
+    }
+  }
+  // the descriptors over the uploaded buffers, written before the launch
+  int write_descs(const bh_test_key_layout *k, hipStream_t st) {
+    std::vector<KeyDesc> d(k->n_keys);
+    u32 col = 0;
+    for (size_t i = 0; i < k->n_keys; i++) {
+      memset(&d[i], 0, sizeof(KeyDesc));
+      d[i].lines = k->lines ? lines.as<line_t>() + i * 3 * MILLER_LINES : nullptr;
+      d[i].qflags = k->qflags ? qflags.as<u32>() + 3 * i : nullptr;
+      d[i].alpha = k->alpha ? alpha.as<G1A>() + i : nullptr;
+      d[i].table = k->tables && k->n_inputs[i] ? tables.as<G1A>() + table_off[i] : nullptr;
+      d[i].ic0 = k->ic0 ? ic0.as<G1A>() + i : nullptr;
+      d[i].f_ab = k->f_ab ? fab.as<fp12_t>() + i : nullptr;
+      d[i].w = k->widths[i];
+      d[i].n_inputs = k->n_inputs[i];
+      d[i].col_off = col;
+      col += k->n_inputs[i] + 1;
+    }
+    BH_HIP_CHECK(hipMemcpyAsync(descs.p, d.data(), d.size() * sizeof(KeyDesc), hipMemcpyHostToDevice, st));
+    BH_HIP_CHECK(hipStreamSynchronize(st));
+    return BH_OK;
+  }
+};
+// every block inside the chunk's n rows and n_scalars inputs, of an existing key, with 1 .. 64 rows
+static bool blocks_ok(const bh_test_key_layout *k, const uint32_t *blocks, size_t nblocks, size_t n, size_t n_scalars) {
+  if (!blocks || !nblocks || nblocks > MAX_N) return false;
+  for (size_t b = 0; b < nblocks; b++) {
+    const uint32_t key = blocks[4 * b], first = blocks[4 * b + 1], count = blocks[4 * b + 2], in_off = blocks[4 * b + 3];
+    if (key >= k->n_keys || !count || count > 64 || (size_t)first + count > n) return false;
+    if ((size_t)in_off + (size_t)count * k->n_inputs[key] > n_scalars) return false;
+  }
+  return true;
+}
+
+int bh_test_pairing_ic_accumulate_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                           const void *inputs, size_t n_scalars, int fmt, size_t n, void *out, uint32_t guards[10]) {
+  KeyBufs kb;
+  if (!ctx || !out || !guards || !n || n > MAX_N || !fmt_ok(fmt) || (n_scalars && !inputs) || !kb.check(keys, true) || !keys->ic0 ||
+      !blocks_ok(keys, blocks, nblocks, n, n_scalars))
+    return BH_ERR_INVALID_ARG;
+  static const char none = 0;
+  DevBuf in, blk, o;
+  DevBuf *bufs[10] = {&in, &blk, &o};
+  size_t sizes[10] = {n_scalars * 32, nblocks * sizeof(KeyBlock), n * sizeof(G1A)};
+  const void *ins[10] = {n_scalars ? inputs : &none, blocks, nullptr};
+  void *outs[10] = {nullptr, nullptr, out};
+  kb.list(keys, bufs, sizes, ins, outs, 3);
+  return BH_STAGE_RUN(10, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_ic_accumulate_keys(st, in.as<fr_t>(), fmt, kb.descs.as<KeyDesc>(), blk.as<KeyBlock>(), nblocks, o.as<G1A>());
+  });
+}
+
+int bh_test_pairing_miller3_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                     const void *a, const void *acc, const void *proofs, const void *blines,
+                                     const uint32_t *bflags, int separate, size_t n, void *f_out, uint32_t guards[14]) {
+  KeyBufs kb;
+  if (!ctx || !a || !acc || !proofs || !blines || !bflags || !f_out || !guards || !n || n > MAX_N || !kb.check(keys, false) ||
+      !keys->lines || !keys->qflags || !blocks_ok(keys, blocks, nblocks, n, ~size_t(0) >> 8))
+    return BH_ERR_INVALID_ARG;
+  DevBuf da, dg, pr, bl, bf, blk, f;
+  DevBuf *bufs[14] = {&da, &dg, &pr, &bl, &bf, &blk, &f};
+  size_t sizes[14] = {n * sizeof(G1A), n * sizeof(G1A), n * sizeof(ProofRec), n * MILLER_LINES * sizeof(line_t), n * 4,
+                      nblocks * sizeof(KeyBlock), (separate ? 3 : 1) * n * sizeof(fp12_t)};
+  const void *ins[14] = {a, acc, proofs, blines, bflags, blocks, nullptr};
+  void *outs[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, f_out};
+  kb.list(keys, bufs, sizes, ins, outs, 7);
+  return BH_STAGE_RUN(14, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_miller3_keys(st, da.as<G1A>(), dg.as<G1A>(), pr.as<ProofRec>(), bl.as<line_t>(), bf.as<u32>(),
+                               kb.descs.as<KeyDesc>(), blk.as<KeyBlock>(), nblocks, separate != 0, f.as<fp12_t>(), n);
+  });
+}
+
+int bh_test_pairing_fold3_const_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                         void *f_inout, size_t n, int separate, uint32_t guards[9]) {
+  KeyBufs kb;
+  if (!ctx || !f_inout || !guards || !n || n > MAX_N || !kb.check(keys, false) || !keys->f_ab ||
+      !blocks_ok(keys, blocks, nblocks, n, ~size_t(0) >> 8))
+    return BH_ERR_INVALID_ARG;
+  DevBuf f, blk;
+  DevBuf *bufs[9] = {&f, &blk};
+  size_t sizes[9] = {(separate ? 3 : 1) * n * sizeof(fp12_t), nblocks * sizeof(KeyBlock)};
+  const void *ins[9] = {f_inout, blocks};
+  void *outs[9] = {f_inout, nullptr};
+  kb.list(keys, bufs, sizes, ins, outs, 2);
+  return BH_STAGE_RUN(9, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_fold3_const_keys(st, f.as<fp12_t>(), kb.descs.as<KeyDesc>(), blk.as<KeyBlock>(), nblocks, n, separate != 0);
+  });
+}
+
+int bh_test_pairing_colsum_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *segs, const void *z,
+                                    const void *inputs, size_t n_scalars, int fmt, size_t n, unsigned nb_override, void *acc_inout,
+                                    void *part_out, uint32_t guards[12]) {
+  KeyBufs kb;
+  if (!ctx || !segs || !z || !acc_inout || !part_out || !guards || !n || n > BATCH_CHUNK || (n_scalars && !inputs) || !fmt_ok(fmt) ||
+      nb_override > COLSUM_BLOCKS || !kb.check(keys, false))
+    return BH_ERR_INVALID_ARG;
+  size_t max_seg = 0;
+  for (size_t k = 0; k < keys->n_keys; k++) {
+    const uint32_t first = segs[4 * k], count = segs[4 * k + 1], in_off = segs[4 * k + 2];
+    if ((size_t)first + count > n || (size_t)in_off + (size_t)count * keys->n_inputs[k] > n_scalars) return BH_ERR_INVALID_ARG;
+    max_seg = std::max<size_t>(max_seg, count);
+  }
+  static const char none = 0;
+  DevBuf dz, in, sg, part, acc;
+  DevBuf *bufs[12] = {&dz, &in, &sg, &part, &acc};
+  size_t sizes[12] = {n * 32, n_scalars * 32, keys->n_keys * sizeof(KeySeg), kb.total_cols * COLSUM_BLOCKS * 32, kb.total_cols * 32};
+  const void *ins[12] = {z, n_scalars ? inputs : &none, segs, nullptr, acc_inout};
+  void *outs[12] = {nullptr, nullptr, nullptr, part_out, acc_inout};
+  kb.list(keys, bufs, sizes, ins, outs, 5);
+  return BH_STAGE_RUN(12, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_colsum_keys(st, dz.as<fr_t>(), in.as<fr_t>(), fmt, kb.descs.as<KeyDesc>(), sg.as<KeySeg>(), keys->n_keys,
+                              kb.max_in + 1, kb.total_cols, max_seg, part.as<fr_t>(), acc.as<fr_t>(), nb_override);
+  });
+}
+
+int bh_test_pairing_g1_mul_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const void *acc_mont, void *out,
+                                    uint32_t guards[9]) {
+  KeyBufs kb;
+  if (!ctx || !acc_mont || !out || !guards || !kb.check(keys, false) || !keys->alpha) return BH_ERR_INVALID_ARG;
+  DevBuf acc, o;
+  DevBuf *bufs[9] = {&acc, &o};
+  size_t sizes[9] = {kb.total_cols * 32, keys->n_keys * sizeof(G1A)};
+  const void *ins[9] = {acc_mont, nullptr};
+  void *outs[9] = {nullptr, out};
+  kb.list(keys, bufs, sizes, ins, outs, 2);
+  return BH_STAGE_RUN(9, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_g1_mul_keys(st, o.as<G1A>(), kb.descs.as<KeyDesc>(), acc.as<fr_t>(), keys->n_keys);
+  });
+}
+
+int bh_test_pairing_miller_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const void *p, void *f_out, uint32_t guards[9]) {
+  KeyBufs kb;
+  if (!ctx || !p || !f_out || !guards || !kb.check(keys, false) || !keys->lines || !keys->qflags) return BH_ERR_INVALID_ARG;
+  DevBuf dp, f;
+  DevBuf *bufs[9] = {&dp, &f};
+  size_t sizes[9] = {3 * keys->n_keys * sizeof(G1A), 3 * keys->n_keys * sizeof(fp12_t)};
+  const void *ins[9] = {p, nullptr};
+  void *outs[9] = {nullptr, f_out};
+  kb.list(keys, bufs, sizes, ins, outs, 2);
+  return BH_STAGE_RUN(9, {
+    const int rc = kb.write_descs(keys, st);
+    if (rc) return rc;
+    return launch_miller_keys(st, dp.as<G1A>(), kb.descs.as<KeyDesc>(), keys->n_keys, f.as<fp12_t>());
+  });
+}
+
 int bh_test_pairing_final_exp_dev(bh_ctx *ctx, const void *f, size_t n, void *out, uint32_t *is_one_out, uint32_t guards[4]) {
   if (!ctx || !f || !out || !is_one_out || !guards || !n || n > 4096) return BH_ERR_INVALID_ARG;
   DevBuf df, o, io, ws;

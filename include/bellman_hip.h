@@ -520,6 +520,57 @@ int bh_groth16_verify_each_compressed(const bh_pvk *pvk, const void *bytes, size
                                       size_t n_inputs, int scalar_fmt, int32_t *verdicts, uint32_t *status, size_t *n_bad);
 /* before bh_ctx_destroy of the key's context (the key's device memory lives in the context's pool) */
 void bh_groth16_pvk_release(bh_pvk *pvk);
+/* ---- proofs of several verifying keys in one call -------------------------------------------------------------------
+ * bh_pvk_set: 1 .. BH_PVK_SET_MAX_KEYS prepared keys of ONE context, addressed by their position.  The caller keeps
+ * owning the keys; they must outlive the set.  The same key may appear twice.  bh_groth16_pvk_set_create returns
+ * BH_ERR_INVALID_ARG for a null entry, keys of different contexts, or n_keys outside 1 .. BH_PVK_SET_MAX_KEYS.  The set
+ * owns one small device table of per-key descriptors (the key's lines and flags, alpha, input count; and, once a
+ * bh_groth16_verify_each_keys* call has needed them, the key's ic window table, its width, ic_0 and f(-alpha, beta)).  What
+ * bh_groth16_verify_each adds to a key is still built once per KEY, by the first call that needs it, single-key or
+ * multi-key; the table budget and the 8 / 4 / 2 / 1-bit fallback apply per key, so keys of one set may have different
+ * widths.  A set is immutable once its descriptors are written: usable from several threads at once.  Release the set
+ * before its keys and before bh_ctx_destroy.
+ *
+ * In the calls below proof j belongs to key key_of[j] (a position in the set).  `inputs` is RAGGED: the concatenation, in
+ * proof order, of bh_groth16_pvk_num_inputs(key key_of[j]) scalars for proof j; n_inputs_total must equal that sum.
+ * Call-level errors, before any work and before any output is written: BH_ERR_INVALID_ARG (a null set or key_of, a scalar
+ * format, some key_of[j] >= bh_groth16_pvk_set_len), then BH_ERR_INVALID_VERIFYING_KEY when n_inputs_total is not the sum
+ * (batch.rs:101-107 for every proof's own key), then BH_ERR_INVALID_ARG for any other null argument that is needed.
+ * n_proofs = 0 is BH_OK.  Rows are grouped by key on the host for the
+ * device (every 64-lane block works for one key) and results return in the caller's order: the outcome does not depend
+ * on how the keys interleave. */
+#define BH_PVK_SET_MAX_KEYS 64
+typedef struct bh_pvk_set bh_pvk_set;
+int bh_groth16_pvk_set_create(const bh_pvk *const *pvks, size_t n_keys, bh_pvk_set **out);
+/* the number of keys (0 for NULL) */
+size_t bh_groth16_pvk_set_len(const bh_pvk_set *set);
+void bh_groth16_pvk_set_release(bh_pvk_set *set);
+/* verdicts[j] is the code bh_groth16_verify(key key_of[j], proof_j, inputs_j, its input count, scalar_fmt) returns for that
+ * proof alone.  Return value, *n_bad and chunking as for bh_groth16_verify_each: chunks of at most 16384 proofs, each on the
+ * call's own stream with one download and one synchronisation; thread-safe. */
+int bh_groth16_verify_each_keys(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, size_t n_proofs,
+                                const void *inputs, size_t n_inputs_total, int scalar_fmt, int32_t *verdicts, size_t *n_bad);
+/* The same over n_proofs x 192 B as Proof::write emits them: verdicts[j] and status[j] (optional) are what
+ * bh_groth16_verify_each_compressed defines for proof j under key key_of[j]. */
+int bh_groth16_verify_each_keys_compressed(const bh_pvk_set *set, const uint32_t *key_of, const void *bytes, size_t n_proofs,
+                                           const void *inputs, size_t n_inputs_total, int scalar_fmt, int32_t *verdicts,
+                                           uint32_t *status, size_t *n_bad);
+/* The batch check over proofs of several keys.  With E_j the value whose being 1 is proof j's verification equation under
+ * its own key, BH_OK exactly when prod_j E_j^{z_j} = 1: the product over the keys of the values bh_groth16_batch_verify
+ * tests key by key, under ONE final exponentiation.  Everything else as in the single-key call: a z_j that is 0 mod q gives
+ * BH_ERR_INVALID_ARG, a point off its curve BH_ERR_INVALID_POINT (before BH_ERR_INVALID_PROOF).  A key of the set that has
+ * no proof in the batch takes no part.
+ * THE z_j MUST BE DRAWN AFTER THE BATCH IS FIXED, from a CSPRNG, and the rule holds ACROSS keys: whoever knows z beforehand
+ * can make the errors of bad proofs cancel - inside one key, as in bh_groth16_batch_verify, and equally between proofs of
+ * DIFFERENT keys, since all of them meet in one product. */
+int bh_groth16_batch_verify_keys(const bh_pvk_set *set, const uint32_t *key_of, const void *proofs, size_t n_proofs,
+                                 const void *inputs, size_t n_inputs_total, int scalar_fmt, const void *z);
+/* The same from the bytes of Proof::write, as bh_groth16_batch_verify_compressed: a proof that fails to read ends the call
+ * with the reader's code for the first such proof of its chunk in the CALLER's order, and *bad_index (optional) is its
+ * position in the caller's order. */
+int bh_groth16_batch_verify_keys_compressed(const bh_pvk_set *set, const uint32_t *key_of, const void *bytes, size_t n_proofs,
+                                            const void *inputs, size_t n_inputs_total, int scalar_fmt, const void *z,
+                                            size_t *bad_index);
 /* ---- R1CS resident in HBM: constraint evaluation as sparse matrix x witness --------
  * The reference evaluates the A/B/C linear combinations of every constraint on one host thread
  * during synthesis (groth16/src/prover.rs:19-55 `eval`, :105-145 `enforce`).  The matrices are a

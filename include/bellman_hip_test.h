@@ -328,6 +328,47 @@ int bh_test_pairing_fold3_const_dev(bh_ctx *ctx, void *f_inout, const void *c, s
 int bh_test_pairing_verdict_dev(bh_ctx *ctx, const uint32_t *words, const uint32_t *pflags, const uint32_t *qflags,
                                 const uint32_t *is_one, size_t n, int32_t *verdicts_out, uint32_t guards[5]);
 int bh_test_pairing_final_exp_dev(bh_ctx *ctx, const void *f, size_t n, void *out, uint32_t *is_one_out, uint32_t guards[4]);
+/* The key-aware kernels of the calls over a bh_pvk_set, each through its launch function (launch_ic_accumulate_keys,
+ * launch_miller3_keys, launch_fold3_const_keys, launch_colsum_keys, launch_g1_mul_keys, launch_miller_keys;
+ * tests/test_gpu_verify_keys_stages.py).  bh_test_key_layout names the keys: n_inputs and widths (1, 2, 4, 8) per key, the
+ * keys' window tables one after another (key k: n_inputs[k] x 256 / w x (2^w - 1) records), and per key ic_0, the 3 x 68
+ * lines of -gamma, -delta, beta with their 3 flag words, f(-alpha, beta) and alpha; an array that the kernel of a hook does
+ * not read may be NULL.  The hook uploads them as seven buffers - tables, ic_0, lines, flags, f(-alpha, beta), alpha,
+ * descriptors - whose guards FOLLOW the hook's own in `guards`, and writes the descriptor table (column offsets: the keys'
+ * n_inputs + 1 columns side by side) before the launch.  blocks: nblocks x {key, first row, row count 1 .. 64, first
+ * scalar}; segs: n_keys x {first row, row count, first scalar, 0}.  Refused before any launch: a key, row or scalar out of
+ * range in blocks or segs, more than 64 keys or inputs per key, an array that the kernel reads left NULL.
+ * ic_accumulate_keys: inputs n_scalars values, out n records.  guards: [inputs, blocks, out] + 7.
+ * miller3_keys: as miller3 with pairs = 7.  guards: [a, acc, proofs, blines, bflags, blocks, f] + 7.
+ * fold3_const_keys: guards [f, blocks] + 7.
+ * colsum_keys: acc_inout and part_out hold the set's total columns (x COLSUM_BLOCKS for part).  guards: [z, inputs, segs,
+ *   part, acc] + 7.
+ * g1_mul_keys: out[k] = [acc_mont[column offset of k]] alpha_k.  guards: [acc, out] + 7.
+ * miller_keys: p and f_out 3 n_keys values, [which][key].  guards: [p, f] + 7. */
+typedef struct bh_test_key_layout {
+  size_t n_keys;
+  const uint32_t *n_inputs;
+  const uint32_t *widths;
+  const void *tables;
+  const void *ic0;
+  const void *lines;
+  const uint32_t *qflags;
+  const void *f_ab;
+  const void *alpha;
+} bh_test_key_layout;
+int bh_test_pairing_ic_accumulate_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                           const void *inputs, size_t n_scalars, int fmt, size_t n, void *out, uint32_t guards[10]);
+int bh_test_pairing_miller3_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                     const void *a, const void *acc, const void *proofs, const void *blines,
+                                     const uint32_t *bflags, int separate, size_t n, void *f_out, uint32_t guards[14]);
+int bh_test_pairing_fold3_const_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *blocks, size_t nblocks,
+                                         void *f_inout, size_t n, int separate, uint32_t guards[9]);
+int bh_test_pairing_colsum_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const uint32_t *segs, const void *z,
+                                    const void *inputs, size_t n_scalars, int fmt, size_t n, unsigned nb_override, void *acc_inout,
+                                    void *part_out, uint32_t guards[12]);
+int bh_test_pairing_g1_mul_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const void *acc_mont, void *out,
+                                    uint32_t guards[9]);
+int bh_test_pairing_miller_keys_dev(bh_ctx *ctx, const bh_test_key_layout *keys, const void *p, void *f_out, uint32_t guards[9]);
 
 /* ---- the powers-of-tau check (csrc/ptau_rlc.cuh, compiled into this library by csrc/test_ceremony_hooks.hip) -----------
  * bh_test_ptau_rlc_host / _dev: the `count` coefficients of vector v (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1)

@@ -48,6 +48,11 @@ pub struct BhProofJob {
 pub struct BhPvk {
     _private: [u8; 0],
 }
+/// opaque `bh_pvk_set`
+#[repr(C)]
+pub struct BhPvkSet {
+    _private: [u8; 0],
+}
 /// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -248,6 +253,13 @@ extern "C" {
     pub fn bh_groth16_verify_each(pvk: *const BhPvk, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, verdicts: *mut i32, n_bad: *mut usize) -> c_int;
     pub fn bh_groth16_verify_each_compressed(pvk: *const BhPvk, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs: usize, scalar_fmt: c_int, verdicts: *mut i32, status: *mut u32, n_bad: *mut usize) -> c_int;
     pub fn bh_groth16_pvk_release(pvk: *mut BhPvk);
+    pub fn bh_groth16_pvk_set_create(pvks: *const *const BhPvk, n_keys: usize, out: *mut *mut BhPvkSet) -> c_int;
+    pub fn bh_groth16_pvk_set_len(set: *const BhPvkSet) -> usize;
+    pub fn bh_groth16_pvk_set_release(set: *mut BhPvkSet);
+    pub fn bh_groth16_verify_each_keys(set: *const BhPvkSet, key_of: *const u32, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs_total: usize, scalar_fmt: c_int, verdicts: *mut i32, n_bad: *mut usize) -> c_int;
+    pub fn bh_groth16_verify_each_keys_compressed(set: *const BhPvkSet, key_of: *const u32, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs_total: usize, scalar_fmt: c_int, verdicts: *mut i32, status: *mut u32, n_bad: *mut usize) -> c_int;
+    pub fn bh_groth16_batch_verify_keys(set: *const BhPvkSet, key_of: *const u32, proofs: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs_total: usize, scalar_fmt: c_int, z: *const c_void) -> c_int;
+    pub fn bh_groth16_batch_verify_keys_compressed(set: *const BhPvkSet, key_of: *const u32, bytes: *const c_void, n_proofs: usize, inputs: *const c_void, n_inputs_total: usize, scalar_fmt: c_int, z: *const c_void, bad_index: *mut usize) -> c_int;
     pub fn bh_r1cs_create(ctx: *mut BhCtx, n_inputs: usize, n_aux: usize, n_constraints: usize, abc: *const BhCsr, coeffs: *const c_void, n_coeffs: usize, out: *mut *mut BhR1cs) -> c_int;
     pub fn bh_r1cs_release(r: *mut BhR1cs);
     pub fn bh_r1cs_shape(r: *const BhR1cs, n_inputs: *mut usize, n_aux: *mut usize, n_constraints: *mut usize) -> c_int;
