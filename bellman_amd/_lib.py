@@ -48,6 +48,7 @@ EXPORTS = [
     "bh_groth16_verify_each_keys_compressed", "bh_groth16_batch_verify_keys", "bh_groth16_batch_verify_keys_compressed",
     "bh_bases_validate", "bh_pairing_product_is_one", "bh_powers_of_tau_verify",
     "bh_bases_first_difference", "bh_pairing_same_ratio_each", "bh_groth16_params_verify_step",
+    "bh_point_mul_each_dev", "bh_bases_scale_powers", "bh_powers_of_tau_contribute",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -69,6 +70,7 @@ TEST_EXPORTS = [
     "bh_test_pairing_colsum_keys_dev", "bh_test_pairing_g1_mul_keys_dev", "bh_test_pairing_miller_keys_dev",
     "bh_test_ptau_rlc_host", "bh_test_ptau_rlc_dev", "bh_test_ptau_sums",
     "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
+    "bh_test_glv_split_host", "bh_test_glv_ladder_host", "bh_test_glv_ladder_dev",
 ]
 
 
@@ -304,6 +306,13 @@ def load():
     lib.bh_test_records_differ_host.argtypes = [i32, vp, vp, sz, vp]
     lib.bh_test_compare_shape.argtypes = [vp]
     lib.bh_test_compare_shape.restype = None
+    lib.bh_point_mul_each_dev.argtypes = [vp, i32, vp, vp, sz, i32, vp, vp]
+    lib.bh_bases_scale_powers.argtypes = [vp, vp, vp, vp, c.POINTER(vp)]
+    lib.bh_powers_of_tau_contribute.argtypes = [vp, vp, vp, vp, vp, c.POINTER(vp), vp]
+    lib.bh_test_glv_split_host.argtypes = [vp, vp, vp, sz]
+    lib.bh_test_glv_split_host.restype = None
+    lib.bh_test_glv_ladder_host.argtypes = [i32, vp, vp, vp, sz, vp]
+    lib.bh_test_glv_ladder_dev.argtypes = [vp, i32, vp, vp, vp, sz, vp]
     lib.bh_test_pairing.argtypes = [vp, sz, vp, vp, vp]
     lib.bh_test_pairing_host.argtypes = [sz, vp, vp, vp]
     lib.bh_test_pairing_host.restype = None

@@ -3,7 +3,9 @@ bh_pairing_product_is_one; include/bellman_hip.h).  `Parameters.from_powers_of_t
 that the four vectors and beta_g2 are powers of ONE (tau, alpha, beta), by random linear combinations and pairings on the
 device.  For the circuit-specific ceremony that follows (contributors rescaling delta): `Parameters.verify_step` checks one
 step, `contribute` / `verify_contributions` make and check the contribution proofs (bh_pairing_same_ratio_each),
-`tau_is_root_of_unity` is the test a transcript needs beside its consistency.  Not covered: deriving the challenge points
+`tau_is_root_of_unity` is the test a transcript needs beside its consistency.  Producing a transcript:
+`new_powers_of_tau`, `contribute_powers_of_tau` (bh_powers_of_tau_contribute) and the receiver's
+`verify_powers_of_tau_update`.  Not covered: deriving the challenge points
 (hashing a ceremony's transcript to G2) and the parsing of any ceremony's file format."""
 
 import ctypes
@@ -136,6 +138,116 @@ def verify_contributions(worker, delta_g1_first, contributions, challenges):
         prev = np.ascontiguousarray(delta_after, dtype=np.uint64)
     rows = same_ratio_each(worker, a, b, A, B)
     return [int(rows[2 * j]) or int(rows[2 * j + 1]) for j in range(n)]
+
+
+# ---- a powers-of-tau ceremony: the starting transcript, one contributor's update, the receiver's check of it -------------------
+# bh_powers_of_tau_contribute multiplies every point of the four vectors by its power of the contributor's secrets (the
+# split-scalar multiplier of csrc/glv.cuh); the check is assembled from the calls above.  AS FOR `contribute`, THE CHALLENGE
+# POINTS ARE THE CALLER'S, and so are the file formats.
+_P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+_G1_GENERATOR = (   # the generators of the Zcash BLS12-381 specification, canonical coordinates
+    0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+    0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1)
+_G2_GENERATOR = (
+    0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
+    0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E,
+    0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
+    0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE)
+SECRETS = ("tau", "alpha", "beta")
+
+
+def _record(coords):
+    """canonical Fp coordinates -> one affine Montgomery record (uint64 words)"""
+    return np.frombuffer(b"".join((c * (1 << 384) % _P).to_bytes(48, "little") for c in coords), dtype=np.uint64).copy()
+
+
+class PowersOfTau(tuple):
+    """(tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2): four `Bases` and one affine G2 record - the argument order of
+    verify_powers_of_tau and Parameters.from_powers_of_tau, so `*transcript` passes it on"""
+    __slots__ = ()
+
+    def __new__(cls, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2):
+        return tuple.__new__(cls, (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, np.ascontiguousarray(beta_g2, dtype=np.uint64).reshape(24)))
+
+    tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2 = (property(lambda self, i=i: self[i]) for i in range(5))
+
+
+def new_powers_of_tau(worker, n_g1, n):
+    """The transcript a ceremony starts from, tau = alpha = beta = 1: every element the generator of its group (n_g1 points
+    of tau_g1, n of each other vector)."""
+    from .multiexp import Bases
+
+    g1, g2 = _record(_G1_GENERATOR), _record(_G2_GENERATOR)
+    return PowersOfTau(Bases(worker, 1, np.tile(g1, (n_g1, 1))), Bases(worker, 2, np.tile(g2, (n, 1))),
+                       Bases(worker, 1, np.tile(g1, (n, 1))), Bases(worker, 1, np.tile(g1, (n, 1))), g2)
+
+
+def contribute_powers_of_tau(worker, transcript, tau, alpha, beta, s_g1, challenges_g2):
+    """One contributor's update of a transcript (bh_powers_of_tau_contribute): (new_transcript, proofs) with T'[i] =
+    [tau^i]T[i], U'[i] = [tau^i]U[i], A'[i] = [alpha tau^i]A[i], B'[i] = [beta tau^i]B[i], beta_g2' = [beta]beta_g2 over the
+    whole length of every vector, and proofs[x] = (s_x, [x]s_x, [x]r_x) for x in "tau", "alpha", "beta" - the convention
+    of `contribute`: s_g1[x] an affine G1 record of the contributor's choice (not the identity), challenges_g2[x] the
+    affine G2 challenge point r_x, which the CALLER derives (by hashing the ceremony's transcript to G2).  tau, alpha,
+    beta: integers mod q, the contributor's secrets; zero raises UnexpectedIdentity.  Validates nothing: run
+    verify_powers_of_tau(validate_points=True) over a transcript before contributing to it."""
+    from .multiexp import Bases, _fr_mont
+
+    secret = dict(zip(SECRETS, (tau, alpha, beta)))
+    t = _PowersOfTau(*[b._h for b in transcript[:4]], transcript.beta_g2.ctypes.data)
+    out = (ctypes.c_void_p * 4)()
+    beta_g2 = np.zeros(24, dtype=np.uint64)
+    check(_lib.load().bh_powers_of_tau_contribute(worker.ctx, ctypes.byref(t), *[_fr_mont(secret[x]) for x in SECRETS], out,
+                                                  beta_g2.ctypes.data_as(ctypes.c_void_p)), "contribute_powers_of_tau")
+    vecs = []
+    for v, before in enumerate(transcript[:4]):
+        b = Bases.__new__(Bases)
+        b.worker, b.group, b.n, b._h = worker, before.group, len(before), ctypes.c_void_p(out[v])
+        vecs.append(b)
+    proofs = {x: (np.ascontiguousarray(s_g1[x], dtype=np.uint64), _mul(1, s_g1[x], secret[x]), _mul(2, challenges_g2[x], secret[x]))
+              for x in SECRETS}
+    return PowersOfTau(*vecs, beta_g2), proofs
+
+
+class PtauUpdateReport:
+    """What verify_powers_of_tau_update found: `transcript_failed` = the FAILED_* bits of verify_powers_of_tau(after),
+    `rows` = the six same-ratio verdicts (2 i: the proof of SECRETS[i] itself, 2 i + 1: that secret against the step
+    T[1] / A[0] / B[0]), `generators_unchanged` = T[0] and U[0] are the records of `before`; `ok` when all of it holds"""
+
+    def __init__(self, transcript_failed, rows, generators_unchanged):
+        self.transcript_failed, self.rows, self.generators_unchanged = transcript_failed, rows, generators_unchanged
+        self.ok = transcript_failed == 0 and not any(rows) and generators_unchanged
+
+
+def verify_powers_of_tau_update(worker, before, after, proofs, challenges_g2, seed=None, validate_points=True):
+    """The receiver's check that `after` is `before` updated by ONE contributor who knows the secrets behind `proofs`
+    (as contribute_powers_of_tau returns them; challenges_g2[x] the challenge point the receiver derived).  Three steps,
+    existing calls only:
+      1. verify_powers_of_tau(after): `after` is powers of one (tau', alpha', beta') over g1' = T'[0], g2' = U'[0];
+      2. one same_ratio_each call of six rows - for each secret x: (s_x, [x]s_x) against (r_x, [x]r_x), knowledge of x;
+         and (T[1], T'[1]) / (A[0], A'[0]) / (B[0], B'[0]) against the same G2 pair, the step taken IS x;
+      3. bases_first_difference: T'[0] = T[0] and U'[0] = U[0], the generators are unchanged.
+    That is the whole update: a consistent `after` is determined by its generators and its three secrets; 3 fixes the
+    generators, and the step rows give tau' = tau x_tau from T[1], alpha' = alpha x_alpha from A[0] = [alpha]g1, beta' =
+    beta x_beta from B[0] - every other element, beta_g2 included (equation BETA_G2 of step 1), then follows.  `before`
+    is assumed verified (it was the previous `after`).  With the caller: deriving the challenge points from the
+    ceremony's transcript, and the file formats.  `seed`: the rule of verify_powers_of_tau.  Points that fail
+    validation raise as there.  Returns a PtauUpdateReport; nothing is raised for a failed check."""
+    try:
+        failed = verify_powers_of_tau(worker, *after, seed=seed, validate_points=validate_points).failed
+    except InvalidTranscript as e:
+        failed = e.report.failed
+    a, b, A, B = np.zeros((6, 12), np.uint64), np.zeros((6, 12), np.uint64), np.zeros((6, 24), np.uint64), np.zeros((6, 24), np.uint64)
+    step = ((0, 1), (2, 0), (3, 0))   # (vector, index) of the element a secret's step is read from
+    for i, x in enumerate(SECRETS):
+        s, xs, xr = proofs[x]
+        v, at = step[i]
+        a[2 * i], b[2 * i] = s, xs
+        a[2 * i + 1], b[2 * i + 1] = before[v].download(at, 1)[0], after[v].download(at, 1)[0]
+        A[2 * i] = A[2 * i + 1] = challenges_g2[x]
+        B[2 * i] = B[2 * i + 1] = xr
+    rows = [int(r) for r in same_ratio_each(worker, a, b, A, B)]
+    same = all(bases_first_difference(worker, before[v], after[v], 0, 0, 1) == 1 for v in (0, 1))
+    return PtauUpdateReport(failed, rows, same)
 
 
 def tau_is_root_of_unity(worker, tau_g1, m):

@@ -27,6 +27,9 @@ int point_distribute_powers(Context &c, int group, void *pts, u64 n, const fr_t 
 int point_divide_by_z(int group, void *pts, uint32_t log_n, hipStream_t st);
 int point_mul_assign(int group, void *pts, const void *scalars_mont, u64 n, hipStream_t st);
 int point_sub_assign(int group, void *a, const void *b, u64 n, hipStream_t st);
+// point_mul.hip
+int point_mul_each(int group, const void *in, void *out, u64 n, const void *scalars, int fmt, hipStream_t st);
+int point_mul_powers(Context &c, int group, const void *in, void *out, u64 n, const fr_t &cc, const fr_t &g, hipStream_t st);
 // msm.hip
 struct MsmJobImpl;
 MsmJobImpl *msm_job_new(Context *ctx, int group);
@@ -1452,6 +1455,43 @@ int bh_fixed_base_mul_dev(bh_ctx *ctx, int group, const void *base_affine_host, 
   if (hipStreamSynchronize(st) != hipSuccess && rc == BH_OK) rc = BH_ERR_HIP;
   ctx->c.pool.release(table);
   return rc;
+}
+
+int bh_point_mul_each_dev(bh_ctx *ctx, int group, const void *in_dev, const void *scalars_dev, size_t n, int scalar_fmt,
+                          void *out_dev, void *stream) {
+  if (!ctx || !group_ok(group) || (scalar_fmt != BH_SCALARS_CANONICAL && scalar_fmt != BH_SCALARS_MONT)) return BH_ERR_INVALID_ARG;
+  if (!n) return BH_OK;
+  if (!in_dev || !scalars_dev || !out_dev) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = pick_stream(ctx, stream);
+  int rc = point_mul_each(group, in_dev, out_dev, n, scalars_dev, scalar_fmt, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == BH_OK) rc = BH_ERR_HIP;
+  return rc;
+}
+
+int bh_bases_scale_powers(bh_ctx *ctx, const bh_bases *in, const void *c_mont, const void *g_mont, bh_bases **out) {
+  if (!ctx || !in || !c_mont || !g_mont || !out) return BH_ERR_INVALID_ARG;
+  *out = nullptr;
+  fr_t c, g, t;
+  memcpy(&c, c_mont, sizeof c);
+  memcpy(&g, g_mont, sizeof g);
+  fe_from_mont(t, c);
+  const bool c_zero = fe_is_zero(t);
+  fe_from_mont(t, g);
+  if (c_zero || fe_is_zero(t)) return BH_ERR_UNEXPECTED_IDENTITY;
+  const size_t rec = in->group == BH_G1 ? 96 : 192;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  DevGuard dev;
+  BH_HIP_CHECK(hipMalloc(&dev.p, in->n ? in->n * rec : 16));
+  if (in->n) {
+    void *st = nullptr;   // a stream of its own: concurrent with other work on the context
+    int rc = bh_stream_create(ctx, &st);
+    if (rc) return rc;
+    rc = point_mul_powers(ctx->c, in->group, in->dev, dev.p, in->n, c, g, (hipStream_t)st);
+    bh_stream_destroy(ctx, st);
+    if (rc) return rc;
+  }
+  return new_bases(ctx, in->group, dev.release(), in->n, true, out);
 }
 
 void bh_point_mul(int group, void *r, const void *a, const void *k_canonical) { host_point_mul(group, r, a, k_canonical); }

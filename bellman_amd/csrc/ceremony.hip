@@ -4,6 +4,8 @@
 // of a circuit-specific contribution needs: bh_pairing_same_ratio_each (one verdict per equation e(a, B) = e(b, A): the
 // contribution proofs) and bh_groth16_params_verify_step - byte comparison of everything a step must leave alone
 // (bh_bases_first_difference, api.hip), one linear combination per side of h and l (phase2_sums.cuh), three equations.
+// And what a CONTRIBUTOR to a transcript runs: bh_powers_of_tau_contribute, four bh_bases_scale_powers (api.hip; the
+// split-scalar multiplier of point_mul.hip) and one host multiplication.
 //
 // The pairings run through the verifier's own launch functions (pairing_kernels.cuh, compiled in pairing.hip - the one
 // unit of this library that includes that header - and declared here): the lines of every Q, one Miller lane per pair,
@@ -238,6 +240,42 @@ int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *
   for (size_t k = 0; k < m; k++)
     if (one[k] != 1) rep.failed |= bit[k];
   return rep.failed ? BH_ERR_INVALID_TRANSCRIPT : BH_OK;
+}
+
+int bh_powers_of_tau_contribute(bh_ctx *ctx, const bh_powers_of_tau *before, const void *tau_mont, const void *alpha_mont,
+                                const void *beta_mont, bh_bases *out[4], void *beta_g2_out) {
+  if (!ctx || !before || !tau_mont || !alpha_mont || !beta_mont || !out || !beta_g2_out || !before->tau_g1 || !before->tau_g2 ||
+      !before->alpha_tau_g1 || !before->beta_tau_g1 || !before->beta_g2)
+    return BH_ERR_INVALID_ARG;
+  const bh_bases *vec[4] = {before->tau_g1, before->tau_g2, before->alpha_tau_g1, before->beta_tau_g1};
+  for (int v = 0; v < 4; v++) {
+    out[v] = nullptr;
+    if (bases_group(vec[v]) != (v == 1 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
+  }
+  fr_t secret[3], canon[3], one;   // tau, alpha, beta
+  const void *src[3] = {tau_mont, alpha_mont, beta_mont};
+  for (int k = 0; k < 3; k++) {
+    memcpy(&secret[k], src[k], sizeof(fr_t));
+    fe_from_mont(canon[k], secret[k]);
+    if (fe_is_zero(canon[k])) return BH_ERR_UNEXPECTED_IDENTITY;
+  }
+  fe_one(one);
+  const fr_t *scale[4] = {&one, &one, &secret[1], &secret[2]};
+  for (int v = 0; v < 4; v++) {   // each on a stream of its own (bh_bases_scale_powers)
+    const int rc = bh_bases_scale_powers(ctx, vec[v], scale[v], &secret[0], &out[v]);
+    if (rc) {
+      for (int w = 0; w < v; w++) {
+        bh_bases_release(ctx, out[w]);
+        out[w] = nullptr;
+      }
+      return rc;
+    }
+  }
+  Affine<Fp2Ops> b2, r2;
+  memcpy(&b2, before->beta_g2, sizeof b2);
+  bh_point_mul(BH_G2, &r2, &b2, &canon[2]);
+  memcpy(beta_g2_out, &r2, sizeof r2);
+  return BH_OK;
 }
 
 int bh_pairing_same_ratio_each(bh_ctx *ctx, const void *a_g1, const void *b_g1, const void *A_g2, const void *B_g2, size_t n,

@@ -206,6 +206,18 @@ class Bases:
         self._auto_precompute()
         return self
 
+    def scale_powers(self, c, g):
+        """A new `Bases` with record i = [c g^i] of this vector's record i, for integers c, g mod q
+        (bh_bases_scale_powers: the split-scalar multiplier, one lane per point).  c = 0 or g = 0 raises
+        UnexpectedIdentity.  This vector is left unchanged; the points are not validated."""
+        new = Bases.__new__(Bases)
+        new.worker, new.group, new.n = self.worker, self.group, self.n
+        h = ctypes.c_void_p()
+        check(_lib.load().bh_bases_scale_powers(self.worker.ctx, self._h, _fr_mont(c), _fr_mont(g), ctypes.byref(h)),
+              "bases_scale_powers")
+        new._h = h
+        return new
+
     def __len__(self):
         return self.n
 
@@ -356,6 +368,41 @@ def multiexp_sharded(workers, shards, density_map, exponents, skip=0, mont=False
         return out
 
     return Waiter(fn=finish)
+
+
+_Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
+def _fr_mont(x):
+    """the 32-byte Montgomery form of an integer mod q (little-endian)"""
+    return ((x % _Q) * (1 << 256) % _Q).to_bytes(32, "little")
+
+
+def point_mul_each(worker, group, points, scalars, mont=False):
+    """out[i] = [scalars[i]] points[i] over affine records ([n, 12|24] uint64) and [n, 4] uint64 scalars (canonical
+    little-endian, taken mod q, unless `mont`), on the device by the split-scalar multiplier (bh_point_mul_each_dev).
+    The identity is the all-zero record; the points are not validated and must lie in the prime-order subgroup."""
+    lib = _lib.load()
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, _WORDS[group])
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    n = len(pts)
+    assert len(sc) == n
+    out = np.zeros_like(pts)
+    if not n:
+        return out
+    d_pts, d_sc = ctypes.c_void_p(), ctypes.c_void_p()
+    check(lib.bh_dev_alloc(worker.ctx, pts.nbytes, ctypes.byref(d_pts)), "dev_alloc")
+    try:
+        check(lib.bh_dev_alloc(worker.ctx, sc.nbytes, ctypes.byref(d_sc)), "dev_alloc")
+        check(lib.bh_dev_upload(worker.ctx, d_pts, pts.ctypes.data_as(ctypes.c_void_p), pts.nbytes), "dev_upload")
+        check(lib.bh_dev_upload(worker.ctx, d_sc, sc.ctypes.data_as(ctypes.c_void_p), sc.nbytes), "dev_upload")
+        check(lib.bh_point_mul_each_dev(worker.ctx, group, d_pts, d_sc, n, 1 if mont else 0, d_pts, None), "point_mul_each")
+        check(lib.bh_dev_download(worker.ctx, out.ctypes.data_as(ctypes.c_void_p), d_pts, pts.nbytes), "dev_download")
+    finally:
+        if d_sc:
+            lib.bh_dev_free(worker.ctx, d_sc)
+        lib.bh_dev_free(worker.ctx, d_pts)
+    return out
 
 
 def point_add(group, a, b):

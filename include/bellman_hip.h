@@ -389,6 +389,15 @@ int bh_msm_sharded_wait(bh_msm_sharded_job *job, void *out_affine);
 int bh_fixed_base_mul_dev(bh_ctx *ctx, int group, const void *base_affine_host,
                           const void *scalars_dev, size_t n, int scalar_fmt, void *out_dev,
                           void *stream);
+/* ---- variable-base scalar multiplication, one scalar per point: out[i] = [s_i] in[i] over affine records on the device
+ * (identity = the all-zero record; the points are NOT validated and must lie in the prime-order subgroup, where the
+ * endomorphism acts as a scalar).  The split-scalar ladder of csrc/glv.cuh: s = s1 + s2 lambda with two 128-bit halves,
+ * 128 joint double-and-add steps over a free three-entry table (csrc/point_mul.hip) instead of the 255
+ * steps of bh_point_mul_assign_dev.  scalars_dev: n scalars of 32 bytes in scalar_fmt (a canonical-format value is taken
+ * mod q).  out_dev may be in_dev.  The call returns when the results are in out_dev (it waits for the stream); n = 0 does
+ * nothing; a bad group or format is BH_ERR_INVALID_ARG. */
+int bh_point_mul_each_dev(bh_ctx *ctx, int group, const void *in_dev, const void *scalars_dev, size_t n, int scalar_fmt,
+                          void *out_dev, void *stream);
 
 /* ---- groth16::create_proof (groth16/src/prover.rs:182-361) --------------------------------------
  * bh_params = `&Parameters` as ParameterSource (groth16/src/lib.rs:435-473): the verifying-key
@@ -652,6 +661,24 @@ int bh_groth16_generate_from_powers_of_tau(bh_ctx *ctx, bh_r1cs *r1cs, const bh_
  * one contributor's step of a circuit-specific ceremony; the receiver checks the step with bh_groth16_params_verify_step
  * and the contribution proofs with bh_pairing_same_ratio_each (below). */
 int bh_groth16_params_rescale_delta(const bh_params *p, const void *d_mont, bh_params **out);
+/* ---- contributing to a transcript (what a phase-1 contributor runs; the receiver's side is bh_powers_of_tau_verify plus
+ * bh_pairing_same_ratio_each below) --------------------------------------------------------------------------------------
+ * bh_bases_scale_powers: a NEW handle with out[i] = [c g^i] in[i] for c, g Montgomery Fr on the host, by
+ * bh_point_mul_each_dev's kernel over a device vector of the powers.  The handle is registered like any other (so it
+ * gets the automatic window table) and is released with bh_bases_release; `in` is left unchanged.  c = 0 or g = 0 is
+ * BH_ERR_UNEXPECTED_IDENTITY.  Runs on a stream of its own: thread-safe.
+ * bh_powers_of_tau_contribute: out[0..3] = new handles T'[i] = [tau^i] T[i], U'[i] = [tau^i] U[i], A'[i] = [alpha tau^i]
+ * A[i], B'[i] = [beta tau^i] B[i] over the WHOLE length of every vector of `before`, and beta_g2_out (192 bytes on the
+ * host) = [beta] beta_g2 (bh_point_mul).  tau, alpha, beta: Montgomery Fr on the host, the contributor's secrets - the
+ * caller erases them; a zero secret is BH_ERR_UNEXPECTED_IDENTITY, a null or wrong-group handle BH_ERR_INVALID_ARG; on
+ * an error no handle is returned.  THIS CALL VALIDATES NOTHING: neither that the points are on their curves and in the
+ * prime-order subgroups - read the transcript with bh_bases_read_uncompressed / _compressed and BH_POINTS_CHECKED, or run
+ * bh_bases_validate over the handles, for that - nor that the four vectors and beta_g2 are consistent powers of one
+ * (tau, alpha, beta), which takes pairings: bh_powers_of_tau_verify below makes both checks.  Each vector runs on a stream
+ * of its own: thread-safe and concurrent with other work on the context. */
+int bh_bases_scale_powers(bh_ctx *ctx, const bh_bases *in, const void *c_mont, const void *g_mont, bh_bases **out);
+int bh_powers_of_tau_contribute(bh_ctx *ctx, const bh_powers_of_tau *before, const void *tau_mont, const void *alpha_mont,
+                                const void *beta_mont, bh_bases *out[4], void *beta_g2_out);
 /* ---- checking a transcript before deriving parameters from it -----------------------------------------------------------
  * bh_pairing_product_is_one: *is_one = (prod_i e(P_i, Q_i) == 1) over n pairs of affine records on the host (96 B / 192 B
  * each): the lines of every Q_i, one Miller lane per pair, the product, one final exponentiation - the verifier's kernels.

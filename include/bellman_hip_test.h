@@ -394,6 +394,16 @@ int bh_test_phase2_sums(bh_ctx *ctx, const bh_params *before, const bh_params *a
 int bh_test_records_differ_host(int group, const void *a, const void *b, size_t n, unsigned char *out);
 void bh_test_compare_shape(uint32_t out2[2]);
 
+/* ---- the split-scalar point multiplier (csrc/glv.cuh, compiled into this library by csrc/test_point_mul_hooks.hip) ------
+ * bh_test_glv_split_host: k1[i] = k[i] mod lambda, k2[i] = k[i] div lambda for n canonical scalars k[i] < q (32 bytes each,
+ * little-endian) by the host build of glv_split; k1, k2 hold n x 16 bytes.
+ * bh_test_glv_ladder_host / _dev: out[i] = [k1[i] + k2[i] lambda] points[i] as affine records, for ARBITRARY 128-bit pairs
+ * (n x 16 bytes each) - not only canonical splits, so that a test reaches the equal- and opposite-point branches of the
+ * mixed addition - by the host build of xyzz_mul_glv and by a kernel of one lane per point.  All arrays on the host. */
+void bh_test_glv_split_host(const void *k, void *k1, void *k2, size_t n);
+int bh_test_glv_ladder_host(int group, const void *points, const void *k1, const void *k2, size_t n, void *out);
+int bh_test_glv_ladder_dev(bh_ctx *ctx, int group, const void *points, const void *k1, const void *k2, size_t n, void *out);
+
 /* host only: where bh_msm_sharded_async cuts the exponents for shards of lens[k] bases (cuts_out[n_shards + 1]), and
  * the size class the workspace pool rounds a request up to */
 int bh_test_shard_cuts(const size_t *lens, size_t n_shards, size_t skip, const uint64_t *density_words, size_t n_scalars,

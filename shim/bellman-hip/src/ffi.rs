@@ -233,6 +233,7 @@ extern "C" {
     pub fn bh_msm_sharded_async(ctxs: *const *mut BhCtx, shards: *const *const BhBases, n_shards: usize, skip: usize, scalars_host: *const c_void, n_scalars: usize, scalar_fmt: c_int, density_words: *const u64, density_len: usize, job: *mut *mut BhMsmShardedJob) -> c_int;
     pub fn bh_msm_sharded_wait(job: *mut BhMsmShardedJob, out_affine: *mut c_void) -> c_int;
     pub fn bh_fixed_base_mul_dev(ctx: *mut BhCtx, group: c_int, base_affine_host: *const c_void, scalars_dev: *const c_void, n: usize, scalar_fmt: c_int, out_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn bh_point_mul_each_dev(ctx: *mut BhCtx, group: c_int, in_dev: *const c_void, scalars_dev: *const c_void, n: usize, scalar_fmt: c_int, out_dev: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bh_groth16_params_create(ctx: *mut BhCtx, alpha_g1: *const c_void, beta_g1: *const c_void, beta_g2: *const c_void, delta_g1: *const c_void, delta_g2: *const c_void, h: *const c_void, nh: usize, l: *const c_void, nl: usize, a: *const c_void, na: usize, b_g1: *const c_void, nb1: usize, b_g2: *const c_void, nb2: usize, out: *mut *mut BhParams) -> c_int;
     pub fn bh_groth16_params_read(ctx: *mut BhCtx, bytes: *const c_void, len: usize, checked: c_int, out: *mut *mut BhParams) -> c_int;
     pub fn bh_groth16_generate(ctx: *mut BhCtx, r1cs: *mut BhR1cs, g1: *const c_void, g2: *const c_void, alpha: *const c_void, beta: *const c_void, gamma: *const c_void, delta: *const c_void, tau: *const c_void, out: *mut *mut BhParams) -> c_int;
@@ -271,6 +272,8 @@ extern "C" {
     pub fn bh_r1cs_eval_transposed_points_dev(ctx: *mut BhCtx, r: *mut BhR1cs, group: c_int, matrix: c_int, lagrange_points_dev: *const c_void, out_points_dev: *mut c_void, accumulate: c_int, stream: *mut c_void) -> c_int;
     pub fn bh_groth16_generate_from_powers_of_tau(ctx: *mut BhCtx, r1cs: *mut BhR1cs, t: *const BhPowersOfTau, out: *mut *mut BhParams) -> c_int;
     pub fn bh_groth16_params_rescale_delta(p: *const BhParams, d_mont: *const c_void, out: *mut *mut BhParams) -> c_int;
+    pub fn bh_bases_scale_powers(ctx: *mut BhCtx, r#in: *const BhBases, c_mont: *const c_void, g_mont: *const c_void, out: *mut *mut BhBases) -> c_int;
+    pub fn bh_powers_of_tau_contribute(ctx: *mut BhCtx, before: *const BhPowersOfTau, tau_mont: *const c_void, alpha_mont: *const c_void, beta_mont: *const c_void, out: *mut *mut BhBases, beta_g2_out: *mut c_void) -> c_int;
     pub fn bh_pairing_product_is_one(ctx: *mut BhCtx, g1_affine_host: *const c_void, g2_affine_host: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
     pub fn bh_powers_of_tau_verify(ctx: *mut BhCtx, t: *const BhPowersOfTau, seed32: *const c_void, flags: c_uint, report: *mut BhPtauReport) -> c_int;
     pub fn bh_bases_first_difference(ctx: *mut BhCtx, a: *const BhBases, first_a: usize, b: *const BhBases, first_b: usize, count: usize, index: *mut usize) -> c_int;
