@@ -49,6 +49,7 @@ EXPORTS = [
     "bh_bases_validate", "bh_pairing_product_is_one", "bh_powers_of_tau_verify",
     "bh_bases_first_difference", "bh_pairing_same_ratio_each", "bh_groth16_params_verify_step",
     "bh_point_mul_each_dev", "bh_bases_scale_powers", "bh_powers_of_tau_contribute",
+    "bh_msm_many_async", "bh_msm_many_async_dev", "bh_msm_many_wait", "bh_msm_many_plan_info", "bh_groth16_prove_witness_batch",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -71,6 +72,7 @@ TEST_EXPORTS = [
     "bh_test_ptau_rlc_host", "bh_test_ptau_rlc_dev", "bh_test_ptau_sums",
     "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
     "bh_test_glv_split_host", "bh_test_glv_ladder_host", "bh_test_glv_ladder_dev",
+    "bh_test_groth16_prove_witness_batch_budget", "bh_test_many_stage_dev",
 ]
 
 
@@ -224,6 +226,13 @@ def load():
     lib.bh_msm_async_scalars.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, vp, c.POINTER(vp)]
     lib.bh_msm_async_dev_after.argtypes = [vp, vp, sz, vp, sz, i32, vp, sz, vp, vp, c.POINTER(vp)]
     lib.bh_msm_start.argtypes = [vp]
+    lib.bh_msm_many_async.argtypes = [vp, vp, sz, vp, sz, sz, sz, i32, vp, sz, vp, c.POINTER(vp)]
+    lib.bh_msm_many_async_dev.argtypes = [vp, vp, sz, vp, sz, sz, sz, i32, vp, sz, vp, vp, c.POINTER(vp)]
+    lib.bh_msm_many_wait.argtypes = [vp, vp, vp, c.POINTER(c.c_float), c.POINTER(c.c_uint64)]
+    lib.bh_msm_many_plan_info.argtypes = [sz, sz, i32, c.c_uint, c.c_uint, vp]
+    lib.bh_groth16_prove_witness_batch.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+    lib.bh_test_many_stage_dev.argtypes = [vp, i32, c.c_uint, vp, i32, sz, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp]
+    lib.bh_test_groth16_prove_witness_batch_budget.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, vp]
     lib.bh_h_poly_fr_scalars.argtypes = [vp, vp, vp, vp, sz, c.POINTER(vp)]
     lib.bh_msm_sharded_async.argtypes = [vp, vp, sz, sz, vp, sz, i32, vp, sz, c.POINTER(vp)]
     lib.bh_msm_sharded_wait.argtypes = [vp, vp]

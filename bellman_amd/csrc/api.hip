@@ -37,6 +37,7 @@ void msm_job_delete(MsmJobImpl *j);
 int msm_job_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,
                     int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table);
 int msm_job_finish(MsmJobImpl &job, void *out_affine, float *ms, u64 *stats8 = nullptr);
+int msm_job_finish_many(MsmJobImpl &job, void *out_affine_k, size_t k, float *ms, u64 *stats8, bool *fallback);
 int msm_debug_stages(Context &c, const void *scalars_host, u64 n, int fmt, unsigned cbits, u64 *pairs_out, u32 *zstart_out);
 void msm_job_track(MsmJobImpl &job);
 int msm_job_start(MsmJobImpl &job);
@@ -1165,9 +1166,11 @@ static bool tiny_msm_on_host(const bh_bases *bases, size_t skip, const void *sca
 
 static int msm_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars, bool scalars_on_host,
                       size_t n, int fmt, const uint64_t *density, bool density_on_host, size_t density_len,
-                      const bh_msm_opts *o, bh_msm_job **out, u64 shard_ref_n = 0, void *after_stream = nullptr) {
+                      const bh_msm_opts *o, bh_msm_job **out, u64 shard_ref_n = 0, void *after_stream = nullptr,
+                      u32 many_vectors = 0, u64 many_stride = 0) {
   if (!ctx || !bases || !out) return BH_ERR_INVALID_ARG;
   MsmOpts opts;
+  opts.vectors = many_vectors; opts.scalar_stride = many_stride;   // (a many-job: resident scalars only, bh_msm_many_*)
   if (shard_ref_n) { opts.ref_n = shard_ref_n; opts.always_resolve_ident = true; }
   if (o) {
     if (o->window_bits && (o->window_bits < 2 || o->window_bits > 24)) return BH_ERR_INVALID_ARG;
@@ -1243,6 +1246,199 @@ static int msm_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const voi
   }
   msm_job_track(*impl);
   *out = new bh_msm_job{impl};
+  return BH_OK;
+}
+// ---- several scalar vectors over one base vector in ONE job ---------------------------------------
+struct bh_msm_many_job {
+  bh_ctx *ctx = nullptr;
+  const bh_bases *bases = nullptr;
+  size_t skip = 0, stride = 0, n = 0, k = 0, dlen = 0;
+  int fmt = 0;
+  const void *sc_dev = nullptr;       // resident scalars (the caller's, or this job's upload)
+  const u64 *dn_dev = nullptr;
+  bh_msm_opts o = {0, 0, 0};          // for the ordinary jobs: without BH_MSM_MANY_FORCE
+  std::vector<void *> owned;          // uploads of the host entry, kept until the wait (the error path reads them again)
+  bh_msm_job *many = nullptr;         // the many-plan job, or
+  std::vector<bh_msm_job *> singles;  // k ordinary jobs issued together
+};
+// Where the many-plan replaces k ordinary jobs without being asked to (BH_MSM_MANY_FORCE).  Set from
+// profiles/msm_many_bench.json (tools/bench_msm_many.py): the many-plan is chosen only at shapes where its min-of-5 wall
+// time is below the baseline's by more than the baseline's own spread in that run.
+// Measured (MI355X, G1 2^10 ... 2^20 and G2 2^10 ... 2^18 terms in steps of 4x, k = 2, 4, 8, 16, bases with their
+// automatic window table): the table flavour wins at every measured shape with 4 <= k <= 16 and 2^10 <= n <= 2^18 in both
+// groups (G1 2^12 x 16: 1.02 ms against 2.73; 2^16 x 8: 2.52 against 3.41; G2 2^18 x 16: 35.9 against 47.8); at k = 2 it wins
+// at six shapes of eleven in that run and at three in the run before, and at 2^20 (20-bit rows, 2^19 buckets per vector) nowhere.  The rule covers the measured
+// box and what lies between its points (k = 5 ... 15, the odd powers of two).  Outside it the call issues ordinary jobs:
+// the classic flavour, fewer than 2^10 or more than 2^18 terms, k < 4, and k > 16 - not measured, and the job's workspace
+// grows with k.
+constexpr size_t MANY_RULE_K_MIN = 4, MANY_RULE_K_MAX = 16, MANY_RULE_LOG_N_MIN = 10, MANY_RULE_LOG_N_MAX = 18;
+static bool many_plan_wins(int group, size_t n, size_t k, bool table) {
+  (void)group;
+  return table && k >= MANY_RULE_K_MIN && k <= MANY_RULE_K_MAX && n >= ((size_t)1 << MANY_RULE_LOG_N_MIN) &&
+         n <= ((size_t)1 << MANY_RULE_LOG_N_MAX);
+}
+static void many_job_free(bh_msm_many_job *mj) {
+  for (void *p : mj->owned) mj->ctx->c.pool.release(p);
+  delete mj;
+}
+static int many_issue_singles(bh_msm_many_job *mj, void *after_stream) {
+  for (size_t v = 0; v < mj->k; v++) {
+    bh_msm_job *j = nullptr;
+    const int rc = msm_common(mj->ctx, mj->bases, mj->skip, (const char *)mj->sc_dev + v * mj->stride, false, mj->n, mj->fmt,
+                              mj->dn_dev, false, mj->dlen, &mj->o, &j, 0, after_stream);
+    if (rc != BH_OK) {
+      unsigned char sink[192];
+      for (bh_msm_job *q : mj->singles) (void)bh_msm_wait(q, sink);
+      mj->singles.clear();
+      return rc;
+    }
+    mj->singles.push_back(j);
+  }
+  return BH_OK;
+}
+static int many_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars, bool on_host, size_t stride,
+                       size_t n, size_t k, int fmt, const uint64_t *density, size_t density_len, const bh_msm_opts *opts,
+                       void *after_stream, bh_msm_many_job **out) {
+  if (!ctx || !bases || !out || (k && n && !scalars)) return BH_ERR_INVALID_ARG;
+  if (fmt != BH_SCALARS_CANONICAL && fmt != BH_SCALARS_MONT) return BH_ERR_INVALID_ARG;
+  if (k && (stride % 32 || stride / 32 < n)) return BH_ERR_INVALID_ARG;
+  if (density && density_len != n) return BH_ERR_INVALID_ARG;   // multiexp.rs:324-329 (assert)
+  if (opts && (opts->flags & BH_MSM_HOLD)) return BH_ERR_INVALID_ARG;
+  if (opts && opts->window_bits && (opts->window_bits < 2 || opts->window_bits > 24)) return BH_ERR_INVALID_ARG;
+  std::unique_ptr<bh_msm_many_job> mj(new bh_msm_many_job());
+  mj->ctx = ctx; mj->bases = bases; mj->skip = skip; mj->stride = stride; mj->n = n; mj->k = k; mj->fmt = fmt;
+  mj->dlen = density ? density_len : 0;
+  if (opts) mj->o = *opts;
+  const bool force = (mj->o.flags & BH_MSM_MANY_FORCE) != 0;
+  mj->o.flags &= ~BH_MSM_MANY_FORCE;
+  if (k == 0) { *out = mj.release(); return BH_OK; }
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  auto fail = [&](int rc) { many_job_free(mj.release()); return rc; };
+  if (on_host && n && n <= TINY_MSM_MAX) {
+    // a handful of terms: every vector is answered as the single call answers it (on the host, at issue time)
+    for (size_t v = 0; v < k; v++) {
+      bh_msm_job *j = nullptr;
+      const int rc = msm_common(ctx, bases, skip, (const char *)scalars + v * stride, true, n, fmt, density, true, mj->dlen,
+                                &mj->o, &j);
+      if (rc != BH_OK) {
+        unsigned char sink[192];
+        for (bh_msm_job *q : mj->singles) (void)bh_msm_wait(q, sink);
+        return fail(rc);
+      }
+      mj->singles.push_back(j);
+    }
+    *out = mj.release();
+    return BH_OK;
+  }
+  mj->sc_dev = scalars; mj->dn_dev = density;
+  if (on_host && n) {
+    // one upload each for the k vectors and the density map, on the context's stream: resident before any job reads them,
+    // and until the wait (the error path answers every vector from them again)
+    const size_t bytes = (k - 1) * stride + n * 32;
+    void *p = ctx->c.pool.acquire(bytes);
+    if (!p) return fail(BH_ERR_HIP);
+    mj->owned.push_back(p);
+    if (hipMemcpyAsync(p, scalars, bytes, hipMemcpyHostToDevice, ctx->c.stream) != hipSuccess) return fail(BH_ERR_HIP);
+    mj->sc_dev = p;
+    if (density) {
+      const size_t nw = (n + 63) / 64;
+      void *d = ctx->c.pool.acquire(nw * 8);
+      if (!d) return fail(BH_ERR_HIP);
+      mj->owned.push_back(d);
+      if (hipMemcpyAsync(d, density, nw * 8, hipMemcpyHostToDevice, ctx->c.stream) != hipSuccess) return fail(BH_ERR_HIP);
+      mj->dn_dev = (const u64 *)d;
+    }
+    if (hipStreamSynchronize(ctx->c.stream) != hipSuccess) return fail(BH_ERR_HIP);
+  }
+  bool use_many = k > 1 && n > 0;
+  if (use_many && !force) {
+    bool table;
+    {
+      std::lock_guard<std::mutex> g(ctx->c.job_mu);
+      table = bases->table != nullptr && (mj->o.window_bits == 0 || mj->o.window_bits == bases->tab.c);   // (msm_enqueue's use_table)
+    }
+    use_many = many_plan_wins(bases->group, n, k, table && !(mj->o.flags & BH_MSM_NO_TABLE));
+  }
+  int rc;
+  if (use_many) {
+    rc = msm_common(ctx, bases, skip, mj->sc_dev, false, n, fmt, mj->dn_dev, false, mj->dlen, &mj->o, &mj->many, 0, after_stream,
+                    (u32)std::min<size_t>(k, 0xffffffffu), stride);
+    // chosen by the rule, not forced: a plan the pipeline cannot index, or a workspace the pool cannot give, is no error of
+    // the caller's - the ordinary jobs serve the call (the failed job has released what it held)
+    if (rc != BH_OK && !force) rc = many_issue_singles(mj.get(), after_stream);
+  } else {
+    rc = many_issue_singles(mj.get(), after_stream);
+  }
+  if (rc != BH_OK) return fail(rc);
+  *out = mj.release();
+  return BH_OK;
+}
+int bh_msm_many_async_dev(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars_dev, size_t stride_bytes,
+                          size_t n_scalars, size_t k, int scalar_fmt, const uint64_t *density_words_dev, size_t density_len,
+                          const bh_msm_opts *opts, void *after_stream, bh_msm_many_job **job) {
+  return many_common(ctx, bases, skip, scalars_dev, false, stride_bytes, n_scalars, k, scalar_fmt, density_words_dev, density_len,
+                     opts, after_stream, job);
+}
+int bh_msm_many_async(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars_host, size_t stride_bytes,
+                      size_t n_scalars, size_t k, int scalar_fmt, const uint64_t *density_words, size_t density_len,
+                      const bh_msm_opts *opts, bh_msm_many_job **job) {
+  return many_common(ctx, bases, skip, scalars_host, true, stride_bytes, n_scalars, k, scalar_fmt, density_words, density_len, opts,
+                     nullptr, job);
+}
+int bh_msm_many_wait(bh_msm_many_job *job, void *out_affine_k, int32_t *rcs_k, float *stage_ms4, uint64_t *stats8) {
+  if (!job) return BH_ERR_INVALID_ARG;
+  std::unique_ptr<bh_msm_many_job, void (*)(bh_msm_many_job *)> mj(job, many_job_free);
+  const size_t rec = mj->bases ? (mj->bases->group == BH_G1 ? 96 : 192) : 0;
+  float ms[4] = {0, 0, 0, 0};
+  u64 st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int call_rc = BH_OK;
+  if (mj->k && (!out_affine_k || !rcs_k)) call_rc = BH_ERR_INVALID_ARG;   // (the jobs are still waited on and freed)
+  std::vector<unsigned char> scratch(mj->k * rec + 192);
+  unsigned char *out = call_rc == BH_OK && out_affine_k ? (unsigned char *)out_affine_k : scratch.data();
+  std::vector<int32_t> rcs(mj->k, BH_OK);
+  if (mj->many) {
+    bool fallback = false;
+    MsmJobImpl *impl = mj->many->impl;
+    int rc = msm_job_finish_many(*impl, out, mj->k, ms, st, &fallback);
+    msm_job_delete(impl);
+    delete mj->many;
+    mj->many = nullptr;
+    if (rc < 0) call_rc = rc;
+    else if (fallback) {
+      // a device flag was set: every vector by the single-vector path, over the inputs that are still resident
+      rc = many_issue_singles(mj.get(), nullptr);
+      if (rc != BH_OK) call_rc = rc;
+    }
+  }
+  for (size_t v = 0; v < mj->singles.size(); v++) {
+    float m1[4];
+    u64 s1[8];
+    const int rc = bh_msm_wait_stats(mj->singles[v], out + v * rec, m1, s1);
+    if (rc < 0) { call_rc = rc; continue; }
+    rcs[v] = rc;
+    if (rc != BH_OK) memset(out + v * rec, 0, rec);
+    for (int q = 0; q < 4; q++) ms[q] += m1[q];
+    for (int q = 0; q < 4; q++) st[q] += s1[q];
+    for (int q = 4; q < 8; q++) st[q] = s1[q];
+  }
+  mj->singles.clear();
+  if (call_rc == BH_OK && rcs_k) memcpy(rcs_k, rcs.data(), mj->k * sizeof(int32_t));
+  if (stage_ms4) memcpy(stage_ms4, ms, sizeof ms);
+  if (stats8) memcpy(stats8, st, sizeof st);
+  return call_rc;
+}
+int bh_msm_many_plan_info(size_t n, size_t k, int group, unsigned table_bits, unsigned num_cus, unsigned *out12) {
+  if (!out12 || (group != BH_G1 && group != BH_G2) || !k || k >= 65536 || n >= ((size_t)1 << 32)) return BH_ERR_INVALID_ARG;
+  if (table_bits && (table_bits < 2 || table_bits > 24)) return BH_ERR_INVALID_ARG;
+  const bool g2 = group == BH_G2;
+  WindowTable t = {table_bits, table_bits ? (256 + table_bits - 1) / table_bits : 0, n};
+  const MsmPlan p = make_many_plan(n, k, table_bits ? &t : nullptr, 0, 0, g2, num_cus ? (int)num_cus : 256);
+  if (!many_plan_valid(p, n)) return BH_ERR_INVALID_ARG;
+  const u64 W = (u64)p.windows_per_vector * k;
+  out12[0] = p.c; out12[1] = (unsigned)W; out12[2] = p.nb; out12[3] = p.chunk; out12[4] = p.chunks_per_window;
+  out12[5] = p.sort_passes; out12[6] = p.n; out12[7] = p.vectors; out12[8] = p.windows_per_vector; out12[9] = p.Wd;
+  const u64 bytes = job_result_bytes(p, g2 ? 384 : 192);   // what msm_enqueue copies to the job's pinned buffer
+  out12[10] = (unsigned)bytes; out12[11] = (unsigned)(bytes >> 32);
   return BH_OK;
 }
 // ---- scalars resident in HBM --------------------------------------------------------------------

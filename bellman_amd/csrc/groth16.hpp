@@ -641,6 +641,36 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *input_assign
                     const Fr *aux_assignment, size_t n_aux, const Fr &r, const Fr &s,
                     ProveTimings *timings = nullptr);
 
+// ---- k proofs of ONE circuit in one call (no reference twin: k calls of create_proof) ---------------------------------
+// Witness path only (the constraint matrices resident in `r1cs`), synchronous, one GPU.  Proof j is exactly what
+// prove_witness returns for witness j and (r, s) j.  The proofs of one circuit share their bases and density maps, so
+// the five long multiexps of each (l, a_aux, b_g1_aux, b_g2_aux, h) can be issued as five many-jobs per group of witnesses
+// (bh_msm_many_async_dev); the h blocks then run one after the other on one stream, the `inputs` multiexps and the
+// assembly stay per proof.  That GROUPED path bounds device memory by processing the witnesses in groups of g with
+// (g + 3) * m * 32 bytes <= the workspace budget (m = the domain size; g coefficient vectors plus the b and c vectors
+// and the FFT scratch the group's h blocks share), at least one witness per group - any k is accepted.
+// Measured, the grouped path beats the same proofs issued through prove_witness_async and kept in flight at two shapes
+// of eight (not the same ones in two runs) and loses on small circuits (profiles/prove_batch_bench.json), so BATCH_AUTO
+// never takes it: it runs the proofs by the single-proof path,
+// BATCH_IN_FLIGHT at a time, and waits for them in order.  BATCH_GROUPED forces the grouped path (tests, measurements).
+// A witness of the wrong shape throws std::invalid_argument before anything runs.
+struct WitnessView {
+  const Fr *inputs; size_t n_inputs;
+  const Fr *aux; size_t n_aux;
+};
+constexpr size_t BATCH_WORKSPACE_BYTES = size_t(1) << 30;   // the default workspace budget of the grouped path: 1 GiB
+constexpr size_t BATCH_IN_FLIGHT = 16;                       // proofs in flight at a time otherwise
+enum { BATCH_AUTO = 0, BATCH_GROUPED = 1 };
+// throws what the FIRST failing proof would throw (the subversion check and the order of reported errors per proof are
+// create_proof's); workspace_budget = 0: the default
+std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
+                                       const std::vector<std::pair<Fr, Fr>> &rs, ProveTimings *timings = nullptr,
+                                       size_t workspace_budget = 0, int mode = BATCH_AUTO);
+// the same with one return code per proof instead of an exception (BH_OK: proofs[j] is written); runtime failures throw
+void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
+                               const Fr *s, Proof *proofs, int *codes, ProveTimings *timings = nullptr,
+                               size_t workspace_budget = 0, int mode = BATCH_AUTO);
+
 // ---- one caller, proofs back to back ---------------------------------------------------------------------------
 // create_proof is synthesis on the host followed by the device part (prover.rs:182-215, then :217-360).  A single
 // caller that proves in a loop leaves the GPU idle during every synthesis and the host idle during every device part.

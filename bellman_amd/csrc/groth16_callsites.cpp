@@ -334,3 +334,11 @@ extern "C" int bh_test_groth16_prove_via_call_sites(bh_params *params, int mode,
   } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
   } catch (...) { return BH_ERR_HIP; }
 }
+
+// bh_groth16_prove_witness_batch through its GROUPED path (many-jobs over groups of witnesses; the product call never takes
+// it by itself), with a workspace budget of the caller's choice (0: the default): the group cut is reachable with small circuits
+extern "C" int bh_test_groth16_prove_witness_batch_budget(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                                          const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                                          void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4) {
+  return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, workspace_budget, groth16::BATCH_GROUPED);
+}

@@ -7,6 +7,8 @@
 #include <functional>
 #include <memory>
 #include <stdexcept>
+#include <vector>
+#include <string.h>
 
 #include "env_settings.hpp"
 #include "groth16.hpp"
@@ -77,6 +79,42 @@ inline int run_guarded(const std::function<groth16::Proof()> &f, void *proof_out
   } catch (const bellman::SynthesisError &e) { return e.code;
   } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
   } catch (...) { return BH_ERR_HIP; }
+}
+
+// bh_groth16_prove_witness_batch, and the test library's twin with a workspace budget of its own (0: the default)
+inline int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
+                                       size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
+                                       float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO) {
+  using namespace groth16;
+  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
+  if (k && (!r || !s || !proofs_out || !rcs || (n_inputs && !inputs) || (n_aux && !aux))) return BH_ERR_INVALID_ARG;
+  ProveTimings tm = {0, 0, 0, 0};
+  int rc = BH_OK;
+  try {
+    R1csView view(r1cs);
+    // caller records may be unaligned: copied then (the witnesses of a large circuit are tens of megabytes each - an
+    // aligned caller's arrays are read in place)
+    std::vector<Fr> in, ax, rr(k), ss(k);
+    const Fr *in_p = (const Fr *)inputs, *ax_p = (const Fr *)aux;
+    if ((uintptr_t)inputs % alignof(Fr) && k * n_inputs) { in.resize(k * n_inputs); memcpy(in.data(), inputs, k * n_inputs * 32); in_p = in.data(); }
+    if ((uintptr_t)aux % alignof(Fr) && k * n_aux) { ax.resize(k * n_aux); memcpy(ax.data(), aux, k * n_aux * 32); ax_p = ax.data(); }
+    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
+    std::vector<WitnessView> ws(k);
+    for (size_t j = 0; j < k; j++) ws[j] = WitnessView{in_p + j * n_inputs, n_inputs, ax_p + j * n_aux, n_aux};
+    std::vector<Proof> proofs(k);
+    std::vector<int> codes(k, BH_OK);
+    prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
+    for (size_t j = 0; j < k; j++) {
+      char *out = (char *)proofs_out + j * 384;
+      rcs[j] = codes[j];
+      if (codes[j] == BH_OK) { memcpy(out, &proofs[j].a, 96); memcpy(out + 96, &proofs[j].b, 192); memcpy(out + 288, &proofs[j].c, 96); }
+      else memset(out, 0, 384);
+    }
+  } catch (const bellman::SynthesisError &e) { rc = e.code;
+  } catch (const std::invalid_argument &) { rc = BH_ERR_INVALID_ARG;
+  } catch (...) { rc = BH_ERR_HIP; }
+  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  return rc;
 }
 
 struct bh_proof_job {

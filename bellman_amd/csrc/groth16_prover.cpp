@@ -3,6 +3,7 @@
 // Reference map in groth16.hpp.
 #include <string.h>
 
+#include <array>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -543,6 +544,221 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *inputs, size
   src.n_cons = r1cs.num_constraints;
   src.r1cs = &r1cs;
   return prove_core(src, params, r, s, tm);
+}
+
+// ---- k proofs of one circuit in one call ------------------------------------------------------------
+// Across the proofs of one circuit the bases and the density maps are the same; only the scalar vectors differ.  So the
+// five long multiexps of every proof (l, a_aux, b_g1_aux, b_g2_aux, h) are issued as five many-jobs over all the witnesses
+// of a group (bh_msm_many_async_dev: one launch chain for the group where the library's size rule takes the many-plan, k
+// ordinary jobs otherwise), the h blocks run one after the other on one stream into strided coefficient vectors, and the
+// `inputs` multiexps and finish_proof stay per witness.  Error order per proof: prove_core's.
+namespace {
+struct ManyJobSet {   // as JobSet: every issued many-job is waited on even when something throws in between
+  std::vector<bh_msm_many_job **> slots;
+  void track(bh_msm_many_job **j) { slots.push_back(j); }
+  ~ManyJobSet() {
+    for (bh_msm_many_job **s : slots)
+      if (*s) { (void)bh_msm_many_wait(*s, nullptr, nullptr, nullptr, nullptr); *s = nullptr; }
+  }
+};
+}  // namespace
+
+// Where the grouped path (many-jobs over a group of witnesses) replaces k proofs in flight without being asked to.
+// Measured (tools/bench_prove_batch.py, profiles/prove_batch_bench.json: MiMC-322 and the chain circuit at 2^14 / 2^16 / 2^18
+// constraints, k = 4 and 16): against k prove_witness_async calls in flight it is 0.51 - 0.66 x on MiMC-322 and 0.97 - 1.29 x
+// on the chain circuit, beyond the baseline's own spread at two shapes of eight (k = 16 at 2^16 and 2^18) - and at another
+// one (2^16, k = 4) in the run before.  No basis for a rule yet: it is "never", and the call runs the proofs in flight,
+// BATCH_IN_FLIGHT at a time.
+static bool grouped_batch_wins(size_t n_constraints, size_t k) {
+  (void)n_constraints; (void)k;
+  return false;
+}
+
+void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r, const Fr *s,
+                               Proof *proofs, int *codes, ProveTimings *tm, size_t workspace_budget, int mode) {
+  for (size_t j = 0; j < k; j++)
+    if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
+      throw std::invalid_argument("witness does not have the shape of the captured circuit");
+  if (tm) *tm = ProveTimings{0, 0, 0, 0};
+  if (!k) return;
+  const double t0 = now_ms();
+  if (mode != BATCH_GROUPED && !grouped_batch_wins(r1cs.num_constraints, k)) {
+    // k proofs by the single-proof path, BATCH_IN_FLIGHT of them in flight (device memory stays bounded), waited in order
+    std::vector<std::unique_ptr<AsyncProof>> jobs(k);
+    auto finish = [&](size_t j) {
+      ProveTimings one = {0, 0, 0, 0};
+      try {
+        proofs[j] = jobs[j]->wait(&one);
+        codes[j] = BH_OK;
+      } catch (const SynthesisError &e) {
+        if (e.code < 0) { jobs.clear(); throw; }   // (the remaining jobs join in their destructors)
+        codes[j] = e.code;
+      }
+      jobs[j].reset();
+      if (tm) { tm->h_poly_ms += one.h_poly_ms; tm->msm_ms += one.msm_ms; }
+    };
+    for (size_t j = 0; j < k; j++) {
+      if (j >= BATCH_IN_FLIGHT) finish(j - BATCH_IN_FLIGHT);
+      jobs[j] = prove_witness_async(r1cs, params, witnesses[j].inputs, witnesses[j].n_inputs, witnesses[j].aux, witnesses[j].n_aux,
+                                    r[j], s[j]);
+    }
+    for (size_t j = k > BATCH_IN_FLIGHT ? k - BATCH_IN_FLIGHT : 0; j < k; j++) finish(j);
+    if (tm) tm->total_ms = (float)(now_ms() - t0);
+    return;
+  }
+  bh_ctx *ctx = params.ctx;
+  const size_t n_in = r1cs.num_inputs, n_aux = r1cs.num_aux, n_cons = r1cs.num_constraints;
+  uint32_t log_m = 0;
+  size_t m = 1;
+  while (m < n_cons) {
+    m *= 2;
+    log_m++;
+    if (log_m >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
+  }
+  // group size: g coefficient vectors (the a vector of each h block, which becomes its quotient) plus the b and c vectors
+  // and the FFT scratch, which the h blocks of a group share (they run one after the other on one stream)
+  const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
+  const size_t vec = m * 32;
+  size_t group = budget / vec > 3 ? budget / vec - 3 : 1;
+  if (group > k) group = k;
+  if (group > 4096) group = 4096;
+  // the blinding terms (five host scalar multiplications per proof) on helper threads, beside the GPU work
+  std::vector<ProofBlinding> blind(k);
+  std::exception_ptr blind_err;
+  std::mutex blind_mu;
+  const size_t n_threads = std::min<size_t>(k, 8);
+  std::vector<std::thread> blind_threads;
+  for (size_t t = 0; t < n_threads; t++)
+    blind_threads.emplace_back([&, t] {
+      try {
+        for (size_t j = t; j < k; j += n_threads) blind[j] = blind_terms(params, r[j], s[j]);
+      } catch (...) {
+        std::lock_guard<std::mutex> g(blind_mu);
+        if (!blind_err) blind_err = std::current_exception();
+      }
+    });
+  struct Joiner {
+    std::vector<std::thread> &ts;
+    ~Joiner() { for (std::thread &t : ts) if (t.joinable()) t.join(); }
+  } joiner{blind_threads};
+
+  const uint64_t *dens_a_aux = nullptr, *dens_b_in = nullptr, *dens_b_aux = nullptr;
+  const uint64_t *hw_a_aux = nullptr, *hw_b_in = nullptr, *hw_b_aux = nullptr;
+  size_t b_in_total = 0;
+  check(bh_r1cs_density(r1cs.handle, 0, &dens_a_aux, &hw_a_aux, nullptr));
+  check(bh_r1cs_density(r1cs.handle, 1, &dens_b_in, &hw_b_in, &b_in_total));
+  check(bh_r1cs_density(r1cs.handle, 2, &dens_b_aux, &hw_b_aux, nullptr));
+  std::vector<MsmSums> sums(k);
+  std::vector<std::array<int, 8>> rcs(k);
+  double h_ms = 0, msm_ms = 0;
+  for (size_t first = 0; first < k; first += group) {
+    const size_t g = std::min(group, k - first);
+    const double t1 = now_ms();
+    const size_t in_stride = n_in * 32, aux_stride = n_aux * 32;
+    DevBuf d_in(ctx, g * in_stride + 32), d_aux(ctx, g * aux_stride + 32);
+    DevBuf da(ctx, g * vec), db(ctx, vec), dc(ctx, vec), dscratch(ctx, log_m > 11 ? vec : 32);
+    ProofStream ps(ctx);
+    StreamDrain drain{ps};
+    std::vector<bh_msm_job *> in_jobs(3 * g, nullptr);
+    bh_msm_many_job *l_job = nullptr, *a_job = nullptr, *b1_job = nullptr, *b2_job = nullptr, *h_job = nullptr;
+    JobSet jobs;
+    for (bh_msm_job *&j : in_jobs) jobs.track(&j);
+    ManyJobSet many_jobs;
+    for (bh_msm_many_job **j : {&l_job, &a_job, &b1_job, &b2_job, &h_job}) many_jobs.track(j);
+    // 1. the witnesses, one strided buffer each
+    for (size_t j = 0; j < g; j++) {
+      const WitnessView &w = witnesses[first + j];
+      if (n_in) check(bh_dev_upload_on(ctx, (char *)d_in.p + j * in_stride, w.inputs, in_stride, ps.st));
+      if (n_aux) check(bh_dev_upload_on(ctx, (char *)d_aux.p + j * aux_stride, w.aux, aux_stride, ps.st));
+    }
+    // 2. four many-jobs over the aux vectors and the shared bases and densities, ordered after the uploads
+    // G2 first: the longest job
+    check(bh_msm_many_async_dev(ctx, params.b_g2, b_in_total, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_b_aux,
+                                dens_b_aux ? n_aux : 0, nullptr, ps.st, &b2_job));
+    check(bh_msm_many_async_dev(ctx, params.l, 0, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &l_job));
+    check(bh_msm_many_async_dev(ctx, params.a, n_in, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_a_aux,
+                                dens_a_aux ? n_aux : 0, nullptr, ps.st, &a_job));
+    check(bh_msm_many_async_dev(ctx, params.b_g1, b_in_total, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_b_aux,
+                                dens_b_aux ? n_aux : 0, nullptr, ps.st, &b1_job));
+    // 3. the h block per witness, on one stream, into the group's strided coefficient vectors; then the H many-job,
+    // ordered after them
+    for (size_t j = 0; j < g; j++) {
+      void *a_j = (char *)da.p + j * vec;
+      check(bh_r1cs_eval_dev(ctx, r1cs.handle, (char *)d_in.p + j * in_stride, (char *)d_aux.p + j * aux_stride, a_j, db.p, dc.p,
+                             log_m, ps.st));
+      check(bh_h_poly_fr_dev_on(ctx, a_j, db.p, dc.p, dscratch.p, log_m, ps.st));
+    }
+    check(bh_msm_many_async_dev(ctx, params.h, 0, da.p, vec, m - 1, g, BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &h_job));   // a.len() - 1
+    // 4. the `inputs` multiexps as the single call issues them (a handful of terms: answered on the host, at issue time -
+    // so they come last, while the GPU works)
+    for (size_t j = 0; j < g; j++) {
+      const WitnessView &w = witnesses[first + j];
+      struct In { bh_bases *bases; const uint64_t *dens_dev, *dens_host; } q[3] = {
+          {params.a, nullptr, nullptr}, {params.b_g1, dens_b_in, hw_b_in}, {params.b_g2, dens_b_in, hw_b_in}};
+      for (int t = 0; t < 3; t++) {
+        if (n_in <= 8)
+          check(bh_msm_async(ctx, q[t].bases, 0, w.inputs, n_in, BH_SCALARS_MONT, q[t].dens_host, q[t].dens_host ? n_in : 0,
+                             &in_jobs[3 * j + t]));
+        else
+          check(bh_msm_async_dev_after(ctx, q[t].bases, 0, (char *)d_in.p + j * in_stride, n_in, BH_SCALARS_MONT, q[t].dens_dev,
+                                       q[t].dens_dev ? n_in : 0, nullptr, ps.st, &in_jobs[3 * j + t]));
+      }
+    }
+    const double t2 = now_ms();
+    // waits, every job even when an earlier one fails; codes per proof in the reference's wait order (prover.rs:339-354)
+    std::vector<G1Affine> g1(g);
+    std::vector<G2Affine> g2(g);
+    std::vector<int32_t> codes_v(g);
+    auto wait_many = [&](bh_msm_many_job *&job, int slot, auto &recs, auto member) {
+      bh_msm_many_job *jb = job;
+      job = nullptr;
+      check(bh_msm_many_wait(jb, recs.data(), codes_v.data(), nullptr, nullptr));
+      for (size_t j = 0; j < g; j++) { sums[first + j].*member = recs[j]; rcs[first + j][slot] = codes_v[j]; }
+    };
+    for (size_t j = 0; j < g; j++) {
+      MsmSums &o = sums[first + j];
+      rcs[first + j][0] = jobs.wait(in_jobs[3 * j + 0], &o.a_in);
+      rcs[first + j][2] = jobs.wait(in_jobs[3 * j + 1], &o.b1_in);
+      rcs[first + j][4] = jobs.wait(in_jobs[3 * j + 2], &o.b2_in);
+    }
+    wait_many(a_job, 1, g1, &MsmSums::a_aux);
+    wait_many(b1_job, 3, g1, &MsmSums::b1_aux);
+    wait_many(b2_job, 5, g2, &MsmSums::b2_aux);
+    wait_many(h_job, 6, g1, &MsmSums::h);
+    wait_many(l_job, 7, g1, &MsmSums::l);
+    h_ms += t2 - t1;
+    msm_ms += now_ms() - t2;
+  }
+  for (std::thread &t : blind_threads) t.join();
+  const bool subverted = params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity();   // prover.rs:320-324
+  if (blind_err && !subverted) std::rethrow_exception(blind_err);
+  for (size_t j = 0; j < k; j++) {
+    int code = subverted ? BH_ERR_UNEXPECTED_IDENTITY : BH_OK;
+    for (int i = 0; i < 8 && code == BH_OK; i++) {
+      if (rcs[j][i] < 0) check(rcs[j][i]);   // a runtime failure is the call's
+      code = rcs[j][i];                       // first failing `?` in wait order
+    }
+    codes[j] = code;
+    if (code == BH_OK) proofs[j] = finish_proof(blind[j], sums[j], r[j], s[j]);
+  }
+  if (tm) {
+    tm->h_poly_ms = (float)h_ms;
+    tm->msm_ms = (float)msm_ms;
+    tm->total_ms = (float)(now_ms() - t0);
+  }
+}
+
+std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
+                                       const std::vector<std::pair<Fr, Fr>> &rs, ProveTimings *tm, size_t workspace_budget, int mode) {
+  if (witnesses.size() != rs.size()) throw std::invalid_argument("one (r, s) per witness");
+  const size_t k = witnesses.size();
+  std::vector<Fr> r(k), s(k);
+  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
+  std::vector<Proof> proofs(k);
+  std::vector<int> codes(k, BH_OK);
+  prove_witness_batch_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(), tm, workspace_budget, mode);
+  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
+  return proofs;
 }
 
 // ---- structure capture (generator.rs:43-131 KeypairAssembly, plus the input rows of prover.rs:208-215)

@@ -175,6 +175,26 @@ int msm_job_finish(MsmJobImpl &job, void *out_affine, float *ms, u64 *stats8) {
   if (stats8) memcpy(stats8, job.done_stats, sizeof job.done_stats);
   return job.done_rc;
 }
+// a many-job: `k` affine records; *fallback = a device flag (EOF, identity) was set and no record was produced
+int msm_job_finish_many(MsmJobImpl &job, void *out_affine_k, size_t k, float *ms, u64 *stats8, bool *fallback) {
+  const size_t rec = job.group == BH_G1 ? 96 : 192;
+  *fallback = false;
+  if (job.trivial) {
+    memset(out_affine_k, 0, k * rec);
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
+    if (stats8) memset(stats8, 0, 8 * sizeof(u64));
+    return job.early_rc;
+  }
+  msm_job_untrack(job);
+  std::lock_guard<std::mutex> g(job.mu);
+  msm_job_complete_locked(job);
+  if (job.done_rc == BH_OK && job.many_out.size() == k * rec) memcpy(out_affine_k, job.many_out.data(), k * rec);
+  else memset(out_affine_k, 0, k * rec);
+  *fallback = job.many_fallback;
+  if (ms) memcpy(ms, job.done_ms, sizeof job.done_ms);
+  if (stats8) memcpy(stats8, job.done_stats, sizeof job.done_stats);
+  return job.done_rc;
+}
 // bring-up / verification aid (bh_msm_debug_stages): stages 1-3 only - signed digits, radix sort, zero-digit count -
 // with the sorted (digit, base) pairs and the per-window zero counts copied to the host
 int msm_debug_stages(Context &c, const void *scalars_host, u64 n, int fmt, unsigned cbits, u64 *pairs_out, u32 *zstart_out) {

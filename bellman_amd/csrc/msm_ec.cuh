@@ -1427,16 +1427,21 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const bool use_table = table && !(opts.flags & BH_MSM_NO_TABLE) && (opts.c == 0 || opts.c == table->c) &&
                          (u64)table->W * table->stride < ((u64)1 << 31) && (u64)table->W * n < ((u64)1 << 32);
   if (opts.padded_table && G2) return BH_ERR_INVALID_ARG;   // only G1 tables are laid out at a 128-byte stride
-  const MsmPlan p = use_table ? make_table_plan(n, *table, opts.chunk, G2, c.num_cus)
-                              : make_plan(n, opts.c, opts.chunk, G2);
+  // a many-job: opts.vectors scalar vectors of n scalars, vector v at scalars_dev + v * opts.scalar_stride
+  const bool many = opts.vectors > 1;
+  if (many && (opts.flags & BH_MSM_HOLD)) return BH_ERR_INVALID_ARG;
+  const MsmPlan p = many        ? make_many_plan(n, opts.vectors, use_table ? table : nullptr, opts.c, opts.chunk, G2, c.num_cus)
+                    : use_table ? make_table_plan(n, *table, opts.chunk, G2, c.num_cus)
+                                : make_plan(n, opts.c, opts.chunk, G2);
   // running bucket sum in LDS: only meaningful for the single-lane G2 kernel (its default), or when forced
   const bool lds_acc = F::LANES == 1 && ((opts.flags & BH_MSM_ACC_LDS) ? true : (opts.flags & BH_MSM_ACC_REGISTERS) ? false : G2);
   job.plan = p;
   if ((u64)p.Wd * n >= ((u64)1 << 32)) return BH_ERR_INVALID_ARG;  // pair positions are 32-bit
   if (n_bases >= ((u64)1 << 31)) return BH_ERR_INVALID_ARG;        // base index shares its word with the sign bit
+  if (many && !many_plan_valid(p, n_bases)) return BH_ERR_INVALID_ARG;
 
   // ---- one workspace block per job, carved into its buffers (one pool round trip, one memset) ----------
-  const u64 npairs = (u64)p.Wd * n;
+  const u64 npairs = many ? (u64)p.W * p.n : (u64)p.Wd * n;
   const u64 ncounts = sort_counts_elems(p);
   const u64 nslots = (u64)p.W * p.chunks_per_window;
   const MergePlan mp = merge_plan<FR>(p, c.num_cus);
@@ -1497,7 +1502,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // 0.7 through the sort: profiles/r6_call54_tiny_g2_bits.txt); the default 13-bit tables have t = 8
   const u32 top_bits = 255u - (p.Wd - 1) * p.c;
   const u64 sliver_load = top_bits >= 31 ? 0 : ((u64)p.nd >> top_bits);
-  const bool small_fused = use_table && !opts.padded_table && p.W == 1 && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
+  const bool small_fused = use_table && !opts.padded_table && plan_fused_sort(p) && !many && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
                            (u64)p.n <= (u64)SMALL_MAX_PER_BUCKET * p.nb && p.c <= 15 && small_fill_lds_bytes(p.nd, p.n) <= 64 * 1024 &&
                            sliver_load + (u64)p.n / p.nb <= SMALL_LIST_CAP / 2 && !(opts.flags & BH_MSM_NO_SMALL_PATH);
   if (small_fused) {
@@ -1508,10 +1513,22 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
                        (const Affine<M> *)bases_dev, pts, err);
     BH_HIP_CHECK(hipGetLastError());
   } else {
-    int rc = msm_run_stages(p, b, scalars_dev, fmt, density_dev, skip, n_bases, st, &sorted);
+    int rc = msm_run_stages(p, b, scalars_dev, fmt, density_dev, skip, n_bases, st, &sorted, opts.scalar_stride);
     if (rc) return rc;
   }
   if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_sorted, st));
+  // the pinned result buffer of a job's resources holds every single-vector plan; a many-job's W * c bit sums may not
+  // fit: the job's resources grow to what its plan needs (and keep it when they are recycled)
+  if (job_result_bytes(p, sizeof(Pt)) != (o_bits - o_err) + bits_bytes) return BH_ERR_INVALID_ARG;   // (bh_msm_many_plan_info reports it)
+  if (many && job_result_bytes(p, sizeof(Pt)) > job.res.pinned_bytes) {
+    const size_t want = (job_result_bytes(p, sizeof(Pt)) + 65535) & ~size_t(65535);
+    void *bigger = nullptr;
+    BH_HIP_CHECK(hipHostMalloc(&bigger, want, hipHostMallocDefault));
+    (void)hipHostFree(job.res.pinned);
+    job.res.pinned = bigger;
+    job.res.pinned_bytes = want;
+    job.host_result = bigger;
+  }
   const bool hold = (opts.flags & BH_MSM_HOLD) != 0;
   if (hold) {
     // the digit / sort stage of a held job joins the barrier set of the accumulation chain: whichever accumulation is
@@ -1616,6 +1633,25 @@ static void msm_host_tail(const MsmPlan &p, const XYZZ<F> *bits_dev_layout, void
   memcpy(out_dev_layout, &res, sizeof res);
 }
 
+// many-plan: the tail over vector v's windows only.  launch_reduce lays the bit sums out window-major over ALL W sets
+// ([W][lo_bits], [W][hi_bits], [W]); the vector's slice of each part, put side by side, is exactly what the tail above
+// reads for a plan of windows_per_vector sets (table flavour: one set, c doublings).
+template <class F>
+static void msm_host_tail_vector(const MsmPlan &p, u32 v, const XYZZ<F> *bits_dev_layout, void *out_dev_layout) {
+  MsmPlan pv = p;
+  pv.vectors = 1;
+  pv.W = p.windows_per_vector;
+  pv.NB = pv.W * p.nb;
+  const u32 cb = p.c - 1;
+  const size_t w0 = (size_t)v * pv.W;
+  std::vector<XYZZ<F>> slice((size_t)pv.W * p.c);
+  const XYZZ<F> *lo = bits_dev_layout, *hi = bits_dev_layout + (size_t)p.W * p.lo_bits, *tot = bits_dev_layout + (size_t)p.W * cb;
+  std::copy(lo + w0 * p.lo_bits, lo + (w0 + pv.W) * p.lo_bits, slice.begin());
+  std::copy(hi + w0 * p.hi_bits, hi + (w0 + pv.W) * p.hi_bits, slice.begin() + (size_t)pv.W * p.lo_bits);
+  std::copy(tot + w0, tot + w0 + pv.W, slice.begin() + (size_t)pv.W * cb);
+  msm_host_tail<F>(pv, slice.data(), out_dev_layout);
+}
+
 template <class F>
 static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
   Context &c = *job.ctx;
@@ -1651,7 +1687,17 @@ static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
     job.done_stats[0] = (u64)p.W * p.n; job.done_stats[1] = ef.zeros; job.done_stats[2] = ef.madds;
     job.done_stats[3] = (u64)p.W * p.chunks_per_window; job.done_stats[4] = p.c; job.done_stats[5] = p.chunk;
     job.done_stats[6] = p.W; job.done_stats[7] = p.Wd;
-    if (ef.ident && (ef.eof || job.always_resolve_ident)) {
+    if (p.vectors > 1) {
+      // many-job: the flags are per job - with either set every vector is answered by the single-vector path
+      // (bh_msm_many_wait), which gives each its own code with the reference's precedence
+      job.many_out.assign((size_t)p.vectors * sizeof(Affine<F>), 0);
+      job.many_fallback = ef.eof || ef.ident;
+      if (!job.many_fallback)
+        for (u32 v = 0; v < p.vectors; v++)
+          msm_host_tail_vector<F>(p, v, (const XYZZ<F> *)((const char *)job.host_result + ERR_SLOT),
+                                  job.many_out.data() + (size_t)v * sizeof(Affine<F>));
+      memset(out_affine, 0, sizeof(Affine<F>));
+    } else if (ef.ident && (ef.eof || job.always_resolve_ident)) {
       // both kinds of failure exist (or the caller folds shards): the reference reports the top window's first failure
       const u64 nref = job.ref_n ? job.ref_n : p.nd;
       const double c_ln = (nref < 32) ? 3.0 : std::ceil(std::log((double)nref));   // multiexp.rs:318-322

@@ -19,7 +19,7 @@ int msm_enqueue_g2(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip
   const int acc = f_pairs ? 1 : f_single ? 2 : f_triples ? 0 : (n >= ((u64)1 << 15) ? 1 : 0);
   // [r6] ... but a big TABLE set (the 2^19 buckets of 20-bit rows) stays on lane triples: with the two-stage sums of msm_ec.cuh
   // its reduction is ~1.5 ms there, 2.8 with one lane per point (profiles/r6_call38_*, r6_call39_*)
-  const bool red_single = f_single ? true : f_triples ? false : ((u64)pl.NB > ((u64)1 << 17) && !with_table);
+  const bool red_single = f_single ? true : f_triples ? false : ((u64)pl.NB * (opts.vectors > 1 ? opts.vectors : 1) > ((u64)1 << 17) && !with_table);   // (a many-job: the buckets of all its vectors)
 #define BH_G2_CASE(F, FR) return msm_enqueue<F, FR>(job, bases_dev, n_bases, skip, scalars_dev, n, fmt, density_dev, opts, table)
   if (red_single) {
     if (acc == 0) BH_G2_CASE(Fp2K3Ops, Fp2Ops);

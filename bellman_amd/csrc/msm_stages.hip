@@ -144,6 +144,49 @@ __global__ void msm_digits_kernel(const void *scalars, int fmt, u32 n, const u64
   }
 }
 
+// 1b. digits of a many-plan: k scalar vectors over ONE base vector and density map (make_many_plan).  One thread per
+// scalar INDEX i and vector slice: the density rank and the EOF test are computed once, then for each of the slice's
+// vectors v the 32-byte scalar is loaded (lane-contiguous across i) and recoded low to high with carry exactly as above.
+// Digit j of vector v goes to pairs[(v * Wd + j) * nd + i]: bucket set v * Wd + j, position i (classic flavour,
+// base_stride == 0), which is also position j * nd + i of set v (table flavour: the set spans Wd * nd pairs and the base
+// field addresses table row j) - either way every bucket set is a contiguous region of p.n pairs, and the stores of a
+// wavefront for fixed (v, j) are 64 consecutive pairs.  blockIdx.y strides over the vectors so that a job of a few
+// thousand scalars still fills the chip.  Live state per thread: one scalar (8 words, shifted down a digit at a time),
+// its carry, the base index.
+__device__ __forceinline__ u64 wide_next_digit(fr_t &s, u32 &carry, u32 c);
+__global__ __launch_bounds__(256) void msm_many_digits_kernel(const void *scalars, u64 scalar_stride, int fmt, u32 nd, u32 vectors,
+                                                              const u64 *density, const u32 *word_prefix, u64 skip,
+                                                              u64 n_bases, u32 c, u32 Wd, u64 base_stride, u64 *pairs,
+                                                              ErrFlags *err) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nd) return;
+  bool dense = true;
+  u64 k = skip + i;
+  if (density) {
+    const u64 word = density[i >> 6];
+    dense = (word >> (i & 63)) & 1;
+    k = skip + word_prefix[i >> 6] + __popcll(word & (((u64)1 << (i & 63)) - 1));
+  }
+  bool live = dense;
+  if (dense && k >= n_bases) {   // every dense entry checks EOF first, whatever its scalars
+    if (blockIdx.y == 0) atomicOr(&err->eof, 1u);
+    live = false;
+  }
+  for (u32 v = blockIdx.y; v < vectors; v += gridDim.y) {
+    fr_t s;
+    if (live) load_scalar((const char *)scalars + (u64)v * scalar_stride, i, fmt, s);
+    else fe_zero(s);
+    u32 carry = 0;
+    u64 *dst = pairs + (u64)v * Wd * nd + i;
+    u32 base = (u32)k;
+    for (u32 j = 0; j < Wd; j++) {
+      const u64 e = wide_next_digit(s, carry, c);
+      dst[(u64)j * nd] = e | (base & 0x7fffffffu);
+      base += (u32)base_stride;
+    }
+  }
+}
+
 // ============================================================================================
 // 2. radix sort (per window region of n pairs, keyed on 8 bits of the digit per pass)
 // ============================================================================================
@@ -299,7 +342,7 @@ static u32 wide_scalars_per_tile(u32 Wd) { return std::max(1u, std::min<u32>(WID
 static u32 wide_first_tiles(const MsmPlan &p) { const u32 spt = wide_scalars_per_tile(p.Wd); return (p.nd + spt - 1) / spt; }
 
 size_t sort_counts_elems(const MsmPlan &p) {
-  if (p.W != 1) return (size_t)p.W * 256 * p.num_tiles;
+  if (!plan_fused_sort(p)) return (size_t)p.W * 256 * p.num_tiles;
   size_t m = ((size_t)1 << wide_pass_bits(p.c, 0)) * wide_first_tiles(p);
   for (u32 pass = 1; pass < p.sort_passes; pass++) m = std::max(m, ((size_t)1 << wide_pass_bits(p.c, pass)) * p.num_tiles);
   return m;
@@ -699,10 +742,51 @@ MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool
   p.sort_passes = wide_passes(p.c);
   return p;
 }
-
+// k scalar vectors in one job.  The stages after the digits process p.W bucket sets of p.n sorted entries each whatever
+// the sets mean, so vector v takes the place of a window: the single-vector plan for n scalars gives c, the buckets per set
+// and the per-set entry count; W is multiplied by k.  The sets are sorted by the 8-bit passes of the classic plan (the fused
+// first pass of a table plan handles one set).  Chunk length: the single plan's - its rules key on the entries and buckets
+// of ONE set, which are unchanged - except that the table rule's "never so long that the chip runs out of lanes" counts
+// the lanes of all k sets.
+MsmPlan make_many_plan(u64 n, u64 k, const WindowTable *table, unsigned forced_c, unsigned forced_chunk, bool g2, int num_cus) {
+  MsmPlan p;
+  if (table) {
+    p = make_table_plan(n, *table, forced_chunk, g2, num_cus);
+    if (!forced_chunk && k > 1 && !(g2 && p.c >= 18)) {
+      const u32 lg = ilog2(p.n ? p.n : 1);
+      const u64 base_k = lg <= 20 ? 8 : lg <= 22 ? 16 : g2 ? 64 : 32;
+      const u64 lanes_min = (u64)num_cus * 4 * 64 * (g2 ? 1 : 2);
+      const u64 avg = (u64)p.n >> (p.c - 1);
+      const u64 kk = std::min<u64>(std::max<u64>(base_k, avg), std::max<u64>(base_k, (u64)p.n * k / lanes_min));
+      p.chunk = (u32)std::max<u64>(p.chunk, kk);
+      p.chunks_per_window = (p.n + p.chunk - 1) / p.chunk;
+    }
+    p.windows_per_vector = 1;
+    if (k > 1) {   // (k == 1 is the table plan itself, fused first pass included)
+      p.num_tiles = (p.n + SORT_TILE - 1) / SORT_TILE;
+      p.sort_passes = (p.c + 7) / 8;
+    }
+  } else {
+    p = make_plan(n, forced_c, forced_chunk, g2);
+    p.windows_per_vector = p.W;
+  }
+  p.vectors = (u32)k;
+  p.W = (u32)(p.windows_per_vector * k);
+  p.NB = p.W * p.nb;
+  return p;
+}
+bool many_plan_valid(const MsmPlan &p, u64 n_bases) {
+  const u64 k = p.vectors, W = (u64)p.windows_per_vector * k;
+  if (!k || k >= ((u64)1 << 16) || W > 65535) return false;                   // a bucket set per blockIdx.y
+  if (W * p.n >= ((u64)1 << 32) || W * p.nb >= ((u64)1 << 32)) return false;   // pair and bucket positions are 32-bit
+  if (W * p.chunks_per_window >= ((u64)1 << 32)) return false;
+  if (n_bases >= ((u64)1 << 31)) return false;                                // base index shares its word with the sign bit
+  if (p.base_stride && (u64)p.Wd * p.base_stride >= ((u64)1 << 31)) return false;
+  return true;
+}
 
 int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_dev, int fmt, const u64 *density_dev,
-                   u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out) {
+                   u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out, u64 scalar_stride) {
   const u64 n = p.nd;   // scalars (the density bitmap is indexed by scalar)
   const u64 nwords = (n + 63) / 64;
   if (density_dev) {
@@ -712,7 +796,7 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
     int rc = exclusive_scan_u32(b.word_prefix, nwords, b.scan_tmp, st);
     if (rc) return rc;
   }
-  if (p.W == 1) {
+  if (plan_fused_sort(p)) {
     // one bucket set: digits and sort in one stage (2b above) - the first pass recodes the scalars and keeps the non-zero
     // digits (*zstart = how many it dropped), the last pass writes them to the END of the array, so that what follows
     // sees *zstart entries to skip and then the sorted stream
@@ -753,8 +837,16 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
     return BH_OK;
   }
   // 1. digits
-  hipLaunchKernelGGL(msm_digits_kernel, dim3((p.nd + 255) / 256), dim3(256), 0, st, scalars_dev, fmt, p.nd,
-                     density_dev, b.word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, b.pairs_a, b.err);
+  if (p.vectors > 1) {
+    // enough workgroups for two wavefronts per SIMD where the job has them: the vectors are strided over blockIdx.y
+    const u32 bx = (p.nd + 255) / 256;
+    const u32 by = std::max(1u, std::min<u32>(p.vectors, (2048u + bx - 1) / bx));
+    hipLaunchKernelGGL(msm_many_digits_kernel, dim3(bx, by), dim3(256), 0, st, scalars_dev, scalar_stride, fmt, p.nd, p.vectors,
+                       density_dev, b.word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, b.pairs_a, b.err);
+  } else {
+    hipLaunchKernelGGL(msm_digits_kernel, dim3((p.nd + 255) / 256), dim3(256), 0, st, scalars_dev, fmt, p.nd,
+                       density_dev, b.word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, b.pairs_a, b.err);
+  }
   BH_HIP_CHECK(hipGetLastError());
   // 2. sort every window by digit, 8 bits per pass; the zero digits sort to the front
   const u64 ncounts = (u64)p.W * 256 * p.num_tiles;

@@ -56,6 +56,10 @@ struct MsmOpts {
   // a G1 window table whose records sit at a 128-byte stride (api.hip bh_bases::table_padded): only the bucket
   // accumulation of the table plan reads it; `bases_dev` of such a job is the dense base vector itself
   const void *padded_table = nullptr;
+  // a many-job (bh_msm_many_*): `vectors` scalar vectors of the job's n scalars each over ONE base vector and density
+  // map, vector v at scalars + v * scalar_stride bytes; 0 = an ordinary job
+  u32 vectors = 0;
+  u64 scalar_stride = 0;
 };
 
 struct MsmPlan {
@@ -68,7 +72,16 @@ struct MsmPlan {
   // and a pair's base field addresses table row j: j*base_stride + base index.
   u32 nd, Wd;
   u64 base_stride;
+  // Many-plan (make_many_plan): `vectors` scalar vectors share the job; vector v owns the windows_per_vector bucket sets
+  // [v * windows_per_vector, (v + 1) * windows_per_vector) - Wd of them (classic flavour, one per digit column) or one
+  // (table flavour).  Every other plan reads as one vector that owns all W sets.
+  u32 vectors = 1, windows_per_vector = 0;   // (0: all W)
 };
+// "one bucket set" used to mean "window-table plan": the fused digit / sort stage (msm_stages.hip 2b) and the one-launch
+// small path are for a single vector's single set only - a many-plan over a table has one set PER VECTOR
+inline bool plan_fused_sort(const MsmPlan &p) { return p.W == 1 && p.vectors == 1; }
+// what a job copies to its pinned result buffer: the 256-byte status slot, then W * c bit sums and totals (XYZZ records)
+inline size_t job_result_bytes(const MsmPlan &p, size_t xyzz_bytes) { return 256 + (size_t)p.W * p.c * xyzz_bytes; }
 // multiples 2^(c*j) P_i, j < W, stored row-major [j][i] (row 0 = the bases themselves)
 struct WindowTable {
   u32 c, W;
@@ -113,6 +126,10 @@ struct MsmJobImpl {
   float done_ms[4] = {0, 0, 0, 0};
   u64 done_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bh_msm_wait_stats
   alignas(16) unsigned char done_out[192];
+  // many-job: one affine record per vector (msm_finish); the device flags are per job, so when either is set no record
+  // is produced and the caller answers every vector by the single-vector path (many_fallback)
+  std::vector<unsigned char> many_out;
+  bool many_fallback = false;
 };
 
 
@@ -124,12 +141,17 @@ struct MsmBuffers {
 };
 MsmPlan make_plan(u64 n, unsigned forced_c, unsigned forced_chunk, bool g2);
 MsmPlan make_table_plan(u64 n, const WindowTable &t, unsigned forced_chunk, bool g2, int num_cus);
+// k scalar vectors of n scalars in one job: table != null -> table flavour (W = k sets of n * Wd entries), else classic
+// (W = k * ceil(256 / c) sets of n entries, set v * Wc + w = digit w of vector v)
+MsmPlan make_many_plan(u64 n, u64 k, const WindowTable *table, unsigned forced_c, unsigned forced_chunk, bool g2, int num_cus);
+bool many_plan_valid(const MsmPlan &p, u64 n_bases);   // the 32-bit limits of the pipeline
 unsigned table_window_bits(u64 n_bases, bool g2);   // the c a window table is built for by default
 size_t scan_tmp_elems(u64 n);
 size_t sort_counts_elems(const MsmPlan &p);   // MsmBuffers::counts holds this many + 1, scan_tmp scan_tmp_elems of that
 // runs stages 1-2 (+ per-window first non-zero position) on `st`; *sorted_out = sorted pairs
+// (scalar_stride: bytes between the scalar vectors of a many-plan)
 int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_dev, int fmt, const u64 *density_dev,
-                   u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out);
+                   u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out, u64 scalar_stride = 0);
 
 // msm_g1.hip / msm_g2.hip
 int msm_enqueue_g1(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,

@@ -659,6 +659,52 @@ def prove_witness(r1cs, params, input_assignment, aux_assignment, r, s, timings=
     return Proof(out)
 
 
+def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None):
+    """k proofs of ONE circuit in one call (bh_groth16_prove_witness_batch): witness j = (inputs_list[j], aux_list[j]),
+    blinding (rs[j], ss[j]) -> [Proof], each exactly what prove_witness returns for that witness.  inputs_list / aux_list:
+    lists of integer lists or [n, 4] Montgomery arrays, or one [k, n, 4] uint64 array each (no copy is made then).  A witness of the wrong
+    shape is refused for the whole call before anything runs, as the single call refuses it; otherwise the error the
+    first failing proof would raise is raised.  (_workspace_budget: the test library's twin of the call, which takes the
+    grouped path - many-jobs over groups of witnesses that fit that many bytes of h-block workspace, 0 = the default 1 GiB -
+    instead of keeping the proofs in flight.)"""
+    lib = _lib.load()
+    k = len(inputs_list)
+    assert len(aux_list) == k and len(rs) == k and len(ss) == k, "one aux vector and one (r, s) per witness"
+
+    def stacked(vectors, n):
+        # a [k, n, 4] uint64 array is the call's own layout (Montgomery limbs, witness j at row j): taken as it is
+        if isinstance(vectors, np.ndarray) and vectors.dtype == np.uint64 and vectors.ndim == 3 and vectors.shape[2] == 4:
+            if vectors.shape[1] != n:
+                check(-2, "create_proof (the witnesses do not have the shape of the captured circuit)")
+            return np.ascontiguousarray(vectors)
+        arrs = [fr_to_mont_array(x if isinstance(x, np.ndarray) else list(x)) for x in vectors]
+        for j, a in enumerate(arrs):
+            if a.shape[0] != n:
+                check(-2, "create_proof (witness %d does not have the shape of the captured circuit)" % j)
+        return np.ascontiguousarray(np.stack(arrs)) if n and k else np.zeros((k, 0, 4), dtype=np.uint64)
+
+    ins, auxs = stacked(inputs_list, r1cs.num_inputs), stacked(aux_list, r1cs.num_aux)
+    if k == 0:
+        return []
+    rr, sv = fr_to_mont_array(list(rs)), fr_to_mont_array(list(ss))
+    out = np.zeros((k, 48), dtype=np.uint64)
+    rcs = np.zeros(k, dtype=np.int32)
+    tm = (ctypes.c_float * 4)()
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    if _workspace_budget is None:
+        rc = lib.bh_groth16_prove_witness_batch(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k, p(rr), p(sv),
+                                                p(out), p(rcs), tm)
+    else:
+        rc = lib.bh_test_groth16_prove_witness_batch_budget(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k,
+                                                            p(rr), p(sv), p(out), p(rcs), _workspace_budget, tm)
+    check(rc, "create_proof")
+    if timings is not None:
+        timings[:] = list(tm)
+    for j in range(k):
+        check(int(rcs[j]), "create_proof")
+    return [Proof(out[j].copy()) for j in range(k)]
+
+
 def create_proof_r1cs(circuit, r1cs, params, r, s, timings=None):
     """create_proof with the constraint evaluation on the device: only `circuit`'s value closures run here."""
     w = WitnessAssignment()

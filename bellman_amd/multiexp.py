@@ -239,6 +239,7 @@ class MsmOpts(ctypes.Structure):
 
 
 ACC_REGISTERS, ACC_LDS, NO_TABLE, NO_SMALL_PATH, G2_SINGLE_LANE, G2_LANE_TRIPLES, STAGE_TIMES, HOLD, G2_LANE_PAIRS = 1, 2, 4, 8, 16, 32, 64, 128, 256
+MANY_FORCE = 512   # multiexp_many: take the many-plan wherever it is valid
 
 
 STATS_FIELDS = ("sorted_entries", "zero_digits", "mixed_additions", "chunk_lanes", "window_bits", "chunk", "bucket_sets", "digit_columns")
@@ -289,6 +290,67 @@ def multiexp(pool, bases, density_map, exponents, skip=0, mont=False, timed=Fals
     w_ = Waiter(fn=finish)
     w_.start = lambda: check(lib.bh_msm_start(job), "multiexp.start")   # for jobs issued with flags=HOLD
     return w_
+
+
+def multiexp_many(pool, bases, density_map, exponents, skip=0, mont=False, window_bits=0, chunk=0, flags=0, stats=False,
+                  scalars_dev=None, stride=None, n=None, k=None, density_dev=None, after_stream=None):
+    """k multiexps over ONE base vector and density map in one job (bh_msm_many_*) -> Waiter.
+
+    exponents: [k, n, 4] uint64 scalars on the host; or pass scalars_dev (device pointer), stride (bytes between the
+    vectors, default 32 n), n and k (and density_dev for a resident density map).  The Waiter's wait() returns a list of
+    k items: the affine result record (numpy uint64[12|24]) of vector v, or the SynthesisError instance the single call
+    would raise for it (returned, not raised).  With stats=True it returns (items, [total, sort, accumulate, reduce]
+    device ms, dict over STATS_FIELDS) for the whole job.  flags: MANY_FORCE takes the many-plan wherever it is valid,
+    NO_TABLE its classic flavour; without MANY_FORCE the library chooses between the many-plan and k ordinary jobs."""
+    from .errors import UnexpectedEof, UnexpectedIdentity
+
+    lib = _lib.load()
+    words, dlen = None, 0
+    if isinstance(density_map, DensityTracker):
+        dlen = density_map.get_query_size()
+        words = density_map.words()
+    job = ctypes.c_void_p()
+    fmt = 1 if mont else 0
+    opts = MsmOpts(window_bits, chunk, flags | (STAGE_TIMES if stats else 0))
+    po = ctypes.cast(ctypes.pointer(opts), ctypes.c_void_p)
+    sc = None
+    if scalars_dev is None:
+        sc = np.ascontiguousarray(exponents, dtype=np.uint64)
+        assert sc.ndim == 3 and sc.shape[2] == 4, "exponents: [k, n, 4] uint64"
+        k, n = sc.shape[0], sc.shape[1]
+        rc = lib.bh_msm_many_async(pool.ctx, bases._h, skip, sc.ctypes.data_as(ctypes.c_void_p), 32 * n, n, k, fmt,
+                                   None if words is None else words.ctypes.data_as(ctypes.c_void_p), dlen, po,
+                                   ctypes.byref(job))
+    else:
+        stride = 32 * n if stride is None else stride
+        rc = lib.bh_msm_many_async_dev(pool.ctx, bases._h, skip, scalars_dev, stride, n, k, fmt, density_dev,
+                                       dlen if density_dev is not None else 0, po, after_stream, ctypes.byref(job))
+    check(rc, "multiexp_many")
+    w = _WORDS[bases.group]
+
+    def finish():
+        _keep = (sc, words)  # noqa: F841  (alive until the job has been waited on)
+        out = np.zeros((k, w), dtype=np.uint64)
+        rcs = np.zeros(k, dtype=np.int32)
+        ms = (ctypes.c_float * 4)()
+        st = (ctypes.c_uint64 * 8)()
+        check(lib.bh_msm_many_wait(job, out.ctypes.data_as(ctypes.c_void_p), rcs.ctypes.data_as(ctypes.c_void_p), ms, st),
+              "multiexp_many.wait")
+        items = []
+        for v in range(k):
+            if rcs[v] == 0:
+                items.append(out[v].copy())
+            elif rcs[v] == 1:
+                items.append(UnexpectedIdentity())
+            elif rcs[v] == 2:
+                items.append(UnexpectedEof("expected more bases from source"))
+            else:
+                check(int(rcs[v]), "multiexp_many.wait")
+        if stats:
+            return items, list(ms), dict(zip(STATS_FIELDS, (int(x) for x in st)))
+        return items
+
+    return Waiter(fn=finish)
 
 
 class Scalars:

@@ -341,6 +341,53 @@ int bh_msm_async_dev_after(bh_ctx *ctx, const bh_bases *bases, size_t skip, cons
                            int scalar_fmt, const uint64_t *density_words_dev, size_t density_len, const bh_msm_opts *opts,
                            void *after_stream, bh_msm_job **job);
 
+/* ---- several scalar vectors over ONE base vector in one job ---------------------------------------------
+ * out[v] = multiexp(pool, (bases, skip), density, exponents_v) for v < k: one base vector, one density map (it belongs
+ * to the circuit), k scalar vectors of n_scalars x 32 bytes, vector v at scalars + v * stride_bytes (stride_bytes >=
+ * 32 n_scalars and a multiple of 32, else BH_ERR_INVALID_ARG).  The reference has no twin: it is k calls of multiexp,
+ * which is also what every result and return code is defined by.  Proofs of one circuit share their bases and density
+ * maps and differ in the scalars only; the many-plan pays the launch chain of a multiexp once - one digit stage, one sort,
+ * one accumulate launch, one reduction, vector v taking the place of a window (table flavour: one bucket set per vector;
+ * classic flavour: ceil(256 / c) sets per vector) - and runs the serial tail per vector on the host.
+ *   dispatch   k = 0: BH_OK, nothing is written.  k = 1, and the host entry with n_scalars <= 8 (answered on the host at
+ *              issue time), never use the many-plan.  Otherwise a size rule chooses between the many-plan and k ordinary
+ *              jobs issued together and waited in order inside the same call; the rule is taken from
+ *              profiles/msm_many_bench.json and is "never" where the many-plan was not measured faster: it takes the
+ *              many-plan for 4 <= k <= 16 vectors of 2^10 ... 2^18 scalars over bases that have a window table.  A plan
+ *              the rule chose and the pipeline or the pool cannot serve falls back to the ordinary jobs: the default
+ *              call accepts every k that k calls of bh_msm_async_dev accept.
+ *              BH_MSM_MANY_FORCE in opts.flags takes the many-plan wherever it is valid (k >= 2, n_scalars >= 1, and
+ *              the 32-bit limits: bucket sets x entries per set < 2^32, at most 65535 sets, base index < 2^31 - beyond
+ *              them BH_ERR_INVALID_ARG); BH_MSM_NO_TABLE forces its classic flavour.  BH_MSM_HOLD is BH_ERR_INVALID_ARG.
+ *   limits     a many-plan job counts as ONE job under max_jobs_in_flight.
+ *   after_stream (optional) as in bh_msm_async_dev_after.  The host entry uploads the k vectors and the density map once
+ *              and keeps them until the wait; it returns when that upload has finished (unlike bh_msm_async, whose
+ *              copy rides the job's stream) - the caller's arrays may be reused at once.  A many-plan job whose W * c
+ *              result records do not fit the 256 KB pinned buffer of a job's resources replaces that buffer at issue
+ *              time, which waits for the device once per growth; the larger buffer stays with the recycled resources.
+ *   wait       k affine records and k return codes: BH_OK / BH_ERR_UNEXPECTED_IDENTITY / BH_ERR_UNEXPECTED_EOF, each
+ *              exactly what the single call returns for that vector; a failed vector's record is all-zero.  The device
+ *              status flags of a many-plan job are per JOB: if either is set once the job has run, every vector is
+ *              answered again by the single-vector path over the still-resident inputs (errors are rare; this gives each
+ *              vector the reference's precedence rule).  The return value carries call-level outcomes only (BH_OK,
+ *              BH_ERR_INVALID_ARG, BH_ERR_HIP), as for bh_groth16_verify_each.  stage_ms4 and stats8 are optional and describe
+ *              the whole job as bh_msm_wait_stats does (k ordinary jobs: the sums of [0..3], the plan of the last).
+ *              scalars, density (device entry) and bases stay valid until the wait. */
+typedef struct bh_msm_many_job bh_msm_many_job;
+#define BH_MSM_MANY_FORCE 512u /* bh_msm_many_*: take the many-plan wherever it is valid */
+int bh_msm_many_async_dev(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars_dev, size_t stride_bytes,
+                          size_t n_scalars, size_t k, int scalar_fmt, const uint64_t *density_words_dev, size_t density_len,
+                          const bh_msm_opts *opts, void *after_stream, bh_msm_many_job **job);
+int bh_msm_many_async(bh_ctx *ctx, const bh_bases *bases, size_t skip, const void *scalars_host, size_t stride_bytes,
+                      size_t n_scalars, size_t k, int scalar_fmt, const uint64_t *density_words, size_t density_len,
+                      const bh_msm_opts *opts, bh_msm_many_job **job);
+int bh_msm_many_wait(bh_msm_many_job *job, void *out_affine_k, int32_t *rcs_k, float *stage_ms4, uint64_t *stats8);
+/* The plan a many-job of k vectors of n scalars would run (host only, no context): table_bits = 0 the classic flavour,
+ * else the table flavour over a window table of that many bits; num_cus = 0: 256.  out12 = c, bucket sets W, buckets per
+ * set, K, chunks per set, sort passes, entries per set, vectors, sets per vector, digit columns per scalar, and the bytes
+ * of the job's result buffer (low, high word).  BH_ERR_INVALID_ARG beyond the 32-bit limits above. */
+int bh_msm_many_plan_info(size_t n, size_t k, int group, unsigned table_bits, unsigned num_cus, unsigned *out12);
+
 /* ---- scalar vectors resident in HBM ------------------------------------------------------------------
  * create_proof hands the same `Arc<Vec<Exponent>>` to several multiexps (groth16/src/prover.rs:267,279,285,300,306,
  * 316,318: input_assignment to three, aux_assignment to four): registered once, uploaded once.  scalar_fmt as for
@@ -797,6 +844,24 @@ int bh_groth16_params_verify_step(bh_ctx *ctx, const bh_params *before, const bh
 int bh_groth16_prove_witness(bh_params *params, const bh_r1cs *r1cs, const void *input_assignment,
                              size_t n_inputs, const void *aux_assignment, size_t n_aux, const void *r,
                              const void *s, void *proof_out, float *timings4);
+/* k proofs of ONE circuit in one call (the reference: k calls of create_proof, prover.rs:217-360): witness j =
+ * (inputs + j * n_inputs * 32, aux + j * n_aux * 32), blinding (r + 32 j, s + 32 j); proofs_out + j * 384 receives
+ * exactly the bytes bh_groth16_prove_witness writes for witness j (all-zero when rcs[j] != BH_OK), rcs[j] its return code:
+ * BH_OK, BH_ERR_UNEXPECTED_IDENTITY (an identity delta - every proof - or an identity base met by a multiexp) or
+ * BH_ERR_UNEXPECTED_EOF, with the order of reported errors per proof that the single call has.  The return value
+ * carries call-level outcomes only: BH_OK, BH_ERR_INVALID_ARG (a null argument, or n_inputs / n_aux do not match the
+ * R1CS: refused before anything runs), BH_ERR_DEGREE_TOO_LARGE, BH_ERR_HIP.  k = 0 is BH_OK.
+ * How it runs: the proofs go through the single-proof path, at most 16 of them in flight at a time (device memory
+ * stays bounded: any k is accepted), and are waited for in order.  A grouped path exists behind it (csrc/groth16.hpp,
+ * BATCH_GROUPED): the five long multiexps of a group of proofs (l, a_aux, b_g1_aux, b_g2_aux, h) as five many-jobs over
+ * the shared bases and densities, the h blocks one after the other on one stream, groups of g witnesses with
+ * (g + 3) * m * 32 bytes <= a workspace budget of 1 GiB (m = the evaluation domain's size).  Measured against the proofs
+ * in flight it is 0.51 - 1.29 x and beyond the run's own spread at two shapes of eight, other ones than in the run before
+ * (profiles/prove_batch_bench.json): no basis for a rule, so this call never takes it.
+ * Witness path, synchronous, one GPU; timings4 as bh_groth16_prove_witness, [1] and [2] summed over the proofs. */
+int bh_groth16_prove_witness_batch(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                   const void *aux, size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out,
+                                   int32_t *rcs, float *timings4);
 /* ---- one caller, proofs back to back: create_proof split at the synthesis / device boundary -----------------
  * The reference's create_proof is synthesis on the host (groth16/src/prover.rs:182-215) followed by the device part
  * (:217-360); a single caller that proves in a loop leaves the GPU idle during every synthesis and the host idle during

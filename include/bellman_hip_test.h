@@ -423,6 +423,25 @@ int bh_test_groth16_prove_via_call_sites(bh_params *params, int mode, const void
                                          const uint64_t *a_aux_density, const uint64_t *b_input_density,
                                          const uint64_t *b_aux_density, const void *r, const void *s, void *proof_out,
                                          float *ms2);
+/* bh_test_many_stage_dev: msm_run_stages once, on the context's stream, under the many-plan make_many_plan gives for k
+ * vectors of nd scalars (table != 0: the table flavour over a window table of c bits and `stride` bases per row; else the
+ * classic flavour with window size c, stride = 0): the density prefix, msm_many_digits_kernel, the 8-bit sort of every
+ * bucket set and the zero-digit search.  scalars: k * nd * 32 bytes, vector v at v * nd * 32 (Montgomery ones below q);
+ * density_words optional, ceil(nd / 64) words.  At most 2^22 entries.  Buffers as msm_enqueue sizes them, without its
+ * rounding to 256 bytes, each with a guard behind it; ErrFlags starts zeroed, everything else holds the sentinel byte.
+ * sorted_out: the W * n sorted pairs (bucket set s at s * n); zstart_out: W words; err_out: one ErrFlags; plan_out4 =
+ * [W, entries per set, sort passes, digit columns]; guards_out8: 1 = intact, for pairs_a, pairs_b, counts, scan scratch,
+ * zstart, word prefix, ErrFlags, scalars. */
+int bh_test_many_stage_dev(bh_ctx *ctx, int table, unsigned c, const void *scalars, int fmt, size_t nd, size_t k,
+                           const uint64_t *density_words, size_t skip, size_t n_bases, size_t stride, uint64_t *sorted_out,
+                           uint32_t *zstart_out, void *err_out, uint32_t plan_out4[4], uint32_t guards_out8[8]);
+/* bh_groth16_prove_witness_batch through its grouped path - five many-jobs per group of witnesses, which the product call
+ * does not take by itself (include/bellman_hip.h) - with a workspace budget in bytes of the caller's choice (0: 1 GiB): the
+ * witnesses are proved in groups of g with (g + 3) * m * 32 <= workspace_budget, at least one per group; timings4
+ * (optional) as the product call, [1] = host time from the start of each group to the issue of its last many-job */
+int bh_test_groth16_prove_witness_batch_budget(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                               const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                               void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,11 @@ pub struct BhPvk {
 pub struct BhPvkSet {
     _private: [u8; 0],
 }
+/// opaque `bh_msm_many_job`
+#[repr(C)]
+pub struct BhMsmManyJob {
+    _private: [u8; 0],
+}
 /// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -223,6 +228,10 @@ extern "C" {
     pub fn bh_msm_async_dev_opts(ctx: *mut BhCtx, bases: *const BhBases, skip: usize, scalars_dev: *const c_void, n_scalars: usize, scalar_fmt: c_int, density_words_dev: *const u64, density_len: usize, opts: *const BhMsmOpts, job: *mut *mut BhMsmJob) -> c_int;
     pub fn bh_msm_start(job: *mut BhMsmJob) -> c_int;
     pub fn bh_msm_async_dev_after(ctx: *mut BhCtx, bases: *const BhBases, skip: usize, scalars_dev: *const c_void, n_scalars: usize, scalar_fmt: c_int, density_words_dev: *const u64, density_len: usize, opts: *const BhMsmOpts, after_stream: *mut c_void, job: *mut *mut BhMsmJob) -> c_int;
+    pub fn bh_msm_many_async_dev(ctx: *mut BhCtx, bases: *const BhBases, skip: usize, scalars_dev: *const c_void, stride_bytes: usize, n_scalars: usize, k: usize, scalar_fmt: c_int, density_words_dev: *const u64, density_len: usize, opts: *const BhMsmOpts, after_stream: *mut c_void, job: *mut *mut BhMsmManyJob) -> c_int;
+    pub fn bh_msm_many_async(ctx: *mut BhCtx, bases: *const BhBases, skip: usize, scalars_host: *const c_void, stride_bytes: usize, n_scalars: usize, k: usize, scalar_fmt: c_int, density_words: *const u64, density_len: usize, opts: *const BhMsmOpts, job: *mut *mut BhMsmManyJob) -> c_int;
+    pub fn bh_msm_many_wait(job: *mut BhMsmManyJob, out_affine_k: *mut c_void, rcs_k: *mut i32, stage_ms4: *mut f32, stats8: *mut u64) -> c_int;
+    pub fn bh_msm_many_plan_info(n: usize, k: usize, group: c_int, table_bits: c_uint, num_cus: c_uint, out12: *mut c_uint) -> c_int;
     pub fn bh_scalars_register(ctx: *mut BhCtx, scalars_host: *const c_void, n: usize, scalar_fmt: c_int, out: *mut *mut BhScalars) -> c_int;
     pub fn bh_scalars_adopt_dev(ctx: *mut BhCtx, scalars_dev: *mut c_void, n: usize, scalar_fmt: c_int, take_ownership: c_int, out: *mut *mut BhScalars) -> c_int;
     pub fn bh_scalars_release(s: *mut BhScalars);
@@ -280,6 +289,7 @@ extern "C" {
     pub fn bh_pairing_same_ratio_each(ctx: *mut BhCtx, a_g1: *const c_void, b_g1: *const c_void, A_g2: *const c_void, B_g2: *const c_void, n: usize, verdicts: *mut i32, n_bad: *mut usize) -> c_int;
     pub fn bh_groth16_params_verify_step(ctx: *mut BhCtx, before: *const BhParams, after: *const BhParams, seed32: *const c_void, flags: c_uint, report: *mut BhParamsStepReport) -> c_int;
     pub fn bh_groth16_prove_witness(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
+    pub fn bh_groth16_prove_witness_batch(params: *mut BhParams, r1cs: *const BhR1cs, inputs: *const c_void, n_inputs: usize, aux: *const c_void, n_aux: usize, k: usize, r: *const c_void, s: *const c_void, proofs_out: *mut c_void, rcs: *mut i32, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_assignment_async(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_prove_witness_async(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_proof_wait(job: *mut BhProofJob, proof_out: *mut c_void, timings4: *mut f32) -> c_int;

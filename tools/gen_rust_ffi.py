@@ -13,7 +13,7 @@ OUT = os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")
 
 OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "bh_params": "BhParams", "bh_r1cs": "BhR1cs",
           "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
-          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet"}
+          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet", "bh_msm_many_job": "BhMsmManyJob"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo",
            "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport",
            "bh_params_step_report": "BhParamsStepReport"}
