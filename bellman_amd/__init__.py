@@ -24,7 +24,7 @@ from .errors import (  # noqa: F401
 from .multicore import Waiter, Worker  # noqa: F401
 from .multiexp import Bases, DensityTracker, FullDensity, Scalars, multiexp, multiexp_scalars, multiexp_sharded, point_add  # noqa: F401
 from .multiexp import MANY_FORCE, multiexp_many  # noqa: F401
-from .domain import EvaluationDomain, PointEvaluationDomain  # noqa: F401
+from .domain import EvaluationDomain, EvaluationDomains, PointEvaluationDomain, h_poly_many  # noqa: F401
 from . import verifier  # noqa: F401,E402
 from .verifier import (KeySet, MultiVerifier, PreparedVerifyingKey, Verifier, prepare_verifying_key, verify_each,  # noqa: F401,E402
                        verify_each_keys, verify_proof)

@@ -31,6 +31,7 @@ EXPORTS = [
     "bh_fft_fr", "bh_fft_fr_dev", "bh_fr_mul_assign_dev", "bh_fr_sub_assign_dev",
     "bh_fr_divide_by_z_on_coset_dev", "bh_fr_distribute_powers_dev", "bh_fft_point_dev", "bh_point_distribute_powers_dev", "bh_point_divide_by_z_on_coset_dev",
     "bh_point_mul_assign_dev", "bh_point_sub_assign_dev", "bh_h_poly_fr", "bh_h_poly_fr_dev", "bh_h_poly_fr_dev_on",
+    "bh_fft_fr_many_dev_on", "bh_fft_fr_many_dev", "bh_fft_fr_many", "bh_h_poly_fr_many_dev_on",
     "bh_bases_register", "bh_bases_register_uncompressed", "bh_bases_read_uncompressed", "bh_bases_read_compressed", "bh_bases_download", "bh_bases_write_uncompressed", "bh_bases_copy_dev", "bh_bases_copy_out_dev", "bh_bases_precompute", "bh_bases_table_info", "bh_bases_wrap_dev", "bh_bases_release", "bh_bases_len",
     "bh_msm_async", "bh_msm_async_dev", "bh_msm_wait", "bh_msm_wait_timed", "bh_msm_wait_profile", "bh_msm_wait_stats", "bh_msm_plan_info", "bh_msm_debug_stages", "bh_point_add", "bh_point_mul", "bh_point_lincomb", "bh_msm_async_opts", "bh_msm_async_dev_opts",
     "bh_scalars_register", "bh_scalars_adopt_dev", "bh_scalars_release", "bh_scalars_len", "bh_scalars_dev_ptr", "bh_msm_async_scalars", "bh_h_poly_fr_scalars", "bh_msm_async_dev_after", "bh_msm_start",
@@ -73,6 +74,7 @@ TEST_EXPORTS = [
     "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
     "bh_test_glv_split_host", "bh_test_glv_ladder_host", "bh_test_glv_ladder_dev",
     "bh_test_groth16_prove_witness_batch_budget", "bh_test_many_stage_dev",
+    "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan",
 ]
 
 
@@ -191,6 +193,12 @@ def load():
     lib.bh_h_poly_fr.argtypes = [vp, vp, vp, vp, sz, vp, c.POINTER(sz)]
     lib.bh_h_poly_fr_dev.argtypes = [vp, vp, vp, vp, u32, vp]
     lib.bh_h_poly_fr_dev_on.argtypes = [vp, vp, vp, vp, vp, u32, vp]
+    lib.bh_fft_fr_many_dev_on.argtypes = [vp, vp, sz, sz, u32, i32, c.c_uint, vp, sz, vp]
+    lib.bh_fft_fr_many_dev.argtypes = [vp, vp, sz, sz, u32, i32, c.c_uint, vp]
+    lib.bh_fft_fr_many.argtypes = [vp, vp, sz, u32, i32]
+    lib.bh_h_poly_fr_many_dev_on.argtypes = [vp, vp, vp, vp, sz, sz, u32, c.c_uint, vp, sz, vp]
+    lib.bh_test_fft_many_plan.argtypes = [u32, sz, sz, sz, i32, vp, sz]
+    lib.bh_test_groth16_prove_witness_batch_mode.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, i32, vp]
     lib.bh_bases_register.argtypes = [vp, i32, vp, sz, sz, c.c_long, c.POINTER(vp)]
     lib.bh_bases_register_uncompressed.argtypes = [vp, i32, vp, sz, c.POINTER(vp)]
     lib.bh_bases_wrap_dev.argtypes = [vp, i32, vp, sz, c.POINTER(vp)]

@@ -21,6 +21,11 @@ int fr_divide_by_z(Context &c, fr_t *a, uint32_t log_n, hipStream_t st);
 int fr_distribute_powers(Context &c, fr_t *a, u64 n, const fr_t &g, hipStream_t st);
 int h_poly_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, fr_t *scratch, uint32_t log_n, hipStream_t st);
 int fr_gen_powers(Context &c, fr_t *out, u64 n, const fr_t &g, const fr_t &scale, hipStream_t st);
+int ntt_run_many(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int mode, fr_t *scratch, u64 scratch_vectors, hipStream_t st);
+int ntt_run_each(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int mode, fr_t *scratch, hipStream_t st);
+int h_poly_many_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, u64 stride, u64 k, uint32_t log_n, fr_t *scratch, u64 scratch_vectors,
+                    hipStream_t st);
+int h_poly_each_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, u64 stride, u64 k, uint32_t log_n, fr_t *scratch, hipStream_t st);
 // point_fft.hip
 int point_fft(Context &c, int group, void *pts, uint32_t log_n, int mode, hipStream_t st);
 int point_distribute_powers(Context &c, int group, void *pts, u64 n, const fr_t &g, hipStream_t st);
@@ -614,6 +619,109 @@ int bh_fft_fr(bh_ctx *ctx, void *data_host, uint32_t log_n, int mode) {
   if (rc == BH_OK) rc = bh_dev_download(ctx, data_host, d, bytes);
   ctx->c.pool.release(d);
   return rc;
+}
+// ---- k vectors per call (fft.hip ntt_run_many) ------------------------------------------------------------------
+// Where the batched launches replace k single-vector transforms without being asked to (BH_FFT_MANY_FORCE).  Set from
+// profiles/fft_many_bench.json (tools/bench_fft_many.py): a shape is taken only where the batched call's min-of-5 wall time
+// is below the baseline's by more than the baseline's own spread in that run.  Shapes nobody measured take the single path.
+// Measured (MI355X, 2^6 ... 2^22 points in steps of 4x, k = 2, 4, 16, 64 with k * n <= 2^24; ifft at every k, the four modes
+// at k = 4, the h block at every k):
+//   transforms  win at every measured shape from 2^6 to 2^20 (2^8 x 64: 0.050 ms against 1.68; 2^16 x 4: 0.069 against
+//               0.25; 2^20 x 16: 1.65 against 2.16) and not at 2^22 (0.97 - 1.01 x; one shape of five, coset_fft x 4, is 1 %
+//               beyond the spread in one run of two: the passes fill the chip by themselves, and the table entries a
+//               group of vectors could share are not what bounds them);
+//   h blocks    win from 2^12 to 2^20 at every k (2^14 x 4: 0.36 ms against 1.37), from 2^6 to 2^10 at k >= 4 only (at k = 2
+//               the single h block's own three-vector launches are 0.16 - 0.22 ms against 0.22 - 0.34), and not at 2^22
+//               (0.91 - 0.96 x).
+// The rule covers the measured box and what lies between its points (odd log_n, k = 3, 5 ... 63).  Outside it - fewer than
+// 2^6 or more than 2^20 points, k = 1, k > 64, more than 2^24 elements in all - the call issues single-vector transforms.
+constexpr uint32_t FFT_MANY_RULE_LOG_N_MIN = 6, FFT_MANY_RULE_LOG_N_MAX = 20, FFT_MANY_RULE_LOG_ELEMS_MAX = 24;
+constexpr size_t FFT_MANY_RULE_K_MIN = 2, FFT_MANY_RULE_K_MAX = 64, FFT_MANY_RULE_H_SMALL_K_MIN = 4;
+static bool fft_many_wins(uint32_t log_n, size_t k, bool h_block = false) {
+  if (log_n < FFT_MANY_RULE_LOG_N_MIN || log_n > FFT_MANY_RULE_LOG_N_MAX || k < FFT_MANY_RULE_K_MIN || k > FFT_MANY_RULE_K_MAX) return false;
+  if ((k << log_n) > ((size_t)1 << FFT_MANY_RULE_LOG_ELEMS_MAX)) return false;
+  if (h_block && log_n <= 11 && k < FFT_MANY_RULE_H_SMALL_K_MIN) return false;
+  return true;
+}
+// the checks the four calls share; *use_many: batched launches or k single-vector transforms
+static int fft_many_args(bh_ctx *ctx, const void *data, size_t stride_bytes, size_t k, uint32_t log_n, int mode, unsigned flags,
+                         bool *use_many, bool h_block = false) {
+  if (log_n >= 32) return BH_ERR_DEGREE_TOO_LARGE;
+  if (!ctx || !data || mode < 0 || mode > 3) return BH_ERR_INVALID_ARG;
+  if (stride_bytes < ((size_t)sizeof(fr_t) << log_n) || stride_bytes % sizeof(fr_t)) return BH_ERR_INVALID_ARG;
+  if ((flags & ~(unsigned)(BH_FFT_MANY_FORCE | BH_FFT_MANY_SINGLE)) || flags == (BH_FFT_MANY_FORCE | BH_FFT_MANY_SINGLE))
+    return BH_ERR_INVALID_ARG;
+  *use_many = (flags & BH_FFT_MANY_FORCE) || (!(flags & BH_FFT_MANY_SINGLE) && fft_many_wins(log_n, k, h_block));
+  return BH_OK;
+}
+static bool fft_many_scratch_ok(uint32_t log_n, const void *scratch, size_t scratch_bytes) {
+  return log_n <= 11 || (scratch && scratch_bytes >= ((size_t)sizeof(fr_t) << log_n));
+}
+int bh_fft_fr_many_dev_on(bh_ctx *ctx, void *data_dev, size_t stride_bytes, size_t k, uint32_t log_n, int mode, unsigned flags,
+                          void *scratch_dev, size_t scratch_bytes, void *stream) {
+  bool use_many = false;
+  int rc = fft_many_args(ctx, data_dev, stride_bytes, k, log_n, mode, flags, &use_many);
+  if (rc) return rc;
+  if (!fft_many_scratch_ok(log_n, scratch_dev, scratch_bytes)) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = pick_stream(ctx, stream);
+  const u64 stride = stride_bytes / sizeof(fr_t);
+  if (!use_many) return ntt_run_each(ctx->c, (fr_t *)data_dev, stride, k, log_n, mode, (fr_t *)scratch_dev, st);
+  return ntt_run_many(ctx->c, (fr_t *)data_dev, stride, k, log_n, mode, (fr_t *)scratch_dev, scratch_bytes >> (log_n + 5), st);
+}
+int bh_fft_fr_many_dev(bh_ctx *ctx, void *data_dev, size_t stride_bytes, size_t k, uint32_t log_n, int mode, unsigned flags,
+                       void *stream) {
+  bool use_many = false;
+  int rc = fft_many_args(ctx, data_dev, stride_bytes, k, log_n, mode, flags, &use_many);
+  if (rc || !k) return rc;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = pick_stream(ctx, stream);
+  void *scratch = nullptr;
+  size_t scratch_bytes = 0;
+  if (log_n > 11) {
+    // a scratch vector per transformed vector, up to 256 MiB; one vector where the pool cannot give more
+    const size_t one = sizeof(fr_t) << log_n;
+    size_t vecs = use_many ? k : 1;
+    while (vecs > 1 && vecs * one > ((size_t)256 << 20)) vecs = (vecs + 1) / 2;
+    scratch = ctx->c.pool.acquire(vecs * one);
+    if (!scratch && vecs > 1) { vecs = 1; scratch = ctx->c.pool.acquire(one); }
+    if (!scratch) return BH_ERR_HIP;
+    scratch_bytes = vecs * one;
+  }
+  rc = bh_fft_fr_many_dev_on(ctx, data_dev, stride_bytes, k, log_n, mode, flags, scratch, scratch_bytes, stream);
+  if (scratch) {
+    // the scratch buffer may be recycled by another stream: fence before returning it
+    if (hipStreamSynchronize(st) != hipSuccess && rc == BH_OK) rc = BH_ERR_HIP;
+    ctx->c.pool.release(scratch);
+  }
+  return rc;
+}
+int bh_fft_fr_many(bh_ctx *ctx, void *data_host, size_t k, uint32_t log_n, int mode) {
+  if (log_n >= 32) return BH_ERR_DEGREE_TOO_LARGE;
+  if (!ctx || !data_host || mode < 0 || mode > 3) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  const size_t one = sizeof(fr_t) << log_n, bytes = one * k;
+  void *d = ctx->c.pool.acquire(bytes);
+  if (!d) return BH_ERR_HIP;
+  int rc = bh_dev_upload(ctx, d, data_host, bytes);
+  if (rc == BH_OK) rc = bh_fft_fr_many_dev(ctx, d, one, k, log_n, mode, 0, nullptr);
+  if (rc == BH_OK) rc = bh_dev_download(ctx, data_host, d, bytes);
+  ctx->c.pool.release(d);
+  return rc;
+}
+int bh_h_poly_fr_many_dev_on(bh_ctx *ctx, void *a, void *b, void *c, size_t stride_bytes, size_t k, uint32_t log_n, unsigned flags,
+                             void *scratch_dev, size_t scratch_bytes, void *stream) {
+  bool use_many = false;
+  int rc = fft_many_args(ctx, a, stride_bytes, k, log_n, BH_FFT, flags, &use_many, true);
+  if (rc) return rc;
+  if (!b || !c || !fft_many_scratch_ok(log_n, scratch_dev, scratch_bytes)) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = pick_stream(ctx, stream);
+  const u64 stride = stride_bytes / sizeof(fr_t);
+  if (!use_many) return h_poly_each_dev(ctx->c, (fr_t *)a, (fr_t *)b, (fr_t *)c, stride, k, log_n, (fr_t *)scratch_dev, st);
+  return h_poly_many_dev(ctx->c, (fr_t *)a, (fr_t *)b, (fr_t *)c, stride, k, log_n, (fr_t *)scratch_dev, scratch_bytes >> (log_n + 5), st);
 }
 int bh_fr_mul_assign_dev(bh_ctx *ctx, void *a, const void *b, size_t n, void *stream) {
   return fr_mul_assign(ctx->c, (fr_t *)a, (const fr_t *)b, n, pick_stream(ctx, stream));

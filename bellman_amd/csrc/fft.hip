@@ -48,6 +48,7 @@
 // assignment is XCD-aware: tiles that share 128-byte lines (the narrow tiles of the 2^21 / 2^22 plans) go to the
 // same XCD back to back, so the other half of a line is an L2 hit instead of a second HBM fetch.
 #include "common.hpp"
+#include "fft_plan.hpp"
 
 namespace bh {
 
@@ -96,6 +97,19 @@ struct NttPass {
   u32 r1;             // radix bits of pass 1 (L == 3: storage order of the middle digit)
   u32 xcd_swizzle;    // tiles % 8 == 0: blockIdx -> tile so that neighbouring tiles share an XCD
 };
+// the second argument of the batched launch (ntt_pass_kernel<ONE, true>; plans in fft_plan.hpp): vector j of the launch is read at
+// in + j * in_stride and written at out + j * out_stride
+struct NttMany {
+  u64 in_stride, out_stride;   // in elements
+  u32 n_vec;                   // vectors of this launch
+  u32 log_v;                   // single-pass sizes: a tile holds 2^log_v vectors, one per column (= NttPass::log_c)
+};
+struct NttPassMany : NttPass { NttMany mv; };
+// the argument of ntt_pass_kernel<ONE, MANY>: the single-vector kernel takes the NttPass alone, as it always did
+template <bool MANY> struct NttArgs { typedef NttPass type; };
+template <> struct NttArgs<true> { typedef NttPassMany type; };
+__device__ __forceinline__ NttMany ntt_many_of(const NttPass &) { return NttMany(); }
+__device__ __forceinline__ NttMany ntt_many_of(const NttPassMany &a) { return a.mv; }
 
 __device__ __forceinline__ fr_t ld_fr(const fr_t *p) {
   fr_t v;
@@ -332,20 +346,44 @@ __device__ __forceinline__ TileGeo tile_geo(const NttPass &a, u64 t) {
 // table and pass), so the chain "multiply while the next entry loads" of the two-level path - whose entries sit in L2 -
 // left a third of the wave cycles waiting (profiles/archive/r4_final_pmc_g2_pairs_and_fft.json: SQ_WAIT_ANY 32 %): all eight
 // entries of a thread are loaded at once, beside the data, before the first product.
-template <bool ONE>
-__global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void ntt_pass_kernel(NttPass a) {
+//
+// MANY: the batched form (bh_fft_fr_many_*): k vectors a stride apart in one launch.  Multi-pass sizes: the grid covers
+// (tile, vector) with the workgroups of one tile neighbours on one XCD (fft_many_block), so a one-level entry that streams
+// from HBM for the first vector is an L2 hit for the others; only the vector's base differs from the single-vector pass.
+// Single-pass sizes (never ONE): the tile's columns are 2^log_v VECTORS - rows contiguous, column stride = the vector stride,
+// table indices by row only - and the dead columns of the last tile neither load nor store.  With MANY = false every
+// batched branch is compiled out and the argument is the NttPass alone: the single-vector kernel as it was.
+template <bool ONE, bool MANY = false>
+__global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void ntt_pass_kernel(typename NttArgs<MANY>::type a) {
   constexpr int TH = NttCfg<ONE>::TH, GMAX = NttCfg<ONE>::GMAX;
+  constexpr bool PACK = MANY && !ONE;   // (single-pass sizes have no one-level tables)
   __shared__ uint4 plane0[NTT_PLANE];
   __shared__ uint4 plane1[NTT_PLANE];
+  const NttMany mv = ntt_many_of(a);
   const u32 R = 1u << a.r, C = 1u << a.log_c;
   const u32 tid = threadIdx.x;
-  const fr_t *vin = blockIdx.y == 0 ? a.in : a.in_y[blockIdx.y - 1];
-  fr_t *vout = blockIdx.y == 0 ? a.out : a.out_y[blockIdx.y - 1];
+  const fr_t *vin = MANY ? a.in : (blockIdx.y == 0 ? a.in : a.in_y[blockIdx.y - 1]);
+  fr_t *vout = MANY ? a.out : (blockIdx.y == 0 ? a.out : a.out_y[blockIdx.y - 1]);
   const u32 n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
   // ---- which tile (XCD-aware: blocks b, b+8, b+16, ... run on one XCD and get consecutive tiles) ------------
   u64 t = blockIdx.x;
-  if (a.xcd_swizzle) {
+  const bool packed = PACK && a.L == 1;
+  u32 live_cols = C;   // packed: the vectors this tile holds
+  if constexpr (MANY) {
+    if (packed) {
+      const u64 v0 = (u64)blockIdx.x << mv.log_v;
+      live_cols = mv.n_vec - v0 < (u64)C ? (u32)(mv.n_vec - v0) : C;
+      vin += v0 * mv.in_stride;
+      vout += v0 * mv.out_stride;
+      t = 0;
+    } else {
+      u32 vec;
+      fft_many_block(blockIdx.x, gridDim.x, mv.n_vec, a.xcd_swizzle, &t, &vec);
+      vin += (u64)vec * mv.in_stride;
+      vout += (u64)vec * mv.out_stride;
+    }
+  } else if (a.xcd_swizzle) {
     const u32 per_xcd = gridDim.x >> 3;
     t = (u64)(blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
   }
@@ -356,7 +394,14 @@ __global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void 
   const u64 tile_first = t << NTT_LOG_TILE;   // one-level tables are in TILE order: entry t * 2048 + e belongs to element e of tile t
 
   // ---- load (bit-reversed rows), optional pre-multiplication ------------------------------
-  const u32 total = R << a.log_c;
+  const u32 total = PACK ? R * live_cols : R << a.log_c;   // (live columns are a prefix of the tile: col * R + row < total)
+  // store phase (lanes walk columns first): is element e of the tile there?
+  auto live_st = [&](u32 e) { return PACK && packed ? (e & (C - 1)) < live_cols : e < total; };
+  // ... and does it go through the chain of table products?  The chain hands each product the NEXT element's entry, so the
+  // elements it skips must be a suffix of a thread's elements: true for e < total, not for the dead columns of a packed
+  // tile with more than TH columns (a thread's elements alternate between two columns) - there every slot of the (full
+  // sized) tile is multiplied, dead ones on whatever the LDS holds, and only the live ones are stored
+  auto chain_st = [&](u32 e) { return (PACK && packed) || e < total; };
   const u32 lb_mask = (1u << a.lb) - 1;
   // All of a thread's loads are issued before anything else happens: a loop of "load, wait, multiply, store to LDS"
   // exposed the full memory latency once per element (8 times per tile, a third of the kernel's time).
@@ -374,7 +419,7 @@ __global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void 
       gi[i] = base + row * in_row_stride + col * in_col_stride;
       const u32 rrow = a.r ? (__brev(row) >> (32 - a.r)) : 0;
       slot[i] = (col << a.r) + rrow;
-      if (e < total) v[i] = ld_fr(vin + gi[i]);
+      if (e < total) v[i] = ld_fr(vin + (PACK && packed ? (u64)col * mv.in_stride : 0) + gi[i]);
     }
     if (ONE && a.pre1) {   // one product per element; entry of element e = tid + i * 256: lanes read consecutive entries
       MReg w[PER];
@@ -459,13 +504,12 @@ __global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void 
 #pragma unroll
     for (int i = 0; i < PER; i++) {
       const u32 e = tid + (u32)i * TH;
-      const bool live = e < total;
       const u32 row = e >> a.log_c, col = e & (C - 1);   // consecutive lanes -> consecutive columns
-      if (live) v[i] = tile_ld(plane0, plane1, (col << a.r) + row);
+      if (chain_st(e)) v[i] = tile_ld(plane0, plane1, (col << a.r) + row);
       const u64 g = out_base + row * out_row_stride + col * out_col_stride;
-      gi[i] = g;
+      gi[i] = g + (PACK && packed ? (u64)col * mv.out_stride : 0);   // (packed: g = row indexes the tables)
       u32 ex = 0;
-      if (live) ex = !a.is_last ? (u32)((((u64)(jp0 + col) * row) << a.s) & n_mask) : (u32)g;
+      if (chain_st(e)) ex = !a.is_last ? (u32)((((u64)(jp0 + col) * row) << a.s) & n_mask) : (u32)g;
       ph[i] = hi_tab ? hi_tab + (ex >> a.lb) : nullptr;   // no table: plain fft / the 1/n of ifft below
       pl[i] = lo_tab ? lo_tab + (ex & lb_mask) : nullptr;
     }
@@ -473,7 +517,7 @@ __global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void 
       TwReg cur = tw_load(ph[0]);
 #pragma unroll
       for (int i = 0; i < PER; i++) {
-        if (tid + (u32)i * TH < total) {
+        if (chain_st(tid + (u32)i * TH)) {
           mul_tw(v[i], cur, pl[i]);
           mul_tw(v[i], cur, i + 1 < PER ? ph[i + 1] : hi_tab);
         }
@@ -482,14 +526,14 @@ __global__ __launch_bounds__(NttCfg<ONE>::TH, NttCfg<ONE>::WAVES_PER_SIMD) void 
       TwReg cur = tw_load(a.post_const);
 #pragma unroll
       for (int i = 0; i < PER; i++) {
-        if (tid + (u32)i * TH < total) mul_tw(v[i], cur, a.post_const);
+        if (live_st(tid + (u32)i * TH)) mul_tw(v[i], cur, a.post_const);
       }
     }
     }   // two-level tables
 #pragma unroll
     for (int i = 0; i < PER; i++) {
       const u32 e = tid + (u32)i * TH;
-      if (e < total) {
+      if (live_st(e)) {
         if (a.is_last) frl_canon(v[i]);   // what leaves the transform is the canonical field element
         st_fr(vout + gi[i], v[i]);
       }
@@ -593,6 +637,19 @@ __global__ void fr_quotient_kernel(fr_t *a, const fr_t *b, const fr_t *c, fr_t z
     st_fr(a + i, x);
   }
 }
+// the same over k triples a stride apart (bh_h_poly_fr_many_dev_on): element e of vector j at j * stride + e; what lies
+// between two vectors is neither read nor written
+__global__ void fr_quotient_many_kernel(fr_t *a, const fr_t *b, const fr_t *c, fr_t zinv, u64 stride, u64 k, u32 log_n) {
+  const u64 total = k << log_n, mask = ((u64)1 << log_n) - 1;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+    const u64 at = (i >> log_n) * stride + (i & mask);
+    fr_t x = ld_fr(a + at), y = ld_fr(b + at), z = ld_fr(c + at);
+    fe_mul(x, x, y);
+    fe_sub(x, x, z);
+    fe_mul(x, x, zinv);
+    st_fr(a + at, x);
+  }
+}
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -675,35 +732,16 @@ void fft_master_free(Context &c) {
   }
 }
 
-// split log_n into 1-3 passes of <= 11 bits, as evenly as possible (largest first)
-static void plan_passes(uint32_t log_n, uint32_t *r, uint32_t *L) {
-  const uint32_t l = log_n <= (uint32_t)NTT_MAX_R ? 1 : (log_n + NTT_MAX_R - 1) / NTT_MAX_R;
-  *L = l;
-  const uint32_t q = log_n / l, rem = log_n % l;
-  for (uint32_t i = 0; i < l; i++) r[i] = q + (i < rem ? 1 : 0);
-}
-
-// the geometry fields of pass p (what tile_geo and the index arithmetic of ntt_pass_kernel read); s = bits consumed by
-// the passes before it
-static NttPass pass_geometry(uint32_t log_n, const uint32_t *r, uint32_t L, uint32_t p, uint32_t s) {
+// (plan_passes and the geometry of a pass: fft_plan.hpp, shared with the host-only plan hook of the test library)
+static_assert(NTT_PLAN_LOG_TILE == (uint32_t)NTT_LOG_TILE && NTT_PLAN_MAX_R == (uint32_t)NTT_MAX_R, "fft_plan.hpp plans for this tile");
+static NttPass pass_from_geo(const NttGeo &g) {
   NttPass a = NttPass();   // (value-initialised: every pointer null)
-  const bool last = (p == L - 1);
-  a.log_n = log_n;
-  a.s = s;
-  a.r = r[p];
-  a.is_last = last ? 1 : 0;
-  a.r0 = r[0];
-  a.L = L;
-  a.r1 = r[1];
-  // tile columns: as many as fit 2048 elements, bounded by the extent of the column dimension
-  uint32_t log_c = NTT_LOG_TILE - r[p];
-  if (L == 1) log_c = 0;
-  else if (last) { if (log_c > r[0]) log_c = r[0]; }
-  else { uint32_t logM = log_n - s - r[p]; if (log_c > logM) log_c = logM; }
-  a.log_c = log_c;
-  const u64 tiles = ((u64)1 << log_n) >> (r[p] + log_c);
-  a.xcd_swizzle = (tiles >= 64 && (tiles & 7) == 0) ? 1 : 0;
+  a.log_n = g.log_n; a.s = g.s; a.r = g.r; a.log_c = g.log_c; a.is_last = g.is_last;
+  a.r0 = g.r0; a.L = g.L; a.r1 = g.r1; a.xcd_swizzle = g.xcd_swizzle;
   return a;
+}
+static NttPass pass_geometry(uint32_t log_n, const uint32_t *r, uint32_t L, uint32_t p, uint32_t s) {
+  return pass_from_geo(pass_geo(log_n, r, L, p, s));
 }
 
 // internal return code of get_tables: `*evict_need` bytes of OTHER sizes' tables have to go first (fft_evict), then call again
@@ -1038,6 +1076,82 @@ int h_poly_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, fr_t *scratch, uint32_t l
   hipLaunchKernelGGL(fr_quotient_kernel, dim3(ew_blocks(c, n)), dim3(256), 0, st, a, b, cc, zinv, n);
   BH_HIP_CHECK(hipGetLastError());
   return ntt_run(c, a, scratch, log_n, BH_ICOSET_FFT, st);
+}
+
+// ---- k vectors in one call (bh_fft_fr_many_*) -------------------------------------------------------------------
+// data: vector j at data + j * stride (stride >= 2^log_n elements), in place.  scratch: scratch_vectors * 2^log_n elements
+// (multi-pass sizes: >= 1 vector).  The launches are those of fft_many_plan (fft_plan.hpp).
+int ntt_run_many(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int mode, fr_t *scratch, u64 scratch_vectors, hipStream_t st) {
+  if (log_n >= 32) return BH_ERR_DEGREE_TOO_LARGE;
+  if (!k) return BH_OK;
+  if (log_n > (uint32_t)NTT_MAX_R && (!scratch || !scratch_vectors)) return BH_ERR_INVALID_ARG;
+  const bool inverse = (mode == BH_IFFT || mode == BH_ICOSET_FFT);
+  const int dir = inverse ? 1 : 0;
+  FftTables tab;
+  const BTw *master = nullptr;
+  TableUse use;   // the tables stay cached until this call's launches are enqueued
+  int rc = acquire_tables(c, log_n, inverse, log_n > (uint32_t)NTT_MAX_R, mode == BH_COSET_FFT, mode == BH_ICOSET_FFT, st, &tab, &master, use);
+  if (rc) return rc;
+  if (tab.one_level && ((log_n > (uint32_t)NTT_MAX_R && !tab.tw1[dir][0]) || (mode == BH_COSET_FFT && !tab.coset1) ||
+                        (mode == BH_ICOSET_FFT && !tab.icoset1)))
+    return BH_ERR_HIP;   // (as ntt_run_batch: a null table would be a silently wrong transform)
+  for (const FftManyLaunch &l : fft_many_plan(log_n, k, stride, scratch_vectors, tab.one_level)) {
+    NttPass a = pass_from_geo(l.geo);
+    const bool last = l.geo.is_last;
+    a.in = l.in_scratch ? scratch : data + l.first_vec * stride;
+    a.out = l.out_scratch ? scratch : data + l.first_vec * stride;
+    a.master = master;
+    a.tw_lo = tab.tw_lo[dir];
+    a.tw_hi = tab.tw_hi[dir];
+    const bool pre = (l.pass == 0 && mode == BH_COSET_FFT), post = (last && mode == BH_ICOSET_FFT);
+    a.pre_lo = pre ? tab.coset_lo : nullptr;
+    a.pre_hi = pre ? tab.coset_hi : nullptr;
+    a.post_lo = post ? tab.icoset_lo : nullptr;
+    a.post_hi = post ? tab.icoset_hi : nullptr;
+    a.tw1 = (tab.one_level && !last) ? tab.tw1[dir][l.pass] : nullptr;
+    a.pre1 = (tab.one_level && pre) ? tab.coset1 : nullptr;
+    a.post1 = (tab.one_level && post) ? tab.icoset1 : nullptr;
+    a.post_const = (last && mode == BH_IFFT && !tab.one_level) ? tab.minv_dev : nullptr;
+    a.lb = tab.lb;
+    NttPassMany am;
+    static_cast<NttPass &>(am) = a;
+    am.mv.in_stride = l.in_stride; am.mv.out_stride = l.out_stride; am.mv.n_vec = (u32)l.n_vec; am.mv.log_v = l.log_v;
+    if (l.one_level) hipLaunchKernelGGL((ntt_pass_kernel<true, true>), dim3(l.grid), dim3(NttCfg<true>::TH), 0, st, am);
+    else hipLaunchKernelGGL((ntt_pass_kernel<false, true>), dim3(l.grid), dim3(NttCfg<false>::TH), 0, st, am);
+    BH_HIP_CHECK(hipGetLastError());
+  }
+  return BH_OK;
+}
+// h_poly_dev over k strided triples: seven batched transforms and one batched pointwise pass; a_j ends as h_poly_dev leaves it
+int h_poly_many_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, u64 stride, u64 k, uint32_t log_n, fr_t *scratch, u64 scratch_vectors,
+                    hipStream_t st) {
+  if (!k) return BH_OK;
+  int rc;
+  fr_t *v[3] = {a, b, cc};
+  for (int mode : {BH_IFFT, BH_COSET_FFT})
+    for (int i = 0; i < 3; i++)
+      if ((rc = ntt_run_many(c, v[i], stride, k, log_n, mode, scratch, scratch_vectors, st))) return rc;
+  fr_t zinv;
+  if ((rc = cached_zinv(c, log_n, st, &zinv))) return rc;
+  hipLaunchKernelGGL(fr_quotient_many_kernel, dim3(ew_blocks(c, k << log_n)), dim3(256), 0, st, a, b, cc, zinv, stride, k, log_n);
+  BH_HIP_CHECK(hipGetLastError());
+  return ntt_run_many(c, a, stride, k, log_n, BH_ICOSET_FFT, scratch, scratch_vectors, st);
+}
+// k single-vector transforms / h blocks through the existing path (BH_FFT_MANY_SINGLE, and what the dispatch rule of
+// api.hip sends here): scratch is one vector
+int ntt_run_each(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int mode, fr_t *scratch, hipStream_t st) {
+  for (u64 j = 0; j < k; j++) {
+    int rc = ntt_run(c, data + j * stride, scratch, log_n, mode, st);
+    if (rc) return rc;
+  }
+  return BH_OK;
+}
+int h_poly_each_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, u64 stride, u64 k, uint32_t log_n, fr_t *scratch, hipStream_t st) {
+  for (u64 j = 0; j < k; j++) {
+    int rc = h_poly_dev(c, a + j * stride, b + j * stride, cc + j * stride, scratch, log_n, st);
+    if (rc) return rc;
+  }
+  return BH_OK;
 }
 
 }  // namespace bh

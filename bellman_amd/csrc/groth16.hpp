@@ -653,6 +653,10 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *input_assign
 // of eight (not the same ones in two runs) and loses on small circuits (profiles/prove_batch_bench.json), so BATCH_AUTO
 // never takes it: it runs the proofs by the single-proof path,
 // BATCH_IN_FLIGHT at a time, and waits for them in order.  BATCH_GROUPED forces the grouped path (tests, measurements).
+// BATCH_GROUPED_H is the grouped path with a BATCHED h block: a, b and c strided per witness (bh_r1cs_eval_dev into a_j, b_j,
+// c_j), one bh_h_poly_fr_many_dev_on (BH_FFT_MANY_FORCE) per group, then the H many-job.  Its groups hold the largest g with
+// 4 * g * m * 32 bytes <= the budget (a, b, c and an FFT scratch vector per witness), at least one.  Forced only, like
+// BATCH_GROUPED.
 // A witness of the wrong shape throws std::invalid_argument before anything runs.
 struct WitnessView {
   const Fr *inputs; size_t n_inputs;
@@ -660,7 +664,7 @@ struct WitnessView {
 };
 constexpr size_t BATCH_WORKSPACE_BYTES = size_t(1) << 30;   // the default workspace budget of the grouped path: 1 GiB
 constexpr size_t BATCH_IN_FLIGHT = 16;                       // proofs in flight at a time otherwise
-enum { BATCH_AUTO = 0, BATCH_GROUPED = 1 };
+enum { BATCH_AUTO = 0, BATCH_GROUPED = 1, BATCH_GROUPED_H = 2 };
 // throws what the FIRST failing proof would throw (the subversion check and the order of reported errors per proof are
 // create_proof's); workspace_budget = 0: the default
 std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,

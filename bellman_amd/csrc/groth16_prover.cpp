@@ -582,7 +582,7 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   if (tm) *tm = ProveTimings{0, 0, 0, 0};
   if (!k) return;
   const double t0 = now_ms();
-  if (mode != BATCH_GROUPED && !grouped_batch_wins(r1cs.num_constraints, k)) {
+  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && !grouped_batch_wins(r1cs.num_constraints, k)) {
     // k proofs by the single-proof path, BATCH_IN_FLIGHT of them in flight (device memory stays bounded), waited in order
     std::vector<std::unique_ptr<AsyncProof>> jobs(k);
     auto finish = [&](size_t j) {
@@ -619,7 +619,9 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   // and the FFT scratch, which the h blocks of a group share (they run one after the other on one stream)
   const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
   const size_t vec = m * 32;
-  size_t group = budget / vec > 3 ? budget / vec - 3 : 1;
+  // (BATCH_GROUPED_H: every witness has its own a, b, c and scratch vector - its h blocks run as ONE batched h block)
+  const bool batched_h = mode == BATCH_GROUPED_H;
+  size_t group = batched_h ? std::max<size_t>(budget / (4 * vec), 1) : budget / vec > 3 ? budget / vec - 3 : 1;
   if (group > k) group = k;
   if (group > 4096) group = 4096;
   // the blinding terms (five host scalar multiplications per proof) on helper threads, beside the GPU work
@@ -656,7 +658,8 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     const double t1 = now_ms();
     const size_t in_stride = n_in * 32, aux_stride = n_aux * 32;
     DevBuf d_in(ctx, g * in_stride + 32), d_aux(ctx, g * aux_stride + 32);
-    DevBuf da(ctx, g * vec), db(ctx, vec), dc(ctx, vec), dscratch(ctx, log_m > 11 ? vec : 32);
+    const size_t bc_vecs = batched_h ? g : 1, scratch_bytes = log_m > 11 ? bc_vecs * vec : 32;
+    DevBuf da(ctx, g * vec), db(ctx, bc_vecs * vec), dc(ctx, bc_vecs * vec), dscratch(ctx, scratch_bytes);
     ProofStream ps(ctx);
     StreamDrain drain{ps};
     std::vector<bh_msm_job *> in_jobs(3 * g, nullptr);
@@ -684,10 +687,13 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     // ordered after them
     for (size_t j = 0; j < g; j++) {
       void *a_j = (char *)da.p + j * vec;
-      check(bh_r1cs_eval_dev(ctx, r1cs.handle, (char *)d_in.p + j * in_stride, (char *)d_aux.p + j * aux_stride, a_j, db.p, dc.p,
-                             log_m, ps.st));
-      check(bh_h_poly_fr_dev_on(ctx, a_j, db.p, dc.p, dscratch.p, log_m, ps.st));
+      const size_t bc = batched_h ? j * vec : 0;
+      check(bh_r1cs_eval_dev(ctx, r1cs.handle, (char *)d_in.p + j * in_stride, (char *)d_aux.p + j * aux_stride, a_j,
+                             (char *)db.p + bc, (char *)dc.p + bc, log_m, ps.st));
+      if (!batched_h) check(bh_h_poly_fr_dev_on(ctx, a_j, db.p, dc.p, dscratch.p, log_m, ps.st));
     }
+    if (batched_h)
+      check(bh_h_poly_fr_many_dev_on(ctx, da.p, db.p, dc.p, vec, g, log_m, BH_FFT_MANY_FORCE, dscratch.p, scratch_bytes, ps.st));
     check(bh_msm_many_async_dev(ctx, params.h, 0, da.p, vec, m - 1, g, BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &h_job));   // a.len() - 1
     // 4. the `inputs` multiexps as the single call issues them (a handful of terms: answered on the host, at issue time -
     // so they come last, while the GPU works)

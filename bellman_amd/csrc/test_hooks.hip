@@ -9,6 +9,7 @@
 #include "msm_ec.cuh"
 #include "point_read.cuh"
 #include "shard_cuts.hpp"
+#include "fft_plan.hpp"
 
 namespace bh {
 template <class P>
@@ -28,6 +29,22 @@ static int test_fe_mul(void *r, const void *a, const void *b, u64 n, hipStream_t
   return BH_OK;
 }
 }  // namespace bh
+
+// ---- test hook: the launch plan of a batched transform (host only; tests/test_fft_many_model_cpu.py) --------------------
+int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t scratch_vectors, int table_kind, uint64_t *out,
+                          size_t cap) {
+  if (log_n >= 32 || stride_elems < ((size_t)1 << log_n) || (log_n > 11 && !scratch_vectors) || (cap && !out)) return BH_ERR_INVALID_ARG;
+  const bool one = table_kind == 1 && log_n >= 12 && log_n <= 24;
+  const std::vector<bh::FftManyLaunch> plan = bh::fft_many_plan(log_n, k, stride_elems, scratch_vectors, one);
+  for (size_t i = 0; i < plan.size() && i < cap; i++) {
+    const bh::FftManyLaunch &l = plan[i];
+    const uint64_t w[20] = {l.grid, l.threads, l.one_level, l.first_vec, l.n_vec, l.in_scratch, l.out_scratch, l.in_stride, l.out_stride,
+                            l.geo.log_n, l.geo.s, l.geo.r, l.geo.log_c, l.geo.is_last, l.geo.r0, l.geo.L, l.geo.r1, l.geo.xcd_swizzle,
+                            l.log_v, l.pass};
+    memcpy(out + 20 * i, w, sizeof w);
+  }
+  return (int)plan.size();
+}
 
 // ---- test hook: the group law in the multi-lane forms on its own (tests/test_gpu_parity.py::test_g2_k3_group_law,
 // test_g2_lane_pair_group_law) --------------------------------------------------------------------------------

@@ -659,14 +659,16 @@ def prove_witness(r1cs, params, input_assignment, aux_assignment, r, s, timings=
     return Proof(out)
 
 
-def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None):
+def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None, _mode=None, _codes=None):
     """k proofs of ONE circuit in one call (bh_groth16_prove_witness_batch): witness j = (inputs_list[j], aux_list[j]),
     blinding (rs[j], ss[j]) -> [Proof], each exactly what prove_witness returns for that witness.  inputs_list / aux_list:
     lists of integer lists or [n, 4] Montgomery arrays, or one [k, n, 4] uint64 array each (no copy is made then).  A witness of the wrong
     shape is refused for the whole call before anything runs, as the single call refuses it; otherwise the error the
     first failing proof would raise is raised.  (_workspace_budget: the test library's twin of the call, which takes the
     grouped path - many-jobs over groups of witnesses that fit that many bytes of h-block workspace, 0 = the default 1 GiB -
-    instead of keeping the proofs in flight.)"""
+    instead of keeping the proofs in flight.  _mode: the twin that takes the path of groth16.hpp's BATCH_* modes - 1 the
+    grouped path, 2 the grouped path with a batched h block (bh_h_poly_fr_many_dev_on), groups by 4 * g * m * 32 bytes.
+    _codes: a list that receives the per-proof return codes instead of the first failing one being raised.)"""
     lib = _lib.load()
     k = len(inputs_list)
     assert len(aux_list) == k and len(rs) == k and len(ss) == k, "one aux vector and one (r, s) per witness"
@@ -691,7 +693,10 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     rcs = np.zeros(k, dtype=np.int32)
     tm = (ctypes.c_float * 4)()
     p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    if _workspace_budget is None:
+    if _mode is not None:
+        rc = lib.bh_test_groth16_prove_witness_batch_mode(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k,
+                                                          p(rr), p(sv), p(out), p(rcs), _workspace_budget or 0, _mode, tm)
+    elif _workspace_budget is None:
         rc = lib.bh_groth16_prove_witness_batch(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k, p(rr), p(sv),
                                                 p(out), p(rcs), tm)
     else:
@@ -700,6 +705,9 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     check(rc, "create_proof")
     if timings is not None:
         timings[:] = list(tm)
+    if _codes is not None:
+        _codes[:] = [int(c) for c in rcs]
+        return [Proof(out[j].copy()) if rcs[j] == 0 else None for j in range(k)]
     for j in range(k):
         check(int(rcs[j]), "create_proof")
     return [Proof(out[j].copy()) for j in range(k)]

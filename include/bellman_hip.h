@@ -141,6 +141,30 @@ int bh_ctx_trim(bh_ctx *ctx);
 int bh_fft_fr(bh_ctx *ctx, void *data_host, uint32_t log_n, int mode);
 /* same on a device pointer, asynchronous on `stream` (a hipStream_t; NULL = context stream) */
 int bh_fft_fr_dev(bh_ctx *ctx, void *data_dev, uint32_t log_n, int mode, void *stream);
+/* The same transforms over k vectors in one call - `EvaluationDomain::{fft, ifft, coset_fft, icoset_fft}` (src/domain.rs:81-125)
+ * on k domains of one size, as a batch prover's k h blocks issue them (groth16/src/prover.rs:221-240 once per proof).
+ * Vector j lives at data + j * stride_bytes, holds 2^log_n Montgomery Fr and is transformed in place; what lies between two
+ * vectors is neither read nor written.  Up to 2^10 points a workgroup transforms 2^(11 - log_n) vectors at once; above, one
+ * launch per pass covers every (tile, vector).
+ *   flags  BH_FFT_MANY_FORCE   batched launches wherever they are valid (every shape)
+ *          BH_FFT_MANY_SINGLE  k single-vector transforms, exactly what k calls of bh_fft_fr_dev enqueue
+ *          0                   batched where it was measured to win (profiles/fft_many_bench.json), single elsewhere
+ *          The result is the same bytes on all three.
+ *   _dev_on  enqueue only: `scratch_dev` = scratch_bytes of caller-owned workspace (may be NULL up to 2^11; at least one
+ *          vector, 32 << log_n bytes, above), which like the data must stay valid until `stream` has drained.  A scratch of
+ *          S vectors lets S vectors share each launch: k > S runs ceil(k / S) sub-batches one after the other.
+ *   _dev   takes the scratch from the context's pool and waits for the stream before it returns, as bh_fft_fr_dev does.
+ *   bh_fft_fr_many  k contiguous vectors on the HOST (stride = 32 << log_n).
+ * log_n >= 32 -> BH_ERR_DEGREE_TOO_LARGE (:57-59), checked first.  BH_ERR_INVALID_ARG: a null ctx or data pointer, a mode
+ * outside 0..3, a stride below 32 << log_n or not a multiple of 32, unknown flag bits (or both flags), log_n > 11 with the
+ * scratch null or smaller than one vector.  k = 0 is BH_OK and launches nothing. */
+#define BH_FFT_MANY_FORCE 1u
+#define BH_FFT_MANY_SINGLE 2u
+int bh_fft_fr_many_dev_on(bh_ctx *ctx, void *data_dev, size_t stride_bytes, size_t k, uint32_t log_n, int mode, unsigned flags,
+                          void *scratch_dev, size_t scratch_bytes, void *stream);
+int bh_fft_fr_many_dev(bh_ctx *ctx, void *data_dev, size_t stride_bytes, size_t k, uint32_t log_n, int mode, unsigned flags,
+                       void *stream);
+int bh_fft_fr_many(bh_ctx *ctx, void *data_host, size_t k, uint32_t log_n, int mode);
 /* pointwise domain ops on device vectors of n Montgomery Fr:
  *   mul_assign (:154-170)  sub_assign (:173-189)  divide_by_z_on_coset (:139-151, n = 2^log_n)
  *   distribute_powers(g) (:101-113; g = 32-byte Montgomery Fr on the HOST) */
@@ -172,6 +196,12 @@ int bh_h_poly_fr_dev(bh_ctx *ctx, void *a_dev, void *b_dev, void *c_dev, uint32_
  * up to 2^11), which like a, b, c must stay valid until `stream` has drained */
 int bh_h_poly_fr_dev_on(bh_ctx *ctx, void *a_dev, void *b_dev, void *c_dev, void *scratch_dev, uint32_t log_n,
                         void *stream);
+/* k h blocks in one call (groth16/src/prover.rs:221-240 for each of k proofs of one circuit): a_j, b_j, c_j at
+ * base + j * stride_bytes.  For every j, a_j ends exactly as bh_h_poly_fr_dev_on leaves it (all 2^log_n words; the first
+ * m - 1 are the h coefficients, :238-239); b_j and c_j are clobbered.  Seven batched transforms and one batched
+ * (a*b-c)/Z pass (src/domain.rs:139-189).  Flags, scratch and return codes as bh_fft_fr_many_dev_on (a, b, c non-null). */
+int bh_h_poly_fr_many_dev_on(bh_ctx *ctx, void *a_dev, void *b_dev, void *c_dev, size_t stride_bytes, size_t k, uint32_t log_n,
+                             unsigned flags, void *scratch_dev, size_t scratch_bytes, void *stream);
 
 /* ---- bases: the `(Arc<Vec<G::Affine>>, usize)` SourceBuilder (src/multiexp.rs:45-86) --
  * Uploads `n` affine points once (the CRS is immutable and shared by every proof,

@@ -442,6 +442,22 @@ int bh_test_many_stage_dev(bh_ctx *ctx, int table, unsigned c, const void *scala
 int bh_test_groth16_prove_witness_batch_budget(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
                                                const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
                                                void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4);
+/* the same with the path of the caller's choice: mode 0 what the product call does, 1 the grouped path above, 2 the grouped
+ * path with a BATCHED h block (groth16.hpp BATCH_GROUPED_H: a, b, c strided per witness, one bh_h_poly_fr_many_dev_on per
+ * group; groups of the largest g with 4 * g * m * 32 <= workspace_budget, at least one) */
+int bh_test_groth16_prove_witness_batch_mode(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                             const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                             void *proofs_out, int32_t *rcs, size_t workspace_budget, int mode, float *timings4);
+/* host only, no GPU: the launches bh_fft_fr_many_dev_on issues with BH_FFT_MANY_FORCE for k vectors of 2^log_n,
+ * stride_elems apart, a scratch of scratch_vectors vectors and tables of table_kind (0 two-level, 1 one-level; sizes outside
+ * 2^12 .. 2^24 have no one-level tables and plan as 0).  Returns the number of launches (BH_ERR_INVALID_ARG < 0 for a shape
+ * the call refuses) and writes the first `cap` of them to out, 20 words each:
+ *   [0] grid  [1] threads  [2] one-level kernel  [3] first vector  [4] vectors  [5] reads the scratch  [6] writes the scratch
+ *   [7] in stride  [8] out stride (elements; the scratch holds vector [3] + j at j << log_n)
+ *   [9] log_n  [10] s  [11] r  [12] log_c  [13] is_last  [14] r0  [15] L  [16] r1  [17] xcd_swizzle   (the pass geometry)
+ *   [18] log_v (single-pass sizes: 2^log_v vectors per tile, one per column)  [19] pass */
+int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t scratch_vectors, int table_kind, uint64_t *out,
+                          size_t cap);
 
 #ifdef __cplusplus
 }

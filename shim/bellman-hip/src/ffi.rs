@@ -187,6 +187,9 @@ extern "C" {
     pub fn bh_ctx_trim(ctx: *mut BhCtx) -> c_int;
     pub fn bh_fft_fr(ctx: *mut BhCtx, data_host: *mut c_void, log_n: u32, mode: c_int) -> c_int;
     pub fn bh_fft_fr_dev(ctx: *mut BhCtx, data_dev: *mut c_void, log_n: u32, mode: c_int, stream: *mut c_void) -> c_int;
+    pub fn bh_fft_fr_many_dev_on(ctx: *mut BhCtx, data_dev: *mut c_void, stride_bytes: usize, k: usize, log_n: u32, mode: c_int, flags: c_uint, scratch_dev: *mut c_void, scratch_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn bh_fft_fr_many_dev(ctx: *mut BhCtx, data_dev: *mut c_void, stride_bytes: usize, k: usize, log_n: u32, mode: c_int, flags: c_uint, stream: *mut c_void) -> c_int;
+    pub fn bh_fft_fr_many(ctx: *mut BhCtx, data_host: *mut c_void, k: usize, log_n: u32, mode: c_int) -> c_int;
     pub fn bh_fr_mul_assign_dev(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn bh_fr_sub_assign_dev(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn bh_fr_divide_by_z_on_coset_dev(ctx: *mut BhCtx, a_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
@@ -199,6 +202,7 @@ extern "C" {
     pub fn bh_h_poly_fr(ctx: *mut BhCtx, a_host: *const c_void, b_host: *const c_void, c_host: *const c_void, n_evals: usize, h_out_host: *mut c_void, h_len: *mut usize) -> c_int;
     pub fn bh_h_poly_fr_dev(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
     pub fn bh_h_poly_fr_dev_on(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, scratch_dev: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
+    pub fn bh_h_poly_fr_many_dev_on(ctx: *mut BhCtx, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, stride_bytes: usize, k: usize, log_n: u32, flags: c_uint, scratch_dev: *mut c_void, scratch_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn bh_bases_register(ctx: *mut BhCtx, group: c_int, host_points: *const c_void, n: usize, stride: usize, inf_offset: c_long, out: *mut *mut BhBases) -> c_int;
     pub fn bh_bases_register_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, out: *mut *mut BhBases) -> c_int;
     pub fn bh_bases_read_uncompressed(ctx: *mut BhCtx, group: c_int, host_bytes: *const c_void, n: usize, flags: c_uint, out: *mut *mut BhBases, bad_index: *mut usize) -> c_int;

@@ -10,6 +10,9 @@ baseline's by more than that baseline's own max - min spread.  The h blocks of t
 the issue of its last many-job - uploads, the k serial h blocks being enqueued, the issue of the jobs (the call's own
 timings; the in-flight path has no such figure: its proofs overlap).  `grouped_wins`: the grouped path
 beats the better baseline by more than that spread - the condition under which the call would take it.
+`grouped_h`: the grouped path with a BATCHED h block (groth16.hpp BATCH_GROUPED_H: one bh_h_poly_fr_many_dev_on per group);
+`grouped_h_share_batched` is the same share of its wall time, `grouped_h_wins` / `grouped_h_speedup_vs_best` as for the
+grouped path.
 
 Usage: python tools/bench_prove_batch.py [--out profiles/prove_batch_bench.json] [--reps 5] [--max-log 18]"""
 import argparse
@@ -110,7 +113,12 @@ def main():
             def grouped():
                 return pg.prove_witness_batch(r1cs, params, ins_k, auxs_k, rs[:k], ss[:k], tm_g, _workspace_budget=0)
 
-            variants = (("sequential", sequential), ("async", in_flight), ("batch", batch), ("grouped", grouped))
+            tm_h = [0, 0, 0, 0]
+
+            def grouped_h():
+                return pg.prove_witness_batch(r1cs, params, ins_k, auxs_k, rs[:k], ss[:k], tm_h, _workspace_budget=0, _mode=2)
+
+            variants = (("sequential", sequential), ("async", in_flight), ("batch", batch), ("grouped", grouped), ("grouped_h", grouped_h))
             times = {v: [] for v, _ in variants}
             res = {}
             for rep in range(args.reps + 1):
@@ -120,7 +128,7 @@ def main():
                     if rep:
                         times[v].append((time.perf_counter() - t0) * 1e3)
             for j in range(k):
-                for v in ("async", "batch", "grouped"):
+                for v in ("async", "batch", "grouped", "grouped_h"):
                     assert all(np.array_equal(getattr(res[v][j], f), getattr(res["sequential"][j], f)) for f in "abc"), (name, k, v, j)
             best = min(("sequential", "async"), key=lambda v: min(times[v]))
             spread = max(times[best]) - min(times[best])
@@ -132,7 +140,11 @@ def main():
                    "batch_speedup_vs_best": round(min(times[best]) / min(times["batch"]), 3),
                    "grouped_wins": bool(min(times["grouped"]) < min(times[best]) - spread),
                    "grouped_speedup_vs_best": round(min(times[best]) / min(times["grouped"]), 3),
-                   "grouped_h_share": round(tm_g[1] / tm_g[3], 3) if tm_g[3] else None}
+                   "grouped_h_share": round(tm_g[1] / tm_g[3], 3) if tm_g[3] else None,
+                   "grouped_h_wins": bool(min(times["grouped_h"]) < min(times[best]) - spread),
+                   "grouped_h_speedup_vs_best": round(min(times[best]) / min(times["grouped_h"]), 3),
+                   "grouped_h_vs_grouped": round(min(times["grouped"]) / min(times["grouped_h"]), 3),
+                   "grouped_h_share_batched": round(tm_h[1] / tm_h[3], 3) if tm_h[3] else None}
             rows.append(row)
             print(json.dumps(row), flush=True)
         params.release()
