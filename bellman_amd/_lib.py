@@ -61,7 +61,7 @@ TEST_EXPORTS = [
     "bh_test_pairing", "bh_test_pairing_host", "bh_test_fp_sqrt_host", "bh_test_fp2_sqrt_host",
     "bh_test_field_ops_shape", "bh_test_field_ops_dev", "bh_test_field_ops_host",
     "bh_test_group_ops_shape", "bh_test_group_ops_dev", "bh_test_group_ops_host", "bh_test_sum_jobs_dev", "bh_test_g1_madd_sliced_dev", "bh_test_g1_madd_sliced_host",
-    "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev",
+    "bh_test_bucket_stage_shape", "bh_test_merge_plan", "bh_test_bucket_stage_dev", "bh_test_msm_sources", "bh_test_window_table_dev",
     "bh_test_reduce_plan", "bh_test_reduce_stage_dev", "bh_test_msm_host_tail",
     "bh_test_sort_plan", "bh_test_scan_dev", "bh_test_sort_stage_dev",
     "bh_test_pairing_stage_shape", "bh_test_proof_status_error", "bh_test_pairing_lines_dev", "bh_test_pairing_miller_dev", "bh_test_pairing_fold_dev",

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <thread>
@@ -39,8 +40,8 @@ int point_mul_powers(Context &c, int group, const void *in, void *out, u64 n, co
 struct MsmJobImpl;
 MsmJobImpl *msm_job_new(Context *ctx, int group);
 void msm_job_delete(MsmJobImpl *j);
-int msm_job_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,
-                    int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table);
+int msm_job_enqueue(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                    const u64 *density_dev, const MsmOpts &opts);
 int msm_job_finish(MsmJobImpl &job, void *out_affine, float *ms, u64 *stats8 = nullptr);
 int msm_job_finish_many(MsmJobImpl &job, void *out_affine_k, size_t k, float *ms, u64 *stats8, bool *fallback);
 int msm_debug_stages(Context &c, const void *scalars_host, u64 n, int fmt, unsigned cbits, u64 *pairs_out, u32 *zstart_out);
@@ -173,20 +174,42 @@ struct bh_bases {
   bh_ctx *ctx = nullptr;
   // [r4] G1 vectors that run the classic plan (>= 2^17 points, owned by the handle): a second copy of the records at a
   // 128-byte stride, which is what the bucket accumulation gathers from - every gather is exactly one cache line (a
-  // 96-byte record at a 96-byte stride straddles two lines half of the time).  profiles/archive/r4_call11_padded_bases.txt:
+  // 96-byte record at a 96-byte stride straddles two lines half of the time).  profiles/archive/r4_call11_*.txt:
   // FETCH_SIZE of the accumulate launch 2.20 -> 1.58 GB at 2^20; accumulate -1 % at 2^20 (the table sits in the
   // Infinity Cache either way), -3 % at 2^22 (it does not).  Dense `dev` stays what every other path and the API see.
   // Vectors whose copy would exceed 1/16 of the device memory are not padded.
   void *padded = nullptr;
   // [r4] ... and the window table of a G1 vector too large for the Infinity Cache (>= 2^19 points: 16 rows of 2^19
-  // records are 0.8 GB) is KEPT at that stride only: `table` then holds W * n records of 128 bytes, read by the bucket
-  // accumulation alone (MsmOpts::padded_table); everything else of such a job reads the dense `dev`.
-  bool table_padded = false;
+  // records are 0.8 GB) is built and kept at that stride only (table_will_pad): `table` then holds W * n records 128 bytes
+  // apart.  What a job reads from which of these three, and at what stride: msm_pick_sources (msm_types.hpp).
+  u32 table_stride = 0;   // bytes between the records of `table`
 };
 namespace bh {
 int bases_group(const ::bh_bases *b) { return b->group; }   // for the units that see the handle only as an opaque type
 }
-static inline size_t table_rec_bytes(const bh_bases *b) { return b->group == BH_G1 ? (b->table_padded ? 128 : 96) : 192; }
+static inline u32 dense_rec_bytes(int group) { return group == BH_G1 ? 96u : 192u; }
+static inline size_t table_bytes(const bh_bases *b) { return b->table ? (size_t)b->tab.W * b->n * b->table_stride : 0; }
+// ONE snapshot of a handle's sources for a job, under job_mu (the caller has reserved its job slot: bh_ctx_trim leaves
+// tables alone while a call is issuing): the pointers and the strides they are read at come from the same moment - a
+// trim + bh_bases_precompute between two reads of the handle could pair a freed table with the other stride
+static MsmBases bases_snapshot(bh_ctx *ctx, const bh_bases *b) {
+  std::lock_guard<std::mutex> g(ctx->c.job_mu);
+  MsmBases s;
+  s.dense = {b->dev, dense_rec_bytes(b->group)};
+  if (b->padded) s.padded = {b->padded, 128u};
+  if (b->table) s.table = {b->table, b->table_stride};
+  s.tab = b->tab;
+  s.n = b->n;
+  return s;
+}
+// forgets the handle's automatic table in the context's books (caller holds job_mu; the table itself is the caller's to free)
+static void forget_auto_table(bh_bases *b) {
+  Context &c = b->ctx->c;
+  c.tables.erase(std::remove(c.tables.begin(), c.tables.end(), b), c.tables.end());
+  const size_t bytes = table_bytes(b);
+  c.table_bytes = c.table_bytes > bytes ? c.table_bytes - bytes : 0;
+  b->auto_table = false;
+}
 // a scalar vector resident in HBM (bh_scalars_*): create_proof hands the same assignment to up to four multiexps
 struct bh_scalars {
   bh_ctx *ctx;
@@ -222,7 +245,7 @@ static int finish_bases(bh_ctx *ctx, bh_bases *b) {
   }
   return BH_OK;
 }
-// Base vectors of up to 2^18 (G1) / 2^22 (G2) points get their window table at registration (BELLMAN_HIP_TABLE_MAX_LOG2
+// Base vectors of up to 2^24 (G1) / 2^22 (G2) points get their window table at registration (BELLMAN_HIP_TABLE_MAX_LOG2
 // overrides both limits, BELLMAN_HIP_TABLE_MAX_LOG2_G1 the G1 limit alone; 0 = never): a multiexp over a few thousand
 // terms is a chain of latency-bound steps, and with the table the chain loses the 255-step doubling ladder over the
 // windows and all but one of its bucket reductions (the CRS is registered once per circuit).
@@ -244,14 +267,10 @@ static unsigned auto_table_max_log2(int group) {
   // budget (a quarter of the memory by default): two of the 28 GB tables of 2^24-point queries fit, the next query stays classic
   return v >= 0 ? (unsigned)v : (group == BH_G1 ? 24u : 22u);
 }
-// G1 tables of 2^19 points and more are stored at a 128-byte record stride (bh_bases::table_padded);
+// G1 tables of 2^19 points and more are built at a 128-byte record stride (bh_bases::table_stride);
 // BELLMAN_HIP_TABLE_PAD=0 keeps them dense
 static bool table_will_pad(const bh_bases *b) {
   return env().table_pad && b->group == BH_G1 && b->n >= ((size_t)1 << 19);
-}
-static size_t table_bytes_for(const bh_bases *b, unsigned c) {
-  const u32 W = (256 + c - 1) / c;
-  return (size_t)W * b->n * (b->group == BH_G1 ? (table_will_pad(b) ? 128 : 96) : 192);
 }
 static int new_bases(bh_ctx *ctx, int group, void *dev, size_t n, bool owned, bh_bases **out) {
   bh_bases *b = new bh_bases{group, dev, n, owned};
@@ -273,7 +292,10 @@ static int new_bases(bh_ctx *ctx, int group, void *dev, size_t n, bool owned, bh
   const unsigned lg_table = auto_table_max_log2(group);
   const bool table_size = lg_table && n > TINY_MSM_MAX && n <= (size_t(1) << lg_table);   // (takes a window table instead)
   if (table_size) {
-    const size_t need = table_bytes_for(b, table_window_bits(n, group == BH_G2));
+    // what the table takes at the stride it is built at - also the peak while it is built: bh_bases_precompute makes this
+    // one allocation and nothing else
+    const u32 c = table_window_bits(n, group == BH_G2);
+    const size_t need = (size_t)((256 + c - 1) / c) * n * (table_will_pad(b) ? 128u : dense_rec_bytes(group));
     bool fits;
     {
       std::lock_guard<std::mutex> g(ctx->c.job_mu);
@@ -285,7 +307,7 @@ static int new_bases(bh_ctx *ctx, int group, void *dev, size_t n, bool owned, bh
         b->auto_table = true;
         std::lock_guard<std::mutex> g(ctx->c.job_mu);
         ctx->c.tables.push_back(b);
-        const size_t actual = (size_t)b->tab.W * b->n * table_rec_bytes(b);   // (dense after all, if the padded copy did not fit)
+        const size_t actual = table_bytes(b);   // (dense after all, if the table did not fit at the 128-byte stride)
         if (actual < need) ctx->c.table_bytes -= need - actual;
       } else {
         std::lock_guard<std::mutex> g(ctx->c.job_mu);
@@ -412,16 +434,14 @@ int bh_ctx_trim(bh_ctx *ctx) {
     // and not yet started has captured its table pointer but enqueued nothing the device synchronise above could have
     // waited for, so the tables stay until a trim finds the context idle
     std::lock_guard<std::mutex> g(ctx->c.job_mu);
-    if (ctx->c.inflight.empty() && ctx->c.issuing == 0)
-    for (bh_bases *b : ctx->c.tables) {
-      if (b->table) (void)hipFree(b->table);
-      b->table = nullptr;
-      b->table_padded = false;
-      b->auto_table = false;
-    }
     if (ctx->c.inflight.empty() && ctx->c.issuing == 0) {
-      ctx->c.tables.clear();
-      ctx->c.table_bytes = 0;
+      while (!ctx->c.tables.empty()) {
+        bh_bases *b = ctx->c.tables.back();
+        forget_auto_table(b);
+        if (b->table) (void)hipFree(b->table);
+        b->table = nullptr;
+      }
+      ctx->c.table_bytes = 0;   // (as before: the count also covers the tables of prepared verifying keys, pairing.hip)
     }
   }
   {
@@ -1131,55 +1151,34 @@ int bh_bases_wrap_dev(bh_ctx *ctx, int group, const void *dev_points, size_t n, 
 }
 int bh_bases_precompute(bh_ctx *ctx, bh_bases *b, unsigned window_bits) {
   if (!ctx || !b) return BH_ERR_INVALID_ARG;
-  if (b->auto_table) {   // replaced by an explicit table: no longer the context's to drop or to count
-    std::lock_guard<std::mutex> g(ctx->c.job_mu);
-    auto &v = ctx->c.tables;
-    for (size_t i = 0; i < v.size(); i++)
-      if (v[i] == b) { v.erase(v.begin() + i); break; }
-    const size_t bytes = (size_t)b->tab.W * b->n * table_rec_bytes(b);
-    ctx->c.table_bytes = ctx->c.table_bytes > bytes ? ctx->c.table_bytes - bytes : 0;
-    b->auto_table = false;
+  if (b->auto_table && b->ctx) {   // replaced by an explicit table: no longer the context's to drop or to count
+    std::lock_guard<std::mutex> g(b->ctx->c.job_mu);
+    forget_auto_table(b);
   }
-  if (b->table) { (void)hipFree(b->table); b->table = nullptr; b->table_padded = false; }
+  if (b->table) { (void)hipFree(b->table); b->table = nullptr; }
   if (b->n == 0) return BH_OK;
   const u32 c = window_bits ? window_bits : table_window_bits(b->n, b->group == BH_G2);
   if (c < 2 || c > 24) return BH_ERR_INVALID_ARG;
   const u32 W = (256 + c - 1) / c;
-  const size_t rec = b->group == BH_G1 ? 96 : 192;
+  const u32 rec = dense_rec_bytes(b->group);
   if ((u64)W * b->n >= ((u64)1 << 31)) return BH_ERR_INVALID_ARG;   // table rows must fit the 31-bit base field
   BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  // ONE allocation, at the stride the table keeps (128 bytes: one cache line per gathered record), and the kernel writes
+  // every row where it stays.  If that size cannot be had the table is built dense - it is the same table
+  u32 stride = table_will_pad(b) ? 128u : rec;
   void *t = nullptr;
-  if (hipMalloc(&t, (size_t)W * b->n * rec) != hipSuccess) {
+  while (hipMalloc(&t, (size_t)W * b->n * stride) != hipSuccess) {
     (void)hipGetLastError();
-    return BH_ERR_HIP;   // not enough HBM for the table: the caller keeps using the plain bases
+    t = nullptr;
+    if (stride == rec) return BH_ERR_HIP;   // not enough HBM for the table: the caller keeps using the plain bases
+    stride = rec;
   }
   hipStream_t st = ctx->c.stream;
-  int rc = BH_OK;
-  if (hipMemcpyAsync(t, b->dev, b->n * rec, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = BH_ERR_HIP;
-  if (rc == BH_OK) rc = window_table(b->group, t, b->n, c, W, st);
+  int rc = window_table(b->group, BaseView{b->dev, rec}, t, stride, b->n, c, W, st);
   if (rc == BH_OK && hipStreamSynchronize(st) != hipSuccess) rc = BH_ERR_HIP;
   if (rc != BH_OK) { (void)hipFree(t); return rc; }
-  bool padded = false;
-  if (table_will_pad(b)) {
-    // re-laid at a 128-byte stride (one cache line per gathered record); the dense build buffer is dropped.  If the
-    // second allocation fails the dense table is kept - it is the same table
-    void *tp = nullptr;
-    if (hipMalloc(&tp, (size_t)W * b->n * 128) == hipSuccess) {
-      if (hipMemcpy2DAsync(tp, 128, t, rec, rec, (size_t)W * b->n, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-          hipStreamSynchronize(st) == hipSuccess) {
-        (void)hipFree(t);
-        t = tp;
-        padded = true;
-      } else {
-        (void)hipGetLastError();
-        (void)hipFree(tp);
-      }
-    } else {
-      (void)hipGetLastError();
-    }
-  }
   b->table = t;
-  b->table_padded = padded;
+  b->table_stride = stride;
   b->tab = WindowTable{c, W, (u64)b->n};
   return BH_OK;
 }
@@ -1187,7 +1186,7 @@ int bh_bases_table_info(const bh_bases *b, unsigned *window_bits, unsigned *rows
   if (!b) return BH_ERR_INVALID_ARG;
   if (window_bits) *window_bits = b->table ? b->tab.c : 0;
   if (rows) *rows = b->table ? b->tab.W : 0;
-  if (bytes) *bytes = b->table ? (size_t)b->tab.W * b->n * table_rec_bytes(b) : 0;
+  if (bytes) *bytes = table_bytes(b);
   return BH_OK;
 }
 void bh_bases_release(bh_ctx *ctx, bh_bases *b) {
@@ -1195,11 +1194,7 @@ void bh_bases_release(bh_ctx *ctx, bh_bases *b) {
   if (!b) return;
   if (b->auto_table && b->ctx) {
     std::lock_guard<std::mutex> g(b->ctx->c.job_mu);
-    auto &v = b->ctx->c.tables;
-    for (size_t i = 0; i < v.size(); i++)
-      if (v[i] == b) { v.erase(v.begin() + i); break; }
-    const size_t bytes = (size_t)b->tab.W * b->n * table_rec_bytes(b);
-    b->ctx->c.table_bytes = b->ctx->c.table_bytes > bytes ? b->ctx->c.table_bytes - bytes : 0;
+    forget_auto_table(b);
   }
   if (b->table) (void)hipFree(b->table);
   if (b->padded) (void)hipFree(b->padded);
@@ -1290,20 +1285,7 @@ static int msm_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const voi
   // back-pressure (src/multicore.rs:47-73): at the cap the issuing thread completes the oldest job itself
   while (!msm_slot_try_reserve(ctx->c))
     if (!msm_complete_oldest(ctx->c)) std::this_thread::yield();   // the slots are held by calls still issuing
-  // ONE snapshot of the handle's table state, taken after the slot is reserved (bh_ctx_trim leaves tables alone while a
-  // call is issuing) and under job_mu: both the pointer the job gathers from and the stride it is read at come from it
-  // (a trim + bh_bases_precompute between two reads of the handle could pair a freed table with the other stride)
-  void *tab_ptr;
-  bool ptab;
-  WindowTable tab_info;
-  {
-    std::lock_guard<std::mutex> g(ctx->c.job_mu);
-    tab_ptr = bases->table;
-    ptab = tab_ptr && bases->table_padded;
-    tab_info = bases->tab;
-    opts.padded_bases = bases->padded;   // (read by the classic plan only)
-  }
-  opts.padded_table = ptab ? tab_ptr : nullptr;
+  const MsmBases src = bases_snapshot(ctx, bases);   // (after the slot is reserved)
   MsmJobImpl *impl = msm_job_new(&ctx->c, bases->group);
   if (!impl) { msm_slot_release(ctx->c); return BH_ERR_HIP; }
   if (n && n <= TINY_MSM_MAX && scalars_on_host && (!density || density_on_host) && !(opts.flags & BH_MSM_NO_SMALL_PATH) &&
@@ -1341,9 +1323,7 @@ static int msm_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const voi
       dn_dev = (const u64 *)p;
     }
   }
-  if (rc == BH_OK)
-    rc = msm_job_enqueue(*impl, (tab_ptr && !ptab) ? tab_ptr : bases->dev, bases->n, skip, sc_dev, n, fmt, dn_dev,
-                         opts, tab_ptr ? &tab_info : nullptr);
+  if (rc == BH_OK) rc = msm_job_enqueue(*impl, src, skip, sc_dev, n, fmt, dn_dev, opts);
   if (rc != BH_OK) {
     float ms[4];
     unsigned char dummy[192];
@@ -1460,12 +1440,10 @@ static int many_common(bh_ctx *ctx, const bh_bases *bases, size_t skip, const vo
   }
   bool use_many = k > 1 && n > 0;
   if (use_many && !force) {
-    bool table;
-    {
-      std::lock_guard<std::mutex> g(ctx->c.job_mu);
-      table = bases->table != nullptr && (mj->o.window_bits == 0 || mj->o.window_bits == bases->tab.c);   // (msm_enqueue's use_table)
-    }
-    use_many = many_plan_wins(bases->group, n, k, table && !(mj->o.flags & BH_MSM_NO_TABLE));
+    MsmOpts mo;
+    mo.c = mj->o.window_bits; mo.flags = mj->o.flags;
+    // (the plan the job would run; the accumulate form, chosen in msm_enqueue, has no part in that)
+    use_many = many_plan_wins(bases->group, n, k, msm_pick_sources(bases_snapshot(ctx, bases), mo, n, bases->group, ACC_MULTI_LANE).use_table);
   }
   int rc;
   if (use_many) {

@@ -11,7 +11,7 @@ struct EnvSettings {
   static constexpr size_t UNSET = (size_t)-1;   // (a byte count parsed from megabytes has its low 20 bits clear)
   int table_max_log2 = -1;        // BELLMAN_HIP_TABLE_MAX_LOG2: largest vector that gets an automatic window table, both groups
   int table_max_log2_g1 = -1;     // BELLMAN_HIP_TABLE_MAX_LOG2_G1: the G1 limit alone (both: clamped to 0 ... 24, 0 = never, -1 = unset)
-  bool table_pad = true;          // BELLMAN_HIP_TABLE_PAD=0: G1 tables of 2^19 points and more stay dense (tools/table_pad_check.py)
+  bool table_pad = true;          // BELLMAN_HIP_TABLE_PAD=0: G1 tables of 2^19 points and more stay dense (tests/test_gpu_round4.py test_g1_window_table_at_128_byte_stride)
   bool fft_one_level = true;      // BELLMAN_HIP_FFT_ONE_LEVEL=0: hi x lo twiddle tables at every size (tests)
   long max_jobs = 0;              // BELLMAN_HIP_MAX_JOBS: jobs in flight per context (<= 0: from the device's memory)
   size_t table_budget = UNSET;    // BELLMAN_HIP_TABLE_BUDGET_MB, in bytes

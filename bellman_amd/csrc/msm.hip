@@ -85,15 +85,14 @@ void msm_job_set_result(MsmJobImpl &job, int rc, const void *affine_record) {
   if (affine_record) memcpy(job.result, affine_record, job.group == BH_G1 ? 96 : 192);
 }
 void msm_job_own(MsmJobImpl &job, void *dev_ptr) { job.dev_allocs.push_back(dev_ptr); }
-int msm_job_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,
-                    int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table) {
+int msm_job_enqueue(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                    const u64 *density_dev, const MsmOpts &opts) {
   if (n == 0) { job.trivial = true; job.early_rc = BH_OK; return BH_OK; }
-  return job.group == BH_G1
-             ? msm_enqueue_g1(job, bases_dev, n_bases, skip, scalars_dev, n, fmt, density_dev, opts, table)
-             : msm_enqueue_g2(job, bases_dev, n_bases, skip, scalars_dev, n, fmt, density_dev, opts, table);
+  return job.group == BH_G1 ? msm_enqueue_g1(job, bases, skip, scalars_dev, n, fmt, density_dev, opts)
+                            : msm_enqueue_g2(job, bases, skip, scalars_dev, n, fmt, density_dev, opts);
 }
-int window_table(int group, void *table_dev, u64 n, u32 c, u32 W, hipStream_t st) {
-  return group == BH_G1 ? window_table_g1(table_dev, n, c, W, st) : window_table_g2(table_dev, n, c, W, st);
+int window_table(int group, BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st) {
+  return group == BH_G1 ? window_table_g1(src, dst, dst_stride, n, c, W, st) : window_table_g2(src, dst, dst_stride, n, c, W, st);
 }
 // runs the group's finish (stream synchronise, error resolution, host tail) once; caller holds job.mu
 static void msm_job_complete_locked(MsmJobImpl &job) {
@@ -130,7 +129,7 @@ static void msm_job_untrack(MsmJobImpl &job) {
 int msm_job_start(MsmJobImpl &job) {
   std::lock_guard<std::mutex> g(job.mu);
   if (job.done || !job.resume) return BH_OK;
-  const int rc = job.resume();
+  const int rc = job.resume(job);
   job.resume = nullptr;
   return rc;
 }

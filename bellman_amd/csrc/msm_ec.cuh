@@ -1044,27 +1044,32 @@ __global__ void __launch_bounds__(64) point_check_kernel(const Affine<F> *pts, u
 }
 // Window table of a registered base vector: row j holds 2^(c*j) P_i in affine form, so that digit j of
 // a scalar can go to the same bucket set as digit 0 (one bucket reduction instead of W, no Horner
-// over windows).  One lane per base walks the rows: c doublings and one inversion per row.
+// over windows).  One lane per base walks the rows: c doublings and one inversion per row.  Lane i reads record i of `src`
+// (src_stride bytes apart) and writes row j at dst + (j n + i) dst_stride: the table is built where and as it stays - at a
+// 128-byte stride for the big G1 tables (api.hip table_will_pad) - and the bytes between two records are never written.
 template <class F>
-__global__ void __launch_bounds__(128) window_table_kernel(Affine<F> *table, u64 n, u32 c, u32 W) {
+__global__ void __launch_bounds__(128) window_table_kernel(const char *src, u32 src_stride, char *dst, u32 dst_stride, u64 n,
+                                                           u32 c, u32 W) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  Affine<F> p = table[i];
-  for (u32 j = 1; j < W; j++) {
-    if (!aff_is_identity(p)) {
+  Affine<F> p = *reinterpret_cast<const Affine<F> *>(src + i * src_stride);
+  for (u32 j = 0; j < W; j++) {
+    if (j && !aff_is_identity(p)) {
       XYZZ<F> acc, t;
       xyzz_dbl_affine(acc, p);
       for (u32 k = 1; k < c; k++) { xyzz_dbl(t, acc); acc = t; }
       xyzz_to_affine(p, acc);
     }
-    table[(u64)j * n + i] = p;
+    *reinterpret_cast<Affine<F> *>(dst + ((u64)j * n + i) * dst_stride) = p;
   }
 }
 template <class F>
-static int window_table_t(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st) {
+static int window_table_t(BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st) {
   const u32 blocks = (u32)((n + 127) / 128);
   if (!blocks) return BH_OK;
-  hipLaunchKernelGGL(window_table_kernel<F>, dim3(blocks), dim3(128), 0, st, (Affine<F> *)table_dev, n, c, W);
+  if (src.stride < sizeof(Affine<F>) || dst_stride < sizeof(Affine<F>) || src.stride % 16 || dst_stride % 16) return BH_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(window_table_kernel<F>, dim3(blocks), dim3(128), 0, st, (const char *)src.ptr, src.stride, (char *)dst,
+                     dst_stride, n, c, W);
   BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
@@ -1413,28 +1418,91 @@ static int launch_reduce(hipStream_t st, const MsmPlan &p, const ReducePlan &rp,
 // bundle of the merge and reduction kernels; records in memory are Affine / XYZZ over F::Mem == FR::Mem, so the two
 // can differ: a big G2 job accumulates one lane per point (throughput) and reduces a window table's 2^15 buckets in
 // lane triples (latency).
+// Everything the stages after the sort read.  msm_enqueue fills it in, and a job issued with BH_MSM_HOLD keeps a copy of it
+// (MsmJobImpl::resume) until it is started: plain values and raw device pointers.  The pointers all lie in the job's
+// workspace block (job.dev_allocs, returned to the pool when the job is waited for) - except `gather`, which points into the
+// base handle's memory: the registered vector, its 128-byte-stride copy or its window table.  The caller keeps the handle
+// until the wait, and bh_ctx_trim leaves automatic tables alone while a job is in flight (api.hip).
+template <class M>
+struct AfterSort {
+  MsmPlan p;
+  MergePlan mp;
+  ReducePlan rp;
+  BaseView gather;             // MsmSources::gather: what the accumulate launch reads, and how far apart
+  bool small_fused, lds_acc;   // the buckets are filled already (msm_small_fill_kernel); the accumulator lives in LDS
+  const u64 *sorted;           // the sorted pairs (null when small_fused)
+  const u32 *zstart;
+  XYZZ<M> *pts, *head, *tail, *piece_out, *rowcol, *part, *bits;
+  LongRun *long_runs;
+  BigRun *big_runs;
+  ErrFlags *err;               // ... and the start of what the job copies to its pinned result buffer: [status slot][bits]
+  size_t result_bytes;
+};
 template <class F, class FR>
-static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev,
-                       u64 n, int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table) {
+static int msm_after_sort(MsmJobImpl &job, const AfterSort<typename F::Mem> &s) {
+  typedef typename F::Mem M;
+  Context &c = *job.ctx;
+  hipStream_t st = job.stream;
+  const MsmPlan &p = s.p;
+  // 4. accumulate equal chunks, then fold the buckets that straddle chunk boundaries
+  if (s.small_fused) {
+    if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));
+  } else {
+    const dim3 grid = accumulate_grid<F>(p);
+    // launches that fill the chip join the context's accumulation chain (common.hpp)
+    const bool chained = (u64)grid.x * grid.y * 128 >= (u64)c.num_cus * 4 * 64;
+    std::unique_lock<std::mutex> chain_lock(c.acc_mu, std::defer_lock);
+    if (chained) {
+      if (!job.res.acc_event) BH_HIP_CHECK(hipEventCreateWithFlags(&job.res.acc_event, hipEventDisableTiming));
+      chain_lock.lock();
+      if (c.last_acc_event) BH_HIP_CHECK(hipStreamWaitEvent(st, c.last_acc_event, 0));
+      for (hipEvent_t ev : c.pending_barriers) BH_HIP_CHECK(hipStreamWaitEvent(st, ev, 0));   // bh_ctx_accumulations_after
+      c.pending_barriers.clear();
+    }
+    const Affine<M> *acc_bases = (const Affine<M> *)s.gather.ptr;
+    if (int rc = launch_accumulate<F>(st, p, s.lds_acc, s.sorted, s.zstart, acc_bases, s.gather.stride, s.pts, s.head, s.tail, s.err)) return rc;
+    if (chained) {
+      BH_HIP_CHECK(hipEventRecord(job.res.acc_event, st));
+      c.last_acc_event = job.res.acc_event;
+      chain_lock.unlock();
+    }
+    if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));   // brackets exactly the accumulate launch
+    const int rc = launch_merges<FR>(st, p, s.mp, c.num_cus, 0, s.sorted, s.zstart, s.pts, s.head, s.tail, s.long_runs, s.big_runs, s.piece_out, s.err);
+    if (rc) return rc;
+  }
+  // 5. reduce: row and column sums, then the bit sums and totals the host tail combines (launch_reduce, above)
+  SumLaunchSink sink;
+  if (int rc = launch_reduce<FR>(st, p, s.rp, c.num_cus, s.pts, s.rowcol, s.part, s.bits, sink)) return rc;
+  if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_end, st));
+  // status words + results to pinned host memory, one copy: [ErrFlags slot (256 B)][bit sums]
+  job.host_result_bytes = s.result_bytes;
+  if (job.host_result_bytes > job.res.pinned_bytes) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipMemcpyAsync(job.host_result, s.err, job.host_result_bytes, hipMemcpyDeviceToHost, st));
+  return BH_OK;
+}
+template <class F, class FR>
+static int msm_enqueue(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                       const u64 *density_dev, const MsmOpts &opts) {
   typedef typename F::Mem M;
   static_assert(sizeof(typename FR::Mem::T) == sizeof(typename M::T), "both bundles work on the same records");
   typedef XYZZ<M> Pt;
   constexpr bool G2 = (M::WORDS == 24);
   Context &c = *job.ctx;
   hipStream_t st = job.stream;
-  // a window table is used when it exists, nobody forces another window size, and its row indices
-  // fit the 31-bit base field of a pair
-  const bool use_table = table && !(opts.flags & BH_MSM_NO_TABLE) && (opts.c == 0 || opts.c == table->c) &&
-                         (u64)table->W * table->stride < ((u64)1 << 31) && (u64)table->W * n < ((u64)1 << 32);
-  if (opts.padded_table && G2) return BH_ERR_INVALID_ARG;   // only G1 tables are laid out at a 128-byte stride
+  // running bucket sum in LDS: only meaningful for the single-lane G2 kernel (its default), or when forced
+  const bool lds_acc = F::LANES == 1 && ((opts.flags & BH_MSM_ACC_LDS) ? true : (opts.flags & BH_MSM_ACC_REGISTERS) ? false : G2);
+  // which plan, and which of the handle's sources each kernel reads (msm_types.hpp)
+  const MsmSources src = msm_pick_sources(bases, opts, n, G2 ? BH_G2 : BH_G1,
+                                          F::LANES != 1 ? ACC_MULTI_LANE : lds_acc ? ACC_ONE_LANE_LDS : ACC_ONE_LANE_REGISTERS);
+  if (!src.valid) return BH_ERR_INVALID_ARG;
+  const bool use_table = src.use_table;
+  const u64 n_bases = bases.n;
   // a many-job: opts.vectors scalar vectors of n scalars, vector v at scalars_dev + v * opts.scalar_stride
   const bool many = opts.vectors > 1;
   if (many && (opts.flags & BH_MSM_HOLD)) return BH_ERR_INVALID_ARG;
-  const MsmPlan p = many        ? make_many_plan(n, opts.vectors, use_table ? table : nullptr, opts.c, opts.chunk, G2, c.num_cus)
-                    : use_table ? make_table_plan(n, *table, opts.chunk, G2, c.num_cus)
+  const MsmPlan p = many        ? make_many_plan(n, opts.vectors, use_table ? &bases.tab : nullptr, opts.c, opts.chunk, G2, c.num_cus)
+                    : use_table ? make_table_plan(n, bases.tab, opts.chunk, G2, c.num_cus)
                                 : make_plan(n, opts.c, opts.chunk, G2);
-  // running bucket sum in LDS: only meaningful for the single-lane G2 kernel (its default), or when forced
-  const bool lds_acc = F::LANES == 1 && ((opts.flags & BH_MSM_ACC_LDS) ? true : (opts.flags & BH_MSM_ACC_REGISTERS) ? false : G2);
   job.plan = p;
   if ((u64)p.Wd * n >= ((u64)1 << 32)) return BH_ERR_INVALID_ARG;  // pair positions are 32-bit
   if (n_bases >= ((u64)1 << 31)) return BH_ERR_INVALID_ARG;        // base index shares its word with the sign bit
@@ -1445,7 +1513,6 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const u64 ncounts = sort_counts_elems(p);
   const u64 nslots = (u64)p.W * p.chunks_per_window;
   const MergePlan mp = merge_plan<FR>(p, c.num_cus);
-  const u32 max_long = mp.max_long, max_big = mp.max_big, max_pieces = mp.max_pieces;
   const ReducePlan rp = reduce_plan<FR>(p, c.num_cus);
   const u64 nwords = (n + 63) / 64;
   size_t off = 0;
@@ -1460,8 +1527,8 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   const size_t o_pairs_a = carve(npairs * 8), o_pairs_b = carve(npairs * 8);
   const size_t o_counts = carve((ncounts + 1) * 4), o_scan = carve(scan_tmp_elems(ncounts + 1) * 4), o_zstart = carve((u64)p.W * 4);
   const size_t o_head = carve(nslots * sizeof(Pt)), o_tail = carve(nslots * sizeof(Pt));
-  const size_t o_long = carve((u64)max_long * sizeof(LongRun)), o_big = carve((u64)max_big * sizeof(BigRun));
-  const size_t o_pieces = carve((u64)max_pieces * sizeof(Pt));
+  const size_t o_long = carve((u64)mp.max_long * sizeof(LongRun)), o_big = carve((u64)mp.max_big * sizeof(BigRun));
+  const size_t o_pieces = carve((u64)mp.max_pieces * sizeof(Pt));
   const size_t o_rowcol = carve(rp.rowcol_elems * sizeof(Pt));
   const bool want_part = rp.want_part;   // (the piece sums of the two-stage row / column sums: reduce_plan)
   const size_t o_part = want_part ? carve(rp.part_elems * sizeof(Pt)) : 0;
@@ -1483,11 +1550,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   ErrFlags *err = b.err;
   job.err_dev = err;
   job.scalars_dev = scalars_dev; job.density_dev = density_dev; job.word_prefix = b.word_prefix;
-  // what the error-resolution pass reads is what the accumulation reads: row 0 of a table at the 128-byte stride if
-  // that is this job's source (a snapshot, like every table), else the base vector / row 0 of a dense table
-  const bool from_padded_table = use_table && opts.padded_table;
-  job.bases_dev = from_padded_table ? opts.padded_table : bases_dev;
-  job.bases_stride = from_padded_table ? 128u : (u32)sizeof(Affine<M>);
+  job.resolve_bases = src.resolve;
   job.skip = skip; job.n_bases = n_bases; job.fmt = fmt;
   job.ref_n = opts.ref_n; job.always_resolve_ident = opts.always_resolve_ident;
 
@@ -1502,7 +1565,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
   // 0.7 through the sort: profiles/r6_call54_tiny_g2_bits.txt); the default 13-bit tables have t = 8
   const u32 top_bits = 255u - (p.Wd - 1) * p.c;
   const u64 sliver_load = top_bits >= 31 ? 0 : ((u64)p.nd >> top_bits);
-  const bool small_fused = use_table && !opts.padded_table && plan_fused_sort(p) && !many && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
+  const bool small_fused = src.small_path && plan_fused_sort(p) && !many && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
                            (u64)p.n <= (u64)SMALL_MAX_PER_BUCKET * p.nb && p.c <= 15 && small_fill_lds_bytes(p.nd, p.n) <= 64 * 1024 &&
                            sliver_load + (u64)p.n / p.nb <= SMALL_LIST_CAP / 2 && !(opts.flags & BH_MSM_NO_SMALL_PATH);
   if (small_fused) {
@@ -1510,7 +1573,7 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     const size_t lds = small_fill_lds_bytes(p.nd, p.n);
     hipLaunchKernelGGL(msm_small_fill_kernel<F>, dim3((p.nb + bpb - 1) / bpb), dim3(SMALL_THREADS), lds, st, scalars_dev, fmt, p.nd,
                        density_dev, b.word_prefix, (u64)skip, (u64)n_bases, p.c, p.Wd, p.base_stride,
-                       (const Affine<M> *)bases_dev, pts, err);
+                       (const Affine<M> *)src.gather.ptr, pts, err);
     BH_HIP_CHECK(hipGetLastError());
   } else {
     int rc = msm_run_stages(p, b, scalars_dev, fmt, density_dev, skip, n_bases, st, &sorted, opts.scalar_stride);
@@ -1540,57 +1603,11 @@ static int msm_enqueue(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 
     if (c.pending_barriers.size() < 32) c.pending_barriers.push_back(job.res.sort_event);
   }
   // everything after the sort: run now, or when the job is started (bh_msm_start / its wait)
-  Context *cp = &c;
-  MsmJobImpl *jp = &job;
-  job.resume = [=]() -> int {
-  Context &c = *cp;
-  MsmJobImpl &job = *jp;
-  // 4. accumulate equal chunks, then fold the buckets that straddle chunk boundaries
-  if (small_fused) {
-    if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));
-  } else {
-    const dim3 grid = accumulate_grid<F>(p);
-    const Affine<M> *bases = (const Affine<M> *)bases_dev;
-    // G1 records at a 128-byte stride for the gathers of the classic plan (api.hip bh_bases::padded)
-    const bool padded = opts.padded_bases && !use_table && !G2 && F::LANES == 1 && !lds_acc;
-    // ... and of the table plan, when the table is one that was laid out that way (bh_bases::table_padded)
-    const bool padded_tab = opts.padded_table && use_table;
-    // launches that fill the chip join the context's accumulation chain (common.hpp)
-    const bool chained = (u64)grid.x * grid.y * 128 >= (u64)c.num_cus * 4 * 64;
-    std::unique_lock<std::mutex> chain_lock(c.acc_mu, std::defer_lock);
-    if (chained) {
-      if (!job.res.acc_event) BH_HIP_CHECK(hipEventCreateWithFlags(&job.res.acc_event, hipEventDisableTiming));
-      chain_lock.lock();
-      if (c.last_acc_event) BH_HIP_CHECK(hipStreamWaitEvent(st, c.last_acc_event, 0));
-      for (hipEvent_t ev : c.pending_barriers) BH_HIP_CHECK(hipStreamWaitEvent(st, ev, 0));   // bh_ctx_accumulations_after
-      c.pending_barriers.clear();
-    }
-    // (every variant of the kernel takes the record stride, so a padded table is read correctly by all of them)
-    const Affine<M> *acc_bases = padded_tab ? (const Affine<M> *)opts.padded_table : padded ? (const Affine<M> *)opts.padded_bases : bases;
-    const u32 acc_stride = (padded || padded_tab) ? 128u : (u32)sizeof(Affine<M>);
-    if (int rc = launch_accumulate<F>(st, p, lds_acc, sorted, b.zstart, acc_bases, acc_stride, pts, head, tail, err)) return rc;
-    if (chained) {
-      BH_HIP_CHECK(hipEventRecord(job.res.acc_event, st));
-      c.last_acc_event = job.res.acc_event;
-      chain_lock.unlock();
-    }
-    if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_accum, st));   // brackets exactly the accumulate launch
-    if (int rc = launch_merges<FR>(st, p, mp, c.num_cus, 0, sorted, b.zstart, pts, head, tail, long_runs, big_runs, piece_out, err)) return rc;
-  }
-  // 5. reduce: row and column sums, then the bit sums and totals the host tail combines (launch_reduce, above)
-  SumLaunchSink sink;
-  if (int rc = launch_reduce<FR>(st, p, rp, c.num_cus, pts, rowcol, part, bits, sink)) return rc;
-  if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_end, st));
-  // status words + results to pinned host memory, one copy: [ErrFlags slot (256 B)][bit sums]
-  job.host_result_bytes = (o_bits - o_err) + bits_bytes;
-  if (job.host_result_bytes > job.res.pinned_bytes) return BH_ERR_INVALID_ARG;
-  BH_HIP_CHECK(hipMemcpyAsync(job.host_result, ws + o_err, job.host_result_bytes, hipMemcpyDeviceToHost, st));
+  const AfterSort<M> after = {p, mp, rp, src.gather, small_fused, lds_acc, sorted, b.zstart, pts, head, tail, piece_out, rowcol, part,
+                             bits, long_runs, big_runs, err, (o_bits - o_err) + bits_bytes};
+  if (!hold) return msm_after_sort<F, FR>(job, after);
+  job.resume = [after](MsmJobImpl &j) { return msm_after_sort<F, FR>(j, after); };
   return BH_OK;
-  };   // job.resume
-  if (hold) return BH_OK;
-  const int rc2 = job.resume();
-  job.resume = nullptr;
-  return rc2;
 }
 
 template <> struct HostOf<FpOps> { typedef HostFpOps type; };
@@ -1662,7 +1679,7 @@ static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
     return job.early_rc;
   }
   if (job.resume) {   // held and never started: start it now
-    rc = job.resume();
+    rc = job.resume(job);
     job.resume = nullptr;
   }
   if (hipStreamSynchronize(job.stream) != hipSuccess) rc = BH_ERR_HIP;
@@ -1704,7 +1721,7 @@ static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
       const u32 c_ref = (u32)c_ln, w_ref = (255 + c_ref - 1) / c_ref, lo_ref = c_ref * (w_ref - 1);
       hipLaunchKernelGGL(msm_err_resolve_kernel<F>, dim3((p.nd + 255) / 256), dim3(256), 0, job.stream,
                          job.scalars_dev, job.fmt, p.nd, job.density_dev, job.word_prefix, job.skip, job.n_bases,
-                         (const Affine<F> *)job.bases_dev, job.bases_stride, lo_ref, job.err_dev);
+                         (const Affine<F> *)job.resolve_bases.ptr, job.resolve_bases.stride, lo_ref, job.err_dev);
       if (hipMemcpyAsync(&ef, job.err_dev, sizeof ef, hipMemcpyDeviceToHost, job.stream) != hipSuccess ||
           hipStreamSynchronize(job.stream) != hipSuccess)
         rc = BH_ERR_HIP;
@@ -1906,8 +1923,8 @@ template <class F> static void devhdr_point_mul_t(void *r, const void *a, const 
 // OPS = the record format in memory (FpOps / Fp2Ops).  msm_enqueue_<group> itself (which kernel bundle accumulates,
 // which one merges and reduces) is written out in msm_g1.hip / msm_g2.hip.
 #define BH_INSTANTIATE_MSM_SUPPORT(SUFFIX, OPS)                                                               \
-  int window_table_##SUFFIX(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st) {                           \
-    return window_table_t<OPS>(table_dev, n, c, W, st);                                                       \
+  int window_table_##SUFFIX(BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st) {   \
+    return window_table_t<OPS>(src, dst, dst_stride, n, c, W, st);                                            \
   }                                                                                                           \
   int msm_finish_##SUFFIX(MsmJobImpl &job, void *out_affine, float *ms) {                                     \
     return msm_finish<OPS>(job, out_affine, ms);                                                              \

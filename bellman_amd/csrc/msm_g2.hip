@@ -8,10 +8,11 @@
 //                               accumulation when forced (BH_MSM_G2_SINGLE_LANE; the default of large jobs until round 4).
 #include "msm_ec.cuh"
 namespace bh {
-int msm_enqueue_g2(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
-                   const u64 *density_dev, const MsmOpts &opts, const WindowTable *table) {
-  const bool with_table = table && !(opts.flags & BH_MSM_NO_TABLE) && (opts.c == 0 || opts.c == table->c);
-  const MsmPlan pl = with_table ? make_table_plan(n, *table, opts.chunk, true, 256) : make_plan(n, opts.c, opts.chunk, true);
+int msm_enqueue_g2(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                   const u64 *density_dev, const MsmOpts &opts) {
+  // (which plan the job runs does not depend on the accumulate form, which is only chosen below)
+  const bool use_table = msm_pick_sources(bases, opts, n, BH_G2, ACC_MULTI_LANE).use_table;
+  const MsmPlan pl = use_table ? make_table_plan(n, bases.tab, opts.chunk, true, 256) : make_plan(n, opts.c, opts.chunk, true);
   // 0 = lane triples, 1 = lane pairs, 2 = one lane per point
   const bool f_single = opts.flags & BH_MSM_G2_SINGLE_LANE, f_triples = !f_single && (opts.flags & BH_MSM_G2_LANE_TRIPLES);
   const bool f_pairs = opts.flags & BH_MSM_G2_LANE_PAIRS;   // accumulation only; combines with the two above
@@ -19,8 +20,8 @@ int msm_enqueue_g2(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip
   const int acc = f_pairs ? 1 : f_single ? 2 : f_triples ? 0 : (n >= ((u64)1 << 15) ? 1 : 0);
   // [r6] ... but a big TABLE set (the 2^19 buckets of 20-bit rows) stays on lane triples: with the two-stage sums of msm_ec.cuh
   // its reduction is ~1.5 ms there, 2.8 with one lane per point (profiles/r6_call38_*, r6_call39_*)
-  const bool red_single = f_single ? true : f_triples ? false : ((u64)pl.NB * (opts.vectors > 1 ? opts.vectors : 1) > ((u64)1 << 17) && !with_table);   // (a many-job: the buckets of all its vectors)
-#define BH_G2_CASE(F, FR) return msm_enqueue<F, FR>(job, bases_dev, n_bases, skip, scalars_dev, n, fmt, density_dev, opts, table)
+  const bool red_single = f_single ? true : f_triples ? false : ((u64)pl.NB * (opts.vectors > 1 ? opts.vectors : 1) > ((u64)1 << 17) && !use_table);   // (a many-job: the buckets of all its vectors)
+#define BH_G2_CASE(F, FR) return msm_enqueue<F, FR>(job, bases, skip, scalars_dev, n, fmt, density_dev, opts)
   if (red_single) {
     if (acc == 0) BH_G2_CASE(Fp2K3Ops, Fp2Ops);
     if (acc == 1) BH_G2_CASE(Fp2PairOps, Fp2Ops);

@@ -52,10 +52,6 @@ struct MsmOpts {
   // top window even when it saw no EOF itself - the fold needs it for the error precedence
   u64 ref_n = 0;
   bool always_resolve_ident = false;
-  const void *padded_bases = nullptr;   // the same G1 records at a 128-byte stride (api.hip bh_bases::padded); null: none
-  // a G1 window table whose records sit at a 128-byte stride (api.hip bh_bases::table_padded): only the bucket
-  // accumulation of the table plan reads it; `bases_dev` of such a job is the dense base vector itself
-  const void *padded_table = nullptr;
   // a many-job (bh_msm_many_*): `vectors` scalar vectors of the job's n scalars each over ONE base vector and density
   // map, vector v at scalars + v * scalar_stride bytes; 0 = an ordinary job
   u32 vectors = 0;
@@ -88,6 +84,45 @@ struct WindowTable {
   u64 stride;   // number of bases per row
 };
 
+// Where a job's base points come from.  A handle (api.hip bh_bases) has up to three sources; api.hip snapshots them once
+// per job, under the context's job_mu, and msm_pick_sources - the ONE place that holds these rules - says which of them
+// each kernel of the job reads and at what stride.  Host only, no HIP calls (tests/test_msm_sources_cpu.py).
+struct BaseView {
+  const void *ptr = nullptr;   // null: the view is absent
+  u32 stride = 0;              // bytes from one record to the next
+};
+struct MsmBases {
+  BaseView dense;    // the registered vector: 96 (G1) / 192 (G2) bytes apart
+  BaseView padded;   // G1: a copy of it 128 bytes apart (one cache line per gather), or absent
+  BaseView table;    // window table, row-major [tab.W][tab.stride] records at its own stride (G1: 96 or 128), or absent
+  WindowTable tab = {0, 0, 0};
+  u64 n = 0;         // points in the vector
+};
+// how the accumulate launch of the job holds its running sum: the padded copy is gathered by the first form only
+enum AccForm { ACC_ONE_LANE_REGISTERS = 0, ACC_ONE_LANE_LDS = 1, ACC_MULTI_LANE = 2 };
+struct MsmSources {
+  bool valid = false;       // false: a table laid out as no kernel reads it (only G1 tables may sit at a 128-byte stride)
+  bool use_table = false;   // the window-table plan
+  BaseView gather;          // what the bucket accumulation (and the small path) gathers from
+  BaseView resolve;         // the view whose leading n records the error-resolution pass reads
+  bool small_path = false;  // the source allows the one-launch small path: msm_small_fill_kernel indexes Affine<M> *
+};
+inline MsmSources msm_pick_sources(const MsmBases &b, const MsmOpts &opts, u64 n, int group, AccForm form) {
+  const u32 rec = group == BH_G1 ? 96u : 192u;
+  MsmSources s;
+  s.valid = !b.table.ptr || b.table.stride == rec || (group == BH_G1 && b.table.stride == 128u);
+  if (!s.valid) return s;
+  // a window table is used when it exists, nobody forces another window size, and its row indices and the job's pair
+  // positions fit their 31- and 32-bit fields
+  s.use_table = b.table.ptr && !(opts.flags & BH_MSM_NO_TABLE) && (opts.c == 0 || opts.c == b.tab.c) &&
+                (u64)b.tab.W * b.tab.stride < ((u64)1 << 31) && (u64)b.tab.W * n < ((u64)1 << 32);
+  const bool padded = b.padded.ptr && group == BH_G1 && form == ACC_ONE_LANE_REGISTERS;
+  s.gather = s.use_table ? b.table : padded ? b.padded : b.dense;
+  s.resolve = s.use_table ? b.table : b.dense;   // (row 0 of a table is a snapshot of the bases)
+  s.small_path = s.use_table && b.table.stride == rec;
+  return s;
+}
+
 struct MsmJobImpl {
   Context *ctx = nullptr;
   int group = BH_G1;
@@ -109,8 +144,7 @@ struct MsmJobImpl {
   const void *scalars_dev = nullptr;
   const u64 *density_dev = nullptr;
   const u32 *word_prefix = nullptr;
-  const void *bases_dev = nullptr;
-  u32 bases_stride = 0;              // bytes between the records of `bases_dev`
+  BaseView resolve_bases;            // MsmSources::resolve
   u64 skip = 0, n_bases = 0;
   int fmt = 0;
   ErrFlags *err_dev = nullptr;
@@ -119,7 +153,9 @@ struct MsmJobImpl {
   u64 ref_n = 0;                     // MsmOpts::ref_n
   bool always_resolve_ident = false;
   bool saw_eof = false, saw_ident = false, saw_ident_top = false;   // after completion
-  std::function<int()> resume;       // the stages after the sort of a job issued with BH_MSM_HOLD (until it is started)
+  // the stages after the sort of a job issued with BH_MSM_HOLD (until it is started): msm_after_sort over a copy of the
+  // job's AfterSort (msm_ec.cuh), which names everything a held job keeps
+  std::function<int(MsmJobImpl &)> resume;
   std::mutex mu;
   bool done = false;
   int done_rc = BH_OK;
@@ -154,10 +190,10 @@ int msm_run_stages(const MsmPlan &p, const MsmBuffers &b, const void *scalars_de
                    u64 skip, u64 n_bases, hipStream_t st, const u64 **sorted_out, u64 scalar_stride = 0);
 
 // msm_g1.hip / msm_g2.hip
-int msm_enqueue_g1(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,
-                   int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table);
-int msm_enqueue_g2(MsmJobImpl &job, const void *bases_dev, u64 n_bases, u64 skip, const void *scalars_dev, u64 n,
-                   int fmt, const u64 *density_dev, const MsmOpts &opts, const WindowTable *table);
+int msm_enqueue_g1(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                   const u64 *density_dev, const MsmOpts &opts);
+int msm_enqueue_g2(MsmJobImpl &job, const MsmBases &bases, u64 skip, const void *scalars_dev, u64 n, int fmt,
+                   const u64 *density_dev, const MsmOpts &opts);
 int msm_finish_g1(MsmJobImpl &job, void *out_affine, float *ms);   // ms: float[4] or null
 int msm_finish_g2(MsmJobImpl &job, void *out_affine, float *ms);
 int fixed_base_mul_g1(const void *base_host, const void *scalars_dev, u64 n, int fmt, void *out_dev, hipStream_t st, void *table_dev);
@@ -200,10 +236,11 @@ inline int proof_status_error(u32 word) {
   return BH_OK;
 }
 // on-curve + prime-order-subgroup test of decoded points (skips entries already invalid / identity)
-// fills rows 1 .. W-1 of a window table whose row 0 holds the n bases
-int window_table_g1(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st);
-int window_table_g2(void *table_dev, u64 n, u32 c, u32 W, hipStream_t st);
-int window_table(int group, void *table_dev, u64 n, u32 c, u32 W, hipStream_t st);
+// writes the W rows of a window table over the n records of `src` at their final place: row j record i at
+// dst + (j * n + i) * dst_stride bytes (dst_stride >= the record size; bytes between records are left as they are)
+int window_table_g1(BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st);
+int window_table_g2(BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st);
+int window_table(int group, BaseView src, void *dst, u32 dst_stride, u64 n, u32 c, u32 W, hipStream_t st);
 int points_check_g1(const void *pts_dev, u64 n, u32 *status_dev, hipStream_t st);
 int points_check_g2(const void *pts_dev, u64 n, u32 *status_dev, hipStream_t st);
 int points_check(int group, const void *pts_dev, u64 n, u32 *status_dev, hipStream_t st);

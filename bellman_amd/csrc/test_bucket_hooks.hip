@@ -3,7 +3,8 @@
 // the launch functions msm_enqueue calls (launch_accumulate, launch_merges, merge_plan, merge_bounds of msm_ec.cuh); everything the
 // kernels wrote comes back raw (bh_test_bucket_stage_* of include/bellman_hip_test.h; tests/test_gpu_bucket_stage.py,
 // tests/test_bucket_stage_model_cpu.py).  Every input is validated on the host before anything is launched: a stream that
-// could make a kernel leave its buffers is refused.
+// could make a kernel leave its buffers is refused.  Next to them: what the stage gathers from - msm_pick_sources on tagged
+// views (bh_test_msm_sources, host only) and window_table_kernel into a sentinel-filled buffer (bh_test_window_table_dev).
 #include <string.h>
 
 #include <vector>
@@ -248,6 +249,43 @@ int bh_test_bucket_stage_dev(bh_ctx *ctx, int acc_form, int merge_form, const ui
       (rc = d_long.fetch(long_out, st)) || (rc = d_big.fetch(big_out, st)) || (rc = d_pieces.fetch(pieces_out, st)) ||
       (rc = d_err.fetch(err_out, st)))
     return rc;
+  BH_HIP_CHECK(hipStreamSynchronize(st));
+  return BH_OK;
+}
+int bh_test_msm_sources(int group, int table_kind, int has_padded, uint32_t flags, unsigned opts_c, unsigned tab_c, unsigned tab_W,
+                        uint64_t tab_row_records, uint64_t n, int acc_form, uint32_t out6[6]) {
+  if (!out6 || (group != BH_G1 && group != BH_G2) || table_kind < 0 || table_kind > 2 || acc_form < 0 || acc_form > 2) return BH_ERR_INVALID_ARG;
+  static const char tag[3] = {0, 0, 0};   // the views' pointers: &tag[0] dense, &tag[1] the padded copy, &tag[2] the table
+  const u32 rec = group == BH_G1 ? 96u : 192u;
+  MsmBases b;
+  b.dense = {&tag[0], rec};
+  if (has_padded) b.padded = {&tag[1], 128u};
+  if (table_kind) b.table = {&tag[2], table_kind == 2 ? 128u : rec};
+  b.tab = WindowTable{tab_c, tab_W, tab_row_records};
+  b.n = tab_row_records;
+  MsmOpts o;
+  o.c = opts_c; o.flags = flags;
+  const MsmSources s = msm_pick_sources(b, o, n, group, (AccForm)acc_form);
+  if (!s.valid) return BH_ERR_INVALID_ARG;
+  out6[0] = s.use_table; out6[1] = (u32)((const char *)s.gather.ptr - tag); out6[2] = s.gather.stride;
+  out6[3] = (u32)((const char *)s.resolve.ptr - tag); out6[4] = s.resolve.stride; out6[5] = s.small_path;
+  return BH_OK;
+}
+int bh_test_window_table_dev(bh_ctx *ctx, int group, const void *points, size_t n, unsigned stride, unsigned c, void *table_out) {
+  if (!ctx || !points || !table_out || !n || n > 4096 || c < 2 || c > 24) return BH_ERR_INVALID_ARG;
+  const u32 rec = group == BH_G1 ? 96u : 192u;
+  if ((group != BH_G1 && group != BH_G2) || (stride != rec && !(group == BH_G1 && stride == 128))) return BH_ERR_INVALID_ARG;
+  const u32 W = (256 + c - 1) / c;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = ctx->c.stream;
+  DevBuf d_src, d_tab;
+  int rc;
+  if ((rc = d_src.alloc(n * rec, 0, st)) || (rc = d_tab.alloc((size_t)W * n * stride, SENTINEL, st))) return rc;
+  BH_HIP_CHECK(hipMemcpyAsync(d_src.p, points, n * rec, hipMemcpyHostToDevice, st));
+  BH_HIP_CHECK(hipStreamSynchronize(st));   // (pageable host memory: the copy above may still be staged)
+  const BaseView src = {d_src.p, rec};
+  rc = group == BH_G1 ? window_table_t<FpOps>(src, d_tab.p, stride, n, c, W, st) : window_table_t<Fp2Ops>(src, d_tab.p, stride, n, c, W, st);
+  if (rc || (rc = d_tab.fetch(table_out, st))) return rc;
   BH_HIP_CHECK(hipStreamSynchronize(st));
   return BH_OK;
 }

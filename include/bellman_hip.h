@@ -127,7 +127,9 @@ int bh_ctx_synchronize(bh_ctx *ctx);
 int bh_ctx_accumulations_after(bh_ctx *ctx, void *stream);
 /* returns the context's idle cached device memory (recycled job workspaces, FFT twiddle tables) to the
  * driver; waits for the device to be idle first.  Purely a memory-footprint control; call it while no
- * other thread is inside a call on this context. */
+ * other thread is inside a call on this context.  Unless a multiexp is in flight it also drops the window tables that
+ * registration built automatically: results do not change, but such handles run the classic plan (slower for vectors
+ * that had a table) until bh_bases_precompute is called on them - nothing rebuilds a dropped table by itself. */
 int bh_ctx_trim(bh_ctx *ctx);
 
 /* ---- EvaluationDomain (src/domain.rs) ------------------------------------------------
@@ -278,7 +280,8 @@ int bh_bases_copy_out_dev(bh_ctx *ctx, const bh_bases *b, int group, size_t firs
 /* wrap an existing device array of packed 96/192-byte records (not owned): a LIVE view - nothing is copied or
  * precomputed from the buffer at wrap time (no host mirror for tiny multiexps, no automatic window table), every
  * multiexp reads the buffer as it is when the job runs; the caller orders its writes before issuing.
- * bh_bases_precompute on such a handle is an explicit SNAPSHOT of the buffer's contents at that call. */
+ * bh_bases_precompute on such a handle is an explicit SNAPSHOT of the buffer's contents at that call.  A multiexp
+ * that does not use that table (BH_MSM_NO_TABLE, another window_bits) reads the live buffer, never the snapshot. */
 int bh_bases_wrap_dev(bh_ctx *ctx, int group, const void *dev_points, size_t n, bh_bases **out);
 void bh_bases_release(bh_ctx *ctx, bh_bases *b);
 size_t bh_bases_len(const bh_bases *b);

@@ -217,6 +217,21 @@ int bh_test_bucket_stage_dev(bh_ctx *ctx, int acc_form, int merge_form, const ui
                              unsigned n, const void *bases, size_t n_bases, unsigned base_stride, unsigned c, unsigned K,
                              unsigned chunks_per_window, const uint32_t *overrides4, uint32_t plan_out8[8], void *pts_out,
                              void *head_out, void *tail_out, void *long_out, void *big_out, void *pieces_out, void *err_out);
+/* Which of a base handle's sources a multiexp reads (csrc/msm_types.hpp msm_pick_sources; tests/test_msm_sources_cpu.py).
+ * Host only: the views' pointers are tags.  table_kind: 0 no window table, 1 one at the dense record stride (96 / 192
+ * bytes), 2 one at a 128-byte stride; tab_c, tab_W, tab_row_records describe it (window bits, rows, records per row);
+ * has_padded: the vector has a copy at a 128-byte stride; flags, opts_c: bh_msm_opts; n scalars; acc_form: 0 one lane per
+ * point with the accumulator in registers, 1 ... in LDS, 2 several lanes per point.  out6 = [use_table, the view the
+ * accumulation gathers from (0 the vector, 1 its padded copy, 2 the table), its stride in bytes, the view the
+ * error-resolution pass reads, its stride, 1 where the source allows the one-launch small path].  BH_ERR_INVALID_ARG for a
+ * layout no kernel reads (a G2 table at 128 bytes). */
+int bh_test_msm_sources(int group, int table_kind, int has_padded, uint32_t flags, unsigned opts_c, unsigned tab_c, unsigned tab_W,
+                        uint64_t tab_row_records, uint64_t n, int acc_form, uint32_t out6[6]);
+/* window_table_kernel on its own (tests/test_gpu_window_table_build.py): the table of n <= 4096 affine records, rows of c
+ * window bits, built by the function bh_bases_precompute builds it with into a buffer of ceil(256 / c) n `stride` bytes
+ * filled with the sentinel byte and followed by the guard (bh_test_bucket_stage_shape); table_out receives both raw.
+ * stride: 96 or 128 (G1), 192 (G2); any other is refused. */
+int bh_test_window_table_dev(bh_ctx *ctx, int group, const void *points, size_t n, unsigned stride, unsigned c, void *table_out);
 
 /* Stage 5 of a multiexp on its own, and its host tail (csrc/test_reduce_hooks.hip; tests/test_gpu_reduce_stage.py,
  * tests/models/reduce_stage_model.py): the row / column sums, their two-stage split over piece sums, the bit sums and the

@@ -116,11 +116,11 @@ def test_large_host_scalar_multiexp_error_semantics(worker):
 
 
 def test_g1_window_table_at_128_byte_stride(worker):
-    """A G1 vector of 2^19 points with its window table re-laid at a 128-byte record stride (api.hip
-    bh_bases::table_padded; 16-bit and 20-bit rows): the multiexp over it == the classic 16-window plan over the dense
+    """A G1 vector of 2^19 points with its window table built at a 128-byte record stride (api.hip
+    bh_bases::table_stride; 16-bit and 20-bit rows): the multiexp over it == the classic 16-window plan over the dense
     vector == [sum s_i t_i]G, with full density, with a density map + skip, with a forced chunk length and with the
     LDS-accumulator variant of the kernel (every variant takes the record stride).  Then the error semantics of
-    src/multiexp.rs:55-80,295-300 on that path - the error-resolution kernel reads the dense vector, not the table: an
+    src/multiexp.rs:55-80,295-300 on that path - the error-resolution kernel reads row 0 of the table at its stride: an
     identity base under a full-size / small / zero scalar, running out of bases, and both at once == what the classic plan
     reports for the same inputs (itself == the oracle in test_large_host_scalar_multiexp_error_semantics).  (Until round 6
     such tables were built on request only - bh_bases_precompute, BELLMAN_HIP_TABLE_MAX_LOG2_G1; a registered vector of up
