@@ -244,6 +244,52 @@ def test_a_set_of_one_key_is_verify_each(lib, mat, case1):
     assert OK in got and INVALID_PROOF in got
 
 
+@pytest.mark.parametrize("fmt", [psm.CANONICAL, psm.MONT])
+@pytest.mark.parametrize("n", [1, 65])
+def test_a_set_of_one_key_is_batch_verify(lib, mat, n, fmt):
+    """the batch check over a set of one key returns what the one-key entry point returns, from records and from bytes: all
+    rows valid, one invalid row, one unreadable row (the same bad_index too), a z equal to q"""
+    from bellman_amd import verifier
+
+    k = 2
+    valid = [mat.valid[k][t % 8].with_key(0) for t in range(n)]
+    rnd = random.Random(4242 + n)
+    zs = [psm.scalar_raw(rnd.randrange(1, Q), fmt) for _ in range(n)]
+    ko = (ctypes.c_uint32 * n)()
+    one = verifier.KeySet([mat.pvks[k]])
+
+    def both(rows, blobs, z_raw):
+        """(set, one key) x (records -> code, bytes -> (code, bad_index)); blobs None: the rows as Proof::write writes them"""
+        ins = psm.fr_bytes(psm.scalar_raw(v, fmt) for r in rows for v in r.inputs)
+        recs, z = b"".join(r.rec for r in rows), psm.fr_bytes(z_raw)
+        data = b"".join(blobs if blobs is not None else [compress(r.points) for r in rows])
+        bad_set, bad_one = ctypes.c_size_t(777), ctypes.c_size_t(777)
+        of_set = (lib.bh_groth16_batch_verify_keys(one._h, ko, recs, n, ins, len(ins) // 32, fmt, z),
+                  (lib.bh_groth16_batch_verify_keys_compressed(one._h, ko, data, n, ins, len(ins) // 32, fmt, z, ctypes.byref(bad_set)),
+                   bad_set.value))
+        of_one = (lib.bh_groth16_batch_verify(mat.pvks[k]._h, recs, n, ins, mat.N_INPUTS[k], fmt, z),
+                  (lib.bh_groth16_batch_verify_compressed(mat.pvks[k]._h, data, n, ins, mat.N_INPUTS[k], fmt, z, ctypes.byref(bad_one)),
+                   bad_one.value))
+        return of_set, of_one
+
+    try:
+        j = n // 2
+        of_set, of_one = both(valid, None, zs)
+        assert of_set == of_one == (OK, (OK, 777))
+        invalid = list(valid)
+        invalid[j] = spoil(mat, valid[j], "wrong c", rnd)
+        of_set, of_one = both(invalid, None, zs)
+        assert of_set == of_one == (INVALID_PROOF, (INVALID_PROOF, 777))
+        blobs = [compress(r.points) for r in valid]
+        blobs[j], code = unreadable(blobs[j], 1)
+        of_set, of_one = both(valid, blobs, zs)                 # (the records are the valid rows: only the bytes are unreadable)
+        assert of_set == of_one == (OK, (code, j)) and code == AT_INFINITY
+        of_set, of_one = both(valid, None, zs[:j] + [Q] + zs[j + 1:])
+        assert of_set == of_one == (INVALID_ARG, (INVALID_ARG, 777))
+    finally:
+        one.release()
+
+
 def test_a_key_without_rows_the_same_key_twice_and_all_rows_on_the_last_key(lib, mat, case1):
     from bellman_amd import verifier
 
