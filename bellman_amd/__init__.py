@@ -19,6 +19,7 @@ from .errors import (  # noqa: F401
     UnconstrainedVariable,
     UnexpectedEof,
     UnexpectedIdentity,
+    Unsatisfiable,
     VerificationError,
 )
 from .multicore import Waiter, Worker  # noqa: F401

@@ -38,7 +38,7 @@ EXPORTS = [
     "bh_msm_sharded_async", "bh_msm_sharded_wait",
     "bh_fixed_base_mul_dev",
     "bh_groth16_params_create", "bh_groth16_params_read", "bh_groth16_generate", "bh_groth16_params_write", "bh_groth16_params_vk_ext", "bh_groth16_params_query", "bh_groth16_params_vk", "bh_proof_write", "bh_groth16_params_release", "bh_groth16_prove_assignment",
-    "bh_r1cs_create", "bh_r1cs_release", "bh_r1cs_shape", "bh_r1cs_density", "bh_r1cs_eval_dev", "bh_r1cs_eval_transposed_dev", "bh_fr_powers_dev", "bh_fr_qap_ext_dev",
+    "bh_r1cs_create", "bh_r1cs_release", "bh_r1cs_shape", "bh_r1cs_density", "bh_r1cs_eval_dev", "bh_r1cs_eval_many_dev", "bh_r1cs_check_many_dev", "bh_r1cs_check_many", "bh_r1cs_eval_transposed_dev", "bh_fr_powers_dev", "bh_fr_qap_ext_dev",
     "bh_r1cs_eval_transposed_points_dev", "bh_groth16_generate_from_powers_of_tau", "bh_groth16_params_rescale_delta",
     "bh_groth16_prove_witness", "bh_groth16_prove_assignment_async", "bh_groth16_prove_witness_async", "bh_groth16_proof_wait",
     "bh_groth16_prove_witness_part", "bh_groth16_sums_add", "bh_groth16_assemble",
@@ -51,6 +51,7 @@ EXPORTS = [
     "bh_bases_first_difference", "bh_pairing_same_ratio_each", "bh_groth16_params_verify_step",
     "bh_point_mul_each_dev", "bh_bases_scale_powers", "bh_powers_of_tau_contribute",
     "bh_msm_many_async", "bh_msm_many_async_dev", "bh_msm_many_wait", "bh_msm_many_plan_info", "bh_groth16_prove_witness_batch",
+    "bh_groth16_prove_witness_batch_checked",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -74,7 +75,8 @@ TEST_EXPORTS = [
     "bh_test_phase2_sums", "bh_test_records_differ_host", "bh_test_compare_shape",
     "bh_test_glv_split_host", "bh_test_glv_ladder_host", "bh_test_glv_ladder_dev",
     "bh_test_groth16_prove_witness_batch_budget", "bh_test_many_stage_dev",
-    "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan",
+    "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan", "bh_test_r1cs_many_tile",
+    "bh_test_groth16_prove_witness_batch_he",
 ]
 
 
@@ -199,6 +201,7 @@ def load():
     lib.bh_h_poly_fr_many_dev_on.argtypes = [vp, vp, vp, vp, sz, sz, u32, c.c_uint, vp, sz, vp]
     lib.bh_test_fft_many_plan.argtypes = [u32, sz, sz, sz, i32, vp, sz]
     lib.bh_test_groth16_prove_witness_batch_mode.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, i32, vp]
+    lib.bh_test_groth16_prove_witness_batch_he.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, vp]
     lib.bh_bases_register.argtypes = [vp, i32, vp, sz, sz, c.c_long, c.POINTER(vp)]
     lib.bh_bases_register_uncompressed.argtypes = [vp, i32, vp, sz, c.POINTER(vp)]
     lib.bh_bases_wrap_dev.argtypes = [vp, i32, vp, sz, c.POINTER(vp)]
@@ -239,6 +242,7 @@ def load():
     lib.bh_msm_many_wait.argtypes = [vp, vp, vp, c.POINTER(c.c_float), c.POINTER(c.c_uint64)]
     lib.bh_msm_many_plan_info.argtypes = [sz, sz, i32, c.c_uint, c.c_uint, vp]
     lib.bh_groth16_prove_witness_batch.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+    lib.bh_groth16_prove_witness_batch_checked.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     lib.bh_test_many_stage_dev.argtypes = [vp, i32, c.c_uint, vp, i32, sz, sz, vp, sz, sz, sz, vp, vp, vp, vp, vp]
     lib.bh_test_groth16_prove_witness_batch_budget.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz, vp]
     lib.bh_h_poly_fr_scalars.argtypes = [vp, vp, vp, vp, sz, c.POINTER(vp)]
@@ -277,6 +281,11 @@ def load():
     lib.bh_r1cs_shape.argtypes = [vp, c.POINTER(sz), c.POINTER(sz), c.POINTER(sz)]
     lib.bh_r1cs_density.argtypes = [vp, i32, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
     lib.bh_r1cs_eval_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, c.c_uint32, vp]
+    lib.bh_r1cs_eval_many_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, vp, sz, c.c_uint32, vp]
+    lib.bh_r1cs_check_many_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp]
+    lib.bh_r1cs_check_many.argtypes = [vp, vp, vp, vp, sz, vp]
+    lib.bh_test_r1cs_many_tile.argtypes = []
+    lib.bh_test_r1cs_many_tile.restype = c.c_uint32
     lib.bh_groth16_prove_witness.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
     lib.bh_groth16_demo_r1cs.argtypes = [vp, i32, sz, c.c_uint64, vp, c.POINTER(vp)]
     lib.bh_groth16_prove_demo_r1cs.argtypes = [vp, vp, i32, sz, c.c_uint64, vp, vp, vp, vp, vp, vp]

@@ -226,7 +226,8 @@ struct Fr {
 
 // ---- src/lib.rs:303-319 -------------------------------------------------------------------------
 struct SynthesisError : std::runtime_error {
-  int code;   // the C-ABI code: 1 UnexpectedIdentity, 2 IoError(UnexpectedEof), 3 PolynomialDegreeTooLarge, 4 AssignmentMissing
+  int code;   // the C-ABI code: 1 UnexpectedIdentity, 2 IoError(UnexpectedEof), 3 PolynomialDegreeTooLarge, 4 AssignmentMissing,
+              // 11 Unsatisfiable (src/lib.rs:310: prove_witness_batch_checked)
   SynthesisError(int c, const char *what) : std::runtime_error(what), code(c) {}
 };
 
@@ -578,14 +579,22 @@ static_assert(sizeof(MsmSums) == 6 * 96 + 2 * 192, "packed: the C ABI hands it o
 // The circuit's three constraint matrices, captured once and kept in HBM.  Capture
 // runs `synthesize` against a structure-only ConstraintSystem that never calls the value closures -
 // the same thing generator.rs:43-131 (KeypairAssembly) does to build the CRS for this circuit.
+struct WitnessView;
 class R1cs {
  public:
   R1cs(bellman::Circuit &shape_of, bh_ctx *ctx);
-  explicit R1cs(bh_r1cs *existing);   // adopt a handle made through the C ABI
+  explicit R1cs(bh_r1cs *existing, bh_ctx *ctx = nullptr);   // adopt a handle made through the C ABI
   ~R1cs();
   R1cs(const R1cs &) = delete;
   bh_r1cs *handle = nullptr;
+  bh_ctx *ctx = nullptr;   // the context the matrices live in (which_is_unsatisfied runs there); null for an adopted handle
+                           // whose context was not given
   size_t num_inputs = 0, num_aux = 0, num_constraints = 0;
+  // TestConstraintSystem::which_is_unsatisfied (src/gadgets/test/mod.rs:254-272) for k witnesses in one device pass
+  // (bh_r1cs_check_many_dev, in groups within BATCH_WORKSPACE_BYTES of device memory): entry j is the index of the first
+  // constraint witness j does not satisfy, or BH_R1CS_SATISFIED.  A witness of the wrong shape throws
+  // std::invalid_argument, as does a handle adopted without its context.
+  std::vector<uint32_t> which_is_unsatisfied(const WitnessView *witnesses, size_t k) const;
 };
 
 // prover.rs:57-162 reduced to witness generation: alloc/alloc_input run the value closures,
@@ -657,6 +666,9 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *input_assign
 // c_j), one bh_h_poly_fr_many_dev_on (BH_FFT_MANY_FORCE) per group, then the H many-job.  Its groups hold the largest g with
 // 4 * g * m * 32 bytes <= the budget (a, b, c and an FFT scratch vector per witness), at least one.  Forced only, like
 // BATCH_GROUPED.
+// BATCH_GROUPED_HE is BATCH_GROUPED_H with the constraint evaluation batched as well: ONE bh_r1cs_eval_many_dev per group in
+// place of its g bh_r1cs_eval_dev calls, and - when witness j + 1's host vector starts where witness j's ends - one upload
+// per vector kind per group in place of g (per witness otherwise, as in the other modes).  Forced only.
 // A witness of the wrong shape throws std::invalid_argument before anything runs.
 struct WitnessView {
   const Fr *inputs; size_t n_inputs;
@@ -664,7 +676,7 @@ struct WitnessView {
 };
 constexpr size_t BATCH_WORKSPACE_BYTES = size_t(1) << 30;   // the default workspace budget of the grouped path: 1 GiB
 constexpr size_t BATCH_IN_FLIGHT = 16;                       // proofs in flight at a time otherwise
-enum { BATCH_AUTO = 0, BATCH_GROUPED = 1, BATCH_GROUPED_H = 2 };
+enum { BATCH_AUTO = 0, BATCH_GROUPED = 1, BATCH_GROUPED_H = 2, BATCH_GROUPED_HE = 3 };
 // throws what the FIRST failing proof would throw (the subversion check and the order of reported errors per proof are
 // create_proof's); workspace_budget = 0: the default
 std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
@@ -674,6 +686,19 @@ std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, con
 void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
                                const Fr *s, Proof *proofs, int *codes, ProveTimings *timings = nullptr,
                                size_t workspace_budget = 0, int mode = BATCH_AUTO);
+// prove_witness_batch behind a check of every witness (R1cs::which_is_unsatisfied over the whole batch first; the prover
+// then uploads the satisfied witnesses once more): a witness with an unsatisfied constraint gets no proof, the others go
+// through prove_witness_batch_codes unchanged - proof j is exactly what prove_witness returns for witness j.
+// The vector form throws SynthesisError(BH_ERR_UNSATISFIABLE, "Unsatisfiable") for the first such witness, after
+// *first_unsatisfied (optional) has received every witness' entry; the codes form writes codes[j] = BH_ERR_UNSATISFIABLE
+// and first_unsatisfied[j] (optional, k words).  timings->synthesis_ms = the pre-pass in host milliseconds.
+std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
+                                               const std::vector<std::pair<Fr, Fr>> &rs,
+                                               std::vector<uint32_t> *first_unsatisfied = nullptr, ProveTimings *timings = nullptr,
+                                               size_t workspace_budget = 0, int mode = BATCH_AUTO);
+void prove_witness_batch_checked_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
+                                       const Fr *s, Proof *proofs, int *codes, uint32_t *first_unsatisfied,
+                                       ProveTimings *timings = nullptr, size_t workspace_budget = 0, int mode = BATCH_AUTO);
 
 // ---- one caller, proofs back to back ---------------------------------------------------------------------------
 // create_proof is synthesis on the host followed by the device part (prover.rs:182-215, then :217-360).  A single

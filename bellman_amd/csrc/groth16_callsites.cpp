@@ -342,11 +342,21 @@ extern "C" int bh_test_groth16_prove_witness_batch_budget(bh_params *params, con
                                                           void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4) {
   return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, workspace_budget, groth16::BATCH_GROUPED);
 }
-// the same with the path of the caller's choice: 0 BATCH_AUTO, 1 BATCH_GROUPED, 2 BATCH_GROUPED_H (the batched h block)
+// the same with the path of the caller's choice: 0 BATCH_AUTO, 1 BATCH_GROUPED, 2 BATCH_GROUPED_H (the batched h block).
+// This hook keeps the modes it was published with - anything else is refused, as its tests pin; BATCH_GROUPED_HE has the
+// hook below.
 extern "C" int bh_test_groth16_prove_witness_batch_mode(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
                                                         const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
                                                         void *proofs_out, int32_t *rcs, size_t workspace_budget, int mode,
                                                         float *timings4) {
   if (mode < groth16::BATCH_AUTO || mode > groth16::BATCH_GROUPED_H) return BH_ERR_INVALID_ARG;
   return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, workspace_budget, mode);
+}
+// BATCH_GROUPED_HE: the grouped path with the batched h block AND the group's constraint evaluations as one
+// bh_r1cs_eval_many_dev (groth16.hpp)
+extern "C" int bh_test_groth16_prove_witness_batch_he(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                                      const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                                      void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4) {
+  return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, workspace_budget,
+                                     groth16::BATCH_GROUPED_HE);
 }

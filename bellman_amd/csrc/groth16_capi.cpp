@@ -195,6 +195,13 @@ int bh_groth16_prove_witness_batch(bh_params *params, const bh_r1cs *r1cs, const
   return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, 0);
 }
 
+int bh_groth16_prove_witness_batch_checked(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                           const void *aux, size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out,
+                                           int32_t *rcs, uint32_t *first_unsatisfied, float *timings4) {
+  return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, 0,
+                                     groth16::BATCH_AUTO, true, first_unsatisfied);
+}
+
 // ---- asynchronous proofs: the device part of a proof on a helper thread (groth16.hpp AsyncProof) ----------------------
 int bh_groth16_prove_assignment_async(bh_params *params, const void *a_evals, const void *b_evals, const void *c_evals,
                                       size_t n_constraints, const void *input_assignment, size_t n_inputs,

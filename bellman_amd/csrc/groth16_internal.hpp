@@ -26,6 +26,7 @@ inline void check(int rc) {
     case BH_ERR_UNEXPECTED_IDENTITY: throw bellman::SynthesisError(rc, "UnexpectedIdentity");
     case BH_ERR_UNEXPECTED_EOF: throw bellman::SynthesisError(rc, "IoError(UnexpectedEof): expected more bases from source");
     case BH_ERR_DEGREE_TOO_LARGE: throw bellman::SynthesisError(rc, "PolynomialDegreeTooLarge");
+    case BH_ERR_UNSATISFIABLE: throw bellman::SynthesisError(rc, "Unsatisfiable");
     default: throw std::runtime_error("bellman_hip: HIP/runtime failure (no CPU fallback)");
   }
 }
@@ -81,10 +82,11 @@ inline int run_guarded(const std::function<groth16::Proof()> &f, void *proof_out
   } catch (...) { return BH_ERR_HIP; }
 }
 
-// bh_groth16_prove_witness_batch, and the test library's twin with a workspace budget of its own (0: the default)
+// bh_groth16_prove_witness_batch (and _checked), and the test library's twin with a workspace budget of its own (0: the default)
 inline int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
                                        size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
-                                       float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO) {
+                                       float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO,
+                                       bool checked = false, uint32_t *first_unsatisfied = nullptr) {
   using namespace groth16;
   if (!params || !r1cs) return BH_ERR_INVALID_ARG;
   if (k && (!r || !s || !proofs_out || !rcs || (n_inputs && !inputs) || (n_aux && !aux))) return BH_ERR_INVALID_ARG;
@@ -103,7 +105,11 @@ inline int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, c
     for (size_t j = 0; j < k; j++) ws[j] = WitnessView{in_p + j * n_inputs, n_inputs, ax_p + j * n_aux, n_aux};
     std::vector<Proof> proofs(k);
     std::vector<int> codes(k, BH_OK);
-    prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
+    if (checked)   // bh_groth16_prove_witness_batch_checked: the check pre-pass, then the satisfied witnesses as below
+      prove_witness_batch_checked_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(),
+                                        first_unsatisfied, &tm, workspace_budget, mode);
+    else
+      prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
     for (size_t j = 0; j < k; j++) {
       char *out = (char *)proofs_out + j * 384;
       rcs[j] = codes[j];

@@ -569,6 +569,47 @@ struct ManyJobSet {   // as JobSet: every issued many-job is waited on even when
 // on the chain circuit, beyond the baseline's own spread at two shapes of eight (k = 16 at 2^16 and 2^18) - and at another
 // one (2^16, k = 4) in the run before.  No basis for a rule yet: it is "never", and the call runs the proofs in flight,
 // BATCH_IN_FLIGHT at a time.
+// The witnesses w[0 .. g) into two strided device buffers (strides = the vectors' lengths), on stream st.  With `coalesce`
+// and every host vector starting where the one before ends, ONE upload per vector kind; otherwise one per witness.
+static void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *d_in, void *d_aux, void *st, bool coalesce) {
+  const size_t n_in = w[0].n_inputs, n_aux = w[0].n_aux, in_stride = n_in * 32, aux_stride = n_aux * 32;
+  bool adjacent = coalesce;
+  for (size_t j = 0; adjacent && j + 1 < g; j++)
+    adjacent = w[j + 1].inputs == w[j].inputs + n_in && w[j + 1].aux == w[j].aux + n_aux;
+  if (adjacent) {
+    if (n_in) check(bh_dev_upload_on(ctx, d_in, w[0].inputs, g * in_stride, st));
+    if (n_aux) check(bh_dev_upload_on(ctx, d_aux, w[0].aux, g * aux_stride, st));
+    return;
+  }
+  for (size_t j = 0; j < g; j++) {
+    if (n_in) check(bh_dev_upload_on(ctx, (char *)d_in + j * in_stride, w[j].inputs, in_stride, st));
+    if (n_aux) check(bh_dev_upload_on(ctx, (char *)d_aux + j * aux_stride, w[j].aux, aux_stride, st));
+  }
+}
+
+// which_is_unsatisfied for k witnesses: groups whose device copies stay within `budget` bytes, one bh_r1cs_check_many_dev each
+static std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, const WitnessView *witnesses, size_t k, size_t budget) {
+  for (size_t j = 0; j < k; j++)
+    if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
+      throw std::invalid_argument("witness does not have the shape of the captured circuit");
+  if (!ctx) throw std::invalid_argument("the R1cs handle was adopted without its context");
+  std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
+  if (!k) return first_bad;
+  const size_t in_stride = r1cs.num_inputs * 32, aux_stride = r1cs.num_aux * 32;
+  const size_t group = std::min(k, std::max<size_t>(budget / (in_stride + aux_stride + 4), 1));
+  for (size_t first = 0; first < k; first += group) {
+    const size_t g = std::min(group, k - first);
+    DevBuf d_in(ctx, g * in_stride + 32), d_aux(ctx, g * aux_stride + 32), d_bad(ctx, g * sizeof(uint32_t));
+    ProofStream ps(ctx);
+    StreamDrain drain{ps};
+    upload_witnesses(ctx, witnesses + first, g, d_in.p, d_aux.p, ps.st, true);
+    check(bh_r1cs_check_many_dev(ctx, r1cs.handle, d_in.p, in_stride, d_aux.p, aux_stride, g, (uint32_t *)d_bad.p, ps.st));
+    check(bh_stream_synchronize(ctx, ps.st));
+    check(bh_dev_download(ctx, first_bad.data() + first, d_bad.p, g * sizeof(uint32_t)));
+  }
+  return first_bad;
+}
+
 static bool grouped_batch_wins(size_t n_constraints, size_t k) {
   (void)n_constraints; (void)k;
   return false;
@@ -582,7 +623,7 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   if (tm) *tm = ProveTimings{0, 0, 0, 0};
   if (!k) return;
   const double t0 = now_ms();
-  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && !grouped_batch_wins(r1cs.num_constraints, k)) {
+  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && mode != BATCH_GROUPED_HE && !grouped_batch_wins(r1cs.num_constraints, k)) {
     // k proofs by the single-proof path, BATCH_IN_FLIGHT of them in flight (device memory stays bounded), waited in order
     std::vector<std::unique_ptr<AsyncProof>> jobs(k);
     auto finish = [&](size_t j) {
@@ -619,8 +660,9 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   // and the FFT scratch, which the h blocks of a group share (they run one after the other on one stream)
   const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
   const size_t vec = m * 32;
-  // (BATCH_GROUPED_H: every witness has its own a, b, c and scratch vector - its h blocks run as ONE batched h block)
-  const bool batched_h = mode == BATCH_GROUPED_H;
+  // (BATCH_GROUPED_H: every witness has its own a, b, c and scratch vector - its h blocks run as ONE batched h block;
+  // BATCH_GROUPED_HE: the same, and the group's constraint evaluations run as ONE bh_r1cs_eval_many_dev)
+  const bool many_eval = mode == BATCH_GROUPED_HE, batched_h = mode == BATCH_GROUPED_H || many_eval;
   size_t group = batched_h ? std::max<size_t>(budget / (4 * vec), 1) : budget / vec > 3 ? budget / vec - 3 : 1;
   if (group > k) group = k;
   if (group > 4096) group = 4096;
@@ -668,12 +710,8 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     for (bh_msm_job *&j : in_jobs) jobs.track(&j);
     ManyJobSet many_jobs;
     for (bh_msm_many_job **j : {&l_job, &a_job, &b1_job, &b2_job, &h_job}) many_jobs.track(j);
-    // 1. the witnesses, one strided buffer each
-    for (size_t j = 0; j < g; j++) {
-      const WitnessView &w = witnesses[first + j];
-      if (n_in) check(bh_dev_upload_on(ctx, (char *)d_in.p + j * in_stride, w.inputs, in_stride, ps.st));
-      if (n_aux) check(bh_dev_upload_on(ctx, (char *)d_aux.p + j * aux_stride, w.aux, aux_stride, ps.st));
-    }
+    // 1. the witnesses, one strided buffer each (BATCH_GROUPED_HE: in one upload each where the host vectors are adjacent)
+    upload_witnesses(ctx, witnesses + first, g, d_in.p, d_aux.p, ps.st, many_eval);
     // 2. four many-jobs over the aux vectors and the shared bases and densities, ordered after the uploads
     // G2 first: the longest job
     check(bh_msm_many_async_dev(ctx, params.b_g2, b_in_total, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_b_aux,
@@ -685,7 +723,9 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
                                 dens_b_aux ? n_aux : 0, nullptr, ps.st, &b1_job));
     // 3. the h block per witness, on one stream, into the group's strided coefficient vectors; then the H many-job,
     // ordered after them
-    for (size_t j = 0; j < g; j++) {
+    if (many_eval)
+      check(bh_r1cs_eval_many_dev(ctx, r1cs.handle, d_in.p, in_stride, d_aux.p, aux_stride, g, da.p, db.p, dc.p, vec, log_m, ps.st));
+    for (size_t j = 0; j < g && !many_eval; j++) {
       void *a_j = (char *)da.p + j * vec;
       const size_t bc = batched_h ? j * vec : 0;
       check(bh_r1cs_eval_dev(ctx, r1cs.handle, (char *)d_in.p + j * in_stride, (char *)d_aux.p + j * aux_stride, a_j,
@@ -763,6 +803,50 @@ std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, con
   std::vector<Proof> proofs(k);
   std::vector<int> codes(k, BH_OK);
   prove_witness_batch_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(), tm, workspace_budget, mode);
+  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
+  return proofs;
+}
+
+void prove_witness_batch_checked_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
+                                       const Fr *s, Proof *proofs, int *codes, uint32_t *first_unsatisfied, ProveTimings *tm,
+                                       size_t workspace_budget, int mode) {
+  if (tm) *tm = ProveTimings{0, 0, 0, 0};
+  const double t0 = now_ms();
+  const std::vector<uint32_t> first_bad =
+      check_witnesses(params.ctx, r1cs, witnesses, k, workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES);
+  const double pre_ms = now_ms() - t0;
+  if (first_unsatisfied)
+    for (size_t j = 0; j < k; j++) first_unsatisfied[j] = first_bad[j];
+  // the satisfied witnesses, in order, through the unchecked batch
+  std::vector<size_t> good;
+  for (size_t j = 0; j < k; j++) {
+    if (first_bad[j] == BH_R1CS_SATISFIED) good.push_back(j);
+    else codes[j] = BH_ERR_UNSATISFIABLE;
+  }
+  const size_t n = good.size();
+  std::vector<WitnessView> ws(n);
+  std::vector<Fr> rr(n), ss(n);
+  std::vector<Proof> ps(n);
+  std::vector<int> cs(n, BH_OK);
+  for (size_t i = 0; i < n; i++) { ws[i] = witnesses[good[i]]; rr[i] = r[good[i]]; ss[i] = s[good[i]]; }
+  prove_witness_batch_codes(r1cs, params, ws.data(), n, rr.data(), ss.data(), ps.data(), cs.data(), tm, workspace_budget, mode);
+  for (size_t i = 0; i < n; i++) { proofs[good[i]] = ps[i]; codes[good[i]] = cs[i]; }
+  if (tm) { tm->synthesis_ms = (float)pre_ms; tm->total_ms = (float)(now_ms() - t0); }
+}
+
+std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
+                                               const std::vector<std::pair<Fr, Fr>> &rs, std::vector<uint32_t> *first_unsatisfied,
+                                               ProveTimings *tm, size_t workspace_budget, int mode) {
+  if (witnesses.size() != rs.size()) throw std::invalid_argument("one (r, s) per witness");
+  const size_t k = witnesses.size();
+  std::vector<Fr> r(k), s(k);
+  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
+  std::vector<Proof> proofs(k);
+  std::vector<int> codes(k, BH_OK);
+  std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
+  prove_witness_batch_checked_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(),
+                                    first_bad.data(), tm, workspace_budget, mode);
+  if (first_unsatisfied) *first_unsatisfied = first_bad;
   for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
   return proofs;
 }
@@ -894,7 +978,7 @@ double capture_check_for_tests(Circuit &shape_of, Circuit &proved, size_t out4[4
   return ms;
 }
 
-R1cs::R1cs(Circuit &shape_of, bh_ctx *ctx) {
+R1cs::R1cs(Circuit &shape_of, bh_ctx *ctx) : ctx(ctx) {
   ShapeAssembly cs;
   capture_shape(shape_of, cs);
   num_inputs = cs.num_inputs; num_aux = cs.num_aux; num_constraints = cs.row_ptr[0].size() - 1;
@@ -902,8 +986,11 @@ R1cs::R1cs(Circuit &shape_of, bh_ctx *ctx) {
   for (int m = 0; m < 3; m++) abc[m] = bh_csr{cs.row_ptr[m].data(), cs.var[m].data(), cs.coeff[m].data()};
   check(bh_r1cs_create(ctx, num_inputs, num_aux, num_constraints, abc, cs.coeffs.data(), cs.coeffs.size(), &handle));
 }
-R1cs::R1cs(bh_r1cs *existing) : handle(existing) {
+R1cs::R1cs(bh_r1cs *existing, bh_ctx *ctx) : handle(existing), ctx(ctx) {
   check(bh_r1cs_shape(existing, &num_inputs, &num_aux, &num_constraints));
+}
+std::vector<uint32_t> R1cs::which_is_unsatisfied(const WitnessView *witnesses, size_t k) const {
+  return check_witnesses(ctx, *this, witnesses, k, BATCH_WORKSPACE_BYTES);
 }
 R1cs::~R1cs() { bh_r1cs_release(handle); }
 

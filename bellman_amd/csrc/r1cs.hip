@@ -9,6 +9,7 @@
 // function of the matrices alone and are computed here once.
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -106,6 +107,232 @@ __global__ void __launch_bounds__(256) r1cs_long_rows_kernel(R1csEvalArgs a) {
   }
   if (threadIdx.x == 0) st_fr16(a.out[mat] + row, part[0]);
 }
+
+// ---- k witnesses against one set of matrices ------------------------------------------------------------------------------
+// The matrices do not depend on the witness, so a lane that owns a row reads every term record and every coefficient ONCE
+// for a tile of T = R1CS_MANY_TILE witnesses and keeps T accumulators; the tiles over k are the grid's second dimension.
+// Witness j is inputs + j * in_stride, aux + j * aux_stride (bytes), output vector j of a matrix out[mat] + j * out_stride.
+struct R1csManyArgs {
+  const u32 *row_ptr[3];
+  const uint2 *terms[3];
+  char *out[3];
+  const fr_t *coeffs;
+  const char *inputs, *aux;
+  u64 in_stride, aux_stride, out_stride;
+  u32 n_inputs, k;
+  u64 n_constraints, m;
+  const uint2 *long_rows;   // eval: (matrix, row) of the rows left to r1cs_long_rows_many_kernel
+  const u32 *long_cons;     // check: the constraints left to r1cs_check_long_many_kernel
+  u32 *first_bad;           // check: one word per witness, BH_R1CS_SATISFIED before the launch
+};
+
+// The witnesses of one tile as wave-uniform base pointers.  A ragged last tile repeats its last witness in the slots at and
+// beyond n: those slots are computed and never stored or reported, and the term loop needs no branch on the slot.
+template <u32 T>
+struct TileWitness {
+  const fr_t *in[T], *aux[T];
+  u32 first, n;
+  __device__ __forceinline__ TileWitness(const R1csManyArgs &a, u32 tile) {
+    first = tile * T;
+    n = a.k - first < T ? a.k - first : T;
+#pragma unroll
+    for (u32 i = 0; i < T; i++) {
+      const u64 j = first + (i < n ? i : n - 1);
+      in[i] = reinterpret_cast<const fr_t *>(a.inputs + j * a.in_stride);
+      aux[i] = reinterpret_cast<const fr_t *>(a.aux + j * a.aux_stride);
+    }
+  }
+};
+
+// acc[i] += sum over the terms lo, lo + step, ... < hi of one row of coefficient * witness i's variable
+template <u32 T>
+__device__ __forceinline__ void row_terms_many(fr_t (&acc)[T], const R1csManyArgs &a, const TileWitness<T> &w, u32 mat, u32 lo,
+                                               u32 hi, u32 step) {
+  for (u32 t = lo; t < hi; t += step) {
+    const uint2 term = a.terms[mat][t];
+    const bool is_input = term.x < a.n_inputs;
+    const u32 idx = is_input ? term.x : term.x - a.n_inputs;
+    fr_t c;
+    if (term.y != 0) c = ld_fr16(a.coeffs + term.y);   // coefficient 1 is by far the most common one (prover.rs:47-52)
+#pragma unroll
+    for (u32 i = 0; i < T; i++) {
+      fr_t v = ld_fr16((is_input ? w.in[i] : w.aux[i]) + idx);
+      if (term.y != 0) fe_mul(v, v, c);
+      fe_add(acc[i], acc[i], v);
+    }
+  }
+}
+
+template <u32 T>
+__device__ __forceinline__ void zero_many(fr_t (&acc)[T]) {
+#pragma unroll
+  for (u32 i = 0; i < T; i++) fe_zero(acc[i]);
+}
+
+// acc[i] <- the sum of acc[i] over the 256 lanes of the workgroup, in every lane
+template <u32 T>
+__device__ __forceinline__ void block_sum_many(fr_t (&acc)[T], fr_t *part) {
+#pragma unroll
+  for (u32 i = 0; i < T; i++) {
+    __syncthreads();   // the readers of the slot before are done with part[0]
+    part[threadIdx.x] = acc[i];
+    for (u32 off = 128; off >= 1; off >>= 1) {
+      __syncthreads();
+      if (threadIdx.x < off) {
+        fr_t x = part[threadIdx.x], y = part[threadIdx.x + off];
+        fe_add(x, x, y);
+        part[threadIdx.x] = x;
+      }
+    }
+    __syncthreads();
+    acc[i] = part[0];
+  }
+}
+
+template <u32 T>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r1cs_eval_many_kernel(R1csManyArgs a) {
+  const TileWitness<T> w(a, blockIdx.y);
+  const u64 total = 3 * a.m;
+  for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (u64)gridDim.x * blockDim.x) {
+    const u32 mat = (u32)(g / a.m);
+    const u64 row = g - (u64)mat * a.m;
+    fr_t acc[T];
+    zero_many(acc);
+    if (row < a.n_constraints) {
+      const u32 lo = a.row_ptr[mat][row], hi = a.row_ptr[mat][row + 1];
+      if (hi - lo > LONG_ROW) continue;   // written by r1cs_long_rows_many_kernel
+      row_terms_many(acc, a, w, mat, lo, hi, 1);
+    }
+#pragma unroll
+    for (u32 i = 0; i < T; i++)
+      if (i < w.n) st_fr16(reinterpret_cast<fr_t *>(a.out[mat] + (u64)(w.first + i) * a.out_stride) + row, acc[i]);
+  }
+}
+
+// one workgroup per (long row, tile of witnesses)
+template <u32 T>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r1cs_long_rows_many_kernel(R1csManyArgs a) {
+  __shared__ fr_t part[256];
+  const TileWitness<T> w(a, blockIdx.y);
+  const uint2 job = a.long_rows[blockIdx.x];
+  const u32 mat = job.x, row = job.y;
+  fr_t acc[T];
+  zero_many(acc);
+  row_terms_many(acc, a, w, mat, a.row_ptr[mat][row] + threadIdx.x, a.row_ptr[mat][row + 1], 256);
+  block_sum_many(acc, part);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (u32 i = 0; i < T; i++)
+      if (i < w.n) st_fr16(reinterpret_cast<fr_t *>(a.out[mat] + (u64)(w.first + i) * a.out_stride) + row, acc[i]);
+  }
+}
+
+// The check, fused: a lane owns one CONSTRAINT and a tile of witnesses, forms <A_i, w> <B_i, w> and <C_i, w> and compares
+// them as field elements (both sides are reduced Montgomery forms: equal values are equal words); nothing but first_bad is
+// written.  A lane keeps the smallest failing row per witness; the wave takes the minimum over its lanes and issues ONE
+// atomicMin per wave and witness - a minimum, so the result does not depend on the order of arrival.
+template <u32 T>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r1cs_check_many_kernel(R1csManyArgs a) {
+  __shared__ fr_t keep[T][256];
+  const TileWitness<T> w(a, blockIdx.y);
+  u32 bad[T];
+#pragma unroll
+  for (u32 i = 0; i < T; i++) bad[i] = BH_R1CS_SATISFIED;
+  // (a constraint with a long part is judged by r1cs_check_long_many_kernel; the lane meets the long part when it comes to it
+  // and drops the constraint there - the row bounds of the parts behind it need not stay in registers for the test)
+  // Only ONE set of T accumulators is in registers at a time: a, and then a * b, wait in the lane's own LDS slots while the
+  // next part is summed (no other lane touches them: no barrier) - with two sets in registers the kernel does not fit 128.
+  for (u64 row = (u64)blockIdx.x * blockDim.x + threadIdx.x; row < a.n_constraints; row += (u64)gridDim.x * blockDim.x) {
+    fr_t x[T];
+    u32 lo = a.row_ptr[0][row], hi = a.row_ptr[0][row + 1];
+    if (hi - lo > LONG_ROW) continue;
+    zero_many(x);
+    row_terms_many(x, a, w, 0, lo, hi, 1);
+#pragma unroll
+    for (u32 i = 0; i < T; i++) keep[i][threadIdx.x] = x[i];
+    lo = a.row_ptr[1][row]; hi = a.row_ptr[1][row + 1];
+    if (hi - lo > LONG_ROW) continue;
+    zero_many(x);
+    row_terms_many(x, a, w, 1, lo, hi, 1);
+#pragma unroll
+    for (u32 i = 0; i < T; i++) {
+      fr_t p = keep[i][threadIdx.x];
+      fe_mul(p, p, x[i]);
+      keep[i][threadIdx.x] = p;
+    }
+    lo = a.row_ptr[2][row]; hi = a.row_ptr[2][row + 1];
+    if (hi - lo > LONG_ROW) continue;
+    zero_many(x);
+    row_terms_many(x, a, w, 2, lo, hi, 1);
+#pragma unroll
+    for (u32 i = 0; i < T; i++) {
+      const fr_t p = keep[i][threadIdx.x];
+      if (!fe_eq(p, x[i]) && (u32)row < bad[i]) bad[i] = (u32)row;
+    }
+  }
+#pragma unroll
+  for (u32 i = 0; i < T; i++) {
+    u32 v = bad[i];
+    for (u32 off = 32; off >= 1; off >>= 1) {
+      const u32 o = __shfl_xor(v, off);
+      v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0 && i < w.n && v != BH_R1CS_SATISFIED) atomicMin(a.first_bad + w.first + i, v);
+  }
+}
+
+// one workgroup per (constraint with a long A, B or C row, tile of witnesses): the three parts block-summed, then the compare
+template <u32 T>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r1cs_check_long_many_kernel(R1csManyArgs a) {
+  __shared__ fr_t part[256];
+  const TileWitness<T> w(a, blockIdx.y);
+  const u32 row = a.long_cons[blockIdx.x];
+  fr_t ab[T], x[T];
+  zero_many(ab);
+  row_terms_many(ab, a, w, 0, a.row_ptr[0][row] + threadIdx.x, a.row_ptr[0][row + 1], 256);
+  block_sum_many(ab, part);
+  zero_many(x);
+  row_terms_many(x, a, w, 1, a.row_ptr[1][row] + threadIdx.x, a.row_ptr[1][row + 1], 256);
+  block_sum_many(x, part);
+#pragma unroll
+  for (u32 i = 0; i < T; i++) fe_mul(ab[i], ab[i], x[i]);
+  zero_many(x);
+  row_terms_many(x, a, w, 2, a.row_ptr[2][row] + threadIdx.x, a.row_ptr[2][row + 1], 256);
+  block_sum_many(x, part);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (u32 i = 0; i < T; i++)
+      if (i < w.n && !fe_eq(ab[i], x[i])) atomicMin(a.first_bad + w.first + i, row);
+  }
+}
+
+static std::vector<u32> find_long_constraints(const std::vector<u32> *row_ptr_of_3) {
+  std::vector<u32> v;
+  for (size_t r = 0; r + 1 < row_ptr_of_3[0].size(); r++) {
+    bool is_long = false;
+    for (u32 m = 0; m < 3; m++) is_long |= row_ptr_of_3[m][r + 1] - row_ptr_of_3[m][r] > LONG_ROW;
+    if (is_long) v.push_back((u32)r);
+  }
+  return v;
+}
+
+// what both k-witness entry points refuse, and the arguments they share
+static bool many_strides_ok(const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev, size_t aux_stride) {
+  return in_stride % 32 == 0 && aux_stride % 32 == 0 && in_stride >= r->n_inputs * 32 && aux_stride >= r->n_aux * 32 &&
+         (inputs_dev || !r->n_inputs) && (aux_dev || !r->n_aux);
+}
+static void many_args(R1csManyArgs &a, const bh_r1cs *r, size_t in_stride, size_t aux_stride) {
+  for (int m = 0; m < 3; m++) { a.row_ptr[m] = r->row_ptr[m]; a.terms[m] = r->terms[m]; a.out[m] = nullptr; }
+  a.coeffs = r->coeffs;
+  a.in_stride = in_stride; a.aux_stride = aux_stride; a.out_stride = 0;
+  a.n_inputs = (u32)r->n_inputs;
+  a.n_constraints = r->n_constraints;
+  a.m = 0;
+  a.long_rows = r->long_rows;
+  a.long_cons = r->long_cons;
+  a.first_bad = nullptr;
+}
+constexpr size_t MANY_MAX_TILES = 65535;   // a grid's second dimension
 
 static std::vector<uint2> find_long_rows(const std::vector<u32> *row_ptr_of_3) {
   std::vector<uint2> v;
@@ -232,6 +459,12 @@ int bh_r1cs_create(bh_ctx *ctx, size_t n_inputs, size_t n_aux, size_t n_constrai
     rc = upload_vec(ctx, &r->long_rows, lr.data(), lr.size());
     if (rc == BH_OK && hipStreamSynchronize(ctx->c.stream) != hipSuccess) rc = BH_ERR_HIP;   // `lr` is a local
   }
+  if (rc == BH_OK) {
+    const std::vector<u32> lc = find_long_constraints(r->h_row_ptr);
+    r->n_long_cons = (u32)lc.size();
+    rc = upload_vec(ctx, &r->long_cons, lc.data(), lc.size());
+    if (rc == BH_OK && hipStreamSynchronize(ctx->c.stream) != hipSuccess) rc = BH_ERR_HIP;   // `lc` is a local
+  }
   if (rc == BH_OK) rc = upload_vec(ctx, &r->coeffs, cf, n_coeffs);
   if (rc == BH_OK && hipStreamSynchronize(ctx->c.stream) != hipSuccess) rc = BH_ERR_HIP;
   if (rc != BH_OK) { bh_r1cs_release(r); return rc; }
@@ -254,6 +487,7 @@ void bh_r1cs_release(bh_r1cs *r) {
   r->ctx->c.pool.release(r->coeff_info);
   r->ctx->c.pool.release(r->long_rows);
   r->ctx->c.pool.release(r->t_long_rows);
+  r->ctx->c.pool.release(r->long_cons);
   r->ctx->c.pool.release(r->coeffs);
   delete r;
 }
@@ -288,6 +522,111 @@ int bh_r1cs_eval_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, cons
   a.m = u64(1) << log_m;
   a.long_rows = r->long_rows;
   return launch_eval(ctx, a, r->n_long, stream ? (hipStream_t)stream : ctx->c.stream);
+}
+
+int bh_r1cs_eval_many_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev,
+                          size_t aux_stride, size_t k, void *a_dev, void *b_dev, void *c_dev, size_t out_stride, uint32_t log_m,
+                          void *stream) {
+  constexpr u32 T = R1CS_MANY_TILE;
+  if (!ctx || !r || log_m >= 32 || (size_t(1) << log_m) < r->n_constraints) return BH_ERR_INVALID_ARG;
+  if (!many_strides_ok(r, inputs_dev, in_stride, aux_dev, aux_stride) || out_stride % 32 || out_stride < (size_t(32) << log_m))
+    return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  if (!a_dev || !b_dev || !c_dev) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->c.stream;
+  R1csManyArgs a;
+  many_args(a, r, in_stride, aux_stride);
+  a.out_stride = out_stride;
+  a.m = u64(1) << log_m;
+  for (size_t first = 0; first < k; first += MANY_MAX_TILES * T) {
+    const size_t n = std::min<size_t>(k - first, MANY_MAX_TILES * T);
+    const u32 tiles = (u32)((n + T - 1) / T);
+    a.k = (u32)n;
+    a.inputs = (const char *)inputs_dev + first * in_stride;
+    a.aux = (const char *)aux_dev + first * aux_stride;
+    a.out[0] = (char *)a_dev + first * out_stride;
+    a.out[1] = (char *)b_dev + first * out_stride;
+    a.out[2] = (char *)c_dev + first * out_stride;
+    const u64 blocks = (3 * a.m + 255) / 256, cap = std::max<u64>((u64)ctx->c.num_cus * 16 / tiles, 1);
+    hipLaunchKernelGGL(r1cs_eval_many_kernel<T>, dim3((u32)std::min(blocks, cap), tiles), dim3(256), 0, st, a);
+    BH_HIP_CHECK(hipGetLastError());
+    if (r->n_long) {
+      hipLaunchKernelGGL(r1cs_long_rows_many_kernel<T>, dim3(r->n_long, tiles), dim3(256), 0, st, a);
+      BH_HIP_CHECK(hipGetLastError());
+    }
+  }
+  return BH_OK;
+}
+
+int bh_r1cs_check_many_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev,
+                           size_t aux_stride, size_t k, uint32_t *first_bad_dev, void *stream) {
+  constexpr u32 T = R1CS_MANY_TILE;
+  if (!ctx || !r || !many_strides_ok(r, inputs_dev, in_stride, aux_dev, aux_stride)) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  if (!first_bad_dev) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->c.stream;
+  BH_HIP_CHECK(hipMemsetAsync(first_bad_dev, 0xFF, k * sizeof(uint32_t), st));   // BH_R1CS_SATISFIED in every word
+  if (!r->n_constraints) return BH_OK;
+  R1csManyArgs a;
+  many_args(a, r, in_stride, aux_stride);
+  for (size_t first = 0; first < k; first += MANY_MAX_TILES * T) {
+    const size_t n = std::min<size_t>(k - first, MANY_MAX_TILES * T);
+    const u32 tiles = (u32)((n + T - 1) / T);
+    a.k = (u32)n;
+    a.inputs = (const char *)inputs_dev + first * in_stride;
+    a.aux = (const char *)aux_dev + first * aux_stride;
+    a.first_bad = first_bad_dev + first;
+    const u64 blocks = (a.n_constraints + 255) / 256, cap = std::max<u64>((u64)ctx->c.num_cus * 16 / tiles, 1);
+    hipLaunchKernelGGL(r1cs_check_many_kernel<T>, dim3((u32)std::min(blocks, cap), tiles), dim3(256), 0, st, a);
+    BH_HIP_CHECK(hipGetLastError());
+    if (r->n_long_cons) {
+      hipLaunchKernelGGL(r1cs_check_long_many_kernel<T>, dim3(r->n_long_cons, tiles), dim3(256), 0, st, a);
+      BH_HIP_CHECK(hipGetLastError());
+    }
+  }
+  return BH_OK;
+}
+
+int bh_r1cs_check_many(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_host, const void *aux_host, size_t k,
+                       uint32_t *first_bad_host) {
+  if (!ctx || !r) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  if (!first_bad_host || (r->n_inputs && !inputs_host) || (r->n_aux && !aux_host)) return BH_ERR_INVALID_ARG;
+  BH_HIP_CHECK(hipSetDevice(ctx->c.device));
+  const size_t in_bytes = r->n_inputs * 32, aux_bytes = r->n_aux * 32;
+  // groups of witnesses whose device copies stay within 1 GiB, at least one witness per group
+  const size_t group = std::min(k, std::max<size_t>((size_t(1) << 30) / (in_bytes + aux_bytes + 4), 1));
+  void *stream = nullptr;
+  int rc = bh_stream_create(ctx, &stream);   // a stream of its own: thread-safe
+  if (rc != BH_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  void *d_in = ctx->c.pool.acquire(group * in_bytes + 32), *d_aux = ctx->c.pool.acquire(group * aux_bytes + 32);
+  uint32_t *d_bad = (uint32_t *)ctx->c.pool.acquire(group * sizeof(uint32_t));
+  if (!d_in || !d_aux || !d_bad) rc = BH_ERR_HIP;
+  auto hip_ok = [&](hipError_t e) {
+    if (e != hipSuccess) {
+      fprintf(stderr, "[bellman_hip] bh_r1cs_check_many: %s\n", hipGetErrorString(e));
+      rc = BH_ERR_HIP;
+    }
+    return e == hipSuccess;
+  };
+  for (size_t first = 0; first < k && rc == BH_OK; first += group) {
+    const size_t g = std::min(group, k - first);
+    if (in_bytes && !hip_ok(hipMemcpyAsync(d_in, (const char *)inputs_host + first * in_bytes, g * in_bytes, hipMemcpyHostToDevice, st))) break;
+    if (aux_bytes && !hip_ok(hipMemcpyAsync(d_aux, (const char *)aux_host + first * aux_bytes, g * aux_bytes, hipMemcpyHostToDevice, st))) break;
+    rc = bh_r1cs_check_many_dev(ctx, r, d_in, in_bytes, d_aux, aux_bytes, g, d_bad, stream);
+    if (rc != BH_OK) break;
+    if (!hip_ok(hipMemcpyAsync(first_bad_host + first, d_bad, g * sizeof(uint32_t), hipMemcpyDeviceToHost, st))) break;
+    if (!hip_ok(hipStreamSynchronize(st))) break;   // the group's buffers are written again by the next one
+  }
+  (void)hipStreamSynchronize(st);
+  ctx->c.pool.release(d_in);
+  ctx->c.pool.release(d_aux);
+  ctx->c.pool.release(d_bad);
+  bh_stream_destroy(ctx, stream);
+  return rc;
 }
 
 // QAP polynomials at tau (generator.rs:369-387 eval_at_tau for every variable): at[v] = sum over the

@@ -10,6 +10,11 @@
 // ONE typically appears in every constraint, so its row of a transposed matrix has ~n terms.
 namespace bh {
 constexpr u32 LONG_ROW = 1024;
+// Witnesses per lane of the k-witness kernels (r1cs.hip: r1cs_eval_many_kernel, r1cs_check_many_kernel): a lane reads a term
+// record and its coefficient once and applies them to this many witnesses.  The largest of 2, 4, 8 at which clang reports no
+// scratch and at most 128 VGPRs for every one of those kernels (tools/kernel_resources.py r1cs.hip; the line is in DESIGN.md
+// 5.4.1): the kernels are bound by the latency of the witness gathers and want waves in flight.
+constexpr u32 R1CS_MANY_TILE = 2;
 }
 
 struct bh_r1cs {
@@ -28,6 +33,8 @@ struct bh_r1cs {
   bh::u32 n_long = 0;
   uint2 *t_long_rows = nullptr;                      // the same for the transposed matrices
   bh::u32 t_n_long = 0;
+  bh::u32 *long_cons = nullptr;                      // constraints with more than LONG_ROW terms in their A, B or C row
+  bh::u32 n_long_cons = 0;
   std::vector<bh::u32> h_row_ptr[3], h_var[3], h_coeff[3];
   std::mutex t_mu;
   bool t_ready = false;

@@ -10,6 +10,7 @@
 #include "point_read.cuh"
 #include "shard_cuts.hpp"
 #include "fft_plan.hpp"
+#include "r1cs_dev.hpp"
 
 namespace bh {
 template <class P>
@@ -334,3 +335,6 @@ void bh_test_pairing_host(size_t n, const void *g1_affine, const void *g2_affine
   }
 }
 }  // extern "C"
+
+// the witness tile of the k-witness constraint kernels (r1cs.hip)
+extern "C" uint32_t bh_test_r1cs_many_tile(void) { return bh::R1CS_MANY_TILE; }

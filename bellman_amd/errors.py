@@ -23,6 +23,15 @@ class UnconstrainedVariable(SynthesisError):
     """groth16/src/generator.rs:464-470"""
 
 
+class Unsatisfiable(SynthesisError):
+    """src/lib.rs:310: a witness does not satisfy a constraint of the circuit (prove_witness_batch(check=True));
+    `.index` is the first unsatisfied constraint where the caller knows it"""
+
+    def __init__(self, index=None):
+        super().__init__("unsatisfiable constraint system" if index is None else "constraint %d is not satisfied" % index)
+        self.index = index
+
+
 class InvalidData(IOError):
     """io::ErrorKind::InvalidData from Parameters::read / VerifyingKey::read (groth16/src/lib.rs:159-215,289-398)"""
 
@@ -67,6 +76,8 @@ def check(rc, what="bellman_hip call"):
         raise PointAtInfinity("point at infinity")
     if rc == 10:
         raise InvalidTranscript()
+    if rc == 11:
+        raise Unsatisfiable()
     if rc == -2:
         # the reference panics here (assert!), e.g. src/multiexp.rs:324-329, src/domain.rs:155,174
         raise AssertionError("%s: invalid argument (the reference panics)" % what)

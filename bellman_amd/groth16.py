@@ -11,7 +11,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .errors import UnexpectedEof, check
+from .errors import UnexpectedEof, Unsatisfiable, check
+
+_check_rc = check  # prove_witness_batch has a keyword argument named `check`
 
 Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _R = (1 << 256) % Q
@@ -500,6 +502,23 @@ class _Csr(ctypes.Structure):
     _fields_ = [("row_ptr", ctypes.c_void_p), ("var", ctypes.c_void_p), ("coeff", ctypes.c_void_p)]
 
 
+SATISFIED = 0xFFFFFFFF  # BH_R1CS_SATISFIED
+
+
+def _stacked(vectors, n, k, what):
+    """k witness vectors of n elements -> one [k, n, 4] uint64 Montgomery array (witness j at row j: the layout of the batch
+    entry points).  A [k, n, 4] uint64 array is taken as it is; a vector of the wrong length is refused."""
+    if isinstance(vectors, np.ndarray) and vectors.dtype == np.uint64 and vectors.ndim == 3 and vectors.shape[2] == 4:
+        if vectors.shape[1] != n:
+            check(-2, "%s (the witnesses do not have the shape of the captured circuit)" % what)
+        return np.ascontiguousarray(vectors)
+    arrs = [fr_to_mont_array(x if isinstance(x, np.ndarray) else list(x)) for x in vectors]
+    for j, a in enumerate(arrs):
+        if a.shape[0] != n:
+            check(-2, "%s (witness %d does not have the shape of the captured circuit)" % (what, j))
+    return np.ascontiguousarray(np.stack(arrs)) if n and k else np.zeros((k, 0, 4), dtype=np.uint64)
+
+
 class R1CS:
     """The circuit's A/B/C matrices registered on the device (bh_r1cs)."""
 
@@ -575,6 +594,59 @@ class R1CS:
             for d in bufs:
                 lib.bh_dev_free(ctx, d)
         return outs
+
+    def eval_many(self, inputs_list, aux_list):
+        """a, b, c evaluations of k witnesses in one call (bh_r1cs_eval_many_dev): three [k, m, 4] uint64 Montgomery arrays,
+        m = next power of two, row j exactly what eval returns for witness j - parity-test hook."""
+        lib = _lib.load()
+        ctx = self.worker.ctx
+        k = len(inputs_list)
+        assert len(aux_list) == k, "one aux vector per witness"
+        log_m = 0
+        while (1 << log_m) < self.num_constraints:
+            log_m += 1
+        m = 1 << log_m
+        ins, auxs = _stacked(inputs_list, self.num_inputs, k, "R1CS.eval_many"), _stacked(aux_list, self.num_aux, k, "R1CS.eval_many")
+        outs = [np.zeros((k, m, 4), dtype=np.uint64) for _ in range(3)]
+        if k == 0:
+            return outs
+        bufs = []
+        for nbytes in (ins.nbytes + 32, auxs.nbytes + 32, k * m * 32, k * m * 32, k * m * 32):
+            d = ctypes.c_void_p()
+            check(lib.bh_dev_alloc(ctx, nbytes, ctypes.byref(d)), "R1CS.eval_many")
+            bufs.append(d)
+        try:
+            for d, a in ((bufs[0], ins), (bufs[1], auxs)):
+                if a.nbytes:
+                    check(lib.bh_dev_upload(ctx, d, a.ctypes.data_as(ctypes.c_void_p), a.nbytes), "R1CS.eval_many")
+            check(lib.bh_r1cs_eval_many_dev(ctx, self._h, bufs[0], self.num_inputs * 32, bufs[1], self.num_aux * 32, k, bufs[2], bufs[3],
+                                            bufs[4], m * 32, log_m, None), "R1CS.eval_many")
+            for d, o in zip(bufs[2:], outs):
+                check(lib.bh_dev_download(ctx, o.ctypes.data_as(ctypes.c_void_p), d, o.nbytes), "R1CS.eval_many")
+        finally:
+            for d in bufs:
+                lib.bh_dev_free(ctx, d)
+        return outs
+
+    def which_is_unsatisfied(self, inputs_list, aux_list):
+        """TestConstraintSystem::which_is_unsatisfied (src/gadgets/test/mod.rs:254-272) for k witnesses in one GPU pass
+        (bh_r1cs_check_many): entry j is the index of the first constraint witness j = (inputs_list[j], aux_list[j]) does
+        not satisfy, or None.  Witnesses as prove_witness_batch takes them."""
+        lib = _lib.load()
+        k = len(inputs_list)
+        assert len(aux_list) == k, "one aux vector per witness"
+        ins = _stacked(inputs_list, self.num_inputs, k, "R1CS.which_is_unsatisfied")
+        auxs = _stacked(aux_list, self.num_aux, k, "R1CS.which_is_unsatisfied")
+        if k == 0:
+            return []
+        bad = np.zeros(k, dtype=np.uint32)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib.bh_r1cs_check_many(self.worker.ctx, self._h, p(ins), p(auxs), k, p(bad)), "R1CS.which_is_unsatisfied")
+        return [None if int(b) == SATISFIED else int(b) for b in bad]
+
+    def is_satisfied(self, input_assignment, aux_assignment):
+        """TestConstraintSystem::is_satisfied for one witness"""
+        return self.which_is_unsatisfied([input_assignment], [aux_assignment])[0] is None
 
     def eval_transposed_points(self, group, matrix, lagrange, accumulate_into=None, stream=None):
         """The raw group-valued product (bh_r1cs_eval_transposed_points_dev): out[v] = sum_j coeff * lagrange[j] over the
@@ -659,7 +731,8 @@ def prove_witness(r1cs, params, input_assignment, aux_assignment, r, s, timings=
     return Proof(out)
 
 
-def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None, _mode=None, _codes=None):
+def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None, _mode=None, _codes=None,
+                        check=False, _first_unsatisfied=None):
     """k proofs of ONE circuit in one call (bh_groth16_prove_witness_batch): witness j = (inputs_list[j], aux_list[j]),
     blinding (rs[j], ss[j]) -> [Proof], each exactly what prove_witness returns for that witness.  inputs_list / aux_list:
     lists of integer lists or [n, 4] Montgomery arrays, or one [k, n, 4] uint64 array each (no copy is made then).  A witness of the wrong
@@ -668,32 +741,37 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     grouped path - many-jobs over groups of witnesses that fit that many bytes of h-block workspace, 0 = the default 1 GiB -
     instead of keeping the proofs in flight.  _mode: the twin that takes the path of groth16.hpp's BATCH_* modes - 1 the
     grouped path, 2 the grouped path with a batched h block (bh_h_poly_fr_many_dev_on), groups by 4 * g * m * 32 bytes.
-    _codes: a list that receives the per-proof return codes instead of the first failing one being raised.)"""
+    3 the same with the group's constraint evaluations as ONE bh_r1cs_eval_many_dev and one upload per vector kind
+    (bh_test_groth16_prove_witness_batch_he).
+    _codes: a list that receives the per-proof return codes instead of the first failing one being raised.)
+    check=True: every witness is first checked against the circuit's constraints on the GPU
+    (bh_groth16_prove_witness_batch_checked); a witness with an unsatisfied constraint gets no proof - errors.Unsatisfiable
+    (`.index` = the constraint) is raised for the first one, or with _codes its code is 11 and its slot None.
+    _first_unsatisfied: a list that receives, per witness, the first unsatisfied constraint or None."""
     lib = _lib.load()
+    check_witnesses, check = check, _check_rc
     k = len(inputs_list)
     assert len(aux_list) == k and len(rs) == k and len(ss) == k, "one aux vector and one (r, s) per witness"
-
-    def stacked(vectors, n):
-        # a [k, n, 4] uint64 array is the call's own layout (Montgomery limbs, witness j at row j): taken as it is
-        if isinstance(vectors, np.ndarray) and vectors.dtype == np.uint64 and vectors.ndim == 3 and vectors.shape[2] == 4:
-            if vectors.shape[1] != n:
-                check(-2, "create_proof (the witnesses do not have the shape of the captured circuit)")
-            return np.ascontiguousarray(vectors)
-        arrs = [fr_to_mont_array(x if isinstance(x, np.ndarray) else list(x)) for x in vectors]
-        for j, a in enumerate(arrs):
-            if a.shape[0] != n:
-                check(-2, "create_proof (witness %d does not have the shape of the captured circuit)" % j)
-        return np.ascontiguousarray(np.stack(arrs)) if n and k else np.zeros((k, 0, 4), dtype=np.uint64)
-
-    ins, auxs = stacked(inputs_list, r1cs.num_inputs), stacked(aux_list, r1cs.num_aux)
+    assert not check_witnesses or (_mode is None and _workspace_budget is None), "the checked entry point has no test twin"
+    ins = _stacked(inputs_list, r1cs.num_inputs, k, "create_proof")
+    auxs = _stacked(aux_list, r1cs.num_aux, k, "create_proof")
     if k == 0:
+        if _first_unsatisfied is not None:
+            _first_unsatisfied[:] = []
         return []
     rr, sv = fr_to_mont_array(list(rs)), fr_to_mont_array(list(ss))
     out = np.zeros((k, 48), dtype=np.uint64)
     rcs = np.zeros(k, dtype=np.int32)
     tm = (ctypes.c_float * 4)()
     p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    if _mode is not None:
+    first_bad = np.full(k, SATISFIED, dtype=np.uint32)
+    if check_witnesses:
+        rc = lib.bh_groth16_prove_witness_batch_checked(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k, p(rr),
+                                                        p(sv), p(out), p(rcs), p(first_bad), tm)
+    elif _mode == 3:   # BATCH_GROUPED_HE has a hook of its own: the mode hook keeps refusing what it refused before
+        rc = lib.bh_test_groth16_prove_witness_batch_he(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k, p(rr), p(sv),
+                                                        p(out), p(rcs), _workspace_budget or 0, tm)
+    elif _mode is not None:
         rc = lib.bh_test_groth16_prove_witness_batch_mode(params._h, r1cs._h, p(ins), r1cs.num_inputs, p(auxs), r1cs.num_aux, k,
                                                           p(rr), p(sv), p(out), p(rcs), _workspace_budget or 0, _mode, tm)
     elif _workspace_budget is None:
@@ -705,10 +783,14 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     check(rc, "create_proof")
     if timings is not None:
         timings[:] = list(tm)
+    if _first_unsatisfied is not None:
+        _first_unsatisfied[:] = [None if int(b) == SATISFIED else int(b) for b in first_bad]
     if _codes is not None:
         _codes[:] = [int(c) for c in rcs]
         return [Proof(out[j].copy()) if rcs[j] == 0 else None for j in range(k)]
     for j in range(k):
+        if int(rcs[j]) == 11:
+            raise Unsatisfiable(int(first_bad[j]))
         check(int(rcs[j]), "create_proof")
     return [Proof(out[j].copy()) for j in range(k)]
 

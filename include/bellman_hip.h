@@ -39,6 +39,7 @@ extern "C" {
 #define BH_ERR_INVALID_VERIFYING_KEY 8 /* VerificationError::InvalidVerifyingKey  src/lib.rs:353-358 */
 #define BH_ERR_INVALID_PROOF 9       /* VerificationError::InvalidProof           src/lib.rs:353-358 */
 #define BH_ERR_INVALID_TRANSCRIPT 10  /* bh_powers_of_tau_verify: a consistency equation of the transcript fails (no reference twin) */
+#define BH_ERR_UNSATISFIABLE 11       /* SynthesisError::Unsatisfiable  src/lib.rs:310 */
 #define BH_ERR_HIP (-1)              /* HIP runtime failure (message on stderr) */
 #define BH_ERR_INVALID_ARG (-2)      /* the reference would panic (e.g. density length mismatch,
                                         src/multiexp.rs:324-329; length mismatch src/domain.rs:155,174) */
@@ -687,6 +688,33 @@ int bh_r1cs_density(const bh_r1cs *r, int which, const uint64_t **dev_words, con
  * (EvaluationDomain::from_coeffs padding, domain.rs:68).  Asynchronous on `stream`. */
 int bh_r1cs_eval_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, const void *aux_dev,
                      void *a_dev, void *b_dev, void *c_dev, uint32_t log_m, void *stream);
+/* ---- k witnesses of one circuit in one call: the evaluation above, and the CHECK that a witness satisfies the circuit -----
+ * (the reference: TestConstraintSystem::which_is_unsatisfied / is_satisfied, src/gadgets/test/mod.rs:254-272 - the first
+ * constraint in order with a * b != c; the provers above accept any witness of the right length and divide a * b - c by Z
+ * without asking whether it divides).  Witness j is inputs_dev + j * in_stride and aux_dev + j * aux_stride: strides in
+ * BYTES, multiples of 32 and at least the vector's length - the layout of bh_msm_many_async_dev and
+ * bh_h_poly_fr_many_dev_on.  A lane reads every term record and coefficient once per tile of witnesses, not once per
+ * witness.  BH_ERR_INVALID_ARG for a null handle or buffer, a stride below the vector's length or not a multiple of 32, and
+ * 2^log_m < n_constraints; k = 0 is BH_OK and launches nothing.
+ *   bh_r1cs_eval_many_dev   a/b/c_dev + j * out_stride (out_stride >= 2^log_m * 32) receive exactly what bh_r1cs_eval_dev
+ *                           writes for witness j, zero padding up to 2^log_m included; nothing beyond 2^log_m records of a
+ *                           vector is written.  Asynchronous on `stream`.
+ *   bh_r1cs_check_many_dev  first_bad_dev[j] = the index of the first constraint witness j does not satisfy, or
+ *                           BH_R1CS_SATISFIED.  No a, b or c vector is written: the call needs no workspace.  Asynchronous
+ *                           on `stream`.
+ *   bh_r1cs_check_many      the same from the host: witness j at inputs_host + j * n_inputs * 32 and aux_host + j * n_aux *
+ *                           32, uploaded in groups that stay within 1 GiB of device memory.  Synchronous, on a stream of its
+ *                           own: thread-safe.
+ * When to call it: before bh_groth16_prove_witness* whenever the witness comes from code that is not yet trusted - a wrong
+ * wire otherwise yields a well-formed proof that fails verification, and nothing names the constraint. */
+#define BH_R1CS_SATISFIED 0xFFFFFFFFu /* n_constraints < 2^32, so never an index */
+int bh_r1cs_eval_many_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev,
+                          size_t aux_stride, size_t k, void *a_dev, void *b_dev, void *c_dev, size_t out_stride,
+                          uint32_t log_m, void *stream);
+int bh_r1cs_check_many_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev,
+                           size_t aux_stride, size_t k, uint32_t *first_bad_dev, void *stream);
+int bh_r1cs_check_many(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_host, const void *aux_host, size_t k,
+                       uint32_t *first_bad_host);
 /* Parameter generation (groth16/src/generator.rs:247-462) - device building blocks:
  *   bh_fr_powers_dev             out[i] = scale * g^i           (:249-263 powers of tau; :266-296 with t(tau)/delta folded in)
  *   bh_r1cs_eval_transposed_dev  at/bt/ct[v] = QAP polynomial of variable v at tau (:369-387) from the
@@ -895,6 +923,16 @@ int bh_groth16_prove_witness(bh_params *params, const bh_r1cs *r1cs, const void 
 int bh_groth16_prove_witness_batch(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
                                    const void *aux, size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out,
                                    int32_t *rcs, float *timings4);
+/* bh_groth16_prove_witness_batch behind a check of every witness (bh_r1cs_check_many_dev over the whole batch, in groups
+ * within the workspace budget): for a witness with an unsatisfied constraint rcs[j] = BH_ERR_UNSATISFIABLE, proofs_out +
+ * 384 j is all zero and first_unsatisfied[j] (k words, may be NULL) is the constraint's index; the satisfied witnesses are
+ * handed to bh_groth16_prove_witness_batch's path unchanged, so every other proof is byte-identical to
+ * bh_groth16_prove_witness for its witness, and its first_unsatisfied[j] is BH_R1CS_SATISFIED.  The pre-pass uploads the
+ * witnesses ONCE MORE than the unchecked call (the prover uploads the satisfied ones again); its price is measured in
+ * profiles/r1cs_many_bench.json.  timings4[0] = the pre-pass in host milliseconds, the rest as the unchecked call. */
+int bh_groth16_prove_witness_batch_checked(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                           const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                           void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4);
 /* ---- one caller, proofs back to back: create_proof split at the synthesis / device boundary -----------------
  * The reference's create_proof is synthesis on the host (groth16/src/prover.rs:182-215) followed by the device part
  * (:217-360); a single caller that proves in a loop leaves the GPU idle during every synthesis and the host idle during

@@ -463,6 +463,12 @@ int bh_test_groth16_prove_witness_batch_budget(bh_params *params, const bh_r1cs 
 int bh_test_groth16_prove_witness_batch_mode(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
                                              const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
                                              void *proofs_out, int32_t *rcs, size_t workspace_budget, int mode, float *timings4);
+/* groth16.hpp BATCH_GROUPED_HE (= 3): mode 2 above with the group's constraint evaluations as ONE bh_r1cs_eval_many_dev and,
+ * where witness j + 1 starts where witness j ends, one upload per vector kind per group.  An entry point of its own: the
+ * hook above keeps refusing every mode beyond 2, as its tests pin. */
+int bh_test_groth16_prove_witness_batch_he(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
+                                           const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
+                                           void *proofs_out, int32_t *rcs, size_t workspace_budget, float *timings4);
 /* host only, no GPU: the launches bh_fft_fr_many_dev_on issues with BH_FFT_MANY_FORCE for k vectors of 2^log_n,
  * stride_elems apart, a scratch of scratch_vectors vectors and tables of table_kind (0 two-level, 1 one-level; sizes outside
  * 2^12 .. 2^24 have no one-level tables and plan as 0).  Returns the number of launches (BH_ERR_INVALID_ARG < 0 for a shape
@@ -473,6 +479,9 @@ int bh_test_groth16_prove_witness_batch_mode(bh_params *params, const bh_r1cs *r
  *   [18] log_v (single-pass sizes: 2^log_v vectors per tile, one per column)  [19] pass */
 int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t scratch_vectors, int table_kind, uint64_t *out,
                           size_t cap);
+/* host only: the number of witnesses a lane of bh_r1cs_eval_many_dev / bh_r1cs_check_many_dev serves (csrc/r1cs_dev.hpp
+ * R1CS_MANY_TILE), so that a test can place k on the tile edges */
+uint32_t bh_test_r1cs_many_tile(void);
 
 #ifdef __cplusplus
 }

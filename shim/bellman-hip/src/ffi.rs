@@ -279,6 +279,9 @@ extern "C" {
     pub fn bh_r1cs_shape(r: *const BhR1cs, n_inputs: *mut usize, n_aux: *mut usize, n_constraints: *mut usize) -> c_int;
     pub fn bh_r1cs_density(r: *const BhR1cs, which: c_int, dev_words: *mut *const u64, host_words: *mut *const u64, total: *mut usize) -> c_int;
     pub fn bh_r1cs_eval_dev(ctx: *mut BhCtx, r: *const BhR1cs, inputs_dev: *const c_void, aux_dev: *const c_void, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, log_m: u32, stream: *mut c_void) -> c_int;
+    pub fn bh_r1cs_eval_many_dev(ctx: *mut BhCtx, r: *const BhR1cs, inputs_dev: *const c_void, in_stride: usize, aux_dev: *const c_void, aux_stride: usize, k: usize, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, out_stride: usize, log_m: u32, stream: *mut c_void) -> c_int;
+    pub fn bh_r1cs_check_many_dev(ctx: *mut BhCtx, r: *const BhR1cs, inputs_dev: *const c_void, in_stride: usize, aux_dev: *const c_void, aux_stride: usize, k: usize, first_bad_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn bh_r1cs_check_many(ctx: *mut BhCtx, r: *const BhR1cs, inputs_host: *const c_void, aux_host: *const c_void, k: usize, first_bad_host: *mut u32) -> c_int;
     pub fn bh_fr_powers_dev(ctx: *mut BhCtx, out_dev: *mut c_void, n: usize, g_host: *const c_void, scale_host: *const c_void, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_eval_transposed_dev(ctx: *mut BhCtx, r: *mut BhR1cs, lagrange_dev: *const c_void, at_dev: *mut c_void, bt_dev: *mut c_void, ct_dev: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bh_fr_qap_ext_dev(ctx: *mut BhCtx, e_dev: *mut c_void, at_dev: *const c_void, bt_dev: *const c_void, ct_dev: *const c_void, n_inputs: usize, n_vars: usize, alpha: *const c_void, beta: *const c_void, gamma_inv: *const c_void, delta_inv: *const c_void, stream: *mut c_void) -> c_int;
@@ -294,6 +297,7 @@ extern "C" {
     pub fn bh_groth16_params_verify_step(ctx: *mut BhCtx, before: *const BhParams, after: *const BhParams, seed32: *const c_void, flags: c_uint, report: *mut BhParamsStepReport) -> c_int;
     pub fn bh_groth16_prove_witness(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_witness_batch(params: *mut BhParams, r1cs: *const BhR1cs, inputs: *const c_void, n_inputs: usize, aux: *const c_void, n_aux: usize, k: usize, r: *const c_void, s: *const c_void, proofs_out: *mut c_void, rcs: *mut i32, timings4: *mut f32) -> c_int;
+    pub fn bh_groth16_prove_witness_batch_checked(params: *mut BhParams, r1cs: *const BhR1cs, inputs: *const c_void, n_inputs: usize, aux: *const c_void, n_aux: usize, k: usize, r: *const c_void, s: *const c_void, proofs_out: *mut c_void, rcs: *mut i32, first_unsatisfied: *mut u32, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_assignment_async(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_prove_witness_async(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_proof_wait(job: *mut BhProofJob, proof_out: *mut c_void, timings4: *mut f32) -> c_int;

@@ -13,6 +13,8 @@ beats the better baseline by more than that spread - the condition under which t
 `grouped_h`: the grouped path with a BATCHED h block (groth16.hpp BATCH_GROUPED_H: one bh_h_poly_fr_many_dev_on per group);
 `grouped_h_share_batched` is the same share of its wall time, `grouped_h_wins` / `grouped_h_speedup_vs_best` as for the
 grouped path.
+`grouped_he`: BATCH_GROUPED_HE - the same with the group's constraint evaluations as ONE bh_r1cs_eval_many_dev and one upload
+per vector kind; `grouped_he_vs_grouped_h` is the ratio of the two minima, `grouped_he_share_batched` the share as above.
 
 Usage: python tools/bench_prove_batch.py [--out profiles/prove_batch_bench.json] [--reps 5] [--max-log 18]"""
 import argparse
@@ -118,7 +120,13 @@ def main():
             def grouped_h():
                 return pg.prove_witness_batch(r1cs, params, ins_k, auxs_k, rs[:k], ss[:k], tm_h, _workspace_budget=0, _mode=2)
 
-            variants = (("sequential", sequential), ("async", in_flight), ("batch", batch), ("grouped", grouped), ("grouped_h", grouped_h))
+            tm_he = [0, 0, 0, 0]
+
+            def grouped_he():
+                return pg.prove_witness_batch(r1cs, params, ins_k, auxs_k, rs[:k], ss[:k], tm_he, _workspace_budget=0, _mode=3)
+
+            variants = (("sequential", sequential), ("async", in_flight), ("batch", batch), ("grouped", grouped), ("grouped_h", grouped_h),
+                        ("grouped_he", grouped_he))
             times = {v: [] for v, _ in variants}
             res = {}
             for rep in range(args.reps + 1):
@@ -128,7 +136,7 @@ def main():
                     if rep:
                         times[v].append((time.perf_counter() - t0) * 1e3)
             for j in range(k):
-                for v in ("async", "batch", "grouped", "grouped_h"):
+                for v in ("async", "batch", "grouped", "grouped_h", "grouped_he"):
                     assert all(np.array_equal(getattr(res[v][j], f), getattr(res["sequential"][j], f)) for f in "abc"), (name, k, v, j)
             best = min(("sequential", "async"), key=lambda v: min(times[v]))
             spread = max(times[best]) - min(times[best])
@@ -144,7 +152,11 @@ def main():
                    "grouped_h_wins": bool(min(times["grouped_h"]) < min(times[best]) - spread),
                    "grouped_h_speedup_vs_best": round(min(times[best]) / min(times["grouped_h"]), 3),
                    "grouped_h_vs_grouped": round(min(times["grouped"]) / min(times["grouped_h"]), 3),
-                   "grouped_h_share_batched": round(tm_h[1] / tm_h[3], 3) if tm_h[3] else None}
+                   "grouped_h_share_batched": round(tm_h[1] / tm_h[3], 3) if tm_h[3] else None,
+                   "grouped_he_wins": bool(min(times["grouped_he"]) < min(times[best]) - spread),
+                   "grouped_he_speedup_vs_best": round(min(times[best]) / min(times["grouped_he"]), 3),
+                   "grouped_he_vs_grouped_h": round(min(times["grouped_h"]) / min(times["grouped_he"]), 3),
+                   "grouped_he_share_batched": round(tm_he[1] / tm_he[3], 3) if tm_he[3] else None}
             rows.append(row)
             print(json.dumps(row), flush=True)
         params.release()
