@@ -507,13 +507,12 @@ int bh_groth16_prove_demo_r1cs(bh_params *params, const bh_r1cs *r1cs, int circu
                                float *timings4) {
   using namespace groth16;
   if (!params || !r1cs || !r || !s || !proof_out) return BH_ERR_INVALID_ARG;
-  Fr rr, ss;
-  memcpy(&rr, r, 32); memcpy(&ss, s, 32);
+  const Fr rr = read_fr(r), ss = read_fr(s);
   ProveTimings tm = {0, 0, 0, 0};
   int rc = with_demo_circuit(circuit_kind, size, seed, witness, constants, [&](bellman::Circuit &c) -> int {
     return run_guarded([&] { R1csView view(r1cs); return create_proof(c, view.r, *params->p, rr, ss, &tm); }, proof_out);
   });
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -521,17 +520,14 @@ int bh_groth16_prove_demo_async(bh_params *params, const bh_r1cs *r1cs, int circ
                                 const void *witness, const void *constants, const void *r, const void *s, bh_proof_job **out) {
   using namespace groth16;
   if (!params || !r || !s || !out) return BH_ERR_INVALID_ARG;
-  Fr rr, ss;
-  memcpy(&rr, r, 32); memcpy(&ss, s, 32);
+  const Fr rr = read_fr(r), ss = read_fr(s);
   std::unique_ptr<bh_proof_job> pj(new bh_proof_job());
   if (r1cs) pj->view.reset(new R1csView(r1cs));
   int rc = with_demo_circuit(circuit_kind, size, seed, witness, constants, [&](bellman::Circuit &c) -> int {
-    try {
+    return guarded([&] {
       pj->job = create_proof_async(c, r1cs ? &pj->view->r : nullptr, *params->p, rr, ss);
       return BH_OK;
-    } catch (const bellman::SynthesisError &e) { return e.code;
-    } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-    } catch (...) { return BH_ERR_HIP; }
+    });
   });
   if (rc != BH_OK) return rc;
   *out = pj.release();
@@ -548,10 +544,7 @@ int bh_groth16_prove_demo_r1cs_part(bh_params *params, const bh_r1cs *r1cs, int 
       R1csView view(r1cs);
       const double t0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
       WitnessAssignment w;
-      w.input_assignment.reserve(view.r.num_inputs);
-      w.aux_assignment.reserve(view.r.num_aux);
-      w.alloc_input([] { return Fr::one(); });
-      c.synthesize(w);
+      synthesize_witness(c, view.r, w);
       const double t1 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
       MsmSums m = prove_witness_part(view.r, *params->p, w.input_assignment.data(), w.input_assignment.size(),
                                      w.aux_assignment.data(), w.aux_assignment.size(), part, parts, &tm);
@@ -560,7 +553,7 @@ int bh_groth16_prove_demo_r1cs_part(bh_params *params, const bh_r1cs *r1cs, int 
       return m;
     }, sums_out);
   });
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -568,8 +561,7 @@ int bh_groth16_prove_demo(bh_params *params, int circuit_kind, size_t size, uint
                           const void *constants, const void *r, const void *s, void *proof_out, float *timings4) {
   using namespace groth16;
   if (!params || !witness || !r || !s || !proof_out) return BH_ERR_INVALID_ARG;
-  Fr rr, ss;
-  memcpy(&rr, r, 32); memcpy(&ss, s, 32);
+  const Fr rr = read_fr(r), ss = read_fr(s);
   ProveTimings tm = {0, 0, 0, 0};
   int rc;
   if (circuit_kind == 0) {   // MiMC: witness = xl | xr, constants = `size` round constants (Montgomery Fr)
@@ -591,7 +583,7 @@ int bh_groth16_prove_demo(bh_params *params, int circuit_kind, size_t size, uint
   } else {
     return BH_ERR_INVALID_ARG;
   }
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  write_timings(timings4, tm);
   return rc;
 }
 

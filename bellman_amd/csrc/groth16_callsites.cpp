@@ -40,27 +40,17 @@ using namespace bellman;
 using namespace detail;
 
 namespace {
-struct CallSiteInputs {
-  const Fr *a, *b, *c; size_t n_cons;
-  const Fr *inputs; size_t n_in;
-  const Fr *aux; size_t n_aux;
-  const uint64_t *a_aux_density, *b_input_density, *b_aux_density;
-};
-size_t popcount_bits(const uint64_t *w, size_t n) {
-  size_t t = 0;
-  for (size_t i = 0; i < n / 64; i++) t += (size_t)__builtin_popcountll(w[i]);
-  if (n & 63) t += (size_t)__builtin_popcountll(w[n / 64] & ((uint64_t(1) << (n & 63)) - 1));
-  return t;
-}
-// every issued job is waited on even when an earlier wait fails or something throws (the Rust MsmJob's Drop)
-struct Jobs {
-  bh_msm_job *j[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~Jobs() {
-    unsigned char sink[192];
-    for (bh_msm_job *&x : j) if (x) { (void)bh_msm_wait(x, sink); x = nullptr; }
+using CallSiteInputs = AssignmentView;
+// the eight multiexps of groth16_internal.hpp over the caller's arrays: the density maps stay on the host here
+struct CallSiteQueries {
+  Densities dens;
+  QueryTable table;
+  CallSiteQueries(const Parameters &p, const CallSiteInputs &in) {
+    dens.on_host(in.a_aux_density, in.b_input_density, in.b_aux_density, in.n_inputs);
+    table = queries(p, in.n_inputs, dens.b_in_total);
   }
-  int wait(int i, void *out) { bh_msm_job *x = j[i]; j[i] = nullptr; return bh_msm_wait(x, out); }
 };
+using Jobs = InFlight<bh_msm_job>;   // by slot; every issued job is waited on whatever throws (the Rust MsmJob's Drop)
 struct ScalarsHandle {
   bh_scalars *s = nullptr;
   ScalarsHandle() = default;
@@ -69,19 +59,11 @@ struct ScalarsHandle {
   ScalarsHandle &operator=(const ScalarsHandle &) = delete;
   ~ScalarsHandle() { if (s) bh_scalars_release(s); }
 };
-// wait order of prover.rs:339-354: a_inputs, a_aux, b_g1_inputs, b_g1_aux, b_g2_inputs, b_g2_aux, h, l
-enum { A_IN, A_AUX, B1_IN, B1_AUX, B2_IN, B2_AUX, H, L };
+// prover.rs:320-354: the subversion check sits between the last multiexp call and the first wait(); it wins over
+// whatever the waits report (first_failure)
 MsmSums wait_all(Jobs &jobs, const Parameters &p) {
-  // prover.rs:320-324 sits between the last multiexp call and the first wait()
-  if (p.vk.delta_g1.is_identity() || p.vk.delta_g2.is_identity())
-    throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
   MsmSums m;
-  int rcs[8];
-  rcs[0] = jobs.wait(A_IN, &m.a_in); rcs[1] = jobs.wait(A_AUX, &m.a_aux);
-  rcs[2] = jobs.wait(B1_IN, &m.b1_in); rcs[3] = jobs.wait(B1_AUX, &m.b1_aux);
-  rcs[4] = jobs.wait(B2_IN, &m.b2_in); rcs[5] = jobs.wait(B2_AUX, &m.b2_aux);
-  rcs[6] = jobs.wait(H, &m.h); rcs[7] = jobs.wait(L, &m.l);
-  for (int rc : rcs) check(rc);   // the first failing `?` in wait order
+  wait_eight(jobs, p, m);
   return m;
 }
 
@@ -90,21 +72,22 @@ MsmSums issue_patched(Parameters &p, const CallSiteInputs &in) {
   bh_ctx *ctx = p.ctx;
   // declared before `jobs`: the jobs are waited on (Jobs' destructor) before the vectors they read are released
   ScalarsHandle inputs, aux, h;
-  Jobs jobs;
-  check(bh_scalars_register(ctx, in.inputs, in.n_in, BH_SCALARS_MONT, &inputs.s));
-  check(bh_scalars_register(ctx, in.aux, in.n_aux, BH_SCALARS_MONT, &aux.s));
-  const size_t b_in_total = popcount_bits(in.b_input_density, in.n_in);
-  // the G2 multiexp first: the longest job; the bucket accumulations run on the device in issue order and its
-  // reduction tail then overlaps the G1 accumulations (csrc/common.hpp, the accumulation chain)
-  check(bh_msm_async_scalars(ctx, p.b_g2, b_in_total, aux.s, 0, in.n_aux, in.b_aux_density, in.n_aux, nullptr, &jobs.j[B2_AUX]));
-  check(bh_msm_async_scalars(ctx, p.l, 0, aux.s, 0, in.n_aux, nullptr, 0, nullptr, &jobs.j[L]));
-  check(bh_msm_async_scalars(ctx, p.a, 0, inputs.s, 0, in.n_in, nullptr, 0, nullptr, &jobs.j[A_IN]));
-  check(bh_msm_async_scalars(ctx, p.a, in.n_in, aux.s, 0, in.n_aux, in.a_aux_density, in.n_aux, nullptr, &jobs.j[A_AUX]));
-  check(bh_msm_async_scalars(ctx, p.b_g1, 0, inputs.s, 0, in.n_in, in.b_input_density, in.n_in, nullptr, &jobs.j[B1_IN]));
-  check(bh_msm_async_scalars(ctx, p.b_g1, b_in_total, aux.s, 0, in.n_aux, in.b_aux_density, in.n_aux, nullptr, &jobs.j[B1_AUX]));
-  check(bh_msm_async_scalars(ctx, p.b_g2, 0, inputs.s, 0, in.n_in, in.b_input_density, in.n_in, nullptr, &jobs.j[B2_IN]));
-  check(bh_h_poly_fr_scalars(ctx, in.a, in.b, in.c, in.n_cons, &h.s));
-  check(bh_msm_async_scalars(ctx, p.h, 0, h.s, 0, bh_scalars_len(h.s), nullptr, 0, nullptr, &jobs.j[H]));
+  Jobs jobs(N_SLOTS);
+  check(bh_scalars_register(ctx, in.input_assignment, in.n_inputs, BH_SCALARS_MONT, &inputs.s));
+  check(bh_scalars_register(ctx, in.aux_assignment, in.n_aux, BH_SCALARS_MONT, &aux.s));
+  const CallSiteQueries qs(p, in);
+  auto issue = [&](Slot slot, const bh_scalars *scalars, size_t n) {
+    const Query &q = qs.table[slot];
+    const uint64_t *density = qs.dens.host_of(q.density);
+    check(bh_msm_async_scalars(ctx, q.bases, q.skip, scalars, 0, n, density, density ? n : 0, nullptr, &jobs.at[slot]));
+  };
+  // the patched prover issues in the order of the mirror (ISSUE_ORDER: the G2 multiexp first), H once the h block is enqueued
+  for (Slot slot : ISSUE_ORDER) {
+    const bool from_inputs = qs.table[slot].scalars == FROM_INPUTS;
+    issue(slot, from_inputs ? inputs.s : aux.s, from_inputs ? in.n_inputs : in.n_aux);
+  }
+  check(bh_h_poly_fr_scalars(ctx, in.a, in.b, in.c, in.n_constraints, &h.s));
+  issue(H, h.s, bh_scalars_len(h.s));
   return wait_all(jobs, p);
 }
 
@@ -131,26 +114,21 @@ std::vector<uint64_t> to_exponents(const Fr *v, size_t n) {
 }
 MsmSums issue_unpatched_prover(Parameters &p, const CallSiteInputs &in) {
   bh_ctx *ctx = p.ctx;
-  // EvaluationDomain::from_coeffs (domain.rs:47-79)
-  uint32_t exp = 0;
-  size_t m = 1;
-  while (m < in.n_cons) {
-    m *= 2;
-    exp++;
-    if (exp >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const Domain dom = domain_of(in.n_constraints);
+  const size_t m = dom.m;
+  const uint32_t exp = dom.log_m;
   std::vector<Fr> a(m, Fr::zero()), b(m, Fr::zero()), c(m, Fr::zero());
-  if (in.n_cons) {
-    memcpy(a.data(), in.a, in.n_cons * 32);
-    memcpy(b.data(), in.b, in.n_cons * 32);
-    memcpy(c.data(), in.c, in.n_cons * 32);
+  if (in.n_constraints) {
+    memcpy(a.data(), in.a, in.n_constraints * 32);
+    memcpy(b.data(), in.b, in.n_constraints * 32);
+    memcpy(c.data(), in.c, in.n_constraints * 32);
   }
   // host buffers handed to bh_msm_async stay valid until the job has been waited on (the Rust closure keeps its
   // `words` alive the same way): declared before `jobs`, destroyed after it
   std::vector<uint64_t> h_exps, in_exps, aux_exps;
   std::vector<std::vector<uint64_t>> call_words;
   call_words.reserve(8);
-  Jobs jobs;
+  Jobs jobs(N_SLOTS);
   // prover.rs:222-230
   for (std::vector<Fr> *v : {&a, &b, &c}) {
     check(bh_fft_fr(ctx, v->data(), exp, BH_IFFT));
@@ -168,23 +146,20 @@ MsmSums issue_unpatched_prover(Parameters &p, const CallSiteInputs &in) {
   check(bh_fft_fr(ctx, a.data(), exp, BH_ICOSET_FFT));
   a.resize(m - 1);                                   // :238-239
   h_exps = to_exponents(a.data(), a.size());         // :241-242
-  auto multiexp = [&](bh_bases *bases, size_t skip, const std::vector<uint64_t> &exps, const uint64_t *density, int slot) {
-    call_words.emplace_back(exps);                   // exponent_words: a fresh Vec<[u64; 4]> per call
+  const CallSiteQueries qs(p, in);
+  auto multiexp = [&](Slot slot) {
+    const Query &q = qs.table[slot];
+    const uint64_t *density = qs.dens.host_of(q.density);
+    call_words.emplace_back(q.scalars == FROM_INPUTS ? in_exps : q.scalars == FROM_AUX ? aux_exps : h_exps);   // exponent_words: a fresh Vec<[u64; 4]> per call
     const std::vector<uint64_t> &words = call_words.back();
     const size_t n = words.size() / 4;
-    check(bh_msm_async(ctx, bases, skip, words.data(), n, BH_SCALARS_CANONICAL, density, density ? n : 0, &jobs.j[slot]));
+    check(bh_msm_async(ctx, q.bases, q.skip, words.data(), n, BH_SCALARS_CANONICAL, density, density ? n : 0, &jobs.at[slot]));
   };
-  multiexp(p.h, 0, h_exps, nullptr, H);              // :244
-  in_exps = to_exponents(in.inputs, in.n_in);        // :247-261
-  aux_exps = to_exponents(in.aux, in.n_aux);
-  const size_t b_in_total = popcount_bits(in.b_input_density, in.n_in);
-  multiexp(p.l, 0, aux_exps, nullptr, L);                               // :263-268
-  multiexp(p.a, 0, in_exps, nullptr, A_IN);                             // :275-280
-  multiexp(p.a, in.n_in, aux_exps, in.a_aux_density, A_AUX);            // :281-286
-  multiexp(p.b_g1, 0, in_exps, in.b_input_density, B1_IN);              // :296-301
-  multiexp(p.b_g1, b_in_total, aux_exps, in.b_aux_density, B1_AUX);     // :302-307
-  multiexp(p.b_g2, 0, in_exps, in.b_input_density, B2_IN);              // :312-317
-  multiexp(p.b_g2, b_in_total, aux_exps, in.b_aux_density, B2_AUX);     // :318
+  multiexp(H);                                       // :244
+  in_exps = to_exponents(in.input_assignment, in.n_inputs);        // :247-261
+  aux_exps = to_exponents(in.aux_assignment, in.n_aux);
+  for (Slot slot : REFERENCE_ORDER)                  // :263-318
+    if (slot != H) multiexp(slot);
   return wait_all(jobs, p);
 }
 // ---- mode 2 ----------------------------------------------------------------------------------------------------------
@@ -238,21 +213,17 @@ std::vector<Fr> to_raw_exponents(const Fr *v, size_t n) {
 }
 MsmSums issue_unpatched_prover_resident(Parameters &p, const CallSiteInputs &in) {
   bh_ctx *ctx = p.ctx;
-  uint32_t exp = 0;
-  size_t m = 1;
-  while (m < in.n_cons) {
-    m *= 2;
-    exp++;
-    if (exp >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const Domain dom = domain_of(in.n_constraints);
+  const size_t m = dom.m;
+  const uint32_t exp = dom.log_m;
   // the Arc<Vec<Exponent>> cache of the patched multiexp: one registration per distinct vector, alive until the jobs end
   std::vector<std::pair<const Fr *, ScalarsHandle>> registered;
   registered.reserve(4);
   std::vector<Fr> h_exps, in_exps, aux_exps;
-  Jobs jobs;
+  Jobs jobs(N_SLOTS);
   {
-    DeviceDomain a(ctx, in.a, in.n_cons, m, exp);
-    std::unique_ptr<DeviceDomain> b(new DeviceDomain(ctx, in.b, in.n_cons, m, exp)), c(new DeviceDomain(ctx, in.c, in.n_cons, m, exp));
+    DeviceDomain a(ctx, in.a, in.n_constraints, m, exp);
+    std::unique_ptr<DeviceDomain> b(new DeviceDomain(ctx, in.b, in.n_constraints, m, exp)), c(new DeviceDomain(ctx, in.c, in.n_constraints, m, exp));
     for (DeviceDomain *v : {&a, b.get(), c.get()}) {   // prover.rs:222-230
       v->transform(BH_IFFT);
       v->transform(BH_COSET_FFT);
@@ -266,7 +237,11 @@ MsmSums issue_unpatched_prover_resident(Parameters &p, const CallSiteInputs &in)
     std::vector<Fr> &av = a.into_coeffs();
     h_exps = to_raw_exponents(av.data(), m - 1);       // :238-242 (truncate, then the map)
   }
-  auto multiexp = [&](bh_bases *bases, size_t skip, const std::vector<Fr> &exps, const uint64_t *density, int slot) {
+  const CallSiteQueries qs(p, in);
+  auto multiexp = [&](Slot slot) {
+    const Query &q = qs.table[slot];
+    const uint64_t *density = qs.dens.host_of(q.density);
+    const std::vector<Fr> &exps = q.scalars == FROM_INPUTS ? in_exps : q.scalars == FROM_AUX ? aux_exps : h_exps;
     bh_scalars *sc = nullptr;
     for (auto &r : registered) if (r.first == exps.data()) sc = r.second.s;
     if (!sc) {
@@ -280,19 +255,13 @@ MsmSums issue_unpatched_prover_resident(Parameters &p, const CallSiteInputs &in)
       sc = registered.back().second.s;
     }
     const size_t n = exps.size();
-    check(bh_msm_async_scalars(ctx, bases, skip, sc, 0, n, density, density ? n : 0, nullptr, &jobs.j[slot]));
+    check(bh_msm_async_scalars(ctx, q.bases, q.skip, sc, 0, n, density, density ? n : 0, nullptr, &jobs.at[slot]));
   };
-  multiexp(p.h, 0, h_exps, nullptr, H);              // :244
-  in_exps = to_raw_exponents(in.inputs, in.n_in);    // :247-261
-  aux_exps = to_raw_exponents(in.aux, in.n_aux);
-  const size_t b_in_total = popcount_bits(in.b_input_density, in.n_in);
-  multiexp(p.l, 0, aux_exps, nullptr, L);                               // :263-268
-  multiexp(p.a, 0, in_exps, nullptr, A_IN);                             // :275-280
-  multiexp(p.a, in.n_in, aux_exps, in.a_aux_density, A_AUX);            // :281-286
-  multiexp(p.b_g1, 0, in_exps, in.b_input_density, B1_IN);              // :296-301
-  multiexp(p.b_g1, b_in_total, aux_exps, in.b_aux_density, B1_AUX);     // :302-307
-  multiexp(p.b_g2, 0, in_exps, in.b_input_density, B2_IN);              // :312-317
-  multiexp(p.b_g2, b_in_total, aux_exps, in.b_aux_density, B2_AUX);     // :318
+  multiexp(H);                                       // :244
+  in_exps = to_raw_exponents(in.input_assignment, in.n_inputs);    // :247-261
+  aux_exps = to_raw_exponents(in.aux_assignment, in.n_aux);
+  for (Slot slot : REFERENCE_ORDER)                  // :263-318
+    if (slot != H) multiexp(slot);
   return wait_all(jobs, p);
 }
 }  // namespace
@@ -316,23 +285,11 @@ extern "C" int bh_test_groth16_prove_via_call_sites(bh_params *params, int mode,
                                                     void *proof_out, float *ms2) {
   using namespace groth16;
   if (!params || !r || !s || !proof_out || mode < 0 || mode > 2) return BH_ERR_INVALID_ARG;
-  if ((n_constraints && (!a_evals || !b_evals || !c_evals)) || (n_inputs && (!input_assignment || !b_input_density)) ||
-      (n_aux && (!aux_assignment || !a_aux_density || !b_aux_density)))
+  CallSiteInputs in;
+  if (!assignment_view(a_evals, b_evals, c_evals, n_constraints, input_assignment, n_inputs, aux_assignment, n_aux, a_aux_density,
+                       b_input_density, b_aux_density, &in))
     return BH_ERR_INVALID_ARG;
-  try {
-    CallSiteInputs in{(const Fr *)a_evals, (const Fr *)b_evals, (const Fr *)c_evals, n_constraints,
-                      (const Fr *)input_assignment, n_inputs, (const Fr *)aux_assignment, n_aux,
-                      a_aux_density, b_input_density, b_aux_density};
-    Fr rr, ss;
-    memcpy(&rr, r, 32); memcpy(&ss, s, 32);
-    const Proof p = prove_via_call_sites(*params->p, in, rr, ss, mode, ms2);
-    memcpy(proof_out, &p.a, 96);
-    memcpy((char *)proof_out + 96, &p.b, 192);
-    memcpy((char *)proof_out + 288, &p.c, 96);
-    return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
+  return run_guarded([&] { return prove_via_call_sites(*params->p, in, read_fr(r), read_fr(s), mode, ms2); }, proof_out);
 }
 
 // bh_groth16_prove_witness_batch through its GROUPED path (many-jobs over groups of witnesses; the product call never takes

@@ -20,7 +20,7 @@ int bh_groth16_params_create(bh_ctx *ctx, const void *alpha_g1, const void *beta
                              const void *delta_g1, const void *delta_g2, const void *h, size_t nh, const void *l,
                              size_t nl, const void *a, size_t na, const void *b_g1, size_t nb1, const void *b_g2,
                              size_t nb2, bh_params **out) {
-  try {
+  return guarded([&] {
     groth16::VerifyingKey vk;
     memcpy(&vk.alpha_g1, alpha_g1, 96); memcpy(&vk.beta_g1, beta_g1, 96); memcpy(&vk.beta_g2, beta_g2, 192);
     memcpy(&vk.delta_g1, delta_g1, 96); memcpy(&vk.delta_g2, delta_g2, 192);
@@ -28,70 +28,56 @@ int bh_groth16_params_create(bh_ctx *ctx, const void *alpha_g1, const void *beta
                                                  (const groth16::G1Affine *)a, na, (const groth16::G1Affine *)b_g1, nb1,
                                                  (const groth16::G2Affine *)b_g2, nb2)};
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_params_read(bh_ctx *ctx, const void *bytes, size_t len, int checked, bh_params **out) {
   if (!ctx || !out || (len && !bytes)) return BH_ERR_INVALID_ARG;
-  try {
+  return guarded([&] {
     *out = new bh_params{new groth16::Parameters(ctx, bytes, len, checked != 0)};
     return BH_OK;
-  } catch (const bellman::IoError &e) { return e.code;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_generate(bh_ctx *ctx, bh_r1cs *r1cs, const void *g1, const void *g2, const void *alpha, const void *beta,
                         const void *gamma, const void *delta, const void *tau, bh_params **out) {
   if (!ctx || !r1cs || !out) return BH_ERR_INVALID_ARG;
   using namespace groth16;
-  try {
+  return guarded([&] {
     R1csView view(r1cs);
     G1Affine p1; G2Affine p2;
-    Fr f[5];
     memcpy(&p1, g1, 96); memcpy(&p2, g2, 192);
-    const void *src[5] = {alpha, beta, gamma, delta, tau};
-    for (int i = 0; i < 5; i++) memcpy(&f[i], src[i], 32);
-    *out = new bh_params{new Parameters(ctx, view.r, p1, p2, f[0], f[1], f[2], f[3], f[4])};
+    *out = new bh_params{new Parameters(ctx, view.r, p1, p2, read_fr(alpha), read_fr(beta), read_fr(gamma), read_fr(delta), read_fr(tau))};
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_generate_from_powers_of_tau(bh_ctx *ctx, bh_r1cs *r1cs, const bh_powers_of_tau *t, bh_params **out) {
   if (!ctx || !r1cs || !t || !out || !t->beta_g2) return BH_ERR_INVALID_ARG;
   using namespace groth16;
-  try {
+  return guarded([&] {
     R1csView view(r1cs);
     PowersOfTau pt;
     pt.tau_g1 = t->tau_g1; pt.tau_g2 = t->tau_g2; pt.alpha_tau_g1 = t->alpha_tau_g1; pt.beta_tau_g1 = t->beta_tau_g1;
     memcpy(&pt.beta_g2, t->beta_g2, 192);
     *out = new bh_params{new Parameters(ctx, view.r, pt)};
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_params_rescale_delta(const bh_params *p, const void *d_mont, bh_params **out) {
   if (!p || !d_mont || !out) return BH_ERR_INVALID_ARG;
-  try {
-    groth16::Fr d;
-    memcpy(&d, d_mont, 32);
-    *out = new bh_params{p->p->rescale_delta(d).release()};
+  return guarded([&] {
+    *out = new bh_params{p->p->rescale_delta(read_fr(d_mont)).release()};
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_params_write(const bh_params *p, void *buf, size_t cap, size_t *len) {
   if (!p || !len) return BH_ERR_INVALID_ARG;
-  try {
+  return guarded([&] {
     const groth16::Parameters &P = *p->p;
     const size_t need = P.serialized_size();
     *len = need;
     if (!buf || cap < need) return buf ? BH_ERR_INVALID_ARG : BH_OK;   // size query when buf == NULL
     P.write_into((unsigned char *)buf, cap);
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 // prepare_verifying_key (groth16/src/verifier.rs:11-21) on the verifying key of params that carry gamma_g2 and ic
 int bh_groth16_pvk_from_params(const bh_params *p, bh_pvk **out) {
@@ -148,24 +134,15 @@ int bh_groth16_prove_assignment(bh_params *params, const void *a_evals, const vo
                                 const uint64_t *b_input_density, const uint64_t *b_aux_density, const void *r,
                                 const void *s, void *proof_out, float *timings4) {
   using namespace groth16;
-  if (!params || !r || !s || !proof_out) return BH_ERR_INVALID_ARG;
-  if ((n_constraints && (!a_evals || !b_evals || !c_evals)) || (n_inputs && (!input_assignment || !b_input_density)) ||
-      (n_aux && (!aux_assignment || !a_aux_density || !b_aux_density)))
+  AssignmentView v;
+  if (!params || !r || !s || !proof_out ||
+      !assignment_view(a_evals, b_evals, c_evals, n_constraints, input_assignment, n_inputs, aux_assignment, n_aux, a_aux_density,
+                       b_input_density, b_aux_density, &v))
     return BH_ERR_INVALID_ARG;
   ProveTimings tm = {0, 0, 0, 0};
-  // everything that can allocate runs inside the guard: no C++ exception may cross the C boundary
-  int rc = run_guarded([&] {
-    // views of the caller's arrays: they are only read as bytes (uploads, the tiny input multiexps), never copied
-    AssignmentView v;
-    v.a = (const Fr *)a_evals; v.b = (const Fr *)b_evals; v.c = (const Fr *)c_evals; v.n_constraints = n_constraints;
-    v.input_assignment = (const Fr *)input_assignment; v.n_inputs = n_inputs;
-    v.aux_assignment = (const Fr *)aux_assignment; v.n_aux = n_aux;
-    v.a_aux_density = a_aux_density; v.b_input_density = b_input_density; v.b_aux_density = b_aux_density;
-    Fr rr, ss;
-    memcpy(&rr, r, 32); memcpy(&ss, s, 32);
-    return prove_assignment(v, *params->p, rr, ss, &tm);
-  }, proof_out);
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  // everything that can allocate runs inside the guard
+  const int rc = run_guarded([&] { return prove_assignment(v, *params->p, read_fr(r), read_fr(s), &tm); }, proof_out);
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -176,16 +153,14 @@ int bh_groth16_prove_witness(bh_params *params, const bh_r1cs *r1cs, const void 
   if (!params || !r1cs || !r || !s || !proof_out || (n_inputs && !input_assignment) || (n_aux && !aux_assignment))
     return BH_ERR_INVALID_ARG;
   ProveTimings tm = {0, 0, 0, 0};
-  int rc = run_guarded([&] {
+  const int rc = run_guarded([&] {
     R1csView view(r1cs);
     std::vector<Fr> in(n_inputs), aux(n_aux);   // caller records may be unaligned
     if (n_inputs) memcpy(in.data(), input_assignment, n_inputs * 32);
     if (n_aux) memcpy(aux.data(), aux_assignment, n_aux * 32);
-    Fr rr, ss;
-    memcpy(&rr, r, 32); memcpy(&ss, s, 32);
-    return prove_witness(view.r, *params->p, in.data(), n_inputs, aux.data(), n_aux, rr, ss, &tm);
+    return prove_witness(view.r, *params->p, in.data(), n_inputs, aux.data(), n_aux, read_fr(r), read_fr(s), &tm);
   }, proof_out);
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -209,50 +184,38 @@ int bh_groth16_prove_assignment_async(bh_params *params, const void *a_evals, co
                                       const uint64_t *b_input_density, const uint64_t *b_aux_density, const void *r,
                                       const void *s, bh_proof_job **out) {
   using namespace groth16;
-  if (!params || !r || !s || !out) return BH_ERR_INVALID_ARG;
-  if ((n_constraints && (!a_evals || !b_evals || !c_evals)) || (n_inputs && (!input_assignment || !b_input_density)) ||
-      (n_aux && (!aux_assignment || !a_aux_density || !b_aux_density)))
+  AssignmentView v;
+  if (!params || !r || !s || !out ||
+      !assignment_view(a_evals, b_evals, c_evals, n_constraints, input_assignment, n_inputs, aux_assignment, n_aux, a_aux_density,
+                       b_input_density, b_aux_density, &v))
     return BH_ERR_INVALID_ARG;
-  try {
-    AssignmentView v;
-    v.a = (const Fr *)a_evals; v.b = (const Fr *)b_evals; v.c = (const Fr *)c_evals; v.n_constraints = n_constraints;
-    v.input_assignment = (const Fr *)input_assignment; v.n_inputs = n_inputs;
-    v.aux_assignment = (const Fr *)aux_assignment; v.n_aux = n_aux;
-    v.a_aux_density = a_aux_density; v.b_input_density = b_input_density; v.b_aux_density = b_aux_density;
-    Fr rr, ss;
-    memcpy(&rr, r, 32); memcpy(&ss, s, 32);
+  return guarded([&] {
     std::unique_ptr<bh_proof_job> pj(new bh_proof_job());
-    pj->job = prove_assignment_async(v, *params->p, rr, ss);
+    pj->job = prove_assignment_async(v, *params->p, read_fr(r), read_fr(s));
     *out = pj.release();
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_prove_witness_async(bh_params *params, const bh_r1cs *r1cs, const void *input_assignment, size_t n_inputs,
                                    const void *aux_assignment, size_t n_aux, const void *r, const void *s, bh_proof_job **out) {
   using namespace groth16;
   if (!params || !r1cs || !r || !s || !out || (n_inputs && !input_assignment) || (n_aux && !aux_assignment))
     return BH_ERR_INVALID_ARG;
-  try {
-    Fr rr, ss;
-    memcpy(&rr, r, 32); memcpy(&ss, s, 32);
+  return guarded([&] {
     std::unique_ptr<bh_proof_job> pj(new bh_proof_job());
     pj->view.reset(new R1csView(r1cs));
-    pj->job = prove_witness_async(pj->view->r, *params->p, input_assignment, n_inputs, aux_assignment, n_aux, rr, ss);
+    pj->job = prove_witness_async(pj->view->r, *params->p, input_assignment, n_inputs, aux_assignment, n_aux, read_fr(r), read_fr(s));
     *out = pj.release();
     return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
+  });
 }
 int bh_groth16_proof_wait(bh_proof_job *job, void *proof_out, float *timings4) {
   using namespace groth16;
   if (!job || !proof_out) return BH_ERR_INVALID_ARG;
   std::unique_ptr<bh_proof_job> pj(job);
   ProveTimings tm = {0, 0, 0, 0};
-  int rc = run_guarded([&] { return pj->job->wait(&tm); }, proof_out);
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  const int rc = run_guarded([&] { return pj->job->wait(&tm); }, proof_out);
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -262,14 +225,14 @@ int bh_groth16_prove_witness_part(bh_params *params, const bh_r1cs *r1cs, const 
   using namespace groth16;
   if (!params || !r1cs || !sums_out || (n_inputs && !input_assignment) || (n_aux && !aux_assignment)) return BH_ERR_INVALID_ARG;
   ProveTimings tm = {0, 0, 0, 0};
-  int rc = run_guarded_sums([&] {
+  const int rc = run_guarded_sums([&] {
     R1csView view(r1cs);
     std::vector<Fr> in(n_inputs), aux(n_aux);
     if (n_inputs) memcpy(in.data(), input_assignment, n_inputs * 32);
     if (n_aux) memcpy(aux.data(), aux_assignment, n_aux * 32);
     return prove_witness_part(view.r, *params->p, in.data(), n_inputs, aux.data(), n_aux, part, parts, &tm);
   }, sums_out);
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+  write_timings(timings4, tm);
   return rc;
 }
 
@@ -286,9 +249,7 @@ int bh_groth16_assemble(bh_params *params, const void *sums, const void *r, cons
   if (!params || !sums || !r || !s || !proof_out) return BH_ERR_INVALID_ARG;
   MsmSums m;
   memcpy(&m, sums, sizeof m);
-  Fr rr, ss;
-  memcpy(&rr, r, 32); memcpy(&ss, s, 32);
-  return run_guarded([&] { return assemble_proof(*params->p, m, rr, ss); }, proof_out);
+  return run_guarded([&] { return assemble_proof(*params->p, m, read_fr(r), read_fr(s)); }, proof_out);
 }
 
 }  // extern "C"

@@ -43,24 +43,203 @@ inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// ---- the eight multiexps of a proof (prover.rs:217-360), stated once for every prover path --------------------------
+// Slots in the order the reference waits for them (prover.rs:339-354): a_inputs, a_aux, b_g1_inputs, b_g1_aux,
+// b_g2_inputs, b_g2_aux, h, l.  It is MsmSums' field order too.
+enum Slot { A_IN, A_AUX, B1_IN, B1_AUX, B2_IN, B2_AUX, H, L, N_SLOTS };
+constexpr Slot WAIT_ORDER[N_SLOTS] = {A_IN, A_AUX, B1_IN, B1_AUX, B2_IN, B2_AUX, H, L};
+inline size_t slot_bytes(int slot) { return slot == B2_IN || slot == B2_AUX ? sizeof(G2Affine) : sizeof(G1Affine); }
+inline void *sum_at(MsmSums &m, int slot) {
+  void *field[N_SLOTS] = {&m.a_in, &m.a_aux, &m.b1_in, &m.b1_aux, &m.b2_in, &m.b2_aux, &m.h, &m.l};
+  return field[slot];
+}
+// The order the seven multiexps that need only the assignments are issued in; H is placed by the path (it needs the h
+// block).  Issue order = order of the bucket accumulations on the device (the accumulation chain, common.hpp): the G2
+// multiexp first - the longest job, its reduction tail then runs beside the G1 accumulations
+// (profiles/archive/r3_call2_proof_timeline.txt, r3_call4_proof_timeline.txt).  For a small proof the host needs ~0.2 ms to
+// enqueue each job's ~20 launches, so what is issued last finishes last: G2 first there too
+// (profiles/archive/r2_call21_mimc_timeline.txt).  The order of waits is the reference's whatever the order of issue.
+constexpr Slot ISSUE_ORDER[7] = {B2_AUX, L, A_IN, A_AUX, B1_IN, B1_AUX, B2_IN};
+// the order of the UNCHANGED call sites of prover.rs:244-318 (the call-site transcriptions of the unpatched prover)
+constexpr Slot REFERENCE_ORDER[N_SLOTS] = {H, L, A_IN, A_AUX, B1_IN, B1_AUX, B2_IN, B2_AUX};
+
+enum ScalarSource { FROM_INPUTS, FROM_AUX, FROM_QUOTIENT };
+enum { DENSITY_FULL = -1, DENSITY_A_AUX = 0, DENSITY_B_INPUT = 1, DENSITY_B_AUX = 2 };   // bh_r1cs_density's `which`
+struct Query {
+  bh_bases *bases;
+  size_t skip;            // bases the query starts at (before what a slice's skipped scalars consume)
+  ScalarSource scalars;
+  int density;
+};
+struct QueryTable {
+  Query q[N_SLOTS];
+  const Query &operator[](int slot) const { return q[slot]; }
+};
+inline QueryTable queries(const Parameters &p, size_t n_in, size_t b_in_total) {
+  QueryTable t;
+  // get_a(num_inputs, _) -> ((a,0),(a,num_inputs))            groth16/src/lib.rs:451-457
+  t.q[A_IN] = Query{p.a, 0, FROM_INPUTS, DENSITY_FULL};
+  t.q[A_AUX] = Query{p.a, n_in, FROM_AUX, DENSITY_A_AUX};
+  // get_b_g1/g2(b_input_density_total, _) -> ((b,0),(b,total))   groth16/src/lib.rs:459-473
+  t.q[B1_IN] = Query{p.b_g1, 0, FROM_INPUTS, DENSITY_B_INPUT};
+  t.q[B1_AUX] = Query{p.b_g1, b_in_total, FROM_AUX, DENSITY_B_AUX};
+  t.q[B2_IN] = Query{p.b_g2, 0, FROM_INPUTS, DENSITY_B_INPUT};
+  t.q[B2_AUX] = Query{p.b_g2, b_in_total, FROM_AUX, DENSITY_B_AUX};
+  t.q[H] = Query{p.h, 0, FROM_QUOTIENT, DENSITY_FULL};      // a.len() - 1 coefficients, prover.rs:238-244
+  t.q[L] = Query{p.l, 0, FROM_AUX, DENSITY_FULL};
+  return t;
+}
+
+// set bits among the first n of an LSB0 bitmap: get_total_density (multiexp.rs:154-156), and the bases a slice's skipped
+// scalars consume
+inline size_t popcount_bits(const uint64_t *w, size_t n) {
+  size_t t = 0;
+  for (size_t i = 0; i < n / 64; i++) t += (size_t)__builtin_popcountll(w[i]);
+  if (n & 63) t += (size_t)__builtin_popcountll(w[n / 64] & ((uint64_t(1) << (n & 63)) - 1));
+  return t;
+}
+// The three density maps of a proof (prover.rs:59-61), indexed by DENSITY_*: LSB0 words on the device (null where a path
+// hands the host words over) and on the host, and b_input_density's total.
+struct Densities {
+  const uint64_t *dev[3] = {nullptr, nullptr, nullptr}, *host[3] = {nullptr, nullptr, nullptr};
+  size_t b_in_total = 0;
+  std::unique_ptr<DevBuf> uploaded[3];   // the device copies `upload` made (released with this object)
+  const uint64_t *dev_of(int density) const { return density < 0 ? nullptr : dev[density]; }
+  const uint64_t *host_of(int density) const { return density < 0 ? nullptr : host[density]; }
+  void on_host(const uint64_t *a_aux, const uint64_t *b_input, const uint64_t *b_aux, size_t n_in) {
+    host[DENSITY_A_AUX] = a_aux; host[DENSITY_B_INPUT] = b_input; host[DENSITY_B_AUX] = b_aux;
+    b_in_total = popcount_bits(b_input, n_in);
+  }
+  void upload(bh_ctx *ctx, size_t n_in, size_t n_aux, void *stream) {   // after on_host
+    const size_t bits[3] = {n_aux, n_in, n_aux};
+    try {
+      for (int i = 0; i < 3; i++) {
+        const size_t nw = (bits[i] + 63) / 64;
+        uploaded[i].reset(new DevBuf(ctx, nw * 8 + 8));
+        if (nw) check(bh_dev_upload_on(ctx, uploaded[i]->p, host[i], nw * 8, stream));
+        dev[i] = (const uint64_t *)uploaded[i]->p;
+      }
+    } catch (...) {
+      // the maps uploaded so far are released as the caller's frame unwinds: not under their queued uploads.  (The caller
+      // synchronises `stream` once everything is queued; from then on only multiexp jobs read the maps.)
+      (void)bh_stream_synchronize(ctx, stream);
+      throw;
+    }
+  }
+  void of(const R1cs &r1cs) {   // resident with the matrices
+    for (int i = 0; i < 3; i++) check(bh_r1cs_density(r1cs.handle, i, &dev[i], &host[i], i == DENSITY_B_INPUT ? &b_in_total : nullptr));
+  }
+};
+
+// EvaluationDomain::from_coeffs (domain.rs:47-79): the smallest power of two >= n_constraints
+struct Domain { size_t m; uint32_t log_m; };
+inline Domain domain_of(size_t n_constraints) {
+  Domain d{1, 0};
+  while (d.m < n_constraints) {
+    d.m *= 2;
+    d.log_m++;
+    if (d.log_m >= 32) throw bellman::SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
+  }
+  return d;
+}
+
+// What a proof reports, from the codes of its eight waits (in slot order).  prover.rs:320-324 returns UnexpectedIdentity
+// for an identity delta BEFORE any multiexp is waited on: it beats whatever a multiexp reports (e.g. UnexpectedEof from a
+// short query); then the first failing `?` in wait order.  A negative code is a runtime failure: the call's, not a proof's.
+inline int first_failure(const Parameters &p, const int codes[N_SLOTS]) {
+  if (p.vk.delta_g1.is_identity() || p.vk.delta_g2.is_identity()) return BH_ERR_UNEXPECTED_IDENTITY;
+  for (Slot s : WAIT_ORDER)
+    if (codes[s] != BH_OK) return codes[s];
+  return BH_OK;
+}
+
+// Every issued multiexp owns device buffers and reads the caller's: each is waited on exactly once, even when something
+// throws between issue and wait (the Rust MsmJob's Drop).  Declare it AFTER every buffer a job reads - it is then
+// destroyed first and drains whatever is still in flight before those buffers are released.
+inline void drain(bh_msm_job *j) { unsigned char sink[192]; (void)bh_msm_wait(j, sink); }
+inline void drain(bh_msm_many_job *j) { (void)bh_msm_many_wait(j, nullptr, nullptr, nullptr, nullptr); }
+template <class Job>
+struct InFlight {
+  std::vector<Job *> at;   // issue into &at[i]; null: not issued, or taken
+  explicit InFlight(size_t n) : at(n, nullptr) {}
+  InFlight(const InFlight &) = delete;
+  Job *take(size_t i) { Job *j = at[i]; at[i] = nullptr; return j; }
+  ~InFlight() { for (Job *&j : at) if (j) { drain(j); j = nullptr; } }
+};
+// the eight waits of prover.rs:339-354 on jobs held by slot, then the verdict: every job is waited on (it owns device
+// resources), even when an earlier one fails
+inline void wait_eight(InFlight<bh_msm_job> &jobs, const Parameters &p, MsmSums &out) {
+  int codes[N_SLOTS];
+  for (Slot s : WAIT_ORDER) codes[s] = bh_msm_wait(jobs.take(s), sum_at(out, s));
+  BH_TRACE("waits done rc=%d %d %d %d %d %d %d %d", codes[0], codes[1], codes[2], codes[3], codes[4], codes[5], codes[6], codes[7]);
+  check(first_failure(p, codes));
+}
+
 }  // namespace detail
 void proof_slice_for_tests(size_t n, size_t part, size_t parts, size_t *lo, size_t *hi);   // groth16_prover.cpp
 double capture_check_for_tests(bellman::Circuit &shape_of, bellman::Circuit &proved, size_t out4[4]);   // groth16_prover.cpp
+// `circuit`'s witness into w (the constant one first, prover.rs:194); groth16_prover.cpp
+void synthesize_witness(bellman::Circuit &circuit, const R1cs &r1cs, WitnessAssignment &w);
 }  // namespace groth16
 
-// ---- pieces shared by the C entry points of the product (groth16_capi.cpp) and of the test library (demo_circuits.cpp)
+// ---- the C boundary: pieces shared by the entry points of the product (groth16_capi.cpp) and of the test library
+// (demo_circuits.cpp, groth16_callsites.cpp)
 struct bh_params {
   groth16::Parameters *p;
 };
 
-inline int run_guarded_sums(const std::function<groth16::MsmSums()> &f, void *sums_out) {
+// no C++ exception may cross the C boundary: runs body() and answers its return code, or the code of what it threw
+template <class F>
+int guarded(F &&body) {
   try {
-    groth16::MsmSums m = f();
-    memcpy(sums_out, &m, sizeof m);
-    return BH_OK;
+    return body();
+  } catch (const bellman::IoError &e) { return e.code;   // (thrown by the read paths only)
   } catch (const bellman::SynthesisError &e) { return e.code;
   } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
   } catch (...) { return BH_ERR_HIP; }
+}
+inline void write_proof(void *out384, const groth16::Proof &p) {
+  memcpy(out384, &p.a, 96);
+  memcpy((char *)out384 + 96, &p.b, 192);
+  memcpy((char *)out384 + 288, &p.c, 96);
+}
+inline void write_timings(float *timings4, const groth16::ProveTimings &tm) {
+  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
+}
+inline groth16::Fr read_fr(const void *mont32) {   // caller records may be unaligned
+  groth16::Fr f;
+  memcpy(&f, mont32, 32);
+  return f;
+}
+template <class F>
+int run_guarded_sums(F &&f, void *sums_out) {
+  return guarded([&] {
+    groth16::MsmSums m = f();
+    memcpy(sums_out, &m, sizeof m);
+    return BH_OK;
+  });
+}
+template <class F>
+int run_guarded(F &&f, void *proof_out) {
+  return guarded([&] {
+    write_proof(proof_out, f());
+    return BH_OK;
+  });
+}
+// The C form of a host-synthesised assignment as a view of the caller's arrays: they are only read as bytes (uploads, the
+// tiny input multiexps), never copied.  False for a null array that should hold something.
+inline bool assignment_view(const void *a_evals, const void *b_evals, const void *c_evals, size_t n_constraints,
+                            const void *input_assignment, size_t n_inputs, const void *aux_assignment, size_t n_aux,
+                            const uint64_t *a_aux_density, const uint64_t *b_input_density, const uint64_t *b_aux_density,
+                            groth16::AssignmentView *v) {
+  using groth16::Fr;
+  if ((n_constraints && (!a_evals || !b_evals || !c_evals)) || (n_inputs && (!input_assignment || !b_input_density)) ||
+      (n_aux && (!aux_assignment || !a_aux_density || !b_aux_density)))
+    return false;
+  *v = groth16::AssignmentView{(const Fr *)a_evals, (const Fr *)b_evals, (const Fr *)c_evals, n_constraints,
+                               (const Fr *)input_assignment, n_inputs, (const Fr *)aux_assignment, n_aux,
+                               a_aux_density, b_input_density, b_aux_density};
+  return true;
 }
 
 // a non-owning groth16::R1cs over a handle that belongs to the C caller
@@ -70,58 +249,12 @@ struct R1csView {
   ~R1csView() { r.handle = nullptr; }
 };
 
-inline int run_guarded(const std::function<groth16::Proof()> &f, void *proof_out) {
-  try {
-    groth16::Proof p = f();
-    memcpy(proof_out, &p.a, 96);
-    memcpy((char *)proof_out + 96, &p.b, 192);
-    memcpy((char *)proof_out + 288, &p.c, 96);
-    return BH_OK;
-  } catch (const bellman::SynthesisError &e) { return e.code;
-  } catch (const std::invalid_argument &) { return BH_ERR_INVALID_ARG;
-  } catch (...) { return BH_ERR_HIP; }
-}
-
-// bh_groth16_prove_witness_batch (and _checked), and the test library's twin with a workspace budget of its own (0: the default)
-inline int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
-                                       size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
-                                       float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO,
-                                       bool checked = false, uint32_t *first_unsatisfied = nullptr) {
-  using namespace groth16;
-  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
-  if (k && (!r || !s || !proofs_out || !rcs || (n_inputs && !inputs) || (n_aux && !aux))) return BH_ERR_INVALID_ARG;
-  ProveTimings tm = {0, 0, 0, 0};
-  int rc = BH_OK;
-  try {
-    R1csView view(r1cs);
-    // caller records may be unaligned: copied then (the witnesses of a large circuit are tens of megabytes each - an
-    // aligned caller's arrays are read in place)
-    std::vector<Fr> in, ax, rr(k), ss(k);
-    const Fr *in_p = (const Fr *)inputs, *ax_p = (const Fr *)aux;
-    if ((uintptr_t)inputs % alignof(Fr) && k * n_inputs) { in.resize(k * n_inputs); memcpy(in.data(), inputs, k * n_inputs * 32); in_p = in.data(); }
-    if ((uintptr_t)aux % alignof(Fr) && k * n_aux) { ax.resize(k * n_aux); memcpy(ax.data(), aux, k * n_aux * 32); ax_p = ax.data(); }
-    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
-    std::vector<WitnessView> ws(k);
-    for (size_t j = 0; j < k; j++) ws[j] = WitnessView{in_p + j * n_inputs, n_inputs, ax_p + j * n_aux, n_aux};
-    std::vector<Proof> proofs(k);
-    std::vector<int> codes(k, BH_OK);
-    if (checked)   // bh_groth16_prove_witness_batch_checked: the check pre-pass, then the satisfied witnesses as below
-      prove_witness_batch_checked_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(),
-                                        first_unsatisfied, &tm, workspace_budget, mode);
-    else
-      prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
-    for (size_t j = 0; j < k; j++) {
-      char *out = (char *)proofs_out + j * 384;
-      rcs[j] = codes[j];
-      if (codes[j] == BH_OK) { memcpy(out, &proofs[j].a, 96); memcpy(out + 96, &proofs[j].b, 192); memcpy(out + 288, &proofs[j].c, 96); }
-      else memset(out, 0, 384);
-    }
-  } catch (const bellman::SynthesisError &e) { rc = e.code;
-  } catch (const std::invalid_argument &) { rc = BH_ERR_INVALID_ARG;
-  } catch (...) { rc = BH_ERR_HIP; }
-  if (timings4) { timings4[0] = tm.synthesis_ms; timings4[1] = tm.h_poly_ms; timings4[2] = tm.msm_ms; timings4[3] = tm.total_ms; }
-  return rc;
-}
+// bh_groth16_prove_witness_batch (and _checked), and the test library's twins with a workspace budget and a mode of their
+// own (0: the default); groth16_prover.cpp
+int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
+                                size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
+                                float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO, bool checked = false,
+                                uint32_t *first_unsatisfied = nullptr);
 
 struct bh_proof_job {
   // members are destroyed in reverse order: the job (whose destructor joins the helper thread) before the view of the

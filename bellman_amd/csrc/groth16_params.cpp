@@ -126,13 +126,9 @@ Parameters::Parameters(bh_ctx *c, R1cs &r1cs, const G1Affine &g1, const G2Affine
     throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
   const Fr gamma_inv = gamma.invert(), delta_inv = delta.invert();
   const size_t n_cons = r1cs.num_constraints, n_in = r1cs.num_inputs, n_vars = r1cs.num_inputs + r1cs.num_aux;
-  uint32_t log_m = 0;
-  size_t m = 1;
-  while (m < n_cons) {   // EvaluationDomain::from_coeffs, generator.rs:204-205
-    m *= 2;
-    log_m++;
-    if (log_m >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const Domain dom = domain_of(n_cons);   // generator.rs:204-205
+  const size_t m = dom.m;
+  const uint32_t log_m = dom.log_m;
   const Fr one = Fr::one();
   // h query: g1^(tau^i * t(tau) / delta), i < m - 1                                      generator.rs:247-296
   const Fr coeff = (tau.pow_vartime(m) - one) * delta_inv;
@@ -197,13 +193,9 @@ void check_arg(int rc) {
 Parameters::Parameters(bh_ctx *c, R1cs &r1cs, const PowersOfTau &t, PtauTimings *tm) : ctx(c) {
   if (!t.tau_g1 || !t.tau_g2 || !t.alpha_tau_g1 || !t.beta_tau_g1) throw std::invalid_argument("PowersOfTau: null handle");
   const size_t n_cons = r1cs.num_constraints, n_in = r1cs.num_inputs, n_vars = r1cs.num_inputs + r1cs.num_aux;
-  uint32_t log_m = 0;
-  size_t m = 1;
-  while (m < n_cons) {   // EvaluationDomain::from_coeffs, generator.rs:204-205
-    m *= 2;
-    log_m++;
-    if (log_m >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const Domain dom = domain_of(n_cons);   // generator.rs:204-205
+  const size_t m = dom.m;
+  const uint32_t log_m = dom.log_m;
   StreamGuard s(ctx);
   const bh_bases *vec[4] = {t.tau_g1, t.tau_g2, t.alpha_tau_g1, t.beta_tau_g1};
   const int grp[4] = {BH_G1, BH_G2, BH_G1, BH_G1};

@@ -155,22 +155,6 @@ struct StreamDrain {
   ProofStream &ps;
   ~StreamDrain() { if (ps.st) (void)bh_stream_synchronize(ps.ctx, ps.st); }
 };
-// Every issued multiexp owns device buffers and reads ours: if anything throws between issue and
-// wait, the jobs still in flight are drained before the DevBufs they read are released.
-struct JobSet {
-  std::vector<bh_msm_job **> slots;
-  void track(bh_msm_job **j) { slots.push_back(j); }
-  int wait(bh_msm_job *&j, void *out) {
-    bh_msm_job *job = j;
-    j = nullptr;
-    return bh_msm_wait(job, out);
-  }
-  ~JobSet() {
-    unsigned char sink[192];
-    for (bh_msm_job **s : slots)
-      if (*s) { (void)bh_msm_wait(*s, sink); *s = nullptr; }
-  }
-};
 template <class A> A add_pts(int group, const A &x, const A &y) { A r; bh_point_add(group, &r, &x, &y, 1); return r; }
 template <class A> A mul_pt(int group, const A &x, const Fr &k) {
   uint64_t kc[4];
@@ -211,11 +195,6 @@ Slice slice_of(size_t n, size_t part, size_t parts) {
   };
   return Slice{cut(part), cut(part + 1)};
 }
-size_t popcount_prefix(const uint64_t *words, size_t bits) {   // bits is a multiple of 64
-  size_t t = 0;
-  for (size_t w = 0; w < bits / 64; w++) t += (size_t)__builtin_popcountll(words[w]);
-  return t;
-}
 }  // namespace
 
 // test hook (host only): the slice of an n-term multiexp part `part` of `parts` computes
@@ -226,101 +205,68 @@ void proof_slice_for_tests(size_t n, size_t part, size_t parts, size_t *lo, size
 }
 
 // prover.rs:217-318 + the waits of :339-354: the eight multiexp results (of this part's slices)
-// `while_running` (optional) is host work that needs no multiexp result: it runs after the last job has been
-// issued and before the first wait, i.e. while the GPU is busy
-static void msm_sums(const AssignmentSource &src, Parameters &params, size_t part, size_t parts, MsmSums &out,
-                     ProveTimings *tm, const std::function<void()> *while_running = nullptr) {
+static void msm_sums(const AssignmentSource &src, Parameters &params, size_t part, size_t parts, MsmSums &out, ProveTimings *tm) {
   bh_ctx *ctx = params.ctx;
   const double t0 = now_ms();
   const size_t n_cons = src.n_cons;
-  // EvaluationDomain::from_coeffs (domain.rs:47-79)
-  uint32_t log_m = 0;
-  size_t m = 1;
-  while (m < n_cons) {
-    m *= 2;
-    log_m++;
-    if (log_m >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const Domain dom = domain_of(n_cons);
+  const size_t m = dom.m;
+  const uint32_t log_m = dom.log_m;
   // assignments: uploaded once, shared by seven multiexps (prover.rs:248-318)
   const size_t n_in = src.n_in, n_aux = src.n_aux;
   DevBuf d_in(ctx, n_in * 32 + 32), d_aux(ctx, n_aux * 32 + 32);
   ProofStream ps(ctx);
   check(bh_dev_upload_on(ctx, d_in.p, src.inputs, n_in * 32, ps.st));
   if (n_aux) check(bh_dev_upload_on(ctx, d_aux.p, src.aux, n_aux * 32, ps.st));
-  std::unique_ptr<DevBuf> dens_buf[3];
-  const uint64_t *dens_a_aux = nullptr, *dens_b_in = nullptr, *dens_b_aux = nullptr;
-  const uint64_t *hw_a_aux = nullptr, *hw_b_in = nullptr, *hw_b_aux = nullptr;   // the same bitmaps on the host
-  size_t b_in_total = 0;
+  Densities dens;
   if (src.host) {
-    auto upload_density = [&](const uint64_t *words, size_t bits, std::unique_ptr<DevBuf> &buf) {
-      const size_t nw = (bits + 63) / 64;
-      buf.reset(new DevBuf(ctx, nw * 8 + 8));
-      if (nw) check(bh_dev_upload_on(ctx, buf->p, words, nw * 8, ps.st));
-      return (const uint64_t *)buf->p;
-    };
-    dens_a_aux = upload_density(src.a_aux_density, n_aux, dens_buf[0]);
-    dens_b_in = upload_density(src.b_input_density, n_in, dens_buf[1]);
-    dens_b_aux = upload_density(src.b_aux_density, n_aux, dens_buf[2]);
-    for (size_t w = 0; w < (n_in + 63) / 64; w++) {   // get_total_density (multiexp.rs:154-156)
-      uint64_t x = src.b_input_density[w];
-      if (w == n_in / 64 && (n_in & 63)) x &= (uint64_t(1) << (n_in & 63)) - 1;
-      b_in_total += (size_t)__builtin_popcountll(x);
-    }
-    hw_a_aux = src.a_aux_density; hw_b_in = src.b_input_density; hw_b_aux = src.b_aux_density;
+    dens.on_host(src.a_aux_density, src.b_input_density, src.b_aux_density, n_in);
+    dens.upload(ctx, n_in, n_aux, ps.st);
   } else {
-    check(bh_r1cs_density(src.r1cs->handle, 0, &dens_a_aux, &hw_a_aux, nullptr));
-    check(bh_r1cs_density(src.r1cs->handle, 1, &dens_b_in, &hw_b_in, &b_in_total));
-    check(bh_r1cs_density(src.r1cs->handle, 2, &dens_b_aux, &hw_b_aux, nullptr));
+    dens.of(*src.r1cs);
   }
+  const QueryTable queries_of = queries(params, n_in, dens.b_in_total);
 
   BH_TRACE("prove_core start: uploads queued");
   check(bh_stream_synchronize(ctx, ps.st));   // the multiexp jobs run on their own streams
   BH_TRACE("assignment resident");
-  bh_msm_job *l_job = nullptr, *a_in_job = nullptr, *a_aux_job = nullptr, *b1_in_job = nullptr, *b1_aux_job = nullptr,
-             *b2_in_job = nullptr, *b2_aux_job = nullptr, *h_job = nullptr;
   // h-block buffers are declared here so that `jobs` (declared after every buffer a job reads) is
   // destroyed first and drains whatever is still in flight if an exception unwinds this frame
   DevBuf da(ctx, m * 32), db(ctx, m * 32), dc(ctx, m * 32);
   StreamDrain drain{ps};
-  JobSet jobs;
-  for (bh_msm_job **j : {&l_job, &a_in_job, &a_aux_job, &b1_in_job, &b1_aux_job, &b2_in_job, &b2_aux_job, &h_job}) jobs.track(j);
-  // one multiexp over this part's slice of the scalars: `skip` advances by the number of bases the
-  // skipped scalars would have consumed (all of them without a density map, the set bits with one)
+  InFlight<bh_msm_job> jobs(N_SLOTS);
   DevBuf dscratch(ctx, log_m > 11 ? m * 32 : 32);   // FFT ping-pong vector of the h block
   StreamDrain drain2{ps};                            // (drains before dscratch is released)
   // (A two-phase issue - BH_MSM_HOLD / bh_msm_start: first every job's digit + sort stage, then the bucket accumulations in
   // chain order - was measured for proofs above 2^16 and is not used: no gain for one proof and 12 % less throughput with
   // twelve in flight, the sorts of one proof no longer fill the gaps of another; profiles/archive/r3_call6_hold_ab.txt.)
-  auto issue = [&](bh_bases *bases, size_t skip, const void *scalars, size_t n, const uint64_t *dens_dev,
-                   const uint64_t *dens_host, bh_msm_job **job, const void *scalars_host = nullptr) {
+  // one multiexp over this part's slice of the slot's scalars: the bases advance by what the skipped scalars would have
+  // consumed (all of them without a density map, the set bits with one)
+  struct SlotSlice { const Query &q; const void *scalars_dev; Slice sl; size_t base_skip; };
+  auto slice_for = [&](Slot slot) {
+    const Query &q = queries_of[slot];
+    const size_t n = q.scalars == FROM_INPUTS ? n_in : q.scalars == FROM_AUX ? n_aux : m - 1;   // a.len() - 1, :238-244
+    const void *dev = q.scalars == FROM_INPUTS ? d_in.p : q.scalars == FROM_AUX ? d_aux.p : da.p;
     const Slice sl = slice_of(n, part, parts);
-    const size_t base_skip = skip + (dens_dev ? popcount_prefix(dens_host, sl.lo) : sl.lo);
-    if (scalars_host && sl.hi - sl.lo <= 8) {
+    return SlotSlice{q, dev, sl, q.skip + (q.density >= 0 ? popcount_bits(dens.host_of(q.density), sl.lo) : sl.lo)};
+  };
+  auto issue = [&](Slot slot) {
+    const SlotSlice s = slice_for(slot);
+    const size_t n = s.sl.hi - s.sl.lo;
+    const uint64_t *dens_dev = dens.dev_of(s.q.density), *dens_host = dens.host_of(s.q.density);
+    if (s.q.scalars == FROM_INPUTS && n <= 8) {
       // the `inputs` multiexps have one or two terms: handed over with their host scalars, the library
       // answers them on the host instead of running a kernel pipeline per term
-      check(bh_msm_async(ctx, bases, base_skip, (const char *)scalars_host + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT,
-                         dens_host ? dens_host + sl.lo / 64 : nullptr, dens_host ? sl.hi - sl.lo : 0, job));
-      BH_TRACE("  multiexp of %zu terms answered on the host", sl.hi - sl.lo);
+      check(bh_msm_async(ctx, s.q.bases, s.base_skip, (const char *)src.inputs + s.sl.lo * 32, n, BH_SCALARS_MONT,
+                         dens_host ? dens_host + s.sl.lo / 64 : nullptr, dens_host ? n : 0, &jobs.at[slot]));
+      BH_TRACE("  multiexp of %zu terms answered on the host", n);
       return;
     }
-    check(bh_msm_async_dev(ctx, bases, base_skip, (const char *)scalars + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT,
-                           dens_dev ? dens_dev + sl.lo / 64 : nullptr, dens_dev ? sl.hi - sl.lo : 0, job));
-    BH_TRACE("  multiexp of %zu terms issued", sl.hi - sl.lo);
+    check(bh_msm_async_dev(ctx, s.q.bases, s.base_skip, (const char *)s.scalars_dev + s.sl.lo * 32, n, BH_SCALARS_MONT,
+                           dens_dev ? dens_dev + s.sl.lo / 64 : nullptr, dens_dev ? n : 0, &jobs.at[slot]));
+    BH_TRACE("  multiexp of %zu terms issued", n);
   };
-  auto issue_seven = [&](bool longest_first) {
-    // get_b_g1/g2(b_input_density_total, _) -> ((b,0),(b,total))   groth16/src/lib.rs:459-473
-    // (small proofs: the G2 multiexp is the longest job, and the host needs ~0.2 ms to enqueue each job's ~20 launches:
-    //  what is issued last finishes last)
-    if (longest_first) issue(params.b_g2, b_in_total, d_aux.p, n_aux, dens_b_aux, hw_b_aux, &b2_aux_job);
-    issue(params.l, 0, d_aux.p, n_aux, nullptr, nullptr, &l_job);
-    // get_a(num_inputs, _) -> ((a,0),(a,num_inputs))            groth16/src/lib.rs:451-457
-    issue(params.a, 0, d_in.p, n_in, nullptr, nullptr, &a_in_job, src.inputs);
-    issue(params.a, n_in, d_aux.p, n_aux, dens_a_aux, hw_a_aux, &a_aux_job);
-    issue(params.b_g1, 0, d_in.p, n_in, dens_b_in, hw_b_in, &b1_in_job, src.inputs);
-    issue(params.b_g1, b_in_total, d_aux.p, n_aux, dens_b_aux, hw_b_aux, &b1_aux_job);
-    issue(params.b_g2, 0, d_in.p, n_in, dens_b_in, hw_b_in, &b2_in_job, src.inputs);
-    if (!longest_first) issue(params.b_g2, b_in_total, d_aux.p, n_aux, dens_b_aux, hw_b_aux, &b2_aux_job);
-  };
+  auto issue_seven = [&] { for (Slot slot : ISSUE_ORDER) issue(slot); };
   // h block (prover.rs:221-245), enqueue only: a, b, c stay in HBM; the quotient's coefficients are consumed by the
   // H multiexp straight from device memory (no host round trip, no serial Fr -> Exponent pass)
   auto enqueue_h_block = [&] {
@@ -350,14 +296,14 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
   if (log_m <= 16) {
     std::exception_ptr helper_error;
     std::thread helper([&] {
-      try { issue_seven(true); } catch (...) { helper_error = std::current_exception(); }
+      try { issue_seven(); } catch (...) { helper_error = std::current_exception(); }
     });
     try {
       enqueue_h_block();
       BH_TRACE("h block enqueued");
       check(bh_stream_synchronize(ctx, ps.st));
       t1 = now_ms();
-      issue(params.h, 0, da.p, m - 1, nullptr, nullptr, &h_job);   // a.len() - 1, :238-244
+      issue(H);
     } catch (...) {
       helper.join();
       throw;
@@ -369,49 +315,28 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
     // them.  With the constraints evaluated on the device the h block is enqueued FIRST - nothing on the host delays it,
     // and started late it queues behind the multiexps' long kernels, the H multiexp then runs alone at the end
     // (profiles/archive/r3_call2_proof_timeline.txt).  With host evaluations the multiexps go first: the GPU works while the
-    // host stages a, b, c (96 MiB of pageable memory at 2^20).
-    auto issue_h = [&] {
-      const Slice sl = slice_of(m - 1, part, parts);   // a.len() - 1, :238-244
-      check(bh_msm_async_dev_after(ctx, params.h, sl.lo, (const char *)da.p + sl.lo * 32, sl.hi - sl.lo, BH_SCALARS_MONT, nullptr,
-                                   0, nullptr, ps.st, &h_job));
-    };
-    // Issue order = order of the bucket accumulations on the device (the accumulation chain, common.hpp): the G2
-    // multiexp first - the longest job, its reduction tail then runs beside the G1 accumulations - and H last, by which
-    // time the h block (enqueued first when nothing on the host delays it) has long finished beside the others.
+    // host stages a, b, c (96 MiB of pageable memory at 2^20).  H comes last, by which time the h block has long finished
+    // beside the others.
     if (!src.host) {
       enqueue_h_block();
       // the accumulations wait for the h block (their digit / sort stages run beside it): behind the G2 accumulation's
       // 5 ms workgroups an FFT pass waits for a free SIMD, and the h block took 17 ms (profiles/archive/r3_call4_proof_timeline.txt)
       check(bh_ctx_accumulations_after(ctx, ps.st));
     }
-    issue_seven(true);
+    issue_seven();
     if (src.host) enqueue_h_block();
-    issue_h();
+    const SlotSlice h = slice_for(H);
+    check(bh_msm_async_dev_after(ctx, h.q.bases, h.base_skip, (const char *)h.scalars_dev + h.sl.lo * 32, h.sl.hi - h.sl.lo,
+                                 BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &jobs.at[H]));
     BH_TRACE("7 multiexps + h block + H issued; n_cons=%zu m=%zu", n_cons, m);
     t1 = now_ms();
   }
 
   BH_TRACE("all msm issued n_in=%zu n_aux=%zu", n_in, n_aux);
-  if (while_running) (*while_running)();
-  // every job must be waited on (it owns device resources), even when an earlier one fails
-  int rcs[8];
-  // prover.rs:339-354 waits in this order: a_inputs, a_aux, b_g1_inputs, b_g1_aux, b_g2_inputs, b_g2_aux, h, l
-  rcs[0] = jobs.wait(a_in_job, &out.a_in);
-  rcs[1] = jobs.wait(a_aux_job, &out.a_aux);
-  rcs[2] = jobs.wait(b1_in_job, &out.b1_in);
-  rcs[3] = jobs.wait(b1_aux_job, &out.b1_aux);
-  rcs[4] = jobs.wait(b2_in_job, &out.b2_in);
-  rcs[5] = jobs.wait(b2_aux_job, &out.b2_aux);
-  rcs[6] = jobs.wait(h_job, &out.h);
-  rcs[7] = jobs.wait(l_job, &out.l);
-  const double t2 = now_ms();
-  BH_TRACE("waits done rc=%d %d %d %d %d %d %d %d", rcs[0], rcs[1], rcs[2], rcs[3], rcs[4], rcs[5], rcs[6], rcs[7]);
-  if (params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity())   // subversion check, prover.rs:320-324
-    throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
-  for (int i = 0; i < 8; i++) check(rcs[i]);                      // first failing `?` in wait order
+  wait_eight(jobs, params, out);
   if (tm) {
     tm->h_poly_ms = (float)(t1 - t0);
-    tm->msm_ms = (float)(t2 - t1);
+    tm->msm_ms = (float)(now_ms() - t1);
     tm->total_ms = (float)(now_ms() - t0);
   }
 }
@@ -472,45 +397,74 @@ void MsmSums::add(const MsmSums &o) {
   h = add_pts(BH_G1, h, o.h); l = add_pts(BH_G1, l, o.l);
 }
 
+// The blinding terms of k (r, s) pairs on min(k, 8) helper threads, started at construction.  They involve only the
+// verifying key, r and s (prover.rs:326-338; five scalar multiplications, ~0.9 ms of host arithmetic per proof) and run
+// beside the enqueueing of the multiexps and the GPU work: for a small proof they are as long as everything else
+// together.  A failure there (identity delta) is kept in `error`, to be reported after the jobs drain.
+struct Blinding {
+  std::vector<ProofBlinding> terms;
+  std::exception_ptr error;
+  Blinding(const Parameters &params, const Fr *r, const Fr *s, size_t k) : terms(k) {
+    const size_t n_threads = std::min<size_t>(k, 8);
+    for (size_t t = 0; t < n_threads; t++)
+      threads_.emplace_back([this, &params, r, s, k, t, n_threads] {
+        try {
+          for (size_t j = t; j < k; j += n_threads) terms[j] = blind_terms(params, r[j], s[j]);
+        } catch (...) {
+          std::lock_guard<std::mutex> g(mu_);
+          if (!error) error = std::current_exception();
+        }
+      });
+  }
+  void join() { for (std::thread &t : threads_) if (t.joinable()) t.join(); }
+  ~Blinding() { join(); }
+
+ private:
+  std::mutex mu_;
+  std::vector<std::thread> threads_;
+};
+
 static Proof prove_core(const AssignmentSource &src, Parameters &params, const Fr &r, const Fr &s, ProveTimings *tm) {
   const double t0 = now_ms();
   MsmSums sums;
-  // the five scalar multiplications that involve only the verifying key, r and s (prover.rs:326-338; ~0.9 ms of host
-  // arithmetic) run on their own host thread from the start, beside the enqueueing of the multiexps and the GPU
-  // work: for a small proof they are as long as everything else together.  A failure there (identity delta) is
-  // reported after the jobs drain.
-  ProofBlinding blind;
-  std::exception_ptr blind_err;
-  std::thread blind_thread([&] {
-    try { blind = blind_terms(params, r, s); } catch (...) { blind_err = std::current_exception(); }
-  });
+  Blinding blind(params, &r, &s, 1);
   std::exception_ptr msm_err;
   try {
-    msm_sums(src, params, 0, 1, sums, tm, nullptr);
+    msm_sums(src, params, 0, 1, sums, tm);
   } catch (...) {
-    msm_err = std::current_exception();   // every job has been drained by now (JobSet)
+    msm_err = std::current_exception();   // every job has been drained by now (InFlight)
   }
-  blind_thread.join();
-  // prover.rs:320-324 returns UnexpectedIdentity for an identity delta BEFORE any multiexp is waited on: that error
-  // takes precedence over whatever a multiexp reports (e.g. UnexpectedEof from a short query)
-  if (blind_err) std::rethrow_exception(blind_err);
+  blind.join();
+  // an identity delta takes precedence over whatever a multiexp reports (first_failure, groth16_internal.hpp)
+  if (blind.error) std::rethrow_exception(blind.error);
   if (msm_err) std::rethrow_exception(msm_err);
-  Proof p = finish_proof(blind, sums, r, s);
+  Proof p = finish_proof(blind.terms[0], sums, r, s);
   if (tm) tm->total_ms = (float)(now_ms() - t0);
   return p;
 }
 
-MsmSums prove_witness_part(const R1cs &r1cs, Parameters &params, const Fr *inputs, size_t n_inputs, const Fr *aux, size_t n_aux,
-                           size_t part, size_t parts, ProveTimings *tm) {
-  if (n_inputs != r1cs.num_inputs || n_aux != r1cs.num_aux || parts == 0 || part >= parts)
-    throw std::invalid_argument("witness does not have the shape of the captured circuit / bad part");
+// a witness has the shape of the captured circuit, or std::invalid_argument - before anything runs
+static void require_shape(const R1cs &r1cs, const WitnessView *witnesses, size_t k) {
+  for (size_t j = 0; j < k; j++)
+    if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
+      throw std::invalid_argument("witness does not have the shape of the captured circuit");
+}
+static AssignmentSource resident_source(const R1cs &r1cs, const Fr *inputs, size_t n_inputs, const Fr *aux, size_t n_aux) {
+  const WitnessView w{inputs, n_inputs, aux, n_aux};
+  require_shape(r1cs, &w, 1);
   AssignmentSource src;
   src.inputs = inputs; src.n_in = n_inputs;
   src.aux = aux; src.n_aux = n_aux;
   src.n_cons = r1cs.num_constraints;
   src.r1cs = &r1cs;
+  return src;
+}
+
+MsmSums prove_witness_part(const R1cs &r1cs, Parameters &params, const Fr *inputs, size_t n_inputs, const Fr *aux, size_t n_aux,
+                           size_t part, size_t parts, ProveTimings *tm) {
+  if (parts == 0 || part >= parts) throw std::invalid_argument("bad part");
   MsmSums sums;
-  msm_sums(src, params, part, parts, sums, tm);
+  msm_sums(resident_source(r1cs, inputs, n_inputs, aux, n_aux), params, part, parts, sums, tm);
   return sums;
 }
 
@@ -536,14 +490,7 @@ Proof prove_assignment(const AssignmentView &v, Parameters &params, const Fr &r,
 
 Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *inputs, size_t n_inputs, const Fr *aux, size_t n_aux,
                     const Fr &r, const Fr &s, ProveTimings *tm) {
-  if (n_inputs != r1cs.num_inputs || n_aux != r1cs.num_aux)
-    throw std::invalid_argument("witness does not have the shape of the captured circuit");
-  AssignmentSource src;
-  src.inputs = inputs; src.n_in = n_inputs;
-  src.aux = aux; src.n_aux = n_aux;
-  src.n_cons = r1cs.num_constraints;
-  src.r1cs = &r1cs;
-  return prove_core(src, params, r, s, tm);
+  return prove_core(resident_source(r1cs, inputs, n_inputs, aux, n_aux), params, r, s, tm);
 }
 
 // ---- k proofs of one circuit in one call ------------------------------------------------------------
@@ -552,23 +499,6 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *inputs, size
 // of a group (bh_msm_many_async_dev: one launch chain for the group where the library's size rule takes the many-plan, k
 // ordinary jobs otherwise), the h blocks run one after the other on one stream into strided coefficient vectors, and the
 // `inputs` multiexps and finish_proof stay per witness.  Error order per proof: prove_core's.
-namespace {
-struct ManyJobSet {   // as JobSet: every issued many-job is waited on even when something throws in between
-  std::vector<bh_msm_many_job **> slots;
-  void track(bh_msm_many_job **j) { slots.push_back(j); }
-  ~ManyJobSet() {
-    for (bh_msm_many_job **s : slots)
-      if (*s) { (void)bh_msm_many_wait(*s, nullptr, nullptr, nullptr, nullptr); *s = nullptr; }
-  }
-};
-}  // namespace
-
-// Where the grouped path (many-jobs over a group of witnesses) replaces k proofs in flight without being asked to.
-// Measured (tools/bench_prove_batch.py, profiles/prove_batch_bench.json: MiMC-322 and the chain circuit at 2^14 / 2^16 / 2^18
-// constraints, k = 4 and 16): against k prove_witness_async calls in flight it is 0.51 - 0.66 x on MiMC-322 and 0.97 - 1.29 x
-// on the chain circuit, beyond the baseline's own spread at two shapes of eight (k = 16 at 2^16 and 2^18) - and at another
-// one (2^16, k = 4) in the run before.  No basis for a rule yet: it is "never", and the call runs the proofs in flight,
-// BATCH_IN_FLIGHT at a time.
 // The witnesses w[0 .. g) into two strided device buffers (strides = the vectors' lengths), on stream st.  With `coalesce`
 // and every host vector starting where the one before ends, ONE upload per vector kind; otherwise one per witness.
 static void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *d_in, void *d_aux, void *st, bool coalesce) {
@@ -589,9 +519,7 @@ static void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *
 
 // which_is_unsatisfied for k witnesses: groups whose device copies stay within `budget` bytes, one bh_r1cs_check_many_dev each
 static std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, const WitnessView *witnesses, size_t k, size_t budget) {
-  for (size_t j = 0; j < k; j++)
-    if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
-      throw std::invalid_argument("witness does not have the shape of the captured circuit");
+  require_shape(r1cs, witnesses, k);
   if (!ctx) throw std::invalid_argument("the R1cs handle was adopted without its context");
   std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
   if (!k) return first_bad;
@@ -610,20 +538,18 @@ static std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, cons
   return first_bad;
 }
 
-static bool grouped_batch_wins(size_t n_constraints, size_t k) {
-  (void)n_constraints; (void)k;
-  return false;
-}
-
 void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r, const Fr *s,
                                Proof *proofs, int *codes, ProveTimings *tm, size_t workspace_budget, int mode) {
-  for (size_t j = 0; j < k; j++)
-    if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
-      throw std::invalid_argument("witness does not have the shape of the captured circuit");
+  require_shape(r1cs, witnesses, k);
   if (tm) *tm = ProveTimings{0, 0, 0, 0};
   if (!k) return;
   const double t0 = now_ms();
-  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && mode != BATCH_GROUPED_HE && !grouped_batch_wins(r1cs.num_constraints, k)) {
+  // BATCH_AUTO never takes the grouped path (many-jobs over a group of witnesses) by itself.  Measured
+  // (tools/bench_prove_batch.py, profiles/prove_batch_bench.json: MiMC-322 and the chain circuit at 2^14 / 2^16 / 2^18
+  // constraints, k = 4 and 16): against k prove_witness_async calls in flight it is 0.51 - 0.66 x on MiMC-322 and
+  // 0.97 - 1.29 x on the chain circuit, beyond the baseline's own spread at two shapes of eight (k = 16 at 2^16 and 2^18) -
+  // and at another one (2^16, k = 4) in the run before.  No basis for a rule yet.
+  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && mode != BATCH_GROUPED_HE) {
     // k proofs by the single-proof path, BATCH_IN_FLIGHT of them in flight (device memory stays bounded), waited in order
     std::vector<std::unique_ptr<AsyncProof>> jobs(k);
     auto finish = [&](size_t j) {
@@ -648,14 +574,10 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     return;
   }
   bh_ctx *ctx = params.ctx;
-  const size_t n_in = r1cs.num_inputs, n_aux = r1cs.num_aux, n_cons = r1cs.num_constraints;
-  uint32_t log_m = 0;
-  size_t m = 1;
-  while (m < n_cons) {
-    m *= 2;
-    log_m++;
-    if (log_m >= 32) throw SynthesisError(BH_ERR_DEGREE_TOO_LARGE, "PolynomialDegreeTooLarge");
-  }
+  const size_t n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
+  const Domain dom = domain_of(r1cs.num_constraints);
+  const size_t m = dom.m;
+  const uint32_t log_m = dom.log_m;
   // group size: g coefficient vectors (the a vector of each h block, which becomes its quotient) plus the b and c vectors
   // and the FFT scratch, which the h blocks of a group share (they run one after the other on one stream)
   const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
@@ -666,34 +588,13 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   size_t group = batched_h ? std::max<size_t>(budget / (4 * vec), 1) : budget / vec > 3 ? budget / vec - 3 : 1;
   if (group > k) group = k;
   if (group > 4096) group = 4096;
-  // the blinding terms (five host scalar multiplications per proof) on helper threads, beside the GPU work
-  std::vector<ProofBlinding> blind(k);
-  std::exception_ptr blind_err;
-  std::mutex blind_mu;
-  const size_t n_threads = std::min<size_t>(k, 8);
-  std::vector<std::thread> blind_threads;
-  for (size_t t = 0; t < n_threads; t++)
-    blind_threads.emplace_back([&, t] {
-      try {
-        for (size_t j = t; j < k; j += n_threads) blind[j] = blind_terms(params, r[j], s[j]);
-      } catch (...) {
-        std::lock_guard<std::mutex> g(blind_mu);
-        if (!blind_err) blind_err = std::current_exception();
-      }
-    });
-  struct Joiner {
-    std::vector<std::thread> &ts;
-    ~Joiner() { for (std::thread &t : ts) if (t.joinable()) t.join(); }
-  } joiner{blind_threads};
+  Blinding blind(params, r, s, k);   // beside the GPU work
 
-  const uint64_t *dens_a_aux = nullptr, *dens_b_in = nullptr, *dens_b_aux = nullptr;
-  const uint64_t *hw_a_aux = nullptr, *hw_b_in = nullptr, *hw_b_aux = nullptr;
-  size_t b_in_total = 0;
-  check(bh_r1cs_density(r1cs.handle, 0, &dens_a_aux, &hw_a_aux, nullptr));
-  check(bh_r1cs_density(r1cs.handle, 1, &dens_b_in, &hw_b_in, &b_in_total));
-  check(bh_r1cs_density(r1cs.handle, 2, &dens_b_aux, &hw_b_aux, nullptr));
+  Densities dens;
+  dens.of(r1cs);
+  const QueryTable queries_of = queries(params, n_in, dens.b_in_total);
   std::vector<MsmSums> sums(k);
-  std::vector<std::array<int, 8>> rcs(k);
+  std::vector<std::array<int, N_SLOTS>> rcs(k);
   double h_ms = 0, msm_ms = 0;
   for (size_t first = 0; first < k; first += group) {
     const size_t g = std::min(group, k - first);
@@ -704,23 +605,19 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     DevBuf da(ctx, g * vec), db(ctx, bc_vecs * vec), dc(ctx, bc_vecs * vec), dscratch(ctx, scratch_bytes);
     ProofStream ps(ctx);
     StreamDrain drain{ps};
-    std::vector<bh_msm_job *> in_jobs(3 * g, nullptr);
-    bh_msm_many_job *l_job = nullptr, *a_job = nullptr, *b1_job = nullptr, *b2_job = nullptr, *h_job = nullptr;
-    JobSet jobs;
-    for (bh_msm_job *&j : in_jobs) jobs.track(&j);
-    ManyJobSet many_jobs;
-    for (bh_msm_many_job **j : {&l_job, &a_job, &b1_job, &b2_job, &h_job}) many_jobs.track(j);
+    InFlight<bh_msm_job> in_jobs(g * N_SLOTS);   // witness j's `inputs` multiexps at j * N_SLOTS + slot
+    InFlight<bh_msm_many_job> many_jobs(N_SLOTS);
     // 1. the witnesses, one strided buffer each (BATCH_GROUPED_HE: in one upload each where the host vectors are adjacent)
     upload_witnesses(ctx, witnesses + first, g, d_in.p, d_aux.p, ps.st, many_eval);
-    // 2. four many-jobs over the aux vectors and the shared bases and densities, ordered after the uploads
-    // G2 first: the longest job
-    check(bh_msm_many_async_dev(ctx, params.b_g2, b_in_total, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_b_aux,
-                                dens_b_aux ? n_aux : 0, nullptr, ps.st, &b2_job));
-    check(bh_msm_many_async_dev(ctx, params.l, 0, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &l_job));
-    check(bh_msm_many_async_dev(ctx, params.a, n_in, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_a_aux,
-                                dens_a_aux ? n_aux : 0, nullptr, ps.st, &a_job));
-    check(bh_msm_many_async_dev(ctx, params.b_g1, b_in_total, d_aux.p, aux_stride, n_aux, g, BH_SCALARS_MONT, dens_b_aux,
-                                dens_b_aux ? n_aux : 0, nullptr, ps.st, &b1_job));
+    // 2. the many-jobs over the aux vectors and the shared bases and densities, ordered after the uploads
+    auto issue_many = [&](Slot slot, const void *scalars, size_t stride, size_t n) {
+      const Query &q = queries_of[slot];
+      const uint64_t *d = dens.dev_of(q.density);
+      check(bh_msm_many_async_dev(ctx, q.bases, q.skip, scalars, stride, n, g, BH_SCALARS_MONT, d, d ? n : 0, nullptr, ps.st,
+                                  &many_jobs.at[slot]));
+    };
+    for (Slot slot : ISSUE_ORDER)
+      if (queries_of[slot].scalars == FROM_AUX) issue_many(slot, d_aux.p, aux_stride, n_aux);
     // 3. the h block per witness, on one stream, into the group's strided coefficient vectors; then the H many-job,
     // ordered after them
     if (many_eval)
@@ -734,58 +631,49 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
     }
     if (batched_h)
       check(bh_h_poly_fr_many_dev_on(ctx, da.p, db.p, dc.p, vec, g, log_m, BH_FFT_MANY_FORCE, dscratch.p, scratch_bytes, ps.st));
-    check(bh_msm_many_async_dev(ctx, params.h, 0, da.p, vec, m - 1, g, BH_SCALARS_MONT, nullptr, 0, nullptr, ps.st, &h_job));   // a.len() - 1
+    issue_many(H, da.p, vec, m - 1);   // a.len() - 1
     // 4. the `inputs` multiexps as the single call issues them (a handful of terms: answered on the host, at issue time -
     // so they come last, while the GPU works)
-    for (size_t j = 0; j < g; j++) {
-      const WitnessView &w = witnesses[first + j];
-      struct In { bh_bases *bases; const uint64_t *dens_dev, *dens_host; } q[3] = {
-          {params.a, nullptr, nullptr}, {params.b_g1, dens_b_in, hw_b_in}, {params.b_g2, dens_b_in, hw_b_in}};
-      for (int t = 0; t < 3; t++) {
+    for (size_t j = 0; j < g; j++)
+      for (Slot slot : ISSUE_ORDER) {
+        const Query &q = queries_of[slot];
+        if (q.scalars != FROM_INPUTS) continue;
+        const uint64_t *dh = dens.host_of(q.density), *dd = dens.dev_of(q.density);
+        bh_msm_job **job = &in_jobs.at[j * N_SLOTS + slot];
         if (n_in <= 8)
-          check(bh_msm_async(ctx, q[t].bases, 0, w.inputs, n_in, BH_SCALARS_MONT, q[t].dens_host, q[t].dens_host ? n_in : 0,
-                             &in_jobs[3 * j + t]));
+          check(bh_msm_async(ctx, q.bases, q.skip, witnesses[first + j].inputs, n_in, BH_SCALARS_MONT, dh, dh ? n_in : 0, job));
         else
-          check(bh_msm_async_dev_after(ctx, q[t].bases, 0, (char *)d_in.p + j * in_stride, n_in, BH_SCALARS_MONT, q[t].dens_dev,
-                                       q[t].dens_dev ? n_in : 0, nullptr, ps.st, &in_jobs[3 * j + t]));
+          check(bh_msm_async_dev_after(ctx, q.bases, q.skip, (char *)d_in.p + j * in_stride, n_in, BH_SCALARS_MONT, dd,
+                                       dd ? n_in : 0, nullptr, ps.st, job));
+      }
+    const double t2 = now_ms();
+    // waits, every job even when an earlier one fails; codes per proof by slot (prover.rs:339-354): each witness' `inputs`
+    // jobs, then the many-jobs, both in wait order
+    for (size_t j = 0; j < g; j++)
+      for (Slot slot : WAIT_ORDER)
+        if (queries_of[slot].scalars == FROM_INPUTS)
+          rcs[first + j][slot] = bh_msm_wait(in_jobs.take(j * N_SLOTS + slot), sum_at(sums[first + j], slot));
+    std::vector<unsigned char> recs(g * sizeof(G2Affine));
+    std::vector<int32_t> codes_v(g);
+    for (Slot slot : WAIT_ORDER) {
+      if (queries_of[slot].scalars == FROM_INPUTS) continue;
+      check(bh_msm_many_wait(many_jobs.take(slot), recs.data(), codes_v.data(), nullptr, nullptr));
+      for (size_t j = 0; j < g; j++) {
+        memcpy(sum_at(sums[first + j], slot), recs.data() + j * slot_bytes(slot), slot_bytes(slot));
+        rcs[first + j][slot] = codes_v[j];
       }
     }
-    const double t2 = now_ms();
-    // waits, every job even when an earlier one fails; codes per proof in the reference's wait order (prover.rs:339-354)
-    std::vector<G1Affine> g1(g);
-    std::vector<G2Affine> g2(g);
-    std::vector<int32_t> codes_v(g);
-    auto wait_many = [&](bh_msm_many_job *&job, int slot, auto &recs, auto member) {
-      bh_msm_many_job *jb = job;
-      job = nullptr;
-      check(bh_msm_many_wait(jb, recs.data(), codes_v.data(), nullptr, nullptr));
-      for (size_t j = 0; j < g; j++) { sums[first + j].*member = recs[j]; rcs[first + j][slot] = codes_v[j]; }
-    };
-    for (size_t j = 0; j < g; j++) {
-      MsmSums &o = sums[first + j];
-      rcs[first + j][0] = jobs.wait(in_jobs[3 * j + 0], &o.a_in);
-      rcs[first + j][2] = jobs.wait(in_jobs[3 * j + 1], &o.b1_in);
-      rcs[first + j][4] = jobs.wait(in_jobs[3 * j + 2], &o.b2_in);
-    }
-    wait_many(a_job, 1, g1, &MsmSums::a_aux);
-    wait_many(b1_job, 3, g1, &MsmSums::b1_aux);
-    wait_many(b2_job, 5, g2, &MsmSums::b2_aux);
-    wait_many(h_job, 6, g1, &MsmSums::h);
-    wait_many(l_job, 7, g1, &MsmSums::l);
     h_ms += t2 - t1;
     msm_ms += now_ms() - t2;
   }
-  for (std::thread &t : blind_threads) t.join();
+  blind.join();
   const bool subverted = params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity();   // prover.rs:320-324
-  if (blind_err && !subverted) std::rethrow_exception(blind_err);
+  if (blind.error && !subverted) std::rethrow_exception(blind.error);
   for (size_t j = 0; j < k; j++) {
-    int code = subverted ? BH_ERR_UNEXPECTED_IDENTITY : BH_OK;
-    for (int i = 0; i < 8 && code == BH_OK; i++) {
-      if (rcs[j][i] < 0) check(rcs[j][i]);   // a runtime failure is the call's
-      code = rcs[j][i];                       // first failing `?` in wait order
-    }
+    const int code = first_failure(params, rcs[j].data());
+    if (code < 0) check(code);   // a runtime failure is the call's
     codes[j] = code;
-    if (code == BH_OK) proofs[j] = finish_proof(blind[j], sums[j], r[j], s[j]);
+    if (code == BH_OK) proofs[j] = finish_proof(blind.terms[j], sums[j], r[j], s[j]);
   }
   if (tm) {
     tm->h_poly_ms = (float)h_ms;
@@ -794,12 +682,18 @@ void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const Witne
   }
 }
 
+static void split_rs(const std::vector<std::pair<Fr, Fr>> &rs, size_t k, std::vector<Fr> &r, std::vector<Fr> &s) {
+  if (k != rs.size()) throw std::invalid_argument("one (r, s) per witness");
+  r.resize(k);
+  s.resize(k);
+  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
+}
+
 std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
                                        const std::vector<std::pair<Fr, Fr>> &rs, ProveTimings *tm, size_t workspace_budget, int mode) {
-  if (witnesses.size() != rs.size()) throw std::invalid_argument("one (r, s) per witness");
   const size_t k = witnesses.size();
-  std::vector<Fr> r(k), s(k);
-  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
+  std::vector<Fr> r, s;
+  split_rs(rs, k, r, s);
   std::vector<Proof> proofs(k);
   std::vector<int> codes(k, BH_OK);
   prove_witness_batch_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(), tm, workspace_budget, mode);
@@ -837,10 +731,9 @@ void prove_witness_batch_checked_codes(const R1cs &r1cs, Parameters &params, con
 std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
                                                const std::vector<std::pair<Fr, Fr>> &rs, std::vector<uint32_t> *first_unsatisfied,
                                                ProveTimings *tm, size_t workspace_budget, int mode) {
-  if (witnesses.size() != rs.size()) throw std::invalid_argument("one (r, s) per witness");
   const size_t k = witnesses.size();
-  std::vector<Fr> r(k), s(k);
-  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
+  std::vector<Fr> r, s;
+  split_rs(rs, k, r, s);
   std::vector<Proof> proofs(k);
   std::vector<int> codes(k, BH_OK);
   std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
@@ -933,14 +826,31 @@ class ShapeAssembly : public ConstraintSystem {
 };
 }  // namespace
 
+// the input rows of prover.rs:208-215: one constraint `input_i * 0 = 0` per input
+static void enforce_input_rows(ConstraintSystem &cs, size_t num_inputs) {
+  for (size_t i = 0; i < num_inputs; i++) {
+    cs.enforce([i](LinearCombination lc) { return lc + Variable::new_unchecked(Index::Input, i); },
+               [](LinearCombination lc) { return lc; }, [](LinearCombination lc) { return lc; });
+  }
+}
+// prover.rs:182-215: `circuit` into a ProvingAssignment (the constant one first), the input rows appended
+static void synthesize_assignment(Circuit &circuit, ProvingAssignment &pa) {
+  pa.alloc_input([] { return Fr::one(); });
+  circuit.synthesize(pa);
+  enforce_input_rows(pa, pa.input_assignment.size());
+}
+void synthesize_witness(Circuit &circuit, const R1cs &r1cs, WitnessAssignment &w) {
+  w.input_assignment.reserve(r1cs.num_inputs);
+  w.aux_assignment.reserve(r1cs.num_aux);
+  w.alloc_input([] { return Fr::one(); });
+  circuit.synthesize(w);
+}
+
 // the circuit's shape with the input rows of prover.rs:208-215 appended
 static void capture_shape(Circuit &shape_of, ShapeAssembly &cs) {
   cs.alloc_input([] { return Fr::one(); });
   shape_of.synthesize(cs);
-  for (size_t i = 0; i < cs.num_inputs; i++) {
-    cs.enforce([i](LinearCombination lc) { return lc + Variable::new_unchecked(Index::Input, i); },
-               [](LinearCombination lc) { return lc; }, [](LinearCombination lc) { return lc; });
-  }
+  enforce_input_rows(cs, cs.num_inputs);
   if (cs.num_inputs + cs.num_aux >= ShapeAssembly::AUX_BIT)   // columns are 32-bit on the device (csrc/r1cs.hip)
     throw std::invalid_argument("R1CS capture: more than 2^31 variables");
   cs.finish();
@@ -954,12 +864,7 @@ double capture_check_for_tests(Circuit &shape_of, Circuit &proved, size_t out4[4
   capture_shape(shape_of, cs);
   const double ms = now_ms() - t0;
   ProvingAssignment pa;
-  pa.alloc_input([] { return Fr::one(); });
-  proved.synthesize(pa);
-  for (size_t i = 0; i < pa.input_assignment.size(); i++) {
-    pa.enforce([i](LinearCombination lc) { return lc + Variable::new_unchecked(Index::Input, i); },
-               [](LinearCombination lc) { return lc; }, [](LinearCombination lc) { return lc; });
-  }
+  synthesize_assignment(proved, pa);
   const size_t rows = cs.row_ptr[0].size() - 1;
   size_t bad = (rows != pa.a.size() || cs.num_inputs != pa.input_assignment.size() || cs.num_aux != pa.aux_assignment.size()) ? 1 : 0;
   const std::vector<Fr> *want[3] = {&pa.a, &pa.b, &pa.c};
@@ -1007,10 +912,7 @@ Proof create_proof(Circuit &circuit, const R1cs &r1cs, Parameters &params, const
   const double t0 = now_ms();
   Recycled<WitnessAssignment> wr(g_witnesses);
   WitnessAssignment &w = *wr;
-  w.input_assignment.reserve(r1cs.num_inputs);
-  w.aux_assignment.reserve(r1cs.num_aux);
-  w.alloc_input([] { return Fr::one(); });
-  circuit.synthesize(w);
+  synthesize_witness(circuit, r1cs, w);
   const double t1 = now_ms();
   ProveTimings local;
   Proof p = prove_witness(r1cs, params, w.input_assignment.data(), w.input_assignment.size(), w.aux_assignment.data(),
@@ -1030,39 +932,14 @@ Proof AsyncProof::wait(ProveTimings *tm) {
   if (error) std::rethrow_exception(error);
   return proof;
 }
-std::unique_ptr<AsyncProof> create_proof_async(Circuit &circuit, const R1cs *r1cs, Parameters &params, const Fr &r, const Fr &s) {
-  std::unique_ptr<AsyncProof> job(new AsyncProof());
-  const double t0 = now_ms();
-  if (r1cs) {
-    job->witness = g_witnesses.get();
-    WitnessAssignment &w = *job->witness;
-    w.input_assignment.reserve(r1cs->num_inputs);
-    w.aux_assignment.reserve(r1cs->num_aux);
-    w.alloc_input([] { return Fr::one(); });
-    circuit.synthesize(w);
-  } else {
-    job->assignment = g_assignments.get();
-    ProvingAssignment &pa = *job->assignment;
-    pa.alloc_input([] { return Fr::one(); });
-    circuit.synthesize(pa);
-    for (size_t i = 0; i < pa.input_assignment.size(); i++) {
-      pa.enforce([i](LinearCombination lc) { return lc + Variable::new_unchecked(Index::Input, i); },
-                 [](LinearCombination lc) { return lc; }, [](LinearCombination lc) { return lc; });
-    }
-  }
-  const float synth_ms = (float)(now_ms() - t0);
-  AsyncProof *j = job.get();
-  Parameters *pp = &params;
-  job->worker = std::thread([j, r1cs, pp, r, s, synth_ms] {
+// The device part of a proof on the job's helper thread: runs `prove`, stores the proof and the timings (with the
+// synthesis the caller did before, if any) or the exception for AsyncProof::wait
+template <class F>
+static void start_worker(AsyncProof *j, float synth_ms, F prove) {
+  j->worker = std::thread([j, synth_ms, prove] {
     try {
       ProveTimings local = {0, 0, 0, 0};
-      if (r1cs) {
-        const WitnessAssignment &w = *j->witness;
-        j->proof = prove_witness(*r1cs, *pp, w.input_assignment.data(), w.input_assignment.size(), w.aux_assignment.data(),
-                                 w.aux_assignment.size(), r, s, &local);
-      } else {
-        j->proof = prove_assignment(*j->assignment, *pp, r, s, &local);
-      }
+      j->proof = prove(&local);
       j->timings = local;
       j->timings.synthesis_ms = synth_ms;
       j->timings.total_ms = local.total_ms + synth_ms;
@@ -1070,21 +947,33 @@ std::unique_ptr<AsyncProof> create_proof_async(Circuit &circuit, const R1cs *r1c
       j->error = std::current_exception();
     }
   });
+}
+static Proof prove_held_witness(const AsyncProof &j, const R1cs &r1cs, Parameters &params, const Fr &r, const Fr &s, ProveTimings *tm) {
+  const WitnessAssignment &w = *j.witness;
+  return prove_witness(r1cs, params, w.input_assignment.data(), w.input_assignment.size(), w.aux_assignment.data(),
+                       w.aux_assignment.size(), r, s, tm);
+}
+std::unique_ptr<AsyncProof> create_proof_async(Circuit &circuit, const R1cs *r1cs, Parameters &params, const Fr &r, const Fr &s) {
+  std::unique_ptr<AsyncProof> job(new AsyncProof());
+  const double t0 = now_ms();
+  if (r1cs) {
+    job->witness = g_witnesses.get();
+    synthesize_witness(circuit, *r1cs, *job->witness);
+  } else {
+    job->assignment = g_assignments.get();
+    synthesize_assignment(circuit, *job->assignment);
+  }
+  const float synth_ms = (float)(now_ms() - t0);
+  AsyncProof *j = job.get();
+  Parameters *pp = &params;
+  if (r1cs) start_worker(j, synth_ms, [j, r1cs, pp, r, s](ProveTimings *tm) { return prove_held_witness(*j, *r1cs, *pp, r, s, tm); });
+  else start_worker(j, synth_ms, [j, pp, r, s](ProveTimings *tm) { return prove_assignment(*j->assignment, *pp, r, s, tm); });
   return job;
 }
 std::unique_ptr<AsyncProof> prove_assignment_async(const AssignmentView &v, Parameters &params, const Fr &r, const Fr &s) {
   std::unique_ptr<AsyncProof> job(new AsyncProof());
-  AsyncProof *j = job.get();
   Parameters *pp = &params;
-  job->worker = std::thread([j, v, pp, r, s] {
-    try {
-      ProveTimings local = {0, 0, 0, 0};
-      j->proof = prove_assignment(v, *pp, r, s, &local);
-      j->timings = local;
-    } catch (...) {
-      j->error = std::current_exception();
-    }
-  });
+  start_worker(job.get(), 0, [v, pp, r, s](ProveTimings *tm) { return prove_assignment(v, *pp, r, s, tm); });
   return job;
 }
 std::unique_ptr<AsyncProof> prove_witness_async(const R1cs &r1cs, Parameters &params, const void *input_assignment, size_t n_inputs,
@@ -1099,17 +988,7 @@ std::unique_ptr<AsyncProof> prove_witness_async(const R1cs &r1cs, Parameters &pa
   AsyncProof *j = job.get();
   const R1cs *rp = &r1cs;
   Parameters *pp = &params;
-  job->worker = std::thread([j, rp, pp, r, s] {
-    try {
-      ProveTimings local = {0, 0, 0, 0};
-      const WitnessAssignment &w = *j->witness;
-      j->proof = prove_witness(*rp, *pp, w.input_assignment.data(), w.input_assignment.size(), w.aux_assignment.data(),
-                               w.aux_assignment.size(), r, s, &local);
-      j->timings = local;
-    } catch (...) {
-      j->error = std::current_exception();
-    }
-  });
+  start_worker(j, 0, [j, rp, pp, r, s](ProveTimings *tm) { return prove_held_witness(*j, *rp, *pp, r, s, tm); });
   return job;
 }
 void ProofPipeline::retire_oldest() {
@@ -1141,12 +1020,7 @@ Proof create_proof(Circuit &circuit, Parameters &params, const Fr &r, const Fr &
   const double t0 = now_ms();
   Recycled<ProvingAssignment> pr(g_assignments);
   ProvingAssignment &prover = *pr;
-  prover.alloc_input([] { return Fr::one(); });
-  circuit.synthesize(prover);
-  for (size_t i = 0; i < prover.input_assignment.size(); i++) {
-    prover.enforce([i](LinearCombination lc) { return lc + Variable::new_unchecked(Index::Input, i); },
-                   [](LinearCombination lc) { return lc; }, [](LinearCombination lc) { return lc; });
-  }
+  synthesize_assignment(circuit, prover);
   const double t1 = now_ms();
   BH_TRACE("synthesised: %zu constraints", prover.a.size());
   ProveTimings local;
@@ -1160,3 +1034,41 @@ Proof create_proof(Circuit &circuit, Parameters &params, const Fr &r, const Fr &
 }
 
 }  // namespace groth16
+
+// bh_groth16_prove_witness_batch (and _checked), and the test library's twins with a workspace budget and a mode of their own
+int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
+                                size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
+                                float *timings4, size_t workspace_budget, int mode, bool checked, uint32_t *first_unsatisfied) {
+  using namespace groth16;
+  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
+  if (k && (!r || !s || !proofs_out || !rcs || (n_inputs && !inputs) || (n_aux && !aux))) return BH_ERR_INVALID_ARG;
+  ProveTimings tm = {0, 0, 0, 0};
+  const int rc = guarded([&] {
+    R1csView view(r1cs);
+    // caller records may be unaligned: copied then (the witnesses of a large circuit are tens of megabytes each - an
+    // aligned caller's arrays are read in place)
+    std::vector<Fr> in, ax, rr(k), ss(k);
+    const Fr *in_p = (const Fr *)inputs, *ax_p = (const Fr *)aux;
+    if ((uintptr_t)inputs % alignof(Fr) && k * n_inputs) { in.resize(k * n_inputs); memcpy(in.data(), inputs, k * n_inputs * 32); in_p = in.data(); }
+    if ((uintptr_t)aux % alignof(Fr) && k * n_aux) { ax.resize(k * n_aux); memcpy(ax.data(), aux, k * n_aux * 32); ax_p = ax.data(); }
+    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
+    std::vector<WitnessView> ws(k);
+    for (size_t j = 0; j < k; j++) ws[j] = WitnessView{in_p + j * n_inputs, n_inputs, ax_p + j * n_aux, n_aux};
+    std::vector<Proof> proofs(k);
+    std::vector<int> codes(k, BH_OK);
+    if (checked)   // bh_groth16_prove_witness_batch_checked: the check pre-pass, then the satisfied witnesses as below
+      prove_witness_batch_checked_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(),
+                                        first_unsatisfied, &tm, workspace_budget, mode);
+    else
+      prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
+    for (size_t j = 0; j < k; j++) {
+      char *out = (char *)proofs_out + j * 384;
+      rcs[j] = codes[j];
+      if (codes[j] == BH_OK) write_proof(out, proofs[j]);
+      else memset(out, 0, 384);
+    }
+    return BH_OK;
+  });
+  write_timings(timings4, tm);
+  return rc;
+}
