@@ -34,3 +34,4 @@ from .ceremony import PtauReport, pairing_product_is_one, verify_powers_of_tau  
 from .ceremony import bases_first_difference, contribute, same_ratio_each, tau_is_root_of_unity, verify_contributions  # noqa: F401,E402
 from .ceremony import PowersOfTau, contribute_powers_of_tau, new_powers_of_tau, verify_powers_of_tau_update  # noqa: F401,E402
 from .multiexp import point_mul_each  # noqa: F401,E402
+from .groth16 import BitsHint, InverseOrZeroHint  # noqa: F401,E402

@@ -52,6 +52,7 @@ EXPORTS = [
     "bh_point_mul_each_dev", "bh_bases_scale_powers", "bh_powers_of_tau_contribute",
     "bh_msm_many_async", "bh_msm_many_async_dev", "bh_msm_many_wait", "bh_msm_many_plan_info", "bh_groth16_prove_witness_batch",
     "bh_groth16_prove_witness_batch_checked",
+    "bh_r1cs_solver_create", "bh_r1cs_solver_release", "bh_r1cs_solver_info", "bh_r1cs_solve_many_dev", "bh_r1cs_solve_many",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -76,7 +77,7 @@ TEST_EXPORTS = [
     "bh_test_glv_split_host", "bh_test_glv_ladder_host", "bh_test_glv_ladder_dev",
     "bh_test_groth16_prove_witness_batch_budget", "bh_test_many_stage_dev",
     "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan", "bh_test_r1cs_many_tile",
-    "bh_test_groth16_prove_witness_batch_he",
+    "bh_test_groth16_prove_witness_batch_he", "bh_test_r1cs_solve_plan", "bh_test_r1cs_solver_tune",
 ]
 
 
@@ -286,6 +287,14 @@ def load():
     lib.bh_r1cs_check_many.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.bh_test_r1cs_many_tile.argtypes = []
     lib.bh_test_r1cs_many_tile.restype = c.c_uint32
+    lib.bh_r1cs_solver_create.argtypes = [vp, vp, vp, c.POINTER(u32), c.POINTER(vp)]
+    lib.bh_r1cs_solver_release.argtypes = [vp]
+    lib.bh_r1cs_solver_release.restype = None
+    lib.bh_r1cs_solver_info.argtypes = [vp, vp]
+    lib.bh_r1cs_solve_many_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp]
+    lib.bh_r1cs_solve_many.argtypes = [vp, vp, vp, vp, sz]
+    lib.bh_test_r1cs_solve_plan.argtypes = [sz, sz, sz, vp, vp, sz, vp, c.POINTER(u32), vp, vp, vp]
+    lib.bh_test_r1cs_solver_tune.argtypes = [vp, u32, u32, c.c_uint64]
     lib.bh_groth16_prove_witness.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
     lib.bh_groth16_demo_r1cs.argtypes = [vp, i32, sz, c.c_uint64, vp, c.POINTER(vp)]
     lib.bh_groth16_prove_demo_r1cs.argtypes = [vp, vp, i32, sz, c.c_uint64, vp, vp, vp, vp, vp, vp]

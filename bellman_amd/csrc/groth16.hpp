@@ -580,6 +580,23 @@ static_assert(sizeof(MsmSums) == 6 * 96 + 2 * 192, "packed: the C ABI hands it o
 // runs `synthesize` against a structure-only ConstraintSystem that never calls the value closures -
 // the same thing generator.rs:43-131 (KeypairAssembly) does to build the CRS for this circuit.
 struct WitnessView;
+// A witness solver of one circuit (bh_r1cs_solver): completes k witnesses on the device from the values of the supplied
+// variables - every other variable is the new variable of an alloc + enforce(a, b, c) pair, alone in c, or the output of a
+// hint (include/bellman_hip.h has the rule).  The R1cs must outlive it.
+class Solver {
+ public:
+  // throws std::invalid_argument, naming the variable (numbered as bh_csr.var) the refusal is about
+  Solver(const R1cs &r1cs, const bh_solver_desc &desc);
+  ~Solver();
+  Solver(const Solver &) = delete;
+  // k witnesses packed as the batch entry points take them (witness j at inputs + j * num_inputs, aux + j * num_aux),
+  // completed in place (bh_r1cs_solve_many); no constraint is checked - R1cs::which_is_unsatisfied does that
+  void solve(Fr *inputs, Fr *aux, size_t k) const;
+  bh_r1cs_solver *handle = nullptr;
+  bh_ctx *ctx = nullptr;
+  size_t supplied = 0, defined = 0, hinted = 0, levels = 0, widest_level = 0;
+};
+
 class R1cs {
  public:
   R1cs(bellman::Circuit &shape_of, bh_ctx *ctx);
@@ -595,6 +612,8 @@ class R1cs {
   // constraint witness j does not satisfy, or BH_R1CS_SATISFIED.  A witness of the wrong shape throws
   // std::invalid_argument, as does a handle adopted without its context.
   std::vector<uint32_t> which_is_unsatisfied(const WitnessView *witnesses, size_t k) const;
+  // a Solver for this circuit (needs the context, as which_is_unsatisfied does)
+  std::unique_ptr<Solver> solver(const bh_solver_desc &desc) const { return std::unique_ptr<Solver>(new Solver(*this, desc)); }
 };
 
 // prover.rs:57-162 reduced to witness generation: alloc/alloc_input run the value closures,

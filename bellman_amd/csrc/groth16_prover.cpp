@@ -899,6 +899,25 @@ std::vector<uint32_t> R1cs::which_is_unsatisfied(const WitnessView *witnesses, s
 }
 R1cs::~R1cs() { bh_r1cs_release(handle); }
 
+Solver::Solver(const R1cs &r1cs, const bh_solver_desc &desc) : ctx(r1cs.ctx) {
+  if (!ctx) throw std::invalid_argument("Solver: the R1cs handle was adopted without its context");
+  uint32_t bad = 0xFFFFFFFFu;
+  const int rc = bh_r1cs_solver_create(ctx, r1cs.handle, &desc, &bad, &handle);
+  if (rc == BH_ERR_INVALID_ARG)
+    throw std::invalid_argument(bad == 0xFFFFFFFFu ? std::string("Solver: malformed description")
+                                                   : "Solver: variable " + std::to_string(bad) +
+                                                         " is not determined by the supplied variables, the hints and the "
+                                                         "constraints in order, or is written by a hint that may not write it");
+  if (rc != BH_OK) throw std::runtime_error("bh_r1cs_solver_create failed");
+  size_t c[5];
+  bh_r1cs_solver_info(handle, c);
+  supplied = c[0]; defined = c[1]; hinted = c[2]; levels = c[3]; widest_level = c[4];
+}
+Solver::~Solver() { bh_r1cs_solver_release(handle); }
+void Solver::solve(Fr *inputs, Fr *aux, size_t k) const {
+  if (bh_r1cs_solve_many(ctx, handle, inputs, aux, k) != BH_OK) throw std::runtime_error("bh_r1cs_solve_many failed");
+}
+
 Variable WitnessAssignment::alloc(ValueFn f) {
   aux_assignment.push_back(f());
   return Variable::new_unchecked(Index::Aux, aux_assignment.size() - 1);

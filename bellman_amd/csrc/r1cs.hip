@@ -29,20 +29,6 @@ struct R1csEvalArgs {
   const uint2 *long_rows; // rows the lane-per-row kernel leaves to r1cs_long_rows_kernel
 };
 
-__device__ __forceinline__ fr_t ld_fr16(const fr_t *p) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-  uint4 lo = q[0], hi = q[1];
-  fr_t r;
-  r.l[0] = lo.x; r.l[1] = lo.y; r.l[2] = lo.z; r.l[3] = lo.w;
-  r.l[4] = hi.x; r.l[5] = hi.y; r.l[6] = hi.z; r.l[7] = hi.w;
-  return r;
-}
-__device__ __forceinline__ void st_fr16(fr_t *p, const fr_t &r) {
-  uint4 *q = reinterpret_cast<uint4 *>(p);
-  q[0] = make_uint4(r.l[0], r.l[1], r.l[2], r.l[3]);
-  q[1] = make_uint4(r.l[4], r.l[5], r.l[6], r.l[7]);
-}
-
 __global__ void __launch_bounds__(256) r1cs_eval_kernel(R1csEvalArgs a) {
   const u64 total = 3 * a.m;
   for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (u64)gridDim.x * blockDim.x) {
@@ -316,11 +302,7 @@ static std::vector<u32> find_long_constraints(const std::vector<u32> *row_ptr_of
   return v;
 }
 
-// what both k-witness entry points refuse, and the arguments they share
-static bool many_strides_ok(const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev, size_t aux_stride) {
-  return in_stride % 32 == 0 && aux_stride % 32 == 0 && in_stride >= r->n_inputs * 32 && aux_stride >= r->n_aux * 32 &&
-         (inputs_dev || !r->n_inputs) && (aux_dev || !r->n_aux);
-}
+// the arguments both k-witness entry points share (what they refuse: many_strides_ok, r1cs_dev.hpp)
 static void many_args(R1csManyArgs &a, const bh_r1cs *r, size_t in_stride, size_t aux_stride) {
   for (int m = 0; m < 3; m++) { a.row_ptr[m] = r->row_ptr[m]; a.terms[m] = r->terms[m]; a.out[m] = nullptr; }
   a.coeffs = r->coeffs;

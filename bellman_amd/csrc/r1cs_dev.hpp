@@ -1,10 +1,11 @@
-// The device-resident R1CS handle (bh_r1cs), shared by r1cs.hip (products with Fr vectors) and r1cs_points.hip
-// (products with vectors of group elements).
+// The device-resident R1CS handle (bh_r1cs), shared by r1cs.hip (products with Fr vectors), r1cs_points.hip
+// (products with vectors of group elements) and r1cs_solve.hip (witnesses completed from their supplied values).
 #pragma once
 #include <mutex>
 #include <vector>
 
 #include "common.hpp"
+#include "solve_plan.hpp"
 
 // A row with more terms than this is summed by a whole workgroup instead of one lane: the constant
 // ONE typically appears in every constraint, so its row of a transposed matrix has ~n terms.
@@ -15,6 +16,47 @@ constexpr u32 LONG_ROW = 1024;
 // scratch and at most 128 VGPRs for every one of those kernels (tools/kernel_resources.py r1cs.hip; the line is in DESIGN.md
 // 5.4.1): the kernels are bound by the latency of the witness gathers and want waves in flight.
 constexpr u32 R1CS_MANY_TILE = 2;
+
+// The solver's launch forms (r1cs_solve.hip).  A level of `width` definitions over k witnesses is one grid-wide launch of its
+// own (LEVEL) when width * k reaches SOLVE_LEVEL_MIN_ITEMS; the levels between two such levels are ONE launch (WALK) in which a
+// workgroup carries W = SOLVE_WALK_ITEMS / (mean width of the run) witnesses, at least 1 and at most SOLVE_WALK_MAX_W,
+// through all of them.  tools/bench_r1cs_solve.py --sweep -> profiles/r1cs_solve_bench_w256.json, the run that chose W:
+//   W      one wavefront's worth of (definition, witness) pairs per level.  Boolean circuit 2^16 x 256 (mean width 19): W = 1 / 4 /
+//          16 / 64 -> 81.1 / 80.0 / 96.7 / 128.5 ms; chain 2^14 x 256 (width 1): 71.1 / 71.9 / 70.8 / 67.9 ms.
+//   switch NOT settled by the sweep: no level of the measured circuits reaches 2^14 items at k = 256 (widest level 29), and one
+//          launch per level throughout loses 1.5 - 2.3 x.  The value stands by reasoning: a launch boundary costs about as much
+//          as four barrier-separated passes of a workgroup, so a level earns a launch where every CU would need that many.
+constexpr u32 SOLVE_WALK_LANES = 256;          // lanes of a workgroup of both kernels
+constexpr u32 SOLVE_WALK_ITEMS = 64;
+constexpr u32 SOLVE_WALK_MAX_W = 64;
+constexpr u64 SOLVE_LEVEL_MIN_ITEMS = (u64)1 << 18;   // 256 CUs x 256 lanes x 4
+enum : u32 { SOLVE_FORM_AUTO = 0, SOLVE_FORM_WALK = 1, SOLVE_FORM_LEVEL = 2 };
+
+// the 16-byte halves of an Fr record (the witness vectors are 32-byte aligned: bh_dev_alloc, strides multiples of 32)
+__device__ __forceinline__ fr_t ld_fr16(const fr_t *p) {
+  const uint4 *q = reinterpret_cast<const uint4 *>(p);
+  uint4 lo = q[0], hi = q[1];
+  fr_t r;
+  r.l[0] = lo.x; r.l[1] = lo.y; r.l[2] = lo.z; r.l[3] = lo.w;
+  r.l[4] = hi.x; r.l[5] = hi.y; r.l[6] = hi.z; r.l[7] = hi.w;
+  return r;
+}
+__device__ __forceinline__ void st_fr16(fr_t *p, const fr_t &r) {
+  uint4 *q = reinterpret_cast<uint4 *>(p);
+  q[0] = make_uint4(r.l[0], r.l[1], r.l[2], r.l[3]);
+  q[1] = make_uint4(r.l[4], r.l[5], r.l[6], r.l[7]);
+}
+
+// the field of solve_plan.hpp: Montgomery Fr of ff.cuh on the host
+struct SolveFr {
+  typedef fr_t Elem;
+  static fr_t zero() { fr_t z; fe_zero(z); return z; }
+  static bool is_zero(const fr_t &a) { return fe_is_zero(a); }
+  static fr_t add(const fr_t &a, const fr_t &b) { fr_t r; fe_add(r, a, b); return r; }
+  static bool is_one(const fr_t &a) { fr_t o; fe_one(o); return fe_eq(a, o); }
+  static bool is_minus_one(const fr_t &a) { fr_t o; fe_one(o); fe_neg(o, o); return fe_eq(a, o); }
+  static fr_t inv(const fr_t &a) { fr_t r; fe_inv(r, a); return r; }
+};
 }
 
 struct bh_r1cs {
@@ -55,7 +97,29 @@ struct bh_r1cs {
   std::vector<uint2> h_t_terms[3];                   // host copy of t_terms, dropped once the plan exists
 };
 
+// A witness solver of one circuit (bh_r1cs_solver_create): the plan of solve_plan.hpp on the device.  The three tuning
+// words are written by the test library alone (bh_test_r1cs_solver_tune), between calls.
+struct bh_r1cs_solver {
+  bh_ctx *ctx = nullptr;
+  const bh_r1cs *r = nullptr;
+  uint4 *defs = nullptr;                 // bh::SolveDef records, sorted by level
+  bh::u32 *level_ptr = nullptr;
+  bh::fr_t *sinv = nullptr;
+  uint2 *hint_terms = nullptr;           // (variable, entry of hint_coeffs)
+  bh::u32 *out_var = nullptr;
+  bh::fr_t *hint_coeffs = nullptr;
+  std::vector<bh::u32> h_level_ptr;
+  size_t counts[5] = {0, 0, 0, 0, 0};    // supplied, defined, hinted, levels, widest level
+  bh::u32 force_form = bh::SOLVE_FORM_AUTO, force_w = 0;
+  bh::u64 level_min_items = bh::SOLVE_LEVEL_MIN_ITEMS;
+};
+
 namespace bh {
+// what the k-witness entry points refuse in their witness buffers
+inline bool many_strides_ok(const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev, size_t aux_stride) {
+  return in_stride % 32 == 0 && aux_stride % 32 == 0 && in_stride >= r->n_inputs * 32 && aux_stride >= r->n_aux * 32 &&
+         (inputs_dev || !r->n_inputs) && (aux_dev || !r->n_aux);
+}
 // builds t_row_ptr / t_terms / t_long_rows on first use (r1cs.hip)
 int r1cs_ensure_transposed(bh_ctx *ctx, bh_r1cs *r);
 template <class T>

@@ -338,3 +338,44 @@ void bh_test_pairing_host(size_t n, const void *g1_affine, const void *g2_affine
 
 // the witness tile of the k-witness constraint kernels (r1cs.hip)
 extern "C" uint32_t bh_test_r1cs_many_tile(void) { return bh::R1CS_MANY_TILE; }
+
+// ---- test hooks of the witness solver: the planner on its own (host only; tests/test_r1cs_solve_model_cpu.py) and the
+// launch forms of a solver (tests/test_gpu_r1cs_solve.py, tools/bench_r1cs_solve.py) ------------------------------------
+extern "C" int bh_test_r1cs_solve_plan(size_t n_inputs, size_t n_aux, size_t n_constraints, const bh_csr abc[3], const void *coeffs,
+                                       size_t n_coeffs, const bh_solver_desc *desc, uint32_t *first_unsolved, int64_t *definer,
+                                       uint32_t *level, size_t counts5[5]) {
+  using namespace bh;
+  if (first_unsolved) *first_unsolved = SOLVE_NO_VAR;
+  if (!abc || !coeffs || !n_coeffs || !desc) return BH_ERR_INVALID_ARG;
+  SolveCsr m[3];
+  for (int i = 0; i < 3; i++) m[i] = SolveCsr{abc[i].row_ptr, abc[i].var, abc[i].coeff};
+  SolveDesc d;
+  d.supplied = desc->supplied; d.n_supplied = desc->n_supplied;
+  d.hints = reinterpret_cast<const SolveHint *>(desc->hints); d.n_hints = desc->n_hints;
+  d.lc_var = desc->lc_var; d.lc_coeff = desc->lc_coeff; d.out_var = desc->out_var;
+  d.n_lc = d.n_out = 0;
+  for (size_t h = 0; h < desc->n_hints; h++) {
+    if (desc->hints[h].lc_end > d.n_lc) d.n_lc = desc->hints[h].lc_end;
+    if (desc->hints[h].out_end > d.n_out) d.n_out = desc->hints[h].out_end;
+  }
+  const SolvePlan<fr_t> p = solve_plan(SolveFr(), n_inputs + n_aux, n_constraints, m, (const fr_t *)coeffs, n_coeffs, d,
+                                       (const fr_t *)desc->hint_coeffs, desc->n_hints ? desc->n_hint_coeffs : 0);
+  if (first_unsolved) *first_unsolved = p.first_unsolved;
+  if (p.status != SOLVE_OK) return p.status;
+  for (size_t v = 0; v < n_inputs + n_aux; v++) {
+    if (definer) definer[v] = p.by[v] == SOLVE_BY_NONE ? -1 : p.by[v] == SOLVE_BY_CONSTRAINT ? (int64_t)p.by_index[v] : -2 - (int64_t)p.by_index[v];
+    if (level) level[v] = p.level[v];
+  }
+  if (counts5) {
+    counts5[0] = p.n_supplied; counts5[1] = p.n_defined; counts5[2] = p.n_hinted;
+    counts5[3] = p.level_ptr.size() - 1; counts5[4] = p.widest;
+  }
+  return BH_OK;
+}
+extern "C" int bh_test_r1cs_solver_tune(bh_r1cs_solver *s, uint32_t form, uint32_t witnesses_per_group, uint64_t level_min_items) {
+  if (!s || form > bh::SOLVE_FORM_LEVEL) return BH_ERR_INVALID_ARG;
+  s->force_form = form;
+  s->force_w = witnesses_per_group;
+  s->level_min_items = level_min_items ? level_min_items : bh::SOLVE_LEVEL_MIN_ITEMS;
+  return BH_OK;
+}

@@ -519,6 +519,100 @@ def _stacked(vectors, n, k, what):
     return np.ascontiguousarray(np.stack(arrs)) if n and k else np.zeros((k, 0, 4), dtype=np.uint64)
 
 
+HINT_BITS, HINT_INV_OR_ZERO = 1, 2  # BH_HINT_*
+NO_VARIABLE = 0xFFFFFFFF
+
+
+class BitsHint:
+    """outs[j] = bit shift + j of the canonical integer of `lc` (a LinearCombination), as the field element 0 or 1: the
+    advice a bit decomposition allocates (src/gadgets/num.rs to_bits_le, the result bits of an adder)."""
+
+    def __init__(self, lc, outs, shift=0):
+        self.kind, self.lc, self.outs, self.shift = HINT_BITS, lc, list(outs), shift
+
+
+class InverseOrZeroHint:
+    """out = 1 / lc, or 0 where lc is 0: the advice of an is-zero or a division gadget."""
+
+    def __init__(self, lc, out):
+        self.kind, self.lc, self.outs, self.shift = HINT_INV_OR_ZERO, lc, [out], 0
+
+
+class _WitnessHint(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("kind", "lc_begin", "lc_end", "out_begin", "out_end", "shift")]
+
+
+class _SolverDesc(ctypes.Structure):
+    _fields_ = [("supplied", ctypes.c_void_p), ("n_supplied", ctypes.c_size_t), ("hints", ctypes.c_void_p), ("n_hints", ctypes.c_size_t),
+                ("lc_var", ctypes.c_void_p), ("lc_coeff", ctypes.c_void_p), ("out_var", ctypes.c_void_p),
+                ("hint_coeffs", ctypes.c_void_p), ("n_hint_coeffs", ctypes.c_size_t)]
+
+
+def solver_desc(supplied, hints):
+    """bh_solver_desc from plain indices: supplied = variable indices (bh_csr.var numbering), hints = (kind, [(variable,
+    coefficient)], [output variables], shift).  -> (the structure, the arrays it points into: keep them alive)."""
+    table, index = [1], {1: 0}
+    lc_var, lc_coeff, out_var = [], [], []
+    recs = (_WitnessHint * max(len(hints), 1))()
+    for h, (kind, lc, outs, shift) in enumerate(hints):
+        b0, o0 = len(lc_var), len(out_var)
+        for var, k in lc:
+            k %= Q
+            if k not in index:
+                index[k] = len(table)
+                table.append(k)
+            lc_var.append(var)
+            lc_coeff.append(index[k])
+        out_var += list(outs)
+        recs[h] = _WitnessHint(kind, b0, len(lc_var), o0, len(out_var), shift)
+    keep = [np.asarray(x, dtype=np.uint32) for x in (list(supplied), lc_var, lc_coeff, out_var)] + [fr_to_mont_array(table), recs]
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    desc = _SolverDesc(ptr(keep[0]), keep[0].size, ctypes.addressof(recs) if hints else None, len(hints), ptr(keep[1]), ptr(keep[2]),
+                       ptr(keep[3]), keep[4].ctypes.data, keep[4].shape[0])
+    return desc, keep
+
+
+class Solver:
+    """A witness solver of one circuit (bh_r1cs_solver, R1CS.solver): completes witnesses on the GPU from the values of the
+    supplied variables.  `.info`: supplied / defined / hinted variables, dependency levels, widest level."""
+
+    def __init__(self, r1cs, handle):
+        self.r1cs, self._h = r1cs, handle   # (the bh_r1cs must outlive the solver: the reference keeps it)
+        counts = (ctypes.c_size_t * 5)()
+        check(_lib.load().bh_r1cs_solver_info(self._h, counts), "R1CS.solver")
+        self.info = dict(zip(("supplied", "defined", "hinted", "levels", "widest_level"), (int(x) for x in counts)))
+
+    def solve_many(self, inputs_list, aux_list):
+        """k witnesses as eval_many takes them, every vector at its full length (what stands in a slot that is not supplied
+        does not matter) -> completed copies ([k, num_inputs, 4], [k, num_aux, 4]) uint64 Montgomery, the form
+        prove_witness_batch and which_is_unsatisfied take without a conversion.  No constraint is checked."""
+        lib = _lib.load()
+        r = self.r1cs
+        k = len(inputs_list)
+        assert len(aux_list) == k, "one aux vector per witness"
+        ins = _stacked(inputs_list, r.num_inputs, k, "Solver.solve_many").copy()
+        auxs = _stacked(aux_list, r.num_aux, k, "Solver.solve_many").copy()
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib.bh_r1cs_solve_many(r.worker.ctx, self._h, p(ins), p(auxs), k), "Solver.solve_many")
+        return ins, auxs
+
+    def solve(self, input_assignment, aux_assignment):
+        ins, auxs = self.solve_many([input_assignment], [aux_assignment])
+        return ins[0], auxs[0]
+
+    def release(self):
+        if self._h:
+            if getattr(self.r1cs.worker, "_ctx", None):   # as R1CS.release: the pool is gone with the Worker
+                _lib.load().bh_r1cs_solver_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class R1CS:
     """The circuit's A/B/C matrices registered on the device (bh_r1cs)."""
 
@@ -648,6 +742,26 @@ class R1CS:
         """TestConstraintSystem::is_satisfied for one witness"""
         return self.which_is_unsatisfied([input_assignment], [aux_assignment])[0] is None
 
+    def solver(self, supplied, hints=()):
+        """A Solver for this circuit: `supplied` = the Variables whose values the caller provides (what the circuit takes
+        from outside), `hints` = BitsHint / InverseOrZeroHint for advice values; every other variable must be the new
+        variable of an `alloc` + `enforce(a, b, c)` pair, alone in c (include/bellman_hip.h has the rule).  ValueError names
+        the first Variable that is not determined that way, or that a hint may not write."""
+        lib = _lib.load()
+        idx = lambda v: v.idx if v.kind == INPUT else self.num_inputs + v.idx  # noqa: E731
+        desc, keep = solver_desc([idx(v) for v in supplied],
+                                 [(h.kind, [(idx(v), k) for v, k in h.lc.terms], [idx(v) for v in h.outs], h.shift) for h in hints])
+        bad, h = ctypes.c_uint32(NO_VARIABLE), ctypes.c_void_p()
+        rc = lib.bh_r1cs_solver_create(self.worker.ctx, self._h, ctypes.byref(desc), ctypes.byref(bad), ctypes.byref(h))
+        del keep
+        if rc == -2 and bad.value != NO_VARIABLE:
+            v = bad.value
+            name = "Variable(INPUT, %d)" % v if v < self.num_inputs else "Variable(AUX, %d)" % (v - self.num_inputs)
+            raise ValueError("R1CS.solver: %s is not determined by the supplied variables, the hints and the constraints in "
+                             "order, or is written by a hint that may not write it" % name)
+        check(rc, "R1CS.solver")
+        return Solver(self, h)
+
     def eval_transposed_points(self, group, matrix, lagrange, accumulate_into=None, stream=None):
         """The raw group-valued product (bh_r1cs_eval_transposed_points_dev): out[v] = sum_j coeff * lagrange[j] over the
         constraints j that use variable v in `matrix` (0 A, 1 B, 2 C).  lagrange: at least num_constraints affine records
@@ -732,7 +846,7 @@ def prove_witness(r1cs, params, input_assignment, aux_assignment, r, s, timings=
 
 
 def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=None, _workspace_budget=None, _mode=None, _codes=None,
-                        check=False, _first_unsatisfied=None):
+                        check=False, _first_unsatisfied=None, solver=None):
     """k proofs of ONE circuit in one call (bh_groth16_prove_witness_batch): witness j = (inputs_list[j], aux_list[j]),
     blinding (rs[j], ss[j]) -> [Proof], each exactly what prove_witness returns for that witness.  inputs_list / aux_list:
     lists of integer lists or [n, 4] Montgomery arrays, or one [k, n, 4] uint64 array each (no copy is made then).  A witness of the wrong
@@ -747,7 +861,9 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     check=True: every witness is first checked against the circuit's constraints on the GPU
     (bh_groth16_prove_witness_batch_checked); a witness with an unsatisfied constraint gets no proof - errors.Unsatisfiable
     (`.index` = the constraint) is raised for the first one, or with _codes its code is 11 and its slot None.
-    _first_unsatisfied: a list that receives, per witness, the first unsatisfied constraint or None."""
+    _first_unsatisfied: a list that receives, per witness, the first unsatisfied constraint or None.
+    solver: a Solver of r1cs (R1CS.solver) - the witnesses are completed through it first (Solver.solve_many: only the
+    supplied variables' slots need to hold values); with check=True the check then judges the completed witnesses."""
     lib = _lib.load()
     check_witnesses, check = check, _check_rc
     k = len(inputs_list)
@@ -755,6 +871,8 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     assert not check_witnesses or (_mode is None and _workspace_budget is None), "the checked entry point has no test twin"
     ins = _stacked(inputs_list, r1cs.num_inputs, k, "create_proof")
     auxs = _stacked(aux_list, r1cs.num_aux, k, "create_proof")
+    if solver is not None and k:
+        ins, auxs = solver.solve_many(ins, auxs)
     if k == 0:
         if _first_unsatisfied is not None:
             _first_unsatisfied[:] = []

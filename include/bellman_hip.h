@@ -715,6 +715,61 @@ int bh_r1cs_check_many_dev(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_dev
                            size_t aux_stride, size_t k, uint32_t *first_bad_dev, void *stream);
 int bh_r1cs_check_many(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_host, const void *aux_host, size_t k,
                        uint32_t *first_bad_host);
+/* ---- the witness itself: k witnesses completed on the device from the values the caller supplies ------------------------
+ * (the reference computes every variable in a closure on one host thread, groth16/src/prover.rs:57-103).  `alloc` followed
+ * by `enforce(a, b, c)` with the new variable alone in c - AllocatedNum::mul, AllocatedBit::and / xor, packing, a MiMC round -
+ * determines that variable from the matrices: v = (<A_i, w> <B_i, w> - rest of C_i) / s_v.  A solver is derived once per
+ * circuit from a bh_r1cs, which must outlive it.  Variable indices are those of bh_csr.var (0 is ONE).
+ *   known from the start   ONE, the `supplied` variables, every output variable of a hint
+ *   one sweep, in order    constraint i defines v when v is the only variable of A_i, B_i, C_i not yet known (terms with a
+ *                          zero coefficient do not count), v has no term in A_i or B_i and the sum s_v of its coefficients in
+ *                          C_i is not zero.  There is no second sweep: synthesis order needs none.
+ *   hints                  values no constraint determines, from a linear combination lc_var / lc_coeff[lc_begin .. lc_end) over
+ *                          a coefficient table of their own (hint_coeffs: Montgomery Fr, entry 0 must be 1):
+ *                          BH_HINT_BITS         out_var[out_begin + j] = bit shift + j of the CANONICAL integer of the
+ *                                               combination, as Fr 0 or 1; shift + count <= 256
+ *                          BH_HINT_INV_OR_ZERO  the one output = the combination's inverse, or 0 when it is 0
+ * bh_r1cs_solver_create returns BH_ERR_INVALID_ARG, and in *first_unsolved (may be NULL) the variable concerned or
+ * 0xFFFFFFFF, when a variable stays unknown after the sweep (the lowest one: supply it or add a hint), when a hint writes
+ * ONE, a supplied variable or another hint's output (that variable), when hints and constraints depend on one another in a
+ * cycle (the lowest variable on or behind it), or when a hint record is malformed.
+ * bh_r1cs_solver_info: counts = supplied variables, constraint-defined variables, hint outputs, dependency levels, the
+ * definitions of the widest level.
+ * bh_r1cs_solve_many_dev completes witness j at inputs_dev + j * in_stride, aux_dev + j * aux_stride (the layout and the
+ * argument checks of bh_r1cs_check_many_dev) in place: it writes every defined and hinted variable whatever the buffer
+ * held, and never ONE, a supplied variable or a byte between the vector's end and the stride.  It checks no constraint -
+ * bh_r1cs_check_many_dev on the same buffers does.  Asynchronous on `stream`; k = 0 is BH_OK and launches nothing.
+ * bh_r1cs_solve_many: the same from and to the host, witness j at j * n_inputs * 32 and j * n_aux * 32, in groups that stay
+ * within 1 GiB of device memory.  Synchronous, on a stream of its own: thread-safe. */
+#define BH_HINT_BITS 1
+#define BH_HINT_INV_OR_ZERO 2
+typedef struct bh_r1cs_solver bh_r1cs_solver;
+typedef struct {
+  uint32_t kind;      /* BH_HINT_* */
+  uint32_t lc_begin;  /* the combination: terms [lc_begin, lc_end) of lc_var / lc_coeff */
+  uint32_t lc_end;
+  uint32_t out_begin; /* the outputs: out_var[out_begin .. out_end) */
+  uint32_t out_end;
+  uint32_t shift;     /* BH_HINT_BITS: the first bit; otherwise 0 */
+} bh_witness_hint;
+typedef struct {
+  const uint32_t *supplied;
+  size_t n_supplied;
+  const bh_witness_hint *hints;
+  size_t n_hints;
+  const uint32_t *lc_var;
+  const uint32_t *lc_coeff;
+  const uint32_t *out_var;
+  const void *hint_coeffs;
+  size_t n_hint_coeffs;
+} bh_solver_desc;
+int bh_r1cs_solver_create(bh_ctx *ctx, const bh_r1cs *r, const bh_solver_desc *desc, uint32_t *first_unsolved,
+                          bh_r1cs_solver **out);
+void bh_r1cs_solver_release(bh_r1cs_solver *s);
+int bh_r1cs_solver_info(const bh_r1cs_solver *s, size_t counts[5]);
+int bh_r1cs_solve_many_dev(bh_ctx *ctx, const bh_r1cs_solver *s, void *inputs_dev, size_t in_stride, void *aux_dev,
+                           size_t aux_stride, size_t k, void *stream);
+int bh_r1cs_solve_many(bh_ctx *ctx, const bh_r1cs_solver *s, void *inputs_host, void *aux_host, size_t k);
 /* Parameter generation (groth16/src/generator.rs:247-462) - device building blocks:
  *   bh_fr_powers_dev             out[i] = scale * g^i           (:249-263 powers of tau; :266-296 with t(tau)/delta folded in)
  *   bh_r1cs_eval_transposed_dev  at/bt/ct[v] = QAP polynomial of variable v at tau (:369-387) from the

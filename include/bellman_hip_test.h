@@ -482,6 +482,17 @@ int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t 
 /* host only: the number of witnesses a lane of bh_r1cs_eval_many_dev / bh_r1cs_check_many_dev serves (csrc/r1cs_dev.hpp
  * R1CS_MANY_TILE), so that a test can place k on the tile edges */
 uint32_t bh_test_r1cs_many_tile(void);
+/* host only: the witness solver's planner (csrc/solve_plan.hpp) on the caller's CSR arrays, no context: abc / coeffs as
+ * bh_r1cs_create takes them, desc as bh_r1cs_solver_create.  Returns the planner's status (BH_OK / BH_ERR_INVALID_ARG) with
+ * *first_unsolved as bh_r1cs_solver_create reports it.  With BH_OK, per variable: definer[v] = -1 (ONE, supplied), the
+ * defining constraint i >= 0, or -2 - h for an output of hint h; level[v]; counts5 as bh_r1cs_solver_info. */
+int bh_test_r1cs_solve_plan(size_t n_inputs, size_t n_aux, size_t n_constraints, const bh_csr abc[3], const void *coeffs,
+                            size_t n_coeffs, const bh_solver_desc *desc, uint32_t *first_unsolved, int64_t *definer,
+                            uint32_t *level, size_t counts5[5]);
+/* the launch forms of bh_r1cs_solve_many_dev for the calls that follow on this solver (csrc/r1cs_dev.hpp): form 0 = chosen
+ * per level, 1 = every level in the walk kernel, 2 = one launch per level; witnesses_per_group 0 = chosen per run;
+ * level_min_items 0 = the shipped switch point.  Not thread-safe: between calls only. */
+int bh_test_r1cs_solver_tune(bh_r1cs_solver *s, uint32_t form, uint32_t witnesses_per_group, uint64_t level_min_items);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,11 @@ pub struct BhPvkSet {
 pub struct BhMsmManyJob {
     _private: [u8; 0],
 }
+/// opaque `bh_r1cs_solver`
+#[repr(C)]
+pub struct BhR1csSolver {
+    _private: [u8; 0],
+}
 /// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -118,6 +123,31 @@ pub struct BhParamsStepReport {
     pub bad_vector: u32,
     pub bad_index: usize,
 }
+/// `bh_witness_hint`: one hint of a witness solver (kind = BH_HINT_*; terms and outputs as ranges of the pools)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhWitnessHint {
+    pub kind: u32,
+    pub lc_begin: u32,
+    pub lc_end: u32,
+    pub out_begin: u32,
+    pub out_end: u32,
+    pub shift: u32,
+}
+/// `bh_solver_desc`: what bh_r1cs_solver_create takes besides the circuit: supplied variables and hints
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BhSolverDesc {
+    pub supplied: *const u32,
+    pub n_supplied: usize,
+    pub hints: *const BhWitnessHint,
+    pub n_hints: usize,
+    pub lc_var: *const u32,
+    pub lc_coeff: *const u32,
+    pub out_var: *const u32,
+    pub hint_coeffs: *const c_void,
+    pub n_hint_coeffs: usize,
+}
 
 pub const BH_OK: c_int = 0;
 pub const BH_ERR_UNEXPECTED_IDENTITY: c_int = 1;
@@ -142,6 +172,8 @@ pub const BH_POINTS_CHECKED: c_uint = 1;
 pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;
 pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;
 pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;
+pub const BH_HINT_BITS: u32 = 1;
+pub const BH_HINT_INV_OR_ZERO: u32 = 2;
 pub const BH_PTAU_FAILED_HEAD: u32 = 0x01;
 pub const BH_PTAU_FAILED_TAU_G1_G2: u32 = 0x02;
 pub const BH_PTAU_FAILED_TAU_G1: u32 = 0x04;
@@ -282,6 +314,11 @@ extern "C" {
     pub fn bh_r1cs_eval_many_dev(ctx: *mut BhCtx, r: *const BhR1cs, inputs_dev: *const c_void, in_stride: usize, aux_dev: *const c_void, aux_stride: usize, k: usize, a_dev: *mut c_void, b_dev: *mut c_void, c_dev: *mut c_void, out_stride: usize, log_m: u32, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_check_many_dev(ctx: *mut BhCtx, r: *const BhR1cs, inputs_dev: *const c_void, in_stride: usize, aux_dev: *const c_void, aux_stride: usize, k: usize, first_bad_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_check_many(ctx: *mut BhCtx, r: *const BhR1cs, inputs_host: *const c_void, aux_host: *const c_void, k: usize, first_bad_host: *mut u32) -> c_int;
+    pub fn bh_r1cs_solver_create(ctx: *mut BhCtx, r: *const BhR1cs, desc: *const BhSolverDesc, first_unsolved: *mut u32, out: *mut *mut BhR1csSolver) -> c_int;
+    pub fn bh_r1cs_solver_release(s: *mut BhR1csSolver);
+    pub fn bh_r1cs_solver_info(s: *const BhR1csSolver, counts: *mut usize) -> c_int;
+    pub fn bh_r1cs_solve_many_dev(ctx: *mut BhCtx, s: *const BhR1csSolver, inputs_dev: *mut c_void, in_stride: usize, aux_dev: *mut c_void, aux_stride: usize, k: usize, stream: *mut c_void) -> c_int;
+    pub fn bh_r1cs_solve_many(ctx: *mut BhCtx, s: *const BhR1csSolver, inputs_host: *mut c_void, aux_host: *mut c_void, k: usize) -> c_int;
     pub fn bh_fr_powers_dev(ctx: *mut BhCtx, out_dev: *mut c_void, n: usize, g_host: *const c_void, scale_host: *const c_void, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_eval_transposed_dev(ctx: *mut BhCtx, r: *mut BhR1cs, lagrange_dev: *const c_void, at_dev: *mut c_void, bt_dev: *mut c_void, ct_dev: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bh_fr_qap_ext_dev(ctx: *mut BhCtx, e_dev: *mut c_void, at_dev: *const c_void, bt_dev: *const c_void, ct_dev: *const c_void, n_inputs: usize, n_vars: usize, alpha: *const c_void, beta: *const c_void, gamma_inv: *const c_void, delta_inv: *const c_void, stream: *mut c_void) -> c_int;

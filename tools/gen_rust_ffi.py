@@ -13,10 +13,10 @@ OUT = os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")
 
 OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "bh_params": "BhParams", "bh_r1cs": "BhR1cs",
           "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
-          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet", "bh_msm_many_job": "BhMsmManyJob"}
+          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet", "bh_msm_many_job": "BhMsmManyJob", "bh_r1cs_solver": "BhR1csSolver"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo",
            "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport",
-           "bh_params_step_report": "BhParamsStepReport"}
+           "bh_params_step_report": "BhParamsStepReport", "bh_witness_hint": "BhWitnessHint", "bh_solver_desc": "BhSolverDesc"}
 SCALAR = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "uint32_t": "u32", "uint64_t": "u64",
     "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char", "void": "c_void",
@@ -118,6 +118,15 @@ def render(decls):
         "/// `bh_params_step_report`: what bh_groth16_params_verify_step found (the BH_STEP_FAILED_* bits; the first position)",
         "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
         "pub struct BhParamsStepReport {", "    pub failed: u32,", "    pub bad_vector: u32,", "    pub bad_index: usize,", "}",
+        "/// `bh_witness_hint`: one hint of a witness solver (kind = BH_HINT_*; terms and outputs as ranges of the pools)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhWitnessHint {", "    pub kind: u32,", "    pub lc_begin: u32,", "    pub lc_end: u32,", "    pub out_begin: u32,",
+        "    pub out_end: u32,", "    pub shift: u32,", "}",
+        "/// `bh_solver_desc`: what bh_r1cs_solver_create takes besides the circuit: supplied variables and hints",
+        "#[repr(C)]", "#[derive(Clone, Copy)]",
+        "pub struct BhSolverDesc {", "    pub supplied: *const u32,", "    pub n_supplied: usize,", "    pub hints: *const BhWitnessHint,",
+        "    pub n_hints: usize,", "    pub lc_var: *const u32,", "    pub lc_coeff: *const u32,", "    pub out_var: *const u32,",
+        "    pub hint_coeffs: *const c_void,", "    pub n_hint_coeffs: usize,", "}",
         "",
     ]
     consts = [("BH_OK", 0), ("BH_ERR_UNEXPECTED_IDENTITY", 1), ("BH_ERR_UNEXPECTED_EOF", 2), ("BH_ERR_DEGREE_TOO_LARGE", 3),
@@ -128,7 +137,8 @@ def render(decls):
     for k, v in consts:
         lines.append("pub const %s: c_int = %d;" % (k, v))
     lines += ["pub const BH_POINTS_CHECKED: c_uint = 1;", "pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;",
-              "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;", "pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;"]
+              "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;", "pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;",
+              "pub const BH_HINT_BITS: u32 = 1;", "pub const BH_HINT_INV_OR_ZERO: u32 = 2;"]
     lines += ["pub const %s: u32 = 0x%02x;" % (k, v) for k, v in
               (("BH_PTAU_FAILED_HEAD", 1), ("BH_PTAU_FAILED_TAU_G1_G2", 2), ("BH_PTAU_FAILED_TAU_G1", 4), ("BH_PTAU_FAILED_TAU_G2", 8),
                ("BH_PTAU_FAILED_ALPHA", 16), ("BH_PTAU_FAILED_BETA", 32), ("BH_PTAU_FAILED_BETA_G2", 64), ("BH_PTAU_FAILED_POINTS", 128))]
