@@ -53,6 +53,7 @@ EXPORTS = [
     "bh_msm_many_async", "bh_msm_many_async_dev", "bh_msm_many_wait", "bh_msm_many_plan_info", "bh_groth16_prove_witness_batch",
     "bh_groth16_prove_witness_batch_checked",
     "bh_r1cs_solver_create", "bh_r1cs_solver_release", "bh_r1cs_solver_info", "bh_r1cs_solve_many_dev", "bh_r1cs_solve_many",
+    "bh_groth16_assemble_many", "bh_proof_finish_dev", "bh_groth16_prove_witness_batch_dev",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -78,6 +79,7 @@ TEST_EXPORTS = [
     "bh_test_groth16_prove_witness_batch_budget", "bh_test_many_stage_dev",
     "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan", "bh_test_r1cs_many_tile",
     "bh_test_groth16_prove_witness_batch_he", "bh_test_r1cs_solve_plan", "bh_test_r1cs_solver_tune",
+    "bh_test_proof_finish_host", "bh_test_proof_finish_host_vk", "bh_test_groth16_prove_witness_batch_dev_mode",
 ]
 
 
@@ -306,6 +308,12 @@ def load():
     lib.bh_groth16_sums_add.argtypes = [vp, vp]
     lib.bh_groth16_sums_add.restype = None
     lib.bh_groth16_assemble.argtypes = [vp, vp, vp, vp, vp]
+    lib.bh_groth16_assemble_many.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    lib.bh_proof_finish_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bh_groth16_prove_witness_batch_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, c.c_uint, vp, vp, vp, vp, vp]
+    lib.bh_test_groth16_prove_witness_batch_dev_mode.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, c.c_uint, vp, vp, vp, vp, vp, sz, i32]
+    lib.bh_test_proof_finish_host.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    lib.bh_test_proof_finish_host_vk.argtypes = [vp, vp, vp, vp, sz, vp, vp]
     lib.bh_groth16_prepare_verifying_key.argtypes = [vp, vp, vp, vp, vp, vp, sz, c.POINTER(vp)]
     lib.bh_groth16_pvk_from_params.argtypes = [vp, c.POINTER(vp)]
     lib.bh_groth16_pvk_num_inputs.argtypes = [vp]

@@ -592,6 +592,9 @@ class Solver {
   // k witnesses packed as the batch entry points take them (witness j at inputs + j * num_inputs, aux + j * num_aux),
   // completed in place (bh_r1cs_solve_many); no constraint is checked - R1cs::which_is_unsatisfied does that
   void solve(Fr *inputs, Fr *aux, size_t k) const;
+  // the same in place on k strided device witnesses (DeviceWitnesses' layout), enqueued on `stream` (null: the context's):
+  // solve -> prove_witness_batch_dev on the same stream needs no host copy
+  void solve_dev(void *inputs_dev, size_t in_stride, void *aux_dev, size_t aux_stride, size_t k, void *stream = nullptr) const;
   bh_r1cs_solver *handle = nullptr;
   bh_ctx *ctx = nullptr;
   size_t supplied = 0, defined = 0, hinted = 0, levels = 0, widest_level = 0;
@@ -665,6 +668,9 @@ MsmSums prove_witness_part(const R1cs &r1cs, Parameters &params, const Fr *input
                            const Fr *aux_assignment, size_t n_aux, size_t part, size_t parts,
                            ProveTimings *timings = nullptr);
 Proof assemble_proof(const Parameters &params, const MsmSums &sums, const Fr &r, const Fr &s);
+// k proofs from k sets of sums in one device call (bh_groth16_assemble_many: csrc/proof_finish.cuh): proof j is exactly
+// assemble_proof(params, sums[j], r[j], s[j]).  An identity delta throws UnexpectedIdentity, as there.
+std::vector<Proof> assemble_proofs(const Parameters &params, const MsmSums *sums, const Fr *r, const Fr *s, size_t k);
 Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *input_assignment, size_t n_inputs,
                     const Fr *aux_assignment, size_t n_aux, const Fr &r, const Fr &s,
                     ProveTimings *timings = nullptr);
@@ -718,6 +724,33 @@ std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &par
 void prove_witness_batch_checked_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
                                        const Fr *s, Proof *proofs, int *codes, uint32_t *first_unsatisfied,
                                        ProveTimings *timings = nullptr, size_t workspace_budget = 0, int mode = BATCH_AUTO);
+
+// ---- k proofs from witnesses that are in device memory already ------------------------------------------------------
+// What bh_r1cs_eval_many_dev / bh_r1cs_check_many_dev / Solver::solve_dev work on: witness j's vectors at
+// inputs + j * in_stride and aux + j * aux_stride in DEVICE memory (strides in bytes, multiples of 32, at least the vector's
+// length).  The prover reads them in place and never writes them; nothing is uploaded.
+struct DeviceWitnesses {
+  const void *inputs; size_t in_stride;
+  const void *aux; size_t aux_stride;
+  size_t k;
+};
+// prove_witness_batch (flags without BH_PROVE_CHECK) or prove_witness_batch_checked (with it: ONE bh_r1cs_check_many_dev
+// over the caller's buffers, the unsatisfied witnesses skipped by index) over such witnesses: proofs, error order and
+// *first_unsatisfied are those calls' on host copies of the same witnesses.  Waits for `stream` (the stream the caller's
+// solve ran on; may be null) before it reads, and drains every job before it returns.  BH_PROVE_FINISH_DEVICE takes the
+// k proofs' tails through assemble_proofs, BH_PROVE_FINISH_HOST through the host arithmetic; neither: the measured rule
+// (measured, DESIGN.md 5.5.2: device finishing is ahead at three of four k = 256 shapes, at the fourth in one run of
+// three, and at no k = 16 shape - so the host, always); both: std::invalid_argument, as for a bad stride - before anything runs.  The proofs go through the
+// single-proof path, BATCH_IN_FLIGHT at a time.  The codes form takes a mode: BATCH_GROUPED_HE forces the grouped path (forced
+// only, as in prove_witness_batch_codes) - a group is a run of consecutive proved witnesses within workspace_budget
+// (4 * g * m * 32 bytes; 0: the default), its vectors the caller's pointers at the group's first witness with the caller's
+// strides; any other mode but BATCH_AUTO is refused.
+std::vector<Proof> prove_witness_batch_dev(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &witnesses,
+                                           const std::vector<std::pair<Fr, Fr>> &rs, unsigned flags = 0, void *stream = nullptr,
+                                           std::vector<uint32_t> *first_unsatisfied = nullptr, ProveTimings *timings = nullptr);
+void prove_witness_batch_dev_codes(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &witnesses, const Fr *r, const Fr *s,
+                                   unsigned flags, void *stream, Proof *proofs, int *codes, uint32_t *first_unsatisfied,
+                                   ProveTimings *timings = nullptr, size_t workspace_budget = 0, int mode = BATCH_AUTO);
 
 // ---- one caller, proofs back to back ---------------------------------------------------------------------------
 // create_proof is synthesis on the host followed by the device part (prover.rs:182-215, then :217-360).  A single

@@ -317,3 +317,11 @@ extern "C" int bh_test_groth16_prove_witness_batch_he(bh_params *params, const b
   return prove_witness_batch_guarded(params, r1cs, inputs, n_inputs, aux, n_aux, k, r, s, proofs_out, rcs, timings4, workspace_budget,
                                      groth16::BATCH_GROUPED_HE);
 }
+extern "C" int bh_test_groth16_prove_witness_batch_dev_mode(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev,
+                                                            size_t in_stride, const void *aux_dev, size_t aux_stride, size_t k,
+                                                            const void *r, const void *s, unsigned flags, void *stream,
+                                                            void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied,
+                                                            float *timings4, size_t workspace_budget, int mode) {
+  return prove_witness_batch_dev_guarded(params, r1cs, inputs_dev, in_stride, aux_dev, aux_stride, k, r, s, flags, stream, proofs_out,
+                                         rcs, first_unsatisfied, timings4, workspace_budget, mode);
+}

@@ -177,6 +177,14 @@ int bh_groth16_prove_witness_batch_checked(bh_params *params, const bh_r1cs *r1c
                                      groth16::BATCH_AUTO, true, first_unsatisfied);
 }
 
+int bh_groth16_prove_witness_batch_dev(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
+                                       const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s,
+                                       unsigned flags, void *stream, void *proofs_out, int32_t *rcs,
+                                       uint32_t *first_unsatisfied, float *timings4) {
+  return prove_witness_batch_dev_guarded(params, r1cs, inputs_dev, in_stride, aux_dev, aux_stride, k, r, s, flags, stream,
+                                         proofs_out, rcs, first_unsatisfied, timings4);
+}
+
 // ---- asynchronous proofs: the device part of a proof on a helper thread (groth16.hpp AsyncProof) ----------------------
 int bh_groth16_prove_assignment_async(bh_params *params, const void *a_evals, const void *b_evals, const void *c_evals,
                                       size_t n_constraints, const void *input_assignment, size_t n_inputs,
@@ -250,6 +258,33 @@ int bh_groth16_assemble(bh_params *params, const void *sums, const void *r, cons
   MsmSums m;
   memcpy(&m, sums, sizeof m);
   return run_guarded([&] { return assemble_proof(*params->p, m, read_fr(r), read_fr(s)); }, proof_out);
+}
+
+int bh_groth16_assemble_many(bh_params *params, const void *sums, const void *r, const void *s, size_t k, void *proofs_out,
+                             int32_t *rcs) {
+  using namespace groth16;
+  if (!params) return BH_ERR_INVALID_ARG;
+  if (!k) return BH_OK;
+  if (!sums || !r || !s || !proofs_out || !rcs) return BH_ERR_INVALID_ARG;
+  return guarded([&] {
+    const Parameters &P = *params->p;
+    if (P.vk.delta_g1.is_identity() || P.vk.delta_g2.is_identity()) {   // prover.rs:320-324: every proof; nothing is launched
+      memset(proofs_out, 0, k * 384);
+      for (size_t j = 0; j < k; j++) rcs[j] = BH_ERR_UNEXPECTED_IDENTITY;
+      return BH_OK;
+    }
+    std::vector<MsmSums> m(k);   // caller records may be unaligned
+    std::vector<Fr> rr(k), ss(k);
+    memcpy(m.data(), sums, k * sizeof(MsmSums));
+    memcpy(rr.data(), r, k * 32);
+    memcpy(ss.data(), s, k * 32);
+    const std::vector<Proof> proofs = assemble_proofs(P, m.data(), rr.data(), ss.data(), k);
+    for (size_t j = 0; j < k; j++) {
+      write_proof((char *)proofs_out + j * 384, proofs[j]);
+      rcs[j] = BH_OK;
+    }
+    return BH_OK;
+  });
 }
 
 }  // extern "C"

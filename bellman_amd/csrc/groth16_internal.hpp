@@ -176,6 +176,9 @@ inline void wait_eight(InFlight<bh_msm_job> &jobs, const Parameters &p, MsmSums 
 }
 
 }  // namespace detail
+// groth16_prover.cpp: bh_proof_finish_dev with params' verifying key
+int finish_proofs_dev(const Parameters &params, const void *sums_dev, const void *r_dev, const void *s_dev, size_t k,
+                      void *proofs_dev, void *stream);
 void proof_slice_for_tests(size_t n, size_t part, size_t parts, size_t *lo, size_t *hi);   // groth16_prover.cpp
 double capture_check_for_tests(bellman::Circuit &shape_of, bellman::Circuit &proved, size_t out4[4]);   // groth16_prover.cpp
 // `circuit`'s witness into w (the constant one first, prover.rs:194); groth16_prover.cpp
@@ -255,6 +258,12 @@ int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const vo
                                 size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
                                 float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO, bool checked = false,
                                 uint32_t *first_unsatisfied = nullptr);
+
+// bh_groth16_prove_witness_batch_dev, and the test library's twin with a workspace budget and a mode; groth16_prover.cpp
+int prove_witness_batch_dev_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
+                                    const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s, unsigned flags,
+                                    void *stream, void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4,
+                                    size_t workspace_budget = 0, int mode = groth16::BATCH_AUTO);
 
 struct bh_proof_job {
   // members are destroyed in reverse order: the job (whose destructor joins the helper thread) before the view of the

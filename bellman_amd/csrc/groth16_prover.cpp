@@ -179,6 +179,11 @@ struct AssignmentSource {
   const uint64_t *a_aux_density = nullptr, *b_input_density = nullptr, *b_aux_density = nullptr;   // LSB0 words
   // device path (prove_witness): matrices and densities already resident
   const R1cs *r1cs = nullptr;
+  // device form of the witness (prove_witness_batch_dev): the two vectors where the caller holds them in device memory,
+  // read in place - nothing is uploaded.  `inputs` is then a host copy for the `inputs` multiexps that are answered on the
+  // host (n_in <= 8), or null; `aux` is null.
+  const void *inputs_dev = nullptr, *aux_dev = nullptr;
+  bool resident = false;
 };
 }  // namespace
 
@@ -214,10 +219,17 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
   const uint32_t log_m = dom.log_m;
   // assignments: uploaded once, shared by seven multiexps (prover.rs:248-318)
   const size_t n_in = src.n_in, n_aux = src.n_aux;
-  DevBuf d_in(ctx, n_in * 32 + 32), d_aux(ctx, n_aux * 32 + 32);
+  std::unique_ptr<DevBuf> own_in, own_aux;   // (none for a witness that is resident already)
+  if (!src.resident) {
+    own_in.reset(new DevBuf(ctx, n_in * 32 + 32));
+    own_aux.reset(new DevBuf(ctx, n_aux * 32 + 32));
+  }
+  const void *const d_in = src.resident ? src.inputs_dev : own_in->p, *const d_aux = src.resident ? src.aux_dev : own_aux->p;
   ProofStream ps(ctx);
-  check(bh_dev_upload_on(ctx, d_in.p, src.inputs, n_in * 32, ps.st));
-  if (n_aux) check(bh_dev_upload_on(ctx, d_aux.p, src.aux, n_aux * 32, ps.st));
+  if (!src.resident) {
+    check(bh_dev_upload_on(ctx, own_in->p, src.inputs, n_in * 32, ps.st));
+    if (n_aux) check(bh_dev_upload_on(ctx, own_aux->p, src.aux, n_aux * 32, ps.st));
+  }
   Densities dens;
   if (src.host) {
     dens.on_host(src.a_aux_density, src.b_input_density, src.b_aux_density, n_in);
@@ -246,7 +258,7 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
   auto slice_for = [&](Slot slot) {
     const Query &q = queries_of[slot];
     const size_t n = q.scalars == FROM_INPUTS ? n_in : q.scalars == FROM_AUX ? n_aux : m - 1;   // a.len() - 1, :238-244
-    const void *dev = q.scalars == FROM_INPUTS ? d_in.p : q.scalars == FROM_AUX ? d_aux.p : da.p;
+    const void *dev = q.scalars == FROM_INPUTS ? d_in : q.scalars == FROM_AUX ? d_aux : da.p;
     const Slice sl = slice_of(n, part, parts);
     return SlotSlice{q, dev, sl, q.skip + (q.density >= 0 ? popcount_bits(dens.host_of(q.density), sl.lo) : sl.lo)};
   };
@@ -254,7 +266,7 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
     const SlotSlice s = slice_for(slot);
     const size_t n = s.sl.hi - s.sl.lo;
     const uint64_t *dens_dev = dens.dev_of(s.q.density), *dens_host = dens.host_of(s.q.density);
-    if (s.q.scalars == FROM_INPUTS && n <= 8) {
+    if (s.q.scalars == FROM_INPUTS && n <= 8 && src.inputs) {
       // the `inputs` multiexps have one or two terms: handed over with their host scalars, the library
       // answers them on the host instead of running a kernel pipeline per term
       check(bh_msm_async(ctx, s.q.bases, s.base_skip, (const char *)src.inputs + s.sl.lo * 32, n, BH_SCALARS_MONT,
@@ -280,7 +292,7 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
       }
     } else {
       // a = A.w, b = B.w, c = C.w straight into the FFT buffers (prover.rs:19-55,105-145 on the device)
-      check(bh_r1cs_eval_dev(ctx, src.r1cs->handle, d_in.p, d_aux.p, da.p, db.p, dc.p, log_m, ps.st));
+      check(bh_r1cs_eval_dev(ctx, src.r1cs->handle, d_in, d_aux, da.p, db.p, dc.p, log_m, ps.st));
     }
     check(bh_h_poly_fr_dev_on(ctx, da.p, db.p, dc.p, dscratch.p, log_m, ps.st));
   };
@@ -388,6 +400,33 @@ static Proof finish_proof(const ProofBlinding &b, const MsmSums &m, const Fr &r,
 }
 Proof assemble_proof(const Parameters &params, const MsmSums &m, const Fr &r, const Fr &s) {
   return finish_proof(blind_terms(params, r, s), m, r, s);
+}
+
+// prover.rs:320-360 for k proofs on the device (bh_proof_finish_dev): sums, r, s and proofs are device buffers, the call
+// returns when the proofs are written.  An identity delta is the caller's to refuse.
+int finish_proofs_dev(const Parameters &params, const void *sums_dev, const void *r_dev, const void *s_dev, size_t k,
+                      void *proofs_dev, void *stream) {
+  const VerifyingKey &vk = params.vk;
+  unsigned char vk5[BH_FINISH_KEY_BYTES];
+  memcpy(vk5, &vk.alpha_g1, 96); memcpy(vk5 + 96, &vk.beta_g1, 96); memcpy(vk5 + 192, &vk.beta_g2, 192);
+  memcpy(vk5 + 384, &vk.delta_g1, 96); memcpy(vk5 + 480, &vk.delta_g2, 192);
+  return bh_proof_finish_dev(params.ctx, vk5, sums_dev, r_dev, s_dev, k, proofs_dev, stream);
+}
+std::vector<Proof> assemble_proofs(const Parameters &params, const MsmSums *sums, const Fr *r, const Fr *s, size_t k) {
+  std::vector<Proof> proofs(k);
+  if (!k) return proofs;
+  if (params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity())   // prover.rs:320-324
+    throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
+  bh_ctx *ctx = params.ctx;
+  static_assert(sizeof(MsmSums) == BH_MSM_SUMS_BYTES && sizeof(Proof) == 384 && sizeof(Fr) == 32, "record sizes");
+  DevBuf d_sums(ctx, k * sizeof(MsmSums)), d_rs(ctx, k * 64), d_proofs(ctx, k * sizeof(Proof));
+  void *d_s = (char *)d_rs.p + k * 32;
+  check(bh_dev_upload(ctx, d_sums.p, sums, k * sizeof(MsmSums)));
+  check(bh_dev_upload(ctx, d_rs.p, r, k * 32));
+  check(bh_dev_upload(ctx, d_s, s, k * 32));
+  check(finish_proofs_dev(params, d_sums.p, d_rs.p, d_s, k, d_proofs.p, nullptr));
+  check(bh_dev_download(ctx, proofs.data(), d_proofs.p, k * sizeof(Proof)));
+  return proofs;
 }
 
 void MsmSums::add(const MsmSums &o) {
@@ -744,6 +783,256 @@ std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &par
   return proofs;
 }
 
+// ---- k proofs from witnesses that are in device memory already (groth16.hpp DeviceWitnesses) ---------------------------
+// The finish rule of flags without a finish bit: device finishing where it was measured ahead of host finishing by more
+// than the host variant's own spread at every shape of that k.  Measured (tools/bench_prove_batch_dev.py,
+// profiles/prove_batch_dev_bench.json, DESIGN.md 5.5.2: MiMC-322, chain 2^14 / 2^16, boolean 2^16; k = 16 and 256): ahead at
+// three of the four k = 256 shapes in each of three runs, at chain 2^16 x 256 in one run of three, and at no k = 16 shape -
+// no k qualifies reproducibly: never.  Device finishing is forced-only, as the grouped path is (mode 3 over device
+// witnesses: 0.54 - 0.90 x the proofs in flight at k = 256, same file).
+static bool finish_on_device_by_rule(size_t /*k*/, size_t /*n_constraints*/) { return false; }
+
+// The grouped path (BATCH_GROUPED_HE of prove_witness_batch_codes: five many-jobs, ONE constraint evaluation and ONE batched
+// h block per group) over resident witnesses: the sums and per-proof codes of the witnesses good[0 .. n), which are
+// indices into the caller's strided buffers.  A group is a run of CONSECUTIVE proved witnesses within the budget - an
+// unsatisfied witness in between ends it - so that a group's vectors are the caller's pointers at its first witness with
+// the caller's strides: nothing is copied.  h_in: the host copy of the input vectors (k x n_in) where the `inputs`
+// multiexps are answered on the host, else empty.  A runtime failure throws once the group's jobs have drained.
+static void grouped_sums_resident(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w, const std::vector<size_t> &good,
+                                  const std::vector<Fr> &h_in, size_t workspace_budget, std::vector<MsmSums> &sums,
+                                  std::vector<int> &rc, double &h_ms, double &msm_ms) {
+  bh_ctx *ctx = params.ctx;
+  const size_t n = good.size(), n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
+  const Domain dom = domain_of(r1cs.num_constraints);
+  const size_t m = dom.m, vec = m * 32;
+  const uint32_t log_m = dom.log_m;
+  const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
+  const size_t group = std::min<size_t>(std::max<size_t>(budget / (4 * vec), 1), 4096);   // a, b, c and a scratch vector each
+  Densities dens;
+  dens.of(r1cs);
+  const QueryTable queries_of = queries(params, n_in, dens.b_in_total);
+  std::vector<std::array<int, N_SLOTS>> rcs(n);
+  for (size_t first = 0; first < n;) {
+    size_t g = 1;
+    while (first + g < n && g < group && good[first + g] == good[first + g - 1] + 1) g++;
+    const double t1 = now_ms();
+    const char *d_in = (const char *)w.inputs + good[first] * w.in_stride, *d_aux = (const char *)w.aux + good[first] * w.aux_stride;
+    const size_t scratch_bytes = log_m > 11 ? g * vec : 32;
+    DevBuf da(ctx, g * vec), db(ctx, g * vec), dc(ctx, g * vec), dscratch(ctx, scratch_bytes);
+    ProofStream ps(ctx);
+    StreamDrain drain{ps};
+    InFlight<bh_msm_job> in_jobs(g * N_SLOTS);   // witness j's `inputs` multiexps at j * N_SLOTS + slot
+    InFlight<bh_msm_many_job> many_jobs(N_SLOTS);
+    auto issue_many = [&](Slot slot, const void *scalars, size_t stride, size_t len) {
+      const Query &q = queries_of[slot];
+      const uint64_t *d = dens.dev_of(q.density);
+      check(bh_msm_many_async_dev(ctx, q.bases, q.skip, scalars, stride, len, g, BH_SCALARS_MONT, d, d ? len : 0, nullptr, ps.st,
+                                  &many_jobs.at[slot]));
+    };
+    for (Slot slot : ISSUE_ORDER)
+      if (queries_of[slot].scalars == FROM_AUX) issue_many(slot, d_aux, w.aux_stride, n_aux);
+    check(bh_r1cs_eval_many_dev(ctx, r1cs.handle, d_in, w.in_stride, d_aux, w.aux_stride, g, da.p, db.p, dc.p, vec, log_m, ps.st));
+    check(bh_h_poly_fr_many_dev_on(ctx, da.p, db.p, dc.p, vec, g, log_m, BH_FFT_MANY_FORCE, dscratch.p, scratch_bytes, ps.st));
+    issue_many(H, da.p, vec, m - 1);   // a.len() - 1
+    for (size_t j = 0; j < g; j++)
+      for (Slot slot : ISSUE_ORDER) {
+        const Query &q = queries_of[slot];
+        if (q.scalars != FROM_INPUTS) continue;
+        const uint64_t *dh = dens.host_of(q.density), *dd = dens.dev_of(q.density);
+        bh_msm_job **job = &in_jobs.at[j * N_SLOTS + slot];
+        if (!h_in.empty())
+          check(bh_msm_async(ctx, q.bases, q.skip, h_in.data() + good[first + j] * n_in, n_in, BH_SCALARS_MONT, dh, dh ? n_in : 0, job));
+        else
+          check(bh_msm_async_dev_after(ctx, q.bases, q.skip, d_in + j * w.in_stride, n_in, BH_SCALARS_MONT, dd, dd ? n_in : 0, nullptr,
+                                       ps.st, job));
+      }
+    const double t2 = now_ms();
+    for (size_t j = 0; j < g; j++)
+      for (Slot slot : WAIT_ORDER)
+        if (queries_of[slot].scalars == FROM_INPUTS)
+          rcs[first + j][slot] = bh_msm_wait(in_jobs.take(j * N_SLOTS + slot), sum_at(sums[first + j], slot));
+    std::vector<unsigned char> recs(g * sizeof(G2Affine));
+    std::vector<int32_t> codes_v(g);
+    for (Slot slot : WAIT_ORDER) {
+      if (queries_of[slot].scalars == FROM_INPUTS) continue;
+      check(bh_msm_many_wait(many_jobs.take(slot), recs.data(), codes_v.data(), nullptr, nullptr));
+      for (size_t j = 0; j < g; j++) {
+        memcpy(sum_at(sums[first + j], slot), recs.data() + j * slot_bytes(slot), slot_bytes(slot));
+        rcs[first + j][slot] = codes_v[j];
+      }
+    }
+    h_ms += t2 - t1;
+    msm_ms += now_ms() - t2;
+    first += g;
+  }
+  for (size_t i = 0; i < n; i++) {
+    rc[i] = BH_OK;
+    for (Slot slot : WAIT_ORDER)
+      if (rcs[i][slot] != BH_OK) { rc[i] = rcs[i][slot]; break; }
+    if (rc[i] < 0) check(rc[i]);   // a runtime failure is the call's
+  }
+}
+
+void prove_witness_batch_dev_codes(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w, const Fr *r, const Fr *s,
+                                   unsigned flags, void *stream, Proof *proofs, int *codes, uint32_t *first_unsatisfied,
+                                   ProveTimings *tm, size_t workspace_budget, int mode) {
+  const size_t k = w.k, n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
+  if (mode != BATCH_AUTO && mode != BATCH_GROUPED_HE) throw std::invalid_argument("mode: BATCH_AUTO or BATCH_GROUPED_HE");
+  if ((flags & BH_PROVE_FINISH_DEVICE) && (flags & BH_PROVE_FINISH_HOST)) throw std::invalid_argument("both finish bits");
+  if (flags & ~(BH_PROVE_CHECK | BH_PROVE_FINISH_DEVICE | BH_PROVE_FINISH_HOST)) throw std::invalid_argument("unknown flag");
+  // the layout rules of bh_r1cs_check_many_dev, before anything runs
+  if (w.in_stride % 32 || w.aux_stride % 32 || w.in_stride < n_in * 32 || w.aux_stride < n_aux * 32)
+    throw std::invalid_argument("witness strides: multiples of 32 bytes, at least the vector's length");
+  if (k && ((n_in && !w.inputs) || (n_aux && !w.aux))) throw std::invalid_argument("null witness buffer");
+  if (tm) *tm = ProveTimings{0, 0, 0, 0};
+  if (!k) return;
+  bh_ctx *ctx = params.ctx;
+  const double t0 = now_ms();
+  // whatever wrote the witnesses (the caller's solve) has finished; null is the context's stream
+  check(bh_stream_synchronize(ctx, stream));
+  auto in_at = [&](size_t j) { return (const char *)w.inputs + j * w.in_stride; };
+  auto aux_at = [&](size_t j) { return (const char *)w.aux + j * w.aux_stride; };
+
+  // which witnesses are proved: all of them, or the satisfied ones - by index, nothing is copied or compacted
+  std::vector<size_t> good;
+  if (flags & BH_PROVE_CHECK) {
+    std::vector<uint32_t> first_bad(k);
+    {
+      DevBuf d_bad(ctx, k * sizeof(uint32_t));
+      ProofStream ps(ctx);
+      StreamDrain drain{ps};
+      check(bh_r1cs_check_many_dev(ctx, r1cs.handle, w.inputs, w.in_stride, w.aux, w.aux_stride, k, (uint32_t *)d_bad.p, ps.st));
+      check(bh_stream_synchronize(ctx, ps.st));
+      check(bh_dev_download(ctx, first_bad.data(), d_bad.p, k * sizeof(uint32_t)));
+    }
+    for (size_t j = 0; j < k; j++) {
+      if (first_unsatisfied) first_unsatisfied[j] = first_bad[j];
+      if (first_bad[j] == BH_R1CS_SATISFIED) good.push_back(j);
+      else codes[j] = BH_ERR_UNSATISFIABLE;
+    }
+  } else {
+    for (size_t j = 0; j < k; j++) good.push_back(j);
+  }
+  const double t1 = now_ms();
+  const size_t n = good.size();
+  // the `inputs` multiexps of a few terms are answered on the host: one small download of the input vectors
+  std::vector<Fr> h_in;
+  if (n_in && n_in <= 8) {
+    h_in.resize(k * n_in);
+    if (w.in_stride == n_in * 32) check(bh_dev_download(ctx, h_in.data(), w.inputs, k * n_in * 32));
+    else
+      for (size_t j = 0; j < k; j++) check(bh_dev_download(ctx, h_in.data() + j * n_in, in_at(j), n_in * 32));
+  }
+  const bool on_device = (flags & BH_PROVE_FINISH_DEVICE) ||
+                         (!(flags & BH_PROVE_FINISH_HOST) && finish_on_device_by_rule(k, r1cs.num_constraints));
+  const bool subverted = params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity();   // prover.rs:320-324
+  std::vector<Fr> rr(n), ss(n);
+  for (size_t i = 0; i < n; i++) { rr[i] = r[good[i]]; ss[i] = s[good[i]]; }
+  // (host finishing: the blinding terms beside the GPU work, as in every other path; an identity delta fails there)
+  std::unique_ptr<Blinding> blind;
+  if (!on_device && n) blind.reset(new Blinding(params, rr.data(), ss.data(), n));
+
+  // the eight multiexps of every proved witness by the single-proof path, BATCH_IN_FLIGHT at a time, waited in order
+  // (BATCH_GROUPED_HE, forced only: by the grouped path)
+  struct Job {
+    std::thread th;
+    MsmSums sums;
+    ProveTimings tm = {0, 0, 0, 0};
+    std::exception_ptr error;
+    ~Job() { if (th.joinable()) th.join(); }   // whatever unwinds this frame: the job is drained first
+  };
+  std::vector<MsmSums> sums(n);
+  std::vector<int> rc(n, BH_OK);
+  std::exception_ptr fatal;
+  double h_ms = 0, msm_ms = 0;
+  if (mode == BATCH_GROUPED_HE) {
+    try {
+      grouped_sums_resident(r1cs, params, w, good, h_in, workspace_budget, sums, rc, h_ms, msm_ms);
+    } catch (...) {
+      fatal = std::current_exception();   // (its jobs have drained: InFlight)
+    }
+  }
+  std::vector<std::unique_ptr<Job>> jobs(n);   // declared after everything a job writes: destroyed, and so joined, first
+  auto finish = [&](size_t i) {
+    Job &job = *jobs[i];
+    job.th.join();
+    if (job.error) {
+      try {
+        std::rethrow_exception(job.error);
+      } catch (const SynthesisError &e) {
+        if (e.code < 0) { if (!fatal) fatal = job.error; }
+        else rc[i] = e.code;
+      } catch (...) {
+        if (!fatal) fatal = job.error;
+      }
+    }
+    sums[i] = job.sums;
+    h_ms += job.tm.h_poly_ms;
+    msm_ms += job.tm.msm_ms;
+    jobs[i].reset();
+  };
+  for (size_t i = 0; i < n && mode == BATCH_AUTO; i++) {
+    if (i >= BATCH_IN_FLIGHT) finish(i - BATCH_IN_FLIGHT);
+    AssignmentSource src;
+    src.n_in = n_in; src.n_aux = n_aux; src.n_cons = r1cs.num_constraints; src.r1cs = &r1cs;
+    src.inputs = h_in.empty() ? nullptr : h_in.data() + good[i] * n_in;
+    src.aux = nullptr;
+    src.resident = true;
+    src.inputs_dev = in_at(good[i]);
+    src.aux_dev = aux_at(good[i]);
+    jobs[i].reset(new Job());
+    Job *job = jobs[i].get();
+    Parameters *pp = &params;
+    job->th = std::thread([job, src, pp] {
+      try { msm_sums(src, *pp, 0, 1, job->sums, &job->tm); } catch (...) { job->error = std::current_exception(); }
+    });
+  }
+  for (size_t i = n > BATCH_IN_FLIGHT ? n - BATCH_IN_FLIGHT : 0; i < n && mode == BATCH_AUTO; i++) finish(i);   // all drained
+  if (blind) blind->join();
+  if (fatal) std::rethrow_exception(fatal);
+  if (blind && blind->error && !subverted) std::rethrow_exception(blind->error);
+  // an identity delta beats whatever a multiexp reported (first_failure, groth16_internal.hpp)
+  for (size_t i = 0; i < n; i++) codes[good[i]] = subverted ? BH_ERR_UNEXPECTED_IDENTITY : rc[i];
+  if (!subverted) {
+    if (on_device) {
+      // the sums of the proofs that have them, k' x 960 on the host, uploaded once; the proofs come back in one download
+      std::vector<size_t> done;
+      for (size_t i = 0; i < n; i++)
+        if (rc[i] == BH_OK) done.push_back(i);
+      std::vector<MsmSums> m(done.size());
+      std::vector<Fr> r2(done.size()), s2(done.size());
+      for (size_t d = 0; d < done.size(); d++) { m[d] = sums[done[d]]; r2[d] = rr[done[d]]; s2[d] = ss[done[d]]; }
+      const std::vector<Proof> out = assemble_proofs(params, m.data(), r2.data(), s2.data(), done.size());
+      for (size_t d = 0; d < done.size(); d++) proofs[good[done[d]]] = out[d];
+    } else {
+      for (size_t i = 0; i < n; i++)
+        if (rc[i] == BH_OK) proofs[good[i]] = finish_proof(blind->terms[i], sums[i], rr[i], ss[i]);
+    }
+  }
+  if (tm) {
+    tm->synthesis_ms = (float)(t1 - t0);
+    tm->h_poly_ms = (float)h_ms;
+    tm->msm_ms = (float)msm_ms;
+    tm->total_ms = (float)(now_ms() - t0);
+  }
+}
+
+std::vector<Proof> prove_witness_batch_dev(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w,
+                                           const std::vector<std::pair<Fr, Fr>> &rs, unsigned flags, void *stream,
+                                           std::vector<uint32_t> *first_unsatisfied, ProveTimings *tm) {
+  const size_t k = w.k;
+  std::vector<Fr> r, s;
+  split_rs(rs, k, r, s);
+  std::vector<Proof> proofs(k);
+  std::vector<int> codes(k, BH_OK);
+  std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
+  prove_witness_batch_dev_codes(r1cs, params, w, r.data(), s.data(), flags, stream, proofs.data(), codes.data(),
+                                (flags & BH_PROVE_CHECK) ? first_bad.data() : nullptr, tm);
+  if (first_unsatisfied && (flags & BH_PROVE_CHECK)) *first_unsatisfied = first_bad;
+  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
+  return proofs;
+}
+
 // ---- structure capture (generator.rs:43-131 KeypairAssembly, plus the input rows of prover.rs:208-215)
 namespace {
 struct FrHash {
@@ -914,6 +1203,11 @@ Solver::Solver(const R1cs &r1cs, const bh_solver_desc &desc) : ctx(r1cs.ctx) {
   supplied = c[0]; defined = c[1]; hinted = c[2]; levels = c[3]; widest_level = c[4];
 }
 Solver::~Solver() { bh_r1cs_solver_release(handle); }
+void Solver::solve_dev(void *inputs_dev, size_t in_stride, void *aux_dev, size_t aux_stride, size_t k, void *stream) const {
+  const int rc = bh_r1cs_solve_many_dev(ctx, handle, inputs_dev, in_stride, aux_dev, aux_stride, k, stream);
+  if (rc == BH_ERR_INVALID_ARG) throw std::invalid_argument("Solver::solve_dev: bad layout");
+  if (rc != BH_OK) throw std::runtime_error("bh_r1cs_solve_many_dev failed");
+}
 void Solver::solve(Fr *inputs, Fr *aux, size_t k) const {
   if (bh_r1cs_solve_many(ctx, handle, inputs, aux, k) != BH_OK) throw std::runtime_error("bh_r1cs_solve_many failed");
 }
@@ -1053,6 +1347,35 @@ Proof create_proof(Circuit &circuit, Parameters &params, const Fr &r, const Fr &
 }
 
 }  // namespace groth16
+
+// bh_groth16_prove_witness_batch_dev
+int prove_witness_batch_dev_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
+                                    const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s, unsigned flags,
+                                    void *stream, void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4,
+                                    size_t workspace_budget, int mode) {
+  using namespace groth16;
+  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
+  if (k && (!r || !s || !proofs_out || !rcs)) return BH_ERR_INVALID_ARG;
+  ProveTimings tm = {0, 0, 0, 0};
+  const int rc = guarded([&] {
+    R1csView view(r1cs);
+    std::vector<Fr> rr(k), ss(k);
+    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
+    std::vector<Proof> proofs(k);
+    std::vector<int> codes(k, BH_OK);
+    prove_witness_batch_dev_codes(view.r, *params->p, DeviceWitnesses{inputs_dev, in_stride, aux_dev, aux_stride, k}, rr.data(),
+                                  ss.data(), flags, stream, proofs.data(), codes.data(), first_unsatisfied, &tm, workspace_budget, mode);
+    for (size_t j = 0; j < k; j++) {
+      char *out = (char *)proofs_out + j * 384;
+      rcs[j] = codes[j];
+      if (codes[j] == BH_OK) write_proof(out, proofs[j]);
+      else memset(out, 0, 384);
+    }
+    return BH_OK;
+  });
+  write_timings(timings4, tm);
+  return rc;
+}
 
 // bh_groth16_prove_witness_batch (and _checked), and the test library's twins with a workspace budget and a mode of their own
 int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,

@@ -596,6 +596,13 @@ class Solver:
         check(lib.bh_r1cs_solve_many(r.worker.ctx, self._h, p(ins), p(auxs), k), "Solver.solve_many")
         return ins, auxs
 
+    def solve_many_dev(self, dev_witnesses, stream=None):
+        """the same in place on DeviceWitnesses (bh_r1cs_solve_many_dev), enqueued on `stream`: what prove_witness_batch_dev
+        reads afterwards without a host copy"""
+        w = dev_witnesses
+        check(_lib.load().bh_r1cs_solve_many_dev(self.r1cs.worker.ctx, self._h, w.inputs, w.in_stride, w.aux, w.aux_stride, w.k, stream),
+              "Solver.solve_many_dev")
+
     def solve(self, input_assignment, aux_assignment):
         ins, auxs = self.solve_many([input_assignment], [aux_assignment])
         return ins[0], auxs[0]
@@ -913,6 +920,121 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
     return [Proof(out[j].copy()) for j in range(k)]
 
 
+PROVE_CHECK, PROVE_FINISH_DEVICE, PROVE_FINISH_HOST = 1, 2, 4   # BH_PROVE_* of include/bellman_hip.h
+
+
+class DeviceWitnesses:
+    """k witnesses of one circuit in device memory, as bh_r1cs_solve_many_dev / bh_r1cs_check_many_dev /
+    bh_groth16_prove_witness_batch_dev take them: witness j's vectors at inputs + j * in_stride and aux + j * aux_stride
+    (bytes).  Owns its two buffers (release)."""
+
+    def __init__(self, worker, inputs, in_stride, aux, aux_stride, k, n_inputs, n_aux):
+        self.worker, self.inputs, self.in_stride, self.aux, self.aux_stride = worker, inputs, in_stride, aux, aux_stride
+        self.k, self.n_inputs, self.n_aux = k, n_inputs, n_aux
+
+    @classmethod
+    def from_host(cls, worker, ins, auxs, stride_extra=0):
+        """ins / auxs: [k, n, 4] uint64 Montgomery arrays; stride_extra: bytes of padding behind every vector (a multiple of
+        32), filled with a pattern so that a test can see it unchanged"""
+        lib = _lib.load()
+        ins, auxs = np.ascontiguousarray(ins, dtype=np.uint64), np.ascontiguousarray(auxs, dtype=np.uint64)
+        k = ins.shape[0]
+        assert auxs.shape[0] == k and stride_extra % 32 == 0
+        bufs = []
+        for v in (ins, auxs):
+            n = v.shape[1]
+            padded = np.full((k, n * 4 + stride_extra // 8), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+            padded[:, :n * 4] = v.reshape(k, n * 4)
+            d = ctypes.c_void_p()
+            check(lib.bh_dev_alloc(worker.ctx, max(padded.nbytes, 32), ctypes.byref(d)), "DeviceWitnesses")
+            if padded.nbytes:
+                check(lib.bh_dev_upload(worker.ctx, d, padded.ctypes.data_as(ctypes.c_void_p), padded.nbytes), "DeviceWitnesses")
+            bufs.append(d)
+        return cls(worker, bufs[0], ins.shape[1] * 32 + stride_extra, bufs[1], auxs.shape[1] * 32 + stride_extra, k,
+                   ins.shape[1], auxs.shape[1])
+
+    def download_raw(self):
+        """the two buffers as they are, padding included: ([k, in_stride / 8], [k, aux_stride / 8]) uint64"""
+        lib = _lib.load()
+        out = []
+        for d, stride in ((self.inputs, self.in_stride), (self.aux, self.aux_stride)):
+            a = np.zeros((self.k, stride // 8), dtype=np.uint64)
+            if a.nbytes:
+                check(lib.bh_dev_download(self.worker.ctx, a.ctypes.data_as(ctypes.c_void_p), d, a.nbytes), "DeviceWitnesses")
+            out.append(a)
+        return out
+
+    def download(self):
+        """([k, n_inputs, 4], [k, n_aux, 4]) uint64 Montgomery"""
+        i, a = self.download_raw()
+        return (np.ascontiguousarray(i[:, :self.n_inputs * 4]).reshape(self.k, self.n_inputs, 4),
+                np.ascontiguousarray(a[:, :self.n_aux * 4]).reshape(self.k, self.n_aux, 4))
+
+    def release(self):
+        if self.inputs is not None:
+            if getattr(self.worker, "_ctx", None):
+                for d in (self.inputs, self.aux):
+                    _lib.load().bh_dev_free(self.worker.ctx, d)
+            self.inputs = self.aux = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def prove_witness_batch_dev(r1cs, params, dev_witnesses, rs, ss, check=False, solver=None, finish=None, _mode=None, _codes=None,
+                            _first_unsatisfied=None, timings=None, stream=None, _workspace_budget=None):
+    """prove_witness_batch over witnesses that are in device memory already (bh_groth16_prove_witness_batch_dev): nothing
+    is uploaded, the buffers are read in place.  check / _codes / _first_unsatisfied / the errors raised: as
+    prove_witness_batch.  finish: None (the measured rule), "host" or "device" (the proofs' tails by
+    bh_proof_finish_dev's kernels).  solver: Solver.solve_many_dev on the buffers first, then the prover behind it on the
+    same stream - no host copy of a solved witness exists.  _mode (0 or 3) / _workspace_budget: the test library's twin
+    of the call (bh_test_groth16_prove_witness_batch_dev_mode) - 3 is the grouped path of groth16.hpp's BATCH_GROUPED_HE over
+    runs of consecutive proved witnesses that fit the budget."""
+    lib = _lib.load()
+    check_witnesses, check = check, _check_rc
+    w = dev_witnesses
+    k = w.k
+    if len(rs) != k or len(ss) != k:
+        raise ValueError("one (r, s) per witness")
+    if (w.n_inputs, w.n_aux) != (r1cs.num_inputs, r1cs.num_aux):
+        raise ValueError("witnesses of another circuit")
+    finish_bits = {None: 0, "host": PROVE_FINISH_HOST, "device": PROVE_FINISH_DEVICE}
+    if finish not in finish_bits:
+        raise ValueError("finish: None, 'host' or 'device'")
+    flags = (PROVE_CHECK if check_witnesses else 0) | finish_bits[finish]
+    if solver is not None and k:
+        solver.solve_many_dev(w, stream)
+    rr, sv = fr_to_mont_array(list(rs)), fr_to_mont_array(list(ss))
+    out = np.zeros((max(k, 1), 48), dtype=np.uint64)
+    rcs = np.zeros(max(k, 1), dtype=np.int32)
+    first_bad = np.full(max(k, 1), SATISFIED, dtype=np.uint32)
+    tm = (ctypes.c_float * 4)()
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    if _mode is None and _workspace_budget is None:
+        rc = lib.bh_groth16_prove_witness_batch_dev(params._h, r1cs._h, w.inputs, w.in_stride, w.aux, w.aux_stride, k, p(rr), p(sv), flags,
+                                                    stream, p(out), p(rcs), p(first_bad), tm)
+    else:
+        rc = lib.bh_test_groth16_prove_witness_batch_dev_mode(params._h, r1cs._h, w.inputs, w.in_stride, w.aux, w.aux_stride, k, p(rr),
+                                                              p(sv), flags, stream, p(out), p(rcs), p(first_bad), tm,
+                                                              _workspace_budget or 0, _mode or 0)
+    check(rc, "create_proof")
+    if timings is not None:
+        timings[:] = list(tm)
+    if _first_unsatisfied is not None:
+        _first_unsatisfied[:] = [None if int(b) == SATISFIED else int(b) for b in first_bad[:k]]
+    if _codes is not None:
+        _codes[:] = [int(c) for c in rcs[:k]]
+        return [Proof(out[j].copy()) if rcs[j] == 0 else None for j in range(k)]
+    for j in range(k):
+        if int(rcs[j]) == 11:
+            raise Unsatisfiable(int(first_bad[j]))
+        check(int(rcs[j]), "create_proof")
+    return [Proof(out[j].copy()) for j in range(k)]
+
+
 def create_proof_r1cs(circuit, r1cs, params, r, s, timings=None):
     """create_proof with the constraint evaluation on the device: only `circuit`'s value closures run here."""
     w = WitnessAssignment()
@@ -986,6 +1108,29 @@ def assemble(params, sums, r, s):
     p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
     check(_lib.load().bh_groth16_assemble(params._h, p(sums), p(rs[0:1]), p(rs[1:2]), p(out)), "create_proof")
     return Proof(out)
+
+
+def assemble_many(params, sums_list, rs, ss, _codes=None):
+    """k proofs from k sets of (summed) multiexp results in one device call (bh_groth16_assemble_many): proof j is exactly
+    assemble(params, sums_list[j], rs[j], ss[j]).  Raises what the first failing proof would (an identity delta:
+    UnexpectedIdentity); with _codes (a list) the per-proof codes are appended instead and failed slots are all zero."""
+    k = len(sums_list)
+    if len(rs) != k or len(ss) != k:
+        raise ValueError("one (r, s) per set of sums")
+    out = np.zeros((k, 48), dtype=np.uint64)
+    if not k:
+        return []
+    sums = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.uint64).reshape(SUMS_WORDS) for x in sums_list]))
+    r, s = fr_to_mont_array(list(rs)), fr_to_mont_array(list(ss))
+    rcs = np.zeros(k, dtype=np.int32)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    check(_lib.load().bh_groth16_assemble_many(params._h, p(sums), p(r), p(s), k, p(out), p(rcs)), "create_proof")
+    if _codes is not None:
+        _codes.extend(int(c) for c in rcs)
+    else:
+        for c in rcs:
+            check(int(c), "create_proof")
+    return [Proof(out[j].copy()) for j in range(k)]
 
 
 # ---- the reference's call sites as the Rust shim issues them (shim/patches, csrc/groth16_callsites.cpp) ----------

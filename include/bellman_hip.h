@@ -988,6 +988,37 @@ int bh_groth16_prove_witness_batch(bh_params *params, const bh_r1cs *r1cs, const
 int bh_groth16_prove_witness_batch_checked(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs,
                                            const void *aux, size_t n_aux, size_t k, const void *r, const void *s,
                                            void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4);
+/* bh_groth16_prove_witness_batch / _checked over witnesses that are in DEVICE memory already - where
+ * bh_r1cs_solve_many_dev left them: witness j = (inputs_dev + j * in_stride, aux_dev + j * aux_stride), layout and argument
+ * checks as bh_r1cs_check_many_dev (strides in bytes, multiples of 32, at least the vector's length; BH_ERR_INVALID_ARG
+ * before anything runs otherwise).  The buffers are read in place and never written, the bytes between a vector's end and
+ * its stride included; nothing is uploaded.  The call waits for `stream` (the stream the caller's solve ran on; may be
+ * NULL) before it reads, and drains every job before it returns.
+ *   BH_PROVE_CHECK           one bh_r1cs_check_many_dev over all k on the caller's buffers first; an unsatisfied witness gets
+ *                            rcs[j] = BH_ERR_UNSATISFIABLE, an all-zero slot and first_unsatisfied[j] (k words, may be NULL),
+ *                            and is skipped by index - nothing is copied or compacted.  Without the bit first_unsatisfied is
+ *                            not touched.
+ *   BH_PROVE_FINISH_DEVICE   the proofs' tails (prover.rs:320-360) by bh_proof_finish_dev's kernels: the waited sums are laid
+ *                            out k x 960 on the host and uploaded once; no blinding threads run
+ *   BH_PROVE_FINISH_HOST     ... by the host arithmetic of bh_groth16_assemble, beside the GPU work
+ *   neither finish bit       the measured rule (profiles/prove_batch_dev_bench.json): device finishing is ahead
+ *                            of host finishing beyond its spread at three of four k = 256 shapes in every run, at the fourth in
+ *                            one run of three, and at no k = 16 shape: no k qualifies and the host finishes;
+ *   both                     BH_ERR_INVALID_ARG
+ * proofs_out, rcs, the order of reported errors and first_unsatisfied are exactly bh_groth16_prove_witness_batch_checked's
+ * (with BH_PROVE_CHECK) or bh_groth16_prove_witness_batch's on host copies of the same witnesses: every proof is
+ * byte-identical to bh_groth16_prove_witness for its witness under every flag combination (prover.rs:217-360).
+ * How it runs: the single-proof path, 16 proofs in flight, the multiexps and bh_r1cs_eval_dev pointed at the caller's
+ * vectors.  For n_inputs <= 8 the `inputs` multiexps are answered on the host, so the input vectors (k x n_inputs x 32
+ * bytes) are downloaded at the start - one copy when in_stride == n_inputs * 32, one per witness otherwise; the aux vectors
+ * never leave the device.  timings4[0] = wait + check in host milliseconds, the rest as the host call. */
+#define BH_PROVE_CHECK 1u
+#define BH_PROVE_FINISH_DEVICE 2u
+#define BH_PROVE_FINISH_HOST 4u
+int bh_groth16_prove_witness_batch_dev(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
+                                       const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s,
+                                       unsigned flags, void *stream, void *proofs_out, int32_t *rcs,
+                                       uint32_t *first_unsatisfied, float *timings4);
 /* ---- one caller, proofs back to back: create_proof split at the synthesis / device boundary -----------------
  * The reference's create_proof is synthesis on the host (groth16/src/prover.rs:182-215) followed by the device part
  * (:217-360); a single caller that proves in a loop leaves the GPU idle during every synthesis and the host idle during
@@ -1023,6 +1054,29 @@ int bh_groth16_prove_witness_part(bh_params *params, const bh_r1cs *r1cs, const 
                                   size_t parts, void *sums_out, float *timings4);
 void bh_groth16_sums_add(void *acc, const void *other);
 int bh_groth16_assemble(bh_params *params, const void *sums, const void *r, const void *s, void *proof_out);
+/* ---- k proofs from k sets of sums in one device call (prover.rs:320-360 for every proof at once) ----------------
+ * bh_groth16_assemble spends five host scalar multiplications and two host linear combinations per proof; for a batch of
+ * small proofs that is more than their device work.  bh_groth16_assemble_many does the same arithmetic in two kernels
+ * (csrc/proof_finish.cuh): one split-scalar multiplication per (proof, product) - [r] delta1, [rs] delta1, [s] alpha1,
+ * [r] beta1, [s] a_inputs, [s] a_aux, [r] b_g1_inputs, [r] b_g1_aux in G1, [s] delta2 in G2 (:326-338, 351-354) - then one
+ * lane per proof element for the sums of :339-354, one inversion and the affine record.
+ *   sums   k x BH_MSM_SUMS_BYTES (host), r, s   k x 32 bytes each, Montgomery (host), proofs_out   k x 384 bytes (host)
+ * proofs_out + 384 j receives exactly the bytes bh_groth16_assemble(params, sums + 960 j, r + 32 j, s + 32 j, .) writes and
+ * rcs[j] that call's return code: an identity delta_g1 or delta_g2 gives BH_ERR_UNEXPECTED_IDENTITY for every j
+ * (prover.rs:320-324) with all-zero slots, and nothing is launched.  Returns BH_OK (k = 0 too), BH_ERR_INVALID_ARG for a
+ * null argument, BH_ERR_HIP.  Synchronous; uploads k x 960 + k x 64 bytes, downloads k x 384; the verifying key's five
+ * points travel as kernel arguments.  Every point must belong to the prime-order subgroup, as sums of multiples of a
+ * CRS do (the split-scalar ladder is defined there only).
+ * bh_proof_finish_dev is the same over device buffers: vk5 = alpha_g1 | beta_g1 | beta_g2 | delta_g1 | delta_g2
+ * (BH_FINISH_KEY_BYTES, host, bh_groth16_params_vk's order), sums_dev / r_dev / s_dev / proofs_dev laid out as above in
+ * device memory, 16-byte aligned.  The kernels are enqueued on `stream` (NULL: the context's) behind whatever wrote the
+ * buffers there, and the call returns once the proofs are written.  An identity delta is BH_ERR_UNEXPECTED_IDENTITY for
+ * the call, before anything is launched; k = 0 is BH_OK. */
+#define BH_FINISH_KEY_BYTES 672
+int bh_groth16_assemble_many(bh_params *params, const void *sums, const void *r, const void *s, size_t k, void *proofs_out,
+                             int32_t *rcs);
+int bh_proof_finish_dev(bh_ctx *ctx, const void *vk5, const void *sums_dev, const void *r_dev, const void *s_dev, size_t k,
+                        void *proofs_dev, void *stream);
 #ifdef __cplusplus
 }
 #endif

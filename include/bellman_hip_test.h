@@ -493,6 +493,22 @@ int bh_test_r1cs_solve_plan(size_t n_inputs, size_t n_aux, size_t n_constraints,
  * per level, 1 = every level in the walk kernel, 2 = one launch per level; witnesses_per_group 0 = chosen per run;
  * level_min_items 0 = the shipped switch point.  Not thread-safe: between calls only. */
 int bh_test_r1cs_solver_tune(bh_r1cs_solver *s, uint32_t form, uint32_t witnesses_per_group, uint64_t level_min_items);
+/* bh_groth16_prove_witness_batch_dev with a path of its own (groth16.hpp): mode 0 the call as shipped, mode 3
+ * BATCH_GROUPED_HE - five many-jobs, one bh_r1cs_eval_many_dev and one batched h block per group, a group being a run of
+ * consecutive proved witnesses (under BH_PROVE_CHECK an unsatisfied witness ends it) with 4 * g * m * 32 <= workspace_budget
+ * (0: the default), read through the caller's pointers and strides.  Any other mode is BH_ERR_INVALID_ARG. */
+int bh_test_groth16_prove_witness_batch_dev_mode(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
+                                                 const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s,
+                                                 unsigned flags, void *stream, void *proofs_out, int32_t *rcs,
+                                                 uint32_t *first_unsatisfied, float *timings4, size_t workspace_budget, int mode);
+/* host only, no GPU: bh_groth16_assemble_many's arguments and results, computed by the HOST compilation of the device
+ * functions of csrc/proof_finish.cuh - the text the kernels compile, lane by lane */
+int bh_test_proof_finish_host(bh_params *params, const void *sums, const void *r, const void *s, size_t k, void *proofs_out,
+                              int32_t *rcs);
+/* the same with the verifying key's five points handed over as bh_proof_finish_dev takes them (vk5, BH_FINISH_KEY_BYTES):
+ * needs no bh_params, which only exist with a device context */
+int bh_test_proof_finish_host_vk(const void *vk5, const void *sums, const void *r, const void *s, size_t k, void *proofs_out,
+                                 int32_t *rcs);
 
 #ifdef __cplusplus
 }

@@ -335,10 +335,13 @@ extern "C" {
     pub fn bh_groth16_prove_witness(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_witness_batch(params: *mut BhParams, r1cs: *const BhR1cs, inputs: *const c_void, n_inputs: usize, aux: *const c_void, n_aux: usize, k: usize, r: *const c_void, s: *const c_void, proofs_out: *mut c_void, rcs: *mut i32, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_witness_batch_checked(params: *mut BhParams, r1cs: *const BhR1cs, inputs: *const c_void, n_inputs: usize, aux: *const c_void, n_aux: usize, k: usize, r: *const c_void, s: *const c_void, proofs_out: *mut c_void, rcs: *mut i32, first_unsatisfied: *mut u32, timings4: *mut f32) -> c_int;
+    pub fn bh_groth16_prove_witness_batch_dev(params: *mut BhParams, r1cs: *const BhR1cs, inputs_dev: *const c_void, in_stride: usize, aux_dev: *const c_void, aux_stride: usize, k: usize, r: *const c_void, s: *const c_void, flags: c_uint, stream: *mut c_void, proofs_out: *mut c_void, rcs: *mut i32, first_unsatisfied: *mut u32, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_assignment_async(params: *mut BhParams, a_evals: *const c_void, b_evals: *const c_void, c_evals: *const c_void, n_constraints: usize, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, a_aux_density: *const u64, b_input_density: *const u64, b_aux_density: *const u64, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_prove_witness_async(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, r: *const c_void, s: *const c_void, job: *mut *mut BhProofJob) -> c_int;
     pub fn bh_groth16_proof_wait(job: *mut BhProofJob, proof_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_prove_witness_part(params: *mut BhParams, r1cs: *const BhR1cs, input_assignment: *const c_void, n_inputs: usize, aux_assignment: *const c_void, n_aux: usize, part: usize, parts: usize, sums_out: *mut c_void, timings4: *mut f32) -> c_int;
     pub fn bh_groth16_sums_add(acc: *mut c_void, other: *const c_void);
     pub fn bh_groth16_assemble(params: *mut BhParams, sums: *const c_void, r: *const c_void, s: *const c_void, proof_out: *mut c_void) -> c_int;
+    pub fn bh_groth16_assemble_many(params: *mut BhParams, sums: *const c_void, r: *const c_void, s: *const c_void, k: usize, proofs_out: *mut c_void, rcs: *mut i32) -> c_int;
+    pub fn bh_proof_finish_dev(ctx: *mut BhCtx, vk5: *const c_void, sums_dev: *const c_void, r_dev: *const c_void, s_dev: *const c_void, k: usize, proofs_dev: *mut c_void, stream: *mut c_void) -> c_int;
 }
