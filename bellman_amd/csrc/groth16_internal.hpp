@@ -4,9 +4,12 @@
 #include <stdlib.h>
 
 #include <chrono>
+#include <exception>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
+#include <thread>
 #include <vector>
 #include <string.h>
 
@@ -143,11 +146,17 @@ inline Domain domain_of(size_t n_constraints) {
   return d;
 }
 
+// the subversion check of prover.rs:320-324: an identity delta is refused by every path that finishes a proof
+inline bool subverted(const Parameters &p) { return p.vk.delta_g1.is_identity() || p.vk.delta_g2.is_identity(); }
+// An `inputs` multiexp of at most this many terms is handed over with its host scalars: the library answers it on the
+// host instead of running a kernel pipeline per term
+constexpr size_t HOST_INPUTS_MAX = 8;
+
 // What a proof reports, from the codes of its eight waits (in slot order).  prover.rs:320-324 returns UnexpectedIdentity
 // for an identity delta BEFORE any multiexp is waited on: it beats whatever a multiexp reports (e.g. UnexpectedEof from a
 // short query); then the first failing `?` in wait order.  A negative code is a runtime failure: the call's, not a proof's.
 inline int first_failure(const Parameters &p, const int codes[N_SLOTS]) {
-  if (p.vk.delta_g1.is_identity() || p.vk.delta_g2.is_identity()) return BH_ERR_UNEXPECTED_IDENTITY;
+  if (subverted(p)) return BH_ERR_UNEXPECTED_IDENTITY;
   for (Slot s : WAIT_ORDER)
     if (codes[s] != BH_OK) return codes[s];
   return BH_OK;
@@ -174,6 +183,70 @@ inline void wait_eight(InFlight<bh_msm_job> &jobs, const Parameters &p, MsmSums 
   BH_TRACE("waits done rc=%d %d %d %d %d %d %d %d", codes[0], codes[1], codes[2], codes[3], codes[4], codes[5], codes[6], codes[7]);
   check(first_failure(p, codes));
 }
+
+// ---- what the k-proof paths (groth16_batch.cpp) share with the single proof: defined in groth16_prover.cpp -------------
+struct ProofStream {   // uploads + h block of one proof; independent of other proofs in flight
+  bh_ctx *ctx;
+  void *st = nullptr;
+  explicit ProofStream(bh_ctx *c);
+  ~ProofStream();   // synchronises, then destroys
+  ProofStream(const ProofStream &) = delete;
+};
+// Declared after every DevBuf the proof stream writes (and so destroyed before them): if an exception
+// unwinds the frame, queued uploads / memsets / evaluations finish before their targets return to the
+// shared pool, where another proof's thread could pick them up.
+struct StreamDrain {
+  ProofStream &ps;
+  ~StreamDrain() { if (ps.st) (void)bh_stream_synchronize(ps.ctx, ps.st); }
+};
+// What differs between the ways of getting a proof's assignment and constraint evaluations into HBM
+struct AssignmentSource {
+  const Fr *inputs; size_t n_in;
+  const Fr *aux; size_t n_aux;
+  size_t n_cons;
+  // host path (prove_assignment): evaluations and density bitmaps computed during synthesis - plain views, so that the
+  // C entry point hands the caller's arrays through without copying them
+  bool host = false;
+  const Fr *a = nullptr, *b = nullptr, *c = nullptr;
+  const uint64_t *a_aux_density = nullptr, *b_input_density = nullptr, *b_aux_density = nullptr;   // LSB0 words
+  // device path (prove_witness): matrices and densities already resident
+  const R1cs *r1cs = nullptr;
+  // device form of the witness (prove_witness_batch_dev): the two vectors where the caller holds them in device memory,
+  // read in place - nothing is uploaded.  `inputs` is then a host copy for the `inputs` multiexps that are answered on the
+  // host (n_in <= HOST_INPUTS_MAX), or null; `aux` is null.
+  const void *inputs_dev = nullptr, *aux_dev = nullptr;
+  bool resident = false;
+};
+// prover.rs:217-318 + the waits of :339-354: the eight multiexp results (of part `part` of `parts`' slices)
+void msm_sums(const AssignmentSource &src, Parameters &params, size_t part, size_t parts, MsmSums &out, ProveTimings *tm);
+// prover.rs:320-338: the part of the proof elements that depends on the verifying key and r, s only
+struct ProofBlinding {
+  G1Affine g_a, g_c;
+  G2Affine g_b;
+};
+// The blinding terms of k (r, s) pairs on min(k, 8) helper threads, started at construction.  They involve only the
+// verifying key, r and s (prover.rs:326-338; five scalar multiplications, ~0.9 ms of host arithmetic per proof) and run
+// beside the enqueueing of the multiexps and the GPU work: for a small proof they are as long as everything else
+// together.  A failure there (identity delta) is kept in `error`, to be reported after the jobs drain.
+struct Blinding {
+  std::vector<ProofBlinding> terms;
+  std::exception_ptr error;
+  Blinding(const Parameters &params, const Fr *r, const Fr *s, size_t k);
+  void join() { for (std::thread &t : threads_) if (t.joinable()) t.join(); }
+  ~Blinding() { join(); }
+
+ private:
+  std::mutex mu_;
+  std::vector<std::thread> threads_;
+};
+Proof finish_proof(const ProofBlinding &b, const MsmSums &m, const Fr &r, const Fr &s);   // prover.rs:339-360
+// a witness has the shape of the captured circuit, or std::invalid_argument - before anything runs
+void require_shape(const R1cs &r1cs, const WitnessView *witnesses, size_t k);
+// The witnesses w[0 .. g) into two strided device buffers (strides = the vectors' lengths), on stream st.  With `coalesce`
+// and every host vector starting where the one before ends, ONE upload per vector kind; otherwise one per witness.
+void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *d_in, void *d_aux, void *st, bool coalesce);
+// which_is_unsatisfied for k witnesses: groups whose device copies stay within `budget` bytes, one bh_r1cs_check_many_dev each
+std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, const WitnessView *witnesses, size_t k, size_t budget);
 
 }  // namespace detail
 // groth16_prover.cpp: bh_proof_finish_dev with params' verifying key
@@ -253,13 +326,13 @@ struct R1csView {
 };
 
 // bh_groth16_prove_witness_batch (and _checked), and the test library's twins with a workspace budget and a mode of their
-// own (0: the default); groth16_prover.cpp
+// own (0: the default); groth16_batch.cpp
 int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
                                 size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
                                 float *timings4, size_t workspace_budget, int mode = groth16::BATCH_AUTO, bool checked = false,
                                 uint32_t *first_unsatisfied = nullptr);
 
-// bh_groth16_prove_witness_batch_dev, and the test library's twin with a workspace budget and a mode; groth16_prover.cpp
+// bh_groth16_prove_witness_batch_dev, and the test library's twin with a workspace budget and a mode; groth16_batch.cpp
 int prove_witness_batch_dev_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
                                     const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s, unsigned flags,
                                     void *stream, void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4,

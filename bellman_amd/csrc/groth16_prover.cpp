@@ -1,17 +1,13 @@
 // groth16::create_proof and friends: linear-combination evaluation during synthesis, the eight
-// multiexps + h block on the device, proof assembly, the R1CS capture and the witness-only path.
-// Reference map in groth16.hpp.
+// multiexps + h block on the device, proof assembly, the R1CS capture, the witness-only path and the
+// async pipeline.  k proofs in one call: groth16_batch.cpp.  Reference map in groth16.hpp.
 #include <string.h>
 
-#include <array>
+#include <exception>
 #include <memory>
 #include <mutex>
 #include <thread>
-#include <unordered_map>
 #include <vector>
-
-#include <exception>
-#include <functional>
 
 #include "groth16_internal.hpp"
 
@@ -137,24 +133,12 @@ void ProvingAssignment::enforce(const LcFn &fa, const LcFn &fb, const LcFn &fc) 
   run(fc, sc, c);
 }
 
+// (the h block is a short dependent chain on the proof's critical path - the H multiexp waits for it.  A high-priority
+// stream for it was measured: no gain for one proof and 8 % less throughput with twelve proofs in flight,
+// profiles/archive/r3_call3_oversub.txt)
+detail::ProofStream::ProofStream(bh_ctx *c) : ctx(c) { check(bh_stream_create_priority(ctx, 0, &st)); }
+detail::ProofStream::~ProofStream() { if (st) { (void)bh_stream_synchronize(ctx, st); (void)bh_stream_destroy(ctx, st); } }
 namespace {
-struct ProofStream {   // uploads + h block of one proof; independent of other proofs in flight
-  bh_ctx *ctx;
-  void *st = nullptr;
-  // the h block is a short dependent chain on the proof's critical path (the H multiexp waits for it).  A high-priority
-  // stream for it was measured: no gain for one proof and 8 % less throughput with twelve proofs in flight
-  // (profiles/archive/r3_call3_oversub.txt)
-  explicit ProofStream(bh_ctx *c) : ctx(c) { check(bh_stream_create_priority(ctx, 0, &st)); }
-  ~ProofStream() { if (st) { (void)bh_stream_synchronize(ctx, st); (void)bh_stream_destroy(ctx, st); } }
-  ProofStream(const ProofStream &) = delete;
-};
-// Declared after every DevBuf the proof stream writes (and so destroyed before them): if an exception
-// unwinds the frame, queued uploads / memsets / evaluations finish before their targets return to the
-// shared pool, where another proof's thread could pick them up.
-struct StreamDrain {
-  ProofStream &ps;
-  ~StreamDrain() { if (ps.st) (void)bh_stream_synchronize(ps.ctx, ps.st); }
-};
 template <class A> A add_pts(int group, const A &x, const A &y) { A r; bh_point_add(group, &r, &x, &y, 1); return r; }
 template <class A> A mul_pt(int group, const A &x, const Fr &k) {
   uint64_t kc[4];
@@ -166,27 +150,6 @@ template <class A> A mul_pt(int group, const A &x, const Fr &k) {
 }  // namespace
 
 // ---- prover.rs:217-360 ----------------------------------------------------------------------------
-namespace {
-// What differs between the two ways of getting the constraint evaluations into HBM
-struct AssignmentSource {
-  const Fr *inputs; size_t n_in;
-  const Fr *aux; size_t n_aux;
-  size_t n_cons;
-  // host path (prove_assignment): evaluations and density bitmaps computed during synthesis - plain views, so that the
-  // C entry point hands the caller's arrays through without copying them
-  bool host = false;
-  const Fr *a = nullptr, *b = nullptr, *c = nullptr;
-  const uint64_t *a_aux_density = nullptr, *b_input_density = nullptr, *b_aux_density = nullptr;   // LSB0 words
-  // device path (prove_witness): matrices and densities already resident
-  const R1cs *r1cs = nullptr;
-  // device form of the witness (prove_witness_batch_dev): the two vectors where the caller holds them in device memory,
-  // read in place - nothing is uploaded.  `inputs` is then a host copy for the `inputs` multiexps that are answered on the
-  // host (n_in <= 8), or null; `aux` is null.
-  const void *inputs_dev = nullptr, *aux_dev = nullptr;
-  bool resident = false;
-};
-}  // namespace
-
 namespace {
 // The slice of an n-term multiexp that part `k` of `parts` computes when one proof is spread over
 // several GPUs: contiguous in the scalar index, cut at multiples of 64 so that the
@@ -210,7 +173,7 @@ void proof_slice_for_tests(size_t n, size_t part, size_t parts, size_t *lo, size
 }
 
 // prover.rs:217-318 + the waits of :339-354: the eight multiexp results (of this part's slices)
-static void msm_sums(const AssignmentSource &src, Parameters &params, size_t part, size_t parts, MsmSums &out, ProveTimings *tm) {
+void detail::msm_sums(const AssignmentSource &src, Parameters &params, size_t part, size_t parts, MsmSums &out, ProveTimings *tm) {
   bh_ctx *ctx = params.ctx;
   const double t0 = now_ms();
   const size_t n_cons = src.n_cons;
@@ -266,9 +229,7 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
     const SlotSlice s = slice_for(slot);
     const size_t n = s.sl.hi - s.sl.lo;
     const uint64_t *dens_dev = dens.dev_of(s.q.density), *dens_host = dens.host_of(s.q.density);
-    if (s.q.scalars == FROM_INPUTS && n <= 8 && src.inputs) {
-      // the `inputs` multiexps have one or two terms: handed over with their host scalars, the library
-      // answers them on the host instead of running a kernel pipeline per term
+    if (s.q.scalars == FROM_INPUTS && n <= HOST_INPUTS_MAX && src.inputs) {   // (one or two terms: answered on the host)
       check(bh_msm_async(ctx, s.q.bases, s.base_skip, (const char *)src.inputs + s.sl.lo * 32, n, BH_SCALARS_MONT,
                          dens_host ? dens_host + s.sl.lo / 64 : nullptr, dens_host ? n : 0, &jobs.at[slot]));
       BH_TRACE("  multiexp of %zu terms answered on the host", n);
@@ -353,16 +314,10 @@ static void msm_sums(const AssignmentSource &src, Parameters &params, size_t par
   }
 }
 
-// prover.rs:326-360 from the eight multiexp results
 // prover.rs:320-338: the part of the proof elements that depends on the verifying key and r, s only
-struct ProofBlinding {
-  G1Affine g_a, g_c;
-  G2Affine g_b;
-};
 static ProofBlinding blind_terms(const Parameters &params, const Fr &r, const Fr &s) {
   const VerifyingKey &vk = params.vk;
-  if (vk.delta_g1.is_identity() || vk.delta_g2.is_identity())   // subversion check, prover.rs:320-324
-    throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
+  if (subverted(params)) throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
   ProofBlinding b;
   b.g_a = add_pts(BH_G1, mul_pt(BH_G1, vk.delta_g1, r), vk.alpha_g1);   // :326-327
   b.g_b = add_pts(BH_G2, mul_pt(BH_G2, vk.delta_g2, s), vk.beta_g2);    // :328-329
@@ -373,7 +328,7 @@ static ProofBlinding blind_terms(const Parameters &params, const Fr &r, const Fr
   return b;
 }
 // prover.rs:339-360: fold the multiexp results in
-static Proof finish_proof(const ProofBlinding &b, const MsmSums &m, const Fr &r, const Fr &s) {
+Proof detail::finish_proof(const ProofBlinding &b, const MsmSums &m, const Fr &r, const Fr &s) {
   // g_a = blind + a_answer; g_b = blind + b_g2_answer; g_c = blind + [s] a_answer + [r] b_g1_answer + h + l with
   // a_answer = a_inputs + a_aux etc. - each as ONE host linear combination (shared doubling chain, one inversion)
   const uint64_t one[4] = {1, 0, 0, 0};
@@ -415,17 +370,22 @@ int finish_proofs_dev(const Parameters &params, const void *sums_dev, const void
 std::vector<Proof> assemble_proofs(const Parameters &params, const MsmSums *sums, const Fr *r, const Fr *s, size_t k) {
   std::vector<Proof> proofs(k);
   if (!k) return proofs;
-  if (params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity())   // prover.rs:320-324
-    throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
+  if (subverted(params)) throw SynthesisError(BH_ERR_UNEXPECTED_IDENTITY, "UnexpectedIdentity");
   bh_ctx *ctx = params.ctx;
   static_assert(sizeof(MsmSums) == BH_MSM_SUMS_BYTES && sizeof(Proof) == 384 && sizeof(Fr) == 32, "record sizes");
   DevBuf d_sums(ctx, k * sizeof(MsmSums)), d_rs(ctx, k * 64), d_proofs(ctx, k * sizeof(Proof));
   void *d_s = (char *)d_rs.p + k * 32;
-  check(bh_dev_upload(ctx, d_sums.p, sums, k * sizeof(MsmSums)));
-  check(bh_dev_upload(ctx, d_rs.p, r, k * 32));
-  check(bh_dev_upload(ctx, d_s, s, k * 32));
-  check(finish_proofs_dev(params, d_sums.p, d_rs.p, d_s, k, d_proofs.p, nullptr));
-  check(bh_dev_download(ctx, proofs.data(), d_proofs.p, k * sizeof(Proof)));
+  try {
+    check(bh_dev_upload(ctx, d_sums.p, sums, k * sizeof(MsmSums)));
+    check(bh_dev_upload(ctx, d_rs.p, r, k * 32));
+    check(bh_dev_upload(ctx, d_s, s, k * 32));
+    check(finish_proofs_dev(params, d_sums.p, d_rs.p, d_s, k, d_proofs.p, nullptr));
+    check(bh_dev_download(ctx, proofs.data(), d_proofs.p, k * sizeof(Proof)));
+  } catch (...) {
+    // what is queued on the context's stream finishes before the three buffers return to the pool as this frame unwinds
+    (void)bh_stream_synchronize(ctx, nullptr);
+    throw;
+  }
   return proofs;
 }
 
@@ -436,32 +396,18 @@ void MsmSums::add(const MsmSums &o) {
   h = add_pts(BH_G1, h, o.h); l = add_pts(BH_G1, l, o.l);
 }
 
-// The blinding terms of k (r, s) pairs on min(k, 8) helper threads, started at construction.  They involve only the
-// verifying key, r and s (prover.rs:326-338; five scalar multiplications, ~0.9 ms of host arithmetic per proof) and run
-// beside the enqueueing of the multiexps and the GPU work: for a small proof they are as long as everything else
-// together.  A failure there (identity delta) is kept in `error`, to be reported after the jobs drain.
-struct Blinding {
-  std::vector<ProofBlinding> terms;
-  std::exception_ptr error;
-  Blinding(const Parameters &params, const Fr *r, const Fr *s, size_t k) : terms(k) {
-    const size_t n_threads = std::min<size_t>(k, 8);
-    for (size_t t = 0; t < n_threads; t++)
-      threads_.emplace_back([this, &params, r, s, k, t, n_threads] {
-        try {
-          for (size_t j = t; j < k; j += n_threads) terms[j] = blind_terms(params, r[j], s[j]);
-        } catch (...) {
-          std::lock_guard<std::mutex> g(mu_);
-          if (!error) error = std::current_exception();
-        }
-      });
-  }
-  void join() { for (std::thread &t : threads_) if (t.joinable()) t.join(); }
-  ~Blinding() { join(); }
-
- private:
-  std::mutex mu_;
-  std::vector<std::thread> threads_;
-};
+detail::Blinding::Blinding(const Parameters &params, const Fr *r, const Fr *s, size_t k) : terms(k) {
+  const size_t n_threads = std::min<size_t>(k, 8);
+  for (size_t t = 0; t < n_threads; t++)
+    threads_.emplace_back([this, &params, r, s, k, t, n_threads] {
+      try {
+        for (size_t j = t; j < k; j += n_threads) terms[j] = blind_terms(params, r[j], s[j]);
+      } catch (...) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!error) error = std::current_exception();
+      }
+    });
+}
 
 static Proof prove_core(const AssignmentSource &src, Parameters &params, const Fr &r, const Fr &s, ProveTimings *tm) {
   const double t0 = now_ms();
@@ -482,8 +428,7 @@ static Proof prove_core(const AssignmentSource &src, Parameters &params, const F
   return p;
 }
 
-// a witness has the shape of the captured circuit, or std::invalid_argument - before anything runs
-static void require_shape(const R1cs &r1cs, const WitnessView *witnesses, size_t k) {
+void detail::require_shape(const R1cs &r1cs, const WitnessView *witnesses, size_t k) {
   for (size_t j = 0; j < k; j++)
     if (witnesses[j].n_inputs != r1cs.num_inputs || witnesses[j].n_aux != r1cs.num_aux)
       throw std::invalid_argument("witness does not have the shape of the captured circuit");
@@ -532,15 +477,8 @@ Proof prove_witness(const R1cs &r1cs, Parameters &params, const Fr *inputs, size
   return prove_core(resident_source(r1cs, inputs, n_inputs, aux, n_aux), params, r, s, tm);
 }
 
-// ---- k proofs of one circuit in one call ------------------------------------------------------------
-// Across the proofs of one circuit the bases and the density maps are the same; only the scalar vectors differ.  So the
-// five long multiexps of every proof (l, a_aux, b_g1_aux, b_g2_aux, h) are issued as five many-jobs over all the witnesses
-// of a group (bh_msm_many_async_dev: one launch chain for the group where the library's size rule takes the many-plan, k
-// ordinary jobs otherwise), the h blocks run one after the other on one stream into strided coefficient vectors, and the
-// `inputs` multiexps and finish_proof stay per witness.  Error order per proof: prove_core's.
-// The witnesses w[0 .. g) into two strided device buffers (strides = the vectors' lengths), on stream st.  With `coalesce`
-// and every host vector starting where the one before ends, ONE upload per vector kind; otherwise one per witness.
-static void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *d_in, void *d_aux, void *st, bool coalesce) {
+// ---- the witnesses of k proofs into device memory, and their check (the k-proof paths: groth16_batch.cpp) ----------
+void detail::upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *d_in, void *d_aux, void *st, bool coalesce) {
   const size_t n_in = w[0].n_inputs, n_aux = w[0].n_aux, in_stride = n_in * 32, aux_stride = n_aux * 32;
   bool adjacent = coalesce;
   for (size_t j = 0; adjacent && j + 1 < g; j++)
@@ -556,8 +494,7 @@ static void upload_witnesses(bh_ctx *ctx, const WitnessView *w, size_t g, void *
   }
 }
 
-// which_is_unsatisfied for k witnesses: groups whose device copies stay within `budget` bytes, one bh_r1cs_check_many_dev each
-static std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, const WitnessView *witnesses, size_t k, size_t budget) {
+std::vector<uint32_t> detail::check_witnesses(bh_ctx *ctx, const R1cs &r1cs, const WitnessView *witnesses, size_t k, size_t budget) {
   require_shape(r1cs, witnesses, k);
   if (!ctx) throw std::invalid_argument("the R1cs handle was adopted without its context");
   std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
@@ -575,462 +512,6 @@ static std::vector<uint32_t> check_witnesses(bh_ctx *ctx, const R1cs &r1cs, cons
     check(bh_dev_download(ctx, first_bad.data() + first, d_bad.p, g * sizeof(uint32_t)));
   }
   return first_bad;
-}
-
-void prove_witness_batch_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r, const Fr *s,
-                               Proof *proofs, int *codes, ProveTimings *tm, size_t workspace_budget, int mode) {
-  require_shape(r1cs, witnesses, k);
-  if (tm) *tm = ProveTimings{0, 0, 0, 0};
-  if (!k) return;
-  const double t0 = now_ms();
-  // BATCH_AUTO never takes the grouped path (many-jobs over a group of witnesses) by itself.  Measured
-  // (tools/bench_prove_batch.py, profiles/prove_batch_bench.json: MiMC-322 and the chain circuit at 2^14 / 2^16 / 2^18
-  // constraints, k = 4 and 16): against k prove_witness_async calls in flight it is 0.51 - 0.66 x on MiMC-322 and
-  // 0.97 - 1.29 x on the chain circuit, beyond the baseline's own spread at two shapes of eight (k = 16 at 2^16 and 2^18) -
-  // and at another one (2^16, k = 4) in the run before.  No basis for a rule yet.
-  if (mode != BATCH_GROUPED && mode != BATCH_GROUPED_H && mode != BATCH_GROUPED_HE) {
-    // k proofs by the single-proof path, BATCH_IN_FLIGHT of them in flight (device memory stays bounded), waited in order
-    std::vector<std::unique_ptr<AsyncProof>> jobs(k);
-    auto finish = [&](size_t j) {
-      ProveTimings one = {0, 0, 0, 0};
-      try {
-        proofs[j] = jobs[j]->wait(&one);
-        codes[j] = BH_OK;
-      } catch (const SynthesisError &e) {
-        if (e.code < 0) { jobs.clear(); throw; }   // (the remaining jobs join in their destructors)
-        codes[j] = e.code;
-      }
-      jobs[j].reset();
-      if (tm) { tm->h_poly_ms += one.h_poly_ms; tm->msm_ms += one.msm_ms; }
-    };
-    for (size_t j = 0; j < k; j++) {
-      if (j >= BATCH_IN_FLIGHT) finish(j - BATCH_IN_FLIGHT);
-      jobs[j] = prove_witness_async(r1cs, params, witnesses[j].inputs, witnesses[j].n_inputs, witnesses[j].aux, witnesses[j].n_aux,
-                                    r[j], s[j]);
-    }
-    for (size_t j = k > BATCH_IN_FLIGHT ? k - BATCH_IN_FLIGHT : 0; j < k; j++) finish(j);
-    if (tm) tm->total_ms = (float)(now_ms() - t0);
-    return;
-  }
-  bh_ctx *ctx = params.ctx;
-  const size_t n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
-  const Domain dom = domain_of(r1cs.num_constraints);
-  const size_t m = dom.m;
-  const uint32_t log_m = dom.log_m;
-  // group size: g coefficient vectors (the a vector of each h block, which becomes its quotient) plus the b and c vectors
-  // and the FFT scratch, which the h blocks of a group share (they run one after the other on one stream)
-  const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
-  const size_t vec = m * 32;
-  // (BATCH_GROUPED_H: every witness has its own a, b, c and scratch vector - its h blocks run as ONE batched h block;
-  // BATCH_GROUPED_HE: the same, and the group's constraint evaluations run as ONE bh_r1cs_eval_many_dev)
-  const bool many_eval = mode == BATCH_GROUPED_HE, batched_h = mode == BATCH_GROUPED_H || many_eval;
-  size_t group = batched_h ? std::max<size_t>(budget / (4 * vec), 1) : budget / vec > 3 ? budget / vec - 3 : 1;
-  if (group > k) group = k;
-  if (group > 4096) group = 4096;
-  Blinding blind(params, r, s, k);   // beside the GPU work
-
-  Densities dens;
-  dens.of(r1cs);
-  const QueryTable queries_of = queries(params, n_in, dens.b_in_total);
-  std::vector<MsmSums> sums(k);
-  std::vector<std::array<int, N_SLOTS>> rcs(k);
-  double h_ms = 0, msm_ms = 0;
-  for (size_t first = 0; first < k; first += group) {
-    const size_t g = std::min(group, k - first);
-    const double t1 = now_ms();
-    const size_t in_stride = n_in * 32, aux_stride = n_aux * 32;
-    DevBuf d_in(ctx, g * in_stride + 32), d_aux(ctx, g * aux_stride + 32);
-    const size_t bc_vecs = batched_h ? g : 1, scratch_bytes = log_m > 11 ? bc_vecs * vec : 32;
-    DevBuf da(ctx, g * vec), db(ctx, bc_vecs * vec), dc(ctx, bc_vecs * vec), dscratch(ctx, scratch_bytes);
-    ProofStream ps(ctx);
-    StreamDrain drain{ps};
-    InFlight<bh_msm_job> in_jobs(g * N_SLOTS);   // witness j's `inputs` multiexps at j * N_SLOTS + slot
-    InFlight<bh_msm_many_job> many_jobs(N_SLOTS);
-    // 1. the witnesses, one strided buffer each (BATCH_GROUPED_HE: in one upload each where the host vectors are adjacent)
-    upload_witnesses(ctx, witnesses + first, g, d_in.p, d_aux.p, ps.st, many_eval);
-    // 2. the many-jobs over the aux vectors and the shared bases and densities, ordered after the uploads
-    auto issue_many = [&](Slot slot, const void *scalars, size_t stride, size_t n) {
-      const Query &q = queries_of[slot];
-      const uint64_t *d = dens.dev_of(q.density);
-      check(bh_msm_many_async_dev(ctx, q.bases, q.skip, scalars, stride, n, g, BH_SCALARS_MONT, d, d ? n : 0, nullptr, ps.st,
-                                  &many_jobs.at[slot]));
-    };
-    for (Slot slot : ISSUE_ORDER)
-      if (queries_of[slot].scalars == FROM_AUX) issue_many(slot, d_aux.p, aux_stride, n_aux);
-    // 3. the h block per witness, on one stream, into the group's strided coefficient vectors; then the H many-job,
-    // ordered after them
-    if (many_eval)
-      check(bh_r1cs_eval_many_dev(ctx, r1cs.handle, d_in.p, in_stride, d_aux.p, aux_stride, g, da.p, db.p, dc.p, vec, log_m, ps.st));
-    for (size_t j = 0; j < g && !many_eval; j++) {
-      void *a_j = (char *)da.p + j * vec;
-      const size_t bc = batched_h ? j * vec : 0;
-      check(bh_r1cs_eval_dev(ctx, r1cs.handle, (char *)d_in.p + j * in_stride, (char *)d_aux.p + j * aux_stride, a_j,
-                             (char *)db.p + bc, (char *)dc.p + bc, log_m, ps.st));
-      if (!batched_h) check(bh_h_poly_fr_dev_on(ctx, a_j, db.p, dc.p, dscratch.p, log_m, ps.st));
-    }
-    if (batched_h)
-      check(bh_h_poly_fr_many_dev_on(ctx, da.p, db.p, dc.p, vec, g, log_m, BH_FFT_MANY_FORCE, dscratch.p, scratch_bytes, ps.st));
-    issue_many(H, da.p, vec, m - 1);   // a.len() - 1
-    // 4. the `inputs` multiexps as the single call issues them (a handful of terms: answered on the host, at issue time -
-    // so they come last, while the GPU works)
-    for (size_t j = 0; j < g; j++)
-      for (Slot slot : ISSUE_ORDER) {
-        const Query &q = queries_of[slot];
-        if (q.scalars != FROM_INPUTS) continue;
-        const uint64_t *dh = dens.host_of(q.density), *dd = dens.dev_of(q.density);
-        bh_msm_job **job = &in_jobs.at[j * N_SLOTS + slot];
-        if (n_in <= 8)
-          check(bh_msm_async(ctx, q.bases, q.skip, witnesses[first + j].inputs, n_in, BH_SCALARS_MONT, dh, dh ? n_in : 0, job));
-        else
-          check(bh_msm_async_dev_after(ctx, q.bases, q.skip, (char *)d_in.p + j * in_stride, n_in, BH_SCALARS_MONT, dd,
-                                       dd ? n_in : 0, nullptr, ps.st, job));
-      }
-    const double t2 = now_ms();
-    // waits, every job even when an earlier one fails; codes per proof by slot (prover.rs:339-354): each witness' `inputs`
-    // jobs, then the many-jobs, both in wait order
-    for (size_t j = 0; j < g; j++)
-      for (Slot slot : WAIT_ORDER)
-        if (queries_of[slot].scalars == FROM_INPUTS)
-          rcs[first + j][slot] = bh_msm_wait(in_jobs.take(j * N_SLOTS + slot), sum_at(sums[first + j], slot));
-    std::vector<unsigned char> recs(g * sizeof(G2Affine));
-    std::vector<int32_t> codes_v(g);
-    for (Slot slot : WAIT_ORDER) {
-      if (queries_of[slot].scalars == FROM_INPUTS) continue;
-      check(bh_msm_many_wait(many_jobs.take(slot), recs.data(), codes_v.data(), nullptr, nullptr));
-      for (size_t j = 0; j < g; j++) {
-        memcpy(sum_at(sums[first + j], slot), recs.data() + j * slot_bytes(slot), slot_bytes(slot));
-        rcs[first + j][slot] = codes_v[j];
-      }
-    }
-    h_ms += t2 - t1;
-    msm_ms += now_ms() - t2;
-  }
-  blind.join();
-  const bool subverted = params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity();   // prover.rs:320-324
-  if (blind.error && !subverted) std::rethrow_exception(blind.error);
-  for (size_t j = 0; j < k; j++) {
-    const int code = first_failure(params, rcs[j].data());
-    if (code < 0) check(code);   // a runtime failure is the call's
-    codes[j] = code;
-    if (code == BH_OK) proofs[j] = finish_proof(blind.terms[j], sums[j], r[j], s[j]);
-  }
-  if (tm) {
-    tm->h_poly_ms = (float)h_ms;
-    tm->msm_ms = (float)msm_ms;
-    tm->total_ms = (float)(now_ms() - t0);
-  }
-}
-
-static void split_rs(const std::vector<std::pair<Fr, Fr>> &rs, size_t k, std::vector<Fr> &r, std::vector<Fr> &s) {
-  if (k != rs.size()) throw std::invalid_argument("one (r, s) per witness");
-  r.resize(k);
-  s.resize(k);
-  for (size_t j = 0; j < k; j++) { r[j] = rs[j].first; s[j] = rs[j].second; }
-}
-
-std::vector<Proof> prove_witness_batch(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
-                                       const std::vector<std::pair<Fr, Fr>> &rs, ProveTimings *tm, size_t workspace_budget, int mode) {
-  const size_t k = witnesses.size();
-  std::vector<Fr> r, s;
-  split_rs(rs, k, r, s);
-  std::vector<Proof> proofs(k);
-  std::vector<int> codes(k, BH_OK);
-  prove_witness_batch_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(), tm, workspace_budget, mode);
-  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
-  return proofs;
-}
-
-void prove_witness_batch_checked_codes(const R1cs &r1cs, Parameters &params, const WitnessView *witnesses, size_t k, const Fr *r,
-                                       const Fr *s, Proof *proofs, int *codes, uint32_t *first_unsatisfied, ProveTimings *tm,
-                                       size_t workspace_budget, int mode) {
-  if (tm) *tm = ProveTimings{0, 0, 0, 0};
-  const double t0 = now_ms();
-  const std::vector<uint32_t> first_bad =
-      check_witnesses(params.ctx, r1cs, witnesses, k, workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES);
-  const double pre_ms = now_ms() - t0;
-  if (first_unsatisfied)
-    for (size_t j = 0; j < k; j++) first_unsatisfied[j] = first_bad[j];
-  // the satisfied witnesses, in order, through the unchecked batch
-  std::vector<size_t> good;
-  for (size_t j = 0; j < k; j++) {
-    if (first_bad[j] == BH_R1CS_SATISFIED) good.push_back(j);
-    else codes[j] = BH_ERR_UNSATISFIABLE;
-  }
-  const size_t n = good.size();
-  std::vector<WitnessView> ws(n);
-  std::vector<Fr> rr(n), ss(n);
-  std::vector<Proof> ps(n);
-  std::vector<int> cs(n, BH_OK);
-  for (size_t i = 0; i < n; i++) { ws[i] = witnesses[good[i]]; rr[i] = r[good[i]]; ss[i] = s[good[i]]; }
-  prove_witness_batch_codes(r1cs, params, ws.data(), n, rr.data(), ss.data(), ps.data(), cs.data(), tm, workspace_budget, mode);
-  for (size_t i = 0; i < n; i++) { proofs[good[i]] = ps[i]; codes[good[i]] = cs[i]; }
-  if (tm) { tm->synthesis_ms = (float)pre_ms; tm->total_ms = (float)(now_ms() - t0); }
-}
-
-std::vector<Proof> prove_witness_batch_checked(const R1cs &r1cs, Parameters &params, const std::vector<WitnessView> &witnesses,
-                                               const std::vector<std::pair<Fr, Fr>> &rs, std::vector<uint32_t> *first_unsatisfied,
-                                               ProveTimings *tm, size_t workspace_budget, int mode) {
-  const size_t k = witnesses.size();
-  std::vector<Fr> r, s;
-  split_rs(rs, k, r, s);
-  std::vector<Proof> proofs(k);
-  std::vector<int> codes(k, BH_OK);
-  std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
-  prove_witness_batch_checked_codes(r1cs, params, witnesses.data(), k, r.data(), s.data(), proofs.data(), codes.data(),
-                                    first_bad.data(), tm, workspace_budget, mode);
-  if (first_unsatisfied) *first_unsatisfied = first_bad;
-  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
-  return proofs;
-}
-
-// ---- k proofs from witnesses that are in device memory already (groth16.hpp DeviceWitnesses) ---------------------------
-// The finish rule of flags without a finish bit: device finishing where it was measured ahead of host finishing by more
-// than the host variant's own spread at every shape of that k.  Measured (tools/bench_prove_batch_dev.py,
-// profiles/prove_batch_dev_bench.json, DESIGN.md 5.5.2: MiMC-322, chain 2^14 / 2^16, boolean 2^16; k = 16 and 256): ahead at
-// three of the four k = 256 shapes in each of three runs, at chain 2^16 x 256 in one run of three, and at no k = 16 shape -
-// no k qualifies reproducibly: never.  Device finishing is forced-only, as the grouped path is (mode 3 over device
-// witnesses: 0.54 - 0.90 x the proofs in flight at k = 256, same file).
-static bool finish_on_device_by_rule(size_t /*k*/, size_t /*n_constraints*/) { return false; }
-
-// The grouped path (BATCH_GROUPED_HE of prove_witness_batch_codes: five many-jobs, ONE constraint evaluation and ONE batched
-// h block per group) over resident witnesses: the sums and per-proof codes of the witnesses good[0 .. n), which are
-// indices into the caller's strided buffers.  A group is a run of CONSECUTIVE proved witnesses within the budget - an
-// unsatisfied witness in between ends it - so that a group's vectors are the caller's pointers at its first witness with
-// the caller's strides: nothing is copied.  h_in: the host copy of the input vectors (k x n_in) where the `inputs`
-// multiexps are answered on the host, else empty.  A runtime failure throws once the group's jobs have drained.
-static void grouped_sums_resident(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w, const std::vector<size_t> &good,
-                                  const std::vector<Fr> &h_in, size_t workspace_budget, std::vector<MsmSums> &sums,
-                                  std::vector<int> &rc, double &h_ms, double &msm_ms) {
-  bh_ctx *ctx = params.ctx;
-  const size_t n = good.size(), n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
-  const Domain dom = domain_of(r1cs.num_constraints);
-  const size_t m = dom.m, vec = m * 32;
-  const uint32_t log_m = dom.log_m;
-  const size_t budget = workspace_budget ? workspace_budget : BATCH_WORKSPACE_BYTES;
-  const size_t group = std::min<size_t>(std::max<size_t>(budget / (4 * vec), 1), 4096);   // a, b, c and a scratch vector each
-  Densities dens;
-  dens.of(r1cs);
-  const QueryTable queries_of = queries(params, n_in, dens.b_in_total);
-  std::vector<std::array<int, N_SLOTS>> rcs(n);
-  for (size_t first = 0; first < n;) {
-    size_t g = 1;
-    while (first + g < n && g < group && good[first + g] == good[first + g - 1] + 1) g++;
-    const double t1 = now_ms();
-    const char *d_in = (const char *)w.inputs + good[first] * w.in_stride, *d_aux = (const char *)w.aux + good[first] * w.aux_stride;
-    const size_t scratch_bytes = log_m > 11 ? g * vec : 32;
-    DevBuf da(ctx, g * vec), db(ctx, g * vec), dc(ctx, g * vec), dscratch(ctx, scratch_bytes);
-    ProofStream ps(ctx);
-    StreamDrain drain{ps};
-    InFlight<bh_msm_job> in_jobs(g * N_SLOTS);   // witness j's `inputs` multiexps at j * N_SLOTS + slot
-    InFlight<bh_msm_many_job> many_jobs(N_SLOTS);
-    auto issue_many = [&](Slot slot, const void *scalars, size_t stride, size_t len) {
-      const Query &q = queries_of[slot];
-      const uint64_t *d = dens.dev_of(q.density);
-      check(bh_msm_many_async_dev(ctx, q.bases, q.skip, scalars, stride, len, g, BH_SCALARS_MONT, d, d ? len : 0, nullptr, ps.st,
-                                  &many_jobs.at[slot]));
-    };
-    for (Slot slot : ISSUE_ORDER)
-      if (queries_of[slot].scalars == FROM_AUX) issue_many(slot, d_aux, w.aux_stride, n_aux);
-    check(bh_r1cs_eval_many_dev(ctx, r1cs.handle, d_in, w.in_stride, d_aux, w.aux_stride, g, da.p, db.p, dc.p, vec, log_m, ps.st));
-    check(bh_h_poly_fr_many_dev_on(ctx, da.p, db.p, dc.p, vec, g, log_m, BH_FFT_MANY_FORCE, dscratch.p, scratch_bytes, ps.st));
-    issue_many(H, da.p, vec, m - 1);   // a.len() - 1
-    for (size_t j = 0; j < g; j++)
-      for (Slot slot : ISSUE_ORDER) {
-        const Query &q = queries_of[slot];
-        if (q.scalars != FROM_INPUTS) continue;
-        const uint64_t *dh = dens.host_of(q.density), *dd = dens.dev_of(q.density);
-        bh_msm_job **job = &in_jobs.at[j * N_SLOTS + slot];
-        if (!h_in.empty())
-          check(bh_msm_async(ctx, q.bases, q.skip, h_in.data() + good[first + j] * n_in, n_in, BH_SCALARS_MONT, dh, dh ? n_in : 0, job));
-        else
-          check(bh_msm_async_dev_after(ctx, q.bases, q.skip, d_in + j * w.in_stride, n_in, BH_SCALARS_MONT, dd, dd ? n_in : 0, nullptr,
-                                       ps.st, job));
-      }
-    const double t2 = now_ms();
-    for (size_t j = 0; j < g; j++)
-      for (Slot slot : WAIT_ORDER)
-        if (queries_of[slot].scalars == FROM_INPUTS)
-          rcs[first + j][slot] = bh_msm_wait(in_jobs.take(j * N_SLOTS + slot), sum_at(sums[first + j], slot));
-    std::vector<unsigned char> recs(g * sizeof(G2Affine));
-    std::vector<int32_t> codes_v(g);
-    for (Slot slot : WAIT_ORDER) {
-      if (queries_of[slot].scalars == FROM_INPUTS) continue;
-      check(bh_msm_many_wait(many_jobs.take(slot), recs.data(), codes_v.data(), nullptr, nullptr));
-      for (size_t j = 0; j < g; j++) {
-        memcpy(sum_at(sums[first + j], slot), recs.data() + j * slot_bytes(slot), slot_bytes(slot));
-        rcs[first + j][slot] = codes_v[j];
-      }
-    }
-    h_ms += t2 - t1;
-    msm_ms += now_ms() - t2;
-    first += g;
-  }
-  for (size_t i = 0; i < n; i++) {
-    rc[i] = BH_OK;
-    for (Slot slot : WAIT_ORDER)
-      if (rcs[i][slot] != BH_OK) { rc[i] = rcs[i][slot]; break; }
-    if (rc[i] < 0) check(rc[i]);   // a runtime failure is the call's
-  }
-}
-
-void prove_witness_batch_dev_codes(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w, const Fr *r, const Fr *s,
-                                   unsigned flags, void *stream, Proof *proofs, int *codes, uint32_t *first_unsatisfied,
-                                   ProveTimings *tm, size_t workspace_budget, int mode) {
-  const size_t k = w.k, n_in = r1cs.num_inputs, n_aux = r1cs.num_aux;
-  if (mode != BATCH_AUTO && mode != BATCH_GROUPED_HE) throw std::invalid_argument("mode: BATCH_AUTO or BATCH_GROUPED_HE");
-  if ((flags & BH_PROVE_FINISH_DEVICE) && (flags & BH_PROVE_FINISH_HOST)) throw std::invalid_argument("both finish bits");
-  if (flags & ~(BH_PROVE_CHECK | BH_PROVE_FINISH_DEVICE | BH_PROVE_FINISH_HOST)) throw std::invalid_argument("unknown flag");
-  // the layout rules of bh_r1cs_check_many_dev, before anything runs
-  if (w.in_stride % 32 || w.aux_stride % 32 || w.in_stride < n_in * 32 || w.aux_stride < n_aux * 32)
-    throw std::invalid_argument("witness strides: multiples of 32 bytes, at least the vector's length");
-  if (k && ((n_in && !w.inputs) || (n_aux && !w.aux))) throw std::invalid_argument("null witness buffer");
-  if (tm) *tm = ProveTimings{0, 0, 0, 0};
-  if (!k) return;
-  bh_ctx *ctx = params.ctx;
-  const double t0 = now_ms();
-  // whatever wrote the witnesses (the caller's solve) has finished; null is the context's stream
-  check(bh_stream_synchronize(ctx, stream));
-  auto in_at = [&](size_t j) { return (const char *)w.inputs + j * w.in_stride; };
-  auto aux_at = [&](size_t j) { return (const char *)w.aux + j * w.aux_stride; };
-
-  // which witnesses are proved: all of them, or the satisfied ones - by index, nothing is copied or compacted
-  std::vector<size_t> good;
-  if (flags & BH_PROVE_CHECK) {
-    std::vector<uint32_t> first_bad(k);
-    {
-      DevBuf d_bad(ctx, k * sizeof(uint32_t));
-      ProofStream ps(ctx);
-      StreamDrain drain{ps};
-      check(bh_r1cs_check_many_dev(ctx, r1cs.handle, w.inputs, w.in_stride, w.aux, w.aux_stride, k, (uint32_t *)d_bad.p, ps.st));
-      check(bh_stream_synchronize(ctx, ps.st));
-      check(bh_dev_download(ctx, first_bad.data(), d_bad.p, k * sizeof(uint32_t)));
-    }
-    for (size_t j = 0; j < k; j++) {
-      if (first_unsatisfied) first_unsatisfied[j] = first_bad[j];
-      if (first_bad[j] == BH_R1CS_SATISFIED) good.push_back(j);
-      else codes[j] = BH_ERR_UNSATISFIABLE;
-    }
-  } else {
-    for (size_t j = 0; j < k; j++) good.push_back(j);
-  }
-  const double t1 = now_ms();
-  const size_t n = good.size();
-  // the `inputs` multiexps of a few terms are answered on the host: one small download of the input vectors
-  std::vector<Fr> h_in;
-  if (n_in && n_in <= 8) {
-    h_in.resize(k * n_in);
-    if (w.in_stride == n_in * 32) check(bh_dev_download(ctx, h_in.data(), w.inputs, k * n_in * 32));
-    else
-      for (size_t j = 0; j < k; j++) check(bh_dev_download(ctx, h_in.data() + j * n_in, in_at(j), n_in * 32));
-  }
-  const bool on_device = (flags & BH_PROVE_FINISH_DEVICE) ||
-                         (!(flags & BH_PROVE_FINISH_HOST) && finish_on_device_by_rule(k, r1cs.num_constraints));
-  const bool subverted = params.vk.delta_g1.is_identity() || params.vk.delta_g2.is_identity();   // prover.rs:320-324
-  std::vector<Fr> rr(n), ss(n);
-  for (size_t i = 0; i < n; i++) { rr[i] = r[good[i]]; ss[i] = s[good[i]]; }
-  // (host finishing: the blinding terms beside the GPU work, as in every other path; an identity delta fails there)
-  std::unique_ptr<Blinding> blind;
-  if (!on_device && n) blind.reset(new Blinding(params, rr.data(), ss.data(), n));
-
-  // the eight multiexps of every proved witness by the single-proof path, BATCH_IN_FLIGHT at a time, waited in order
-  // (BATCH_GROUPED_HE, forced only: by the grouped path)
-  struct Job {
-    std::thread th;
-    MsmSums sums;
-    ProveTimings tm = {0, 0, 0, 0};
-    std::exception_ptr error;
-    ~Job() { if (th.joinable()) th.join(); }   // whatever unwinds this frame: the job is drained first
-  };
-  std::vector<MsmSums> sums(n);
-  std::vector<int> rc(n, BH_OK);
-  std::exception_ptr fatal;
-  double h_ms = 0, msm_ms = 0;
-  if (mode == BATCH_GROUPED_HE) {
-    try {
-      grouped_sums_resident(r1cs, params, w, good, h_in, workspace_budget, sums, rc, h_ms, msm_ms);
-    } catch (...) {
-      fatal = std::current_exception();   // (its jobs have drained: InFlight)
-    }
-  }
-  std::vector<std::unique_ptr<Job>> jobs(n);   // declared after everything a job writes: destroyed, and so joined, first
-  auto finish = [&](size_t i) {
-    Job &job = *jobs[i];
-    job.th.join();
-    if (job.error) {
-      try {
-        std::rethrow_exception(job.error);
-      } catch (const SynthesisError &e) {
-        if (e.code < 0) { if (!fatal) fatal = job.error; }
-        else rc[i] = e.code;
-      } catch (...) {
-        if (!fatal) fatal = job.error;
-      }
-    }
-    sums[i] = job.sums;
-    h_ms += job.tm.h_poly_ms;
-    msm_ms += job.tm.msm_ms;
-    jobs[i].reset();
-  };
-  for (size_t i = 0; i < n && mode == BATCH_AUTO; i++) {
-    if (i >= BATCH_IN_FLIGHT) finish(i - BATCH_IN_FLIGHT);
-    AssignmentSource src;
-    src.n_in = n_in; src.n_aux = n_aux; src.n_cons = r1cs.num_constraints; src.r1cs = &r1cs;
-    src.inputs = h_in.empty() ? nullptr : h_in.data() + good[i] * n_in;
-    src.aux = nullptr;
-    src.resident = true;
-    src.inputs_dev = in_at(good[i]);
-    src.aux_dev = aux_at(good[i]);
-    jobs[i].reset(new Job());
-    Job *job = jobs[i].get();
-    Parameters *pp = &params;
-    job->th = std::thread([job, src, pp] {
-      try { msm_sums(src, *pp, 0, 1, job->sums, &job->tm); } catch (...) { job->error = std::current_exception(); }
-    });
-  }
-  for (size_t i = n > BATCH_IN_FLIGHT ? n - BATCH_IN_FLIGHT : 0; i < n && mode == BATCH_AUTO; i++) finish(i);   // all drained
-  if (blind) blind->join();
-  if (fatal) std::rethrow_exception(fatal);
-  if (blind && blind->error && !subverted) std::rethrow_exception(blind->error);
-  // an identity delta beats whatever a multiexp reported (first_failure, groth16_internal.hpp)
-  for (size_t i = 0; i < n; i++) codes[good[i]] = subverted ? BH_ERR_UNEXPECTED_IDENTITY : rc[i];
-  if (!subverted) {
-    if (on_device) {
-      // the sums of the proofs that have them, k' x 960 on the host, uploaded once; the proofs come back in one download
-      std::vector<size_t> done;
-      for (size_t i = 0; i < n; i++)
-        if (rc[i] == BH_OK) done.push_back(i);
-      std::vector<MsmSums> m(done.size());
-      std::vector<Fr> r2(done.size()), s2(done.size());
-      for (size_t d = 0; d < done.size(); d++) { m[d] = sums[done[d]]; r2[d] = rr[done[d]]; s2[d] = ss[done[d]]; }
-      const std::vector<Proof> out = assemble_proofs(params, m.data(), r2.data(), s2.data(), done.size());
-      for (size_t d = 0; d < done.size(); d++) proofs[good[done[d]]] = out[d];
-    } else {
-      for (size_t i = 0; i < n; i++)
-        if (rc[i] == BH_OK) proofs[good[i]] = finish_proof(blind->terms[i], sums[i], rr[i], ss[i]);
-    }
-  }
-  if (tm) {
-    tm->synthesis_ms = (float)(t1 - t0);
-    tm->h_poly_ms = (float)h_ms;
-    tm->msm_ms = (float)msm_ms;
-    tm->total_ms = (float)(now_ms() - t0);
-  }
-}
-
-std::vector<Proof> prove_witness_batch_dev(const R1cs &r1cs, Parameters &params, const DeviceWitnesses &w,
-                                           const std::vector<std::pair<Fr, Fr>> &rs, unsigned flags, void *stream,
-                                           std::vector<uint32_t> *first_unsatisfied, ProveTimings *tm) {
-  const size_t k = w.k;
-  std::vector<Fr> r, s;
-  split_rs(rs, k, r, s);
-  std::vector<Proof> proofs(k);
-  std::vector<int> codes(k, BH_OK);
-  std::vector<uint32_t> first_bad(k, BH_R1CS_SATISFIED);
-  prove_witness_batch_dev_codes(r1cs, params, w, r.data(), s.data(), flags, stream, proofs.data(), codes.data(),
-                                (flags & BH_PROVE_CHECK) ? first_bad.data() : nullptr, tm);
-  if (first_unsatisfied && (flags & BH_PROVE_CHECK)) *first_unsatisfied = first_bad;
-  for (size_t j = 0; j < k; j++) check(codes[j]);   // what the first failing proof would throw
-  return proofs;
 }
 
 // ---- structure capture (generator.rs:43-131 KeypairAssembly, plus the input rows of prover.rs:208-215)
@@ -1347,70 +828,3 @@ Proof create_proof(Circuit &circuit, Parameters &params, const Fr &r, const Fr &
 }
 
 }  // namespace groth16
-
-// bh_groth16_prove_witness_batch_dev
-int prove_witness_batch_dev_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs_dev, size_t in_stride,
-                                    const void *aux_dev, size_t aux_stride, size_t k, const void *r, const void *s, unsigned flags,
-                                    void *stream, void *proofs_out, int32_t *rcs, uint32_t *first_unsatisfied, float *timings4,
-                                    size_t workspace_budget, int mode) {
-  using namespace groth16;
-  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
-  if (k && (!r || !s || !proofs_out || !rcs)) return BH_ERR_INVALID_ARG;
-  ProveTimings tm = {0, 0, 0, 0};
-  const int rc = guarded([&] {
-    R1csView view(r1cs);
-    std::vector<Fr> rr(k), ss(k);
-    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
-    std::vector<Proof> proofs(k);
-    std::vector<int> codes(k, BH_OK);
-    prove_witness_batch_dev_codes(view.r, *params->p, DeviceWitnesses{inputs_dev, in_stride, aux_dev, aux_stride, k}, rr.data(),
-                                  ss.data(), flags, stream, proofs.data(), codes.data(), first_unsatisfied, &tm, workspace_budget, mode);
-    for (size_t j = 0; j < k; j++) {
-      char *out = (char *)proofs_out + j * 384;
-      rcs[j] = codes[j];
-      if (codes[j] == BH_OK) write_proof(out, proofs[j]);
-      else memset(out, 0, 384);
-    }
-    return BH_OK;
-  });
-  write_timings(timings4, tm);
-  return rc;
-}
-
-// bh_groth16_prove_witness_batch (and _checked), and the test library's twins with a workspace budget and a mode of their own
-int prove_witness_batch_guarded(bh_params *params, const bh_r1cs *r1cs, const void *inputs, size_t n_inputs, const void *aux,
-                                size_t n_aux, size_t k, const void *r, const void *s, void *proofs_out, int32_t *rcs,
-                                float *timings4, size_t workspace_budget, int mode, bool checked, uint32_t *first_unsatisfied) {
-  using namespace groth16;
-  if (!params || !r1cs) return BH_ERR_INVALID_ARG;
-  if (k && (!r || !s || !proofs_out || !rcs || (n_inputs && !inputs) || (n_aux && !aux))) return BH_ERR_INVALID_ARG;
-  ProveTimings tm = {0, 0, 0, 0};
-  const int rc = guarded([&] {
-    R1csView view(r1cs);
-    // caller records may be unaligned: copied then (the witnesses of a large circuit are tens of megabytes each - an
-    // aligned caller's arrays are read in place)
-    std::vector<Fr> in, ax, rr(k), ss(k);
-    const Fr *in_p = (const Fr *)inputs, *ax_p = (const Fr *)aux;
-    if ((uintptr_t)inputs % alignof(Fr) && k * n_inputs) { in.resize(k * n_inputs); memcpy(in.data(), inputs, k * n_inputs * 32); in_p = in.data(); }
-    if ((uintptr_t)aux % alignof(Fr) && k * n_aux) { ax.resize(k * n_aux); memcpy(ax.data(), aux, k * n_aux * 32); ax_p = ax.data(); }
-    if (k) { memcpy(rr.data(), r, k * 32); memcpy(ss.data(), s, k * 32); }
-    std::vector<WitnessView> ws(k);
-    for (size_t j = 0; j < k; j++) ws[j] = WitnessView{in_p + j * n_inputs, n_inputs, ax_p + j * n_aux, n_aux};
-    std::vector<Proof> proofs(k);
-    std::vector<int> codes(k, BH_OK);
-    if (checked)   // bh_groth16_prove_witness_batch_checked: the check pre-pass, then the satisfied witnesses as below
-      prove_witness_batch_checked_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(),
-                                        first_unsatisfied, &tm, workspace_budget, mode);
-    else
-      prove_witness_batch_codes(view.r, *params->p, ws.data(), k, rr.data(), ss.data(), proofs.data(), codes.data(), &tm, workspace_budget, mode);
-    for (size_t j = 0; j < k; j++) {
-      char *out = (char *)proofs_out + j * 384;
-      rcs[j] = codes[j];
-      if (codes[j] == BH_OK) write_proof(out, proofs[j]);
-      else memset(out, 0, 384);
-    }
-    return BH_OK;
-  });
-  write_timings(timings4, tm);
-  return rc;
-}

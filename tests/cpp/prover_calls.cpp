@@ -1,19 +1,24 @@
-// The Groth16 prover host layer (csrc/groth16_prover.cpp, groth16_callsites.cpp) calls only the C ABI of
+// The Groth16 prover host layer (csrc/groth16_prover.cpp, groth16_batch.cpp, groth16_callsites.cpp) calls only the C ABI of
 // include/bellman_hip.h, so it runs here against a FAKE of that ABI - no GPU, no shared library.  The fake keeps a ledger
 // (buffers, streams, jobs and what each job / queued stream operation was given pointers into) and a transcript of every
 // call in a form free of addresses and scheduling.  Two things are held:
 //   1. transcript: the calls of every scenario equal tests/cpp/prover_calls.expected.txt, which was recorded by this same
-//      program built against the csrc of the commit BEFORE the prover paths were folded onto one multiexp table - it is
-//      never regenerated from later code: a line that differs is a bug in the prover;
+//      program in two parts.  Lines 1-1328 (host witnesses, up to the wrong-shaped witnesses): built against the csrc of the
+//      commit BEFORE the prover paths were folded onto one multiexp table.  From line 1329 (the "dev ..." scenarios, witnesses
+//      in device memory): built against the csrc of the commit BEFORE the grouped body of prove_witness_batch_dev_codes and
+//      that of prove_witness_batch_codes were folded into one and the k-proof paths moved to groth16_batch.cpp; the first
+//      part came out byte-identical in that recording.  Neither part is ever regenerated from later code: a line that
+//      differs is a bug in the prover;
 //   2. unwind: with each fallible call of a scenario made to fail in turn (issue / stream / memory calls with BH_ERR_HIP, a
 //      job's wait with BH_ERR_UNEXPECTED_EOF, once more with an identity delta_g1 on top), every issued job is waited on
 //      exactly once, every buffer is freed and every stream destroyed, no buffer is freed while an unwaited job or an
 //      unsynchronised stream operation refers to it - and the code or exception equals the recorded one.  (The ledger is
 //      an invariant of the code under test and not part of the record: the recorded commit itself left it dirty in 12 runs
 //      - a failing allocation or upload of a host-evaluated proof's density maps freed the maps uploaded before it under
-//      their queued uploads.)
+//      their queued uploads; the commit of the second part in 4 runs of "dev grouped, checked" - a failing upload, finish or
+//      download of assemble_proofs freed its buffers under what was queued on the context's stream.)
 // usage: prover_calls.bin EXPECTED        compare (exit 0 / 1)
-//        prover_calls.bin --record FILE   write the transcript (only ever against the commit named above)
+//        prover_calls.bin --record FILE   write the transcript (only ever against the commits named above)
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -52,7 +57,11 @@ struct bh_r1cs {
 
 namespace {
 enum Kind { PLAIN = 0, ISSUE = 1, WAIT = 2 };
-struct Region { int id; size_t size; std::string name; bool dev; };
+// dev: a device buffer - pointers into it are bounds-checked and tracked in a job's / a stream's references.  callers: a
+// device buffer that belongs to the caller of the prover (resident witnesses): tracked like any other, so that a buffer of
+// the proof freed under a job that also reads the caller's stays findable, but never freed by the prover and not counted
+// as "never freed".
+struct Region { int id; size_t size; std::string name; bool dev; bool callers = false; };
 struct Stream { std::vector<int> pending; bool live = true; };
 struct Fallible { std::string line; int occ; int kind; };
 
@@ -108,9 +117,9 @@ std::string P(const void *p, std::vector<int> *refs = nullptr) {
   if (refs && r->dev) refs->push_back(r->id);
   return fmt("%s[%zu]+%zu", r->name.c_str(), r->size, off);
 }
-void *add_region(size_t bytes, const char *name, bool dev) {
+void *add_region(size_t bytes, const char *name, bool dev, bool callers = false) {
   void *p = malloc(bytes ? bytes : 1);
-  regions[(uintptr_t)p] = Region{next_region++, bytes, name, dev};
+  regions[(uintptr_t)p] = Region{next_region++, bytes, name, dev, callers};
   return p;
 }
 void name_host(const char *name, const void *p, size_t bytes) {
@@ -414,6 +423,19 @@ int bh_r1cs_check_many_dev(bh_ctx *, const bh_r1cs *, const void *in, size_t in_
   queue_on(st, refs);
   return BH_OK;
 }
+int bh_proof_finish_dev(bh_ctx *, const void *vk5, const void *sums, const void *r, const void *s, size_t k, void *proofs, void *st) {
+  LOCK;
+  std::vector<int> refs;
+  const std::string line = fmt("bh_proof_finish_dev vk5=%s sums=%s r=%s s=%s k=%zu -> %s %s", P(vk5).c_str(), P(sums, &refs).c_str(),
+                               P(r, &refs).c_str(), P(s, &refs).c_str(), k, P(proofs, &refs).c_str(), S(st));
+  if (int rc = note(line, ISSUE)) return rc;
+  in_bounds(sums, k * BH_MSM_SUMS_BYTES, "bh_proof_finish_dev");
+  in_bounds(r, k * 32, "bh_proof_finish_dev");
+  in_bounds(s, k * 32, "bh_proof_finish_dev");
+  if (in_bounds(proofs, k * 384, "bh_proof_finish_dev")) memset(proofs, 0, k * 384);
+  queue_on(st, refs);
+  return BH_OK;
+}
 }  // extern "C"
 
 // ---- fixtures -------------------------------------------------------------------------------------------------------------
@@ -434,6 +456,7 @@ struct World {
   std::unique_ptr<groth16::Parameters> params;
   std::unique_ptr<groth16::R1cs> shape;
   std::vector<groth16::WitnessView> views;
+  void *dev_inputs = nullptr, *dev_aux = nullptr;   // the caller's device buffers (resident)
   World(size_t n_in_, size_t n_aux_, size_t n_cons_, size_t k_ = 1, size_t gap_ = 0, bool identity_delta = false)
       : n_in(n_in_), n_aux(n_aux_), n_cons(n_cons_), k(k_), gap(gap_) {
     Quiet q;
@@ -475,7 +498,24 @@ struct World {
     params.reset();
     std::lock_guard<std::mutex> g(mu);
     for (int i = 0; i < 3; i++) free(r1cs.dev[i]);
+    free(dev_inputs);
+    free(dev_aux);
     regions.clear();
+  }
+  // the k witnesses once more in two caller-owned device buffers, `pad` bytes between one vector's end and the next
+  groth16::DeviceWitnesses resident(size_t pad) {
+    Quiet q;
+    std::lock_guard<std::mutex> g(mu);
+    const size_t in_stride = n_in * 32 + pad, aux_stride = n_aux * 32 + pad;
+    dev_inputs = add_region(k * in_stride, "dev_inputs", true, true);
+    dev_aux = add_region(k * aux_stride, "dev_aux", true, true);
+    memset(dev_inputs, 0, k * in_stride);
+    memset(dev_aux, 0, k * aux_stride);
+    for (size_t j = 0; j < k; j++) {
+      memcpy((char *)dev_inputs + j * in_stride, (const void *)views[j].inputs, n_in * 32);
+      memcpy((char *)dev_aux + j * aux_stride, (const void *)views[j].aux, n_aux * 32);
+    }
+    return groth16::DeviceWitnesses{dev_inputs, in_stride, dev_aux, aux_stride, k};
   }
   groth16::AssignmentView assignment() const {
     return groth16::AssignmentView{a.data(), b.data(), c.data(), n_cons, inputs.data(), n_in, aux.data(), n_aux,
@@ -512,7 +552,7 @@ std::string ledger() {
   for (auto &j : jobs) unwaited += !j->waited;
   for (auto &j : many_jobs) unwaited += !j->waited;
   for (auto &s : streams) live_streams += s->live;
-  for (auto &r : regions) live_buffers += r.second.dev;
+  for (auto &r : regions) live_buffers += r.second.dev && !r.second.callers;
   if (unwaited) v.push_back(fmt("%zu jobs never waited on", unwaited));
   if (live_streams) v.push_back(fmt("%zu streams never destroyed", live_streams));
   if (live_buffers) v.push_back(fmt("%zu buffers never freed", live_buffers));
@@ -649,6 +689,60 @@ Scenario wrong_shape(const char *name, int door) {
   }};
 }
 
+// prove_witness_batch_dev_codes over World's resident witnesses (n_in inputs, N_AUX aux, 13 constraints)
+Scenario dev_batch(const char *name, size_t n_in, size_t k, size_t pad, unsigned flags, int mode, size_t budget, bool sweep) {
+  return Scenario{name, sweep, [=](bool idd) {
+    World w(n_in, N_AUX, 13, k, 0, idd);
+    const groth16::DeviceWitnesses dw = w.resident(pad);
+    const bool checked = flags & BH_PROVE_CHECK;
+    if (checked) check_answers = {BH_R1CS_SATISFIED, BH_R1CS_SATISFIED, 7, BH_R1CS_SATISFIED};
+    std::vector<groth16::Proof> proofs(k);
+    std::vector<int> codes(k, -99);
+    std::vector<uint32_t> bad(k, 0);
+    return ledgered(w, [&] {
+      groth16::prove_witness_batch_dev_codes(*w.shape, *w.params, dw, w.r.data(), w.s.data(), flags, nullptr, proofs.data(), codes.data(),
+                                             checked ? bad.data() : nullptr, nullptr, budget, mode);
+      std::string t = codes_text(codes);
+      if (checked) { t += " first_unsatisfied"; for (uint32_t x : bad) t += fmt(" %u", x); }
+      return t;
+    });
+  }};
+}
+// what prove_witness_batch_dev_codes refuses before anything runs, and k = 0
+Scenario dev_refusals(const char *name) {
+  return Scenario{name, false, [=](bool) {
+    World w(2, N_AUX, 13, 2);
+    const groth16::DeviceWitnesses ok = w.resident(0);
+    groth16::Proof proofs[2];
+    int codes[2];
+    std::string t;
+    auto attempt = [&](const char *what, groth16::DeviceWitnesses dw, unsigned flags, int mode) {
+      t += fmt(" [%s: ", what) + outcome_of([&] {
+        groth16::prove_witness_batch_dev_codes(*w.shape, *w.params, dw, w.r.data(), w.s.data(), flags, nullptr, proofs, codes, nullptr,
+                                               nullptr, 0, mode);
+        return std::string();
+      }) + "]";
+    };
+    groth16::DeviceWitnesses dw = ok;
+    dw.in_stride += 8;
+    attempt("stride no multiple of 32", dw, 0, groth16::BATCH_AUTO);
+    dw = ok;
+    dw.aux_stride -= 32;
+    attempt("stride shorter than the vector", dw, 0, groth16::BATCH_AUTO);
+    attempt("both finish bits", ok, BH_PROVE_FINISH_DEVICE | BH_PROVE_FINISH_HOST, groth16::BATCH_AUTO);
+    attempt("unknown flag", ok, 8u, groth16::BATCH_AUTO);
+    attempt("mode BATCH_GROUPED", ok, 0, groth16::BATCH_GROUPED);
+    dw = ok;
+    dw.inputs = nullptr;
+    attempt("null buffer", dw, 0, groth16::BATCH_AUTO);
+    dw = ok;
+    dw.k = 0;
+    attempt("k = 0", dw, 0, groth16::BATCH_AUTO);
+    close_ledger();
+    return "refusals" + t;
+  }};
+}
+
 std::vector<Scenario> scenarios() {
   std::vector<Scenario> v;
   // the `inputs` multiexps go to the host at <= 8 terms; the two issue strategies split at log_m <= 16
@@ -680,6 +774,17 @@ std::vector<Scenario> scenarios() {
   v.push_back(wrong_shape("wrong-shaped witness: prove_witness_part", 1));
   v.push_back(wrong_shape("wrong-shaped witness: prove_witness_batch_codes", 2));
   v.push_back(wrong_shape("wrong-shaped witness: which_is_unsatisfied", 3));
+  // ---- the second part of the record: witnesses in device memory (prove_witness_batch_dev_codes).  Domain 16 as above
+  const unsigned CHECK = BH_PROVE_CHECK, ON_DEV = BH_PROVE_FINISH_DEVICE, ON_HOST = BH_PROVE_FINISH_HOST;
+  v.push_back(dev_batch("dev in-flight, one witness", 2, 1, 0, 0, groth16::BATCH_AUTO, 0, true));
+  v.push_back(dev_batch("dev in-flight, inputs on device", 9, 1, 0, ON_HOST, groth16::BATCH_AUTO, 0, true));
+  v.push_back(dev_batch("dev in-flight k=3", 2, 3, 96, 0, groth16::BATCH_AUTO, 0, false));
+  v.push_back(dev_batch("dev grouped k=5 in groups of 2, 2, 1", 2, 5, 0, ON_HOST, groth16::BATCH_GROUPED_HE, 8 * 512, true));
+  // (a group cap of 3: the groups {0, 1} and {3, 4} show the break at the unsatisfied witness, not the cap)
+  v.push_back(dev_batch("dev grouped, checked, witness 2 unsatisfied", 2, 5, 96, CHECK | ON_DEV, groth16::BATCH_GROUPED_HE, 12 * 512, true));
+  v.push_back(dev_batch("dev grouped, inputs on device", 9, 3, 96, ON_HOST, groth16::BATCH_GROUPED_HE, 0, true));
+  v.push_back(dev_batch("dev in-flight, checked, witness 2 unsatisfied", 2, 4, 0, CHECK, groth16::BATCH_AUTO, 0, false));
+  v.push_back(dev_refusals("dev refusals"));
   return v;
 }
 }  // namespace

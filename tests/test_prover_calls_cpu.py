@@ -1,8 +1,11 @@
 """The Groth16 prover host layer against a fake C ABI (tests/cpp/prover_calls.cpp): the sequence of C-ABI calls of every
 prover path, and the outcome and the clean-up when each of those calls fails in turn, equal the record in
-tests/cpp/prover_calls.expected.txt.  The record was made by the same program from the prover as it stood before its
-paths were put on one table of the eight multiexps; it is data, never regenerated from later code.  Run twice: as built
-by default, and with every source under ASan + UBSan (a stand-alone program, nothing preloaded)."""
+tests/cpp/prover_calls.expected.txt.  The record was made by the same program in two parts: lines 1-1328 (host witnesses)
+from the prover as it stood before its paths were put on one table of the eight multiexps; from line 1329 (the "dev ..."
+scenarios: prove_witness_batch_dev_codes over witnesses in device memory, bh_proof_finish_dev) from the prover as it stood
+before the grouped bodies of its two batch entries were folded into one and moved to csrc/groth16_batch.cpp.  Both parts
+are data, never regenerated from later code.  Run twice: as built by default, and with every source under ASan + UBSan (a
+stand-alone program, nothing preloaded)."""
 
 import os
 import subprocess

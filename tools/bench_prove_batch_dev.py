@@ -8,7 +8,7 @@ timing only), the same values, r and s for every variant; the variants' proofs a
 
 Method (tools/bench_prove_batch.py's): host wall time, min of REPS repetitions, the variants interleaved in one process after
 one warm-up round, every variant's own max - min spread recorded.  `device_finish_wins`: the device variant is ahead of the
-host variant by more than the host variant's spread - the condition of the finish rule (groth16_prover.cpp
+host variant by more than the host variant's spread - the condition of the finish rule (groth16_batch.cpp
 finish_on_device_by_rule), which needs it at every measured shape of a k.  `grouped_wins`: mode 3 with device finishing is
 ahead of mode 0 with device finishing by more than that variant's spread - the same criterion for an automatic switch.
 
