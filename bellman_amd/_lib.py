@@ -54,6 +54,7 @@ EXPORTS = [
     "bh_groth16_prove_witness_batch_checked",
     "bh_r1cs_solver_create", "bh_r1cs_solver_release", "bh_r1cs_solver_info", "bh_r1cs_solve_many_dev", "bh_r1cs_solve_many",
     "bh_groth16_assemble_many", "bh_proof_finish_dev", "bh_groth16_prove_witness_batch_dev",
+    "bh_word_witness_create", "bh_word_witness_generate_dev", "bh_word_witness_generate", "bh_word_witness_destroy",
 ]
 # ... and what include/bellman_hip_test.h declares: test hooks and the built-in demo circuits, in libbellman_hip_test.so
 TEST_EXPORTS = [
@@ -80,6 +81,7 @@ TEST_EXPORTS = [
     "bh_test_groth16_prove_witness_batch_mode", "bh_test_fft_many_plan", "bh_test_r1cs_many_tile",
     "bh_test_groth16_prove_witness_batch_he", "bh_test_r1cs_solve_plan", "bh_test_r1cs_solver_tune",
     "bh_test_proof_finish_host", "bh_test_proof_finish_host_vk", "bh_test_groth16_prove_witness_batch_dev_mode",
+    "bh_test_word_program", "bh_test_word_witness_chunk",
 ]
 
 
@@ -312,6 +314,13 @@ def load():
     lib.bh_proof_finish_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
     lib.bh_groth16_prove_witness_batch_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, c.c_uint, vp, vp, vp, vp, vp]
     lib.bh_test_groth16_prove_witness_batch_dev_mode.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, c.c_uint, vp, vp, vp, vp, vp, sz, i32]
+    lib.bh_word_witness_create.argtypes = [vp, vp, c.POINTER(vp), vp]
+    lib.bh_word_witness_generate_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, sz, vp]
+    lib.bh_word_witness_generate.argtypes = [vp, vp, vp, vp, vp, sz]
+    lib.bh_word_witness_destroy.argtypes = [vp]
+    lib.bh_word_witness_destroy.restype = None
+    lib.bh_test_word_program.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.bh_test_word_witness_chunk.argtypes = [vp, sz]
     lib.bh_test_proof_finish_host.argtypes = [vp, vp, vp, vp, sz, vp, vp]
     lib.bh_test_proof_finish_host_vk.argtypes = [vp, vp, vp, vp, sz, vp, vp]
     lib.bh_groth16_prepare_verifying_key.argtypes = [vp, vp, vp, vp, vp, vp, sz, c.POINTER(vp)]

@@ -600,6 +600,24 @@ class Solver {
   size_t supplied = 0, defined = 0, hinted = 0, levels = 0, widest_level = 0;
 };
 
+// A word-program witness generator (bh_word_witness): k witnesses of a gadget circuit computed on the device from their
+// external words, in place of the value closures of prover.rs:206.  The descriptor comes from whoever recorded the program
+// (the Python gadgets' capture; include/bellman_hip.h has the format).
+class WordWitness {
+ public:
+  // throws std::invalid_argument with the validator's reason (BH_WORD_BAD_*) and index
+  WordWitness(bh_ctx *ctx, const bh_word_witness_desc &desc);
+  ~WordWitness();
+  WordWitness(const WordWitness &) = delete;
+  // witness j from the n_ext uint32 at ext_dev + j * ext_stride into k strided device witnesses (DeviceWitnesses' layout),
+  // enqueued on `stream` (null: the context's): generate_dev -> prove_witness_batch_dev on the same stream needs no host copy
+  void generate_dev(const void *ext_dev, size_t ext_stride, void *inputs_dev, size_t in_stride, void *aux_dev, size_t aux_stride,
+                    size_t k, void *stream = nullptr) const;
+  bh_word_witness *handle = nullptr;
+  bh_ctx *ctx = nullptr;
+  size_t num_inputs = 0, num_aux = 0, num_ext = 0;
+};
+
 class R1cs {
  public:
   R1cs(bellman::Circuit &shape_of, bh_ctx *ctx);

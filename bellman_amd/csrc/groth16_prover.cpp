@@ -693,6 +693,23 @@ void Solver::solve(Fr *inputs, Fr *aux, size_t k) const {
   if (bh_r1cs_solve_many(ctx, handle, inputs, aux, k) != BH_OK) throw std::runtime_error("bh_r1cs_solve_many failed");
 }
 
+WordWitness::WordWitness(bh_ctx *ctx_, const bh_word_witness_desc &desc)
+    : ctx(ctx_), num_inputs(desc.n_inputs), num_aux(desc.n_aux), num_ext(desc.n_ext) {
+  uint32_t bad[2] = {0, 0xFFFFFFFFu};
+  const int rc = bh_word_witness_create(ctx, &desc, &handle, bad);
+  if (rc == BH_ERR_INVALID_ARG)
+    throw std::invalid_argument(bad[0] ? "WordWitness: program refused, reason " + std::to_string(bad[0]) + " at index " + std::to_string(bad[1])
+                                       : std::string("WordWitness: malformed description"));
+  if (rc != BH_OK) throw std::runtime_error("bh_word_witness_create failed");
+}
+WordWitness::~WordWitness() { bh_word_witness_destroy(handle); }
+void WordWitness::generate_dev(const void *ext_dev, size_t ext_stride, void *inputs_dev, size_t in_stride, void *aux_dev,
+                               size_t aux_stride, size_t k, void *stream) const {
+  const int rc = bh_word_witness_generate_dev(ctx, handle, ext_dev, ext_stride, inputs_dev, in_stride, aux_dev, aux_stride, k, stream);
+  if (rc == BH_ERR_INVALID_ARG) throw std::invalid_argument("WordWitness::generate_dev: bad layout");
+  if (rc != BH_OK) throw std::runtime_error("bh_word_witness_generate_dev failed");
+}
+
 Variable WitnessAssignment::alloc(ValueFn f) {
   aux_assignment.push_back(f());
   return Variable::new_unchecked(Index::Aux, aux_assignment.size() - 1);

@@ -1,11 +1,13 @@
 // The device-resident R1CS handle (bh_r1cs), shared by r1cs.hip (products with Fr vectors), r1cs_points.hip
-// (products with vectors of group elements) and r1cs_solve.hip (witnesses completed from their supplied values).
+// (products with vectors of group elements), r1cs_solve.hip (witnesses completed from their supplied values) and
+// word_witness.hip (witnesses computed from a gadget circuit's word program).
 #pragma once
 #include <mutex>
 #include <vector>
 
 #include "common.hpp"
 #include "solve_plan.hpp"
+#include "word_program.hpp"
 
 // A row with more terms than this is summed by a whole workgroup instead of one lane: the constant
 // ONE typically appears in every constraint, so its row of a transposed matrix has ~n terms.
@@ -31,6 +33,15 @@ constexpr u32 SOLVE_WALK_ITEMS = 64;
 constexpr u32 SOLVE_WALK_MAX_W = 64;
 constexpr u64 SOLVE_LEVEL_MIN_ITEMS = (u64)1 << 18;   // 256 CUs x 256 lanes x 4
 enum : u32 { SOLVE_FORM_AUTO = 0, SOLVE_FORM_WALK = 1, SOLVE_FORM_LEVEL = 2 };
+
+// The word-program witness generator (word_witness.hip).  The run kernel gives every witness one lane, so a workgroup is one
+// wavefront: k witnesses spread over k / 64 CUs.  The expansion writes 32 bytes per lane, 256 consecutive variables of one
+// witness per workgroup.  Witnesses go through in chunks whose scratch word file (8 bytes x words x witnesses) stays within
+// WORD_SCRATCH_MAX_BYTES: 256 MiB hold 21 000 witnesses of a one-block SHA-256 (1 555 words) - beyond that a chunk's two
+// launches are long enough (tens of ms at HBM store speed) that one more pair costs nothing measurable.  Not swept.
+constexpr u32 WORD_RUN_LANES = 64;
+constexpr u32 WORD_EXPAND_LANES = 256;
+constexpr u64 WORD_SCRATCH_MAX_BYTES = (u64)256 << 20;
 
 // the 16-byte halves of an Fr record (the witness vectors are 32-byte aligned: bh_dev_alloc, strides multiples of 32)
 __device__ __forceinline__ fr_t ld_fr16(const fr_t *p) {
@@ -114,7 +125,37 @@ struct bh_r1cs_solver {
   bh::u64 level_min_items = bh::SOLVE_LEVEL_MIN_ITEMS;
 };
 
+// A word program on the device (bh_word_witness_create).  The scratch word file belongs to the handle and is reused by its
+// calls: `mu` serialises their enqueueing, `done` orders a call behind the previous one on whatever stream that ran.
+// force_chunk is written by the test library alone (bh_test_word_witness_chunk), between calls.
+struct bh_word_witness {
+  bh_ctx *ctx = nullptr;
+  size_t n_inputs = 0, n_aux = 0, n_ext = 0, n_instrs = 0, n_words = 0;
+  uint4 *instrs = nullptr;               // bh::WordInstr
+  bh::u32 *pool = nullptr;
+  uint2 *bits = nullptr;                 // bh::WordBit
+  uint2 *recs = nullptr;                 // bh::WordRec, per variable
+  std::mutex mu;
+  bh::u64 *scratch = nullptr;
+  size_t scratch_bytes = 0;
+  hipEvent_t done = nullptr;
+  bool used = false;
+  size_t force_chunk = 0;
+};
+
 namespace bh {
+// the field of word_program.hpp: Montgomery Fr of ff.cuh on the host
+struct WordFr {
+  typedef fr_t Elem;
+  static fr_t zero() { fr_t z; fe_zero(z); return z; }
+  static fr_t one() { fr_t o; fe_one(o); return o; }
+  static fr_t from_canonical(const uint64_t limbs[4]) {
+    fr_t c, r;
+    for (int i = 0; i < 4; i++) { c.l[2 * i] = (u32)limbs[i]; c.l[2 * i + 1] = (u32)(limbs[i] >> 32); }
+    fe_to_mont(r, c);
+    return r;
+  }
+};
 // what the k-witness entry points refuse in their witness buffers
 inline bool many_strides_ok(const bh_r1cs *r, const void *inputs_dev, size_t in_stride, const void *aux_dev, size_t aux_stride) {
   return in_stride % 32 == 0 && aux_stride % 32 == 0 && in_stride >= r->n_inputs * 32 && aux_stride >= r->n_aux * 32 &&

@@ -379,3 +379,28 @@ extern "C" int bh_test_r1cs_solver_tune(bh_r1cs_solver *s, uint32_t form, uint32
   s->level_min_items = level_min_items ? level_min_items : bh::SOLVE_LEVEL_MIN_ITEMS;
   return BH_OK;
 }
+
+// ---- test hooks of the word-program witness generator: validator and host interpreter on their own (host only;
+// tests/test_word_program_cpu.py) and the scratch chunk of a handle (tests/test_gpu_word_witness.py) --------------------------
+extern "C" int bh_test_word_program(const bh_word_witness_desc *desc, uint32_t bad_index[2], const uint32_t *ext, void *inputs_out,
+                                    void *aux_out, uint64_t *words_out) {
+  using namespace bh;
+  if (bad_index) { bad_index[0] = 0; bad_index[1] = WORD_NO_INDEX; }
+  if (!desc) return BH_ERR_INVALID_ARG;
+  const WordDesc &d = *reinterpret_cast<const WordDesc *>(desc);
+  const WordProgram p = word_program_validate(d);
+  if (p.status != WORD_OK) {
+    if (bad_index) { bad_index[0] = p.bad_code; bad_index[1] = p.bad_index; }
+    return p.status;
+  }
+  if (!ext && d.n_ext) return BH_OK;
+  if (!inputs_out && !aux_out) return BH_OK;
+  if (!inputs_out || (d.n_aux && !aux_out)) return BH_ERR_INVALID_ARG;
+  word_program_interpret(WordFr(), d, p, ext, (fr_t *)inputs_out, (fr_t *)aux_out, words_out);
+  return BH_OK;
+}
+extern "C" int bh_test_word_witness_chunk(bh_word_witness *w, size_t witnesses_per_chunk) {
+  if (!w) return BH_ERR_INVALID_ARG;
+  w->force_chunk = witnesses_per_chunk;
+  return BH_OK;
+}

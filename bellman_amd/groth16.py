@@ -69,6 +69,15 @@ class LinearCombination:
         coeff, var = (1, other) if isinstance(other, Variable) else other
         return LinearCombination(self.terms + [(var, (-coeff) % Q)])
 
+    def add_scaled(self, coeff, other):
+        """`self + (coeff, &other)` (src/lib.rs:263-280): every term of `other` times coeff, appended in order"""
+        coeff %= Q
+        return LinearCombination(self.terms + [(var, k * coeff % Q) for var, k in other.terms])
+
+    def sub_scaled(self, coeff, other):
+        """`self - (coeff, &other)` (src/lib.rs:282-299)"""
+        return self.add_scaled(-coeff, other)
+
 
 class ConstraintSystem:
     """src/lib.rs:374-437 (subset used by circuits: one, alloc, alloc_input, enforce)."""

@@ -770,6 +770,99 @@ int bh_r1cs_solver_info(const bh_r1cs_solver *s, size_t counts[5]);
 int bh_r1cs_solve_many_dev(bh_ctx *ctx, const bh_r1cs_solver *s, void *inputs_dev, size_t in_stride, void *aux_dev,
                            size_t aux_stride, size_t k, void *stream);
 int bh_r1cs_solve_many(bh_ctx *ctx, const bh_r1cs_solver *s, void *inputs_host, void *aux_host, size_t k);
+/* ---- the witness of a gadget circuit from its WORD PROGRAM: k witnesses computed on the device from their external words --
+ * (replaces the values `circuit.synthesize` computes in its closures, groth16/src/prover.rs:206, for circuits built from the
+ * UInt32 gadgets of src/gadgets/uint32.rs: a SHA-256 block is ~26 000 one-bit variables that a few thousand 32-bit operations
+ * determine).  A trace word is a u64; words 0 .. n_ext - 1 are EXTERNAL - one uint32 each per witness, e.g. the message -
+ * and instruction j writes word n_ext + j from words below its own.  The 32-bit operations read the low 32 bits of their
+ * sources and write a 32-bit value:
+ *   BH_WORD_CONST  a = the value          BH_WORD_ROTR, BH_WORD_SHR  word a by b, 1 <= b <= 31      BH_WORD_XOR, BH_WORD_AND  words a, b
+ *   BH_WORD_CH     (a & b) ^ (~a & c)     BH_WORD_MAJ  (a & b) ^ (a & c) ^ (b & c), words a, b, c
+ *   BH_WORD_ADD    the FULL sum, up to 36 bits, of the low halves of words pool[a .. a + b), 2 <= b <= 10
+ *   BH_WORD_PACK   bit i of the result = bit source bits[a + i], i < 32
+ * A bit source is bit `bit_neg & 0xff` (below 64) of `word`, negated when bit 8 of bit_neg is set.  Every variable but ONE
+ * (indices as bh_csr.var) has exactly one record: a bit variable (the field element 0 or 1 of its source) or a packed
+ * variable (the sum of bit source bits[bits_begin + i] * 2^i over i < n_bits <= 254).
+ * bh_word_witness_create validates the program (host code, csrc/word_program.hpp) and copies it to the device.  A refused
+ * program gives BH_ERR_INVALID_ARG with bad_index[0] = the reason and bad_index[1] = what that reason counts (bad_index may
+ * be NULL):
+ *   BH_WORD_BAD_SOURCE        instruction: a source is not strictly earlier than its destination
+ *   BH_WORD_BAD_BIT           instruction, a PACK: a bit index of 64 or more
+ *   BH_WORD_BAD_ADD_ARITY     instruction, an ADD: fewer than 2 or more than 10 sources
+ *   BH_WORD_BAD_OP            instruction: unknown operation, amount outside 1 .. 31, a range that leaves its pool
+ *   BH_WORD_BAD_VAR_SOURCE    variable: its record names a word or a bit that does not exist
+ *   BH_WORD_BAD_PACKED_BITS   variable: packed from more than 254 bits
+ *   BH_WORD_BAD_VAR_RANGE     record, bit records counted first and packed records behind them: variable index out of range
+ *   BH_WORD_BAD_UNCOVERED     variable: no record - the lowest such variable
+ *   BH_WORD_BAD_COVERED_TWICE variable: two records, or a record for ONE
+ * bh_word_witness_generate_dev writes witness j to inputs_dev + j * in_stride and aux_dev + j * aux_stride (the layout and
+ * stride rules of bh_r1cs_solve_many_dev) from the n_ext uint32 at ext_dev + j * ext_stride (bytes, a multiple of 4): every
+ * variable, ONE included, whatever the buffers held, and no byte between a vector's end and its stride.  The buffers are
+ * what bh_r1cs_check_many_dev and bh_groth16_prove_witness_batch_dev read.  Asynchronous on `stream`; k = 0 is BH_OK.  A
+ * handle owns the scratch its calls share (witnesses go through in chunks of bounded scratch): calls on one handle are
+ * ordered one behind the other, on whatever streams they run.
+ * bh_word_witness_generate: the same from and to the host, witness j at j * n_ext * 4, j * n_inputs * 32 and j * n_aux * 32,
+ * in groups that stay within 1 GiB of device memory.  Synchronous, on a stream of its own. */
+#define BH_WORD_CONST 1
+#define BH_WORD_ROTR 2
+#define BH_WORD_SHR 3
+#define BH_WORD_XOR 4
+#define BH_WORD_AND 5
+#define BH_WORD_CH 6
+#define BH_WORD_MAJ 7
+#define BH_WORD_ADD 8
+#define BH_WORD_PACK 9
+#define BH_WORD_BAD_SOURCE 1
+#define BH_WORD_BAD_BIT 2
+#define BH_WORD_BAD_ADD_ARITY 3
+#define BH_WORD_BAD_OP 4
+#define BH_WORD_BAD_VAR_SOURCE 5
+#define BH_WORD_BAD_PACKED_BITS 6
+#define BH_WORD_BAD_VAR_RANGE 7
+#define BH_WORD_BAD_UNCOVERED 8
+#define BH_WORD_BAD_COVERED_TWICE 9
+typedef struct bh_word_witness bh_word_witness;
+typedef struct {
+  uint32_t op; /* BH_WORD_* */
+  uint32_t a;
+  uint32_t b;
+  uint32_t c;
+} bh_word_instr;
+typedef struct {
+  uint32_t word;
+  uint32_t bit_neg; /* bit | neg << 8 */
+} bh_word_bit;
+typedef struct {
+  uint32_t var;
+  uint32_t word;
+  uint32_t bit_neg;
+} bh_word_var;
+typedef struct {
+  uint32_t var;
+  uint32_t bits_begin;
+  uint32_t n_bits;
+} bh_word_packed;
+typedef struct {
+  size_t n_inputs; /* ONE included */
+  size_t n_aux;
+  size_t n_ext;
+  const bh_word_instr *instrs;
+  size_t n_instrs;
+  const uint32_t *pool;
+  size_t n_pool;
+  const bh_word_bit *bits;
+  size_t n_bits;
+  const bh_word_var *vars;
+  size_t n_vars;
+  const bh_word_packed *packed;
+  size_t n_packed;
+} bh_word_witness_desc;
+int bh_word_witness_create(bh_ctx *ctx, const bh_word_witness_desc *desc, bh_word_witness **out, uint32_t bad_index[2]);
+int bh_word_witness_generate_dev(bh_ctx *ctx, const bh_word_witness *w, const void *ext_dev, size_t ext_stride, void *inputs_dev,
+                                 size_t in_stride, void *aux_dev, size_t aux_stride, size_t k, void *stream);
+int bh_word_witness_generate(bh_ctx *ctx, const bh_word_witness *w, const void *ext_host, void *inputs_host, void *aux_host,
+                             size_t k);
+void bh_word_witness_destroy(bh_word_witness *w);
 /* Parameter generation (groth16/src/generator.rs:247-462) - device building blocks:
  *   bh_fr_powers_dev             out[i] = scale * g^i           (:249-263 powers of tau; :266-296 with t(tau)/delta folded in)
  *   bh_r1cs_eval_transposed_dev  at/bt/ct[v] = QAP polynomial of variable v at tau (:369-387) from the

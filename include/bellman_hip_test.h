@@ -509,6 +509,15 @@ int bh_test_proof_finish_host(bh_params *params, const void *sums, const void *r
  * needs no bh_params, which only exist with a device context */
 int bh_test_proof_finish_host_vk(const void *vk5, const void *sums, const void *r, const void *s, size_t k, void *proofs_out,
                                  int32_t *rcs);
+/* host only, no context: the word-program validator and interpreter (csrc/word_program.hpp) on a descriptor as
+ * bh_word_witness_create takes it.  Returns BH_OK, or BH_ERR_INVALID_ARG with bad_index as bh_word_witness_create reports it.
+ * With BH_OK and ext (n_ext uint32) not NULL, one witness is interpreted on the host: inputs_out [n_inputs] and aux_out
+ * [n_aux] Montgomery Fr, words_out (may be NULL) the n_ext + n_instrs trace words. */
+int bh_test_word_program(const bh_word_witness_desc *desc, uint32_t bad_index[2], const uint32_t *ext, void *inputs_out,
+                         void *aux_out, uint64_t *words_out);
+/* witnesses per scratch chunk of bh_word_witness_generate_dev for the calls that follow on this handle (0: the shipped
+ * bound, csrc/r1cs_dev.hpp WORD_SCRATCH_MAX_BYTES).  Not thread-safe: between calls only. */
+int bh_test_word_witness_chunk(bh_word_witness *w, size_t witnesses_per_chunk);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,11 @@ pub struct BhMsmManyJob {
 pub struct BhR1csSolver {
     _private: [u8; 0],
 }
+/// opaque `bh_word_witness`
+#[repr(C)]
+pub struct BhWordWitness {
+    _private: [u8; 0],
+}
 /// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -148,6 +153,56 @@ pub struct BhSolverDesc {
     pub hint_coeffs: *const c_void,
     pub n_hint_coeffs: usize,
 }
+/// `bh_word_instr`: one instruction of a word program (op = BH_WORD_*)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhWordInstr {
+    pub op: u32,
+    pub a: u32,
+    pub b: u32,
+    pub c: u32,
+}
+/// `bh_word_bit`: a bit source (bit | neg << 8 of a trace word)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhWordBit {
+    pub word: u32,
+    pub bit_neg: u32,
+}
+/// `bh_word_var`: the record of a bit variable
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhWordVar {
+    pub var: u32,
+    pub word: u32,
+    pub bit_neg: u32,
+}
+/// `bh_word_packed`: the record of a packed variable (a range of bit sources)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhWordPacked {
+    pub var: u32,
+    pub bits_begin: u32,
+    pub n_bits: u32,
+}
+/// `bh_word_witness_desc`: what bh_word_witness_create takes: the program and the variable records
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BhWordWitnessDesc {
+    pub n_inputs: usize,
+    pub n_aux: usize,
+    pub n_ext: usize,
+    pub instrs: *const BhWordInstr,
+    pub n_instrs: usize,
+    pub pool: *const u32,
+    pub n_pool: usize,
+    pub bits: *const BhWordBit,
+    pub n_bits: usize,
+    pub vars: *const BhWordVar,
+    pub n_vars: usize,
+    pub packed: *const BhWordPacked,
+    pub n_packed: usize,
+}
 
 pub const BH_OK: c_int = 0;
 pub const BH_ERR_UNEXPECTED_IDENTITY: c_int = 1;
@@ -174,6 +229,24 @@ pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;
 pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;
 pub const BH_HINT_BITS: u32 = 1;
 pub const BH_HINT_INV_OR_ZERO: u32 = 2;
+pub const BH_WORD_CONST: u32 = 1;
+pub const BH_WORD_ROTR: u32 = 2;
+pub const BH_WORD_SHR: u32 = 3;
+pub const BH_WORD_XOR: u32 = 4;
+pub const BH_WORD_AND: u32 = 5;
+pub const BH_WORD_CH: u32 = 6;
+pub const BH_WORD_MAJ: u32 = 7;
+pub const BH_WORD_ADD: u32 = 8;
+pub const BH_WORD_PACK: u32 = 9;
+pub const BH_WORD_BAD_SOURCE: u32 = 1;
+pub const BH_WORD_BAD_BIT: u32 = 2;
+pub const BH_WORD_BAD_ADD_ARITY: u32 = 3;
+pub const BH_WORD_BAD_OP: u32 = 4;
+pub const BH_WORD_BAD_VAR_SOURCE: u32 = 5;
+pub const BH_WORD_BAD_PACKED_BITS: u32 = 6;
+pub const BH_WORD_BAD_VAR_RANGE: u32 = 7;
+pub const BH_WORD_BAD_UNCOVERED: u32 = 8;
+pub const BH_WORD_BAD_COVERED_TWICE: u32 = 9;
 pub const BH_PTAU_FAILED_HEAD: u32 = 0x01;
 pub const BH_PTAU_FAILED_TAU_G1_G2: u32 = 0x02;
 pub const BH_PTAU_FAILED_TAU_G1: u32 = 0x04;
@@ -319,6 +392,10 @@ extern "C" {
     pub fn bh_r1cs_solver_info(s: *const BhR1csSolver, counts: *mut usize) -> c_int;
     pub fn bh_r1cs_solve_many_dev(ctx: *mut BhCtx, s: *const BhR1csSolver, inputs_dev: *mut c_void, in_stride: usize, aux_dev: *mut c_void, aux_stride: usize, k: usize, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_solve_many(ctx: *mut BhCtx, s: *const BhR1csSolver, inputs_host: *mut c_void, aux_host: *mut c_void, k: usize) -> c_int;
+    pub fn bh_word_witness_create(ctx: *mut BhCtx, desc: *const BhWordWitnessDesc, out: *mut *mut BhWordWitness, bad_index: *mut u32) -> c_int;
+    pub fn bh_word_witness_generate_dev(ctx: *mut BhCtx, w: *const BhWordWitness, ext_dev: *const c_void, ext_stride: usize, inputs_dev: *mut c_void, in_stride: usize, aux_dev: *mut c_void, aux_stride: usize, k: usize, stream: *mut c_void) -> c_int;
+    pub fn bh_word_witness_generate(ctx: *mut BhCtx, w: *const BhWordWitness, ext_host: *const c_void, inputs_host: *mut c_void, aux_host: *mut c_void, k: usize) -> c_int;
+    pub fn bh_word_witness_destroy(w: *mut BhWordWitness);
     pub fn bh_fr_powers_dev(ctx: *mut BhCtx, out_dev: *mut c_void, n: usize, g_host: *const c_void, scale_host: *const c_void, stream: *mut c_void) -> c_int;
     pub fn bh_r1cs_eval_transposed_dev(ctx: *mut BhCtx, r: *mut BhR1cs, lagrange_dev: *const c_void, at_dev: *mut c_void, bt_dev: *mut c_void, ct_dev: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bh_fr_qap_ext_dev(ctx: *mut BhCtx, e_dev: *mut c_void, at_dev: *const c_void, bt_dev: *const c_void, ct_dev: *const c_void, n_inputs: usize, n_vars: usize, alpha: *const c_void, beta: *const c_void, gamma_inv: *const c_void, delta_inv: *const c_void, stream: *mut c_void) -> c_int;

@@ -13,10 +13,13 @@ OUT = os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")
 
 OPAQUE = {"bh_ctx": "BhCtx", "bh_bases": "BhBases", "bh_msm_job": "BhMsmJob", "bh_params": "BhParams", "bh_r1cs": "BhR1cs",
           "bh_scalars": "BhScalars", "bh_msm_sharded_job": "BhMsmShardedJob", "bh_proof_job": "BhProofJob",
-          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet", "bh_msm_many_job": "BhMsmManyJob", "bh_r1cs_solver": "BhR1csSolver"}
+          "bh_pvk": "BhPvk", "bh_pvk_set": "BhPvkSet", "bh_msm_many_job": "BhMsmManyJob", "bh_r1cs_solver": "BhR1csSolver",
+          "bh_word_witness": "BhWordWitness"}
 STRUCTS = {"bh_csr": "BhCsr", "bh_msm_opts": "BhMsmOpts", "bh_ctx_info_t": "BhCtxInfo",
            "bh_powers_of_tau": "BhPowersOfTau", "bh_ptau_report": "BhPtauReport",
-           "bh_params_step_report": "BhParamsStepReport", "bh_witness_hint": "BhWitnessHint", "bh_solver_desc": "BhSolverDesc"}
+           "bh_params_step_report": "BhParamsStepReport", "bh_witness_hint": "BhWitnessHint", "bh_solver_desc": "BhSolverDesc",
+           "bh_word_instr": "BhWordInstr", "bh_word_bit": "BhWordBit", "bh_word_var": "BhWordVar", "bh_word_packed": "BhWordPacked",
+           "bh_word_witness_desc": "BhWordWitnessDesc"}
 SCALAR = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "uint32_t": "u32", "uint64_t": "u64",
     "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char", "void": "c_void",
@@ -127,6 +130,24 @@ def render(decls):
         "pub struct BhSolverDesc {", "    pub supplied: *const u32,", "    pub n_supplied: usize,", "    pub hints: *const BhWitnessHint,",
         "    pub n_hints: usize,", "    pub lc_var: *const u32,", "    pub lc_coeff: *const u32,", "    pub out_var: *const u32,",
         "    pub hint_coeffs: *const c_void,", "    pub n_hint_coeffs: usize,", "}",
+        "/// `bh_word_instr`: one instruction of a word program (op = BH_WORD_*)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhWordInstr {", "    pub op: u32,", "    pub a: u32,", "    pub b: u32,", "    pub c: u32,", "}",
+        "/// `bh_word_bit`: a bit source (bit | neg << 8 of a trace word)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhWordBit {", "    pub word: u32,", "    pub bit_neg: u32,", "}",
+        "/// `bh_word_var`: the record of a bit variable",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhWordVar {", "    pub var: u32,", "    pub word: u32,", "    pub bit_neg: u32,", "}",
+        "/// `bh_word_packed`: the record of a packed variable (a range of bit sources)",
+        "#[repr(C)]", "#[derive(Clone, Copy, Default, Debug)]",
+        "pub struct BhWordPacked {", "    pub var: u32,", "    pub bits_begin: u32,", "    pub n_bits: u32,", "}",
+        "/// `bh_word_witness_desc`: what bh_word_witness_create takes: the program and the variable records",
+        "#[repr(C)]", "#[derive(Clone, Copy)]",
+        "pub struct BhWordWitnessDesc {", "    pub n_inputs: usize,", "    pub n_aux: usize,", "    pub n_ext: usize,",
+        "    pub instrs: *const BhWordInstr,", "    pub n_instrs: usize,", "    pub pool: *const u32,", "    pub n_pool: usize,",
+        "    pub bits: *const BhWordBit,", "    pub n_bits: usize,", "    pub vars: *const BhWordVar,", "    pub n_vars: usize,",
+        "    pub packed: *const BhWordPacked,", "    pub n_packed: usize,", "}",
         "",
     ]
     consts = [("BH_OK", 0), ("BH_ERR_UNEXPECTED_IDENTITY", 1), ("BH_ERR_UNEXPECTED_EOF", 2), ("BH_ERR_DEGREE_TOO_LARGE", 3),
@@ -139,6 +160,10 @@ def render(decls):
     lines += ["pub const BH_POINTS_CHECKED: c_uint = 1;", "pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;",
               "pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;", "pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;",
               "pub const BH_HINT_BITS: u32 = 1;", "pub const BH_HINT_INV_OR_ZERO: u32 = 2;"]
+    lines += ["pub const BH_WORD_%s: u32 = %d;" % (k, i + 1) for i, k in enumerate(
+        ("CONST", "ROTR", "SHR", "XOR", "AND", "CH", "MAJ", "ADD", "PACK"))]
+    lines += ["pub const BH_WORD_BAD_%s: u32 = %d;" % (k, i + 1) for i, k in enumerate(
+        ("SOURCE", "BIT", "ADD_ARITY", "OP", "VAR_SOURCE", "PACKED_BITS", "VAR_RANGE", "UNCOVERED", "COVERED_TWICE"))]
     lines += ["pub const %s: u32 = 0x%02x;" % (k, v) for k, v in
               (("BH_PTAU_FAILED_HEAD", 1), ("BH_PTAU_FAILED_TAU_G1_G2", 2), ("BH_PTAU_FAILED_TAU_G1", 4), ("BH_PTAU_FAILED_TAU_G2", 8),
                ("BH_PTAU_FAILED_ALPHA", 16), ("BH_PTAU_FAILED_BETA", 32), ("BH_PTAU_FAILED_BETA_G2", 64), ("BH_PTAU_FAILED_POINTS", 128))]
