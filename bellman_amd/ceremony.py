@@ -13,24 +13,18 @@ import secrets
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import C
 from .errors import InvalidData, InvalidTranscript, check
 
 _Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
-VALIDATE_POINTS = 1
-FAILED_HEAD, FAILED_TAU_G1_G2, FAILED_TAU_G1, FAILED_TAU_G2 = 0x01, 0x02, 0x04, 0x08
-FAILED_ALPHA, FAILED_BETA, FAILED_BETA_G2, FAILED_POINTS = 0x10, 0x20, 0x40, 0x80
-
-
-class PtauReport(ctypes.Structure):
-    """bh_ptau_report: `failed` = the FAILED_* bits; with FAILED_POINTS `bad_vector` (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1,
-    3 beta_tau_g1) and `bad_index` name the first bad point"""
-    _fields_ = [("failed", ctypes.c_uint32), ("bad_vector", ctypes.c_uint32), ("bad_index", ctypes.c_size_t)]
-
-
-class _PowersOfTau(ctypes.Structure):
-    _fields_ = [("tau_g1", ctypes.c_void_p), ("tau_g2", ctypes.c_void_p), ("alpha_tau_g1", ctypes.c_void_p),
-                ("beta_tau_g1", ctypes.c_void_p), ("beta_g2", ctypes.c_void_p)]
+VALIDATE_POINTS = C.BH_PTAU_VALIDATE_POINTS
+FAILED_HEAD, FAILED_TAU_G1_G2, FAILED_TAU_G1, FAILED_TAU_G2, FAILED_ALPHA, FAILED_BETA, FAILED_BETA_G2, FAILED_POINTS = (
+    getattr(C, "BH_PTAU_FAILED_" + x) for x in ("HEAD", "TAU_G1_G2", "TAU_G1", "TAU_G2", "ALPHA", "BETA", "BETA_G2", "POINTS"))
+# bh_ptau_report: `failed` = the FAILED_* bits; with FAILED_POINTS `bad_vector` (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1,
+# 3 beta_tau_g1) and `bad_index` name the first bad point
+PtauReport = _abi.STRUCTS["bh_ptau_report"]
+_PowersOfTau = _abi.STRUCTS["bh_powers_of_tau"]
 
 
 def verify_powers_of_tau(worker, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, seed=None, validate_points=True):
@@ -48,7 +42,7 @@ def verify_powers_of_tau(worker, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta
     rep = PtauReport()
     rc = _lib.load().bh_powers_of_tau_verify(worker.ctx, ctypes.byref(t), seed, VALIDATE_POINTS if validate_points else 0,
                                              ctypes.byref(rep))
-    if rc == 10:
+    if rc == C.BH_ERR_INVALID_TRANSCRIPT:
         raise InvalidTranscript(rep)
     try:
         check(rc, "verify_powers_of_tau")

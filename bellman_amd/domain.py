@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._abi import C
 from .errors import PolynomialDegreeTooLarge, check
 
 FR_S = 32  # 2-adicity of BLS12-381 Fr (ff::PrimeField::S)
@@ -59,16 +60,16 @@ class EvaluationDomain:
         self.worker.synchronize()
 
     def fft(self, worker=None):
-        self._fft(0)
+        self._fft(C.BH_FFT)
 
     def ifft(self, worker=None):
-        self._fft(1)
+        self._fft(C.BH_IFFT)
 
     def coset_fft(self, worker=None):
-        self._fft(2)
+        self._fft(C.BH_COSET_FFT)
 
     def icoset_fft(self, worker=None):
-        self._fft(3)
+        self._fft(C.BH_ICOSET_FFT)
 
     def distribute_powers(self, worker, g_mont):
         g = np.ascontiguousarray(g_mont, dtype=np.uint64).reshape(4)
@@ -91,7 +92,7 @@ class EvaluationDomain:
         self.worker.synchronize()
 
 
-MANY_FORCE, MANY_SINGLE = 1, 2   # BH_FFT_MANY_FORCE / BH_FFT_MANY_SINGLE (include/bellman_hip.h)
+MANY_FORCE, MANY_SINGLE = C.BH_FFT_MANY_FORCE, C.BH_FFT_MANY_SINGLE
 
 
 def _pad_all(list_of_coeffs):
@@ -152,16 +153,16 @@ class EvaluationDomains:
         self.worker.synchronize()
 
     def fft(self, worker=None, flags=0):
-        self._fft(0, flags)
+        self._fft(C.BH_FFT, flags)
 
     def ifft(self, worker=None, flags=0):
-        self._fft(1, flags)
+        self._fft(C.BH_IFFT, flags)
 
     def coset_fft(self, worker=None, flags=0):
-        self._fft(2, flags)
+        self._fft(C.BH_COSET_FFT, flags)
 
     def icoset_fft(self, worker=None, flags=0):
-        self._fft(3, flags)
+        self._fft(C.BH_ICOSET_FFT, flags)
 
     def divide_by_z_on_coset(self, worker=None):
         """every member by Z(7) (domain.rs:139-151).  The existing call takes a domain size, so it runs once per member."""
@@ -261,16 +262,16 @@ class PointEvaluationDomain:
         check(self._lib.bh_fft_point_dev(self.worker.ctx, self.group, self._dev, self.exp, mode, None), "point fft")
 
     def fft(self, worker=None):
-        self._fft(0)
+        self._fft(C.BH_FFT)
 
     def ifft(self, worker=None):
-        self._fft(1)
+        self._fft(C.BH_IFFT)
 
     def coset_fft(self, worker=None):
-        self._fft(2)
+        self._fft(C.BH_COSET_FFT)
 
     def icoset_fft(self, worker=None):
-        self._fft(3)
+        self._fft(C.BH_ICOSET_FFT)
 
     def distribute_powers(self, worker, g_mont):
         g = np.ascontiguousarray(g_mont, dtype=np.uint64).reshape(4)

@@ -1,5 +1,7 @@
 """SynthesisError mirror (reference: src/lib.rs:303-319) + C-ABI return-code mapping."""
 
+from ._abi import C
+
 
 class SynthesisError(Exception):
     pass
@@ -60,28 +62,28 @@ class BellmanHipError(RuntimeError):
 
 
 def check(rc, what="bellman_hip call"):
-    if rc == 0:
+    if rc == C.BH_OK:
         return
-    if rc == 1:
+    if rc == C.BH_ERR_UNEXPECTED_IDENTITY:
         raise UnexpectedIdentity()
-    if rc == 2:
+    if rc == C.BH_ERR_UNEXPECTED_EOF:
         raise UnexpectedEof("expected more bases from source")
-    if rc == 3:
+    if rc == C.BH_ERR_DEGREE_TOO_LARGE:
         raise PolynomialDegreeTooLarge()
-    if rc == 5:
+    if rc == C.BH_ERR_UNCONSTRAINED_VARIABLE:
         raise UnconstrainedVariable()
-    if rc == 6:
+    if rc == C.BH_ERR_INVALID_POINT:
         raise InvalidPoint("invalid G1/G2")
-    if rc == 7:
+    if rc == C.BH_ERR_POINT_AT_INFINITY:
         raise PointAtInfinity("point at infinity")
-    if rc == 10:
+    if rc == C.BH_ERR_INVALID_TRANSCRIPT:
         raise InvalidTranscript()
-    if rc == 11:
+    if rc == C.BH_ERR_UNSATISFIABLE:
         raise Unsatisfiable()
-    if rc == -2:
+    if rc == C.BH_ERR_INVALID_ARG:
         # the reference panics here (assert!), e.g. src/multiexp.rs:324-329, src/domain.rs:155,174
         raise AssertionError("%s: invalid argument (the reference panics)" % what)
-    if rc == -3:
+    if rc == C.BH_ERR_NO_DEVICE:
         raise BellmanHipError("%s: no gfx950 device available (no CPU fallback)" % what)
     raise BellmanHipError("%s failed with code %d" % (what, rc))
 
@@ -100,8 +102,8 @@ class InvalidProof(VerificationError):
 
 def check_verification(rc, what="verification"):
     """the return code of bh_groth16_verify / bh_groth16_batch_verify"""
-    if rc == 8:
+    if rc == C.BH_ERR_INVALID_VERIFYING_KEY:
         raise InvalidVerifyingKey()
-    if rc == 9:
+    if rc == C.BH_ERR_INVALID_PROOF:
         raise InvalidProof()
     check(rc, what)

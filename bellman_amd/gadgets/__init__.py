@@ -12,7 +12,8 @@ import ctypes
 
 import numpy as np
 
-from .. import _lib
+from .. import _abi, _lib
+from .._abi import C
 from ..errors import check
 from ..groth16 import INPUT, BitsHint, DeviceWitnesses, R1CS, ShapeAssembly, Variable, WitnessAssignment
 from .boolean import AllocatedBit, Boolean
@@ -27,7 +28,9 @@ __all__ = ["AllocatedBit", "Boolean", "UInt32", "MultiEq", "CAPACITY", "pack_int
            "Recorder", "RecordingShape", "Shape", "WordWitness", "WordProgramError", "capture", "synthesize"]
 
 # BH_WORD_BAD_*: why bh_word_witness_create refused a program, and what the index it reports counts
-BAD_SOURCE, BAD_BIT, BAD_ADD_ARITY, BAD_OP, BAD_VAR_SOURCE, BAD_PACKED_BITS, BAD_VAR_RANGE, BAD_UNCOVERED, BAD_COVERED_TWICE = range(1, 10)
+BAD_SOURCE, BAD_BIT, BAD_ADD_ARITY, BAD_OP, BAD_VAR_SOURCE, BAD_PACKED_BITS, BAD_VAR_RANGE, BAD_UNCOVERED, BAD_COVERED_TWICE = (
+    getattr(C, "BH_WORD_BAD_" + x) for x in ("SOURCE", "BIT", "ADD_ARITY", "OP", "VAR_SOURCE", "PACKED_BITS", "VAR_RANGE", "UNCOVERED",
+                                             "COVERED_TWICE"))
 _BAD_TEXT = {
     BAD_SOURCE: "instruction %d reads a word that is not strictly earlier than its own",
     BAD_BIT: "instruction %d (a PACK) reads a bit index of 64 or more",
@@ -49,12 +52,7 @@ class WordProgramError(ValueError):
         self.code, self.index = code, index
 
 
-class _Desc(ctypes.Structure):
-    """bh_word_witness_desc"""
-    _fields_ = [("n_inputs", ctypes.c_size_t), ("n_aux", ctypes.c_size_t), ("n_ext", ctypes.c_size_t),
-                ("instrs", ctypes.c_void_p), ("n_instrs", ctypes.c_size_t), ("pool", ctypes.c_void_p), ("n_pool", ctypes.c_size_t),
-                ("bits", ctypes.c_void_p), ("n_bits", ctypes.c_size_t), ("vars", ctypes.c_void_p), ("n_vars", ctypes.c_size_t),
-                ("packed", ctypes.c_void_p), ("n_packed", ctypes.c_size_t)]
+_Desc = _abi.STRUCTS["bh_word_witness_desc"]
 
 
 def make_desc(num_inputs, num_aux, program):
@@ -79,7 +77,7 @@ def check_program(num_inputs, num_aux, program):
     bad = (ctypes.c_uint32 * 2)()
     rc = _load().bh_test_word_program(ctypes.byref(desc), bad, None, None, None, None)
     del keep
-    if rc == -2 and bad[0]:
+    if rc == C.BH_ERR_INVALID_ARG and bad[0]:
         raise WordProgramError(int(bad[0]), int(bad[1]))
     check(rc, "word program")
 
@@ -96,7 +94,7 @@ def interpret(num_inputs, num_aux, program, ext_row):
     p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
     rc = _load().bh_test_word_program(ctypes.byref(desc), bad, p(ext), p(ins), p(aux), p(words))
     del keep
-    if rc == -2 and bad[0]:
+    if rc == C.BH_ERR_INVALID_ARG and bad[0]:
         raise WordProgramError(int(bad[0]), int(bad[1]))
     check(rc, "word program")
     return ins, aux, words
@@ -114,7 +112,7 @@ class WordWitness:
         rc = lib.bh_word_witness_create(worker.ctx, ctypes.byref(desc), ctypes.byref(h), bad)
         del keep
         self._h = None
-        if rc == -2 and bad[0]:
+        if rc == C.BH_ERR_INVALID_ARG and bad[0]:
             raise WordProgramError(int(bad[0]), int(bad[1]))
         check(rc, "WordWitness")
         self._h = h

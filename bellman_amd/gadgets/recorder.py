@@ -7,9 +7,11 @@ the arrays of bh_word_witness_desc (include/bellman_hip.h)."""
 
 import numpy as np
 
+from .._abi import C
 from ..groth16 import INPUT
 
-CONST, ROTR, SHR, XOR, AND, CH, MAJ, ADD, PACK = range(1, 10)   # BH_WORD_*
+CONST, ROTR, SHR, XOR, AND, CH, MAJ, ADD, PACK = (getattr(C, "BH_WORD_" + x) for x in (
+    "CONST", "ROTR", "SHR", "XOR", "AND", "CH", "MAJ", "ADD", "PACK"))
 MAX_PACKED_BITS = 254                                            # Scalar::CAPACITY
 
 

@@ -10,7 +10,8 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import C
 from .errors import UnexpectedEof, Unsatisfiable, check
 
 _check_rc = check  # prove_witness_batch has a keyword argument named `check`
@@ -19,15 +20,13 @@ Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _R = (1 << 256) % Q
 _MASK = (1 << 64) - 1
 INPUT, AUX = 0, 1
-STEP_VALIDATE_POINTS = 1
-STEP_FAILED_SHAPE, STEP_FAILED_HEAD, STEP_FAILED_KEY, STEP_FAILED_A, STEP_FAILED_B_G1 = 0x001, 0x002, 0x004, 0x008, 0x010
-STEP_FAILED_B_G2, STEP_FAILED_DELTA, STEP_FAILED_H, STEP_FAILED_L, STEP_FAILED_POINTS = 0x020, 0x040, 0x080, 0x100, 0x200
-
-
-class ParamsStepReport(ctypes.Structure):
-    """bh_params_step_report: `failed` = the STEP_FAILED_* bits; `bad_vector` (0 key, 1 a, 2 b_g1, 3 b_g2; with
-    STEP_FAILED_POINTS 4 h, 5 l, 6 delta_g1, 7 delta_g2) and `bad_index` name the first finding that has a position"""
-    _fields_ = [("failed", ctypes.c_uint32), ("bad_vector", ctypes.c_uint32), ("bad_index", ctypes.c_size_t)]
+STEP_VALIDATE_POINTS = C.BH_STEP_VALIDATE_POINTS
+(STEP_FAILED_SHAPE, STEP_FAILED_HEAD, STEP_FAILED_KEY, STEP_FAILED_A, STEP_FAILED_B_G1, STEP_FAILED_B_G2, STEP_FAILED_DELTA, STEP_FAILED_H,
+ STEP_FAILED_L, STEP_FAILED_POINTS) = (getattr(C, "BH_STEP_FAILED_" + x) for x in (
+     "SHAPE", "HEAD", "KEY", "A", "B_G1", "B_G2", "DELTA", "H", "L", "POINTS"))
+# bh_params_step_report: `failed` = the STEP_FAILED_* bits; `bad_vector` (0 key, 1 a, 2 b_g1, 3 b_g2; with
+# STEP_FAILED_POINTS 4 h, 5 l, 6 delta_g1, 7 delta_g2) and `bad_index` name the first finding that has a position
+ParamsStepReport = _abi.STRUCTS["bh_params_step_report"]
 
 
 def fr_to_mont_array(vals):
@@ -193,7 +192,7 @@ def read_proofs(worker, data, return_status=False):
     p = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
     rc = _lib.load().bh_proofs_read(worker.ctx, p(buf) if n else None, n, p(out) if n else None, p(status), ctypes.byref(bad))
     if return_status:
-        if rc not in (0, 6, 7):
+        if rc not in (C.BH_OK, C.BH_ERR_INVALID_POINT, C.BH_ERR_POINT_AT_INFINITY):
             check(rc, "proofs_read")
         return [Proof(out[i]) if status[i] == 0 else None for i in range(n)], status
     try:
@@ -304,7 +303,7 @@ class Parameters:
         rep = ParamsStepReport()
         rc = _lib.load().bh_groth16_params_verify_step(self.worker.ctx, self._h, after._h, seed,
                                                        STEP_VALIDATE_POINTS if validate_points else 0, ctypes.byref(rep))
-        if rc == 10:
+        if rc == C.BH_ERR_INVALID_TRANSCRIPT:
             raise InvalidTranscript(rep, "not a rescaling of delta alone")
         try:
             check(rc, "Parameters.verify_step")
@@ -502,16 +501,9 @@ class ShapeAssembly(ConstraintSystem):
         return out, table
 
 
-class _PowersOfTau(ctypes.Structure):
-    _fields_ = [("tau_g1", ctypes.c_void_p), ("tau_g2", ctypes.c_void_p), ("alpha_tau_g1", ctypes.c_void_p),
-                ("beta_tau_g1", ctypes.c_void_p), ("beta_g2", ctypes.c_void_p)]
-
-
-class _Csr(ctypes.Structure):
-    _fields_ = [("row_ptr", ctypes.c_void_p), ("var", ctypes.c_void_p), ("coeff", ctypes.c_void_p)]
-
-
-SATISFIED = 0xFFFFFFFF  # BH_R1CS_SATISFIED
+_PowersOfTau = _abi.STRUCTS["bh_powers_of_tau"]
+_Csr = _abi.STRUCTS["bh_csr"]
+SATISFIED = C.BH_R1CS_SATISFIED
 
 
 def _stacked(vectors, n, k, what):
@@ -519,16 +511,16 @@ def _stacked(vectors, n, k, what):
     entry points).  A [k, n, 4] uint64 array is taken as it is; a vector of the wrong length is refused."""
     if isinstance(vectors, np.ndarray) and vectors.dtype == np.uint64 and vectors.ndim == 3 and vectors.shape[2] == 4:
         if vectors.shape[1] != n:
-            check(-2, "%s (the witnesses do not have the shape of the captured circuit)" % what)
+            check(C.BH_ERR_INVALID_ARG, "%s (the witnesses do not have the shape of the captured circuit)" % what)
         return np.ascontiguousarray(vectors)
     arrs = [fr_to_mont_array(x if isinstance(x, np.ndarray) else list(x)) for x in vectors]
     for j, a in enumerate(arrs):
         if a.shape[0] != n:
-            check(-2, "%s (witness %d does not have the shape of the captured circuit)" % (what, j))
+            check(C.BH_ERR_INVALID_ARG, "%s (witness %d does not have the shape of the captured circuit)" % (what, j))
     return np.ascontiguousarray(np.stack(arrs)) if n and k else np.zeros((k, 0, 4), dtype=np.uint64)
 
 
-HINT_BITS, HINT_INV_OR_ZERO = 1, 2  # BH_HINT_*
+HINT_BITS, HINT_INV_OR_ZERO = C.BH_HINT_BITS, C.BH_HINT_INV_OR_ZERO
 NO_VARIABLE = 0xFFFFFFFF
 
 
@@ -547,14 +539,8 @@ class InverseOrZeroHint:
         self.kind, self.lc, self.outs, self.shift = HINT_INV_OR_ZERO, lc, [out], 0
 
 
-class _WitnessHint(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_uint32) for n in ("kind", "lc_begin", "lc_end", "out_begin", "out_end", "shift")]
-
-
-class _SolverDesc(ctypes.Structure):
-    _fields_ = [("supplied", ctypes.c_void_p), ("n_supplied", ctypes.c_size_t), ("hints", ctypes.c_void_p), ("n_hints", ctypes.c_size_t),
-                ("lc_var", ctypes.c_void_p), ("lc_coeff", ctypes.c_void_p), ("out_var", ctypes.c_void_p),
-                ("hint_coeffs", ctypes.c_void_p), ("n_hint_coeffs", ctypes.c_size_t)]
+_WitnessHint = _abi.STRUCTS["bh_witness_hint"]
+_SolverDesc = _abi.STRUCTS["bh_solver_desc"]
 
 
 def solver_desc(supplied, hints):
@@ -770,7 +756,7 @@ class R1CS:
         bad, h = ctypes.c_uint32(NO_VARIABLE), ctypes.c_void_p()
         rc = lib.bh_r1cs_solver_create(self.worker.ctx, self._h, ctypes.byref(desc), ctypes.byref(bad), ctypes.byref(h))
         del keep
-        if rc == -2 and bad.value != NO_VARIABLE:
+        if rc == C.BH_ERR_INVALID_ARG and bad.value != NO_VARIABLE:
             v = bad.value
             name = "Variable(INPUT, %d)" % v if v < self.num_inputs else "Variable(AUX, %d)" % (v - self.num_inputs)
             raise ValueError("R1CS.solver: %s is not determined by the supplied variables, the hints and the constraints in "
@@ -923,13 +909,13 @@ def prove_witness_batch(r1cs, params, inputs_list, aux_list, rs, ss, timings=Non
         _codes[:] = [int(c) for c in rcs]
         return [Proof(out[j].copy()) if rcs[j] == 0 else None for j in range(k)]
     for j in range(k):
-        if int(rcs[j]) == 11:
+        if int(rcs[j]) == C.BH_ERR_UNSATISFIABLE:
             raise Unsatisfiable(int(first_bad[j]))
         check(int(rcs[j]), "create_proof")
     return [Proof(out[j].copy()) for j in range(k)]
 
 
-PROVE_CHECK, PROVE_FINISH_DEVICE, PROVE_FINISH_HOST = 1, 2, 4   # BH_PROVE_* of include/bellman_hip.h
+PROVE_CHECK, PROVE_FINISH_DEVICE, PROVE_FINISH_HOST = C.BH_PROVE_CHECK, C.BH_PROVE_FINISH_DEVICE, C.BH_PROVE_FINISH_HOST
 
 
 class DeviceWitnesses:
@@ -1038,7 +1024,7 @@ def prove_witness_batch_dev(r1cs, params, dev_witnesses, rs, ss, check=False, so
         _codes[:] = [int(c) for c in rcs[:k]]
         return [Proof(out[j].copy()) if rcs[j] == 0 else None for j in range(k)]
     for j in range(k):
-        if int(rcs[j]) == 11:
+        if int(rcs[j]) == C.BH_ERR_UNSATISFIABLE:
             raise Unsatisfiable(int(first_bad[j]))
         check(int(rcs[j]), "create_proof")
     return [Proof(out[j].copy()) for j in range(k)]
@@ -1069,7 +1055,7 @@ def create_proof_demo_r1cs(params, r1cs, kind, size, seed, witness, constants, r
 
 
 # ---- one proof over several GPUs ------------------------------------------------------
-SUMS_WORDS = 120  # BH_MSM_SUMS_BYTES / 8
+SUMS_WORDS = C.BH_MSM_SUMS_BYTES // 8
 
 
 def prove_witness_part(r1cs, params, input_assignment, aux_assignment, part, parts, timings=None):

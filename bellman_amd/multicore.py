@@ -6,7 +6,7 @@ On the MI355X a Worker is a device context (one per GPU per process): `compute` 
 
 import ctypes
 
-from . import _lib
+from . import _abi, _lib
 from .errors import check
 
 
@@ -40,16 +40,9 @@ class Worker:
 
     def info(self):
         """bh_ctx_info as a dict (device, CUs, HBM, hardware-queue request, jobs in flight, pool and table bytes)."""
-        class _Info(ctypes.Structure):
-            _fields_ = [("device", ctypes.c_int32), ("num_cus", ctypes.c_uint32), ("hbm_bytes", ctypes.c_uint64),
-                        ("hw_queues_requested", ctypes.c_uint32), ("hw_queues_set_before_hip_init", ctypes.c_uint32),
-                        ("max_jobs_in_flight", ctypes.c_uint32), ("jobs_in_flight", ctypes.c_uint32),
-                        ("pool_bytes_held", ctypes.c_uint64), ("pool_bytes_idle", ctypes.c_uint64),
-                        ("table_bytes", ctypes.c_uint64), ("table_budget", ctypes.c_uint64),
-                        ("fft_table_bytes", ctypes.c_uint64), ("fft_table_budget", ctypes.c_uint64)]
-        i = _Info()
+        i = _abi.STRUCTS["bh_ctx_info_t"]()
         check(self._lib.bh_ctx_info(self._ctx, ctypes.byref(i)))
-        return {k: getattr(i, k) for k, _ in _Info._fields_}
+        return {k: getattr(i, k) for k, _ in i._fields_}
 
     # ---- host-side task helpers (multicore.rs:33-91): device work goes through multiexp /
     # EvaluationDomain; these exist for caller code that used the pool for its own host tasks ----

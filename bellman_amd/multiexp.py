@@ -9,12 +9,17 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import C
 from .errors import check
 from .multicore import Waiter
 
-G1, G2 = 1, 2
+G1, G2 = C.BH_G1, C.BH_G2
 _WORDS = {G1: 12, G2: 24}
+
+
+def _scalar_fmt(mont):
+    return C.BH_SCALARS_MONT if mont else C.BH_SCALARS_CANONICAL
 
 
 class FullDensity:
@@ -103,7 +108,7 @@ class Bases:
         self = cls.__new__(cls)
         self.worker, self.group, self.n = worker, group, buf.size // rec
         h, bad = ctypes.c_void_p(), ctypes.c_size_t(0)
-        flags = (1 if checked else 0) | (2 if forbid_identity else 0)
+        flags = (C.BH_POINTS_CHECKED if checked else 0) | (C.BH_POINTS_FORBID_IDENTITY if forbid_identity else 0)
         try:
             check(_lib.load().bh_bases_read_uncompressed(worker.ctx, group, buf.ctypes.data_as(ctypes.c_void_p), self.n, flags,
                                                          ctypes.byref(h), ctypes.byref(bad)), "bases_read_uncompressed")
@@ -125,7 +130,7 @@ class Bases:
         self = cls.__new__(cls)
         self.worker, self.group, self.n = worker, group, buf.size // enc
         h, bad = ctypes.c_void_p(), ctypes.c_size_t(0)
-        flags = (1 if checked else 0) | (2 if forbid_identity else 0)
+        flags = (C.BH_POINTS_CHECKED if checked else 0) | (C.BH_POINTS_FORBID_IDENTITY if forbid_identity else 0)
         try:
             check(_lib.load().bh_bases_read_compressed(worker.ctx, group, buf.ctypes.data_as(ctypes.c_void_p), self.n, flags,
                                                        ctypes.byref(h), ctypes.byref(bad)), "bases_read_compressed")
@@ -172,7 +177,7 @@ class Bases:
         count = self.n - first if count is None else count
         st = np.zeros(count, dtype=np.uint32) if return_status else None
         bad = ctypes.c_size_t(0)
-        flags = (1 if checked else 0) | (2 if forbid_identity else 0)
+        flags = (C.BH_POINTS_CHECKED if checked else 0) | (C.BH_POINTS_FORBID_IDENTITY if forbid_identity else 0)
         try:
             check(_lib.load().bh_bases_validate(self.worker.ctx, self._h, first, count, flags,
                                                 st.ctypes.data_as(ctypes.c_void_p) if return_status else None, ctypes.byref(bad)),
@@ -233,13 +238,12 @@ class Bases:
             pass
 
 
-class MsmOpts(ctypes.Structure):
-    """bh_msm_opts: per-job plan overrides (window bits c, chunk K, BH_MSM_* flags); zero = tuned default"""
-    _fields_ = [("window_bits", ctypes.c_uint32), ("chunk", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
-
-
-ACC_REGISTERS, ACC_LDS, NO_TABLE, NO_SMALL_PATH, G2_SINGLE_LANE, G2_LANE_TRIPLES, STAGE_TIMES, HOLD, G2_LANE_PAIRS = 1, 2, 4, 8, 16, 32, 64, 128, 256
-MANY_FORCE = 512   # multiexp_many: take the many-plan wherever it is valid
+# bh_msm_opts: per-job plan overrides (window bits c, chunk K, BH_MSM_* flags); zero = tuned default
+MsmOpts = _abi.STRUCTS["bh_msm_opts"]
+ACC_REGISTERS, ACC_LDS, NO_TABLE, NO_SMALL_PATH, G2_SINGLE_LANE, G2_LANE_TRIPLES, STAGE_TIMES, HOLD, G2_LANE_PAIRS = (
+    getattr(C, "BH_MSM_" + x) for x in ("ACC_REGISTERS", "ACC_LDS", "NO_TABLE", "NO_SMALL_PATH", "G2_SINGLE_LANE", "G2_LANE_TRIPLES",
+                                        "STAGE_TIMES", "HOLD", "G2_LANE_PAIRS"))
+MANY_FORCE = C.BH_MSM_MANY_FORCE   # multiexp_many: take the many-plan wherever it is valid
 
 
 STATS_FIELDS = ("sorted_entries", "zero_digits", "mixed_additions", "chunk_lanes", "window_bits", "chunk", "bucket_sets", "digit_columns")
@@ -262,7 +266,7 @@ def multiexp(pool, bases, density_map, exponents, skip=0, mont=False, timed=Fals
         dlen = density_map.get_query_size()
         words = density_map.words()
     job = ctypes.c_void_p()
-    fmt = 1 if mont else 0
+    fmt = _scalar_fmt(mont)
     opts = MsmOpts(window_bits, chunk, flags | (STAGE_TIMES if timed else 0))
     po = ctypes.cast(ctypes.pointer(opts), ctypes.c_void_p)
     if scalars_dev is None:
@@ -310,7 +314,7 @@ def multiexp_many(pool, bases, density_map, exponents, skip=0, mont=False, windo
         dlen = density_map.get_query_size()
         words = density_map.words()
     job = ctypes.c_void_p()
-    fmt = 1 if mont else 0
+    fmt = _scalar_fmt(mont)
     opts = MsmOpts(window_bits, chunk, flags | (STAGE_TIMES if stats else 0))
     po = ctypes.cast(ctypes.pointer(opts), ctypes.c_void_p)
     sc = None
@@ -338,11 +342,11 @@ def multiexp_many(pool, bases, density_map, exponents, skip=0, mont=False, windo
               "multiexp_many.wait")
         items = []
         for v in range(k):
-            if rcs[v] == 0:
+            if rcs[v] == C.BH_OK:
                 items.append(out[v].copy())
-            elif rcs[v] == 1:
+            elif rcs[v] == C.BH_ERR_UNEXPECTED_IDENTITY:
                 items.append(UnexpectedIdentity())
-            elif rcs[v] == 2:
+            elif rcs[v] == C.BH_ERR_UNEXPECTED_EOF:
                 items.append(UnexpectedEof("expected more bases from source"))
             else:
                 check(int(rcs[v]), "multiexp_many.wait")
@@ -361,7 +365,7 @@ class Scalars:
         sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
         self.worker, self.n = worker, sc.shape[0]
         h = ctypes.c_void_p()
-        check(_lib.load().bh_scalars_register(worker.ctx, sc.ctypes.data_as(ctypes.c_void_p), self.n, 1 if mont else 0,
+        check(_lib.load().bh_scalars_register(worker.ctx, sc.ctypes.data_as(ctypes.c_void_p), self.n, _scalar_fmt(mont),
                                               ctypes.byref(h)), "scalars_register")
         self._h = h
 
@@ -418,7 +422,7 @@ def multiexp_sharded(workers, shards, density_map, exponents, skip=0, mont=False
     ctxs = (ctypes.c_void_p * k)(*[w.ctx for w in workers])
     hs = (ctypes.c_void_p * k)(*[b._h for b in shards])
     job = ctypes.c_void_p()
-    check(lib.bh_msm_sharded_async(ctxs, hs, k, skip, sc.ctypes.data_as(ctypes.c_void_p), sc.shape[0], 1 if mont else 0,
+    check(lib.bh_msm_sharded_async(ctxs, hs, k, skip, sc.ctypes.data_as(ctypes.c_void_p), sc.shape[0], _scalar_fmt(mont),
                                    None if words is None else words.ctypes.data_as(ctypes.c_void_p), dlen, ctypes.byref(job)),
           "multiexp (sharded)")
     w = _WORDS[shards[0].group]
@@ -458,7 +462,7 @@ def point_mul_each(worker, group, points, scalars, mont=False):
         check(lib.bh_dev_alloc(worker.ctx, sc.nbytes, ctypes.byref(d_sc)), "dev_alloc")
         check(lib.bh_dev_upload(worker.ctx, d_pts, pts.ctypes.data_as(ctypes.c_void_p), pts.nbytes), "dev_upload")
         check(lib.bh_dev_upload(worker.ctx, d_sc, sc.ctypes.data_as(ctypes.c_void_p), sc.nbytes), "dev_upload")
-        check(lib.bh_point_mul_each_dev(worker.ctx, group, d_pts, d_sc, n, 1 if mont else 0, d_pts, None), "point_mul_each")
+        check(lib.bh_point_mul_each_dev(worker.ctx, group, d_pts, d_sc, n, _scalar_fmt(mont), d_pts, None), "point_mul_each")
         check(lib.bh_dev_download(worker.ctx, out.ctypes.data_as(ctypes.c_void_p), d_pts, pts.nbytes), "dev_download")
     finally:
         if d_sc:

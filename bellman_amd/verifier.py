@@ -13,11 +13,12 @@ import secrets
 import numpy as np
 
 from . import _lib
+from ._abi import C
 from .errors import (InvalidPoint, InvalidProof, InvalidVerifyingKey, PointAtInfinity, UnexpectedEof, check,
                      check_verification)
 
 Q = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
-_CANONICAL = 0
+_CANONICAL = C.BH_SCALARS_CANONICAL
 
 
 def _fr_bytes(vals):
@@ -88,15 +89,29 @@ def verify_proof(pvk, proof, public_inputs):
 
 def _verdict_error(code):
     """the exception Item.verify_single raises for a verdict code of bh_groth16_verify_each (None for BH_OK)"""
-    if code == 0:
+    if code == C.BH_OK:
         return None
-    if code == 9:
+    if code == C.BH_ERR_INVALID_PROOF:
         return InvalidProof()
-    if code == 6:
+    if code == C.BH_ERR_INVALID_POINT:
         return InvalidPoint("invalid G1/G2")
-    if code == 7:
+    if code == C.BH_ERR_POINT_AT_INFINITY:
         return PointAtInfinity("point at infinity")
     raise AssertionError("unexpected verdict code %d" % code)
+
+
+_READ_VERDICTS = (C.BH_OK, C.BH_ERR_INVALID_POINT, C.BH_ERR_POINT_AT_INFINITY)   # what bh_proofs_read returns per proof
+
+
+def _status_error(word):
+    """the exception a status word of bh_proofs_read stands for (None for a readable proof)"""
+    for e in range(3):   # the first bad element in the order a, b, c
+        byte = (word >> (8 * e)) & 0xFF
+        if byte & C.BH_PROOF_STATUS_INVALID:
+            return InvalidPoint("invalid G1/G2")
+        if byte & C.BH_PROOF_STATUS_IDENTITY:
+            return PointAtInfinity("point at infinity")
+    return None
 
 
 def verify_each(pvk, items):
@@ -133,18 +148,10 @@ def verify_each(pvk, items):
         recs = np.zeros((len(where), 48), dtype=np.uint64)
         status = (ctypes.c_uint32 * len(where))()
         rc = lib.bh_proofs_read(pvk.worker.ctx, raw, len(where), recs.ctypes.data_as(ctypes.c_void_p), status, None)
-        if rc not in (0, 6, 7):
+        if rc not in _READ_VERDICTS:
             check(rc, "Proof.read")
         for k, i in enumerate(where):
-            word = status[k]
-            for e in range(3):   # the first bad element in the order a, b, c
-                byte = (word >> (8 * e)) & 0xFF
-                if byte & 0xEE:
-                    out[i] = InvalidPoint("invalid G1/G2")
-                    break
-                if byte & 0x10:
-                    out[i] = PointAtInfinity("point at infinity")
-                    break
+            out[i] = _status_error(status[k])
             decoded[i] = Proof(recs[k].copy())
     live = [i for i in range(n) if out[i] is None]
     if live:
@@ -316,16 +323,6 @@ def _key_of(items):
     return (ctypes.c_uint32 * max(len(items), 1))(*[it.key_index for it in items])
 
 
-def _status_error(word):
-    for e in range(3):   # the first bad element in the order a, b, c
-        byte = (word >> (8 * e)) & 0xFF
-        if byte & 0xEE:
-            return InvalidPoint("invalid G1/G2")
-        if byte & 0x10:
-            return PointAtInfinity("point at infinity")
-    return None
-
-
 def verify_each_keys(keyset, items):
     """verify_each over proofs of several keys: items are (key_index, proof, inputs); the result holds, item by item, None
     or the exception Item(proof, inputs).verify_single(keyset.pvks[key_index]) would raise.  Byte and Proof items mix as in
@@ -356,7 +353,7 @@ def verify_each_keys(keyset, items):
         recs = np.zeros((len(where), 48), dtype=np.uint64)
         status = (ctypes.c_uint32 * len(where))()
         rc = lib.bh_proofs_read(keyset.worker.ctx, raw, len(where), recs.ctypes.data_as(ctypes.c_void_p), status, None)
-        if rc not in (0, 6, 7):
+        if rc not in _READ_VERDICTS:
             check(rc, "Proof.read")
         for k, i in enumerate(where):
             out[i] = _status_error(status[k])

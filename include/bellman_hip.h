@@ -741,8 +741,8 @@ int bh_r1cs_check_many(bh_ctx *ctx, const bh_r1cs *r, const void *inputs_host, c
  * bh_r1cs_check_many_dev on the same buffers does.  Asynchronous on `stream`; k = 0 is BH_OK and launches nothing.
  * bh_r1cs_solve_many: the same from and to the host, witness j at j * n_inputs * 32 and j * n_aux * 32, in groups that stay
  * within 1 GiB of device memory.  Synchronous, on a stream of its own: thread-safe. */
-#define BH_HINT_BITS 1
-#define BH_HINT_INV_OR_ZERO 2
+#define BH_HINT_BITS 1u
+#define BH_HINT_INV_OR_ZERO 2u
 typedef struct bh_r1cs_solver bh_r1cs_solver;
 typedef struct {
   uint32_t kind;      /* BH_HINT_* */
@@ -803,24 +803,24 @@ int bh_r1cs_solve_many(bh_ctx *ctx, const bh_r1cs_solver *s, void *inputs_host, 
  * ordered one behind the other, on whatever streams they run.
  * bh_word_witness_generate: the same from and to the host, witness j at j * n_ext * 4, j * n_inputs * 32 and j * n_aux * 32,
  * in groups that stay within 1 GiB of device memory.  Synchronous, on a stream of its own. */
-#define BH_WORD_CONST 1
-#define BH_WORD_ROTR 2
-#define BH_WORD_SHR 3
-#define BH_WORD_XOR 4
-#define BH_WORD_AND 5
-#define BH_WORD_CH 6
-#define BH_WORD_MAJ 7
-#define BH_WORD_ADD 8
-#define BH_WORD_PACK 9
-#define BH_WORD_BAD_SOURCE 1
-#define BH_WORD_BAD_BIT 2
-#define BH_WORD_BAD_ADD_ARITY 3
-#define BH_WORD_BAD_OP 4
-#define BH_WORD_BAD_VAR_SOURCE 5
-#define BH_WORD_BAD_PACKED_BITS 6
-#define BH_WORD_BAD_VAR_RANGE 7
-#define BH_WORD_BAD_UNCOVERED 8
-#define BH_WORD_BAD_COVERED_TWICE 9
+#define BH_WORD_CONST 1u
+#define BH_WORD_ROTR 2u
+#define BH_WORD_SHR 3u
+#define BH_WORD_XOR 4u
+#define BH_WORD_AND 5u
+#define BH_WORD_CH 6u
+#define BH_WORD_MAJ 7u
+#define BH_WORD_ADD 8u
+#define BH_WORD_PACK 9u
+#define BH_WORD_BAD_SOURCE 1u
+#define BH_WORD_BAD_BIT 2u
+#define BH_WORD_BAD_ADD_ARITY 3u
+#define BH_WORD_BAD_OP 4u
+#define BH_WORD_BAD_VAR_SOURCE 5u
+#define BH_WORD_BAD_PACKED_BITS 6u
+#define BH_WORD_BAD_VAR_RANGE 7u
+#define BH_WORD_BAD_UNCOVERED 8u
+#define BH_WORD_BAD_COVERED_TWICE 9u
 typedef struct bh_word_witness bh_word_witness;
 typedef struct {
   uint32_t op; /* BH_WORD_* */

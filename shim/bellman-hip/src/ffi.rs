@@ -18,14 +18,9 @@ pub struct BhBases {
 pub struct BhMsmJob {
     _private: [u8; 0],
 }
-/// opaque `bh_params`
+/// opaque `bh_msm_many_job`
 #[repr(C)]
-pub struct BhParams {
-    _private: [u8; 0],
-}
-/// opaque `bh_r1cs`
-#[repr(C)]
-pub struct BhR1cs {
+pub struct BhMsmManyJob {
     _private: [u8; 0],
 }
 /// opaque `bh_scalars`
@@ -38,9 +33,14 @@ pub struct BhScalars {
 pub struct BhMsmShardedJob {
     _private: [u8; 0],
 }
-/// opaque `bh_proof_job`
+/// opaque `bh_params`
 #[repr(C)]
-pub struct BhProofJob {
+pub struct BhParams {
+    _private: [u8; 0],
+}
+/// opaque `bh_r1cs`
+#[repr(C)]
+pub struct BhR1cs {
     _private: [u8; 0],
 }
 /// opaque `bh_pvk`
@@ -53,11 +53,6 @@ pub struct BhPvk {
 pub struct BhPvkSet {
     _private: [u8; 0],
 }
-/// opaque `bh_msm_many_job`
-#[repr(C)]
-pub struct BhMsmManyJob {
-    _private: [u8; 0],
-}
 /// opaque `bh_r1cs_solver`
 #[repr(C)]
 pub struct BhR1csSolver {
@@ -68,23 +63,12 @@ pub struct BhR1csSolver {
 pub struct BhWordWitness {
     _private: [u8; 0],
 }
-/// `bh_csr`: one constraint matrix in CSR form (include/bellman_hip.h)
+/// opaque `bh_proof_job`
 #[repr(C)]
-#[derive(Clone, Copy)]
-pub struct BhCsr {
-    pub row_ptr: *const u32,
-    pub var: *const u32,
-    pub coeff: *const u32,
+pub struct BhProofJob {
+    _private: [u8; 0],
 }
-/// `bh_msm_opts`: per-job plan overrides; all-zero = tuned defaults
-#[repr(C)]
-#[derive(Clone, Copy, Default)]
-pub struct BhMsmOpts {
-    pub window_bits: u32,
-    pub chunk: u32,
-    pub flags: u32,
-}
-/// `bh_ctx_info_t`: what bh_ctx_info reports about a context
+/// `bh_ctx_info_t` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhCtxInfo {
@@ -102,33 +86,23 @@ pub struct BhCtxInfo {
     pub fft_table_bytes: u64,
     pub fft_table_budget: u64,
 }
-/// `bh_powers_of_tau`: a powers-of-tau transcript as device-resident handles plus [beta]G2 on the host
+/// `bh_msm_opts` (include/bellman_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhMsmOpts {
+    pub window_bits: u32,
+    pub chunk: u32,
+    pub flags: u32,
+}
+/// `bh_csr` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
-pub struct BhPowersOfTau {
-    pub tau_g1: *const BhBases,
-    pub tau_g2: *const BhBases,
-    pub alpha_tau_g1: *const BhBases,
-    pub beta_tau_g1: *const BhBases,
-    pub beta_g2: *const c_void,
+pub struct BhCsr {
+    pub row_ptr: *const u32,
+    pub var: *const u32,
+    pub coeff: *const u32,
 }
-/// `bh_ptau_report`: what bh_powers_of_tau_verify found (the BH_PTAU_FAILED_* bits; the first bad point)
-#[repr(C)]
-#[derive(Clone, Copy, Default, Debug)]
-pub struct BhPtauReport {
-    pub failed: u32,
-    pub bad_vector: u32,
-    pub bad_index: usize,
-}
-/// `bh_params_step_report`: what bh_groth16_params_verify_step found (the BH_STEP_FAILED_* bits; the first position)
-#[repr(C)]
-#[derive(Clone, Copy, Default, Debug)]
-pub struct BhParamsStepReport {
-    pub failed: u32,
-    pub bad_vector: u32,
-    pub bad_index: usize,
-}
-/// `bh_witness_hint`: one hint of a witness solver (kind = BH_HINT_*; terms and outputs as ranges of the pools)
+/// `bh_witness_hint` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhWitnessHint {
@@ -139,7 +113,7 @@ pub struct BhWitnessHint {
     pub out_end: u32,
     pub shift: u32,
 }
-/// `bh_solver_desc`: what bh_r1cs_solver_create takes besides the circuit: supplied variables and hints
+/// `bh_solver_desc` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct BhSolverDesc {
@@ -153,7 +127,7 @@ pub struct BhSolverDesc {
     pub hint_coeffs: *const c_void,
     pub n_hint_coeffs: usize,
 }
-/// `bh_word_instr`: one instruction of a word program (op = BH_WORD_*)
+/// `bh_word_instr` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhWordInstr {
@@ -162,14 +136,14 @@ pub struct BhWordInstr {
     pub b: u32,
     pub c: u32,
 }
-/// `bh_word_bit`: a bit source (bit | neg << 8 of a trace word)
+/// `bh_word_bit` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhWordBit {
     pub word: u32,
     pub bit_neg: u32,
 }
-/// `bh_word_var`: the record of a bit variable
+/// `bh_word_var` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhWordVar {
@@ -177,7 +151,7 @@ pub struct BhWordVar {
     pub word: u32,
     pub bit_neg: u32,
 }
-/// `bh_word_packed`: the record of a packed variable (a range of bit sources)
+/// `bh_word_packed` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct BhWordPacked {
@@ -185,7 +159,7 @@ pub struct BhWordPacked {
     pub bits_begin: u32,
     pub n_bits: u32,
 }
-/// `bh_word_witness_desc`: what bh_word_witness_create takes: the program and the variable records
+/// `bh_word_witness_desc` (include/bellman_hip.h)
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct BhWordWitnessDesc {
@@ -203,6 +177,32 @@ pub struct BhWordWitnessDesc {
     pub packed: *const BhWordPacked,
     pub n_packed: usize,
 }
+/// `bh_powers_of_tau` (include/bellman_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct BhPowersOfTau {
+    pub tau_g1: *const BhBases,
+    pub tau_g2: *const BhBases,
+    pub alpha_tau_g1: *const BhBases,
+    pub beta_tau_g1: *const BhBases,
+    pub beta_g2: *const c_void,
+}
+/// `bh_ptau_report` (include/bellman_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhPtauReport {
+    pub failed: u32,
+    pub bad_vector: u32,
+    pub bad_index: usize,
+}
+/// `bh_params_step_report` (include/bellman_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct BhParamsStepReport {
+    pub failed: u32,
+    pub bad_vector: u32,
+    pub bad_index: usize,
+}
 
 pub const BH_OK: c_int = 0;
 pub const BH_ERR_UNEXPECTED_IDENTITY: c_int = 1;
@@ -211,7 +211,10 @@ pub const BH_ERR_DEGREE_TOO_LARGE: c_int = 3;
 pub const BH_ERR_UNCONSTRAINED_VARIABLE: c_int = 5;
 pub const BH_ERR_INVALID_POINT: c_int = 6;
 pub const BH_ERR_POINT_AT_INFINITY: c_int = 7;
+pub const BH_ERR_INVALID_VERIFYING_KEY: c_int = 8;
+pub const BH_ERR_INVALID_PROOF: c_int = 9;
 pub const BH_ERR_INVALID_TRANSCRIPT: c_int = 10;
+pub const BH_ERR_UNSATISFIABLE: c_int = 11;
 pub const BH_ERR_HIP: c_int = -1;
 pub const BH_ERR_INVALID_ARG: c_int = -2;
 pub const BH_ERR_NO_DEVICE: c_int = -3;
@@ -223,10 +226,24 @@ pub const BH_FFT: c_int = 0;
 pub const BH_IFFT: c_int = 1;
 pub const BH_COSET_FFT: c_int = 2;
 pub const BH_ICOSET_FFT: c_int = 3;
-pub const BH_POINTS_CHECKED: c_uint = 1;
-pub const BH_POINTS_FORBID_IDENTITY: c_uint = 2;
-pub const BH_PTAU_VALIDATE_POINTS: c_uint = 1;
-pub const BH_STEP_VALIDATE_POINTS: c_uint = 1;
+pub const BH_FFT_MANY_FORCE: u32 = 1;
+pub const BH_FFT_MANY_SINGLE: u32 = 2;
+pub const BH_POINTS_CHECKED: u32 = 1;
+pub const BH_POINTS_FORBID_IDENTITY: u32 = 2;
+pub const BH_MSM_ACC_REGISTERS: u32 = 1;
+pub const BH_MSM_ACC_LDS: u32 = 2;
+pub const BH_MSM_NO_TABLE: u32 = 4;
+pub const BH_MSM_NO_SMALL_PATH: u32 = 8;
+pub const BH_MSM_STAGE_TIMES: u32 = 64;
+pub const BH_MSM_HOLD: u32 = 128;
+pub const BH_MSM_G2_SINGLE_LANE: u32 = 16;
+pub const BH_MSM_G2_LANE_TRIPLES: u32 = 32;
+pub const BH_MSM_G2_LANE_PAIRS: u32 = 256;
+pub const BH_MSM_MANY_FORCE: u32 = 512;
+pub const BH_PROOF_STATUS_IDENTITY: u32 = 0x10;
+pub const BH_PROOF_STATUS_INVALID: u32 = 0xee;
+pub const BH_PVK_SET_MAX_KEYS: c_int = 64;
+pub const BH_R1CS_SATISFIED: u32 = 0xFFFFFFFF;
 pub const BH_HINT_BITS: u32 = 1;
 pub const BH_HINT_INV_OR_ZERO: u32 = 2;
 pub const BH_WORD_CONST: u32 = 1;
@@ -247,6 +264,7 @@ pub const BH_WORD_BAD_PACKED_BITS: u32 = 6;
 pub const BH_WORD_BAD_VAR_RANGE: u32 = 7;
 pub const BH_WORD_BAD_UNCOVERED: u32 = 8;
 pub const BH_WORD_BAD_COVERED_TWICE: u32 = 9;
+pub const BH_PTAU_VALIDATE_POINTS: u32 = 1;
 pub const BH_PTAU_FAILED_HEAD: u32 = 0x01;
 pub const BH_PTAU_FAILED_TAU_G1_G2: u32 = 0x02;
 pub const BH_PTAU_FAILED_TAU_G1: u32 = 0x04;
@@ -255,6 +273,7 @@ pub const BH_PTAU_FAILED_ALPHA: u32 = 0x10;
 pub const BH_PTAU_FAILED_BETA: u32 = 0x20;
 pub const BH_PTAU_FAILED_BETA_G2: u32 = 0x40;
 pub const BH_PTAU_FAILED_POINTS: u32 = 0x80;
+pub const BH_STEP_VALIDATE_POINTS: u32 = 1;
 pub const BH_STEP_FAILED_SHAPE: u32 = 0x001;
 pub const BH_STEP_FAILED_HEAD: u32 = 0x002;
 pub const BH_STEP_FAILED_KEY: u32 = 0x004;
@@ -265,7 +284,11 @@ pub const BH_STEP_FAILED_DELTA: u32 = 0x040;
 pub const BH_STEP_FAILED_H: u32 = 0x080;
 pub const BH_STEP_FAILED_L: u32 = 0x100;
 pub const BH_STEP_FAILED_POINTS: u32 = 0x200;
+pub const BH_PROVE_CHECK: u32 = 1;
+pub const BH_PROVE_FINISH_DEVICE: u32 = 2;
+pub const BH_PROVE_FINISH_HOST: u32 = 4;
 pub const BH_MSM_SUMS_BYTES: usize = 960;
+pub const BH_FINISH_KEY_BYTES: usize = 672;
 
 #[link(name = "bellman_hip")]
 extern "C" {

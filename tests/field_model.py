@@ -514,14 +514,6 @@ def case_id(case):
     return "%s-%s" % (FORM_NAMES[form], names[op])
 
 
-def bind(lib):
-    vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    lib.bh_test_field_ops_shape.argtypes = [i32, i32, vp]
-    lib.bh_test_field_ops_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, sz]
-    lib.bh_test_field_ops_host.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, sz]
-    return lib
-
-
 def shape(lib, form, op):
     out = (ctypes.c_size_t * 4)()
     assert lib.bh_test_field_ops_shape(form, op, out) == 0, (form, op)

@@ -446,14 +446,6 @@ TABLE_SIZES = {
 
 
 # --------------------------------------------------------------------------------------------- the hooks through ctypes
-def bind(lib):
-    vp, sz, i32, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
-    lib.bh_test_group_ops_shape.argtypes = [i32, i32, vp]
-    lib.bh_test_group_ops_dev.argtypes = [vp, i32, i32, u32, vp, vp, vp, vp, sz]
-    lib.bh_test_group_ops_host.argtypes = [i32, i32, u32, vp, vp, vp, vp, sz]
-    return lib
-
-
 def shape(lib, form, op):
     out = (ctypes.c_size_t * 4)()
     assert lib.bh_test_group_ops_shape(form, op, out) == 0, (form, op)

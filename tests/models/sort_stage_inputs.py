@@ -2,7 +2,6 @@
 shapes that reach each tile, key and word edge.  The tile sizes come from bh_test_sort_plan (plan_info), never from here.
 
 A case is a small dict (cheap to list at collection time); build(case) turns it into the arrays a run needs."""
-import ctypes
 import random
 
 import numpy as np
@@ -32,11 +31,6 @@ def test_lib():
         from bellman_amd import _lib as loader
 
         _lib = loader.load().test
-        c = ctypes
-        _lib.bh_test_sort_plan.argtypes = [c.c_int, c.c_size_t, c.c_uint, c.c_size_t, c.c_int, c.c_int, c.c_void_p]
-        _lib.bh_test_scan_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
-        _lib.bh_test_sort_stage_dev.argtypes = [c.c_void_p, c.c_int, c.c_uint, c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_size_t,
-                                                c.c_size_t, c.c_size_t] + [c.c_void_p] * 8
     return _lib
 
 

@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-from bellman_amd import _lib
+from bellman_amd import _abi, _lib
 from oracle import cref
 from oracle.pyref import bls12_381 as bls
 
@@ -49,15 +49,18 @@ def test_header_symbols_all_exported(lib):
     built-in demo circuits (include/bellman_hip_test.h) live in libbellman_hip_test.so, which links against it.
     [r6] ... and NOTHING else: no mangled C++ internal is in any library's dynamic symbol table (csrc/libbellman_hip.map);
     the test library gets the C++ host API from the static archive libbellman_groth16.a and everything else through the C ABI."""
-    hdr = open(os.path.join(ROOT, "include", "bellman_hip.h")).read()
+    hdr = _abi.strip_comments(open(os.path.join(ROOT, "include", "bellman_hip.h")).read())
     declared = set(re.findall(r"\b(bh_[a-z0-9_]+)\s*\(", hdr))
     assert declared, "no declarations parsed"
     # the product boundary carries no test hooks and no demo circuits: they live in their own header and library
     assert not [d for d in declared if d.startswith("bh_test_") or "demo" in d]
-    test_hdr = open(os.path.join(ROOT, "include", "bellman_hip_test.h")).read()
+    test_hdr = _abi.strip_comments(open(os.path.join(ROOT, "include", "bellman_hip_test.h")).read())
     hooks = set(re.findall(r"\b(bh_[a-z0-9_]+)\s*\(", test_hdr))
     assert hooks and all(h.startswith("bh_test_") or "demo" in h for h in hooks)
     assert declared == set(_lib.EXPORTS) and hooks == set(_lib.TEST_EXPORTS)
+    # the naive scan above is the independent count: the parser of bellman_amd/_abi.py must find the same names, once each
+    assert sorted(f.name for f in _abi.PRODUCT.functions) == sorted(declared)
+    assert sorted(f.name for f in _abi.TEST.functions) == sorted(hooks)
     assert _exported_c_symbols(_lib.LIB_PATH) == declared
     assert _exported_c_symbols(_lib.TEST_LIB_PATH) == hooks
     assert _all_dynamic_symbols(_lib.LIB_PATH) == declared, sorted(_all_dynamic_symbols(_lib.LIB_PATH) - declared)[:10]
@@ -487,3 +490,123 @@ def test_plain_c_caller_builds_and_passes_host_checks(tmp_path):
                     "-Wl,-rpath," + libdir], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "host checks passed" in r.stdout, r.stdout + r.stderr
+
+
+def test_every_entry_point_is_declared_bound_and_exported(lib):
+    """Every function of the two headers: declared, in the lists _lib.py derives, a `T` symbol of the library that should
+    export it, matched by a `global:` pattern of csrc/libbellman_hip.map, and - the product header - a `pub fn` of ffi.rs.
+    (The per-feature copies of this loop in test_phase2_cpu.py, test_ptau_cpu.py and test_ptau_verify_cpu.py held for three
+    names each.)"""
+    import fnmatch
+    import subprocess
+
+    patterns = re.findall(r"global:\s*([^;]+);", open(os.path.join(ROOT, "bellman_amd", "csrc", "libbellman_hip.map")).read())
+    ffi = open(os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")).read()
+    for header, path, exports, cdll in ((_abi.PRODUCT_HEADER, _lib.LIB_PATH, _lib.EXPORTS, lib.product),
+                                        (_abi.TEST_HEADER, _lib.TEST_LIB_PATH, _lib.TEST_EXPORTS, lib.test)):
+        text = _abi.strip_comments(open(header).read())
+        syms = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        assert len(exports) == len(set(exports)) > 50
+        for name in exports:
+            assert re.search(r"\b%s\s*\(" % name, text), name
+            assert re.search(r" T %s$" % name, syms, flags=re.M), name
+            assert any(fnmatch.fnmatchcase(name, p.strip()) for p in patterns), name
+            assert getattr(cdll, name).argtypes is not None, name
+            assert ("pub fn %s(" % name in ffi) == (header == _abi.PRODUCT_HEADER), name
+
+
+def test_bindings_follow_the_headers(lib):
+    """argtypes of the declared length and the mapped restype on every function of both headers; the mapping itself is
+    pinned by value where a wrong width would truncate silently."""
+    c = ctypes
+    for header, cdll in ((_abi.PRODUCT, lib.product), (_abi.TEST, lib.test)):
+        for fn in header.functions:
+            f = getattr(cdll, fn.name)
+            assert f.argtypes is not None and len(f.argtypes) == len(fn.params), fn.name
+            assert all(t is not None for t in f.argtypes), fn.name
+            want = {"void": None, "int": c.c_int, "size_t": c.c_size_t, "uint32_t": c.c_uint32, "double": c.c_double,
+                    "const char *": c.c_char_p, "const void *": c.c_void_p}[fn.ret]
+            assert f.restype is want, fn.name
+            for (_, ctype), t in zip(fn.params, f.argtypes):
+                assert (t is c.c_void_p) == ("*" in ctype), (fn.name, ctype)
+    params = {fn.name: dict(fn.params) for fn in _abi.PRODUCT.functions}
+    reg = lib.bh_bases_register
+    assert list(params["bh_bases_register"]) == ["ctx", "group", "host_points", "n", "stride", "inf_offset", "out"]
+    assert reg.argtypes[5] is c.c_long and reg.argtypes[3] is c.c_size_t and reg.argtypes[1] is c.c_int and reg.restype is c.c_int
+    assert lib.bh_test_synthesis_ms.restype is c.c_double
+    assert lib.bh_test_synthesis_ms.argtypes == [c.c_int, c.c_size_t, c.c_uint64, c.c_int]
+    assert lib.bh_scalars_dev_ptr.restype is c.c_void_p
+    assert lib.bh_groth16_pvk_num_inputs.restype is c.c_size_t
+    assert lib.bh_test_pool_size_class.restype is c.c_size_t and lib.bh_test_pool_size_class.argtypes == [c.c_size_t]
+    assert lib.bh_version.restype is c.c_char_p and lib.bh_version.argtypes == []
+    assert lib.bh_ctx_destroy.restype is None
+    assert lib.bh_fft_fr.argtypes == [c.c_void_p, c.c_void_p, c.c_uint32, c.c_int]
+    assert lib.bh_msm_plan_info.argtypes == [c.c_size_t, c.c_int, c.c_uint, c.c_void_p]
+    assert c.sizeof(c.c_uint32) == 4 and c.sizeof(c.c_uint64) == 8 and c.sizeof(c.c_int32) == 4
+
+
+def test_struct_layouts_and_constants_against_the_c_compiler(tmp_path):
+    """The compiler, not a second hand copy, says what the layouts and values are: a C11 program that includes the two
+    headers prints sizeof and every field's offsetof and size for every parsed struct and every parsed #define as long
+    long; the derived ctypes classes and the parsed constants must agree.  The program is generated from the parsed names
+    only - that no name is missing is the business of the name checks above and of the counts asserted here."""
+    import subprocess
+
+    structs = {name: fields for h in (_abi.PRODUCT, _abi.TEST) for name, fields in h.structs.items()}
+    constants = {name: k for h in (_abi.PRODUCT, _abi.TEST) for name, k in h.constants.items()}
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "bellman_hip.h"', '#include "bellman_hip_test.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        src.append('  printf("S %s %%zu\\n", sizeof(%s));' % (name, name))
+        for field, _ in fields:
+            src.append('  printf("F %s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (name, field, name, field, name, field))
+    for name in constants:
+        src.append('  printf("C %s %%lld\\n", (long long)(%s));' % (name, name))
+    src += ["  return 0;", "}", ""]
+    (tmp_path / "layout.c").write_text("\n".join(src))
+    exe = str(tmp_path / "layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-O1", "-I", os.path.join(ROOT, "include"),
+                    str(tmp_path / "layout.c"), "-o", exe], check=True)
+    got = dict(ln.split(" ", 2)[1:] for ln in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
+    want = {}
+    for name, fields in structs.items():
+        cls = _abi.STRUCTS[name]
+        assert [f for f, _ in cls._fields_] == [f for f, _ in fields], name
+        want[name] = "%d" % ctypes.sizeof(cls)
+        for field, _ in fields:
+            want["%s.%s" % (name, field)] = "%d %d" % (getattr(cls, field).offset, getattr(cls, field).size)
+    for name, k in constants.items():
+        want[name] = "%d" % k.value
+        assert getattr(_abi.C, name) == k.value
+    assert got == want, sorted(k for k in want if got.get(k) != want[k])
+    # the typedefs and defines a plain scan of the headers counts
+    text = "".join(_abi.strip_comments(open(h).read()) for h in (_abi.PRODUCT_HEADER, _abi.TEST_HEADER))
+    assert len(structs) == len(re.findall(r"typedef\s+struct\s*\w*\s*\{", text)) == 14
+    assert len(constants) == len(re.findall(r"^\s*#\s*define\s+BH_", text, flags=re.M)) >= 85
+    opaque = _abi.PRODUCT.opaque + _abi.TEST.opaque
+    assert len(opaque) == len(re.findall(r"typedef\s+struct\s+\w+\s+\w+\s*;", text)) == 13
+    assert _abi.PRODUCT.constants["BH_ERR_HIP"] == (-1, False, "-1") and _abi.PRODUCT.constants["BH_MSM_MANY_FORCE"] == (512, True, "512")
+    assert _abi.PRODUCT.constants["BH_STEP_FAILED_L"] == (0x100, True, "0x100")
+
+
+def test_header_parser_is_strict():
+    """Nothing is skipped quietly: an unknown type, a struct that does not close and a `bh_*(` that is no declaration each
+    raise an error that names the symbol; so does a #define BH_* that is no integer literal, and a missing header."""
+    ok = "typedef struct bh_ctx bh_ctx;\nint bh_fine(bh_ctx *ctx, const uint64_t words[4], unsigned flags);\n#define BH_TWO (-2)\n"
+    h = _abi.parse(ok)
+    assert h.functions == [("bh_fine", "int", [("ctx", "bh_ctx *"), ("words", "const uint64_t *"), ("flags", "unsigned")])]
+    assert h.opaque == ["bh_ctx"] and h.constants == {"BH_TWO": (-2, False, "-2")}
+    for text, symbol in (
+            (ok + "int bh_unknown_type(bh_ctx *ctx, uint128_t x);\n", "bh_unknown_type"),
+            (ok + "uint128_t bh_unknown_return(void);\n", "bh_unknown_return"),
+            (ok + "typedef struct { uint128_t x; } bh_unknown_field;\n", "bh_unknown_field"),
+            (ok + "typedef struct bh_never_closed {\n  uint32_t a;\nint bh_after(void);\n", "bh_never_closed"),
+            (ok + "int bh_no_paren(bh_ctx *ctx;\nint bh_after(void);\n", "bh_no_paren"),
+            (ok + "int bh_callback(void (*fn)(int), size_t n);\n", "bh_callback"),
+            (ok + "int bh_unnamed(int);\n", "bh_unnamed"),
+            (ok + "static inline int bh_inline(int a) { return a; }\n", "bh_inline"),
+            (ok + "#define BH_EXPR (1 << 4)\n", "BH_EXPR"),
+            (ok + "#define BH_MACRO(x) (x)\n", "BH_MACRO")):
+        with pytest.raises(_abi.AbiError, match=r"\b%s\b" % symbol):
+            _abi.parse(text)
+    with pytest.raises(_abi.AbiError, match="no_such_header.h"):
+        _abi._read(os.path.join(ROOT, "include", "no_such_header.h"))

@@ -46,7 +46,6 @@ def test_boolmix_mirror_oracle_and_fast_form_agree(rounds):
         assert a * b % circuits.Q == c % circuits.Q
     # the structure capture of the same circuit reproduces its ProvingAssignment
     lib = _lib.load()
-    lib.bh_test_capture_check.restype = ctypes.c_double
     out4 = (ctypes.c_size_t * 4)()
     ms = lib.bh_test_capture_check(5, ctypes.c_size_t(rounds), ctypes.c_uint64(seed), out4)
     assert ms >= 0 and out4[0] == len(pa.a) and out4[3] == 0, list(out4)

@@ -20,11 +20,7 @@ RAW = {"g1": 6, "k3": 7, "g2": 8}
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load().test
-    u32, i32, vp = ctypes.c_uint, ctypes.c_int, ctypes.c_void_p
-    lib.bh_test_bucket_stage_shape.argtypes = [i32, i32, vp]
-    lib.bh_test_merge_plan.argtypes = [i32, u32, u32, u32, u32, u32, i32, vp, vp]
-    return lib
+    return _lib.load().test
 
 
 def shape(lib, merge_form):
@@ -260,7 +256,6 @@ def test_merge_plan_computes_what_msm_enqueue_computed_inline(lib, bundle):
     from bellman_amd import _lib
 
     product = _lib.load().product
-    product.bh_msm_plan_info.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
     g2 = bundle != "g1"
     checked = 0
     for num_cus in (256, 64):

@@ -20,7 +20,7 @@ P, Q = fm.P, fm.Q
 def lib():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
-    return fm.bind(_lib.load())
+    return _lib.load()
 
 
 def _rand(rnd, like):

@@ -57,11 +57,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load().test
-    u32, i32, vp, sz = ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
-    lib.bh_test_bucket_stage_shape.argtypes = [i32, i32, vp]
-    lib.bh_test_bucket_stage_dev.argtypes = [vp, i32, i32, vp, vp, u32, u32, vp, sz, u32, u32, u32, u32, vp, vp] + [vp] * 7
-    return lib
+    return _lib.load().test
 
 
 PLAN_FIELDS = ("walk", "run_lanes", "runs_on_pairs", "big_chunks", "piece", "max_long", "max_big", "max_pieces")

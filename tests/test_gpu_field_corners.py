@@ -43,7 +43,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    return fm.bind(_lib.load())
+    return _lib.load()
 
 
 @pytest.mark.parametrize("case", fm.cases(), ids=fm.case_id)

@@ -44,7 +44,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    return gm.bind(_lib.load())
+    return _lib.load()
 
 
 @pytest.mark.parametrize("case", gm.cases(), ids=gm.case_id)

@@ -26,7 +26,7 @@ P = gm.P
 def lib():
     from bellman_amd import _lib
 
-    return gm.bind(_lib.load())
+    return _lib.load()
 
 
 @pytest.fixture(scope="module")

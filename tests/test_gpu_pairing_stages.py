@@ -37,22 +37,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load()
-    vp, sz, i32, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
-    lib.bh_test_pairing_stage_shape.argtypes = [vp]
-    lib.bh_test_pairing_lines_dev.argtypes = [vp, vp, sz, i32, sz, vp, vp, vp]
-    lib.bh_test_pairing_miller_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, vp, vp]
-    lib.bh_test_pairing_fold_dev.argtypes = [vp, vp, sz, vp]
-    lib.bh_test_pairing_proof_prep_dev.argtypes = [vp, vp, vp, i32, sz, i32, vp, vp, vp, vp, vp, vp]
-    lib.bh_test_pairing_g1_mul_one_dev.argtypes = [vp, vp, vp, vp, vp]
-    lib.bh_test_pairing_colsum_dev.argtypes = [vp, vp, vp, sz, i32, sz, u32, vp, vp, vp]
-    lib.bh_test_pairing_ic_table_dev.argtypes = [vp, vp, sz, u32, vp, vp]
-    lib.bh_test_pairing_ic_accumulate_dev.argtypes = [vp, vp, sz, i32, vp, u32, vp, sz, vp, vp]
-    lib.bh_test_pairing_miller3_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, u32, sz, vp, vp]
-    lib.bh_test_pairing_fold3_const_dev.argtypes = [vp, vp, vp, sz, i32, vp]
-    lib.bh_test_pairing_verdict_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
-    lib.bh_test_pairing_final_exp_dev.argtypes = [vp, vp, sz, vp, vp, vp]
-    return lib
+    return _lib.load()
 
 
 def out(nbytes):

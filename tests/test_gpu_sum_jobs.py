@@ -19,7 +19,6 @@ each path of the kernel:
   three different jobs in one launch (lane pairs; lane triples with 84- and 64-worker workgroups side by side)
 Bytes after the last output must come back untouched."""
 
-import ctypes
 import random
 
 import numpy as np
@@ -117,10 +116,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load().test
-    vp, sz = ctypes.c_void_p, ctypes.c_size_t
-    lib.bh_test_sum_jobs_dev.argtypes = [vp, ctypes.c_int, ctypes.c_uint, vp, sz, vp, sz, vp, sz]
-    return lib
+    return _lib.load().test
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from bellman_amd import _abi
 from tests import field_model as fm
 from tests import group_model as gm
 from tests.models import pairing_stage_model as psm
@@ -24,9 +25,7 @@ KEY_OF = [0] + [1] * 63 + [2] * 65 + [3]
 KEY_BUFS = ("tables", "ic0", "key lines", "key flags", "f_ab", "alpha", "descriptors")
 
 
-class KeyLayout(ctypes.Structure):
-    _fields_ = [("n_keys", ctypes.c_size_t)] + [(name, ctypes.c_void_p) for name in
-                                                 ("n_inputs", "widths", "tables", "ic0", "lines", "qflags", "f_ab", "alpha")]
+KeyLayout = _abi.STRUCTS["bh_test_key_layout"]
 
 
 @pytest.fixture(scope="module")
@@ -42,15 +41,7 @@ def worker():
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load()
-    vp, sz, i32, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
-    lib.bh_test_pairing_ic_accumulate_keys_dev.argtypes = [vp, vp, vp, sz, vp, sz, i32, sz, vp, vp]
-    lib.bh_test_pairing_miller3_keys_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, i32, sz, vp, vp]
-    lib.bh_test_pairing_fold3_const_keys_dev.argtypes = [vp, vp, vp, sz, vp, sz, i32, vp]
-    lib.bh_test_pairing_colsum_keys_dev.argtypes = [vp, vp, vp, vp, vp, sz, i32, sz, u32, vp, vp, vp]
-    lib.bh_test_pairing_g1_mul_keys_dev.argtypes = [vp, vp, vp, vp, vp]
-    lib.bh_test_pairing_miller_keys_dev.argtypes = [vp, vp, vp, vp, vp]
-    return lib
+    return _lib.load()
 
 
 class Layout:

@@ -28,8 +28,6 @@ def hook():
     from bellman_amd import _lib
 
     lib = _lib.load()
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint
-    lib.bh_test_window_table_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, u32, u32, vp]
     shape = (ctypes.c_size_t * 12)()
     assert lib.bh_test_bucket_stage_shape(0, 0, shape) == 0
     return lib, int(shape[7]), int(shape[11])   # guard bytes, sentinel byte

@@ -24,7 +24,7 @@ P = gm.P
 def lib():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
-    return gm.bind(_lib.load())
+    return _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------------------ the model

@@ -28,10 +28,7 @@ SIZES = [(1024, 1024), ((1 << 27) - 1, 1024), (1 << 27, 1024), (1024, (1 << 28) 
 def lib():
     from bellman_amd import _lib
 
-    lib = _lib.load().test
-    i32, u32, u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_uint64
-    lib.bh_test_msm_sources.argtypes = [i32, i32, i32, ctypes.c_uint32, u32, u32, u32, u64, u64, i32, ctypes.c_void_p]
-    return lib
+    return _lib.load().test
 
 
 def pick(lib, group, kind, padded, flags, opts_c, row, n, form):

@@ -105,7 +105,6 @@ def test_accumulation_by_table_terms_is_the_affine_sum():
 
 
 def test_verdict_model_against_proof_status_error(lib):
-    lib.bh_test_proof_status_error.argtypes = [__import__("ctypes").c_uint32]
     for s in range(256):
         for pos in range(3):
             word = s << (8 * pos)

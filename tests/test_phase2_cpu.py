@@ -6,7 +6,6 @@ in the header, the ctypes table, the library and the generated Rust declarations
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -161,17 +160,15 @@ def test_host_predicate_equals_numpy(group, words):
 
 
 def test_entry_points_declared_bound_and_exported():
+    """what this feature adds to the boundary; that EVERY declared entry point is bound, exported, in ffi.rs and in the
+    version script is tests/test_abi_cpu.py::test_every_entry_point_is_declared_bound_and_exported"""
     header = open(os.path.join(ROOT, "include", "bellman_hip.h")).read()
     from bellman_amd import _lib
     from bellman_amd import ceremony, groth16
 
     ffi = open(os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")).read()
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     for name in ENTRY_POINTS:
         assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.EXPORTS, name
-        assert re.search(r" T %s$" % name, syms, flags=re.M), name
-        assert "pub fn %s(" % name in ffi, name
     assert "bh_params_step_report;" in header and "pub struct BhParamsStepReport" in ffi
     for bit, name in enumerate(("SHAPE", "HEAD", "KEY", "A", "B_G1", "B_G2", "DELTA", "H", "L", "POINTS")):
         assert re.search(r"#define BH_STEP_FAILED_%s 0x%03xu\b" % (name, 1 << bit), header), name

@@ -2,7 +2,6 @@
 generate_parameters with gamma = delta = 1 - the transcript is made from known (tau, alpha, beta), so the two must give
 the same group elements - and the three entry points in the header, the ctypes table and the export map."""
 
-import fnmatch
 import os
 import random
 import re
@@ -74,17 +73,12 @@ def test_model_errors():
 
 
 def test_entry_points_declared_bound_and_exported():
+    """what this feature adds to the boundary; that EVERY declared entry point is bound, exported, in ffi.rs and in the
+    version script is tests/test_abi_cpu.py::test_every_entry_point_is_declared_bound_and_exported"""
     header = open(os.path.join(ROOT, "include", "bellman_hip.h")).read()
-    from bellman_amd import _lib
-
-    patterns = re.findall(r"global:\s*([^;]+);", open(os.path.join(ROOT, "bellman_amd", "csrc", "libbellman_hip.map")).read())
     for name in ENTRY_POINTS:
         assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.EXPORTS, name
-        assert any(fnmatch.fnmatchcase(name, p.strip()) for p in patterns), name
     assert "bh_powers_of_tau;" in header
     assert re.search(r"VALIDATES NOTHING", header)   # the transcript call must say that it checks no point
     ffi = open(os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert "pub fn %s(" % name in ffi, name
     assert "pub struct BhPowersOfTau" in ffi

@@ -4,10 +4,8 @@ oracle/pyref, and the new entry points in the header, the ctypes table, the expo
 Rust declarations."""
 
 import ctypes
-import fnmatch
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -93,18 +91,14 @@ def test_model_masks():
 
 
 def test_entry_points_declared_bound_and_exported():
+    """what this feature adds to the boundary; that EVERY declared entry point is bound, exported, in ffi.rs and in the
+    version script is tests/test_abi_cpu.py::test_every_entry_point_is_declared_bound_and_exported"""
     header = open(os.path.join(ROOT, "include", "bellman_hip.h")).read()
     from bellman_amd import _lib
 
-    patterns = re.findall(r"global:\s*([^;]+);", open(os.path.join(ROOT, "bellman_amd", "csrc", "libbellman_hip.map")).read())
     ffi = open(os.path.join(ROOT, "shim", "bellman-hip", "src", "ffi.rs")).read()
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     for name in ENTRY_POINTS:
         assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.EXPORTS, name
-        assert any(fnmatch.fnmatchcase(name, p.strip()) for p in patterns), name
-        assert re.search(r" T %s$" % name, syms, flags=re.M), name
-        assert "pub fn %s(" % name in ffi, name
     assert "bh_ptau_report;" in header and "pub struct BhPtauReport" in ffi
     assert re.search(r"#define BH_ERR_INVALID_TRANSCRIPT 10\b", header) and "BH_ERR_INVALID_TRANSCRIPT: c_int = 10" in ffi
     assert re.search(r"SEED MUST BE CHOSEN AFTER THE TRANSCRIPT IS FIXED", header)

@@ -118,7 +118,6 @@ def test_every_form_of_linear_combination_matches_the_oracle(kind, rounds):
         bits = np.unpackbits(asg[key].view(np.uint8), bitorder="little")[:len(want)].astype(bool)
         assert list(bits) == [bool(b) for b in want], key
     lib = _lib.load()
-    lib.bh_test_capture_check.restype = ctypes.c_double
     out4 = (ctypes.c_size_t * 4)()
     ms = lib.bh_test_capture_check(kind, ctypes.c_size_t(rounds), ctypes.c_uint64(seed), out4)
     assert ms >= 0 and out4[0] == len(pa.a) and out4[3] == 0, list(out4)
@@ -233,6 +232,5 @@ def test_closures_that_discard_terms_are_refused(variant, rounds):
     with pytest.raises(AssertionError, match="invalid argument"):   # BH_ERR_INVALID_ARG (the reference would panic)
         pg.demo_assignment(4, rounds, variant, [0x55AA55AA])
     lib = _lib.load()
-    lib.bh_test_capture_check.restype = ctypes.c_double
     out4 = (ctypes.c_size_t * 4)()
     assert lib.bh_test_capture_check(4, ctypes.c_size_t(rounds), ctypes.c_uint64(variant), out4) < 0

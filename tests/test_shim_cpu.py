@@ -94,25 +94,39 @@ def test_patched_rust_files_are_balanced():
 
 def test_ffi_rs_is_generated_from_the_header():
     import gen_rust_ffi as g
+    from bellman_amd import _abi, _lib
 
-    decls = g.parse_decls(open(g.HEADER).read())
-    assert open(g.OUT).read() == g.render(decls), "run python tools/gen_rust_ffi.py"
-    names = [d[0] for d in decls]
+    assert open(g.OUT).read() == g.render(_abi.PRODUCT), "run python tools/gen_rust_ffi.py"
+    names = [f.name for f in _abi.PRODUCT.functions]
     assert len(names) == len(set(names)) and "bh_msm_async" in names and "bh_fft_fr" in names
     assert not [n for n in names if n.startswith("bh_test_")]
     # every entry point the library exports through the product header is bound, and nothing else
-    from bellman_amd import _lib
-
+    rs = open(g.OUT).read()
+    assert re.findall(r"pub fn (\w+)\(", rs) == names
     assert set(names) == {s for s in _lib.EXPORTS if not s.startswith("bh_test_")}
+    # every opaque handle and struct of the header, under the CamelCase of its C name
+    assert g.rust_name("bh_ctx_info_t") == "BhCtxInfo" and g.rust_name("bh_r1cs_solver") == "BhR1csSolver"
+    assert re.findall(r"pub struct (\w+) \{", rs) == [g.rust_name(n) for n in _abi.PRODUCT.opaque + list(_abi.PRODUCT.structs)]
 
 
 def test_ffi_constants_match_the_header():
+    """every #define BH_* of the header is a constant of ffi.rs with the header's value (decimal or hex), and ffi.rs holds
+    no other; unsuffixed literals are c_int, `u` ones u32, *_BYTES sizes usize"""
     import gen_rust_ffi as g
+    from bellman_amd import _abi
 
-    hdr = g.header_constants()
-    rs = open(g.OUT).read()
-    for name, val in re.findall(r"pub const (BH_\w+): \w+ = (-?\d+);", rs):
-        assert name in hdr and int(hdr[name]) == int(val), name
+    hdr = _abi.PRODUCT.constants
+    found = re.findall(r"pub const (\w+): (\w+) = (-?(?:0[xX][0-9a-fA-F]+|\d+));", open(g.OUT).read())
+    assert len(found) == len(re.findall(r"pub const ", open(g.OUT).read())), "a constant of ffi.rs is not an integer literal"
+    assert [name for name, _, _ in found] == list(hdr)
+    for name, rtype, val in found:
+        assert int(val, 0) == hdr[name].value, name
+        assert rtype == ("usize" if name.endswith("_BYTES") else "u32" if hdr[name].unsigned else "c_int"), name
+    # ... against the text of the header itself, read without the parser
+    text = open(_abi.PRODUCT_HEADER).read()
+    plain = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(BH_\w+)\s+\(?(-?(?:0[xX][0-9a-fA-F]+|\d+))[uU]?\)?", text)}
+    assert plain == {name: int(val, 0) for name, _, val in found}
+    assert plain["BH_ERR_NO_DEVICE"] == -3 and plain["BH_R1CS_SATISFIED"] == 0xFFFFFFFF and plain["BH_MSM_SUMS_BYTES"] == 960
 
 
 def test_ffi_signatures_spot_checks():

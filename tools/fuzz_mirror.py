@@ -15,7 +15,6 @@ from oracle.pyref import prover as oprover
 from oracle.pyref.core import INPUT, Variable
 from tests import circuits
 lib = _lib.load()
-lib.bh_test_capture_check.restype = ctypes.c_double
 rnd = random.Random(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 n_ok = 0
 for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 200):
