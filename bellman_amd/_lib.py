@@ -91,7 +91,7 @@ def load():
             "libbellman_hip.so not built (run `make -C bellman_amd/csrc`); "
             "bellman_amd has no CPU fallback"
         )
-    # more hardware queues than the runtime's 4: a proof runs 6-7 job streams at once (see api.hip); must be in the
+    # more hardware queues than the runtime's 4: a proof runs 6-7 job streams at once (see api_context.hip); must be in the
     # environment before the process' first HIP call
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     product = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)

@@ -1,9 +1,9 @@
-// Comparison of resident point records (bh_bases_first_difference, api.hip): the first index at which two ranges of dense
+// Comparison of resident point records (bh_bases_first_difference, api_bases.hip): the first index at which two ranges of dense
 // 96- / 192-byte records differ.  One lane per record; a record is read as VEC 16-byte vectors (6 for G1, 12 for G2) and
 // the two sides are XORed into one word, so a lane holds two vectors and an accumulator at a time - no scratch, few
 // registers, full occupancy.  The wavefront's lanes are combined by a ballot; one 64-bit atomicMin per wavefront that saw
 // a difference.  The kernel does no arithmetic to speak of: it is bound by the 2 x count x 96|192 bytes it reads.
-// Included by api.hip (the product) and by test_phase2_hooks.hip (the test library), which runs the predicate on the host.
+// Included by api_bases.hip (the product) and by test_phase2_hooks.hip (the test library), which runs the predicate on the host.
 #pragma once
 #include "common.hpp"
 

@@ -3,32 +3,26 @@
 // linear combination of each vector against its own shift (ptau_rlc.cuh) and six pairing equations.  And what a receiver
 // of a circuit-specific contribution needs: bh_pairing_same_ratio_each (one verdict per equation e(a, B) = e(b, A): the
 // contribution proofs) and bh_groth16_params_verify_step - byte comparison of everything a step must leave alone
-// (bh_bases_first_difference, api.hip), one linear combination per side of h and l (phase2_sums.cuh), three equations.
-// And what a CONTRIBUTOR to a transcript runs: bh_powers_of_tau_contribute, four bh_bases_scale_powers (api.hip; the
+// (bh_bases_first_difference, api_bases.hip), one linear combination per side of h and l (phase2_sums.cuh), three equations.
+// And what a CONTRIBUTOR to a transcript runs: bh_powers_of_tau_contribute, four bh_bases_scale_powers (api_bases.hip; the
 // split-scalar multiplier of point_mul.hip) and one host multiplication.
 //
 // The pairings run through the verifier's own launch functions (pairing_kernels.cuh, compiled in pairing.hip - the one
-// unit of this library that includes that header - and declared here): the lines of every Q, one Miller lane per pair,
+// unit of this library that includes that header - and declared in pairing_launch.hpp): the lines of every Q, one Miller lane per pair,
 // the fold, the final exponentiation.  An equation e(X, Y) = e(Z, W) is evaluated as e(X, Y) e(-Z, W) == 1 on two lanes.
 #include <string.h>
 
 #include <vector>
 
 #include "fp12.cuh"
-#include "msm_types.hpp"
+#include "handles.hpp"
+#include "pairing_launch.hpp"
 #include "phase2_sums.cuh"
 #include "point_read.cuh"
+#include "points.hpp"
 #include "ptau_rlc.cuh"
 
 namespace bh {
-int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int negate, line_t *lines, u32 *flags, size_t n);
-int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
-                  const line_t *lines1, const u32 *qflags1, size_t n1);
-int launch_fold(hipStream_t st, fp12_t *f, size_t m);
-int launch_fold_rows(hipStream_t st, fp12_t *f, size_t m);
-int launch_final_exp(hipStream_t st, const fp12_t *f, size_t n, fp12_t *out, u32 *is_one, fp12_t *ws);
-int bases_group(const ::bh_bases *b);   // api.hip
-
 namespace {
 
 struct OwnStream {
@@ -137,7 +131,7 @@ int bh_powers_of_tau_verify(bh_ctx *ctx, const bh_powers_of_tau *t, const void *
   const bh_bases *vec[4] = {t->tau_g1, t->tau_g2, t->alpha_tau_g1, t->beta_tau_g1};
   static const size_t min_len[4] = {2, 2, 1, 1};
   for (int v = 0; v < 4; v++)
-    if (bases_group(vec[v]) != (v == 1 ? BH_G2 : BH_G1) || bh_bases_len(vec[v]) < min_len[v]) return BH_ERR_INVALID_ARG;
+    if (vec[v]->group != (v == 1 ? BH_G2 : BH_G1) || bh_bases_len(vec[v]) < min_len[v]) return BH_ERR_INVALID_ARG;
   BH_HIP_CHECK(hipSetDevice(ctx->c.device));
 
   if (flags & BH_PTAU_VALIDATE_POINTS)
@@ -250,7 +244,7 @@ int bh_powers_of_tau_contribute(bh_ctx *ctx, const bh_powers_of_tau *before, con
   const bh_bases *vec[4] = {before->tau_g1, before->tau_g2, before->alpha_tau_g1, before->beta_tau_g1};
   for (int v = 0; v < 4; v++) {
     out[v] = nullptr;
-    if (bases_group(vec[v]) != (v == 1 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
+    if (vec[v]->group != (v == 1 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
   }
   fr_t secret[3], canon[3], one;   // tau, alpha, beta
   const void *src[3] = {tau_mont, alpha_mont, beta_mont};
@@ -349,7 +343,7 @@ int bh_groth16_params_verify_step(bh_ctx *ctx, const bh_params *before, const bh
     for (int w = 0; w < 5; w++) {
       const int rc = bh_groth16_params_query(side[s], w, &qv[s][w], nullptr);
       if (rc) return rc;
-      if (!qv[s][w] || bases_group(qv[s][w]) != (w == 4 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
+      if (!qv[s][w] || qv[s][w]->group != (w == 4 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARG;
     }
     const int rc = bh_groth16_params_vk_ext(side[s], nullptr, nullptr, 0, &n_ic[s]);
     if (rc) return rc;

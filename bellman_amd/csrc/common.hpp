@@ -202,11 +202,6 @@ struct Context {
 
 }  // namespace bh
 
-namespace bh {
-void fft_tables_free(FftTables &t);   // fft.hip
-void fft_master_free(Context &c);
-}  // namespace bh
-
 struct bh_ctx {
   bh::Context c;
 };

@@ -48,6 +48,7 @@
 // assignment is XCD-aware: tiles that share 128-byte lines (the narrow tiles of the 2^21 / 2^22 plans) go to the
 // same XCD back to back, so the other half of a line is an L2 hit instead of a second HBM fetch.
 #include "common.hpp"
+#include "fft.hpp"
 #include "fft_plan.hpp"
 
 namespace bh {
@@ -956,6 +957,31 @@ static int acquire_tables(Context &c, uint32_t log_n, bool inverse, bool need_tw
   return rc;
 }
 
+// What the two launch drivers below share.  One kind of tables per size: the one-level kernel multiplies by whatever its
+// table pointers say, so every table a call needs has to be there (get_tables guarantees it; a null pointer here would be
+// a silently wrong transform).  dir: 0 forward, 1 inverse
+static bool tables_complete(const FftTables &tab, bool multi_pass, int mode, int dir) {
+  return !(tab.one_level && ((multi_pass && !tab.tw1[dir][0]) || (mode == BH_COSET_FFT && !tab.coset1) ||
+                             (mode == BH_ICOSET_FFT && !tab.icoset1)));
+}
+// the table pointers of pass `pass` of a transform
+static void pass_tables(NttPass &a, const FftTables &tab, const BTw *master, int mode, int dir, uint32_t pass, bool last) {
+  a.master = master;
+  a.tw_lo = tab.tw_lo[dir];
+  a.tw_hi = tab.tw_hi[dir];
+  const bool pre = (pass == 0 && mode == BH_COSET_FFT), post = (last && mode == BH_ICOSET_FFT);
+  a.pre_lo = pre ? tab.coset_lo : nullptr;
+  a.pre_hi = pre ? tab.coset_hi : nullptr;
+  a.post_lo = post ? tab.icoset_lo : nullptr;
+  a.post_hi = post ? tab.icoset_hi : nullptr;
+  // one-level tables (L >= 2): the inverse twiddle table of pass 0 carries the 1/n, so ifft has no scaling product
+  a.tw1 = (tab.one_level && !last) ? tab.tw1[dir][pass] : nullptr;
+  a.pre1 = (tab.one_level && pre) ? tab.coset1 : nullptr;
+  a.post1 = (tab.one_level && post) ? tab.icoset1 : nullptr;
+  a.post_const = (last && mode == BH_IFFT && !tab.one_level) ? tab.minv_dev : nullptr;
+  a.lb = tab.lb;
+}
+
 // data: device, 2^log_n Montgomery Fr, in place.  scratch: device, same size (ping-pong for the
 // digit-reversing last pass; may be null when log_n <= NTT_MAX_R).
 // `more`: up to two further vectors transformed in place by the same launch - only for single-pass sizes (no scratch
@@ -974,11 +1000,7 @@ static int ntt_run_batch(Context &c, fr_t *data, fr_t *scratch, uint32_t log_n, 
   TableUse use;   // the tables stay cached until this call's launches are enqueued
   int rc = acquire_tables(c, log_n, inverse, L > 1, mode == BH_COSET_FFT, mode == BH_ICOSET_FFT, st, &tab, &master, use);
   if (rc) return rc;
-  // one kind of tables per size: the one-level kernel multiplies by whatever its table pointers say, so every table
-  // this call needs has to be there (get_tables guarantees it; a null pointer here would be a silently wrong transform)
-  if (tab.one_level && ((L > 1 && !tab.tw1[inverse ? 1 : 0][0]) || (mode == BH_COSET_FFT && !tab.coset1) ||
-                        (mode == BH_ICOSET_FFT && !tab.icoset1)))
-    return BH_ERR_HIP;
+  if (!tables_complete(tab, L > 1, mode, inverse ? 1 : 0)) return BH_ERR_HIP;
   uint32_t s = 0;
   for (uint32_t p = 0; p < L; p++) {
     NttPass a = pass_geometry(log_n, r, L, p, s);
@@ -988,20 +1010,7 @@ static int ntt_run_batch(Context &c, fr_t *data, fr_t *scratch, uint32_t log_n, 
     a.in = (p == 0) ? data : scratch;
     a.out = (last) ? data : scratch;
     for (u32 y = 0; y < 2; y++) { a.in_y[y] = y < n_more ? more[y] : nullptr; a.out_y[y] = y < n_more ? more[y] : nullptr; }
-    a.master = master;
-    a.tw_lo = tab.tw_lo[inverse ? 1 : 0];
-    a.tw_hi = tab.tw_hi[inverse ? 1 : 0];
-    const bool pre = (p == 0 && mode == BH_COSET_FFT), post = (last && mode == BH_ICOSET_FFT);
-    a.pre_lo = pre ? tab.coset_lo : nullptr;
-    a.pre_hi = pre ? tab.coset_hi : nullptr;
-    a.post_lo = post ? tab.icoset_lo : nullptr;
-    a.post_hi = post ? tab.icoset_hi : nullptr;
-    // one-level tables (L >= 2): the inverse twiddle table of pass 0 carries the 1/n, so ifft has no scaling product
-    a.tw1 = (tab.one_level && !last) ? tab.tw1[inverse ? 1 : 0][p] : nullptr;
-    a.pre1 = (tab.one_level && pre) ? tab.coset1 : nullptr;
-    a.post1 = (tab.one_level && post) ? tab.icoset1 : nullptr;
-    a.post_const = (last && mode == BH_IFFT && !tab.one_level) ? tab.minv_dev : nullptr;
-    a.lb = tab.lb;
+    pass_tables(a, tab, master, mode, inverse ? 1 : 0, p, last);
     const u64 tiles = ((u64)1 << log_n) >> (r[p] + a.log_c);
     if (n_more && L != 1) return BH_ERR_INVALID_ARG;
     if (tab.one_level) hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3((u32)tiles, 1 + n_more), dim3(NttCfg<true>::TH), 0, st, a);
@@ -1092,27 +1101,13 @@ int ntt_run_many(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int 
   TableUse use;   // the tables stay cached until this call's launches are enqueued
   int rc = acquire_tables(c, log_n, inverse, log_n > (uint32_t)NTT_MAX_R, mode == BH_COSET_FFT, mode == BH_ICOSET_FFT, st, &tab, &master, use);
   if (rc) return rc;
-  if (tab.one_level && ((log_n > (uint32_t)NTT_MAX_R && !tab.tw1[dir][0]) || (mode == BH_COSET_FFT && !tab.coset1) ||
-                        (mode == BH_ICOSET_FFT && !tab.icoset1)))
-    return BH_ERR_HIP;   // (as ntt_run_batch: a null table would be a silently wrong transform)
+  if (!tables_complete(tab, log_n > (uint32_t)NTT_MAX_R, mode, dir)) return BH_ERR_HIP;
   for (const FftManyLaunch &l : fft_many_plan(log_n, k, stride, scratch_vectors, tab.one_level)) {
     NttPass a = pass_from_geo(l.geo);
     const bool last = l.geo.is_last;
     a.in = l.in_scratch ? scratch : data + l.first_vec * stride;
     a.out = l.out_scratch ? scratch : data + l.first_vec * stride;
-    a.master = master;
-    a.tw_lo = tab.tw_lo[dir];
-    a.tw_hi = tab.tw_hi[dir];
-    const bool pre = (l.pass == 0 && mode == BH_COSET_FFT), post = (last && mode == BH_ICOSET_FFT);
-    a.pre_lo = pre ? tab.coset_lo : nullptr;
-    a.pre_hi = pre ? tab.coset_hi : nullptr;
-    a.post_lo = post ? tab.icoset_lo : nullptr;
-    a.post_hi = post ? tab.icoset_hi : nullptr;
-    a.tw1 = (tab.one_level && !last) ? tab.tw1[dir][l.pass] : nullptr;
-    a.pre1 = (tab.one_level && pre) ? tab.coset1 : nullptr;
-    a.post1 = (tab.one_level && post) ? tab.icoset1 : nullptr;
-    a.post_const = (last && mode == BH_IFFT && !tab.one_level) ? tab.minv_dev : nullptr;
-    a.lb = tab.lb;
+    pass_tables(a, tab, master, mode, dir, l.pass, last);
     NttPassMany am;
     static_cast<NttPass &>(am) = a;
     am.mv.in_stride = l.in_stride; am.mv.out_stride = l.out_stride; am.mv.n_vec = (u32)l.n_vec; am.mv.log_v = l.log_v;
@@ -1138,7 +1133,7 @@ int h_poly_many_dev(Context &c, fr_t *a, fr_t *b, fr_t *cc, u64 stride, u64 k, u
   return ntt_run_many(c, a, stride, k, log_n, BH_ICOSET_FFT, scratch, scratch_vectors, st);
 }
 // k single-vector transforms / h blocks through the existing path (BH_FFT_MANY_SINGLE, and what the dispatch rule of
-// api.hip sends here): scratch is one vector
+// api_domain.hip sends here): scratch is one vector
 int ntt_run_each(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int mode, fr_t *scratch, hipStream_t st) {
   for (u64 j = 0; j < k; j++) {
     int rc = ntt_run(c, data + j * stride, scratch, log_n, mode, st);

@@ -30,11 +30,12 @@
 #include <thread>
 #include <vector>
 
-#include "msm_types.hpp"
+#include "msm_job.hpp"
+#include "points.hpp"
 
 namespace bh {
 
-// ---- job management / dispatch (used by api.hip) ------------------------------------------------
+// ---- job management / dispatch (used by api_msm.hip) ------------------------------------------------
 constexpr size_t JOB_PINNED_BYTES = 256 * 1024;   // >= W*c*sizeof(XYZZ<Fp2>) + flags for every plan
 
 MsmJobImpl *msm_job_new(Context *ctx, int group) {

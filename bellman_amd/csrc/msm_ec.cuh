@@ -13,6 +13,7 @@
 #include "host_fp.hpp"
 #include "msm_scalar.cuh"
 #include "msm_types.hpp"
+#include "points.hpp"
 
 namespace bh {
 
@@ -1046,7 +1047,7 @@ __global__ void __launch_bounds__(64) point_check_kernel(const Affine<F> *pts, u
 // a scalar can go to the same bucket set as digit 0 (one bucket reduction instead of W, no Horner
 // over windows).  One lane per base walks the rows: c doublings and one inversion per row.  Lane i reads record i of `src`
 // (src_stride bytes apart) and writes row j at dst + (j n + i) dst_stride: the table is built where and as it stays - at a
-// 128-byte stride for the big G1 tables (api.hip table_will_pad) - and the bytes between two records are never written.
+// 128-byte stride for the big G1 tables (api_bases.hip table_will_pad) - and the bytes between two records are never written.
 template <class F>
 __global__ void __launch_bounds__(128) window_table_kernel(const char *src, u32 src_stride, char *dst, u32 dst_stride, u64 n,
                                                            u32 c, u32 W) {
@@ -1422,7 +1423,7 @@ static int launch_reduce(hipStream_t st, const MsmPlan &p, const ReducePlan &rp,
 // (MsmJobImpl::resume) until it is started: plain values and raw device pointers.  The pointers all lie in the job's
 // workspace block (job.dev_allocs, returned to the pool when the job is waited for) - except `gather`, which points into the
 // base handle's memory: the registered vector, its 128-byte-stride copy or its window table.  The caller keeps the handle
-// until the wait, and bh_ctx_trim leaves automatic tables alone while a job is in flight (api.hip).
+// until the wait, and bh_ctx_trim leaves automatic tables alone while a job is in flight (api_context.hip).
 template <class M>
 struct AfterSort {
   MsmPlan p;

@@ -2,16 +2,18 @@
 // tests, the thirteen kernels of the one-key calls, the six key-aware ones of the calls over a key set, and the functions
 // that launch them.  Included by pairing.hip (the product) and by test_pairing_hooks.hip (the test library), which runs
 // every kernel on its own: tests/test_gpu_pairing_stages.py, tests/test_gpu_verify_keys_stages.py.
-// ONE translation unit per library may include this header: the kernels and the launch_* functions have external linkage
-// (the text is pairing.hip's, unchanged), so a second including unit in the same library would define them twice.  Another
-// unit of the same library that needs a launch function declares it (test_hooks.hip does, for bh_test_pairing).
+// ONE translation unit per library may include this header: the kernels and the launch_* functions other units call
+// (pairing_launch.hpp) have external linkage, so a second including unit in the same library would define them twice.
+// Another unit of the same library that needs one of those includes pairing_launch.hpp (ceremony.hip; test_hooks.hip
+// for bh_test_pairing).
 #pragma once
 #include <algorithm>
 
 #include "common.hpp"
 #include "final_exp.cuh"
 #include "fp12.cuh"
-#include "msm_types.hpp"
+#include "pairing_launch.hpp"
+#include "points.hpp"
 
 namespace bh {
 
@@ -490,7 +492,7 @@ int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int 
   return BH_OK;
 }
 int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
-                  const line_t *lines1 = nullptr, const u32 *qflags1 = nullptr, size_t n1 = 0) {
+                  const line_t *lines1, const u32 *qflags1, size_t n1) {
   if (!(n + n1)) return BH_OK;
   (void)hipGetLastError();
   hipLaunchKernelGGL(miller_kernel, dim3(blocks_of(n + n1, 64)), dim3(64), 0, st, p, lines, qflags, (u32)n, lines1, qflags1, f,
@@ -529,8 +531,8 @@ int launch_final_exp(hipStream_t st, const fp12_t *f, size_t n, fp12_t *out, u32
 // the column sums of one chunk: part[col * nb + block] by fr_colsum_kernel, then acc[col] += the column's nb partial sums
 // (part: ncol * COLSUM_BLOCKS values).  nb = 0: one block row per COLSUM_THREADS proofs, COLSUM_BLOCKS at the most - what
 // the batch verifier runs; any other nb <= COLSUM_BLOCKS is for the stage tests (tests/test_gpu_pairing_stages.py)
-int launch_colsum(hipStream_t st, const fr_t *z, const fr_t *inputs, size_t n_inputs, int fmt, size_t m, fr_t *part, fr_t *acc,
-                  u32 nb = 0) {
+static int launch_colsum(hipStream_t st, const fr_t *z, const fr_t *inputs, size_t n_inputs, int fmt, size_t m, fr_t *part, fr_t *acc,
+                         u32 nb = 0) {
   const size_t ncol = n_inputs + 1;
   if (!nb) nb = (u32)std::min<size_t>(COLSUM_BLOCKS, blocks_of(m, COLSUM_THREADS));
   (void)hipGetLastError();
@@ -540,7 +542,7 @@ int launch_colsum(hipStream_t st, const fr_t *z, const fr_t *inputs, size_t n_in
   return BH_OK;
 }
 // per proof, after miller3_kernel: f[j] *= f[m + j] * f[2 m + j] where the three pairs ran apart (separate), then f[j] *= *c
-int launch_fold3_const(hipStream_t st, fp12_t *f, const fp12_t *c, size_t m, bool separate) {
+static int launch_fold3_const(hipStream_t st, fp12_t *f, const fp12_t *c, size_t m, bool separate) {
   if (!m) return BH_OK;
   const dim3 g(blocks_of(m, 64)), blk(64);
   (void)hipGetLastError();
@@ -554,8 +556,8 @@ int launch_fold3_const(hipStream_t st, fp12_t *f, const fp12_t *c, size_t m, boo
 }
 
 // ---- several keys: `blocks` holds nblocks KeyBlock of the grouped chunk, `keys` the set's descriptors (both on the device)
-int launch_ic_accumulate_keys(hipStream_t st, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeyBlock *blocks,
-                              size_t nblocks, Affine<FpOps> *out) {
+static int launch_ic_accumulate_keys(hipStream_t st, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeyBlock *blocks,
+                                     size_t nblocks, Affine<FpOps> *out) {
   if (!nblocks) return BH_OK;
   (void)hipGetLastError();
   hipLaunchKernelGGL(ic_accumulate_keys_kernel, dim3((u32)nblocks), dim3(64), 0, st, inputs, fmt, keys, blocks, out);
@@ -563,9 +565,9 @@ int launch_ic_accumulate_keys(hipStream_t st, const fr_t *inputs, int fmt, const
   return BH_OK;
 }
 // f: 3 m values where the three pairs run apart (separate), else m
-int launch_miller3_keys(hipStream_t st, const Affine<FpOps> *a, const Affine<FpOps> *acc, const ProofRec *proofs,
-                        const line_t *blines, const u32 *bflags, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks,
-                        bool separate, fp12_t *f, size_t m) {
+static int launch_miller3_keys(hipStream_t st, const Affine<FpOps> *a, const Affine<FpOps> *acc, const ProofRec *proofs,
+                               const line_t *blines, const u32 *bflags, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks,
+                               bool separate, fp12_t *f, size_t m) {
   if (!nblocks) return BH_OK;
   (void)hipGetLastError();
   hipLaunchKernelGGL(miller3_keys_kernel, dim3((u32)nblocks, separate ? 3 : 1), dim3(64), 0, st, a, acc, proofs, blines, bflags,
@@ -574,8 +576,8 @@ int launch_miller3_keys(hipStream_t st, const Affine<FpOps> *a, const Affine<FpO
   return BH_OK;
 }
 // launch_fold3_const with the constant of every row's key
-int launch_fold3_const_keys(hipStream_t st, fp12_t *f, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks, size_t m,
-                            bool separate) {
+static int launch_fold3_const_keys(hipStream_t st, fp12_t *f, const KeyDesc *keys, const KeyBlock *blocks, size_t nblocks, size_t m,
+                                   bool separate) {
   if (!m || !nblocks) return BH_OK;
   const dim3 g(blocks_of(m, 64)), blk(64);
   (void)hipGetLastError();
@@ -590,8 +592,8 @@ int launch_fold3_const_keys(hipStream_t st, fp12_t *f, const KeyDesc *keys, cons
 // the column sums of one grouped chunk for every key of the set: one launch whatever n_keys is, then the finish step over
 // the set's total_cols columns (part: total_cols * COLSUM_BLOCKS values; acc: total_cols).  max_seg: the longest run of
 // the chunk; max_cols: the largest n_inputs + 1 of the set; nb as for launch_colsum
-int launch_colsum_keys(hipStream_t st, const fr_t *z, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeySeg *segs,
-                       size_t n_keys, size_t max_cols, size_t total_cols, size_t max_seg, fr_t *part, fr_t *acc, u32 nb = 0) {
+static int launch_colsum_keys(hipStream_t st, const fr_t *z, const fr_t *inputs, int fmt, const KeyDesc *keys, const KeySeg *segs,
+                              size_t n_keys, size_t max_cols, size_t total_cols, size_t max_seg, fr_t *part, fr_t *acc, u32 nb = 0) {
   if (!nb) nb = (u32)std::max<size_t>(1, std::min<size_t>(COLSUM_BLOCKS, blocks_of(max_seg, COLSUM_THREADS)));
   (void)hipGetLastError();
   hipLaunchKernelGGL(fr_colsum_keys_kernel, dim3((u32)max_cols, (u32)(n_keys * nb)), dim3(COLSUM_THREADS), 0, st, z, inputs, fmt,
@@ -600,14 +602,14 @@ int launch_colsum_keys(hipStream_t st, const fr_t *z, const fr_t *inputs, int fm
   BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
-int launch_g1_mul_keys(hipStream_t st, Affine<FpOps> *out, const KeyDesc *keys, const fr_t *acc, size_t n_keys) {
+static int launch_g1_mul_keys(hipStream_t st, Affine<FpOps> *out, const KeyDesc *keys, const fr_t *acc, size_t n_keys) {
   (void)hipGetLastError();
   hipLaunchKernelGGL(g1_mul_keys_kernel, dim3(blocks_of(n_keys, 64)), dim3(64), 0, st, out, keys, acc, (u32)n_keys);
   BH_HIP_CHECK(hipGetLastError());
   return BH_OK;
 }
 // p, f: 3 n_keys values, [which][key]
-int launch_miller_keys(hipStream_t st, const Affine<FpOps> *p, const KeyDesc *keys, size_t n_keys, fp12_t *f) {
+static int launch_miller_keys(hipStream_t st, const Affine<FpOps> *p, const KeyDesc *keys, size_t n_keys, fp12_t *f) {
   (void)hipGetLastError();
   hipLaunchKernelGGL(miller_keys_kernel, dim3(blocks_of(3 * n_keys, 64)), dim3(64), 0, st, p, keys, (u32)n_keys, f);
   BH_HIP_CHECK(hipGetLastError());

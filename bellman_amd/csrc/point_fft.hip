@@ -18,14 +18,10 @@
 // twiddles within a wavefront.  Identity, equal and opposite operands (zero padding, constant inputs) take
 // xyzz_add's own branches.
 #include "common.hpp"
+#include "fft.hpp"   // the Fr power tables and domain constants shared with the scalar transforms
+#include "point_ops.hpp"
 
 namespace bh {
-// fft.hip: the Fr power tables and domain constants shared with the scalar transforms
-int launch_gen_powers(fr_t *out, u64 n, const fr_t &g, const fr_t &scale, int mul_into, hipStream_t st);
-fr_t fr_domain_omega_host(uint32_t log_n);
-fr_t fr_from_u64_host(u64 v);
-fr_t zinv_host(uint32_t log_n);
-
 namespace {
 
 constexpr u32 PF_THREADS = 128;

@@ -5,12 +5,11 @@
 // c g^i of bh_bases_scale_powers are such a vector, built in front by launch_gen_powers (fft.hip).  Affine
 // out, one inversion per lane as everywhere; `out` may alias `in` (a lane reads its record before it writes it).
 #include "common.hpp"
+#include "fft.hpp"
 #include "glv.cuh"
+#include "point_ops.hpp"
 
 namespace bh {
-// fft.hip
-int launch_gen_powers(fr_t *out, u64 n, const fr_t &g, const fr_t &scale, int mul_into, hipStream_t st);
-
 namespace {
 
 // one wavefront per block: the G1 kernel is sized for one wave per SIMD, and 2^16 points are then one wave on every SIMD

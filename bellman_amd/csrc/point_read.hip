@@ -1,7 +1,7 @@
 // from_compressed / from_compressed_unchecked of bls12_381 on the device: the compressed Zcash encoding (48 bytes for G1,
 // 96 for G2: x big-endian, G2 c1 before c0, the flag bits compressed / infinity / sort in the top of byte 0) -> affine
 // Montgomery records plus a PointStatus word per point.  What Proof::read (groth16/src/lib.rs:47-99) does to the three
-// points of a proof; declared in msm_types.hpp, called from api.hip (bh_bases_read_compressed) and pairing.hip
+// points of a proof; declared in points.hpp, called from api_bases.hip (bh_bases_read_compressed) and pairing.hip
 // (bh_proofs_read, bh_groth16_batch_verify_compressed).
 //
 // One lane per point:
@@ -15,8 +15,8 @@
 // A lane whose point is already invalid or the identity takes no part in steps 2 and 3 (its lanes are masked off; the
 // loops are over compile-time constants and the same for every lane).
 #include "common.hpp"
-#include "msm_types.hpp"
 #include "point_read.cuh"
+#include "points.hpp"
 
 namespace bh {
 

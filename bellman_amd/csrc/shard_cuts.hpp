@@ -1,4 +1,4 @@
-// Where a multiexp over several contexts (bh_msm_sharded_async, api.hip) cuts its exponents; shared with the test
+// Where a multiexp over several contexts (bh_msm_sharded_async, api_msm.hip) cuts its exponents; shared with the test
 // library's hook (test_hooks.hip).
 #pragma once
 #include <stddef.h>

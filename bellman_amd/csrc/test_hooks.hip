@@ -7,6 +7,7 @@
 #include "final_exp.cuh"
 #include "fp12.cuh"
 #include "msm_ec.cuh"
+#include "pairing_launch.hpp"
 #include "point_read.cuh"
 #include "shard_cuts.hpp"
 #include "fft_plan.hpp"
@@ -260,10 +261,8 @@ void bh_test_point_mul_host(int group, void *r, const void *a, const void *k) {
 
 // ---- test hook: full pairings (tests/test_gpu_verifier.py, tests/test_verifier_cpu.py) ------------------------------
 namespace bh {
-// the shipped launch functions of csrc/pairing_kernels.cuh, which test_pairing_hooks.hip compiles into this library
-int launch_g2_lines(hipStream_t st, const void *q_dev, size_t stride_bytes, int negate, line_t *lines, u32 *flags, size_t n);
-int launch_miller(hipStream_t st, const Affine<FpOps> *p, const line_t *lines, const u32 *qflags, fp12_t *f, size_t n,
-                  const line_t *lines1, const u32 *qflags1, size_t n1);
+// (pairing_launch.hpp: the shipped launch functions of csrc/pairing_kernels.cuh, which test_pairing_hooks.hip compiles into
+// this library)
 // one pairing per lane; out = 12 canonical Fp (not Montgomery) in w-basis order w^0, w^1 (each c0 then c1 of Fp2), ...
 BH_HD void pairing_one(fp12_t &r, const Affine<FpOps> &p, const Affine<Fp2Ops> &q, const line_t *lines) {
   fp12_t f;

@@ -87,7 +87,7 @@ int bh_test_pairing_stage_shape(uint64_t out16[16]) {
   return BH_OK;
 }
 
-// host only: the shipped proof_status_error (csrc/msm_types.hpp) of a status word
+// host only: the shipped proof_status_error (csrc/points.hpp) of a status word
 int bh_test_proof_status_error(uint32_t word) { return proof_status_error(word); }
 
 int bh_test_pairing_lines_dev(bh_ctx *ctx, const void *records, size_t stride_bytes, int negate, size_t n, void *lines_out,

@@ -116,7 +116,7 @@ def test_large_host_scalar_multiexp_error_semantics(worker):
 
 
 def test_g1_window_table_at_128_byte_stride(worker):
-    """A G1 vector of 2^19 points with its window table built at a 128-byte record stride (api.hip
+    """A G1 vector of 2^19 points with its window table built at a 128-byte record stride (api_bases.hip
     bh_bases::table_stride; 16-bit and 20-bit rows): the multiexp over it == the classic 16-window plan over the dense
     vector == [sum s_i t_i]G, with full density, with a density map + skip, with a forced chunk length and with the
     LDS-accumulator variant of the kernel (every variant takes the record stride).  Then the error semantics of

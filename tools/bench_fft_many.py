@@ -1,5 +1,5 @@
 """k Fr transforms (and k h blocks) of one size: the k calls a caller can make today against the batched call
-(bh_fft_fr_many_dev, bh_h_poly_fr_many_dev_on), the measurement the dispatch rule of api.hip (fft_many_wins) is set from.
+(bh_fft_fr_many_dev, bh_h_poly_fr_many_dev_on), the measurement the dispatch rule of api_domain.hip (fft_many_wins) is set from.
 
 Method: host wall time from the first issue to a final stream synchronisation, min of REPS repetitions after one warm-up
 round, the three variants interleaved in one process (A B C A B C ...), the same device-resident inputs for every variant,

@@ -1,5 +1,5 @@
 """k multiexps over one base vector: k ordinary jobs issued together against the many-plan (bh_msm_many_*), the
-measurement the dispatch rule of api.hip (many_plan_wins) is set from.
+measurement the dispatch rule of api_msm.hip (many_plan_wins) is set from.
 
 Method: host wall time from the first issue to the last result, min of REPS repetitions, the three variants interleaved
 in one process (A B C A B C ...), the same registered bases (automatic window table where registration builds one) and
