@@ -270,10 +270,22 @@ BH_HD bool xyzz_madd(XYZZ<F> &acc, const Affine<F> &q) {
 // Only the accumulation uses it: with 26 instead of 24 argument registers per product the register-bound G1 kernels
 // that also call xyzz_madd (fixed_base_table_kernel 226, point_check_kernel 239 VGPRs) fell to one wave per SIMD.
 // Returns what xyzz_madd returns.
-template <class F>
+// INLINE_PRODUCTS: the six products and two squarings of the add path are the always-inline twins (ff.cuh fp_mul_hh_inl,
+// fp_sqr_h_inl) - the same fe_mul_hh / fe_sqr_h, so the same words.  msm_accumulate_kernel<FpOps, false> alone sets it:
+// its addition becomes one basic block without calls (profiles/accumulate_inline_ab.txt).  The doubling branch is rare
+// and keeps its calls.
+template <class F, bool INLINE_PRODUCTS = false>
 BH_HD bool xyzz_madd_sliced(XYZZ<F> &acc, const Affine<F> &q) {
   typedef typename F::T T;
   typedef typename F::H H;
+  auto mul_hh = [](T &r, const H &a, const H &b) {
+    if constexpr (INLINE_PRODUCTS) F::mul_hh_inl(r, a, b);
+    else F::mul_hh(r, a, b);
+  };
+  auto sqr_h = [](T &r, const H &a) {
+    if constexpr (INLINE_PRODUCTS) F::sqr_h_inl(r, a);
+    else F::sqr_h(r, a);
+  };
   if (xyzz_is_identity(acc)) {
     acc.x = q.x;
     acc.y = q.y;
@@ -285,11 +297,11 @@ BH_HD bool xyzz_madd_sliced(XYZZ<F> &acc, const Affine<F> &q) {
   H ha, hb, hzz, hzzz;
   F::slice(ha, q.x);
   F::slice(hzz, acc.zz);
-  F::mul_hh(p, ha, hzz);
+  mul_hh(p, ha, hzz);
   F::sub(p, p, acc.x);     // P = U2 - X1
   F::slice(ha, q.y);
   F::slice(hzzz, acc.zzz);
-  F::mul_hh(r, ha, hzzz);
+  mul_hh(r, ha, hzzz);
   F::sub(r, r, acc.y);     // R = S2 - Y1
   if (F::is_zero(p)) {
     if (F::is_zero(r)) {
@@ -300,16 +312,16 @@ BH_HD bool xyzz_madd_sliced(XYZZ<F> &acc, const Affine<F> &q) {
     return true;
   }
   F::slice(ha, p);
-  F::sqr_h(pp, ha);
+  sqr_h(pp, ha);
   F::slice(hb, pp);                   // PP, for its three products
-  F::mul_hh(ppp, ha, hb);             // p dead
+  mul_hh(ppp, ha, hb);                // p dead
   F::slice(ha, acc.x);
-  F::mul_hh(qq, ha, hb);              // Q = X1*PP
-  F::mul_hh(acc.zz, hzz, hb);         // ZZ3 = ZZ1*PP          (pp dead)
+  mul_hh(qq, ha, hb);                 // Q = X1*PP
+  mul_hh(acc.zz, hzz, hb);            // ZZ3 = ZZ1*PP          (pp dead)
   F::slice(hb, ppp);                  // PPP, for ZZZ3 and the tail
-  F::mul_hh(acc.zzz, hzzz, hb);       // ZZZ3 = ZZZ1*PPP
+  mul_hh(acc.zzz, hzzz, hb);          // ZZZ3 = ZZZ1*PPP
   F::slice(ha, r);                    // R, for its square and the tail
-  F::sqr_h(t, ha);
+  sqr_h(t, ha);
   F::sub(t, t, ppp);
   F::sub(t, t, qq);
   F::sub(t, t, qq);                   // X3 = R^2 - PPP - 2Q

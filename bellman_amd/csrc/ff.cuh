@@ -739,6 +739,20 @@ BH_HD fp_t fp_sqr_h_call(const fp_h &a) {
   return fp_sqr_hvec(u32x4{a.l[0], a.l[1], a.l[2], a.l[3]}, u32x4{a.l[4], a.l[5], a.l[6], a.l[7]},
                      u32x4{a.l[8], a.l[9], a.l[10], a.l[11]}, a.l[12]);
 }
+// The same two sliced products ALWAYS INLINE: for the mixed addition of the G1 bucket accumulation alone (ec.cuh
+// xyzz_madd_sliced<F, true>), whose eight calls per addition cost more in argument moves, forced waits and call sequences
+// than its one hot block costs in instruction fetch (profiles/accumulate_inline_ab.txt).  The same fe_mul_hh / fe_sqr_h,
+// the same words.
+BH_HD fp_t fp_mul_hh_inl(const fp_h &a, const fp_h &b) {
+  fp_t r;
+  fe_mul_hh<FpParams, false>(r, a.l, b.l);   // lazily reduced
+  return r;
+}
+BH_HD fp_t fp_sqr_h_inl(const fp_h &a) {
+  fp_t r;
+  fe_sqr_h<FpParams, false>(r, a.l);         // lazily reduced
+  return r;
+}
 
 // ---------------------------------------------------------------------------------------
 // Fp2
@@ -792,6 +806,8 @@ struct FpOps {
   BH_HD static void slice(H &h, const T &a) { fe_to_hform<FpParams>(h.l, a); }
   BH_HD static void mul_hh(T &r, const H &a, const H &b) { r = fp_mul_hh_call(a, b); }
   BH_HD static void sqr_h(T &r, const H &a) { r = fp_sqr_h_call(a); }
+  BH_HD static void mul_hh_inl(T &r, const H &a, const H &b) { r = fp_mul_hh_inl(a, b); }   // no call: the accumulation
+  BH_HD static void sqr_h_inl(T &r, const H &a) { r = fp_sqr_h_inl(a); }
   // r = a*b - c*d, inline like mul2_sub_tail; a and d arrive sliced, b and c are cut here (c as 2p - c)
   BH_HD static void mul2_sub_tail_h(T &r, const H &a, const T &b, const T &c, const H &d) {
     T nc;

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(128) void msm_accumulate_kernel(const u64 *pairs, c
       load_affine<F>(q, base_at((u32)e & 0x7fffffffu));
       if (aff_is_identity(q)) { saw_identity = true; continue; }
       if ((u32)e >> 31) F::neg(q.y, q.y);   // negative digit: add -P
-      if constexpr (SLICED_MADD) adds += xyzz_madd_sliced(acc, q) ? 1u : 0u;   // G1 in registers: every value cut once
+      if constexpr (SLICED_MADD) adds += xyzz_madd_sliced<F, true>(acc, q) ? 1u : 0u;   // G1 in registers: every value cut once, products inline
       else adds += xyzz_madd(acc, q) ? 1u : 0u;
     }
   }

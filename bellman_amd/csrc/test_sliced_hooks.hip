@@ -9,12 +9,12 @@ namespace bh {
 namespace slicedops {
 
 // flag word: bit 0 xyzz_madd returned true, bit 1 xyzz_madd_sliced did, bit 4 the base was the identity (skipped, as the
-// accumulation does: both results = a)
+// accumulation does: both results = a).  The sliced addition is the form msm_accumulate_kernel<FpOps, false> runs: products inline.
 BH_HD u32 one_case(XYZZ<FpOps> &ref, XYZZ<FpOps> &chk, const XYZZ<FpOps> &a, const Affine<FpOps> &q) {
   ref = a;
   chk = a;
   if (aff_is_identity(q)) return 16u;
-  return (xyzz_madd(ref, q) ? 1u : 0u) | (xyzz_madd_sliced(chk, q) ? 2u : 0u);
+  return (xyzz_madd(ref, q) ? 1u : 0u) | (xyzz_madd_sliced<FpOps, true>(chk, q) ? 2u : 0u);
 }
 
 __global__ __launch_bounds__(128) void madd_sliced_kernel(XYZZ<FpOps> *r, u32 *flags, const XYZZ<FpOps> *a, const Affine<FpOps> *q, u32 n) {
