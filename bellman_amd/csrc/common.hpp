@@ -17,6 +17,7 @@ struct bh_bases;
 #include "ec.cuh"
 #include "env_settings.hpp"
 #include "ff.cuh"
+#include "fft_tables_plan.hpp"
 
 namespace bh {
 
@@ -135,27 +136,33 @@ struct JobResources {
 struct alignas(16) BTw {
   u32 l[12];
 };
-// Per-size FFT tables (fft.hip), all in B form and two-level: entry e of a virtual n-entry table is
-// hi[e >> lb] * lo[e & (2^lb - 1)].  [0] forward, [1] inverse.
+// Per-size FFT tables (fft.hip).  A size runs on ONE kind of tables (fft_tables_plan.hpp FftTableKind), a table per role
+// (FftTableRole; what each holds: fft.hip FFT_ROLE_SPECS):
+//   two[role][0 lo / 1 hi]  B form; entry e of a virtual n-entry table is hi[e >> lb] * lo[e & (2^lb - 1)]
+//   one[role][pass]         [r4] one-level tables in tile order (2^12 .. 2^24 points), n entries each: a twiddle role has one
+//                           per non-last pass, a coset role only [0].  [r5] An entry is the 32-byte Montgomery element (the
+//                           pointers are typed BTw* for the two-level tables they sit beside).
 struct FftTables {
-  bool init = false;
+  uint32_t kind = FFT_TABLES_NONE;
   uint32_t lb = 0;
-  BTw *tw_lo[2] = {nullptr, nullptr}, *tw_hi[2] = {nullptr, nullptr};   // omega_n^(+-e): inter-pass twiddles
-  BTw *coset_lo = nullptr, *coset_hi = nullptr;                           // 7^i
-  BTw *icoset_lo = nullptr, *icoset_hi = nullptr;                         // 7^-i / n
-  fr_t minv;                                                              // n^-1 (Montgomery)
-  fr_t zinv;                                                              // (7^n - 1)^-1: divide_by_z_on_coset
-  BTw *minv_dev = nullptr;                                                // ... as a one-entry table
-  // [r4] one-level tables in tile order (fft.hip; 2^12 .. 2^24 points): inter-pass twiddles per direction and non-last
-  // pass - the inverse direction's first one carries the 1/n -, 7^i and 7^-i.  n entries each; [r5] an entry is the
-  // 32-byte Montgomery element (the pointers are typed BTw* for the two-level tables they sit beside).
-  bool one_level = false, one_level_failed = false;
-  BTw *tw1[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  BTw *coset1 = nullptr, *icoset1 = nullptr;
+  BTw *one[FFT_ROLES][2] = {}, *two[FFT_ROLES][2] = {};
+  fr_t minv;                 // n^-1 (Montgomery)
+  fr_t zinv;                 // (7^n - 1)^-1: divide_by_z_on_coset
+  BTw *minv_dev = nullptr;   // ... as a one-entry table: set once the size is cached
   // [r5] what this size holds in device memory and when it was last used: the cache is bounded (Context::fft_table_budget),
   // least recently used sizes go first
   size_t bytes = 0;
   uint64_t last_use = 0;
+  // what the policy sees of this size: a role is held when the first table of it in the size's kind is there (a role's
+  // tables are set together or not at all)
+  FftHoldings held() const {
+    FftHoldings h;
+    h.kind = kind;
+    h.bytes = bytes;
+    for (uint32_t role = 0; role < FFT_ROLES; role++)
+      if ((kind == FFT_TABLES_ONE_LEVEL ? one : two)[role][0]) h.roles |= 1u << role;
+    return h;
+  }
 };
 
 struct Context {
@@ -165,10 +172,10 @@ struct Context {
   std::mutex fft_mu;
   std::map<uint32_t, FftTables> fft_tables;  // keyed by log_n
   BTw *fft_master[2] = {nullptr, nullptr};   // omega_2048^(+-i), i < 1024: in-tile twiddles of every pass
-  // [r5] The per-size tables are a cache with a budget (bh_ctx_set_limits; default an eighth of the device's memory): a
-  // size whose complete one-level set would not fit runs on the small two-level tables, and building a table that does
-  // not fit beside the others first drops the least recently used OTHER sizes.  Dropping needs the tables idle: a transform
-  // holds fft_use_mu shared from get_tables to its last launch, the evictor takes it exclusively and synchronises the device.
+  // [r5] The per-size tables are a cache with a budget (bh_ctx_set_limits; default an eighth of the device's memory).  Which
+  // kind of tables a size gets and which OTHER sizes are dropped to make room: fft_tables_plan.hpp.  Dropping needs the tables
+  // idle: a transform holds fft_use_mu shared from get_tables to its last launch, the evictor takes it exclusively and
+  // synchronises the device.
   size_t fft_table_bytes = 0, fft_table_budget = 0;
   uint64_t fft_tick = 0;
   std::shared_mutex fft_use_mu;

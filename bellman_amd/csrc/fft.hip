@@ -719,12 +719,13 @@ static int make_btw_table(BTw **out, u64 count, const fr_t &g, const fr_t &scale
 }
 
 void fft_tables_free(FftTables &t) {
-  BTw **all[] = {&t.tw_lo[0], &t.tw_lo[1], &t.tw_hi[0], &t.tw_hi[1], &t.coset_lo, &t.coset_hi, &t.icoset_lo, &t.icoset_hi,
-                 &t.minv_dev, &t.tw1[0][0], &t.tw1[0][1], &t.tw1[1][0], &t.tw1[1][1], &t.coset1, &t.icoset1};
-  for (BTw **p : all) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
+  auto drop = [](BTw *&p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  };
+  for (uint32_t role = 0; role < FFT_ROLES; role++)
+    for (int i = 0; i < 2; i++) { drop(t.one[role][i]); drop(t.two[role][i]); }
+  drop(t.minv_dev);
 }
 void fft_master_free(Context &c) {
   for (int d = 0; d < 2; d++) {
@@ -747,9 +748,75 @@ static NttPass pass_geometry(uint32_t log_n, const uint32_t *r, uint32_t L, uint
 
 // internal return code of get_tables: `*evict_need` bytes of OTHER sizes' tables have to go first (fft_evict), then call again
 constexpr int BH_FFT_EVICT = -1000;
-// the complete one-level set of a size: an inter-pass twiddle table per non-last pass and direction, 7^i, 7^-i
-static size_t one_level_set_bytes(uint32_t log_n, uint32_t L) { return (size_t)(2 * (L - 1) + 2) * ((size_t)NTT_ONE_STRIDE << log_n); }
+static_assert(FFT_ONE_LEVEL_ENTRY_BYTES == (size_t)NTT_ONE_STRIDE && FFT_TWO_LEVEL_ENTRY_BYTES == sizeof(BTw), "fft_tables_plan.hpp counts these entries");
 
+// What the tables of a role hold (in FftTableRole order): scale * base^i, i < n.  base is omega_n or 7 (ff's
+// MULTIPLICATIVE_GENERATOR), inverted for the inverse roles.  The 1/n of the inverse transforms rides in a table, once per kind:
+//   one-level  in the inverse twiddle table of pass 0, so that ifft and icoset_fft have no scaling product
+//   two-level  in the `lo` table of the inverse coset pair (7^-i / n); ifft multiplies by the one-entry table minv_dev,
+//              which nothing else reads
+// tile: the order of a one-level role's entries - entry t * 2048 + e belongs to element e of tile t of its pass
+// (gen_tile_table_kernel): 0 the store order of every non-last pass (a table each), 1 the load order of pass 0, 2 the store
+// order of the last pass
+struct FftRoleSpec {
+  bool base_seven, inverse;
+  int tile;
+  bool minv_one_level, minv_two_level;
+};
+static const FftRoleSpec FFT_ROLE_SPECS[FFT_ROLES] = {
+    {false, false, 0, false, false},   // forward twiddles omega_n^e
+    {false, true, 0, true, false},     // inverse twiddles omega_n^-e
+    {true, false, 1, false, false},    // coset 7^i
+    {true, true, 2, false, true},      // inverse coset 7^-i
+};
+
+// allocates and fills a B-form table; what was allocated goes to `fresh` (the caller frees it when its call fails)
+static int make_fresh(std::vector<BTw *> &fresh, BTw **dst, u64 count, const fr_t &base, const fr_t &scale, hipStream_t st) {
+  BTw *p = nullptr;
+  int rc = make_btw_table(&p, count, base, scale, st);
+  if (p) fresh.push_back(p);
+  if (rc == BH_OK) *dst = p;
+  return rc;
+}
+// builds the tables of `roles` in `kind` into t (a copy the caller discards on failure)
+static int build_role_tables(FftTables &t, uint32_t kind, uint32_t roles, uint32_t log_n, std::vector<BTw *> &fresh, hipStream_t st) {
+  fr_t one;
+  fe_one(one);
+  uint32_t pr[3] = {0, 0, 0}, pL = 1;
+  plan_passes(log_n, pr, &pL);
+  const u64 n = (u64)1 << log_n, n_lo = (u64)1 << t.lb, n_hi = n >> t.lb;
+  for (uint32_t role = 0; role < FFT_ROLES; role++) {
+    if (!(roles >> role & 1)) continue;
+    const FftRoleSpec &spec = FFT_ROLE_SPECS[role];
+    fr_t base = spec.base_seven ? fr_from_u64_host(7) : fr_domain_omega_host(log_n);
+    if (spec.inverse) fe_inv(base, base);
+    if (kind == FFT_TABLES_TWO_LEVEL) {
+      BTw *lo = nullptr, *hi = nullptr;
+      int rc = make_fresh(fresh, &lo, n_lo, base, spec.minv_two_level ? t.minv : one, st);
+      if (rc == BH_OK) rc = make_fresh(fresh, &hi, n_hi, fr_pow_u64_host(base, n_lo), one, st);
+      if (rc) return rc;
+      t.two[role][0] = lo; t.two[role][1] = hi;   // a pair is set together or not at all
+      continue;
+    }
+    const uint32_t p0 = spec.tile == 2 ? pL - 1 : 0, p1 = spec.tile == 0 ? pL - 1 : p0 + 1;   // the passes with a table
+    uint32_t s_bits = 0;
+    for (uint32_t p = 0; p < p0; p++) s_bits += pr[p];
+    for (uint32_t p = p0; p < p1; p++) {
+      BTw *tab = nullptr;
+      if (hipMalloc((void **)&tab, FFT_ONE_LEVEL_ENTRY_BYTES << log_n) != hipSuccess) return BH_ERR_HIP;
+      fresh.push_back(tab);
+      const NttPass geo = pass_geometry(log_n, pr, pL, p, s_bits);
+      hipLaunchKernelGGL(gen_tile_table_kernel, dim3((u32)(n >> NTT_LOG_TILE)), dim3(256), 0, st, tab, geo,
+                         make_pow_table(base, (spec.minv_one_level && p == 0) ? t.minv : one), spec.tile);
+      if (hipGetLastError() != hipSuccess) return BH_ERR_HIP;
+      t.one[role][p - p0] = tab;
+      s_bits += pr[p];
+    }
+  }
+  return BH_OK;
+}
+
+// Executes what the cache's policy (fft_tables_plan.hpp) decides for this call.
 static int get_tables(Context &c, uint32_t log_n, bool inverse, bool need_tw, bool need_coset, bool need_icoset,
                       hipStream_t st, FftTables *out, const BTw **master, size_t *evict_need) {
   std::lock_guard<std::mutex> g(c.fft_mu);
@@ -758,173 +825,85 @@ static int get_tables(Context &c, uint32_t log_n, bool inverse, bool need_tw, bo
   const int dir = inverse ? 1 : 0;
   auto it = c.fft_tables.find(log_n);
   FftTables t = it != c.fft_tables.end() ? it->second : FftTables();
-  const u64 n = (u64)1 << log_n;
+  const FftHoldings held = t.held();
   uint32_t pr[3] = {0, 0, 0}, pL = 1;
   plan_passes(log_n, pr, &pL);
-  // One-level tables (n entries each: 0.13 GB at 2^22, 0.5 GB at 2^24) where the size's COMPLETE set fits the cache's
-  // budget - so that dropping the other sizes always makes room for whichever of its tables is asked for next, and the
-  // kind of tables a size uses never changes while it is cached (the inverse twiddle table carries the 1/n: the two kinds
-  // are never mixed within a size).  A size that holds two-level tables (over budget, a failed allocation) keeps them.
-  const bool has_two_level = t.tw_lo[0] || t.tw_lo[1] || t.coset_lo || t.icoset_lo;
-  bool one_level = env().fft_one_level && log_n >= 12 && log_n <= 24 && !t.one_level_failed && !has_two_level &&
-                   (t.one_level || one_level_set_bytes(log_n, pL) <= c.fft_table_budget);
-  const size_t entry_bytes = (size_t)NTT_ONE_STRIDE << log_n;
-  const size_t others = c.fft_table_bytes - (it != c.fft_tables.end() ? it->second.bytes : 0);
-  if (one_level) {
-    size_t need = 0;
-    if (need_tw && !t.tw1[dir][0]) need += (size_t)(pL - 1) * entry_bytes;
-    if (need_coset && !t.coset1) need += entry_bytes;
-    if (need_icoset && !t.icoset1) need += entry_bytes;
-    if (need && c.fft_table_bytes + need > c.fft_table_budget) {
-      if (others) { *evict_need = need; return BH_FFT_EVICT; }   // (nothing built yet: nothing to undo)
-      if (!t.one_level) one_level = false;   // the budget was lowered under this call: two-level tables
-      // (a size that already runs on one-level tables completes its set: at most its own set over the new budget)
-    }
-  }
+  FftTableDecision d = fft_tables_decide(held, log_n, pL, dir, need_tw, need_coset, need_icoset, c.fft_table_bytes, c.fft_table_budget,
+                                         env().fft_one_level);
+  if (d.evict_need) { *evict_need = d.evict_need; return BH_FFT_EVICT; }
   // Everything new is built into locals and PUBLISHED into the context only after every allocation and launch of
   // this call succeeded (and the generating stream drained): a failed hipMalloc / launch leaves the cache exactly as
   // it was, so a retry regenerates instead of running a kernel with half a table pair (null *_hi pointer).
   std::vector<BTw *> fresh;   // freed on failure
-  size_t fresh_bytes = 0;
   auto fail = [&](int rc) {
     (void)hipStreamSynchronize(st);
     for (BTw *p : fresh) (void)hipFree(p);
-    return rc;
-  };
-  auto make = [&](BTw **dst, u64 count, const fr_t &base, const fr_t &scale) -> int {
-    BTw *p = nullptr;
-    int rc = make_btw_table(&p, count, base, scale, st);
-    if (p) { fresh.push_back(p); fresh_bytes += count * sizeof(BTw); }
-    if (rc == BH_OK) *dst = p;
     return rc;
   };
   BTw *new_master = nullptr;
   if (!c.fft_master[dir]) {   // the in-tile twiddles (96 KiB, shared by every size: not part of the budget)
     fr_t w = fr_domain_omega_host(NTT_LOG_TILE);
     if (inverse) fe_inv(w, w);
-    int rc = make(&new_master, 1024, w, one);
+    int rc = make_fresh(fresh, &new_master, 1024, w, one, st);
     if (rc) return fail(rc);
-    fresh_bytes -= 1024 * sizeof(BTw);
   }
-  if (!t.init) {
-    t.lb = (log_n + 1) / 2;
-    fr_t nn = fr_from_u64_host(n);
+  if (!t.minv_dev) {
+    t.lb = fft_two_level_low_bits(log_n);
+    fr_t nn = fr_from_u64_host((u64)1 << log_n);
     fe_inv(t.minv, nn);
     t.zinv = zinv_host(log_n);   // ~800 host field products: computed once per domain size, not per proof
-    int rc = make(&t.minv_dev, 1, one, t.minv);   // the single entry 1/n
+    int rc = make_fresh(fresh, &t.minv_dev, 1, one, t.minv, st);   // the single entry 1/n
     if (rc) return fail(rc);
-    t.init = true;
   }
-  if (one_level) {
-    const size_t mark = fresh.size(), mark_bytes = fresh_bytes;
-    FftTables t1 = t;
-    bool ok = true;
-    // entry t * 2048 + e of a table belongs to element e of tile t of its pass (gen_tile_table_kernel)
-    auto tile_table = [&](BTw **dst, uint32_t p, uint32_t s_bits, int kind, const fr_t &base, const fr_t &scale) {
-      BTw *tab_p = nullptr;
-      if (hipMalloc((void **)&tab_p, entry_bytes) != hipSuccess) return false;
-      fresh.push_back(tab_p);
-      fresh_bytes += entry_bytes;
-      const NttPass geo = pass_geometry(log_n, pr, pL, p, s_bits);
-      hipLaunchKernelGGL(gen_tile_table_kernel, dim3((u32)(n >> NTT_LOG_TILE)), dim3(256), 0, st, tab_p, geo,
-                         make_pow_table(base, scale), kind);
-      if (hipGetLastError() != hipSuccess) return false;
-      *dst = tab_p;
-      return true;
-    };
-    if (need_tw && !t1.tw1[dir][0]) {
-      fr_t w = fr_domain_omega_host(log_n);
-      if (inverse) fe_inv(w, w);
-      uint32_t s_bits = 0;
-      for (uint32_t p = 0; p + 1 < pL && ok; p++) {
-        ok = tile_table(&t1.tw1[dir][p], p, s_bits, 0, w, (inverse && p == 0) ? t.minv : one);   // the 1/n of ifft / icoset_fft rides here
-        s_bits += pr[p];
-      }
+  const size_t mark = fresh.size();
+  FftTables built = t;
+  int rc = build_role_tables(built, d.kind, d.roles, log_n, fresh, st);
+  if (rc && d.kind == FFT_TABLES_ONE_LEVEL) {
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+    const FftBuildFailure f = fft_tables_build_failed(held, c.fft_table_bytes - held.bytes);
+    if (f != FFT_FALL_BACK_TWO_LEVEL) {
+      for (BTw *p : fresh) (void)hipFree(p);
+      if (f == FFT_FAIL) return BH_ERR_HIP;
+      *evict_need = FFT_EVICT_ALL;
+      return BH_FFT_EVICT;
     }
-    if (ok && need_coset && !t1.coset1) ok = tile_table(&t1.coset1, 0, 0, 1, fr_from_u64_host(7), one);
-    if (ok && need_icoset && !t1.icoset1) {
-      fr_t ginv;
-      fe_inv(ginv, fr_from_u64_host(7));
-      uint32_t s_last = 0;
-      for (uint32_t p = 0; p + 1 < pL; p++) s_last += pr[p];
-      ok = tile_table(&t1.icoset1, pL - 1, s_last, 2, ginv, one);
-    }
-    // (the size counts as running on one-level tables only once it HOLDS one: a call that built none - a cached 1/Z, a
-    // single-pass request - must not let later calls skip the budget gate above)
-    if (ok) { t = t1; t.one_level = t.one_level || t1.tw1[0][0] || t1.tw1[1][0] || t1.coset1 || t1.icoset1; }
-    else {
-      (void)hipStreamSynchronize(st);
-      (void)hipGetLastError();
-      if (t.one_level || others) {
-        // The size already runs on one-level tables (its inverse twiddles carry the 1/n): it must not fall back to the
-        // two-level kind half way (a forward call whose allocation failed after an inverse call had built its
-        // tables ran the one-level kernel with null table pointers) - make room by dropping the other sizes, and if
-        // there is nothing to drop the call fails.  A size without tables yet also tries that before it gives up.
-        for (BTw *p : fresh) (void)hipFree(p);
-        if (others) { *evict_need = (size_t)-1; return BH_FFT_EVICT; }
-        return BH_ERR_HIP;
-      }
-      for (size_t i = mark; i < fresh.size(); i++) (void)hipFree(fresh[i]);
-      fresh.resize(mark);
-      fresh_bytes = mark_bytes;
-      t.one_level_failed = true;   // this size stays on the two-level tables for good
-      one_level = false;
-    }
+    for (size_t i = mark; i < fresh.size(); i++) (void)hipFree(fresh[i]);
+    fresh.resize(mark);
+    d.kind = FFT_TABLES_TWO_LEVEL;
+    d.bytes = fft_tables_build_bytes(held, d.kind, d.roles, log_n, pL);
+    built = t;
+    rc = build_role_tables(built, d.kind, d.roles, log_n, fresh, st);
   }
-  const u64 n_lo = (u64)1 << t.lb, n_hi = (u64)1 << (log_n - t.lb);
-  auto two_level = [&](BTw **lo, BTw **hi, const fr_t &base, const fr_t &scale) -> int {
-    BTw *l = nullptr, *h = nullptr;
-    int rc = make(&l, n_lo, base, scale);
-    if (rc) return rc;
-    const fr_t step = fr_pow_u64_host(base, n_lo);
-    rc = make(&h, n_hi, step, one);
-    if (rc) return rc;
-    *lo = l; *hi = h;   // a pair is set together or not at all
-    return BH_OK;
-  };
-  if (!one_level && need_tw && !t.tw_lo[dir]) {
-    fr_t w = fr_domain_omega_host(log_n);
-    if (inverse) fe_inv(w, w);
-    int rc = two_level(&t.tw_lo[dir], &t.tw_hi[dir], w, one);
-    if (rc) return fail(rc);
-  }
-  if (!one_level && need_coset && !t.coset_lo) {
-    int rc = two_level(&t.coset_lo, &t.coset_hi, fr_from_u64_host(7), one);   // MULTIPLICATIVE_GENERATOR
-    if (rc) return fail(rc);
-  }
-  if (!one_level && need_icoset && !t.icoset_lo) {
-    fr_t ginv;
-    fe_inv(ginv, fr_from_u64_host(7));
-    int rc = two_level(&t.icoset_lo, &t.icoset_hi, ginv, t.minv);   // 7^-i / n
-    if (rc) return fail(rc);
-  }
+  if (rc) return fail(rc);
+  t = built;
+  if (d.roles) t.kind = d.kind;   // (only a size that HOLDS a table has a kind: fft_tables_plan.hpp)
   // tables are generated on `st`; later users may be on other streams
   if (!fresh.empty() && hipStreamSynchronize(st) != hipSuccess) return fail(BH_ERR_HIP);
   if (new_master) c.fft_master[dir] = new_master;
-  t.bytes += fresh_bytes;
+  t.bytes += d.bytes;
   t.last_use = ++c.fft_tick;
-  c.fft_table_bytes += fresh_bytes;
+  c.fft_table_bytes += d.bytes;
   c.fft_tables[log_n] = t;
   *out = t;
   *master = c.fft_master[dir];
   return BH_OK;
 }
 
-// drops the least recently used sizes other than `keep_log_n` until `need` more bytes fit the budget ((size_t)-1: all of
+// drops the least recently used sizes other than `keep_log_n` until `need` more bytes fit the budget (FFT_EVICT_ALL: all of
 // them).  The caller holds fft_use_mu EXCLUSIVELY: no transform is between its get_tables and its last launch; the device is
 // drained before a free.
 static void fft_evict_locked(Context &c, uint32_t keep_log_n, size_t need) {
   (void)hipDeviceSynchronize();
   std::lock_guard<std::mutex> g(c.fft_mu);
-  for (;;) {
-    if (need != (size_t)-1 && c.fft_table_bytes + need <= c.fft_table_budget) break;
-    auto victim = c.fft_tables.end();
-    for (auto i = c.fft_tables.begin(); i != c.fft_tables.end(); ++i)
-      if (i->first != keep_log_n && i->second.bytes && (victim == c.fft_tables.end() || i->second.last_use < victim->second.last_use)) victim = i;
-    if (victim == c.fft_tables.end()) break;
+  std::vector<FftCacheEntry> sizes;
+  for (auto &kv : c.fft_tables) sizes.push_back({kv.first, kv.second.bytes, kv.second.last_use});
+  for (int v; (v = fft_evict_victim(sizes.data(), sizes.size(), keep_log_n, c.fft_table_bytes, need, c.fft_table_budget)) >= 0;) {
+    auto victim = c.fft_tables.find(sizes[v].log_n);
     c.fft_table_bytes -= victim->second.bytes;
     fft_tables_free(victim->second);
     c.fft_tables.erase(victim);
+    sizes[v].bytes = 0;   // (gone: holds nothing)
   }
 }
 // What a transform holds on the table cache from get_tables to its last launch: the use lock shared - or, after an eviction,
@@ -961,24 +940,23 @@ static int acquire_tables(Context &c, uint32_t log_n, bool inverse, bool need_tw
 // table pointers say, so every table a call needs has to be there (get_tables guarantees it; a null pointer here would be
 // a silently wrong transform).  dir: 0 forward, 1 inverse
 static bool tables_complete(const FftTables &tab, bool multi_pass, int mode, int dir) {
-  return !(tab.one_level && ((multi_pass && !tab.tw1[dir][0]) || (mode == BH_COSET_FFT && !tab.coset1) ||
-                             (mode == BH_ICOSET_FFT && !tab.icoset1)));
+  return !(fft_roles_needed(dir, multi_pass, mode == BH_COSET_FFT, mode == BH_ICOSET_FFT) & ~tab.held().roles);
 }
-// the table pointers of pass `pass` of a transform
+// the table pointers of pass `pass` of a transform (a size holds one kind: the other kind's pointers are null; where the
+// 1/n comes from: FFT_ROLE_SPECS)
 static void pass_tables(NttPass &a, const FftTables &tab, const BTw *master, int mode, int dir, uint32_t pass, bool last) {
   a.master = master;
-  a.tw_lo = tab.tw_lo[dir];
-  a.tw_hi = tab.tw_hi[dir];
+  a.tw_lo = tab.two[FFT_ROLE_TW_FWD + dir][0];
+  a.tw_hi = tab.two[FFT_ROLE_TW_FWD + dir][1];
   const bool pre = (pass == 0 && mode == BH_COSET_FFT), post = (last && mode == BH_ICOSET_FFT);
-  a.pre_lo = pre ? tab.coset_lo : nullptr;
-  a.pre_hi = pre ? tab.coset_hi : nullptr;
-  a.post_lo = post ? tab.icoset_lo : nullptr;
-  a.post_hi = post ? tab.icoset_hi : nullptr;
-  // one-level tables (L >= 2): the inverse twiddle table of pass 0 carries the 1/n, so ifft has no scaling product
-  a.tw1 = (tab.one_level && !last) ? tab.tw1[dir][pass] : nullptr;
-  a.pre1 = (tab.one_level && pre) ? tab.coset1 : nullptr;
-  a.post1 = (tab.one_level && post) ? tab.icoset1 : nullptr;
-  a.post_const = (last && mode == BH_IFFT && !tab.one_level) ? tab.minv_dev : nullptr;
+  a.pre_lo = pre ? tab.two[FFT_ROLE_COSET][0] : nullptr;
+  a.pre_hi = pre ? tab.two[FFT_ROLE_COSET][1] : nullptr;
+  a.post_lo = post ? tab.two[FFT_ROLE_ICOSET][0] : nullptr;
+  a.post_hi = post ? tab.two[FFT_ROLE_ICOSET][1] : nullptr;
+  a.tw1 = !last ? tab.one[FFT_ROLE_TW_FWD + dir][pass] : nullptr;
+  a.pre1 = pre ? tab.one[FFT_ROLE_COSET][0] : nullptr;
+  a.post1 = post ? tab.one[FFT_ROLE_ICOSET][0] : nullptr;
+  a.post_const = (last && mode == BH_IFFT && tab.kind != FFT_TABLES_ONE_LEVEL) ? tab.minv_dev : nullptr;
   a.lb = tab.lb;
 }
 
@@ -1013,7 +991,7 @@ static int ntt_run_batch(Context &c, fr_t *data, fr_t *scratch, uint32_t log_n, 
     pass_tables(a, tab, master, mode, inverse ? 1 : 0, p, last);
     const u64 tiles = ((u64)1 << log_n) >> (r[p] + a.log_c);
     if (n_more && L != 1) return BH_ERR_INVALID_ARG;
-    if (tab.one_level) hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3((u32)tiles, 1 + n_more), dim3(NttCfg<true>::TH), 0, st, a);
+    if (tab.kind == FFT_TABLES_ONE_LEVEL) hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3((u32)tiles, 1 + n_more), dim3(NttCfg<true>::TH), 0, st, a);
     else hipLaunchKernelGGL(ntt_pass_kernel<false>, dim3((u32)tiles, 1 + n_more), dim3(NttCfg<false>::TH), 0, st, a);
     BH_HIP_CHECK(hipGetLastError());
     s += r[p];
@@ -1102,7 +1080,7 @@ int ntt_run_many(Context &c, fr_t *data, u64 stride, u64 k, uint32_t log_n, int 
   int rc = acquire_tables(c, log_n, inverse, log_n > (uint32_t)NTT_MAX_R, mode == BH_COSET_FFT, mode == BH_ICOSET_FFT, st, &tab, &master, use);
   if (rc) return rc;
   if (!tables_complete(tab, log_n > (uint32_t)NTT_MAX_R, mode, dir)) return BH_ERR_HIP;
-  for (const FftManyLaunch &l : fft_many_plan(log_n, k, stride, scratch_vectors, tab.one_level)) {
+  for (const FftManyLaunch &l : fft_many_plan(log_n, k, stride, scratch_vectors, tab.kind == FFT_TABLES_ONE_LEVEL)) {
     NttPass a = pass_from_geo(l.geo);
     const bool last = l.geo.is_last;
     a.in = l.in_scratch ? scratch : data + l.first_vec * stride;

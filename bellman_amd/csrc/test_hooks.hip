@@ -11,6 +11,7 @@
 #include "point_read.cuh"
 #include "shard_cuts.hpp"
 #include "fft_plan.hpp"
+#include "fft_tables_plan.hpp"
 #include "r1cs_dev.hpp"
 
 namespace bh {
@@ -46,6 +47,34 @@ int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t 
     memcpy(out + 20 * i, w, sizeof w);
   }
   return (int)plan.size();
+}
+
+// ---- test hook: the rules of the FFT table cache (host only; tests/test_fft_table_cache_cpu.py) ---------------------------
+int bh_test_fft_table_policy(int rule, const uint64_t *in, size_t n_in, uint64_t *out) {
+  if (!in || !out) return BH_ERR_INVALID_ARG;
+  bh::FftHoldings h;
+  if (rule == 0 || rule == 1) {
+    if (n_in != (rule == 0 ? 11u : 4u)) return BH_ERR_INVALID_ARG;
+    h.kind = (uint32_t)in[0]; h.roles = (uint32_t)in[1]; h.bytes = (size_t)in[2];
+  }
+  if (rule == 0) {
+    if (in[3] >= 32) return BH_ERR_INVALID_ARG;
+    uint32_t r[3] = {0, 0, 0}, L = 1;
+    bh::plan_passes((uint32_t)in[3], r, &L);
+    const bh::FftTableDecision d = bh::fft_tables_decide(h, (uint32_t)in[3], L, (int)in[4], in[5] != 0, in[6] != 0, in[7] != 0, (size_t)in[8],
+                                                         (size_t)in[9], in[10] != 0);
+    out[0] = d.evict_need; out[1] = d.kind; out[2] = d.roles; out[3] = d.bytes;
+  } else if (rule == 1) {
+    out[0] = bh::fft_tables_build_failed(h, (size_t)in[3]);
+  } else if (rule == 2) {
+    if (n_in < 4 || (n_in - 4) % 3) return BH_ERR_INVALID_ARG;
+    std::vector<bh::FftCacheEntry> e;
+    for (size_t i = 4; i < n_in; i += 3) e.push_back({(uint32_t)in[i], (size_t)in[i + 1], in[i + 2]});
+    out[0] = (uint64_t)(int64_t)bh::fft_evict_victim(e.data(), e.size(), (uint32_t)in[0], (size_t)in[1], (size_t)in[2], (size_t)in[3]);
+  } else {
+    return BH_ERR_INVALID_ARG;
+  }
+  return BH_OK;
 }
 
 // ---- test hook: the group law in the multi-lane forms on its own (tests/test_gpu_parity.py::test_g2_k3_group_law,

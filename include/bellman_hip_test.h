@@ -479,6 +479,18 @@ int bh_test_groth16_prove_witness_batch_he(bh_params *params, const bh_r1cs *r1c
  *   [18] log_v (single-pass sizes: 2^log_v vectors per tile, one per column)  [19] pass */
 int bh_test_fft_many_plan(uint32_t log_n, size_t k, size_t stride_elems, size_t scratch_vectors, int table_kind, uint64_t *out,
                           size_t cap);
+/* host only, no GPU: the rules of the per-size FFT table cache (csrc/fft_tables_plan.hpp) on plain integers.  What a size
+ * holds is (kind, roles, bytes): kind 0 none / 1 one-level / 2 two-level tables; roles bit 0 forward twiddles, 1 inverse
+ * twiddles, 2 coset, 3 inverse coset; bytes with the size's 48-byte 1/n entry (0: not cached).
+ *   rule 0, what a call does: in[11] = kind, roles, bytes, log_n (< 32), dir (0 forward, 1 inverse), need_tw, need_coset,
+ *     need_icoset, bytes the whole cache holds, budget, the BELLMAN_HIP_FFT_ONE_LEVEL switch;  out[4] = bytes of other sizes
+ *     to evict first (0: none, then:), the kind to build in, the roles to build, the bytes that adds
+ *   rule 1, after a failed one-level build: in[4] = kind, roles, bytes, bytes the other sizes hold;  out[1] = 0 fall back to
+ *     two-level tables, 1 evict every other size and retry, 2 fail
+ *   rule 2, the next size an eviction drops: in[4 + 3 * sizes] = the size to keep, bytes the cache holds, bytes to make room
+ *     for (UINT64_MAX: drop everything else), budget, then (log_n, bytes, last use) per size;  out[1] = its index, UINT64_MAX: none
+ * Returns BH_OK, or BH_ERR_INVALID_ARG for another rule, another n_in or log_n >= 32. */
+int bh_test_fft_table_policy(int rule, const uint64_t *in, size_t n_in, uint64_t *out);
 /* host only: the number of witnesses a lane of bh_r1cs_eval_many_dev / bh_r1cs_check_many_dev serves (csrc/r1cs_dev.hpp
  * R1CS_MANY_TILE), so that a test can place k on the tile edges */
 uint32_t bh_test_r1cs_many_tile(void);
