@@ -198,6 +198,6 @@ int msm_finish_g1(MsmJobImpl &job, void *out_affine, float *ms);   // ms: float[
 int msm_finish_g2(MsmJobImpl &job, void *out_affine, float *ms);
 int fixed_base_mul_g1(const void *base_host, const void *scalars_dev, u64 n, int fmt, void *out_dev, hipStream_t st, void *table_dev);
 int fixed_base_mul_g2(const void *base_host, const void *scalars_dev, u64 n, int fmt, void *out_dev, hipStream_t st, void *table_dev);
-constexpr size_t FIXED_BASE_TABLE_RECORDS = 32 * 255;   // msm_ec.cuh FB_ROWS x FB_COLS
+constexpr size_t FIXED_BASE_TABLE_RECORDS = 32 * 255;   // point_kernels.cuh FB_ROWS x FB_COLS
 
 }  // namespace bh

@@ -1,6 +1,6 @@
 // Reading, validating and combining point records outside a multiexp job: the status word of the loaders, the compressed
 // readers (point_read.hip), the curve and subgroup tests, the window-table builders and the host-side group law
-// (msm_ec.cuh, instantiated in msm_g1.hip / msm_g2.hip; the by-group dispatchers are in msm.hip).
+// (point_kernels.cuh and msm_ec.cuh, instantiated in msm_g1.hip / msm_g2.hip; the by-group dispatchers are in msm.hip).
 #pragma once
 #include "msm_types.hpp"
 

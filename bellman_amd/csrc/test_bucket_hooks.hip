@@ -1,7 +1,7 @@
 // libbellman_hip_test.so: stage 4 of a multiexp on its own - msm_accumulate_kernel, msm_merge_chunks_kernel and the tail
 // (msm_merge_tail_kernel, or msm_merge_runs_kernel + msm_merge_long_kernel) over a sorted pair stream the caller chooses, through
-// the launch functions msm_enqueue calls (launch_accumulate, launch_merges, merge_plan, merge_bounds of msm_ec.cuh); everything the
-// kernels wrote comes back raw (bh_test_bucket_stage_* of include/bellman_hip_test.h; tests/test_gpu_bucket_stage.py,
+// the functions msm_enqueue calls (launch_accumulate, launch_merges of msm_ec.cuh; merge_plan, merge_bounds of
+// msm_stage_plans.hpp); everything the kernels wrote comes back raw (bh_test_bucket_stage_* of include/bellman_hip_test.h; tests/test_gpu_bucket_stage.py,
 // tests/test_bucket_stage_model_cpu.py).  Every input is validated on the host before anything is launched: a stream that
 // could make a kernel leave its buffers is refused.  Next to them: what the stage gathers from - msm_pick_sources on tagged
 // views (bh_test_msm_sources, host only) and window_table_kernel into a sentinel-filled buffer (bh_test_window_table_dev).
@@ -26,28 +26,25 @@ constexpr bool is_pow2(u32 g) { return g && !(g & (g - 1)); }
 constexpr int acc_group(int f) { return f < 2 ? 1 : 2; }
 constexpr int merge_group(int f) { return f < 2 ? 1 : 2; }
 
-struct MergeInfo {
-  u32 piece, medium_per_wave, big_per_wave;
-};
-template <class FR, bool PAIRS>
-static MergeInfo merge_info() {
-  typedef typename MergeWorkers<FR>::HalfWK HalfWK;
-  return {long_piece<HalfWK>(), PAIRS ? HalfWK::PER_WAVE : XyzzWorker<FR>::PER_WAVE, HalfWK::PER_WAVE};
-}
-static bool merge_form_info(int form, MergeInfo &mi) {
+// the bundle of a merge form, and whether the form puts the medium runs on the group's half-point worker
+static bool merge_form_geom(int form, BundleGeom &g, bool &pairs) {
+  pairs = false;
   switch (form) {
-    case 0: mi = merge_info<FpOps, false>(); return true;
-    case 1: mi = merge_info<FpOps, true>(); return true;
-    case 2: mi = merge_info<Fp2K3Ops, false>(); return true;
-    case 3: mi = merge_info<Fp2K3Ops, true>(); return true;
-    case 4: case 5: mi = merge_info<Fp2Ops, false>(); return true;
+    case 0: g = bundle_geom<FpOps>(); return true;
+    case 1: g = bundle_geom<FpOps>(); pairs = true; return true;
+    case 2: g = bundle_geom<Fp2K3Ops>(); return true;
+    case 3: g = bundle_geom<Fp2K3Ops>(); pairs = true; return true;
+    case 4: case 5: g = bundle_geom<Fp2Ops>(); return true;
     // the plan query alone: a bundle's plan as msm_enqueue gets it, whichever worker it puts the medium runs on
-    case RAW_G1: mi = merge_info<FpOps, false>(); return true;
-    case RAW_G2_K3: mi = merge_info<Fp2K3Ops, false>(); return true;
-    case RAW_G2: mi = merge_info<Fp2Ops, false>(); return true;
+    case RAW_G1: g = bundle_geom<FpOps>(); return true;
+    case RAW_G2_K3: g = bundle_geom<Fp2K3Ops>(); return true;
+    case RAW_G2: g = bundle_geom<Fp2Ops>(); return true;
     default: return false;
   }
 }
+// workers per wavefront of the kernels' two parts: the big pieces run on the half-point worker where the group has one
+static u32 medium_per_wave(const BundleGeom &g, bool pairs) { return pairs ? g.half_per_wave : g.per_wave; }
+static u32 big_per_wave(const BundleGeom &g) { return g.half_kind != WK_NONE ? g.half_per_wave : g.per_wave; }
 
 static MsmPlan stage_plan(u32 W, u32 n, u32 c, u32 K, u32 chunks_per_window) {
   MsmPlan p{};
@@ -70,15 +67,13 @@ static bool plan_args_ok(int merge_form, u32 W, u32 n, u32 c, u32 K, u32 chunks_
 }
 // the shipped merge_plan of the form's bundle, then the overrides, then the shipped bounds for what results
 static bool stage_merge_plan(int merge_form, const MsmPlan &p, int num_cus, const u32 *ov, MergePlan &mp) {
-  MergeInfo mi;
-  if (!merge_form_info(merge_form, mi) || num_cus <= 0) return false;
-  const bool g1 = merge_form < 2 || merge_form == RAW_G1, k3 = merge_form == 2 || merge_form == 3 || merge_form == RAW_G2_K3;
-  mp = g1 ? merge_plan<FpOps>(p, num_cus) : k3 ? merge_plan<Fp2K3Ops>(p, num_cus) : merge_plan<Fp2Ops>(p, num_cus);
+  BundleGeom geom;
+  bool pairs;
+  if (!merge_form_geom(merge_form, geom, pairs) || num_cus <= 0) return false;
+  mp = merge_plan(p, geom, num_cus);
   if (merge_form >= MERGE_FORMS) {
-    if (g1 && mp.runs_on_pairs) mi = merge_info<FpOps, true>();
-    if (k3 && mp.runs_on_pairs) mi = merge_info<Fp2K3Ops, true>();
+    pairs = mp.runs_on_pairs;
   } else if (merge_form < 4) {   // the form says which worker folds the medium runs; its G has to fit that worker
-    const bool pairs = merge_form & 1;
     if (pairs != mp.runs_on_pairs && !(ov && ov[OV_RUN_LANES])) mp.run_lanes = 8;
     mp.runs_on_pairs = pairs;
   }
@@ -87,7 +82,7 @@ static bool stage_merge_plan(int merge_form, const MsmPlan &p, int num_cus, cons
     if (ov[OV_RUN_LANES]) mp.run_lanes = ov[OV_RUN_LANES];
     if (ov[OV_BIG_CHUNKS]) mp.big_chunks = ov[OV_BIG_CHUNKS];
   }
-  if (!is_pow2(mp.run_lanes) || mp.run_lanes < 8 || mp.run_lanes > mi.medium_per_wave) return false;
+  if (!is_pow2(mp.run_lanes) || mp.run_lanes < 8 || mp.run_lanes > medium_per_wave(geom, pairs)) return false;
   if (mp.big_chunks < mp.walk) return false;
   const MergeBounds mb = merge_bounds((u64)p.W * p.chunks_per_window, mp.walk, mp.big_chunks, mp.piece);
   mp.max_long = mb.max_long; mp.max_big = mb.max_big; mp.max_pieces = mb.max_pieces;
@@ -166,17 +161,18 @@ using namespace bh;
 using namespace bh::bucketstage;
 extern "C" {
 int bh_test_bucket_stage_shape(int acc_form, int merge_form, size_t out12[12]) {
-  MergeInfo mi;
-  if (!out12 || acc_form < 0 || acc_form >= ACC_FORMS || merge_form >= MERGE_FORMS || !merge_form_info(merge_form, mi)) return BH_ERR_INVALID_ARG;
+  BundleGeom geom;
+  bool pairs;
+  if (!out12 || acc_form < 0 || acc_form >= ACC_FORMS || merge_form >= MERGE_FORMS || !merge_form_geom(merge_form, geom, pairs)) return BH_ERR_INVALID_ARG;
   if (acc_group(acc_form) != merge_group(merge_form)) return BH_ERR_INVALID_ARG;
   const bool g1 = acc_group(acc_form) == 1;
   out12[0] = g1 ? sizeof(XYZZ<FpOps>) : sizeof(XYZZ<Fp2Ops>);
   out12[1] = g1 ? sizeof(Affine<FpOps>) : sizeof(Affine<Fp2Ops>);
-  out12[2] = mi.piece;
-  out12[3] = mi.medium_per_wave;
-  out12[4] = mi.big_per_wave;
+  out12[2] = geom.long_piece;
+  out12[3] = medium_per_wave(geom, pairs);
+  out12[4] = big_per_wave(geom);
   out12[5] = 8;                    // G: a power of two from 8 (merge_plan's sweep starts there) to the medium worker's wavefront
-  out12[6] = mi.medium_per_wave;
+  out12[6] = medium_per_wave(geom, pairs);
   out12[7] = GUARD;
   out12[8] = sizeof(LongRun);
   out12[9] = sizeof(BigRun);

@@ -10,7 +10,8 @@
 #include "../../include/bellman_hip_test.h"
 #include "final_exp.cuh"
 #include "fp12.cuh"
-#include "msm_ec.cuh"
+#include "handles.hpp"
+#include "msm_workers.cuh"
 #include "point_read.cuh"
 
 namespace bh {

@@ -1,7 +1,7 @@
 // libbellman_hip_test.so: ONE group operation per worker on raw projective operands the caller chooses, raw results back
 // (bh_test_group_ops_dev / _host of include/bellman_hip_test.h; tests/test_gpu_group_law.py, tests/test_group_model_cpu.py).
 // Every operation goes through the functions the kernels call (xyzz_add / xyzz_madd / xyzz_dbl of ec.cuh, half_add,
-// group_reduce_points / half_group_reduce and long_block_sum of msm_ec.cuh) through the kernels' own worker policies
+// group_reduce_points / half_group_reduce and long_block_sum of msm_sums.cuh and msm_merge.cuh) through the kernels' own worker policies
 // (XyzzWorker<F>, HalfWorker<P>); nothing is canonicalised on the way out.  The one-lane forms compile for the host too: the
 // same `apply` runs in the kernel and in the host loop, and the host trees add in the order of the shuffle trees.
 // bh_test_sum_jobs_dev runs msm_sum_kernel itself (tests/test_gpu_sum_jobs.py).
@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "../../include/bellman_hip_test.h"
-#include "msm_ec.cuh"
+#include "msm_merge.cuh"
 
 namespace bh {
 namespace groupops {

@@ -6,8 +6,9 @@
 #include "../../include/bellman_hip_test.h"
 #include "final_exp.cuh"
 #include "fp12.cuh"
-#include "msm_ec.cuh"
+#include "msm_sums.cuh"
 #include "pairing_launch.hpp"
+#include "point_kernels.cuh"
 #include "point_read.cuh"
 #include "shard_cuts.hpp"
 #include "fft_plan.hpp"

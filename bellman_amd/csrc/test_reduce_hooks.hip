@@ -1,9 +1,9 @@
 // libbellman_hip_test.so: stage 5 of a multiexp on its own - the row / column sums, their two-stage split, the bit sums and
-// totals - over filled buckets the caller chooses, through the functions msm_enqueue calls (reduce_plan and launch_reduce of
-// msm_ec.cuh), and the host tail (msm_host_tail) over what they leave (bh_test_reduce_* and bh_test_msm_host_tail of
-// include/bellman_hip_test.h; tests/test_gpu_reduce_stage.py, tests/test_reduce_stage_model_cpu.py).  The plan query runs the
-// same launch_reduce with a sink that records every launch instead of issuing it; the device hook checks that record
-// against its buffers on the host before anything is launched.
+// totals - over filled buckets the caller chooses, through the functions msm_enqueue calls (reduce_plan of msm_stage_plans.hpp,
+// launch_reduce of msm_ec.cuh), and the host tail (msm_host_tail) over what they leave (bh_test_reduce_* and
+// bh_test_msm_host_tail of include/bellman_hip_test.h; tests/test_gpu_reduce_stage.py, tests/test_reduce_stage_model_cpu.py).
+// The plan query copies out the schedule reduce_plan returns - the one launch_reduce issues; the device hook checks that
+// schedule against its buffers on the host before anything is launched.
 #include <string.h>
 
 #include <type_traits>
@@ -22,7 +22,6 @@ enum { FORM_G1, FORM_G2_K3, FORM_G2, FORMS };
 enum { KIND_CLASSIC = 0, KIND_TABLE = 1 };
 enum { PL_C, PL_W, PL_NB_WINDOW, PL_NB, PL_LO_BITS, PL_HI_BITS, PL_TWO_LEN, PL_WANT_PART, PL_ROWCOL, PL_PART, PL_BITS, PL_GUARD,
        PL_SENTINEL, PL_RECORD, PL_AFFINE, PL_NUM_CUS, PL_WORDS };
-enum { BUF_PTS, BUF_ROWCOL, BUF_PART, BUF_BITS, BUFS };
 // a job: the 11 words of bh_test_sum_jobs_dev (offsets inside the job's buffers), then which buffers and its workgroups
 enum { SJ_MODE, SJ_GROUPS, SJ_COUNT, SJ_INNER, SJ_STRIDE, SJ_ISTRIDE, SJ_GROUP_SHIFT, SJ_SPLITS, SJ_LANES, SJ_IN_OFF, SJ_OUT_OFF,
        SJ_IN_BUF, SJ_OUT_BUF, SJ_NBLOCKS, SJ_WORDS };
@@ -30,53 +29,6 @@ enum { SJ_MODE, SJ_GROUPS, SJ_COUNT, SJ_INNER, SJ_STRIDE, SJ_ISTRIDE, SJ_GROUP_S
 enum { LA_KIND, LA_WAVES, LA_BLOCKS, LA_MAX_LANES, LA_JOBS, LA_WORDS = LA_JOBS + 3 * SJ_WORDS };
 
 constexpr bool is_pow2(u32 g) { return g && !(g & (g - 1)); }
-
-template <class WK>
-constexpr u32 worker_kind() {
-  return std::is_same<WK, XyzzWorker<FpOps>>::value ? 0u : std::is_same<WK, K2Worker>::value ? 1u :
-         std::is_same<WK, XyzzWorker<Fp2Ops>>::value ? 2u : std::is_same<WK, XyzzWorker<Fp2K3Ops>>::value ? 3u : 5u;
-}
-static_assert(worker_kind<K6Worker>() == 5, "K6Worker is the only worker kind left for 5");
-
-// Records what sum_launch would launch: sum_count clamps and counts exactly as it does there.  The buffers are told apart
-// by address: the query hands launch_reduce bases that no record count can carry into one another.
-struct RecordSink {
-  uintptr_t base[BUFS];
-  size_t rec;
-  std::vector<u32> words;
-  bool bad = false;
-  static constexpr uintptr_t SPAN = (uintptr_t)1 << 40;
-  void locate(const void *ptr, u32 &buf, u32 &off) {
-    const uintptr_t a = (uintptr_t)ptr;
-    for (u32 k = 0; k < BUFS; k++)
-      if (a >= base[k] && a - base[k] < SPAN && (a - base[k]) % rec == 0 && (a - base[k]) / rec < ((u64)1 << 32)) {
-        buf = k; off = (u32)((a - base[k]) / rec);
-        return;
-      }
-    bad = true;
-    buf = off = 0xffffffffu;
-  }
-  template <class WK, u32 NWAVES>
-  bool launch(SumJobs<typename WK::Mem> js, hipStream_t) {
-    const u32 total = sum_count<WK, NWAVES>(js);
-    if (!total) return true;   // (sum_launch launches nothing)
-    const size_t at = words.size();
-    words.resize(at + LA_WORDS, 0);
-    u32 *w = words.data() + at;
-    w[LA_KIND] = worker_kind<WK>(); w[LA_WAVES] = NWAVES; w[LA_BLOCKS] = total; w[LA_MAX_LANES] = NWAVES * WK::PER_WAVE;
-    for (int q = 0; q < 3; q++) {
-      const SumJob<typename WK::Mem> &j = js.j[q];
-      u32 *s = w + LA_JOBS + q * SJ_WORDS;
-      s[SJ_MODE] = j.d.mode; s[SJ_GROUPS] = j.d.groups; s[SJ_COUNT] = j.d.count; s[SJ_INNER] = j.d.inner; s[SJ_STRIDE] = j.d.stride;
-      s[SJ_ISTRIDE] = j.d.istride; s[SJ_GROUP_SHIFT] = j.d.group_shift; s[SJ_SPLITS] = j.d.splits; s[SJ_LANES] = j.d.lanes;
-      s[SJ_NBLOCKS] = j.nblocks;
-      if (!j.d.groups) { s[SJ_IN_BUF] = s[SJ_OUT_BUF] = 0xffffffffu; continue; }   // nothing to do: its pointers are never used
-      locate(j.in, s[SJ_IN_BUF], s[SJ_IN_OFF]);
-      locate(j.out, s[SJ_OUT_BUF], s[SJ_OUT_OFF]);
-    }
-    return true;
-  }
-};
 
 static bool args_ok(int form, int kind, u32 c) {
   return form >= 0 && form < FORMS && (kind == KIND_CLASSIC || kind == KIND_TABLE) && c >= 2 && c <= 24;
@@ -89,38 +41,41 @@ static MsmPlan stage_plan(int form, int kind, u32 c, int num_cus) {
   t.c = c; t.W = (256 + c - 1) / c; t.stride = 1024;
   return make_table_plan(1024, t, 8, g2, num_cus);
 }
-// The bases handed to launch_reduce here are invented addresses, apart far enough that no record count carries one buffer
-// into another: launch_reduce may offset them and pass them on to its sink and nothing else - the host path must never
-// dereference, compare or inspect a buffer pointer (an alignment assert, say), or this query stops being valid.
-template <class FR>
-static int record(const MsmPlan &p, const ReducePlan &rp, int num_cus, RecordSink &sink) {
-  typedef XYZZ<typename FR::Mem> Pt;
-  sink.rec = sizeof(Pt);
-  for (u32 k = 0; k < BUFS; k++) sink.base[k] = (uintptr_t)(k + 1) << 44;
-  return launch_reduce<FR>(nullptr, p, rp, num_cus, (const Pt *)sink.base[BUF_PTS], (Pt *)sink.base[BUF_ROWCOL],
-                           rp.want_part ? (Pt *)sink.base[BUF_PART] : nullptr, (Pt *)sink.base[BUF_BITS], sink);
-}
 struct Stage {
   MsmPlan p;
   ReducePlan rp;
   size_t rec, arec;
-  u64 elems[BUFS];
+  u64 elems[RB_BUFS];
   std::vector<u32> launches;
 };
 static int stage(int form, int kind, u32 c, int num_cus, Stage &s) {
   s.p = stage_plan(form, kind, c, num_cus);
   if (s.p.c != c || s.p.NB != (u64)s.p.W << (c - 1)) return BH_ERR_INVALID_ARG;
-  RecordSink sink;
-  int rc;
-  if (form == FORM_G1) { s.rp = reduce_plan<FpOps>(s.p, num_cus); rc = record<FpOps>(s.p, s.rp, num_cus, sink); }
-  else if (form == FORM_G2_K3) { s.rp = reduce_plan<Fp2K3Ops>(s.p, num_cus); rc = record<Fp2K3Ops>(s.p, s.rp, num_cus, sink); }
-  else { s.rp = reduce_plan<Fp2Ops>(s.p, num_cus); rc = record<Fp2Ops>(s.p, s.rp, num_cus, sink); }
-  if (rc) return rc;
-  if (sink.bad) return BH_ERR_INVALID_ARG;
+  const BundleGeom geom = form == FORM_G1 ? bundle_geom<FpOps>() : form == FORM_G2_K3 ? bundle_geom<Fp2K3Ops>() : bundle_geom<Fp2Ops>();
+  s.rp = reduce_plan(s.p, geom, num_cus);
+  if (s.rp.overflow) return BH_ERR_INVALID_ARG;
   s.rec = form == FORM_G1 ? sizeof(XYZZ<FpOps>) : sizeof(XYZZ<Fp2Ops>);
   s.arec = form == FORM_G1 ? sizeof(Affine<FpOps>) : sizeof(Affine<Fp2Ops>);
-  s.elems[BUF_PTS] = s.p.NB; s.elems[BUF_ROWCOL] = s.rp.rowcol_elems; s.elems[BUF_PART] = s.rp.part_elems; s.elems[BUF_BITS] = s.rp.bits_elems;
-  s.launches.swap(sink.words);
+  s.elems[RB_PTS] = s.p.NB; s.elems[RB_ROWCOL] = s.rp.rowcol_elems; s.elems[RB_PART] = s.rp.part_elems; s.elems[RB_BITS] = s.rp.bits_elems;
+  // the plan's schedule in the word layout of include/bellman_hip_test.h
+  s.launches.assign((size_t)s.rp.n_launches * LA_WORDS, 0);
+  for (u32 i = 0; i < s.rp.n_launches; i++) {
+    const ReduceLaunch &l = s.rp.launch[i];
+    u32 *w = s.launches.data() + (size_t)i * LA_WORDS;
+    w[LA_KIND] = l.kind; w[LA_WAVES] = l.waves; w[LA_BLOCKS] = l.blocks;
+    w[LA_MAX_LANES] = l.waves * (l.kind == geom.full_kind ? geom.per_wave : geom.half_per_wave);
+    for (int q = 0; q < 3; q++) {
+      const ReduceJob &j = l.j[q];
+      u32 *sj = w + LA_JOBS + q * SJ_WORDS;
+      sj[SJ_MODE] = j.d.mode; sj[SJ_GROUPS] = j.d.groups; sj[SJ_COUNT] = j.d.count; sj[SJ_INNER] = j.d.inner; sj[SJ_STRIDE] = j.d.stride;
+      sj[SJ_ISTRIDE] = j.d.istride; sj[SJ_GROUP_SHIFT] = j.d.group_shift; sj[SJ_SPLITS] = j.d.splits; sj[SJ_LANES] = j.d.lanes;
+      sj[SJ_NBLOCKS] = j.nblocks;
+      if (!j.d.groups) { sj[SJ_IN_BUF] = sj[SJ_OUT_BUF] = 0xffffffffu; continue; }   // nothing to do: its buffers are never used
+      if (j.in_off >= ((u64)1 << 32) || j.out_off >= ((u64)1 << 32)) return BH_ERR_INVALID_ARG;
+      sj[SJ_IN_BUF] = j.in_buf; sj[SJ_IN_OFF] = (u32)j.in_off;
+      sj[SJ_OUT_BUF] = j.out_buf; sj[SJ_OUT_OFF] = (u32)j.out_off;
+    }
+  }
   return BH_OK;
 }
 static void plan_words(const Stage &s, int num_cus, u32 *out) {
@@ -138,7 +93,7 @@ static bool launches_in_bounds(const Stage &s) {
       const u32 *w = l + LA_JOBS + q * SJ_WORDS;
       const u64 groups = w[SJ_GROUPS], count = w[SJ_COUNT], inner = w[SJ_INNER], splits = w[SJ_SPLITS];
       if (!groups) continue;
-      if (w[SJ_IN_BUF] >= BUFS || w[SJ_OUT_BUF] >= BUFS || w[SJ_OUT_BUF] == BUF_PTS || w[SJ_IN_BUF] == BUF_BITS) return false;
+      if (w[SJ_IN_BUF] >= RB_BUFS || w[SJ_OUT_BUF] >= RB_BUFS || w[SJ_OUT_BUF] == RB_PTS || w[SJ_IN_BUF] == RB_BITS) return false;
       if (!count || !inner || !splits || count % splits || groups % splits || w[SJ_GROUP_SHIFT] > 24) return false;
       if (!is_pow2(w[SJ_LANES]) || w[SJ_LANES] > l[LA_MAX_LANES]) return false;
       if (w[SJ_OUT_OFF] + groups > s.elems[w[SJ_OUT_BUF]]) return false;
@@ -177,10 +132,9 @@ static u32 guard_intact(const unsigned char *g) {
   return 1;
 }
 template <class FR>
-static int run_reduce(hipStream_t st, const Stage &s, int num_cus, const void *pts, void *rowcol, void *part, void *bits) {
+static int run_reduce(hipStream_t st, const Stage &s, const void *pts, void *rowcol, void *part, void *bits) {
   typedef XYZZ<typename FR::Mem> Pt;
-  SumLaunchSink sink;
-  return launch_reduce<FR>(st, s.p, s.rp, num_cus, (const Pt *)pts, (Pt *)rowcol, s.rp.want_part ? (Pt *)part : nullptr, (Pt *)bits, sink);
+  return launch_reduce<FR>(st, s.rp, (const Pt *)pts, (Pt *)rowcol, s.rp.want_part ? (Pt *)part : nullptr, (Pt *)bits);
 }
 }  // namespace reducestage
 }  // namespace bh
@@ -218,26 +172,26 @@ int bh_test_reduce_stage_dev(bh_ctx *ctx, int form, int kind, unsigned c, int nu
   hipStream_t st = cx.stream;
   DevBuf d_pts, d_rowcol, d_part, d_bits;
   int rc;
-  if ((rc = d_pts.alloc(s.elems[BUF_PTS] * s.rec, 0, st)) ||
+  if ((rc = d_pts.alloc(s.elems[RB_PTS] * s.rec, 0, st)) ||
       // zeroed, as in production: the result slots
-      (rc = d_bits.alloc(s.elems[BUF_BITS] * s.rec, 0, st)) ||
+      (rc = d_bits.alloc(s.elems[RB_BITS] * s.rec, 0, st)) ||
       // from the pool, not zeroed
-      (rc = d_rowcol.alloc(s.elems[BUF_ROWCOL] * s.rec, SENTINEL, st)) || (rc = d_part.alloc(s.elems[BUF_PART] * s.rec, SENTINEL, st)))
+      (rc = d_rowcol.alloc(s.elems[RB_ROWCOL] * s.rec, SENTINEL, st)) || (rc = d_part.alloc(s.elems[RB_PART] * s.rec, SENTINEL, st)))
     return rc;
   BH_HIP_CHECK(hipMemcpyAsync(d_pts.p, pts_in, d_pts.bytes, hipMemcpyHostToDevice, st));
   BH_HIP_CHECK(hipStreamSynchronize(st));   // (pageable host memory: the copy above may still be staged)
-  rc = form == FORM_G1      ? run_reduce<FpOps>(st, s, num_cus, d_pts.p, d_rowcol.p, d_part.p, d_bits.p)
-       : form == FORM_G2_K3 ? run_reduce<Fp2K3Ops>(st, s, num_cus, d_pts.p, d_rowcol.p, d_part.p, d_bits.p)
-                            : run_reduce<Fp2Ops>(st, s, num_cus, d_pts.p, d_rowcol.p, d_part.p, d_bits.p);
+  rc = form == FORM_G1      ? run_reduce<FpOps>(st, s, d_pts.p, d_rowcol.p, d_part.p, d_bits.p)
+       : form == FORM_G2_K3 ? run_reduce<Fp2K3Ops>(st, s, d_pts.p, d_rowcol.p, d_part.p, d_bits.p)
+                            : run_reduce<Fp2Ops>(st, s, d_pts.p, d_rowcol.p, d_part.p, d_bits.p);
   if (rc) return rc;
-  std::vector<unsigned char> g(BUFS * GUARD);
+  std::vector<unsigned char> g(RB_BUFS * GUARD);
   std::vector<unsigned char> pts_back(d_pts.bytes);   // the buckets are read-only here: they have to come back as they went
-  if ((rc = d_pts.fetch(pts_back.data(), g.data() + BUF_PTS * GUARD, st)) || (rc = d_rowcol.fetch(rowcol_out, g.data() + BUF_ROWCOL * GUARD, st)) ||
-      (rc = d_part.fetch(part_out, g.data() + BUF_PART * GUARD, st)) || (rc = d_bits.fetch(bits_out, g.data() + BUF_BITS * GUARD, st)))
+  if ((rc = d_pts.fetch(pts_back.data(), g.data() + RB_PTS * GUARD, st)) || (rc = d_rowcol.fetch(rowcol_out, g.data() + RB_ROWCOL * GUARD, st)) ||
+      (rc = d_part.fetch(part_out, g.data() + RB_PART * GUARD, st)) || (rc = d_bits.fetch(bits_out, g.data() + RB_BITS * GUARD, st)))
     return rc;
   BH_HIP_CHECK(hipStreamSynchronize(st));
-  for (int k = 0; k < BUFS; k++) guards_out4[k] = guard_intact(g.data() + (size_t)k * GUARD);
-  if (memcmp(pts_back.data(), pts_in, d_pts.bytes) != 0) guards_out4[BUF_PTS] = 0;
+  for (int k = 0; k < RB_BUFS; k++) guards_out4[k] = guard_intact(g.data() + (size_t)k * GUARD);
+  if (memcmp(pts_back.data(), pts_in, d_pts.bytes) != 0) guards_out4[RB_PTS] = 0;
   // the shipped host tail over what the device left (as msm_finish: the records of `bits` in their device layout)
   if (form == FORM_G1) msm_host_tail<FpOps>(s.p, (const XYZZ<FpOps> *)bits_out, affine_out);
   else msm_host_tail<Fp2Ops>(s.p, (const XYZZ<Fp2Ops> *)bits_out, affine_out);

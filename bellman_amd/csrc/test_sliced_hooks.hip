@@ -3,7 +3,8 @@
 // back (bh_test_g1_madd_sliced_dev / _host of include/bellman_hip_test.h; tests/test_gpu_madd_sliced.py).  The same function
 // runs in the kernel and in the host loop.
 #include "../../include/bellman_hip_test.h"
-#include "msm_ec.cuh"
+#include "handles.hpp"
+#include "msm_workers.cuh"
 
 namespace bh {
 namespace slicedops {

@@ -50,7 +50,7 @@ int bh_test_point_add_dev(bh_ctx *ctx, int group, void *r_dev, const void *a_dev
  * addition, by the mixed addition (a[i] stays when b[i] is the identity), and 2 a[i]; n affine records each, HOST */
 int bh_test_g2_k3_dev(bh_ctx *ctx, void *out_add_host, void *out_madd_host, void *out_dbl_host, const void *a_dev,
                       const void *b_dev, size_t n);
-/* the general addition in the lane-SEXTET (K6) form of the merge kernels (csrc/msm_ec.cuh 5''): a[i] + b[i], affine out, HOST */
+/* the general addition in the lane-SEXTET (K6) form of the merge kernels (csrc/msm_sums.cuh 5a): a[i] + b[i], affine out, HOST */
 int bh_test_g2_k6_dev(bh_ctx *ctx, void *out_add_host, const void *a_dev, const void *b_dev, size_t n);
 /* the same in the lane-pair form (csrc/fp2pair.cuh: schoolbook Fp2 products, one reduction per lane) */
 int bh_test_g2_pairs_dev(bh_ctx *ctx, void *out_add_host, void *out_madd_host, void *out_dbl_host, const void *a_dev,
@@ -236,19 +236,20 @@ int bh_test_window_table_dev(bh_ctx *ctx, int group, const void *points, size_t 
 /* Stage 5 of a multiexp on its own, and its host tail (csrc/test_reduce_hooks.hip; tests/test_gpu_reduce_stage.py,
  * tests/models/reduce_stage_model.py): the row / column sums, their two-stage split over piece sums, the bit sums and the
  * window totals over FILLED BUCKETS of the caller's choice, issued by the function msm_enqueue issues them with
- * (launch_reduce of csrc/msm_ec.cuh) into buffers of exactly the sizes msm_enqueue carves (reduce_plan).
+ * (launch_reduce of csrc/msm_ec.cuh) into buffers of exactly the sizes msm_enqueue carves (reduce_plan of
+ * csrc/msm_stage_plans.hpp).
  *   form   0 G1 (FpOps)   1 G2 on lane triples (Fp2K3Ops)   2 G2 one lane (Fp2Ops): the bundles msm_enqueue reduces with
  *   kind   0 the classic plan (make_plan: W = ceil(256 / c) windows)   1 the table plan (make_table_plan: W = 1)
  *   c      window bits, 2 ... 24.  num_cus: 0 = the context's own, else passed to the plan in its place (it steers choices
  *          only; grids come from the descriptors)
  * bh_test_reduce_plan (host only; ctx may be NULL unless num_cus is 0): plan_out16 = [c, W, nb, NB, lo_bits, hi_bits, two_len,
  * want_part, records of rowcol, of part, of bits, guard bytes, the sentinel byte, XYZZ record bytes, affine record bytes,
- * num_cus used].  *n_launches_out = the launches launch_reduce issues, in order - recorded by running launch_reduce itself
- * with a sink that records where production's launches; launches_out (optional, room for max_launches) = 46 words each:
+ * num_cus used].  *n_launches_out = the launches launch_reduce issues, in order - the schedule of the plan that reduce_plan
+ * returns, which is all launch_reduce reads; launches_out (optional, room for max_launches) = 46 words each:
  * [worker kind (the forms of bh_test_sum_jobs_dev), wavefronts per workgroup, workgroups, lanes a workgroup holds], then three
  * jobs of 14 words: the 11 of bh_test_sum_jobs_dev after sum_count's clamping, with offsets in records inside the job's
  * buffers, then [buffer read, buffer written, workgroups]; buffers 0 pts, 1 rowcol (rows, then cols at W 2^hi_bits), 2 part,
- * 3 bits.  A job with groups = 0 does nothing; launches of no workgroup are not issued and not recorded.
+ * 3 bits.  A job with groups = 0 does nothing; launches of no workgroup are not part of the plan.
  * bh_test_reduce_stage_dev: pts_in = NB raw XYZZ records.  rowcol, part and bits are allocated at exactly the planned sizes,
  * each followed by a guard; bits starts zeroed as in production, rowcol, part and every guard filled with the sentinel byte.
  * launch_reduce runs once on the context's stream; rowcol_out, part_out, bits_out receive the buffers raw (part_out may not be

@@ -1,4 +1,4 @@
-"""Stage 4 of a multiexp (bellman_amd/csrc/msm_ec.cuh: effective_chunk, chunk_view, msm_accumulate_kernel, run_last_chunk,
+"""Stage 4 of a multiexp (bellman_amd/csrc/msm_accumulate.cuh, msm_merge.cuh: effective_chunk, chunk_view, msm_accumulate_kernel, run_last_chunk,
 msm_merge_chunks_kernel and the queues the tail kernels consume) restated on plain integers, statement by statement, so that
 a change there shows here.  tests/test_bucket_stage_model_cpu.py checks the model against brute force and the shipped queue
 bounds against it; tests/test_gpu_bucket_stage.py compares everything the kernels write with it.

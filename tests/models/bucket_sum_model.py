@@ -1,4 +1,4 @@
-"""Index arithmetic of the sum kernel (bellman_amd/csrc/msm_ec.cuh, section 5c: nth_with_bit, partial_sum<WK>,
+"""Index arithmetic of the sum kernel (bellman_amd/csrc/msm_sums.cuh, section 5c: nth_with_bit, partial_sum<WK>,
 msm_sum_kernel<WK, NWAVES>) restated over any abelian group: plain integers in tests/test_bucket_sum_model_cpu.py, curve points
 (tests/group_model.add, None = the identity) in tests/test_gpu_sum_jobs.py.  A job is a dict with the fields of SumDesc:
 mode ("strided" / "bits"), groups, count, inner, stride, istride, group_shift, splits.  Everything is mirrored statement by
@@ -6,7 +6,7 @@ statement from the kernel, so a change there shows here."""
 import operator
 
 
-def nth_with_bit(j, k):   # msm_ec.cuh nth_with_bit
+def nth_with_bit(j, k):   # msm_sums.cuh nth_with_bit
     return ((j >> k) << (k + 1)) | (1 << k) | (j & ((1 << k) - 1))
 
 

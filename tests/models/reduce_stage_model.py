@@ -1,9 +1,10 @@
-"""Stage 5 of a multiexp - the reduction of filled buckets - and its host tail, restated over plain integers (csrc/msm_ec.cuh:
-reduce_plan, launch_reduce, msm_host_tail; tests/test_reduce_stage_model_cpu.py, tests/test_gpu_reduce_stage.py).
+"""Stage 5 of a multiexp - the reduction of filled buckets - and its host tail, restated over plain integers
+(csrc/msm_stage_plans.hpp: reduce_plan; csrc/msm_ec.cuh: launch_reduce, msm_host_tail; tests/test_reduce_stage_model_cpu.py,
+tests/test_gpu_reduce_stage.py).
 
-The launches are not rewritten here: bh_test_reduce_plan runs the shipped launch_reduce with a sink that records every launch
-it would issue, and `execute` replays that record over integer buckets - with tests/models/bucket_sum_model.run_job, or, where
-2^22 buckets would take minutes, with an index matrix that is pinned against run_job on the small plans.  While replaying it
+The launches are not rewritten here: bh_test_reduce_plan hands out the schedule of the shipped reduce_plan - every launch
+launch_reduce issues, as data - and `execute` replays that schedule over integer buckets - with
+tests/models/bucket_sum_model.run_job, or, where 2^22 buckets would take minutes, with an index matrix that is pinned against run_job on the small plans.  While replaying it
 checks what no parity test of a whole multiexp can see: every record a job reads lies inside its buffer and was written by an
 earlier launch (`pts`: is an input), every cell of rows, cols and bits is written exactly once, nothing is written outside the
 planned sizes, lane counts are powers of two that fit their workgroups.  What comes out is compared with the definitions:
@@ -120,7 +121,7 @@ def access_key(launches):
 
 
 def execute(plan, launches, buckets, slow=None):
-    """Replays the recorded launches over integer buckets (an integer array of NB values).  Returns (values, written): per
+    """Replays the planned launches over integer buckets (an integer array of NB values).  Returns (values, written): per
     buffer an int64 array (pts: as given) and how often each cell was written.  Raises PlanError where a job leaves its
     buffers, reads a cell no earlier launch wrote, or has a malformed shape.  slow: also replay every job with
     bucket_sum_model.run_job and compare (default: plans of at most SMALL buckets)."""

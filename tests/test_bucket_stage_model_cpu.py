@@ -1,5 +1,5 @@
 """The index model of stage 4 (tests/models/bucket_stage_model.py) against brute force, the shipped queue bounds
-(merge_bounds of csrc/msm_ec.cuh through bh_test_merge_plan) against the model's counts, and the shipped merge_plan against
+(merge_bounds of csrc/msm_stage_plans.hpp through bh_test_merge_plan) against the model's counts, and the shipped merge_plan against
 the formulas msm_enqueue computed inline before they moved.  No GPU: bh_test_merge_plan and bh_test_bucket_stage_shape are
 host code."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Index arithmetic of the bucket reduction (bellman_amd/csrc/msm_ec.cuh, section 5c), restated over plain integers.
+"""Index arithmetic of the bucket reduction (bellman_amd/csrc/msm_sums.cuh, section 5c), restated over plain integers.
 
 The device computes  sum_d (d + 1) * B[d]  over 2^(c-1) buckets without a serial running sum: d = hi * 2^l + lo, row sums over
 lo, column sums over hi, then per-bit sums of those vectors and a plain total; the host finishes with

@@ -1,6 +1,6 @@
 """The G1 bucket accumulation over small, adversarial sorted streams, through the public multiexp (`pytest -m gpu`).
 
-msm_accumulate_kernel<FpOps, false> (csrc/msm_ec.cuh) adds with the mixed addition over sliced operands (ec.cuh
+msm_accumulate_kernel<FpOps, false> (csrc/msm_accumulate.cuh) adds with the mixed addition over sliced operands (ec.cuh
 xyzz_madd_sliced).  An entry that opens a bucket or a chunk partial is a copy, an addition may double or cancel, and
 `mixed_additions` counts exactly the additions into a non-empty accumulator: the patterns below put each of those at every
 position of a chunk.

@@ -3,7 +3,7 @@
 The reference special-cases Exponent::Zero / One (src/multiexp.rs:172-182,245-252) because witnesses of bit-level circuits
 (src/gadgets/boolean.rs, sha256.rs:307-331) are almost only zeros and ones; SURVEY.md 8(d) lists "boolean-heavy vectors
 (~50 % zeros/ones)" in the input suite.  On the device such a vector puts a quarter (or all) of its entries into ONE bucket
-of window 0 - a run of thousands of chunks through msm_merge_chunks -> merge_runs -> merge_long (csrc/msm_ec.cuh) that the
+of window 0 - a run of thousands of chunks through msm_merge_chunks -> merge_runs -> merge_long (csrc/msm_merge.cuh) that the
 uniform scalars of every other large test never produce.  Here, at BASELINE sizes:
 
   * G1 at 2^20 and 2^22 terms, G2 at 2^20: mixes {50 % 0/1, 90 % 0/1, all ones, 90 % below 2^8} x {classic plan, window-table

@@ -134,7 +134,7 @@ def test_g2_k3_group_law(worker):
 
 
 def test_g2_lane_sextet_addition(worker):
-    """[r6] The lane-sextet (K6) general addition the G2 merge kernels run (csrc/msm_ec.cuh 5'': the x / y split of a point
+    """[r6] The lane-sextet (K6) general addition the G2 merge kernels run (csrc/msm_sums.cuh 5a: the x / y split of a point
     over two lane triples, seven product slots instead of fourteen): a + b for G2 points including P + P (the doubling
     fallback), P + (-P) and the identity on either side, against the oracle's group law.  70 points: nine wavefronts of 8
     sextets, a ragged tail."""

@@ -4,7 +4,7 @@ bit sums and totals over FILLED BUCKETS of the test's choice, issued by the func
 
 Buckets hold k G for |k| <= 8, picked from a pool of raw records - every point in several scalings with +p masks, the identity
 all-zero and as ZZ = 0 with garbage - by a seeded index array, so every expected value is an integer sum
-(tests/models/reduce_stage_model.py replays the launches bh_test_reduce_plan records) turned into a point once per output.  All
+(tests/models/reduce_stage_model.py replays the launches bh_test_reduce_plan hands out) turned into a point once per output.  All
 sums stay far below the group order: "sum = 0" is "identity".  Classes: dense, sparse (90 % all-zero records), every bucket the
 same point (every tree level doubles), alternating +-P (level one cancels), one live bucket at either end of the first and
 last window, all identities.  Shapes: the smallest that reach each path - see CASES; the plan query says what each reaches, and

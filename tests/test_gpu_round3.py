@@ -580,7 +580,7 @@ def test_reductions_with_equal_and_opposite_partial_sums(worker, group):
 @pytest.mark.parametrize("group", [1, 2])
 def test_bucket_runs_of_every_length_class(worker, group):
     """[r4] Bucket runs that straddle chunk boundaries are folded by the owner lane of the merge kernel (up to four
-    further chunks), by the wavefront-parallel merge (queued runs) or by the workgroup-parallel one (csrc/msm_ec.cuh).
+    further chunks), by the wavefront-parallel merge (queued runs) or by the workgroup-parallel one (csrc/msm_merge.cuh).
     Scalars drawn from a small set of values give every window a few dozen buckets whose runs are 1 ... 60 chunks long,
     so with chunks of 8 / 16 / 32 entries every route and every kernel bundle (one lane, lane pairs, lane triples per G2
     point) sees runs of every length class.  Against the restated multiexp (src/multiexp.rs:210-301).  (Written for the

@@ -1,4 +1,4 @@
-"""The window table of a base vector as bh_bases_precompute builds it: ONE pass of window_table_kernel (csrc/msm_ec.cuh)
+"""The window table of a base vector as bh_bases_precompute builds it: ONE pass of window_table_kernel (csrc/point_kernels.cuh)
 that writes every row at the stride the table keeps - through bh_test_window_table_dev, which builds into a buffer filled
 with a sentinel byte and followed by a guard and returns both raw (run with `pytest -m gpu` on a MI355X).
 

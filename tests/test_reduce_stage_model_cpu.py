@@ -1,7 +1,7 @@
 """Stage 5 of a multiexp and its host tail without a GPU (bh_test_reduce_plan and bh_test_msm_host_tail are host code):
 
-  the plan      every launch the shipped launch_reduce would issue - recorded by launch_reduce itself through a recording
-                sink - replayed over integer buckets by tests/models/reduce_stage_model.py, for every c in [2, 24] x both plan
+  the plan      every launch the shipped launch_reduce issues - the schedule that reduce_plan returns and launch_reduce
+                walks - replayed over integer buckets by tests/models/reduce_stage_model.py, for every c in [2, 24] x both plan
                 kinds x the three bundles msm_enqueue reduces with x 32, 64, 128 and 256 compute units (an MI355X in a
                 partitioned compute mode reports the smaller counts and then takes other branches);
   coverage      the matrix must reach every worker kind and workgroup width, both sides of every switch (asserted);
