@@ -2,6 +2,7 @@
 // and the error-resolution pass (launched by launch_accumulate / msm_enqueue / msm_finish of msm_ec.cuh).
 #pragma once
 #include "msm_scalar.cuh"
+#include "msm_stage_plans.hpp"
 #include "msm_sums.cuh"
 
 namespace bh {
@@ -184,12 +185,8 @@ __global__ __launch_bounds__(128) void msm_accumulate_kernel(const u64 *pairs, c
 // thread, redundantly per workgroup) and then each worker owns one bucket and scans the digit table for its entries:
 // density prefix, digits, radix sort, zero count, accumulation and the three merge kernels become one launch.
 // (profiles/archive/r3_call7_small_fused.txt)
-constexpr u32 SMALL_MAX_SCALARS = 2048, SMALL_MAX_ENTRIES = 20480 + 1024, SMALL_MAX_PER_BUCKET = 16, SMALL_LIST_CAP = 24;
-constexpr u32 SMALL_THREADS = 256, SMALL_LANES_PER_BUCKET = 4;
-// dynamic LDS of the kernel: base indices, digit table, per-bucket entry lists of the workgroup's buckets
-inline size_t small_fill_lds_bytes(u32 nd, u32 n_entries) {
-  return (size_t)nd * 4 + (((size_t)n_entries * 2 + 3) & ~size_t(3)) + SMALL_THREADS * 4 + (size_t)SMALL_THREADS * SMALL_LIST_CAP * 2;
-}
+// The SMALL_* constants, the dynamic LDS size (small_fill_lds_bytes) and the gate that keeps a job inside them
+// (small_fill_plan) are host plan data: msm_stage_plans.hpp
 template <class F>
 __global__ __launch_bounds__(SMALL_THREADS) void msm_small_fill_kernel(const void *scalars, int fmt, u32 nd, const u64 *density,
                                                              u32 *word_prefix_out, u64 skip, u64 n_bases, u32 c, u32 Wd,

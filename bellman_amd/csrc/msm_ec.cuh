@@ -94,6 +94,32 @@ static int launch_merges(hipStream_t st, const MsmPlan &p, const MergePlan &mp, 
   return BH_OK;
 }
 
+// 4'. the one-launch small path: exactly the launch sp says (small_fill_plan over the workers per workgroup of the bundle F that
+// accumulates, small_fill_workers<F>(); csrc/test_small_hooks.hip runs the same function).  pts: nb zeroed buckets;
+// word_prefix (null without a density): ceil(nd / 64) + 1 words for the error-resolution pass
+template <class F>
+constexpr u32 small_fill_workers() { return workers_per_block<F>(SMALL_THREADS, tree_per_wave<F>()); }
+template <class F>
+static int launch_small_fill(hipStream_t st, const MsmPlan &p, const SmallFillPlan &sp, const void *scalars_dev, int fmt,
+                             const u64 *density_dev, u32 *word_prefix, u64 skip, u64 n_bases, const Affine<typename F::Mem> *table,
+                             XYZZ<typename F::Mem> *pts, ErrFlags *err) {
+  if (!sp.fused || !sp.workgroups) return BH_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(msm_small_fill_kernel<F>, dim3(sp.workgroups), dim3(sp.threads), sp.lds_bytes, st, scalars_dev, fmt, p.nd,
+                     density_dev, word_prefix, skip, n_bases, p.c, p.Wd, p.base_stride, table, pts, err);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+// The error-resolution pass over the nd scalars of a job whose flags say both EOF and an identity (msm_finish; also run on its
+// own by csrc/test_small_hooks.hip): sets err->ident_top.  bases: the records the job's accumulation read, base_stride bytes apart
+template <class F>
+static int launch_err_resolve(hipStream_t st, const void *scalars_dev, int fmt, u32 nd, const u64 *density_dev, const u32 *word_prefix,
+                              u64 skip, u64 n_bases, const Affine<F> *bases, u32 base_stride, u32 lo_ref, ErrFlags *err) {
+  hipLaunchKernelGGL(msm_err_resolve_kernel<F>, dim3((nd + 255) / 256), dim3(256), 0, st, scalars_dev, fmt, nd, density_dev,
+                     word_prefix, skip, n_bases, bases, base_stride, lo_ref, err);
+  BH_HIP_CHECK(hipGetLastError());
+  return BH_OK;
+}
+
 // 5. reduce: the launches of rp (reduce_plan; also run on their own by csrc/test_reduce_hooks.hip), each on the sum kernel of
 // its worker kind and wavefront count.  pts: NB filled buckets; rowcol, part (null unless rp.want_part), bits (zeroed): rp's
 // element counts
@@ -286,23 +312,13 @@ static int msm_enqueue(MsmJobImpl &job, const MsmBases &bases, u64 skip, const v
   if (job.timed) BH_HIP_CHECK(hipEventRecord(job.ev_begin, st));
   BH_HIP_CHECK(hipMemsetAsync(ws, 0, zero_bytes, st));
   const u64 *sorted = nullptr;
-  // small multiexps over a window table: one launch for everything up to the filled buckets (msm_small_fill_kernel)
-  // ... and only when no bucket is EXPECTED to outgrow its list: rows whose top one is a sliver of t = 255 - (Wd - 1) c bits (10-bit
-  // rows: t = 5, 11 bits: 2, 12 bits: 3) send the top digit of every scalar to 2^t buckets, nd / 2^t entries each - such buckets fall
-  // back to a scan of the whole digit table per worker (an explicit 11-bit table over 2^9 points took 8.9 ms in this kernel against
-  // 0.7 through the sort: profiles/r6_call54_tiny_g2_bits.txt); the default 13-bit tables have t = 8
-  const u32 top_bits = 255u - (p.Wd - 1) * p.c;
-  const u64 sliver_load = top_bits >= 31 ? 0 : ((u64)p.nd >> top_bits);
-  const bool small_fused = src.small_path && plan_fused_sort(p) && !many && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
-                           (u64)p.n <= (u64)SMALL_MAX_PER_BUCKET * p.nb && p.c <= 15 && small_fill_lds_bytes(p.nd, p.n) <= 64 * 1024 &&
-                           sliver_load + (u64)p.n / p.nb <= SMALL_LIST_CAP / 2 && !(opts.flags & BH_MSM_NO_SMALL_PATH);
+  // small multiexps over a window table: one launch for everything up to the filled buckets (small_fill_plan has the gate)
+  const SmallFillPlan sp = small_fill_plan(p, src.small_path, many, opts.flags, small_fill_workers<F>());
+  const bool small_fused = sp.fused;
   if (small_fused) {
-    const u32 bpb = workers_per_block<F>(SMALL_THREADS, tree_per_wave<F>()) / SMALL_LANES_PER_BUCKET;   // buckets per workgroup
-    const size_t lds = small_fill_lds_bytes(p.nd, p.n);
-    hipLaunchKernelGGL(msm_small_fill_kernel<F>, dim3((p.nb + bpb - 1) / bpb), dim3(SMALL_THREADS), lds, st, scalars_dev, fmt, p.nd,
-                       density_dev, b.word_prefix, (u64)skip, (u64)n_bases, p.c, p.Wd, p.base_stride,
-                       (const Affine<M> *)src.gather.ptr, pts, err);
-    BH_HIP_CHECK(hipGetLastError());
+    int rc = launch_small_fill<F>(st, p, sp, scalars_dev, fmt, density_dev, b.word_prefix, (u64)skip, (u64)n_bases,
+                                  (const Affine<M> *)src.gather.ptr, pts, err);
+    if (rc) return rc;
   } else {
     int rc = msm_run_stages(p, b, scalars_dev, fmt, density_dev, skip, n_bases, st, &sorted, opts.scalar_stride);
     if (rc) return rc;
@@ -442,12 +458,10 @@ static int msm_finish(MsmJobImpl &job, void *out_affine, float *ms) {
     } else if (ef.ident && (ef.eof || job.always_resolve_ident)) {
       // both kinds of failure exist (or the caller folds shards): the reference reports the top window's first failure
       const u64 nref = job.ref_n ? job.ref_n : p.nd;
-      const double c_ln = (nref < 32) ? 3.0 : std::ceil(std::log((double)nref));   // multiexp.rs:318-322
-      const u32 c_ref = (u32)c_ln, w_ref = (255 + c_ref - 1) / c_ref, lo_ref = c_ref * (w_ref - 1);
-      hipLaunchKernelGGL(msm_err_resolve_kernel<F>, dim3((p.nd + 255) / 256), dim3(256), 0, job.stream,
-                         job.scalars_dev, job.fmt, p.nd, job.density_dev, job.word_prefix, job.skip, job.n_bases,
-                         (const Affine<F> *)job.resolve_bases.ptr, job.resolve_bases.stride, lo_ref, job.err_dev);
-      if (hipMemcpyAsync(&ef, job.err_dev, sizeof ef, hipMemcpyDeviceToHost, job.stream) != hipSuccess ||
+      const u32 lo_ref = err_resolve_lo_ref(nref);   // (msm_stage_plans.hpp)
+      if (launch_err_resolve<F>(job.stream, job.scalars_dev, job.fmt, p.nd, job.density_dev, job.word_prefix, job.skip, job.n_bases,
+                                (const Affine<F> *)job.resolve_bases.ptr, job.resolve_bases.stride, lo_ref, job.err_dev) != BH_OK ||
+          hipMemcpyAsync(&ef, job.err_dev, sizeof ef, hipMemcpyDeviceToHost, job.stream) != hipSuccess ||
           hipStreamSynchronize(job.stream) != hipSuccess)
         rc = BH_ERR_HIP;
       else {

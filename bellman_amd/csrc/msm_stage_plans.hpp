@@ -1,8 +1,11 @@
-// Host plans of stages 4 and 5 of a multiexp: the merge parameters and queue bounds (merge_plan), and the reduction's buffer
-// sizes and its whole launch schedule (reduce_plan) - pure functions of a plan, a bundle's geometry and the chip's CU count.
+// Host plans of stages 4 and 5 of a multiexp: whether a job takes the one-launch small path and that launch
+// (small_fill_plan), the merge parameters and queue bounds (merge_plan), the reduction's buffer sizes and its whole launch
+// schedule (reduce_plan), and the top window of the error-resolution pass (err_resolve_lo_ref) - pure functions of a plan, a
+// bundle's geometry and the chip's CU count.
 // Plain C++: no HIP call, no device function, no field or point type.  The kernels these plans are for live in
-// msm_merge.cuh and msm_sums.cuh; msm_merge.cuh derives a bundle's BundleGeom from its worker types (bundle_geom<FR>()), and
-// msm_ec.cuh launches what the plans say.  Tests read the plans through bh_test_merge_plan / bh_test_reduce_plan.
+// msm_accumulate.cuh, msm_merge.cuh and msm_sums.cuh; msm_merge.cuh derives a bundle's BundleGeom from its worker types
+// (bundle_geom<FR>()), and msm_ec.cuh launches what the plans say.  Tests read the plans through bh_test_small_fill_plan /
+// bh_test_merge_plan / bh_test_reduce_plan / bh_test_err_resolve_lo_ref.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -24,6 +27,58 @@ struct BundleGeom {
   u32 long_piece;                // partials per piece of a big run, on the worker that folds the pieces
   bool g2;
 };
+
+// ============================================================================================
+// stages 1 - 4 in one launch: which multiexps take msm_small_fill_kernel (msm_accumulate.cuh), and its launch
+// ============================================================================================
+constexpr u32 SMALL_MAX_SCALARS = 2048, SMALL_MAX_ENTRIES = 20480 + 1024, SMALL_MAX_PER_BUCKET = 16, SMALL_LIST_CAP = 24;
+constexpr u32 SMALL_THREADS = 256, SMALL_LANES_PER_BUCKET = 4;
+// dynamic LDS of the kernel: base indices, digit table, per-bucket entry lists of the workgroup's buckets
+inline size_t small_fill_lds_bytes(u32 nd, u32 n_entries) {
+  return (size_t)nd * 4 + (((size_t)n_entries * 2 + 3) & ~size_t(3)) + SMALL_THREADS * 4 + (size_t)SMALL_THREADS * SMALL_LIST_CAP * 2;
+}
+struct SmallFillPlan {
+  bool fused;                  // the job takes the one-launch path; the rest describes that launch
+  u32 workgroups, threads;
+  size_t lds_bytes;
+  u32 buckets_per_workgroup;   // workers_per_workgroup / SMALL_LANES_PER_BUCKET
+  u32 top_bits;                // bits of a scalar that reach the table's top row
+  u64 sliver_load;             // entries the top row alone is expected to send to each of its 2^top_bits buckets
+};
+// small multiexps over a window table: one launch for everything up to the filled buckets (msm_small_fill_kernel)
+// ... and only when no bucket is EXPECTED to outgrow its list: rows whose top one is a sliver of t = 255 - (Wd - 1) c bits (10-bit
+// rows: t = 5, 11 bits: 2, 12 bits: 3) send the top digit of every scalar to 2^t buckets, nd / 2^t entries each - such buckets fall
+// back to a scan of the whole digit table per worker (an explicit 11-bit table over 2^9 points took 8.9 ms in this kernel against
+// 0.7 through the sort: profiles/r6_call54_tiny_g2_bits.txt); the default 13-bit tables have t = 8
+// What each term keeps the kernel inside: nd <= SMALL_MAX_SCALARS - its density prefix walks at most 32 words per scalar;
+// n <= SMALL_MAX_ENTRIES and the LDS bound - base indices, digits and lists fit a workgroup's 64 KiB, and an entry id its list's
+// 16 bits; c <= 15 - a digit, up to 2^(c-1) in magnitude, fits a `short`; one bucket set of one vector - the kernel has no other.
+// small_path: MsmSources::small_path; many: the job holds several scalar vectors; flags: MsmOpts::flags;
+// workers_per_workgroup: workers_per_block<F>(SMALL_THREADS, tree_per_wave<F>()) of the bundle F that accumulates
+inline SmallFillPlan small_fill_plan(const MsmPlan &p, bool small_path, bool many, u32 flags, u32 workers_per_workgroup) {
+  SmallFillPlan s;
+  s.top_bits = 255u - (p.Wd - 1) * p.c;
+  s.sliver_load = s.top_bits >= 31 ? 0 : ((u64)p.nd >> s.top_bits);
+  s.lds_bytes = small_fill_lds_bytes(p.nd, p.n);
+  s.fused = small_path && plan_fused_sort(p) && !many && p.nd <= SMALL_MAX_SCALARS && p.n <= SMALL_MAX_ENTRIES &&
+            (u64)p.n <= (u64)SMALL_MAX_PER_BUCKET * p.nb && p.c <= 15 && s.lds_bytes <= 64 * 1024 &&
+            s.sliver_load + (u64)p.n / p.nb <= SMALL_LIST_CAP / 2 && !(flags & BH_MSM_NO_SMALL_PATH);
+  s.threads = SMALL_THREADS;
+  s.buckets_per_workgroup = workers_per_workgroup / SMALL_LANES_PER_BUCKET;
+  s.workgroups = s.buckets_per_workgroup ? (p.nb + s.buckets_per_workgroup - 1) / s.buckets_per_workgroup : 0;
+  return s;
+}
+
+// ============================================================================================
+// the error-resolution pass (msm_err_resolve_kernel): where the reference's top window starts
+// ============================================================================================
+// The reference sizes its windows by the number of exponents, c = 3 below 32 of them and ceil(ln n) from there on
+// (multiexp.rs:318-322), and reports the first failure of its top window: bits [lo_ref, 256) of a scalar
+inline u32 err_resolve_lo_ref(u64 nref) {
+  const double c_ln = (nref < 32) ? 3.0 : std::ceil(std::log((double)nref));
+  const u32 c_ref = (u32)c_ln, w_ref = (255 + c_ref - 1) / c_ref;
+  return c_ref * (w_ref - 1);
+}
 
 // ============================================================================================
 // stage 4: the merge parameters of a plan and the queue bounds

@@ -292,6 +292,44 @@ int bh_test_sort_stage_dev(bh_ctx *ctx, int kind, unsigned c, const void *scalar
                            int *sorted_is_b_out, uint32_t *zstart_out, uint32_t *counts_out, uint32_t *word_prefix_out, void *err_out,
                            uint32_t guards_out8[8]);
 
+/* The one-launch small path and the error-resolution pass on their own (csrc/test_small_hooks.hip; tests/test_gpu_small_fill.py,
+ * tests/test_small_fill_model_cpu.py, tests/models/small_fill_model.py): msm_small_fill_kernel - signed digits, density rank,
+ * EOF rule, per-bucket entry lists and their table-scan fallback, four workers per bucket - which replaces stages 1 - 4 of a
+ * small multiexp over a window table, launched by the function msm_enqueue launches it with (launch_small_fill of
+ * csrc/msm_ec.cuh) as the shipped plans say (make_table_plan; small_fill_plan of csrc/msm_stage_plans.hpp, which holds the gate
+ * that chooses the path); and msm_err_resolve_kernel, launched as msm_finish launches it (err_resolve_lo_ref, launch_err_resolve).
+ *   form   0 FpOps (G1)   1 Fp2K3Ops (G2, lane triples)   2 Fp2PairOps (G2, lane pairs)   3 Fp2Ops (G2, one lane)
+ * A table: ceil(256 / c) rows of row_records affine records at the dense stride (96 / 192 bytes), row w at w row_records.
+ * Refused everywhere: a form that does not exist, nd = 0, c outside [2, 24], Wd nd >= 2^32, Wd row_records >= 2^31 - the
+ * conditions of msm_enqueue and msm_pick_sources.
+ * bh_test_small_fill_plan (host only): the plans of nd scalars over such a table with the option flags `flags` (bh_msm_opts):
+ * plan_out20 = [fused, workgroups, threads, dynamic LDS bytes, buckets per workgroup, top_bits, sliver_load, Wd, entries (Wd nd),
+ * nb (2^(c-1) buckets), SMALL_MAX_SCALARS, SMALL_MAX_ENTRIES, SMALL_MAX_PER_BUCKET, SMALL_LIST_CAP, SMALL_LANES_PER_BUCKET, XYZZ
+ * record bytes, affine record bytes, guard bytes, the sentinel byte, sizeof ErrFlags].
+ * bh_test_small_fill_dev: launch_small_fill once, on the context's stream, over nd scalars (32 bytes each; Montgomery ones
+ * must be below q), an optional density bitmap of ceil(nd / 64) words, skip, n_bases, and table = Wd row_records affine
+ * records.  Buffers as msm_enqueue carves them, without its rounding to 256 bytes: pts_out nb XYZZ records and err_out one
+ * ErrFlags, both zeroed as in production; word_prefix_out ceil(nd / 64) + 1 words, filled with the sentinel byte, passed to the
+ * kernel - and wanted here - exactly when density_words is given.  All three come back raw.  guards_out6 = [pts, word_prefix,
+ * ErrFlags, scalars, density, table]: 1 = the guard bytes behind the buffer came back untouched.  Refused before any launch: a
+ * shape the shipped plan does not fuse, n_bases > row_records (a live scalar's base cursor is below n_bases: inside a row),
+ * row_records > 2^16, skip >= 2^31, a scalar format that does not exist, a Montgomery scalar >= q.
+ * bh_test_err_resolve_lo_ref (host only): err_resolve_lo_ref(nref), the first bit of the reference's top window over nref
+ * exponents.
+ * bh_test_err_resolve_dev: launch_err_resolve once over nd <= 2^20 scalars, an optional density bitmap WITH its word prefix
+ * (ceil(nd / 64) + 1 words, the caller's), skip, n_bases, bases = n_records affine records of group 1 / 2 base_stride bytes apart
+ * (n_bases <= n_records <= 2^20: what lies behind n_bases is there to be left alone; strides 96 or 128 in G1, 192 in G2, any other
+ * is refused) and the top window of ref_n exponents (0: of nd, as msm_finish takes it).  err_inout: one ErrFlags, uploaded as the
+ * caller set it and returned raw.  guards_out5 = [scalars, density, word_prefix, bases, ErrFlags]. */
+int bh_test_small_fill_plan(int form, size_t nd, unsigned c, size_t row_records, uint32_t flags, uint64_t plan_out20[20]);
+int bh_test_small_fill_dev(bh_ctx *ctx, int form, unsigned c, const void *scalars, int fmt, size_t nd, const uint64_t *density_words,
+                           size_t skip, size_t n_bases, const void *table, size_t row_records, void *pts_out,
+                           uint32_t *word_prefix_out, void *err_out, uint32_t guards_out6[6]);
+uint32_t bh_test_err_resolve_lo_ref(uint64_t nref);
+int bh_test_err_resolve_dev(bh_ctx *ctx, int group, const void *scalars, int fmt, size_t nd, const uint64_t *density_words,
+                            const uint32_t *word_prefix, size_t skip, size_t n_bases, const void *bases, size_t n_records,
+                            unsigned base_stride, uint64_t ref_n, void *err_inout, uint32_t guards_out5[5]);
+
 /* The kernels of the Groth16 verifier on their own (csrc/test_pairing_hooks.hip, which compiles csrc/pairing_kernels.cuh a
  * second time into the test library; tests/test_gpu_pairing_stages.py, tests/models/pairing_stage_model.py).  Each call runs
  * one stage once on the context's stream through the shipped launch function (launch_g2_lines, launch_miller, launch_fold,
